@@ -1,6 +1,6 @@
 """bench.py — masked-LM training throughput of the OmniBioTE encoder hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]          (N > 1: launched by torchrun, one rank per GPU)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]          (N > 1: launched by torchrun, one rank per GPU)
 
 A *step* is one optimizer step of the reference's training loop (training/train_encoder.py:241-323) on this rank's
 128 rows of 1024 synthetic tokens: 16 accumulated micro-batches of mini_batch_size 8 (k of them per forward/backward pass,
@@ -94,7 +94,12 @@ def parse():
                         "(omnibiote_amd/comm.py); either way per-bucket device events are recorded and reported in config.collectives")
     p.add_argument("--plan_cache", default="", help="JSON file of tuned GEMM plans: loaded if present (no tuning launches), else tuned and written")
     p.add_argument("--shapes_out", default="", help="write the per-shape launch table (from the profiler step) to this file")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", dest="dump_outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last of them computed to DIR/<name>.npy (rank 0): see dump_outputs")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1: ms_per_step is the timed time over that many steps")
+    return a
 
 
 def harness_args(cfg, a, world):
@@ -417,6 +422,44 @@ class Watchdog:
         return False
 
 
+DUMP_SAMPLE = 1 << 15          # elements kept of each parameter and gradient larger than this
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, out: dict, model) -> None:
+    """Write what one train step hands its caller as .npy files under ``path``, so that two builds can be compared output
+    for output: ``loss`` and ``tokens`` (float64 scalars, the step's return value), and the parameters and gradients it
+    leaves on the model as ``param.<name>`` / ``grad.<name>`` (float32).  A tensor larger than DUMP_SAMPLE elements is
+    represented by a fixed sample of its flattened elements: DUMP_SAMPLE sorted positions drawn by a generator seeded with
+    the CRC-32 of the parameter's name, the same in every run.  ``grad_norm`` (float64) holds every gradient's full L2 norm,
+    in the order of model.named_parameters().  Tokens, MLM masks and initial weights are seeded, but the GEMM plans and the
+    micro-batches per pass are chosen by timing at start-up, so two runs agree to bf16 rounding, not bit for bit."""
+    import zlib
+    files = {"loss": np.asarray(float(out["loss"].item()), dtype=np.float64),
+             "tokens": np.asarray(float(out["tokens"].item()), dtype=np.float64)}
+    norms = []
+    for name, p in model.named_parameters():
+        n = p.numel()
+        idx = None
+        if n > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, DUMP_SAMPLE, replace=False))
+            idx = torch.from_numpy(pos).to(p.device)
+        for kind, t in (("param", p), ("grad", p.grad)):
+            if t is None:
+                raise SystemExit(f"bench.py: --dump-outputs: {name} has no gradient after the step")
+            flat = t.detach().reshape(-1)
+            files[f"{kind}.{name}"] = (flat if idx is None else flat[idx]).float().cpu().numpy()
+        norms.append(torch.linalg.vector_norm(p.grad.detach(), dtype=torch.float64).item())
+    files["grad_norm"] = np.asarray(norms, dtype=np.float64)
+    total = sum(v.nbytes for v in files.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, over the {DUMP_MAX_BYTES} limit")
+    os.makedirs(path, exist_ok=True)
+    for k, v in files.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    log(f"outputs of the last timed step: {len(files)} arrays, {total / 2 ** 20:.1f} MB in {path}")
+
+
 def self_launch(n_gpus: int) -> int:
     """`python bench.py --gpus N` outside torchrun: start the N ranks as a CHILD process group (one rank per GPU,
     `python -m torch.distributed.run`, rendezvous on 127.0.0.1) before this process has made any HIP call, pass the
@@ -580,10 +623,13 @@ def main():
         sync()
         t0 = time.perf_counter()
         for i in range(a.steps):
-            losses.append(step(batches[(a.warmup + i) % len(batches)])["loss"])
+            last = step(batches[(a.warmup + i) % len(batches)])
+            losses.append(last["loss"])
         sync()
         elapsed = time.perf_counter() - t0
     _lib.check_device_status("timed steps")   # a kernel that found its own results invalid (device status word): a failed run, not a number
+    if a.dump_outputs and rank == 0:   # before the profiled step and the variants train the model further
+        dump_outputs(a.dump_outputs, last, m)
     exchange = None
     th = getattr(model, "_obte_timed_hook", None)
     if th is not None:   # per-bucket device events of the gradient exchange; the LAST timed step's buckets are reported

@@ -11,6 +11,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -37,7 +38,8 @@ def test_bench_two_ranks_prints_one_line(tmp_path):
     rccl = torch.cuda.device_count() >= 2
     # the tiny config (BASELINE configs[0]: 2L / 128d / 2h, ctx 128) keeps the gloo rehearsal short — 34 MB of gradients cross the
     # host per step instead of 470 MB; the control flow under test does not depend on the model size
-    rc, so, se = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--rows_per_rank", "24", "--no_cpu_baseline", "--config", "tiny"],
+    rc, so, se = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--rows_per_rank", "24", "--no_cpu_baseline", "--config", "tiny",
+                             "--dump-outputs", str(tmp_path / "dump")],
                             {} if rccl else {"OBTE_BENCH_REHEARSE": "1"}, tmp_path)
     assert rc == 0, se[-4000:]
     lines = [l for l in so.splitlines() if l.startswith("{")]
@@ -50,6 +52,9 @@ def test_bench_two_ranks_prints_one_line(tmp_path):
     assert (col["rccl_version"] is not None) == rccl and ("RCCL" in col["backend"]) == rccl
     assert line["config"]["global_batch_rows"] == 48 and line["config"]["parallelism"] == "dp2"
     assert 0.0 < line["final_loss"] < 20.0
+    assert abs(float(np.load(tmp_path / "dump" / "loss.npy")) - line["final_loss"]) <= 1e-4   # the last timed step's outputs
+    gn = np.load(tmp_path / "dump" / "grad_norm.npy")
+    assert len(gn) >= 15 and np.isfinite(gn).all() and (gn > 0).any()
     assert "mfma_fraction_whole_step" not in line and line["mfma_fraction_whole_step_executed"] >= 0 and line["flops_per_token_executed"] > 0
     assert len(line["gemm_plans"]["table"]) >= 15 and len(line["gemm_plans"]["sha16"]) == 16
     assert line["roofline"]["bound"] == "mfma" and line["roofline"]["frac"] > 0

@@ -380,3 +380,34 @@ def test_block_activation_buffer_leaves_out_the_dropout_keep_bits_without_dropou
         assert lib.obte_block_act_bytes_p(B, T, C, H, 0.1) == full
         lean = lib.obte_block_act_bytes_p(B, T, C, H, 0.0)
         assert full - lean == (bits + 255) // 256 * 256 and lean > 0
+
+
+def test_bench_output_dump_is_a_fixed_float_sample(tmp_path):
+    """bench.py --dump-outputs: the same model state gives byte-identical float32 / float64 files, small tensors whole and
+    large ones at fixed sample positions, without drawing from the global NumPy stream the benchmark's MLM masks come from."""
+    import bench
+    torch.manual_seed(0)
+    c = OmniBioTAConfig()
+    c.block_size, c.vocab_size, c.n_layer, c.n_head, c.n_embd, c.dropout, c.flash = 128, 4096, 2, 2, 128, 0.0, True
+    m = OmniBioTA(c).to(torch.bfloat16)
+    for p in m.parameters():
+        p.grad = torch.randn_like(p)
+    params = dict(m.named_parameters())
+    before = np.random.get_state()[1].copy()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"loss": torch.tensor(3.25), "tokens": torch.tensor(1024)}, m)
+    assert np.array_equal(np.random.get_state()[1], before)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and len(names) == 2 * len(params) + 3
+    for f in names:
+        x = np.load(tmp_path / "a" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, np.load(tmp_path / "b" / f)), f
+    assert np.load(tmp_path / "a" / "loss.npy") == 3.25 and np.load(tmp_path / "a" / "tokens.npy") == 1024
+    ln = params["transformer.h.0.ln_1.weight"]
+    assert np.array_equal(np.load(tmp_path / "a" / "grad.transformer.h.0.ln_1.weight.npy"), ln.grad.float().numpy())
+    wte = params["transformer.wte.weight"]
+    assert wte.numel() > bench.DUMP_SAMPLE
+    got = np.load(tmp_path / "a" / "param.transformer.wte.weight.npy")
+    assert got.shape == (bench.DUMP_SAMPLE,) and np.isin(got, wte.detach().float().numpy()).all()
+    norms = [torch.linalg.vector_norm(p.grad, dtype=torch.float64).item() for p in params.values()]
+    assert np.allclose(np.load(tmp_path / "a" / "grad_norm.npy"), norms, rtol=1e-12)

@@ -138,7 +138,11 @@ def test_rope_and_gelu_helpers(golden_dir):
     np.testing.assert_array_equal(R.apply_rope(q.bfloat16(), tb).float().numpy(), g["oq_bf16"])
     np.testing.assert_array_equal(R.apply_rope(k.bfloat16(), tb).float().numpy(), g["ok_bf16"])
     x = torch.from_numpy(g["gelu_x"])
-    np.testing.assert_allclose(R.gelu_erf(x).numpy(), g["gelu_y"], atol=1e-7)
+    # float32 erf differs in its last bit between CPUs' math libraries (erf(-5.5 / 1.41421) is -1 on some, one ulp above on
+    # others); near erf = -1 that ulp (2^-24) reaches the output times |x| / 2.  The bound still tells the reference's
+    # truncated 1.41421 from sqrt(2), and from exact or tanh GELU, by a factor of 5 or more.
+    d = np.abs(R.gelu_erf(x).numpy() - g["gelu_y"])
+    assert (d <= 1e-7 + np.abs(g["gelu_x"]) * 2.0 ** -25).all(), d.max()
     np.testing.assert_array_equal(R.gelu_erf(x.bfloat16()).float().numpy(), g["gelu_y_bf16"])
 
 
