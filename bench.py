@@ -1,6 +1,6 @@
 """bench.py — masked-LM training throughput of the OmniBioTE encoder hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]          (N > 1: launched by torchrun, one rank per GPU)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]          (N > 1: launched by torchrun, one rank per GPU)
 
 A *step* is one optimizer step of the reference's training loop (training/train_encoder.py:241-323) on this rank's
 128 rows of 1024 synthetic tokens: 16 accumulated micro-batches of mini_batch_size 8 (k of them per forward/backward pass,
@@ -10,15 +10,17 @@ MLM-masked positions only (``--readout masked``, the default since round 3: the 
 zero, train_encoder.py:304, so loss and gradients are the reference's; the last block's MLP half, its attention's queries with
 the attention projection (round 5; keys and values of every position) and ln_f run on those positions too — ``model.forward(rows=...)``; ``--readout dense`` / ``dense_full`` compute every position's logits as
 rounds 1-2 did and are reported as variants), backward, global-norm clip, MuAdamW-grouped AdamW, LinearLR — BASELINE.json
-configs[1] at N=1 and configs[2] (batch_size 1024 over 8 ranks) at N=8.  At N=1 the line also carries ``other_configs``:
-driver-timed steps of BASELINE configs 4 (small, ctx 4096) and 5 (large 24L/2048d/16h, its single-GPU leg).  Per-rank work is fixed as N grows (weak scaling).  Inputs are resident in
-HBM before the timed region.  Rank 0 prints ONE JSON line.
+configs[1] at N=1 and configs[2] (batch_size 1024 over 8 ranks) at N=8.  Per-rank work is fixed as N grows (weak scaling).  Inputs are
+resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
-Extra objects: ``roofline`` for the dominant kernel family (bf16 MFMA GEMM; per-launch durations from HIP events
-recorded on the launch stream by the library's opt-in profiler during one extra step right after the timed region:
+A plain run does only what the headline needs: set-up (model, GEMM plans, micro-batches per pass), the warm-up and timed steps,
+--dump-outputs if given, the line.  ``--full`` adds everything measured after the timed steps, each part still switched off by its
+``--no_*`` option: ``variants`` (the same step in other regimes, 10 steps each); at N=1 ``other_configs`` (driver-timed steps of
+BASELINE configs 4 (small, ctx 4096) and 5 (large 24L/2048d/16h, its single-GPU leg)); ``roofline`` for the dominant kernel
+family (bf16 MFMA GEMM; per-launch durations from HIP events recorded on the launch stream by the library's opt-in profiler during one extra step right after the timed region:
 bracketing every launch of the timed steps themselves with events was measured to cost 6 % of ``value`` — the events keep
-the tail of one kernel from overlapping the head of the next — so the timed region runs un-instrumented), and, at N=1, ``cpu_baseline`` — the CPU oracle (oracle/omnibiote_ref.py, the reference's
-arithmetic restated in plain torch) timed on this host on a bounded sample of the same workload.
+the tail of one kernel from overlapping the head of the next — so the timed region runs un-instrumented); and, at N=1, ``cpu_baseline`` — the CPU oracle (oracle/omnibiote_ref.py, the reference's
+arithmetic restated in plain torch) timed on this host on a bounded sample of the same workload — and ``eager_gpu_baseline``.
 """
 from __future__ import annotations
 
@@ -55,7 +57,7 @@ CONFIGS = {
 }
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
@@ -71,12 +73,15 @@ def parse():
                         "dense [M,V] d(logits) and full-size backward products (the reference's literal graph)")
     p.add_argument("--masked_lm_head", action="store_true", help="alias of --readout masked")
     p.add_argument("--dropout", type=float, default=0.0, help="0.0 = the parity regime (default); 0.1 = the reference's default")
-    p.add_argument("--no_cpu_baseline", action="store_true")
-    p.add_argument("--no_roofline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure the profiled step (roofline), the variants, the other configs and the CPU / "
+                        "eager-GPU baselines (each can still be skipped by its --no_* option); a plain run prints the headline alone")
+    p.add_argument("--no_cpu_baseline", action="store_true", help="--full: skip cpu_baseline and eager_gpu_baseline")
+    p.add_argument("--no_roofline", action="store_true", help="--full: skip the profiled step (roofline)")
     p.add_argument("--dense_mask", action="store_true",
                    help="pass the reference's dense additive (B,H,T,T) mask (expand view) instead of key ranges")
-    p.add_argument("--no_other_configs", action="store_true", help="skip the driver-timed steps of BASELINE configs 4 (small4k) and 5 (large)")
-    p.add_argument("--no_variants", action="store_true", help="skip the extra measurements (masked-rows readout, dropout 0.1, dense-mask calling convention)")
+    p.add_argument("--no_other_configs", action="store_true", help="--full: skip the driver-timed steps of BASELINE configs 4 (small4k) and 5 (large)")
+    p.add_argument("--no_variants", action="store_true", help="--full: skip the extra measurements (masked-rows readout, dropout 0.1, dense-mask calling convention)")
     p.add_argument("--pipeline_streams", type=int, default=2, choices=[1, 2, 3],
                    help="2: forward of micro-batch j+1 beside the backward of micro-batch j on a second HIP stream (bitwise the same results)")
     p.add_argument("--full_last_block", action="store_true",
@@ -93,12 +98,16 @@ def parse():
                    help="N > 1: DDP's bucketed all-reduce (the reference's), or the direct reduce-scatter + all-gather over all xGMI links "
                         "(omnibiote_amd/comm.py); either way per-bucket device events are recorded and reported in config.collectives")
     p.add_argument("--plan_cache", default="", help="JSON file of tuned GEMM plans: loaded if present (no tuning launches), else tuned and written")
-    p.add_argument("--shapes_out", default="", help="write the per-shape launch table (from the profiler step) to this file")
+    p.add_argument("--shapes_out", default="", help="--full: write the per-shape launch table (from the profiled step) to this file")
     p.add_argument("--dump-outputs", dest="dump_outputs", default="", metavar="DIR",
                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (rank 0): see dump_outputs")
-    a = p.parse_args()
+    a = p.parse_args(argv)
     if a.steps < 1:
         p.error("--steps must be at least 1: ms_per_step is the timed time over that many steps")
+    if a.shapes_out and not a.full:
+        p.error("--shapes_out needs --full: the table comes from the profiled step")
+    if not a.full:   # a plain run: nothing after the timed steps but --dump-outputs and the line
+        a.no_roofline = a.no_variants = a.no_other_configs = a.no_cpu_baseline = True
     return a
 
 

@@ -1,8 +1,8 @@
 """bench.py's N > 1 control flow under test on the GPU box: `python bench.py --gpus 2` starts its two
 ranks as a child `torch.distributed.run` (a fresh process tree — never a re-exec of a process that touched the GPU), every
 rank goes through process-group set-up, the first-contact all-reduce, plan broadcast, DDP wrap, the timed steps (no_sync +
-bucketed all-reduce on the last micro-batch, two-stream pipeline), the every-rank profiled step, the per-rank variants and the
-final barrier, and rank 0 prints ONE JSON line.  On a one-GPU box both ranks share cuda:0 over gloo
+bucketed all-reduce on the last micro-batch, two-stream pipeline), with --full the every-rank profiled step and the per-rank
+variants, and the final barrier, and rank 0 prints ONE JSON line.  On a one-GPU box both ranks share cuda:0 over gloo
 (OBTE_BENCH_REHEARSE=1: RCCL refuses two ranks on one device); with two or more GPUs the same test runs over RCCL.
 The numbers mean nothing here — the flow, the line's fields and the exit codes are what is checked.
 Reference counterpart: training/train_encoder.py:105-118,185,284-311 under torchrun."""
@@ -38,7 +38,7 @@ def test_bench_two_ranks_prints_one_line(tmp_path):
     rccl = torch.cuda.device_count() >= 2
     # the tiny config (BASELINE configs[0]: 2L / 128d / 2h, ctx 128) keeps the gloo rehearsal short — 34 MB of gradients cross the
     # host per step instead of 470 MB; the control flow under test does not depend on the model size
-    rc, so, se = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--rows_per_rank", "24", "--no_cpu_baseline", "--config", "tiny",
+    rc, so, se = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--rows_per_rank", "24", "--full", "--no_cpu_baseline", "--config", "tiny",
                              "--dump-outputs", str(tmp_path / "dump")],
                             {} if rccl else {"OBTE_BENCH_REHEARSE": "1"}, tmp_path)
     assert rc == 0, se[-4000:]
@@ -61,6 +61,24 @@ def test_bench_two_ranks_prints_one_line(tmp_path):
     assert set(line["variants"]) >= {"dense_logits_forward", "masked_readout_full_last_block", "dense_dlogits_full_backward", "dropout_0.1", "dense_mask_calling_convention"}
     assert ("REHEARSAL" in line["data"]) == (not rccl)
     assert "first all-reduce ok" in se
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_prints_the_headline_alone(tmp_path):
+    """Without --full one GPU runs set-up, warm-up and the timed steps, writes --dump-outputs and prints the line: no profiled
+    step, variants, other configs or baselines."""
+    rc, so, se = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--rows_per_rank", "24", "--config", "tiny",
+                             "--dump-outputs", str(tmp_path / "dump")], {}, tmp_path, timeout=240)
+    assert rc == 0, se[-4000:]
+    lines = [l for l in so.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, so[-2000:]
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["unit"] == "tokens/s" and line["higher_is_better"]
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["dtype"] == "bf16"
+    assert abs(line["value"] - 24 * 128 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]
+    assert line["roofline"] is None
+    assert not set(line) & {"variants", "other_configs", "cpu_baseline", "eager_gpu_baseline"}
+    assert abs(float(np.load(tmp_path / "dump" / "loss.npy")) - line["final_loss"]) <= 1e-4
 
 
 @pytest.mark.timeout(300)

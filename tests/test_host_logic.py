@@ -411,3 +411,19 @@ def test_bench_output_dump_is_a_fixed_float_sample(tmp_path):
     assert got.shape == (bench.DUMP_SAMPLE,) and np.isin(got, wte.detach().float().numpy()).all()
     norms = [torch.linalg.vector_norm(p.grad, dtype=torch.float64).item() for p in params.values()]
     assert np.allclose(np.load(tmp_path / "a" / "grad_norm.npy"), norms, rtol=1e-12)
+
+
+def test_bench_plain_run_skips_everything_after_the_timed_steps():
+    """bench.py without --full measures the headline alone; --full turns the profiled step, the variants, the other configs and
+    the baselines back on, each still switched off by its --no_* option."""
+    import bench
+    extras = ("no_roofline", "no_variants", "no_other_configs", "no_cpu_baseline")
+    plain = bench.parse(["--steps", "3", "--warmup", "1"])
+    assert not plain.full and all(getattr(plain, k) for k in extras)
+    full = bench.parse(["--full"])
+    assert full.full and not any(getattr(full, k) for k in extras)
+    some = bench.parse(["--full", "--no_cpu_baseline", "--no_other_configs"])
+    assert some.no_cpu_baseline and some.no_other_configs and not some.no_roofline and not some.no_variants
+    with pytest.raises(SystemExit):
+        bench.parse(["--shapes_out", "shapes.txt"])   # the table comes from the profiled step, which only --full runs
+    assert bench.parse(["--full", "--shapes_out", "shapes.txt"]).shapes_out == "shapes.txt"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Copy the summaries of one round's profile runs from gpurun_out/ (scratch) into profiles/ (tracked):
 #   tools/collect_profiles.sh r03 gpurun_out/prof_r3z gpurun_out/pmc_r3z gpurun_out/prof_cfg_r3z [final_line.json]
-# (outputs of tools/profile_round.sh, tools/profile_pmc_bench.sh, tools/profile_configs.sh and a plain `python bench.py`)
+# (outputs of tools/profile_round.sh, tools/profile_pmc_bench.sh, tools/profile_configs.sh and `python bench.py --full`)
 set -eu
 R=$1; PR=$2; PMC=$3; CFG=$4; LINE=${5:-}
 cd "$(dirname "$0")/.."
