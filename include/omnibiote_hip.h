@@ -58,8 +58,9 @@ int obte_fault_inject(int what);
  * While enabled, every obte_gemm_bf16 / obte_attn_fwd / obte_attn_bwd call is bracketed by two hipEvents on the
  * caller's stream.  obte_profile_collect synchronises those events and returns up to cap records:
  * ms[i] = elapsed milliseconds, dims[3*i..] = (M,N,K) for a GEMM or (B*H, T, head_dim) for attention,
- * kind[i] = a_kmajor*8 + b_kmajor*4 + epilogue (+ 32.. for a grouped launch) + 1000 * kernel structure (1 gemm_bf16_kernel,
- * 2 gemm_v2_kernel, 3 gemm_v3_kernel) for a GEMM, 100 = attention forward, 101 = attention backward; the HBM-bound
+ * kind[i] = a_kmajor*8 + b_kmajor*4 + epilogue + 1000 * kernel structure (1 gemm_bf16_kernel, 2 gemm_v2_kernel,
+ * 3 gemm_v3_kernel, 4 gemm_v4_kernel, 7 gemm_v7_kernel) for a GEMM, its split-K reduce inside the same record; 32 + 1 (the first
+ * and last problems differ in layout) + 2 (accumulate) for a grouped launch; 100 = attention forward, 101 = attention backward; the HBM-bound
  * kernels record (rows, cols, flag): 110 LayerNorm forward, 111 LayerNorm backward (flag = residual gradient added),
  * 112 masked CE over (n_rows, vocab), 113 AdamW over (elements, 1, 1).
  * Returns the number of records written (records are cleared). */
@@ -150,13 +151,15 @@ int obte_gemm_bf16_ws(const obte_gemm_args* g, void* workspace, int64_t workspac
  * across tiles — whole tiles, at least one per CU, no split-K, the x W^T and dy W layouts; numbers 5 and 6 were structures
  * that lost every comparison and were removed); which is fastest depends on the shape
  * (tile quantisation against 256 CUs, K length, where the operands are served from).  A host-side tuner times the candidates once
- * per (layout, epilogue, M, N, K) and records the winner here; unknown shapes fall back to a built-in heuristic, and a plan a shape
- * cannot run (a borrowed near-match, edge tiles) falls back the same way.
- * obte_gemm_workspace_bytes_max: a workspace size that admits any recordable plan. */
+ * per (layout, epilogue, M, N, K) and records the winner here; it is also the only way to force a structure.  obte_gemm_plan_set
+ * refuses a plan whose structure has no kernel for that tile width, layout, epilogue and split.  A call uses the plan of its shape
+ * (ADD, ROPE_QK: else the NONE plan; ADD_DROPOUT: else the ADD plan; else one whose one differing dimension is within 20 %, its
+ * split count trimmed to one round of 256 CUs), or a built-in heuristic on structure 2.  A split-K plan without a workspace that
+ * holds it runs the heuristic without split; where a structure cannot run the plan as given it falls back: 7 (edge tiles, fewer
+ * tiles than CUs, K < 256, a large output) to 3 at one split; 3 and 4 (fewer than two K-tiles per split) to 2 at the same width. */
 int obte_gemm_plan_set(int a_kmajor, int b_kmajor, int epilogue, int64_t M, int64_t N, int64_t K, int variant, int bn,
                        int splits);
 int obte_gemm_plan_clear(void);
-int64_t obte_gemm_workspace_bytes_max(int64_t M, int64_t N, int64_t K);
 
 /* Grouped launch: `count` (1..OBTE_GROUP_MAX) independent GEMMs in a single grid of 256x256 tiles, each tile running its
  * full K (>= 128) — no split-K workspace, no reduce launches.  The problems may MIX layouts (a_kmajor / b_kmajor per

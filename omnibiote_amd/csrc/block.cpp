@@ -372,7 +372,7 @@ extern "C" int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, 
         g.a_kmajor = 1; g.b_kmajor = 0; g.epilogue = OBTE_EPI_NONE; g.alpha = 1.0f;
         const int rcd = obte_gemm_rowdot_bf16(&g, yat, delta, d->T, hs, s);
         if (rcd == OBTE_OK) delta_ready = true;
-        else if (rcd == 1) TRY(obte_gemm_bf16(&g, s));
+        else if (rcd == OBTE_ROWDOT_NOT_TAKEN) TRY(obte_gemm_bf16(&g, s));
         else return rcd;
     }
     if (!grouped && !rows_p) TRY(gemm(dx1_proj, yat, dproj_w, C, C, M, C, C, 0, 0, wepi, accumulate_matrices ? dproj_w : nullptr, nullptr, s, gws, W.gemmws_bytes));                       // dW_proj = dx1^T y

@@ -1,4 +1,4 @@
-// bf16 GEMM, first structure (kept selectable with OBTE_GEMM=v1 for A/B runs; the default is gemm_bf16_v2.hip).
+// bf16 GEMM, first structure (kept selectable through the plan table, structure 1, for A/B runs).
 // bf16 GEMM on CDNA4 MFMA (v_mfma_f32_16x16x32_bf16), fp32 accumulate, bf16 output with fused epilogues.
 //
 // Replaces the nn.Linear calls of the reference's block and readout (training/model.py:102,151,163,166,253)
@@ -17,7 +17,7 @@
 // consecutive output columns; the tile is then staged through LDS as bf16 and written with 16-B stores in
 // full 128-B row segments, where the epilogue (GELU, residual add, GELU backward) is applied.
 // Workgroup ids are remapped so that each XCD (own L2) works on a compact 8 x n group of tiles.
-#include "common.h"
+#include "gemm_common.h"
 
 namespace obte_gemm_v1 {
 
@@ -313,69 +313,23 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmParams p) {
     }
 }
 
-template <bool AK, bool BK, int EPI>
-int launch(const GemmParams& p, hipStream_t st) {
-    static bool attr_set = false;  // idempotent; a race only repeats the call
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<AK, BK, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_bf16_kernel<AK, BK, EPI>), dim3(p.tiles_m * p.tiles_n), dim3(256), SMEM_BYTES, st, p);
-    OBTE_CHECK_LAUNCH("obte_gemm_bf16");
-    return OBTE_OK;
-}
-
-template <bool AK, bool BK>
-int dispatch_epi(const GemmParams& p, int epi, hipStream_t st) {
-    switch (epi) {
-        case OBTE_EPI_NONE: return launch<AK, BK, OBTE_EPI_NONE>(p, st);
-        case OBTE_EPI_GELU: return launch<AK, BK, OBTE_EPI_GELU>(p, st);
-        case OBTE_EPI_ADD: return launch<AK, BK, OBTE_EPI_ADD>(p, st);
-        case OBTE_EPI_GELU_BWD: return launch<AK, BK, OBTE_EPI_GELU_BWD>(p, st);
-        case OBTE_EPI_ADD_DROPOUT: return launch<AK, BK, OBTE_EPI_ADD_DROPOUT>(p, st);
-        case OBTE_EPI_ROPE_QK: return launch<AK, BK, OBTE_EPI_ROPE_QK>(p, st);
-    }
-    obte_set_error("obte_gemm_bf16: unknown epilogue %d", epi);
-    return OBTE_EINVAL;
-}
-
 }  // namespace obte_gemm_v1
-using namespace obte_gemm_v1;
 
-int obte_gemm_bf16_v1(const obte_gemm_args* g, obte_stream s) {
-    OBTE_REQUIRE(g && g->a && g->b && g->d, "obte_gemm_bf16: null pointer");
-    OBTE_REQUIRE(g->M > 0 && g->N > 0 && g->K > 0, "obte_gemm_bf16: empty problem M=%lld N=%lld K=%lld",
-                 (long long)g->M, (long long)g->N, (long long)g->K);
-    OBTE_REQUIRE(g->lda % 8 == 0 && g->ldb % 8 == 0 && g->ldd % 8 == 0 && g->N % 8 == 0,
-                 "obte_gemm_bf16: lda/ldb/ldd/N must be multiples of 8 (16-byte rows)");
-    OBTE_REQUIRE(!(g->a_kmajor) || g->K % 64 == 0, "obte_gemm_bf16: k-contiguous A needs K %% 64 == 0 (K=%lld)", (long long)g->K);
-    OBTE_REQUIRE(!(g->b_kmajor) || g->K % 64 == 0, "obte_gemm_bf16: k-contiguous B needs K %% 64 == 0 (K=%lld)", (long long)g->K);
-    OBTE_REQUIRE(g->a_kmajor ? g->lda >= g->K : g->lda >= g->M, "obte_gemm_bf16: lda too small");
-    OBTE_REQUIRE(g->b_kmajor ? g->ldb >= g->K : g->ldb >= g->N, "obte_gemm_bf16: ldb too small");
-    OBTE_REQUIRE(g->ldd >= g->N, "obte_gemm_bf16: ldd too small");
-    OBTE_REQUIRE(g->lda <= 1 << 20 && g->ldb <= 1 << 20, "obte_gemm_bf16: leading dimension too large");
-    if (g->epilogue == OBTE_EPI_ADD || g->epilogue == OBTE_EPI_GELU_BWD || g->epilogue == OBTE_EPI_ADD_DROPOUT) OBTE_REQUIRE(g->aux, "obte_gemm_bf16: epilogue needs aux");
-    if (g->epilogue == OBTE_EPI_ADD_DROPOUT) OBTE_REQUIRE(g->dropout_p >= 0.f && g->dropout_p < 1.f, "obte_gemm_bf16: dropout p must be in [0,1)");
-    if (g->epilogue == OBTE_EPI_ROPE_QK)
-        OBTE_REQUIRE(g->rope_cos && g->rope_sin && g->rope_T > 0 && g->rope_head_dim > 0 && g->rope_head_dim % 8 == 0 && g->N % 3 == 0 &&
-                         (g->N / 3) % g->rope_head_dim == 0,
-                     "obte_gemm_bf16: EPI_ROPE_QK needs cos/sin tables, T, head_dim %% 8 == 0 and N = 3 * n_head * head_dim");
-    if (g->epilogue == OBTE_EPI_GELU) OBTE_REQUIRE(g->d2, "obte_gemm_bf16: GELU epilogue needs d2");
-    if (g->epilogue != OBTE_EPI_NONE && g->epilogue != OBTE_EPI_ADD) OBTE_REQUIRE(g->alpha == 1.0f, "obte_gemm_bf16: alpha != 1 only with EPI_NONE / EPI_ADD");
+int obte_gemm_v1_launch(const obte_gemm_v2::GemmParams& q, bool ak, bool bk, int epi, hipStream_t st) {
+    using namespace obte_gemm_v1;
     GemmParams p;
-    p.a = (const bf16*)g->a; p.b = (const bf16*)g->b; p.d = (bf16*)g->d; p.aux = (const bf16*)g->aux; p.d2 = (bf16*)g->d2;
-    p.M = g->M; p.N = g->N; p.K = g->K; p.lda = g->lda; p.ldb = g->ldb; p.ldd = g->ldd;
-    p.a_elems = (g->a_kmajor ? g->M : g->K) * g->lda;
-    p.b_elems = (g->b_kmajor ? g->N : g->K) * g->ldb;
-    const int64_t tm = cdiv64(g->M, BM), tn = cdiv64(g->N, BN);
+    p.a = q.a; p.b = q.b; p.d = q.d; p.aux = q.aux; p.d2 = q.d2;
+    p.M = q.M; p.N = q.N; p.K = q.K; p.lda = q.lda; p.ldb = q.ldb; p.ldd = q.ldd;
+    p.a_elems = (ak ? q.M : q.K) * q.lda;   // (not q's: the debug build's timing hooks do not apply to this structure)
+    p.b_elems = (bk ? q.N : q.K) * q.ldb;
+    const int64_t tm = cdiv64(q.M, BM), tn = cdiv64(q.N, BN);
     OBTE_REQUIRE(tm * tn < (1ll << 30), "obte_gemm_bf16: too many tiles");
     p.tiles_m = (int)tm; p.tiles_n = (int)tn;
-    p.alpha = g->alpha;
-    p.rope_cos = g->rope_cos; p.rope_sin = g->rope_sin; p.rope_T = g->rope_T; p.rope_hs = g->rope_head_dim;
-    p.drop = make_drop(g->epilogue == OBTE_EPI_ADD_DROPOUT ? g->dropout_p : 0.f, g->dropout_seed, (uint32_t)g->dropout_site);
-    hipStream_t st = (hipStream_t)s;
-    if (g->a_kmajor && g->b_kmajor) return dispatch_epi<true, true>(p, g->epilogue, st);
-    if (g->a_kmajor && !g->b_kmajor) return dispatch_epi<true, false>(p, g->epilogue, st);
-    if (!g->a_kmajor && g->b_kmajor) return dispatch_epi<false, true>(p, g->epilogue, st);
-    return dispatch_epi<false, false>(p, g->epilogue, st);
+    p.alpha = q.alpha;
+    p.rope_cos = q.rope_cos; p.rope_sin = q.rope_sin; p.rope_T = q.rope_T; p.rope_hs = q.rope_hs;
+    p.drop = q.drop;
+    return gemm_dispatch<1, 128>(ak, bk, epi, false, [&](auto f) {
+        using F = decltype(f);
+        return gemm_launch<gemm_bf16_kernel<F::a_kmajor, F::b_kmajor, F::epilogue>, SMEM_BYTES>(p.tiles_m * p.tiles_n, 256, st, p);
+    });
 }

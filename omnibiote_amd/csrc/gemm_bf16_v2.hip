@@ -23,14 +23,6 @@
 // Split-K (for weight gradients whose output has fewer tiles than the chip has CUs): each split writes an fp32
 // partial tile to a slab; a second kernel sums the splits in a fixed order (bitwise reproducible) and rounds once.
 #include "gemm_common.h"
-#include <string.h>
-
-int obte_gemm_bf16_v1(const obte_gemm_args* g, obte_stream s);
-// structure 7 (gemm_bf16_v7.hip): which (layout, epilogue) combinations it is instantiated for, whether a problem can run on it, its launch
-namespace obte_gemm_v2 { struct GemmParams; }
-bool obte_gemm_v7_has(bool a_kmajor, bool b_kmajor, int epilogue);
-bool obte_gemm_v7_eligible(const obte_gemm_args* g);
-int obte_gemm_v7_launch(const obte_gemm_v2::GemmParams& p, bool a_kmajor, bool b_kmajor, int epilogue, hipStream_t st);
 
 namespace obte_gemm_v2 {
 
@@ -555,13 +547,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_v3_kernel(GemmParams p) {
 // class 1 = the rest — and when both class sizes divide by 8 every XCD receives its share of class 0 first, then
 // its share of class 1, so the short tiles start on the CUs that got no long one and behind the first finishers.
 // Layout and accumulate/overwrite are per problem (uniform branches; aux == null means overwrite).
-constexpr int GROUP_MAX = OBTE_GROUP_MAX;   // include/omnibiote_hip.h
-struct GroupParams {
-    GemmParams g[GROUP_MAX];
-    int first_wg[GROUP_MAX + 1];
-    int layout[GROUP_MAX];      // bit 1: A k-contiguous, bit 0: B k-contiguous
-    int n_class0;               // workgroups of class 0 (0: single class)
-};
+// (GroupParams: gemm_common.h)
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_v3_group_kernel(GroupParams gp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nwg = gp.first_wg[GROUP_MAX];
@@ -585,17 +571,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_v3_group_kernel(GroupParams 
     }
 }
 
-int launch_group(const GroupParams& gp, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_v3_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, V3_SMEM);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(gemm_v3_group_kernel, dim3(gp.first_wg[GROUP_MAX]), dim3(NTHREADS), V3_SMEM, st, gp);
-    OBTE_CHECK_LAUNCH("obte_gemm_grouped_bf16");
-    return OBTE_OK;
-}
-
 #define OBTE_INST3(AK, BK)                                                                   \
     template __global__ void gemm_v3_kernel<AK, BK, OBTE_EPI_NONE, true>(GemmParams);        \
     template __global__ void gemm_v3_kernel<AK, BK, OBTE_EPI_NONE, false>(GemmParams);       \
@@ -609,33 +584,6 @@ OBTE_INST3(true, false)
 OBTE_INST3(false, true)
 OBTE_INST3(false, false)
 #undef OBTE_INST3
-
-template <bool AK, bool BK, int EPI, bool SPLIT>
-int launch3(const GemmParams& p, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_v3_kernel<AK, BK, EPI, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_SMEM);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_v3_kernel<AK, BK, EPI, SPLIT>), dim3(p.tiles_m * p.tiles_n * p.splits), dim3(NTHREADS), V3_SMEM, st, p);
-    OBTE_CHECK_LAUNCH("obte_gemm_bf16");
-    return OBTE_OK;
-}
-
-template <bool AK, bool BK>
-int dispatch3(const GemmParams& p, int epi, hipStream_t st) {
-    if (p.splits > 1) return launch3<AK, BK, OBTE_EPI_NONE, true>(p, st);
-    switch (epi) {
-        case OBTE_EPI_NONE: return launch3<AK, BK, OBTE_EPI_NONE, false>(p, st);
-        case OBTE_EPI_GELU: return launch3<AK, BK, OBTE_EPI_GELU, false>(p, st);
-        case OBTE_EPI_ADD: return launch3<AK, BK, OBTE_EPI_ADD, false>(p, st);
-        case OBTE_EPI_GELU_BWD: return launch3<AK, BK, OBTE_EPI_GELU_BWD, false>(p, st);
-        case OBTE_EPI_ADD_DROPOUT: return launch3<AK, BK, OBTE_EPI_ADD_DROPOUT, false>(p, st);
-        case OBTE_EPI_ROPE_QK: return launch3<AK, BK, OBTE_EPI_ROPE_QK, false>(p, st);
-    }
-    obte_set_error("obte_gemm_bf16: unknown epilogue %d", epi);
-    return OBTE_EINVAL;
-}
 
 // ---- fourth structure: 256x128 tile, FOUR waves, ring of THREE half K-tiles (24 KiB each), TWO workgroups per CU ------------
 // What the K = 1024 shapes of the block lose (measured with the timing-only hooks on c_fc + GELU, 8192 x 4096 x 1024: 96 us
@@ -816,33 +764,6 @@ OBTE_INST4(false, true)
 OBTE_INST4(false, false)
 #undef OBTE_INST4
 
-template <bool AK, bool BK, int EPI, bool SPLIT>
-int launch4(const GemmParams& p, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_v4_kernel<AK, BK, EPI, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, V4_SMEM);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_v4_kernel<AK, BK, EPI, SPLIT>), dim3(p.tiles_m * p.tiles_n * p.splits), dim3(V4_THREADS), V4_SMEM, st, p);
-    OBTE_CHECK_LAUNCH("obte_gemm_bf16");
-    return OBTE_OK;
-}
-
-template <bool AK, bool BK>
-int dispatch4(const GemmParams& p, int epi, hipStream_t st) {
-    if (p.splits > 1) return launch4<AK, BK, OBTE_EPI_NONE, true>(p, st);
-    switch (epi) {
-        case OBTE_EPI_NONE: return launch4<AK, BK, OBTE_EPI_NONE, false>(p, st);
-        case OBTE_EPI_GELU: return launch4<AK, BK, OBTE_EPI_GELU, false>(p, st);
-        case OBTE_EPI_ADD: return launch4<AK, BK, OBTE_EPI_ADD, false>(p, st);
-        case OBTE_EPI_GELU_BWD: return launch4<AK, BK, OBTE_EPI_GELU_BWD, false>(p, st);
-        case OBTE_EPI_ADD_DROPOUT: return launch4<AK, BK, OBTE_EPI_ADD_DROPOUT, false>(p, st);
-        case OBTE_EPI_ROPE_QK: return launch4<AK, BK, OBTE_EPI_ROPE_QK, false>(p, st);
-    }
-    obte_set_error("obte_gemm_bf16: unknown epilogue %d", epi);
-    return OBTE_EINVAL;
-}
-
 // d[m][n] = bf16(alpha * sum_s slab[s][m][n]) in split order
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, bf16* __restrict__ d, const bf16* aux,
                                                              int64_t MN4, int64_t MN, int splits, float alpha) {
@@ -864,425 +785,45 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 }
 
-template <bool AK, bool BK, int EPI, bool SPLIT, int BN>
-int launch(const GemmParams& p, hipStream_t st) {
-    static bool attr_set = false;  // idempotent; a race only repeats the call
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_v2_kernel<AK, BK, EPI, SPLIT, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<BN>::SMEM);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_v2_kernel<AK, BK, EPI, SPLIT, BN>), dim3(p.tiles_m * p.tiles_n * p.splits), dim3(NTHREADS), Cfg<BN>::SMEM, st, p);
-    OBTE_CHECK_LAUNCH("obte_gemm_bf16");
-    return OBTE_OK;
-}
-
-template <bool AK, bool BK, int BN>
-int dispatch_bn(const GemmParams& p, int epi, hipStream_t st) {
-    if (p.splits > 1) return launch<AK, BK, OBTE_EPI_NONE, true, BN>(p, st);
-    switch (epi) {
-        case OBTE_EPI_NONE: return launch<AK, BK, OBTE_EPI_NONE, false, BN>(p, st);
-        case OBTE_EPI_GELU: return launch<AK, BK, OBTE_EPI_GELU, false, BN>(p, st);
-        case OBTE_EPI_ADD: return launch<AK, BK, OBTE_EPI_ADD, false, BN>(p, st);
-        case OBTE_EPI_GELU_BWD: return launch<AK, BK, OBTE_EPI_GELU_BWD, false, BN>(p, st);
-        case OBTE_EPI_ADD_DROPOUT: return launch<AK, BK, OBTE_EPI_ADD_DROPOUT, false, BN>(p, st);
-        case OBTE_EPI_ROPE_QK: return launch<AK, BK, OBTE_EPI_ROPE_QK, false, BN>(p, st);
-    }
-    obte_set_error("obte_gemm_bf16: unknown epilogue %d", epi);
-    return OBTE_EINVAL;
-}
-
-template <bool AK, bool BK>
-int dispatch(const GemmParams& p, int epi, int bn, hipStream_t st) {
-    return bn == 256 ? dispatch_bn<AK, BK, 256>(p, epi, st) : dispatch_bn<AK, BK, 128>(p, epi, st);
-}
-int dispatch192(const GemmParams& p, int epi, hipStream_t st) {   // k-contiguous A and B, no split
-    switch (epi) {
-        case OBTE_EPI_NONE: return launch<true, true, OBTE_EPI_NONE, false, 192>(p, st);
-        case OBTE_EPI_GELU: return launch<true, true, OBTE_EPI_GELU, false, 192>(p, st);
-        case OBTE_EPI_ADD: return launch<true, true, OBTE_EPI_ADD, false, 192>(p, st);
-        case OBTE_EPI_ADD_DROPOUT: return launch<true, true, OBTE_EPI_ADD_DROPOUT, false, 192>(p, st);
-        case OBTE_EPI_ROPE_QK: return launch<true, true, OBTE_EPI_ROPE_QK, false, 192>(p, st);
-    }
-    obte_set_error("obte_gemm_bf16: epilogue %d has no 192-wide form", epi);
-    return OBTE_EINVAL;
-}
-
-bool use_v1() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("OBTE_GEMM");
-        v = (e && e[0] == 'v' && e[1] == '1') ? 1 : 0;
-    }
-    return v == 1;
-}
-
-// OBTE_GEMM=v3 forces the four-half-stage structure wherever the plan is 256 wide (diagnostics / A-B timing)
-bool use_v3(int variant) {
-    if (variant == 3) return true;
-    const char* e = getenv("OBTE_GEMM");   // not cached: the tests flip it
-    return e && e[0] == 'v' && e[1] == '3';
-}
-
-// OBTE_GEMM=v4 forces the two-workgroups-per-CU structure wherever the plan is 128 wide (tests / A-B timing)
-bool use_v4(int variant) {
-    if (variant == 4) return true;
-    const char* e = getenv("OBTE_GEMM");   // not cached: the tests flip it
-    return e && e[0] == 'v' && e[1] == '4';
-}
-
 }  // namespace obte_gemm_v2
 using namespace obte_gemm_v2;
 
-// Tile width and split-K plan.  Prefer the 256-wide tile (higher FLOP per loaded byte) whenever it still yields
-// at least one workgroup per CU, directly or through a split of a long K; otherwise the 128-wide tile.
-// Split-K needs a workspace, epilogue NONE and ldd == N.
-struct Plan { int bn; int splits; int variant; };   // variant: 1 = first structure (gemm_bf16_v1.hip), 2 / 3 / 4 = this file (K-tile ring / half-tile ring / half-tile ring at two workgroups per CU)
-static int splits_for(int64_t tiles, int64_t nk) {
-    if (tiles >= 200 || nk < 16) return 1;
-    int s = (int)(256 / tiles);   // the largest split whose tiles * s workgroups still fit ONE round of the 256 CUs (rounding up instead
-                                  // put e.g. 20 tiles x 13 = 260 workgroups into two rounds: the readout's row-compact input gradient)
-    while (s > 1 && nk / s < 8) --s;
-    return s < 1 ? 1 : (s > 16 ? 16 : s);
-}
-static Plan make_plan(int64_t M, int64_t N, int64_t K, bool can_split) {
-    const int64_t nk = cdiv64(K, BKT);
-    const int64_t tm = cdiv64(M, BM);
-    const char* force = getenv("OBTE_GEMM_BN");
-    int bn = 0;
-    if (force) bn = atoi(force) == 256 ? 256 : 128;
-    if (!bn) {
-        const int64_t t256 = tm * cdiv64(N, 256);
-        const int s256 = can_split ? splits_for(t256, nk) : 1;
-        bn = (N >= 256 && t256 * s256 >= 200) ? 256 : 128;
-    }
-    const int64_t tiles = tm * cdiv64(N, bn);
-    return Plan{bn, can_split ? splits_for(tiles, nk) : 1, 2};
-}
-
-// ---- tuned plans: (layout, epilogue, M, N, K) -> plan, filled by the host-side tuner (omnibiote_amd/tune.py), which
-// times the candidates on the actual device once per shape.  Lookups are per call, under a mutex.
-#include <map>
-#include <mutex>
-#include <tuple>
-typedef std::tuple<int, int, int64_t, int64_t, int64_t> PlanKey;
-static std::mutex g_plan_mu;
-static std::map<PlanKey, Plan> g_plans;
-static bool lookup_plan(const obte_gemm_args* g, Plan* out, bool* near_match = nullptr) {
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    auto it = g_plans.find(PlanKey((g->a_kmajor ? 2 : 0) + (g->b_kmajor ? 1 : 0), g->epilogue, g->M, g->N, g->K));
-    if (it == g_plans.end() && g->epilogue == OBTE_EPI_ADD)   // accumulate-into-grad reuses the plan tuned for the plain form
-        it = g_plans.find(PlanKey((g->a_kmajor ? 2 : 0) + (g->b_kmajor ? 1 : 0), OBTE_EPI_NONE, g->M, g->N, g->K));
-    if (it == g_plans.end() && g->epilogue == OBTE_EPI_ROPE_QK)       // the c_attn projection: plan of the plain form
-        it = g_plans.find(PlanKey((g->a_kmajor ? 2 : 0) + (g->b_kmajor ? 1 : 0), OBTE_EPI_NONE, g->M, g->N, g->K));
-    if (it == g_plans.end() && g->epilogue == OBTE_EPI_ADD_DROPOUT)   // same main loop as the residual-add form
-        it = g_plans.find(PlanKey((g->a_kmajor ? 2 : 0) + (g->b_kmajor ? 1 : 0), OBTE_EPI_ADD, g->M, g->N, g->K));
-    if (it == g_plans.end()) {
-        // The readout's row-compact backward contracts over the MLM-masked rows of a micro-batch: their count changes from
-        // call to call (about 15 % of the rows), so its two shapes never match a tuned entry exactly.  Take the plan of an
-        // entry with the same layout and epilogue whose ONE differing dimension is within 20 %.
-        const int lay = (g->a_kmajor ? 2 : 0) + (g->b_kmajor ? 1 : 0);
-        const int epi = g->epilogue == OBTE_EPI_ADD ? OBTE_EPI_NONE : g->epilogue;
-        auto near = [](int64_t a, int64_t b) { return a * 5 >= b * 4 && a * 5 <= b * 6; };
-        for (auto jt = g_plans.begin(); jt != g_plans.end(); ++jt) {
-            if (std::get<0>(jt->first) != lay || std::get<1>(jt->first) != epi) continue;
-            const int64_t m = std::get<2>(jt->first), n = std::get<3>(jt->first), k = std::get<4>(jt->first);
-            const int same = (m == g->M) + (n == g->N) + (k == g->K);
-            if (same == 2 && near(m, g->M) && near(n, g->N) && near(k, g->K)) { it = jt; if (near_match) *near_match = true; break; }
-        }
-    }
-    if (it == g_plans.end()) return false;
-    *out = it->second;
-    return true;
-}
-
-extern "C" int obte_gemm_plan_set(int a_kmajor, int b_kmajor, int epilogue, int64_t M, int64_t N, int64_t K, int variant,
-                                  int bn, int splits) {
-    OBTE_REQUIRE(variant >= 1 && variant <= 7 && variant != 5 && variant != 6 && (bn == 128 || bn == 256 || bn == 192) && splits >= 1 && splits <= 64, "obte_gemm_plan_set: bad plan");
-    OBTE_REQUIRE(!(variant == 7 && (bn != 256 || splits != 1 || !obte_gemm_v7_has(a_kmajor != 0, b_kmajor != 0, epilogue))),
-                 "obte_gemm_plan_set: the persistent continuous-ring structure is 256 wide, no split-K, x W^T and dy W layouts with their epilogues");
-    OBTE_REQUIRE(!(bn == 192 && (variant != 2 || splits != 1 || !a_kmajor || !b_kmajor || epilogue == OBTE_EPI_GELU_BWD)),
-                 "obte_gemm_plan_set: the 192-wide tile exists for the K-tile ring, k-contiguous operands, no split-K");
-    OBTE_REQUIRE(!(variant == 3 && bn != 256), "obte_gemm_plan_set: the four-half-stage structure is 256 wide");
-    OBTE_REQUIRE(!(variant == 4 && bn != 128), "obte_gemm_plan_set: the two-workgroups-per-CU structure is 128 wide");
-    OBTE_REQUIRE(!(variant == 1 && splits != 1), "obte_gemm_plan_set: the first structure has no split-K");
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    g_plans[PlanKey((a_kmajor ? 2 : 0) + (b_kmajor ? 1 : 0), epilogue, M, N, K)] = Plan{bn, splits, variant};
-    return OBTE_OK;
-}
-extern "C" int obte_gemm_plan_clear(void) {
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    g_plans.clear();
-    return OBTE_OK;
-}
-extern "C" int64_t obte_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-    int splits = make_plan(M, N, K, true).splits;
-    {
-        std::lock_guard<std::mutex> lk(g_plan_mu);
-        bool tuned = false;
-        int ts = 1;
-        auto near = [](int64_t a, int64_t b) { return a * 5 >= b * 4 && a * 5 <= b * 6; };
-        for (auto& kv : g_plans) {
-            const int64_t m = std::get<2>(kv.first), n = std::get<3>(kv.first), k = std::get<4>(kv.first);
-            const int same = (m == M) + (n == N) + (k == K);
-            if (same == 3 || (same == 2 && near(m, M) && near(n, N) && near(k, K))) {   // exact, or the near match lookup_plan accepts
-                tuned = true;
-                if (kv.second.splits > ts) ts = kv.second.splits;
-            }
-        }
-        if (tuned) splits = ts > splits ? ts : splits;
-    }
-    return splits > 1 ? (int64_t)splits * M * N * 4 : 0;
-}
-extern "C" int64_t obte_gemm_workspace_bytes_max(int64_t M, int64_t N, int64_t K) {
-    (void)K;
-    return 8 * M * N * 4;   // enough for any plan the tuner tries (splits <= 8)
-}
-
-
-static int validate_args(const obte_gemm_args* g) {
-    OBTE_REQUIRE(g && g->a && g->b && g->d, "obte_gemm_bf16: null pointer");
-    OBTE_REQUIRE(g->M > 0 && g->N > 0 && g->K > 0, "obte_gemm_bf16: empty problem M=%lld N=%lld K=%lld",
-                 (long long)g->M, (long long)g->N, (long long)g->K);
-    OBTE_REQUIRE(g->lda % 8 == 0 && g->ldb % 8 == 0 && g->ldd % 8 == 0 && g->N % 8 == 0,
-                 "obte_gemm_bf16: lda/ldb/ldd/N must be multiples of 8 (16-byte rows)");
-    OBTE_REQUIRE(!(g->a_kmajor) || g->K % 64 == 0, "obte_gemm_bf16: k-contiguous A needs K %% 64 == 0 (K=%lld)", (long long)g->K);
-    OBTE_REQUIRE(!(g->b_kmajor) || g->K % 64 == 0, "obte_gemm_bf16: k-contiguous B needs K %% 64 == 0 (K=%lld)", (long long)g->K);
-    OBTE_REQUIRE(g->a_kmajor ? g->lda >= g->K : g->lda >= g->M, "obte_gemm_bf16: lda too small");
-    OBTE_REQUIRE(g->b_kmajor ? g->ldb >= g->K : g->ldb >= g->N, "obte_gemm_bf16: ldb too small");
-    OBTE_REQUIRE(g->ldd >= g->N, "obte_gemm_bf16: ldd too small");
-    OBTE_REQUIRE(g->lda <= 1 << 20 && g->ldb <= 1 << 20, "obte_gemm_bf16: leading dimension too large");
-    if (g->epilogue == OBTE_EPI_ADD || g->epilogue == OBTE_EPI_GELU_BWD || g->epilogue == OBTE_EPI_ADD_DROPOUT) OBTE_REQUIRE(g->aux, "obte_gemm_bf16: epilogue needs aux");
-    if (g->epilogue == OBTE_EPI_ADD_DROPOUT) OBTE_REQUIRE(g->dropout_p >= 0.f && g->dropout_p < 1.f, "obte_gemm_bf16: dropout p must be in [0,1)");
-    if (g->epilogue == OBTE_EPI_ROPE_QK)
-        OBTE_REQUIRE(g->rope_cos && g->rope_sin && g->rope_T > 0 && g->rope_head_dim > 0 && g->rope_head_dim % 8 == 0 && g->N % 3 == 0 &&
-                         (g->N / 3) % g->rope_head_dim == 0,
-                     "obte_gemm_bf16: EPI_ROPE_QK needs cos/sin tables, T, head_dim %% 8 == 0 and N = 3 * n_head * head_dim");
-    if (g->epilogue == OBTE_EPI_GELU) OBTE_REQUIRE(g->d2, "obte_gemm_bf16: GELU epilogue needs d2");
-    if (g->epilogue != OBTE_EPI_NONE && g->epilogue != OBTE_EPI_ADD) OBTE_REQUIRE(g->alpha == 1.0f, "obte_gemm_bf16: alpha != 1 only with EPI_NONE / EPI_ADD");
+// ---- launchers (gemm_common.h) ---------------------------------------------------------------------------------------------------------
+int obte_gemm_splitk_reduce(const GemmParams& p, const bf16* aux, hipStream_t st) {
+    const int64_t mn = p.M * p.N;
+    int64_t blocks = cdiv64(mn / 4, 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)p.slab, p.d, aux, mn / 4, mn, p.splits, p.alpha);
+    hipError_t e_ = hipGetLastError();
+    if (e_ != hipSuccess) { obte_set_error("obte_gemm_bf16(split-K reduce): %s", hipGetErrorString(e_)); return OBTE_ELAUNCH; }
     return OBTE_OK;
 }
 
-static void fill_params(const obte_gemm_args* g, void* workspace, GemmParams& p) {
-    p.a = (const bf16*)g->a; p.b = (const bf16*)g->b; p.d = (bf16*)g->d; p.aux = (const bf16*)g->aux; p.d2 = (bf16*)g->d2;
-    p.slab = (float*)workspace;
-    p.M = g->M; p.N = g->N; p.K = g->K; p.lda = g->lda; p.ldb = g->ldb; p.ldd = g->ldd;
-    p.a_elems = (g->a_kmajor ? g->M : g->K) * g->lda;
-    p.b_elems = (g->b_kmajor ? g->N : g->K) * g->ldb;
-    p.store_rows = p.M;
-    p.delay_sleeps = 0;
-    p.dbg_times = nullptr;
-    p.nt_store = (g->M * g->N * 2 > (256ll << 20)) ? 1 : 0;
-    // the GELU epilogue's d (the derivative, 67 MB at the hot-path shape) is read again only in the backward pass: stored
-    // non-temporally it does not push the activation d2 — the next GEMM's operand — and the operand panels out of L2 /
-    // Infinity Cache (c_fc + GELU 97.8 -> 94.5 us, cold operands)
-    if (g->epilogue == OBTE_EPI_GELU) p.nt_store = 1;
-#ifdef OBTE_DEBUG_HOOKS
-    {   // timing-only diagnostics of the debug build (results are wrong): zero-record descriptors drop every LDS-DMA / no stores
-        static int noload = -1, nostore = -1, exit_now = -1;
-        if (noload < 0) {
-            const char* e = getenv("OBTE_GEMM_DEBUG");
-            nostore = (e && strstr(e, "nostore")) ? 1 : 0;
-            exit_now = (e && strstr(e, "exit")) ? 1 : 0;
-            noload = (e && strstr(e, "noload")) ? 1 : 0;
-            if (noload || nostore || exit_now) fprintf(stderr, "libomnibiote_hip (DEBUG build): OBTE_GEMM_DEBUG=%s is active — GEMM results are WRONG, timing only\n", e);
-        }
-        if (noload) { p.a_elems = 0; p.b_elems = 0; }
-        if (exit_now) p.store_rows = -1; else if (nostore) p.store_rows = 0;
-        static int delay = -1;
-        if (delay < 0) { const char* d = getenv("OBTE_GEMM_V4_DELAY"); delay = d ? atoi(d) : 0; }
-        p.delay_sleeps = delay;
-    }
-#endif
+template <int BN>
+int obte_gemm_v2_launch(const GemmParams& p, bool ak, bool bk, int epi, hipStream_t st) {
+    return gemm_dispatch<2, BN>(ak, bk, epi, p.splits > 1, [&](auto f) {
+        using F = decltype(f);
+        return gemm_launch<gemm_v2_kernel<F::a_kmajor, F::b_kmajor, F::epilogue, F::split, BN>, Cfg<BN>::SMEM>(p.tiles_m * p.tiles_n * p.splits, NTHREADS, st, p);
+    });
+}
+template int obte_gemm_v2_launch<128>(const GemmParams&, bool, bool, int, hipStream_t);
+template int obte_gemm_v2_launch<192>(const GemmParams&, bool, bool, int, hipStream_t);
+template int obte_gemm_v2_launch<256>(const GemmParams&, bool, bool, int, hipStream_t);
+
+int obte_gemm_v3_launch(const GemmParams& p, bool ak, bool bk, int epi, hipStream_t st) {
+    return gemm_dispatch<3, 256>(ak, bk, epi, p.splits > 1, [&](auto f) {
+        using F = decltype(f);
+        return gemm_launch<gemm_v3_kernel<F::a_kmajor, F::b_kmajor, F::epilogue, F::split>, V3_SMEM>(p.tiles_m * p.tiles_n * p.splits, NTHREADS, st, p);
+    });
 }
 
-#ifdef OBTE_DEBUG_HOOKS
-// OBTE_GEMM_TIMES=1 (debug build): where a GEMM launch spends its time, from s_memrealtime stamps (100 MHz) of every workgroup
-#include <vector>
-static unsigned long long* debug_gemm_times_buffer(int64_t groups) {
-    static int on = -1;
-    static unsigned long long* buf = nullptr;
-    static int64_t cap = 0;
-    if (on < 0) { const char* e = getenv("OBTE_GEMM_TIMES"); on = (e && e[0] == '1') ? 1 : 0; }
-    if (!on) return nullptr;
-    if (cap < groups) {
-        if (buf) (void)hipFree(buf);
-        if (hipMalloc((void**)&buf, (size_t)groups * 64) != hipSuccess) { buf = nullptr; cap = 0; return nullptr; }
-        cap = groups;
-    }
-    (void)hipMemset(buf, 0, (size_t)groups * 64);
-    return buf;
-}
-static void debug_gemm_report(const GemmParams& p, int variant, int epi, hipStream_t st) {
-    const int n = p.tiles_m * p.tiles_n * p.splits;
-    static std::vector<unsigned long long> h;
-    h.resize((size_t)n * 8);
-    if (hipStreamSynchronize(st) != hipSuccess) return;
-    if (hipMemcpy(h.data(), p.dbg_times, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
-    unsigned long long t0 = ~0ull, tend = 0;
-    for (int i = 0; i < n; ++i) { if (h[(size_t)i * 8] && h[(size_t)i * 8] < t0) t0 = h[(size_t)i * 8]; if (h[(size_t)i * 8 + 4] > tend) tend = h[(size_t)i * 8 + 4]; }
-    // workgroups of the first wave of residents (entered within 2 us of the first) and the rest (later rounds)
-    double seg[2][4] = {{0}}, entry[2] = {0, 0}, done[2] = {0, 0}, ep1[2] = {0, 0}, ep2[2] = {0, 0}, ep3[2] = {0, 0}; int cnt[2] = {0, 0};
-    for (int i = 0; i < n; ++i) {
-        const unsigned long long* r = &h[(size_t)i * 8];
-        if (!r[0]) continue;
-        const int c = (r[0] - t0) > 200 ? 1 : 0;
-        cnt[c]++; entry[c] += (double)(r[0] - t0); done[c] += (double)(r[4] - t0);
-        for (int k = 0; k < 4; ++k) seg[c][k] += (double)(r[k + 1] - r[k]);
-        if (r[5] && r[6]) { ep1[c] += (double)(r[5] - r[2]); ep2[c] += (double)(r[6] - r[5]); ep3[c] += (double)(r[7] - r[6]); }   // epilogue: until every wave is out of the loop / staging written and published
-    }
-    fprintf(stderr, "[gemm v%d epi %d %lldx%lldx%lld, %d workgroups, us] span %.2f", variant, epi, (long long)p.M, (long long)p.N, (long long)p.K, n, (tend - t0) * 0.01);
-    for (int c = 0; c < 2; ++c)
-        if (cnt[c]) fprintf(stderr, " | %s %d: entry +%.2f, prologue %.2f, loop %.2f, epilogue issue %.2f (all waves out of the loop %.2f + staging %.2f + read back %.2f + arithmetic, stores), drain %.2f, done +%.2f", c ? "later" : "first", cnt[c], entry[c] / cnt[c] * 0.01,
-                            seg[c][0] / cnt[c] * 0.01, seg[c][1] / cnt[c] * 0.01, seg[c][2] / cnt[c] * 0.01, ep1[c] / cnt[c] * 0.01, ep2[c] / cnt[c] * 0.01, ep3[c] / cnt[c] * 0.01, seg[c][3] / cnt[c] * 0.01, done[c] / cnt[c] * 0.01);
-    fprintf(stderr, "\n");
-}
-#endif
-
-extern "C" int obte_gemm_bf16_ws(const obte_gemm_args* g, void* workspace, int64_t workspace_bytes, obte_stream s) {
-    { const int vrc = validate_args(g); if (vrc != OBTE_OK) return vrc; }
-    hipStream_t st = (hipStream_t)s;
-    int rc;
-    const bool can_split = workspace && (g->epilogue == OBTE_EPI_NONE || g->epilogue == OBTE_EPI_ADD) && g->ldd == g->N;
-    Plan pl;
-    bool near_match = false;
-    if (!lookup_plan(g, &pl, &near_match)) pl = make_plan(g->M, g->N, g->K, can_split);
-    if (near_match && pl.splits > 1) {   // a borrowed split count must still fit one round for THIS tile count (1288 rows: 24 tiles x 12 = 288)
-        const int64_t tiles = cdiv64(g->M, BM) * cdiv64(g->N, pl.bn);
-        while (pl.splits > 1 && tiles <= 256 && tiles * pl.splits > 256) --pl.splits;
-    }
-    if (pl.splits > 1 && (!can_split || (int64_t)pl.splits * g->M * g->N * 4 > workspace_bytes)) pl = make_plan(g->M, g->N, g->K, false);
-    if (pl.bn == 192 && !(g->a_kmajor && g->b_kmajor && g->epilogue != OBTE_EPI_GELU_BWD)) pl = make_plan(g->M, g->N, g->K, false);
-    if (pl.variant == 7 && !obte_gemm_v7_eligible(g)) pl = Plan{256, 1, 3};              // (the same: the half-tile ring one tile per workgroup)
-    // profiler record kind = layout/epilogue code + 1000 * kernel structure (1: gemm_bf16_kernel, 2: gemm_v2_kernel, 3: gemm_v3_kernel)
-    const int kind0 = (g->a_kmajor ? 8 : 0) + (g->b_kmajor ? 4 : 0) + g->epilogue;
-    if (use_v1() || pl.variant == 1) {
-        const int prof = obte_prof_begin(st, kind0 + 1000, g->M, g->N, g->K);
-        rc = obte_gemm_bf16_v1(g, s);
-        obte_prof_end(prof, st);
-        return rc;
-    }
-    GemmParams p;
-    fill_params(g, workspace, p);
-    const int64_t tm = cdiv64(g->M, BM), tn = cdiv64(g->N, pl.bn);
-    OBTE_REQUIRE(tm * tn < (1ll << 26), "obte_gemm_bf16: too many tiles");
-    p.tiles_m = (int)tm; p.tiles_n = (int)tn;
-    const int64_t nk = cdiv64(g->K, BKT);
-    const int splits = pl.splits;
-    p.k_per_split = (int)cdiv64(nk, splits);
-    p.splits = (int)cdiv64(nk, p.k_per_split);   // no empty splits
-    p.alpha = g->alpha;
-    p.rope_cos = g->rope_cos; p.rope_sin = g->rope_sin; p.rope_T = g->rope_T; p.rope_hs = g->rope_head_dim;
-    p.drop = make_drop(g->epilogue == OBTE_EPI_ADD_DROPOUT ? g->dropout_p : 0.f, g->dropout_seed, (uint32_t)g->dropout_site);
-#ifdef OBTE_DEBUG_HOOKS
-    p.dbg_times = debug_gemm_times_buffer((int64_t)p.tiles_m * p.tiles_n * p.splits);
-#endif
-    const bool long_enough = p.k_per_split >= 2 && nk - (int64_t)(p.splits - 1) * p.k_per_split >= 2;   // the half-tile rings need >= 4 half-steps
-    if (pl.variant == 7 && pl.bn == 256 && p.splits == 1) {
-        const int prof7 = obte_prof_begin(st, kind0 + 7000, g->M, g->N, g->K);
-        rc = obte_gemm_v7_launch(p, g->a_kmajor != 0, g->b_kmajor != 0, g->epilogue, st);
-        obte_prof_end(prof7, st);
-        return rc;
-    }
-    const bool v3 = use_v3(pl.variant) && pl.bn == 256 && long_enough;
-    const bool v4 = !v3 && use_v4(pl.variant) && pl.bn == 128 && long_enough;
-    const int prof = obte_prof_begin(st, kind0 + (v3 ? 3000 : (v4 ? 4000 : 2000)), g->M, g->N, g->K);
-    if (v4) {
-        if (g->a_kmajor && g->b_kmajor) rc = dispatch4<true, true>(p, g->epilogue, st);
-        else if (g->a_kmajor && !g->b_kmajor) rc = dispatch4<true, false>(p, g->epilogue, st);
-        else if (!g->a_kmajor && g->b_kmajor) rc = dispatch4<false, true>(p, g->epilogue, st);
-        else rc = dispatch4<false, false>(p, g->epilogue, st);
-    } else if (v3) {
-        if (g->a_kmajor && g->b_kmajor) rc = dispatch3<true, true>(p, g->epilogue, st);
-        else if (g->a_kmajor && !g->b_kmajor) rc = dispatch3<true, false>(p, g->epilogue, st);
-        else if (!g->a_kmajor && g->b_kmajor) rc = dispatch3<false, true>(p, g->epilogue, st);
-        else rc = dispatch3<false, false>(p, g->epilogue, st);
-    } else if (pl.bn == 192) rc = dispatch192(p, g->epilogue, st);
-    else if (g->a_kmajor && g->b_kmajor) rc = dispatch<true, true>(p, g->epilogue, pl.bn, st);
-    else if (g->a_kmajor && !g->b_kmajor) rc = dispatch<true, false>(p, g->epilogue, pl.bn, st);
-    else if (!g->a_kmajor && g->b_kmajor) rc = dispatch<false, true>(p, g->epilogue, pl.bn, st);
-    else rc = dispatch<false, false>(p, g->epilogue, pl.bn, st);
-#ifdef OBTE_DEBUG_HOOKS
-    if (rc == OBTE_OK && p.dbg_times) debug_gemm_report(p, v3 ? 3 : (v4 ? 4 : 2), g->epilogue, st);
-#endif
-    if (rc == OBTE_OK && p.splits > 1) {
-        const int64_t mn = g->M * g->N;
-        int64_t blocks = cdiv64(mn / 4, 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)workspace, (bf16*)g->d,
-                           g->epilogue == OBTE_EPI_ADD ? (const bf16*)g->aux : (const bf16*)nullptr, mn / 4, mn, p.splits, g->alpha);
-        hipError_t e_ = hipGetLastError();
-        if (e_ != hipSuccess) { obte_set_error("obte_gemm_bf16(split-K reduce): %s", hipGetErrorString(e_)); rc = OBTE_ELAUNCH; }
-    }
-    obte_prof_end(prof, st);
-    return rc;
+int obte_gemm_v4_launch(const GemmParams& p, bool ak, bool bk, int epi, hipStream_t st) {
+    return gemm_dispatch<4, 128>(ak, bk, epi, p.splits > 1, [&](auto f) {
+        using F = decltype(f);
+        return gemm_launch<gemm_v4_kernel<F::a_kmajor, F::b_kmajor, F::epilogue, F::split>, V4_SMEM>(p.tiles_m * p.tiles_n * p.splits, V4_THREADS, st, p);
+    });
 }
 
-extern "C" int obte_gemm_bf16(const obte_gemm_args* g, obte_stream s) { return obte_gemm_bf16_ws(g, nullptr, 0, s); }
-
-// common.h: the plain dy W product with the row-dot epilogue, on structure 7 or not at all (1)
-extern "C" int obte_gemm_rowdot_bf16(const obte_gemm_args* g, const obte_bf16* other, float* rowdot, int64_t T, int32_t head_dim, obte_stream s) {
-    { const int vrc = validate_args(g); if (vrc != OBTE_OK) return vrc; }
-    OBTE_REQUIRE(other && rowdot && T > 0, "obte_gemm_rowdot_bf16: null pointer");
-    OBTE_REQUIRE(g->epilogue == OBTE_EPI_NONE && g->a_kmajor && !g->b_kmajor && g->alpha == 1.0f, "obte_gemm_rowdot_bf16: the plain dy W product only");
-    static const bool off = [] { const char* e = getenv("OBTE_GEMM_ROWDOT"); return e && e[0] == '0'; }();   // (A/B timing: the prep launch forms delta instead)
-    obte_gemm_args g2 = *g;
-    g2.epilogue = OBTE_EPI_ROWDOT;
-    if (off || head_dim != 128 || g->N % 128 != 0 || g->M % T != 0 || T >= (1ll << 31) || g->M >= (1ll << 31) || !obte_gemm_v7_eligible(&g2)) return 1;
-    hipStream_t st = (hipStream_t)s;
-    GemmParams p;
-    fill_params(g, nullptr, p);
-    p.aux = (const bf16*)other;
-    p.slab = rowdot;                      // (no split-K here: the slot carries the row-dot output)
-    p.tiles_m = (int)(g->M / BM); p.tiles_n = (int)(g->N / 256);
-    p.k_per_split = (int)cdiv64(g->K, BKT); p.splits = 1;
-    p.alpha = 1.0f;
-    p.rope_cos = nullptr; p.rope_sin = nullptr; p.rope_T = T; p.rope_hs = head_dim;
-    p.drop = make_drop(0.f, 0, 0);
-#ifdef OBTE_DEBUG_HOOKS
-    p.dbg_times = nullptr;
-#endif
-    const int prof = obte_prof_begin(st, 8 + OBTE_EPI_NONE + 7000, g->M, g->N, g->K);   // (recorded as the dy W product it is)
-    const int rc = obte_gemm_v7_launch(p, true, false, OBTE_EPI_ROWDOT, st);
-    obte_prof_end(prof, st);
-    return rc;
-}
-
-// Grouped launch (see gemm_v3_group_kernel).  Each problem: any layout, epilogue NONE or ADD, K >= 128.
-extern "C" int obte_gemm_grouped_bf16(const obte_gemm_args* gs, int count, obte_stream s) {
-    OBTE_REQUIRE(gs && count >= 1 && count <= GROUP_MAX, "obte_gemm_grouped_bf16: count must be 1..%d", GROUP_MAX);
-    GroupParams gp;
-    memset(&gp, 0, sizeof(gp));
-    hipStream_t st = (hipStream_t)s;
-    int wg = 0, class0 = 0;
-    bool in_class0 = true;
-    double flop = 0.0;
-    for (int i = 0; i < count; ++i) {
-        const obte_gemm_args* g = gs + i;
-        OBTE_REQUIRE(g->epilogue == OBTE_EPI_NONE || g->epilogue == OBTE_EPI_ADD, "obte_gemm_grouped_bf16: epilogue must be NONE or ADD");
-        { const int vrc = validate_args(g); if (vrc != OBTE_OK) return vrc; }
-        OBTE_REQUIRE(g->K >= 128, "obte_gemm_grouped_bf16: K must be >= 128 (K=%lld)", (long long)g->K);
-        GemmParams& p = gp.g[i];
-        fill_params(g, nullptr, p);
-        if (g->epilogue == OBTE_EPI_NONE) p.aux = nullptr;
-        const int64_t tm = cdiv64(g->M, BM), tn = cdiv64(g->N, 256);
-        OBTE_REQUIRE(tm * tn < (1ll << 24), "obte_gemm_grouped_bf16: too many tiles");
-        p.tiles_m = (int)tm; p.tiles_n = (int)tn; p.splits = 1;
-        p.k_per_split = (int)cdiv64(g->K, BKT);
-        p.alpha = g->alpha;
-        p.drop = make_drop(0.f, 0, 0);
-        gp.layout[i] = (g->a_kmajor ? 2 : 0) + (g->b_kmajor ? 1 : 0);
-        gp.first_wg[i] = wg;
-        wg += (int)(tm * tn);
-        if (in_class0 && p.k_per_split == gp.g[0].k_per_split) class0 = wg; else in_class0 = false;
-        flop += 2.0 * (double)g->M * (double)g->N * (double)g->K;
-    }
-    for (int i = count; i <= GROUP_MAX; ++i) gp.first_wg[i] = wg;
-    for (int i = count; i < GROUP_MAX; ++i) { gp.g[i] = gp.g[0]; gp.layout[i] = gp.layout[0]; }   // never selected
-    gp.n_class0 = (class0 < wg && class0 % 8 == 0 && (wg - class0) % 8 == 0) ? class0 : 0;
-    // profiler record: one entry; d0 chosen so that 2*d0*d1*d2 is the group's total FLOP
-    const int prof = obte_prof_begin(st, 32 + (count > 1 && gp.layout[count - 1] != gp.layout[0] ? 1 : 0) + (gs[0].epilogue == OBTE_EPI_ADD ? 2 : 0),
-                                     (int64_t)(flop / (2.0 * (double)gs[0].N * (double)gs[0].K) + 0.5), gs[0].N, gs[0].K);
-    const int rc = launch_group(gp, st);
-    obte_prof_end(prof, st);
-    return rc;
+int obte_gemm_group_launch(const GroupParams& gp, hipStream_t st) {
+    return gemm_launch<gemm_v3_group_kernel, V3_SMEM>(gp.first_wg[GROUP_MAX], NTHREADS, st, gp, "obte_gemm_grouped_bf16");
 }

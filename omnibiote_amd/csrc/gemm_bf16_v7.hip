@@ -23,7 +23,6 @@
 // a free slot and touches no memory), which keeps every wait of the loop the same immediate to the end.
 // Whole tiles only (M, N multiples of 256; K a multiple of 64, >= 256), no split-K; x W^T and dy W layouts.
 #include "gemm_common.h"
-#include <type_traits>
 
 using namespace obte_gemm_v2;
 
@@ -324,36 +323,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_v7_kernel(GemmParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the zero-record pieces of the last half-steps write LDS too: none may land after the workgroup has gone)
 }
 
-template <bool AK, bool BK, int EPI>
-int launch7(const GemmParams& p, hipStream_t st) {
-    static const bool attr_set = [] {
-        (void)hipFuncSetAttribute((const void*)gemm_v7_kernel<AK, BK, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, V7_SMEM);
-        return true;
-    }();
-    (void)attr_set;
-    const int ntiles = p.tiles_m * p.tiles_n;
-    hipLaunchKernelGGL((gemm_v7_kernel<AK, BK, EPI>), dim3(ntiles < 256 ? ntiles : 256), dim3(NTHREADS), V7_SMEM, st, p);
-    OBTE_CHECK_LAUNCH("obte_gemm_bf16");
-    return OBTE_OK;
-}
-
 }  // namespace
-
-bool obte_gemm_v7_has(bool a_kmajor, bool b_kmajor, int epilogue) {
-    if (a_kmajor && b_kmajor)
-        return epilogue == OBTE_EPI_NONE || epilogue == OBTE_EPI_GELU || epilogue == OBTE_EPI_ADD || epilogue == OBTE_EPI_ADD_DROPOUT ||
-               epilogue == OBTE_EPI_ROPE_QK;
-    if (a_kmajor && !b_kmajor) return epilogue == OBTE_EPI_NONE || epilogue == OBTE_EPI_GELU_BWD || epilogue == OBTE_EPI_ROWDOT;
-    return false;
-}
-
-// whole 256 x 256 tiles, at least one per CU, eight half-steps or more per tile (the ring is refilled four half-steps ahead across tiles)
-bool obte_gemm_v7_eligible(const obte_gemm_args* g) {
-    return obte_gemm_v7_has(g->a_kmajor != 0, g->b_kmajor != 0, g->epilogue) && g->M % BM == 0 && g->N % 256 == 0 && g->K % BKT == 0 &&
-           g->K >= 4 * BKT && (g->M / BM) * (g->N / 256) >= 256 && (g->epilogue != OBTE_EPI_ADD || g->aux != nullptr) &&
-           g->ldd < (1ll << 24) &&                        // (32-bit element offsets inside a wave's 64-row tile; the tile origin is 64-bit)
-           g->M * g->N * 2 <= (256ll << 20);              // (an output beyond the Infinity Cache wants non-temporal stores: structures 2 / 3)
-}
 
 #ifdef OBTE_DEBUG_HOOKS
 #include <vector>
@@ -378,21 +348,9 @@ int obte_gemm_v7_launch(const GemmParams& p, bool ak, bool bk, int epi, hipStrea
 #ifdef OBTE_DEBUG_HOOKS
     struct Rep { const GemmParams& p; int epi; hipStream_t st; ~Rep() { if (p.dbg_times) v7_report(p, epi, st); } } rep{p, epi, st};
 #endif
-    if (ak && bk) {
-        switch (epi) {
-            case OBTE_EPI_NONE: return launch7<true, true, OBTE_EPI_NONE>(p, st);
-            case OBTE_EPI_GELU: return launch7<true, true, OBTE_EPI_GELU>(p, st);
-            case OBTE_EPI_ADD: return launch7<true, true, OBTE_EPI_ADD>(p, st);
-            case OBTE_EPI_ADD_DROPOUT: return launch7<true, true, OBTE_EPI_ADD_DROPOUT>(p, st);
-            case OBTE_EPI_ROPE_QK: return launch7<true, true, OBTE_EPI_ROPE_QK>(p, st);
-        }
-    } else if (ak && !bk) {
-        switch (epi) {
-            case OBTE_EPI_NONE: return launch7<true, false, OBTE_EPI_NONE>(p, st);
-            case OBTE_EPI_GELU_BWD: return launch7<true, false, OBTE_EPI_GELU_BWD>(p, st);
-            case OBTE_EPI_ROWDOT: return launch7<true, false, OBTE_EPI_ROWDOT>(p, st);
-        }
-    }
-    obte_set_error("obte_gemm_bf16: structure 7 has no form for this layout / epilogue (%d %d %d)", (int)ak, (int)bk, epi);
-    return OBTE_EINVAL;
+    return gemm_dispatch<7, 256>(ak, bk, epi, false, [&](auto f) {
+        using F = decltype(f);
+        const int ntiles = p.tiles_m * p.tiles_n;
+        return gemm_launch<gemm_v7_kernel<F::a_kmajor, F::b_kmajor, F::epilogue>, V7_SMEM>(ntiles < 256 ? ntiles : 256, NTHREADS, st, p);
+    });
 }

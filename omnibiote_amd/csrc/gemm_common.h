@@ -133,3 +133,88 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 }  // namespace obte_gemm_v2
+
+// ---- the GEMM family's host interface: capability table, launch helper, dispatcher, one launcher per structure --------------------
+// Does structure S at tile width BN have a kernel for (layout, epilogue, split-K)?  A split-K form runs epilogue NONE into fp32 slabs;
+// the reduce kernel applies ADD.  Each structure file instantiates exactly these forms and its dispatcher reaches no other;
+// obte_gemm_plan_set validates plans against the same answer and the plan resolver (gemm.cpp) falls back from it.
+constexpr bool gemm_has_form(int s, int bn, bool ak, bool bk, int epi, bool split) {
+    const bool abi = epi >= OBTE_EPI_NONE && epi <= OBTE_EPI_ROPE_QK;                          // the six epilogues of the public ABI
+    const bool ring = abi && (!split || epi == OBTE_EPI_NONE || epi == OBTE_EPI_ADD);
+    switch (s) {
+        case 1: return bn == 128 && abi && !split;                                             // gemm_bf16_v1.hip
+        case 2: return bn == 192 ? ak && bk && abi && !split && epi != OBTE_EPI_GELU_BWD         // gemm_bf16_v2.hip
+                                 : (bn == 128 || bn == 256) && ring;
+        case 3: return bn == 256 && ring;
+        case 4: return bn == 128 && ring;
+        case 7: return bn == 256 && !split && ak &&                                            // gemm_bf16_v7.hip: x W^T and dy W
+                       (bk ? epi == OBTE_EPI_NONE || epi == OBTE_EPI_GELU || epi == OBTE_EPI_ADD || epi == OBTE_EPI_ADD_DROPOUT || epi == OBTE_EPI_ROPE_QK
+                           : epi == OBTE_EPI_NONE || epi == OBTE_EPI_GELU_BWD || epi == OBTE_EPI_ROWDOT);
+    }
+    return false;
+}
+
+// Launch one GEMM kernel with SMEM bytes of dynamic LDS; the attribute is set once per kernel (a function-local static: thread-safe).
+// `entry` names the API entry point in the launch-failure error.
+template <auto KERNEL, int SMEM, class P>
+int gemm_launch(int grid, int threads, hipStream_t st, const P& p, const char* entry = "obte_gemm_bf16") {
+    static const hipError_t attr = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+    (void)attr;
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(threads), SMEM, st, p);
+    OBTE_CHECK_LAUNCH(entry);
+    return OBTE_OK;
+}
+
+// Dispatcher: gemm_dispatch<S, BN>(a_kmajor, b_kmajor, epilogue, split, f) calls f(GemmForm<...>{}) with the form named at run time
+// as template arguments, if the capability table lists it; otherwise it reports the missing form.  Only listed forms are instantiated.
+template <bool AK, bool BK, int EPI, bool SPLIT> struct GemmForm {
+    static constexpr bool a_kmajor = AK, b_kmajor = BK, split = SPLIT;
+    static constexpr int epilogue = EPI;
+};
+int gemm_no_form(int s, int bn, bool ak, bool bk, int epi, bool split);   // gemm.cpp: sets the error, returns OBTE_EINVAL
+
+template <int S, int BN, bool AK, bool BK, int EPI, bool SPLIT, class F>
+int gemm_form(F& f) {
+    if constexpr (gemm_has_form(S, BN, AK, BK, EPI, SPLIT)) return f(GemmForm<AK, BK, EPI, SPLIT>{});
+    else return gemm_no_form(S, BN, AK, BK, EPI, SPLIT);
+}
+template <int S, int BN, bool AK, bool BK, class F>
+int gemm_dispatch_epi(int epi, bool split, F& f) {
+    if (split) return gemm_form<S, BN, AK, BK, OBTE_EPI_NONE, true>(f);
+    switch (epi) {
+        case OBTE_EPI_NONE: return gemm_form<S, BN, AK, BK, OBTE_EPI_NONE, false>(f);
+        case OBTE_EPI_GELU: return gemm_form<S, BN, AK, BK, OBTE_EPI_GELU, false>(f);
+        case OBTE_EPI_ADD: return gemm_form<S, BN, AK, BK, OBTE_EPI_ADD, false>(f);
+        case OBTE_EPI_GELU_BWD: return gemm_form<S, BN, AK, BK, OBTE_EPI_GELU_BWD, false>(f);
+        case OBTE_EPI_ADD_DROPOUT: return gemm_form<S, BN, AK, BK, OBTE_EPI_ADD_DROPOUT, false>(f);
+        case OBTE_EPI_ROPE_QK: return gemm_form<S, BN, AK, BK, OBTE_EPI_ROPE_QK, false>(f);
+        case OBTE_EPI_ROWDOT: return gemm_form<S, BN, AK, BK, OBTE_EPI_ROWDOT, false>(f);
+    }
+    return gemm_no_form(S, BN, AK, BK, epi, false);
+}
+template <int S, int BN, class F>
+int gemm_dispatch(bool ak, bool bk, int epi, bool split, F&& f) {
+    if (ak) return bk ? gemm_dispatch_epi<S, BN, true, true>(epi, split, f) : gemm_dispatch_epi<S, BN, true, false>(epi, split, f);
+    return bk ? gemm_dispatch_epi<S, BN, false, true>(epi, split, f) : gemm_dispatch_epi<S, BN, false, false>(epi, split, f);
+}
+
+// Grouped launch (gemm_v3_group_kernel): up to GROUP_MAX problems in one grid of 256 x 256 tiles
+namespace obte_gemm_v2 {
+constexpr int GROUP_MAX = OBTE_GROUP_MAX;   // include/omnibiote_hip.h
+struct GroupParams {
+    GemmParams g[GROUP_MAX];
+    int first_wg[GROUP_MAX + 1];
+    int layout[GROUP_MAX];      // bit 1: A k-contiguous, bit 0: B k-contiguous
+    int n_class0;               // workgroups of class 0 (0: single class)
+};
+}  // namespace obte_gemm_v2
+
+// One launcher per structure: the kernel of the form (a_kmajor, b_kmajor, epilogue, split-K = p.splits > 1) over the grid p describes.
+// gemm.cpp fills the parameters; obte_gemm_v1_launch builds its own kernel's from them.
+int obte_gemm_v1_launch(const obte_gemm_v2::GemmParams& p, bool ak, bool bk, int epi, hipStream_t st);                     // gemm_bf16_v1.hip: 128 x 128
+template <int BN> int obte_gemm_v2_launch(const obte_gemm_v2::GemmParams& p, bool ak, bool bk, int epi, hipStream_t st);   // gemm_bf16_v2.hip: BN = 128, 192, 256
+int obte_gemm_v3_launch(const obte_gemm_v2::GemmParams& p, bool ak, bool bk, int epi, hipStream_t st);
+int obte_gemm_v4_launch(const obte_gemm_v2::GemmParams& p, bool ak, bool bk, int epi, hipStream_t st);
+int obte_gemm_v7_launch(const obte_gemm_v2::GemmParams& p, bool ak, bool bk, int epi, hipStream_t st);                     // gemm_bf16_v7.hip
+int obte_gemm_splitk_reduce(const obte_gemm_v2::GemmParams& p, const bf16* aux, hipStream_t st);   // after a split-K launch: p.d = alpha x the sum of the slabs (+ aux)
+int obte_gemm_group_launch(const obte_gemm_v2::GroupParams& gp, hipStream_t st);

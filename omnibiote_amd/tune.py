@@ -51,7 +51,7 @@ def _time_once(a, b, M, N, K, ak, bk, epi, aux, out, reps=6, rope=None) -> float
 
 
 def v7_applies(M: int, N: int, K: int, epi: int, a_kmajor: bool, b_kmajor: bool) -> bool:
-    """Mirror of obte_gemm_v7_eligible (csrc/gemm_bf16_v7.hip): whole 256 x 256 tiles, one or more per CU, K >= 256, x W^T or dy W
+    """Mirror of structure 7's rule (csrc/gemm.cpp runs_as_given, csrc/gemm_common.h gemm_has_form): whole 256 x 256 tiles, one or more per CU, K >= 256, x W^T or dy W
     with the epilogues it is built for, an output that stays within the Infinity Cache."""
     if not a_kmajor:
         return False

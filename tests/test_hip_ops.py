@@ -849,44 +849,54 @@ def test_gemm_linearity_full_size():
     close(y[rows], ref, atol=0.02, what="full-size rows")
 
 
-def _force_gemm(monkeypatch, bn):
-    """'128' / '256': tile width of the K-tile ring; '256h': the 256-wide half-tile ring (structure 3); '128q': the 128-wide
-    half-tile ring with four waves and two workgroups per CU (structure 4)."""
-    monkeypatch.setenv("OBTE_GEMM_BN", bn[:3])
-    if bn.endswith("h"):
-        monkeypatch.setenv("OBTE_GEMM", "v3")
-    if bn.endswith("q"):
-        monkeypatch.setenv("OBTE_GEMM", "v4")
+# structure and tile width forced through the plan table: the K-tile ring at both widths, the 256-wide half-tile ring (structure 3) and
+# the 128-wide half-tile ring with four waves and two workgroups per CU (structure 4)
+_FORCED = {"128": (2, 128), "256": (2, 256), "256h": (3, 256), "128q": (4, 128)}
 
 
 @pytest.mark.parametrize("bn", ["128", "256", "256h", "128q"])
-def test_gemm_both_tile_widths(monkeypatch, bn):
+def test_gemm_both_tile_widths(bn):
     """Every layout, epilogue and the split-K path on both tile widths and both ring structures (the library picks
-    per shape; here forced)."""
-    _force_gemm(monkeypatch, bn)
-    o = ops()
-    for (M, N, K) in [(520, 392, 256), (256, 256, 128), (300, 1024, 1024)]:
-        x, w = rnd(M, K, seed=41), rnd(N, K, seed=42, scale=0.2)
-        close(o.linear_fwd(x.to(DEV), w.to(DEV)), x.float() @ w.float().t(), atol=0.02 * math.sqrt(K) * 0.2, what=f"NT bn{bn}")
-        dy, w2 = rnd(M, K, seed=43), rnd(K, N, seed=44, scale=0.2)
-        close(o.linear_dgrad(dy.to(DEV), w2.to(DEV)), dy.float() @ w2.float(), atol=0.02 * math.sqrt(K) * 0.2, what=f"NN bn{bn}")
-    for (M, N, K) in [(384, 520, 300), (1024, 1024, 2048), (256, 264, 77)]:
-        dy, xx = rnd(K, M, seed=45, scale=0.5), rnd(K, N, seed=46, scale=0.5)
-        close(o.linear_wgrad(dy.to(DEV), xx.to(DEV)), dy.float().t() @ xx.float(), atol=0.01 * math.sqrt(K), what=f"TN bn{bn}")
-    # identity checks: exact
-    eye = torch.eye(256).to(BF)
-    b = (torch.arange(512 * 256).reshape(512, 256) % 251 - 125).float().to(BF)
-    assert torch.equal(o.linear_fwd(eye.to(DEV), b.to(DEV)).cpu().float(), b.float().t())
-    assert torch.equal(o.linear_dgrad(eye.to(DEV), b.t().contiguous().to(DEV)).cpu().float(), b.float().t())
-    assert torch.equal(o.linear_wgrad(eye.to(DEV), b.t().contiguous().to(DEV)).cpu().float(), b.float().t())
-    # epilogues
-    M, N, K = 300, 512, 128
-    x, w, r = rnd(M, K, seed=7), rnd(N, K, seed=8, scale=0.2), rnd(M, N, seed=9)
-    acc = x.float() @ w.float().t()
-    close(o.linear_fwd(x.to(DEV), w.to(DEV), epilogue=L().EPI_ADD, aux=r.to(DEV)), r.float() + acc.to(BF).float(), atol=0.03, what="add")
-    d, d2 = o.linear_fwd(x.to(DEV), w.to(DEV), epilogue=L().EPI_GELU)
-    close(d2, R.gelu_erf(acc.to(BF).float()), atol=0.03, what="gelu act")
-    close(o.linear_fwd(x.to(DEV), w.to(DEV), alpha=1 / 42.0), acc / 42.0, atol=2e-3, what="alpha")
+    per shape; here forced through the plan table)."""
+    structure, width = _FORCED[bn]
+    o, Lm = ops(), L()
+    lib = Lm.lib()
+    def plan(ak, bk, M, N, K, splits=1, epis=(Lm.EPI_NONE,)):
+        for epi in epis:
+            Lm.check(lib.obte_gemm_plan_set(ak, bk, epi, M, N, K, structure, width, splits), "obte_gemm_plan_set")
+    try:
+        for (M, N, K) in [(520, 392, 256), (256, 256, 128), (300, 1024, 1024)]:
+            splits = 2 if K >= 1024 else 1
+            plan(1, 1, M, N, K, splits)
+            plan(1, 0, M, N, K, splits)
+            x, w = rnd(M, K, seed=41), rnd(N, K, seed=42, scale=0.2)
+            close(o.linear_fwd(x.to(DEV), w.to(DEV)), x.float() @ w.float().t(), atol=0.02 * math.sqrt(K) * 0.2, what=f"NT bn{bn}")
+            dy, w2 = rnd(M, K, seed=43), rnd(K, N, seed=44, scale=0.2)
+            close(o.linear_dgrad(dy.to(DEV), w2.to(DEV)), dy.float() @ w2.float(), atol=0.02 * math.sqrt(K) * 0.2, what=f"NN bn{bn}")
+        for (M, N, K) in [(384, 520, 300), (1024, 1024, 2048), (256, 264, 77)]:
+            dy, xx = rnd(K, M, seed=45, scale=0.5), rnd(K, N, seed=46, scale=0.5)
+            for splits in (1, 4 if K >= 2048 else 2):   # the plain and the split-K form
+                plan(0, 0, M, N, K, splits)
+                close(o.linear_wgrad(dy.to(DEV), xx.to(DEV)), dy.float().t() @ xx.float(), atol=0.01 * math.sqrt(K), what=f"TN bn{bn} splits {splits}")
+        # identity checks: exact
+        for ak, bk in ((1, 1), (1, 0), (0, 0)):
+            plan(ak, bk, 256, 512, 256)
+        eye = torch.eye(256).to(BF)
+        b = (torch.arange(512 * 256).reshape(512, 256) % 251 - 125).float().to(BF)
+        assert torch.equal(o.linear_fwd(eye.to(DEV), b.to(DEV)).cpu().float(), b.float().t())
+        assert torch.equal(o.linear_dgrad(eye.to(DEV), b.t().contiguous().to(DEV)).cpu().float(), b.float().t())
+        assert torch.equal(o.linear_wgrad(eye.to(DEV), b.t().contiguous().to(DEV)).cpu().float(), b.float().t())
+        # epilogues (ADD runs under the NONE plan)
+        M, N, K = 300, 512, 128
+        plan(1, 1, M, N, K, epis=(Lm.EPI_NONE, Lm.EPI_GELU))
+        x, w, r = rnd(M, K, seed=7), rnd(N, K, seed=8, scale=0.2), rnd(M, N, seed=9)
+        acc = x.float() @ w.float().t()
+        close(o.linear_fwd(x.to(DEV), w.to(DEV), epilogue=Lm.EPI_ADD, aux=r.to(DEV)), r.float() + acc.to(BF).float(), atol=0.03, what="add")
+        d, d2 = o.linear_fwd(x.to(DEV), w.to(DEV), epilogue=Lm.EPI_GELU)
+        close(d2, R.gelu_erf(acc.to(BF).float()), atol=0.03, what="gelu act")
+        close(o.linear_fwd(x.to(DEV), w.to(DEV), alpha=1 / 42.0), acc / 42.0, atol=2e-3, what="alpha")
+    finally:
+        Lm.check(lib.obte_gemm_plan_clear(), "obte_gemm_plan_clear")
 
 
 def test_gemm_row_dot_epilogue_forms_the_softmax_backward_delta():
@@ -1218,14 +1228,19 @@ def test_embedding_dropout_fwd_bwd():
 
 
 @pytest.mark.parametrize("bn", ["128", "256", "256h"])
-def test_gemm_residual_dropout_epilogue(monkeypatch, bn):
-    _force_gemm(monkeypatch, bn)
+def test_gemm_residual_dropout_epilogue(bn):
     M, N, K, p = 300, 512, 128, 0.2
+    structure, width = _FORCED[bn]
+    lib = L().lib()
     x, w, r = rnd(M, K, seed=7), rnd(N, K, seed=8, scale=0.2), rnd(M, N, seed=9)
     acc = (x.float() @ w.float().t()).to(BF)
     mask = R.dropout_scale_mask((M, N), p, SEED, 2)
     ref = r.float() + R.dropout_apply(acc, mask).float()
-    got = ops().linear_fwd(x.to(DEV), w.to(DEV), epilogue=L().EPI_ADD_DROPOUT, aux=r.to(DEV), dropout=(p, SEED, 2))
+    L().check(lib.obte_gemm_plan_set(1, 1, L().EPI_ADD_DROPOUT, M, N, K, structure, width, 1), "obte_gemm_plan_set")
+    try:
+        got = ops().linear_fwd(x.to(DEV), w.to(DEV), epilogue=L().EPI_ADD_DROPOUT, aux=r.to(DEV), dropout=(p, SEED, 2))
+    finally:
+        L().check(lib.obte_gemm_plan_clear(), "obte_gemm_plan_clear")
     # the bf16 rounding of acc can differ by an ulp from the fp32 reference matmul: compare with tolerance, but the
     # dropped positions must be exactly the residual
     close(got, ref, atol=0.04, what="residual dropout")

@@ -1,6 +1,8 @@
 """Micro-benchmark of the GEMM entry point on the hot-path shapes (random bf16 data).  Usage:
-    python tools/gemm_bench.py [--reps 20] [--shapes small|all] [--only NAME]
-Prints TFLOP/s per shape (median of reps, HIP events on the launch stream)."""
+    python tools/gemm_bench.py [--reps 20] [--shapes small|all] [--only NAME] [--structure S [--bn BN] [--splits N]]
+Prints TFLOP/s per shape (median of reps, HIP events on the launch stream).  --structure installs the plan (S, BN, N splits) for
+every shape through obte_gemm_plan_set (BN: the structure's width, 256 for structure 2 unless given; N: 1 unless given, and 1 for
+the products whose epilogue has no split-K form)."""
 import argparse
 import os
 import sys
@@ -23,7 +25,7 @@ SHAPES = {
 }
 
 
-def run(name, reps):
+def run(name, reps, structure=0, bn=0, splits=1):
     kind, m, n, k = SHAPES[name]
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)
@@ -33,6 +35,9 @@ def run(name, reps):
     ak, bk = kind.startswith("nt") or kind.startswith("nn"), kind.startswith("nt")
     epi = {"nt": L.EPI_NONE, "nn": L.EPI_NONE, "tn": L.EPI_NONE, "nt_add": L.EPI_ADD, "nt_gelu": L.EPI_GELU, "nn_gelubwd": L.EPI_GELU_BWD}[kind]
     out = torch.empty(m * n, device=dev, dtype=torch.bfloat16)
+    if structure:
+        s = splits if epi in (L.EPI_NONE, L.EPI_ADD) else 1
+        L.check(L.lib().obte_gemm_plan_set(int(ak), int(bk), epi, m, n, k, structure, bn, s), "obte_gemm_plan_set")
     for _ in range(3):
         ops.gemm(a, b, m, n, k, ak, bk, epi, aux, out=out)
     torch.cuda.synchronize()
@@ -53,8 +58,12 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--only", default="")
-    a = ap.parse_args()
+    ap.add_argument("--structure", type=int, default=0, help="force this GEMM structure (1, 2, 3, 4, 7) through the plan table")
+    ap.add_argument("--bn", type=int, default=0, help="its tile width (default: the structure's own; 256 for structure 2)")
+    ap.add_argument("--splits", type=int, default=1, help="its split-K count (epilogue NONE / ADD products only; the others run unsplit)")
+    args = ap.parse_args()
+    bn = args.bn or {1: 128, 4: 128}.get(args.structure, 256)
     for name in SHAPES:
-        if a.only and name not in a.only.split(","):
+        if args.only and name not in args.only.split(","):
             continue
-        run(name, a.reps)
+        run(name, args.reps, args.structure, bn, args.splits)
