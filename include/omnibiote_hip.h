@@ -257,8 +257,8 @@ int obte_mask_bounds(const obte_bf16* mask, int64_t mask_sb, int64_t mask_sh, in
 
 /* ---- token embedding (training/model.py:203,241) ------------------------------------------------------------
  * fwd: out[r,:] = wte[idx[r],:].  bwd: dwte (dense [V,C], fully written) = scatter-add of dout rows, summed in
- * fp32 in a fixed order (deterministic).  order = a stable argsort of idx (int32 [rows]); ws: fp32
- * [2*ceil(rows/32)*C + ...] see obte_embedding_bwd_ws_bytes. */
+ * fp32 in a fixed order (deterministic).  order = a stable argsort of idx (int32 [rows]): obte_token_order below
+ * computes it on the device; ws: fp32 [2*ceil(rows/32)*C + ...] see obte_embedding_bwd_ws_bytes. */
 int obte_embedding_fwd(const int64_t* idx, const obte_bf16* wte, obte_bf16* out, int64_t rows, int cols,
                        int64_t vocab, obte_stream s);
 /* with the embedding dropout of model.py:242 fused (site 0) */
@@ -274,6 +274,30 @@ int obte_embedding_bwd_acc(const int64_t* idx, const int32_t* order, const obte_
 int obte_embedding_bwd_dropout(const int64_t* idx, const int32_t* order, const obte_bf16* dout, obte_bf16* dwte,
                                void* ws, int64_t rows, int cols, int64_t vocab, int accumulate, float p, uint64_t seed,
                                obte_stream s);
+
+/* ---- integer prelude of a step: key ranges and the embedding sort order, from the token ids -----------------------
+ * Both results are integers with one right answer: every launch gives the same bytes, and no atomic decides where
+ * anything lands.  Caller-owned buffers, the caller's stream, no host synchronisation, no allocation.
+ *
+ * Key ranges of the reference's document mask, straight from the token ids (training/train_encoder.py:25-57): what
+ * obte_block_desc.key_ranges and the key_ranges of the attention argument structs take.
+ * ids int64 [B, T] (contiguous); key_ranges int32 [B, T, 2], the [k_start, k_end) of every query.  1 <= B < 2^31,
+ * 1 <= T < 2^24.  padding == 0: the reference appends an EOS column (train_encoder.py:33-37); it is implied, not read.
+ * padding != 0: positions after a row's last EOS (the PAD tail) get the empty range [0, 0); a row without any EOS
+ * attends everywhere.  In every row but the first of a group the first EOS does not advance the block start (the
+ * reference's quirk, train_encoder.py:48-51: the first two documents of such a row share one block).  group > 0: ids
+ * stacks mini-batches of `group` rows each and the exception restarts every `group` rows; group == 0: one group. */
+int obte_key_ranges_from_tokens(const int64_t* ids, int64_t B, int64_t T, int64_t eos_token, int padding, int64_t group,
+                                int32_t* key_ranges, obte_stream s);
+/* order[g, :] = the stable argsort of ids[g, :] for each of `segments` rows of `seg_len` ids (indices local to the
+ * segment, int32 [segments, seg_len]): what obte_embedding_bwd* takes as `order` for that segment.  A radix sort over
+ * the low ceil(log2(vocab) / 8) bytes of the ids, three launches per byte.  ids int64 [segments, seg_len] in [0, vocab)
+ * (an id outside is the caller's error, as for obte_embedding_fwd: it is sorted by its low bytes, nothing faults).
+ * segments >= 1, seg_len >= 1, segments * seg_len < 2^31, 1 <= vocab <= 2^17.  ws: obte_token_order_ws_bytes bytes,
+ * 256-byte aligned, contents irrelevant before and after; the size is 0 for a shape the entry point rejects. */
+int64_t obte_token_order_ws_bytes(int64_t segments, int64_t seg_len, int64_t vocab);
+int obte_token_order(const int64_t* ids, int64_t segments, int64_t seg_len, int64_t vocab, int32_t* order, void* ws,
+                     obte_stream s);
 
 /* ---- masked-LM cross entropy, forward + backward in one pass (training/train_encoder.py:301-305) -------------
  * loss_sum[0] += sum over rows with mlm_mask!=0 of (logsumexp(logits[r]) - logits[r,target[r]]) * row_scale

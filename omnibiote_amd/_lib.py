@@ -106,6 +106,9 @@ SYMBOLS = {
     "obte_embedding_bwd_ws_bytes": (C.c_int64, [C.c_int64, C.c_int]),
     "obte_embedding_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_int64, c_stream]),
     "obte_embedding_bwd_acc": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_int64, C.c_int, c_stream]),
+    "obte_key_ranges_from_tokens": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_void_p, c_stream]),
+    "obte_token_order_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "obte_token_order": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, c_stream]),
     "obte_masked_ce_fwd_bwd": (C.c_int, [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 3 + [C.c_int64, C.c_int64, c_stream]),
     "obte_masked_ce_fwd_bwd_reuse": (C.c_int, [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 2 + [C.c_int64, C.c_int64, c_stream]),
     "obte_rows_gather_bf16": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_int32, c_stream]),

@@ -8,7 +8,9 @@ instead of 2*T — and skip KV tiles outside a workgroup's range.
 ``RangeMask.from_tokens`` is the builder: pure tensor ops on whatever device the tokens live on (no ``nonzero()``,
 no host sync, no Python loop over EOS positions) and reproduces the reference builder's output exactly, including
 its quirk: in every batch row except row 0 the first EOS does not advance the block start (train_encoder.py:48-51),
-so the first two documents of those rows share one block.
+so the first two documents of those rows share one block.  For int64 ids on the GPU it is one HIP launch
+(``obte_key_ranges_from_tokens``, csrc/prelude.hip) that gives the same integers; the tensor-op form serves CPU tensors
+and ``OBTE_PRELUDE_HIP=0``.
 
 One documented difference: positions that the reference leaves fully masked (the PAD tail after the last EOS in
 ``--use_padding`` mode) get the empty range here.  The reference's softmax over an all -1e9 row degenerates to a
@@ -45,6 +47,10 @@ class RangeMask:
         ops for a whole optimizer step's rows instead of one per micro-step."""
         B, T = input_ids.shape
         dev = input_ids.device
+        if input_ids.is_cuda and input_ids.dtype == torch.int64 and input_ids.numel() > 0:
+            from . import ops
+            if ops.prelude_hip():   # one launch (obte_key_ranges_from_tokens) instead of the tensor ops below; same integers
+                return RangeMask(ops.key_ranges_from_tokens(input_ids.contiguous(), eos_token, padding, group))
         is_eos = input_ids == eos_token
         if not padding:  # the reference appends an EOS column (train_encoder.py:33-37)
             is_eos = torch.cat([is_eos, torch.ones(B, 1, dtype=torch.bool, device=dev)], dim=1)

@@ -7,6 +7,7 @@ stream.  Nothing here synchronises the host.  PyTorch is plumbing only: allocati
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -344,8 +345,10 @@ def embedding_bwd(idx, dout, vocab, accumulate_into=None, dropout_p=0.0, dropout
     _need(idx, "idx", torch.int64); _need(dout, "dout")
     rows, Cc = idx.numel(), dout.shape[-1]
     if order is None:
-        # the order is plumbing (a stable sort of <= a few 10k token ids); the summation itself is ours
-        order = torch.sort(idx.reshape(-1), stable=True).indices.to(torch.int32)
+        if prelude_hip():
+            order = token_order(idx.reshape(1, -1), vocab).reshape(-1)
+        else:
+            order = torch.sort(idx.reshape(-1), stable=True).indices.to(torch.int32)
     else:
         _need(order, "order", torch.int32); assert order.numel() == rows
     ws = torch.empty(max(int(L.lib().obte_embedding_bwd_ws_bytes(rows, Cc)), 16), dtype=torch.uint8, device=dout.device)
@@ -358,6 +361,52 @@ def embedding_bwd(idx, dout, vocab, accumulate_into=None, dropout_p=0.0, dropout
     L.check(L.lib().obte_embedding_bwd_dropout(_ptr(idx), _ptr(order), _ptr(dout), _ptr(dwte), _ptr(ws), rows, Cc, vocab, 0,
                                                 float(dropout_p), int(dropout_seed), _stream()), "obte_embedding_bwd")
     return dwte
+
+
+# ------------------------------------------------------------------------------------------------ step prelude
+def prelude_hip() -> bool:
+    """OBTE_PRELUDE_HIP=0: key ranges and the embedding sort order from tensor ops / torch.sort instead of the HIP entry
+    points.  Both forms give the same integers."""
+    return os.environ.get("OBTE_PRELUDE_HIP", "") != "0"
+
+
+def key_ranges_from_tokens(ids, eos_token: int = 3, padding: bool = False, group: int = 0):
+    """int32 (B, T, 2): the [k_start, k_end) of every query under the reference's document mask
+    (masks.RangeMask.from_tokens is the tensor-op form of the same function)."""
+    _need(ids, "ids", torch.int64)
+    if ids.dim() != 2 or ids.numel() == 0:
+        raise RuntimeError(f"ids: expected a non-empty (B, T) tensor, got {tuple(ids.shape)}")
+    B, T = ids.shape
+    out = torch.empty((B, T, 2), dtype=torch.int32, device=ids.device)
+    L.check(L.lib().obte_key_ranges_from_tokens(_ptr(ids), B, T, int(eos_token), 1 if padding else 0, int(group), _ptr(out),
+                                                _stream()), "obte_key_ranges_from_tokens")
+    return out
+
+
+def token_order_workspace(segments: int, seg_len: int, vocab: int, device) -> torch.Tensor:
+    nbytes = int(L.lib().obte_token_order_ws_bytes(segments, seg_len, vocab))
+    if nbytes <= 0:
+        raise RuntimeError(f"token_order: unsupported shape ({segments} x {seg_len} ids, vocab {vocab}): segments * seg_len "
+                           "must be below 2^31 and vocab in 1 .. 2^17")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def token_order(ids_2d, vocab: int, ws: Optional[torch.Tensor] = None):
+    """int32 (segments, seg_len): row g is the stable argsort of ids_2d[g] — the ``order`` of embedding_bwd for that row.
+    ws: a buffer from token_order_workspace for this shape, if the caller keeps one."""
+    _need(ids_2d, "ids", torch.int64)
+    if ids_2d.dim() != 2 or ids_2d.numel() == 0:
+        raise RuntimeError(f"ids: expected a non-empty (segments, seg_len) tensor, got {tuple(ids_2d.shape)}")
+    segments, seg_len = ids_2d.shape
+    if ws is None:
+        ws = token_order_workspace(segments, seg_len, vocab, ids_2d.device)
+    else:
+        _need(ws, "ws", torch.uint8)
+        assert ws.numel() >= int(L.lib().obte_token_order_ws_bytes(segments, seg_len, vocab)) > 0
+    order = torch.empty((segments, seg_len), dtype=torch.int32, device=ids_2d.device)
+    L.check(L.lib().obte_token_order(_ptr(ids_2d), segments, seg_len, int(vocab), _ptr(order), _ptr(ws), _stream()),
+            "obte_token_order")
+    return order
 
 
 # ---------------------------------------------------------------------------------------------- loss, optimizer

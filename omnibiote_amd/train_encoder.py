@@ -222,6 +222,7 @@ class TrainStep:
         self._slot = 0
         self._prev_bwd_done = None
         self._host_bufs = {}
+        self._order_ws = {}
         self._ln_store = None
 
     @staticmethod
@@ -240,6 +241,17 @@ class TrainStep:
         if self._ln_store is None:
             self._ln_store = LnPartialStore()     # this step object's own fp32 LayerNorm partial sums
         return accumulate_grads_inplace(enabled, ln_partial_mode, store=self._ln_store, order=self._order)
+
+    def _token_order_ws(self, segments: int, seg_len: int, vocab: int, dev) -> torch.Tensor:
+        """The workspace of ops.token_order: allocated once per shape and reused (every use is on the caller's stream)."""
+        key = (segments, seg_len, vocab, dev)
+        ws = self._order_ws.get(key)
+        if ws is None:
+            from . import ops
+            if len(self._order_ws) >= 4:           # like _host_bufs: --batch_ramp walks through many row counts
+                self._order_ws.pop(next(iter(self._order_ws)))
+            ws = self._order_ws[key] = ops.token_order_workspace(segments, seg_len, vocab, dev)
+        return ws
 
     def _mask(self, tokens: torch.Tensor, dtype, j: int = -1, k: int = 1):
         from . import masks
@@ -454,7 +466,13 @@ class TrainStep:
         if input_ids.is_cuda and self.loss_impl == "fused" and self.fused_loss_fn is None and hasattr(core_model, "transformer"):
             # the embedding backward sums gradient rows in sorted-token order: ONE segmented sort for all micro-batches of
             # the step instead of a radix sort (four launches) per micro-batch
-            emb_orders = torch.sort(masked_ids.reshape(n_pass, -1), dim=1, stable=True).indices.to(torch.int32)
+            from . import ops
+            if ops.prelude_hip():
+                seg = masked_ids.reshape(n_pass, -1).contiguous()
+                vocab = core_model.transformer.wte.weight.shape[0]
+                emb_orders = ops.token_order(seg, vocab, ws=self._token_order_ws(n_pass, seg.shape[1], vocab, seg.device))
+            else:
+                emb_orders = torch.sort(masked_ids.reshape(n_pass, -1), dim=1, stable=True).indices.to(torch.int32)
         cum_loss = torch.zeros((), dtype=torch.float32, device=input_ids.device)
         from . import masks
         self._all_ranges = masks.RangeMask.from_tokens(input_ids, padding=self.use_padding, group=self.mini).key_ranges

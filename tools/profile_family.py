@@ -8,7 +8,8 @@ FAMILIES = [("gemm", ("gemm_v2_kernel", "gemm_v3_", "gemm_v4_kernel", "gemm_v7_k
             ("attn_fwd", ("attn_fwd_kernel",)),
             ("attn_bwd", ("attn_bwd_", "attn_delta", "attn_dq_reduce")),   # (attn_bwd_prep_kernel, attn_bwd_fused_kernel, the dQ / dK/dV pair)
             ("layernorm", ("ln_",)),
-            ("masked_ce", ("masked_ce",)), ("adamw/sumsq", ("adamw", "sumsq")), ("embedding", ("embed",))]
+            ("masked_ce", ("masked_ce",)), ("adamw/sumsq", ("adamw", "sumsq")), ("embedding", ("embed",)),
+            ("prelude", ("key_ranges_kernel", "token_hist_kernel", "token_scan_kernel", "token_scatter_kernel"))]
 
 
 def main(path):
