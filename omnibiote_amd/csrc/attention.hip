@@ -1297,25 +1297,6 @@ __global__ __launch_bounds__(256) void attn_rows_blocks_kernel(const int32_t* q_
     }
     if (tid == 0) q_blk_off[0] = 0;
 }
-// one wave per row, 16 B per lane per step
-__global__ __launch_bounds__(256) void rows_fill_strided_kernel(const bf16* src, const int32_t* inv, bf16* dst, int64_t total_rows, int64_t ld, int cols) {
-    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (m >= total_rows) return;
-    const int lane = threadIdx.x & 63;
-    const int32_t j = inv[m];
-    for (int c = lane * 8; c < cols; c += 512) {
-        bf16x8 v = {};
-        if (j >= 0) v = *reinterpret_cast<const bf16x8*>(src + (int64_t)j * cols + c);
-        *reinterpret_cast<bf16x8*>(dst + m * ld + c) = v;
-    }
-}
-__global__ __launch_bounds__(256) void rows_gather_strided_kernel(const bf16* src, int64_t ld, const int64_t* rows, bf16* dst, int64_t n_rows, int cols) {
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n_rows) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t r = rows[i];
-    for (int c = lane * 8; c < cols; c += 512) *reinterpret_cast<bf16x8*>(dst + i * cols + c) = *reinterpret_cast<const bf16x8*>(src + r * ld + c);
-}
 }  // namespace
 
 int obte_attn_rows_prep(const int64_t* rows, int64_t n, int64_t B, int64_t T, const int32_t* key_ranges_full, int32_t* q_off, int32_t* q_blk_off,
@@ -1327,18 +1308,6 @@ int obte_attn_rows_prep(const int64_t* rows, int64_t n, int64_t B, int64_t T, co
     OBTE_CHECK_LAUNCH("obte_attn_rows_prep");
     hipLaunchKernelGGL(attn_rows_blocks_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, q_off, q_blk_off, B);
     OBTE_CHECK_LAUNCH("obte_attn_rows_prep(blocks)");
-    return OBTE_OK;
-}
-int obte_rows_fill_strided_bf16(const obte_bf16* src, const int32_t* inv, obte_bf16* dst, int64_t total_rows, int64_t ld, int32_t cols, obte_stream s) {
-    OBTE_REQUIRE(src && inv && dst && total_rows > 0 && cols > 0 && cols % 8 == 0 && ld % 8 == 0 && ld >= cols, "obte_rows_fill_strided_bf16: bad arguments");
-    hipLaunchKernelGGL(rows_fill_strided_kernel, dim3((unsigned)cdiv64(total_rows, 4)), dim3(256), 0, (hipStream_t)s, (const bf16*)src, inv, (bf16*)dst, total_rows, ld, (int)cols);
-    OBTE_CHECK_LAUNCH("obte_rows_fill_strided_bf16");
-    return OBTE_OK;
-}
-int obte_rows_gather_strided_bf16(const obte_bf16* src, int64_t ld, const int64_t* rows, obte_bf16* dst, int64_t n_rows, int32_t cols, obte_stream s) {
-    OBTE_REQUIRE(src && rows && dst && n_rows > 0 && cols > 0 && cols % 8 == 0 && ld % 8 == 0 && ld >= cols, "obte_rows_gather_strided_bf16: bad arguments");
-    hipLaunchKernelGGL(rows_gather_strided_kernel, dim3((unsigned)cdiv64(n_rows, 4)), dim3(256), 0, (hipStream_t)s, (const bf16*)src, ld, rows, (bf16*)dst, n_rows, (int)cols);
-    OBTE_CHECK_LAUNCH("obte_rows_gather_strided_bf16");
     return OBTE_OK;
 }
 

@@ -4,53 +4,99 @@
 //     x1 = x  + c_proj(attn(rope(c_attn(ln_1(x)))))        out = x1 + mlp.c_proj(gelu(c_fc(ln_2(x1))))
 // The residual adds live in the GEMM epilogues, GELU in c_fc's epilogue, GELU' in the mlp.c_proj dgrad epilogue,
 // the residual-gradient adds in the LayerNorm backward kernels, inverse RoPE in the attention backward epilogue.
+//
+// A call takes one of three forms (BlockForm, resolve() below; n = n_out_rows wanted rows, M = B T positions):
+//
+//                  full (out_rows null)               rows, key ranges / no mask            rows, dense mask
+//   c_attn         one product, RoPE in epilogue      k, v thirds on M rows + RoPE pass;    as full
+//                                                     q third on the n rows + RoPE pass
+//   attention      M queries                          n queries (obte_attn_*_rows)          as full, output rows gathered
+//   c_proj, MLP    M rows, dropout in the epilogues   n rows; c_proj's dropout a pass of its own (mask elements (rows[i], c))
+//   backward       dy_attn with the row-dot           c_proj and c_attn's q third on n      c_proj on n rows, d(attention output)
+//                  epilogue; c_attn from the whole    rows, c_attn by thirds; dh1 =         scattered; attention and c_attn as
+//                  dqkv                               [dK dV] W_kv + rows(dQ W_q)           full
+//   weight grads   all four + dh1 in one grouped      each its own launch; the MLP half's two as one pair where n >= 256
+//                  launch where that fills the chip
+//   regions        as named                           y: Q of the rows; x1: the rows' attention output; x1r: ln_1(x) rows, then
+//                                                     x, then x1 of the rows; h2 / hpre before ln_2 / c_fc write them: c_proj
+//                                                     staging and split-K workspace.  Dense mask: y is the full output, x1
+//                                                     its gathered rows, x1r holds x / x1 rows only
+//   workspace      dym / dym2: dy and dx1 under       dyattn: dx1 rows, then ln_1(x) rows (dense mask: then the full d(attention
+//                  their dropout masks                output)); dym: d(attention output) rows, then dQ W_q rows; dym2: masked dx1
+//                                                     rows, then dQ rows
+// The reuses are named members of ActLayout / WsLayout, each with the moment from which its region is free.
 #include "common.h"
 
 namespace {
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~int64_t(255); }
 
+// The activation buffer of one block: typed pointers to its regions, laid out from `base` (null: only `total` means anything).
+// The rows form reuses regions under other roles; every reuse has its NAME here, with the moment from which the region is free.
 struct ActLayout {
-    int64_t mean1, rstd1, h1, qkv, lse, y, x1, mean2, rstd2, h2, hpre, hact, x1r, r_off, r_boff, r_pos, r_kr, r_qb, r_inv, dropbits, total;
+    float *mean1, *rstd1, *lse, *mean2, *rstd2;
+    obte_bf16 *h1, *qkv, *y, *x1, *h2, *hpre, *hact, *x1r;
+    int32_t *r_off, *r_boff, *r_pos, *r_kr, *r_qb, *r_inv;   // the tables of obte_attn_rows_prep (r_inv: written by it, no reader left; it
+                                                              // stays so that neither the buffer's size nor that launch changes)
+    uint32_t* dropbits;
+    int64_t total;
+    obte_bf16* rows_q;          // = y: Q of the wanted rows (the attention's queries are those rows: the full output is never formed)
+    obte_bf16* rows_attn_out;   // = x1: the attention output at the wanted rows, kept for the backward (the full x1 is never formed)
+    obte_bf16* rows_h1;         // = x1r: ln_1(x) at the wanted rows, read by the q product before ...
+    obte_bf16* rows_x1;         // = x1r: ... x, then x1 at the wanted rows (the backward reads it)
+    obte_bf16* proj_stage;      // = h2: the rows' projection before its dropout (ln_2 writes h2 after)
+    void* splitk_ws;            // = hpre: split-K workspace of the rows' q and projection products (c_fc writes hpre after)
+    int64_t splitk_ws_bytes;
     // with_bits: the attention dropout's keep bits (B H ceil(T/32) T words: 134 MB per block at B = 8, T = 4096) are part of the
     // buffer only when dropout is on; they are the LAST region, so every other offset is the same either way
-    ActLayout(int64_t B, int64_t T, int C, int H, bool with_bits = true) {
+    ActLayout(int64_t B, int64_t T, int C, int H, bool with_bits = true, const void* base = nullptr) {
         const int64_t M = B * T;
-        int64_t o = 0;
-        auto take = [&](int64_t bytes) { int64_t r = o; o += align256(bytes); return r; };
-        mean1 = take(M * 4); rstd1 = take(M * 4);
-        h1 = take(M * C * 2);
-        qkv = take(M * 3 * C * 2);
-        lse = take(B * H * T * 4);
-        y = take(M * C * 2);
-        x1 = take(M * C * 2);
-        mean2 = take(M * 4); rstd2 = take(M * 4);
-        h2 = take(M * C * 2);
-        hpre = take(M * 4 * C * 2);
-        hact = take(M * 4 * C * 2);
-        x1r = take(M * C * 2);      // rows form (obte_block_desc::out_rows): x1 at the wanted positions
-        // rows form with the attention's queries at the wanted positions only (rows_attn below): the tables of obte_attn_rows_prep
-        r_off = take((B + 1) * 4); r_boff = take((B + 1) * 4); r_pos = take(M * 4); r_kr = take(M * 8); r_qb = take(M * 8); r_inv = take(M * 4);
-        dropbits = take(with_bits ? obte_attn_drop_bits_bytes(B, T, H) : 0);   // attention dropout: the forward's keep bits for the backward
-        total = o;
+        uintptr_t o = (uintptr_t)base;
+        auto take = [&](int64_t bytes) { void* r = (void*)o; o += align256(bytes); return r; };
+        mean1 = (float*)take(M * 4); rstd1 = (float*)take(M * 4);
+        h1 = (obte_bf16*)take(M * C * 2);
+        qkv = (obte_bf16*)take(M * 3 * C * 2);
+        lse = (float*)take(B * H * T * 4);
+        y = (obte_bf16*)take(M * C * 2); x1 = (obte_bf16*)take(M * C * 2);
+        mean2 = (float*)take(M * 4); rstd2 = (float*)take(M * 4);
+        h2 = (obte_bf16*)take(M * C * 2);
+        hpre = (obte_bf16*)take(M * 4 * C * 2); hact = (obte_bf16*)take(M * 4 * C * 2);
+        x1r = (obte_bf16*)take(M * C * 2);      // rows form (obte_block_desc::out_rows): x1 at the wanted positions
+        r_off = (int32_t*)take((B + 1) * 4); r_boff = (int32_t*)take((B + 1) * 4); r_pos = (int32_t*)take(M * 4);
+        r_kr = (int32_t*)take(M * 8); r_qb = (int32_t*)take(M * 8); r_inv = (int32_t*)take(M * 4);
+        dropbits = (uint32_t*)take(with_bits ? obte_attn_drop_bits_bytes(B, T, H) : 0);   // attention dropout: the forward's keep bits for the backward
+        total = (int64_t)(o - (uintptr_t)base);
+        rows_q = y; rows_attn_out = x1; rows_h1 = rows_x1 = x1r; proj_stage = h2;
+        splitk_ws = hpre; splitk_ws_bytes = M * 4 * C * 2;
     }
 };
 
+// The same for the backward's workspace.
 struct WsLayout {
-    int64_t dhpre, dh, dx1, dyattn, dqkv, delta, lnws, dym, dym2, gemmws, gemmws_bytes, attnws, attnws_bytes, total;
-    WsLayout(int64_t B, int64_t T, int C, int H) {
+    obte_bf16 *dhpre, *dh, *dx1, *dyattn, *dqkv, *dym, *dym2;
+    float *delta, *lnws;
+    void *gemmws, *attnws;   // null where the byte count is 0
+    int64_t gemmws_bytes, attnws_bytes, total;
+    obte_bf16* dx1_rows;          // = dyattn: d x1 at the wanted rows, until the projection's two products have read it; then
+    obte_bf16* h1_rows;           // = dyattn: ln_1(x) at the wanted rows, for dW_q
+    obte_bf16* dy_attn_rows;      // = dym: d(attention output) at the wanted rows (the MLP half's products were dym's last readers; a dense
+                                  //   mask: scattered into dyattn once both of the projection's products have read dx1_rows there); then
+    obte_bf16* dh1_rows;          // = dym: dQ W_q at the wanted rows (the attention backward has read its d_o)
+    obte_bf16* dx1_rows_masked;   // = dym2: d x1 at the wanted rows under the projection's mask, until both products have read it; then
+    obte_bf16* dq_rows;           // = dym2: dQ of the wanted rows
+    WsLayout(int64_t B, int64_t T, int C, int H, void* base = nullptr) {
         const int64_t M = B * T;
-        int64_t o = 0;
-        auto take = [&](int64_t bytes) { int64_t r = o; o += align256(bytes); return r; };
-        dhpre = take(M * 4 * C * 2);
-        dh = take(M * C * 2);       // dh2, later dh1
-        dx1 = take(M * C * 2);
-        dyattn = take(M * C * 2);
-        dqkv = take(M * 3 * C * 2);
-        delta = take(B * H * T * 4);
-        lnws = take((int64_t)obte_layernorm_bwd_ws_rows() * C * 4);
-        dym = take(M * C * 2);      // dropout-masked copies of the two incoming gradients (only touched when dropout_p > 0);
-        dym2 = take(M * C * 2);     // two buffers: both stay live until the grouped weight-gradient launch at the end
+        uintptr_t o = (uintptr_t)base;
+        auto take = [&](int64_t bytes) { void* r = (void*)o; o += align256(bytes); return r; };
+        dhpre = (obte_bf16*)take(M * 4 * C * 2);
+        dh = (obte_bf16*)take(M * C * 2);       // dh2, later dh1
+        dx1 = (obte_bf16*)take(M * C * 2);
+        dyattn = (obte_bf16*)take(M * C * 2);
+        dqkv = (obte_bf16*)take(M * 3 * C * 2);
+        delta = (float*)take(B * H * T * 4);
+        lnws = (float*)take((int64_t)obte_layernorm_bwd_ws_rows() * C * 4);
+        dym = (obte_bf16*)take(M * C * 2);      // dropout-masked copies of the two incoming gradients, dy and dx1 (only touched when dropout_p > 0);
+        dym2 = (obte_bf16*)take(M * C * 2);     // two buffers: both stay live until the grouped weight-gradient launch at the end
         gemmws_bytes = 0;
         const int64_t shapes[4][2] = {{C, 4 * C}, {4 * C, C}, {C, C}, {3 * C, C}};   // the four weight gradients
         for (auto& sh : shapes) {
@@ -60,35 +106,38 @@ struct WsLayout {
         gemmws = take(gemmws_bytes > 0 ? gemmws_bytes : 256);
         attnws_bytes = obte_attn_bwd_ws_bytes(B, T, H, C / H);   // the one-kernel attention backward's dQ contributions (0: not applicable)
         attnws = take(attnws_bytes > 0 ? attnws_bytes : 256);
-        total = o;
+        total = (int64_t)(o - (uintptr_t)base);
+        if (gemmws_bytes == 0) gemmws = nullptr;
+        if (attnws_bytes == 0) attnws = nullptr;
+        dx1_rows = h1_rows = dyattn; dy_attn_rows = dh1_rows = dym; dx1_rows_masked = dq_rows = dym2;
     }
 };
 
-int gemm(const obte_bf16* a, const obte_bf16* b, obte_bf16* d, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
-         int ak, int bk, int epi, const obte_bf16* aux, obte_bf16* d2, obte_stream s, void* ws = nullptr, int64_t ws_bytes = 0,
-         float drop_p = 0.f, uint64_t drop_seed = 0, int drop_site = 0, int64_t ldd = 0) {
+// ---- products of the block: x W^T, dy W and a^T b (row-major operands), the rest of obte_gemm_args set by name at the call ------------
+obte_gemm_args product(const obte_bf16* a, const obte_bf16* b, obte_bf16* out, int64_t m, int64_t n, int64_t k, int ak, int bk) {
     obte_gemm_args g = {};
-    g.a = a; g.b = b; g.d = d; g.aux = aux; g.d2 = d2;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldd = ldd > 0 ? ldd : N;
-    g.a_kmajor = ak; g.b_kmajor = bk; g.epilogue = epi; g.alpha = 1.0f;
-    if (epi == OBTE_EPI_ADD && drop_p > 0.f) {   // residual add with dropout on the projection output
-        g.epilogue = OBTE_EPI_ADD_DROPOUT; g.dropout_p = drop_p; g.dropout_seed = drop_seed; g.dropout_site = drop_site;
-    }
-    return obte_gemm_bf16_ws(&g, ws, ws_bytes, s);
+    g.a = a; g.b = b; g.d = out; g.M = m; g.N = n; g.K = k;
+    g.lda = ak ? k : m; g.ldb = bk ? k : n; g.ldd = n;
+    g.a_kmajor = ak; g.b_kmajor = bk; g.epilogue = OBTE_EPI_NONE; g.alpha = 1.0f;
+    return g;
 }
-
-// The four weight gradients of a block go out as ONE grouped launch (obte_gemm_grouped_bf16) when their 256x256 tiles
-// fill the chip reasonably (>= 70 % of the CU slots of the rounds they need); tiny widths keep the per-matrix split-K
-// launches.  OBTE_GROUPED_WGRAD=0/1 overrides (A/B timing, tests).
-bool use_grouped_wgrad(int C, int64_t M) {
-    const char* e = getenv("OBTE_GROUPED_WGRAD");
-    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1' && M >= 128;
-    if (M < 1024) return false;
-    auto t = [](int64_t m, int64_t n) { return ((m + 255) / 256) * ((n + 255) / 256); };
-    const int64_t tiles = t(C, 4 * C) + t(4 * C, C) + t(C, C) + t(3 * C, C);
-    const int64_t rounds = (tiles + 255) / 256;
-    return tiles * 10 >= rounds * 256 * 7;
+// out[m, n] = x[m, k] w[n, k]^T
+obte_gemm_args xWt(const obte_bf16* x, const obte_bf16* w, obte_bf16* out, int64_t m, int64_t n, int64_t k) { return product(x, w, out, m, n, k, 1, 1); }
+// out[m, n] = dy[m, k] w[k, n]
+obte_gemm_args dyW(const obte_bf16* dy, const obte_bf16* w, obte_bf16* out, int64_t m, int64_t n, int64_t k) { return product(dy, w, out, m, n, k, 1, 0); }
+// dw[m, n] (+)= a[k, m]^T b[k, n]: a weight gradient over k rows, overwritten or accumulated in place
+obte_gemm_args aTb(const obte_bf16* a, const obte_bf16* b, obte_bf16* dw, int64_t m, int64_t n, int64_t k, bool accumulate) {
+    obte_gemm_args g = product(a, b, dw, m, n, k, 0, 0);
+    if (accumulate) { g.epilogue = OBTE_EPI_ADD; g.aux = dw; }
+    return g;
 }
+// out = resid + [dropout under (seed, site)] (the product): the residual adds of the forward
+obte_gemm_args plus_residual(obte_gemm_args g, const obte_bf16* resid, float p = 0.f, uint64_t seed = 0, int site = 0) {
+    g.epilogue = OBTE_EPI_ADD; g.aux = resid;
+    if (p > 0.f) { g.epilogue = OBTE_EPI_ADD_DROPOUT; g.dropout_p = p; g.dropout_seed = seed; g.dropout_site = site; }
+    return g;
+}
+int run(const obte_gemm_args& g, obte_stream s, void* ws = nullptr, int64_t ws_bytes = 0) { return obte_gemm_bf16_ws(&g, ws, ws_bytes, s); }
 
 // dropout sites of one block (csrc/common.h OBTE_SITE_*): 1 attention probabilities, 2 attention c_proj, 3 MLP c_proj
 enum { SITE_RESID = 2, SITE_MLP = 3 };
@@ -109,344 +158,309 @@ int check_desc(const char* who, const obte_block_desc* d) {
 
 #define TRY(x) do { int rc_ = (x); if (rc_ != OBTE_OK) return rc_; } while (0)
 
-// rows form with the attention projection on the wanted rows only (see obte_block_fwd); OBTE_ROWS_PROJ=0 keeps the projection on
-// every row (A/B timing, tests)
-// ... and the attention itself with its QUERIES at the wanted rows only (keys and values of every position; common.h obte_attn_rows):
-// the wanted rows' attention output is all the rest of the block reads.  Key ranges or no mask; OBTE_ROWS_ATTN=0 keeps the full attention.
-// ... and c_attn split by its output thirds: keys and values for every position, queries for the wanted rows only (the same products:
-// W_attn's rows 0 .. C-1 make q, C .. 3C-1 make k and v); RoPE then runs as its own small passes (on the k third by position = row % T,
-// on the gathered q rows by their positions) with the arithmetic of the fused epilogue.  OBTE_ROWS_QSPLIT=0 keeps the whole c_attn.
-bool rows_attn(const obte_block_desc* d);
-bool rows_qsplit(const obte_block_desc* d) {
-    static const bool off = [] { const char* e = getenv("OBTE_ROWS_QSPLIT"); return e && e[0] == '0'; }();
-    return rows_attn(d) && !off;
-}
-bool rows_proj(const obte_block_desc* d);
-bool rows_attn(const obte_block_desc* d) {
-    static const bool off = [] { const char* e = getenv("OBTE_ROWS_ATTN"); return e && e[0] == '0'; }();
-    return rows_proj(d) && d->mask == nullptr && !off;
-}
-bool rows_proj(const obte_block_desc* d) {
-    static const bool off = [] { const char* e = getenv("OBTE_ROWS_PROJ"); return e && e[0] == '0'; }();
-    return d->out_rows != nullptr && !off;
+// ---- the form of one call: every decision of the forward and the backward, taken once ------------------------------------------------
+// The backward reads the regions the forward filled according to these flags, so both start from resolve(d) and derive nothing else.
+struct BlockForm {
+    int64_t M, Mm;     // positions of the block; positions the MLP half and (rows form) the attention projection run on
+    bool drop;         // dropout on
+    bool rows;         // rows form (obte_block_desc::out_rows, the model's last block)
+    bool rows_attn;    // rows form without a dense mask: the attention's queries and c_attn's q third at the wanted rows only
+    bool grouped;      // backward, not the rows form: ONE grouped launch for the four weight gradients and dh1 = dqkv W_attn
+    bool pair_mlp;     // backward, rows form: the MLP half's two weight gradients (K = Mm) as one launch of their own
+};
+
+// The four weight gradients of a block go out as ONE grouped launch (obte_gemm_grouped_bf16) when their 256x256 tiles
+// fill the chip reasonably (>= 70 % of the CU slots of the rounds they need); tiny widths keep the per-matrix split-K
+// launches.  OBTE_GROUPED_WGRAD=0/1 overrides (tests reach both forms at small sizes: read per call).
+bool use_grouped_wgrad(int C, int64_t M) {
+    const char* e = getenv("OBTE_GROUPED_WGRAD");
+    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1' && M >= 128;
+    if (M < 1024) return false;
+    auto t = [](int64_t m, int64_t n) { return ((m + 255) / 256) * ((n + 255) / 256); };
+    const int64_t tiles = t(C, 4 * C) + t(4 * C, C) + t(C, C) + t(3 * C, C);
+    const int64_t rounds = (tiles + 255) / 256;
+    return tiles * 10 >= rounds * 256 * 7;
 }
 
-}  // namespace
-
-extern "C" int64_t obte_block_act_bytes(int64_t B, int64_t T, int32_t n_embd, int32_t n_head) {
-    return ActLayout(B, T, n_embd, n_head).total;
+BlockForm resolve(const obte_block_desc* d) {
+    BlockForm f = {};
+    f.M = d->B * d->T;
+    f.drop = d->dropout_p > 0.f;
+    f.rows = d->out_rows != nullptr;
+    f.Mm = f.rows ? d->n_out_rows : f.M;
+    f.rows_attn = f.rows && d->mask == nullptr;
+    // Rows form: the attention half's two weight gradients and dh1 are an unbalanced group (686 us against ~430 as three launches with
+    // their tuned plans: DESIGN.md 13.4), so each is its own launch; the MLP half's two contract over the Mm wanted rows and pair up
+    // when those are enough for the grouped kernel's K.
+    const bool grouped_ok = use_grouped_wgrad(d->n_embd, f.M);
+    f.grouped = grouped_ok && !f.rows;
+    f.pair_mlp = grouped_ok && f.rows && f.Mm >= 256;
+    return f;
 }
-extern "C" int64_t obte_block_act_bytes_p(int64_t B, int64_t T, int32_t n_embd, int32_t n_head, float dropout_p) {
-    return ActLayout(B, T, n_embd, n_head, dropout_p > 0.f).total;
-}
-extern "C" int64_t obte_block_bwd_ws_bytes(int64_t B, int64_t T, int32_t n_embd, int32_t n_head) {
-    return WsLayout(B, T, n_embd, n_head).total;
-}
 
-extern "C" int obte_block_fwd(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* act, obte_stream s) {
-    TRY(check_desc("obte_block_fwd", d));
-    OBTE_REQUIRE(x && y_out && act, "obte_block_fwd: null pointer");
-    const int C = d->n_embd, H = d->n_head, hs = C / H;
-    const int64_t M = d->B * d->T;
-    const ActLayout L(d->B, d->T, C, H);
-    char* A = (char*)act;
-    float *mean1 = (float*)(A + L.mean1), *rstd1 = (float*)(A + L.rstd1), *mean2 = (float*)(A + L.mean2), *rstd2 = (float*)(A + L.rstd2);
-    obte_bf16 *h1 = (obte_bf16*)(A + L.h1), *qkv = (obte_bf16*)(A + L.qkv), *yat = (obte_bf16*)(A + L.y), *x1 = (obte_bf16*)(A + L.x1),
-              *h2 = (obte_bf16*)(A + L.h2), *hpre = (obte_bf16*)(A + L.hpre), *hact = (obte_bf16*)(A + L.hact);
-    float* lse = (float*)(A + L.lse);
-
-    TRY(obte_layernorm_fwd(x, d->ln1_w, h1, mean1, rstd1, M, C, 1e-5f, s));
-    const bool q_split = rows_qsplit(d);
-    if (q_split) {   // keys and values of every position (the k third rotated in place); the queries follow below, for the wanted rows only
-        TRY(gemm(h1, d->attn_w + (int64_t)C * C, qkv + C, M, 2 * C, C, C, C, 1, 1, OBTE_EPI_NONE, nullptr, nullptr, s, nullptr, 0, 0.f, 0, 0, 3 * (int64_t)C));
-        TRY(obte_rope_cols_bf16(qkv + C, 3 * (int64_t)C, C, d->rope_cos, d->rope_sin, M, d->T, nullptr, hs, s));
-    } else
-    {   // c_attn with RoPE on its q and k thirds fused in the epilogue (model.py:102-108)
-        obte_gemm_args g = {};
-        g.a = h1; g.b = d->attn_w; g.d = qkv;
-        g.M = M; g.N = 3 * C; g.K = C; g.lda = C; g.ldb = C; g.ldd = 3 * C;
-        g.a_kmajor = 1; g.b_kmajor = 1; g.epilogue = OBTE_EPI_ROPE_QK; g.alpha = 1.0f;
-        g.rope_cos = d->rope_cos; g.rope_sin = d->rope_sin; g.rope_T = d->T; g.rope_head_dim = hs;
-        TRY(obte_gemm_bf16(&g, s));
-    }
-    const bool r_attn = rows_attn(d);
+obte_attn_rows attn_rows_tables(const obte_block_desc* d, const ActLayout& a) {
     obte_attn_rows ar = {};
-    if (r_attn) {   // tables of the row set (q_off, positions, the rows' key ranges, the keys' row bounds, inverse index): once per call
-        ar.q_off = (const int32_t*)(A + L.r_off); ar.q_blk_off = (const int32_t*)(A + L.r_boff); ar.q_pos = (const int32_t*)(A + L.r_pos); ar.n = d->n_out_rows;
-        ar.key_ranges = d->key_ranges ? (const int32_t*)(A + L.r_kr) : nullptr;
-        ar.query_bounds = d->key_ranges ? (const int32_t*)(A + L.r_qb) : nullptr;
-        TRY(obte_attn_rows_prep(d->out_rows, d->n_out_rows, d->B, d->T, d->key_ranges, (int32_t*)(A + L.r_off), (int32_t*)(A + L.r_boff), (int32_t*)(A + L.r_pos),
-                                (int32_t*)(A + L.r_kr), (int32_t*)(A + L.r_qb), (int32_t*)(A + L.r_inv), s));
+    ar.q_off = a.r_off; ar.q_blk_off = a.r_boff; ar.q_pos = a.r_pos; ar.n = d->n_out_rows;
+    if (d->key_ranges) { ar.key_ranges = a.r_kr; ar.query_bounds = a.r_qb; }
+    return ar;
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------------------------
+
+// attention with its queries at the wanted rows: q = ln_1(x) W_q^T formed for those rows and rotated at their positions, the output
+// where the projection expects it
+int fwd_attention_rows(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, obte_attn_fwd_args af, obte_stream s) {
+    const int C = d->n_embd;
+    const obte_attn_rows ar = attn_rows_tables(d, a);   // (filled once per call: the backward reads them)
+    TRY(obte_attn_rows_prep(d->out_rows, d->n_out_rows, d->B, d->T, d->key_ranges, a.r_off, a.r_boff, a.r_pos, a.r_kr, a.r_qb, a.r_inv, s));
+    TRY(obte_rows_gather_bf16(a.h1, d->out_rows, a.rows_h1, f.Mm, f.M, C, s));
+    TRY(run(xWt(a.rows_h1, d->attn_w, a.rows_q, f.Mm, C, C), s, a.splitk_ws, a.splitk_ws_bytes));
+    TRY(obte_rope_cols_bf16(a.rows_q, C, C, d->rope_cos, d->rope_sin, f.Mm, d->T, a.r_pos, af.head_dim, s));
+    af.o = a.rows_attn_out;
+    return obte_attn_fwd_rows(&af, &ar, a.rows_q, s);
+}
+
+// ln_1, c_attn with RoPE, attention
+int fwd_attention(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, const obte_bf16* x, obte_stream s) {
+    const int C = d->n_embd, H = d->n_head, hs = C / H;
+    TRY(obte_layernorm_fwd(x, d->ln1_w, a.h1, a.mean1, a.rstd1, f.M, C, 1e-5f, s));
+    if (f.rows_attn) {   // c_attn by its output thirds: W_attn's rows C .. 3C-1 make k and v for every position (the k third rotated in
+                         // place), rows 0 .. C-1 q for the wanted rows; RoPE as its own passes with the arithmetic of the fused epilogue
+        obte_gemm_args g = xWt(a.h1, d->attn_w + (int64_t)C * C, a.qkv + C, f.M, 2 * C, C);
+        g.ldd = 3 * C;
+        TRY(run(g, s));
+        TRY(obte_rope_cols_bf16(a.qkv + C, 3 * (int64_t)C, C, d->rope_cos, d->rope_sin, f.M, d->T, nullptr, hs, s));
+    } else {   // c_attn with RoPE on its q and k thirds fused in the epilogue (model.py:102-108)
+        obte_gemm_args g = xWt(a.h1, d->attn_w, a.qkv, f.M, 3 * C, C);
+        g.epilogue = OBTE_EPI_ROPE_QK; g.rope_cos = d->rope_cos; g.rope_sin = d->rope_sin; g.rope_T = d->T; g.rope_head_dim = hs;
+        TRY(run(g, s));
     }
     obte_attn_fwd_args af = {};
-    af.qkv = qkv; af.o = yat; af.lse = lse; af.key_ranges = d->key_ranges; af.mask = d->mask;
-    af.mask_sb = d->mask_sb; af.mask_sh = d->mask_sh; af.mask_sq = d->mask_sq;
+    af.qkv = a.qkv; af.o = a.y; af.lse = a.lse; af.key_ranges = d->key_ranges; af.mask = d->mask;
+    af.mask_sb = d->mask_sb; af.mask_sh = d->mask_sh; af.mask_sq = d->mask_sq; af.ranges_exact = d->ranges_exact;
     af.B = d->B; af.T = d->T; af.n_head = H; af.head_dim = hs; af.scale = 8.0f / (float)C;  // model.py:119
     af.dropout_p = d->dropout_p; af.dropout_seed = d->dropout_seed;
-    af.drop_bits = (d->dropout_p > 0.f && !r_attn) ? (uint32_t*)(A + L.dropbits) : nullptr;   // (a gathered query set hashes in both passes)
-    if (af.drop_bits) {   // words of key tiles the forward skips (pairs the mask excludes) stay defined whoever reads them
+    if (f.rows_attn) return fwd_attention_rows(d, f, a, af, s);   // (no keep bits: a gathered query set hashes in both passes)
+    if (f.drop) {   // the keep bits for the backward; words of key tiles the forward skips (pairs the mask excludes) stay defined whoever reads them
+        af.drop_bits = a.dropbits;
         if (hipMemsetAsync(af.drop_bits, 0, (size_t)obte_attn_drop_bits_bytes(d->B, d->T, H), (hipStream_t)s) != hipSuccess) {
             obte_set_error("obte_block_fwd: memset of the dropout keep bits failed");
             return OBTE_ELAUNCH;
         }
     }
-    af.ranges_exact = d->ranges_exact;
-    if (r_attn) {   // Q of the wanted rows gathered into the region of the full attention output (not formed in this form); the rows'
-                    // attention output lands where the projection below expects its gathered input: the region of the full x1
-        obte_bf16* qr = yat;
-        if (q_split) {   // q = ln_1(x) W_q^T for the wanted rows, rotated at their positions (ln_1's rows gathered into the region x1r fills later)
-            obte_bf16* h1r = (obte_bf16*)(A + L.x1r);
-            TRY(obte_rows_gather_bf16(h1, d->out_rows, h1r, d->n_out_rows, M, C, s));
-            TRY(gemm(h1r, d->attn_w, qr, d->n_out_rows, C, C, C, C, 1, 1, OBTE_EPI_NONE, nullptr, nullptr, s, (void*)(A + L.hpre), M * 4 * C * 2));
-            TRY(obte_rope_cols_bf16(qr, C, C, d->rope_cos, d->rope_sin, d->n_out_rows, d->T, (const int32_t*)(A + L.r_pos), hs, s));
-        } else {
-            TRY(obte_rows_gather_strided_bf16(qkv, 3 * (int64_t)C, d->out_rows, qr, d->n_out_rows, C, s));
-        }
-        af.o = x1;
-        TRY(obte_attn_fwd_rows(&af, &ar, qr, s));
-    } else {
-        TRY(obte_attn_fwd(&af, s));
+    return obte_attn_fwd(&af, s);
+}
+
+// x1 = x + dropout(y W_proj^T) for the wanted rows alone (per-position arithmetic, same results there): the attention output and the
+// block input gathered
+int fwd_proj_rows(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, const obte_bf16* x, obte_stream s) {
+    const int C = d->n_embd;
+    TRY(obte_rows_gather_bf16(x, d->out_rows, a.rows_x1, f.Mm, f.M, C, s));
+    if (!f.rows_attn) TRY(obte_rows_gather_bf16(a.y, d->out_rows, a.rows_attn_out, f.Mm, f.M, C, s));   // (a dense mask; else the attention wrote the wanted rows there itself)
+    if (f.drop) {   // the mask of site 2 is defined on the whole activation — element (rows[i], c) for gathered row i — so not in the epilogue
+        TRY(run(xWt(a.rows_attn_out, d->proj_w, a.proj_stage, f.Mm, C, C), s, a.splitk_ws, a.splitk_ws_bytes));
+        return obte_dropout_rows_bf16(a.proj_stage, a.rows_x1, a.rows_x1, d->out_rows, f.Mm, C, d->dropout_p, d->dropout_seed, SITE_RESID, s);
     }
-    // the attention projection and the MLP half: on every position, or (rows form) on the n wanted positions only — per-position
-    // arithmetic, same results there.  Rows form without dropout: the projection too runs on the wanted rows (the attention output
-    // and the block input gathered; x1 = x + y W_proj^T formed for those rows alone; the region of the full x1 keeps the gathered
-    // attention output for the backward).  With dropout the projection's mask is defined on whole activations: all rows, then gather.
-    int64_t Mm = M;
-    const obte_bf16* x1m = x1;
-    if (rows_proj(d)) {
-        obte_bf16* x1r = (obte_bf16*)(A + L.x1r);
-        obte_bf16* yr = x1;
-        Mm = d->n_out_rows; x1m = x1r;
-        TRY(obte_rows_gather_bf16(x, d->out_rows, x1r, Mm, M, C, s));
-        if (!r_attn) TRY(obte_rows_gather_bf16(yat, d->out_rows, yr, Mm, M, C, s));   // (rows_attn: the attention wrote the wanted rows there itself)
-        if (d->dropout_p > 0.f) {   // the projection's dropout mask (site 2) is defined on the whole activation: element (rows[i], c) for gathered row i
-            obte_bf16* pr = (obte_bf16*)(A + L.h2);   // (ln_2's output region: written below)
-            TRY(gemm(yr, d->proj_w, pr, Mm, C, C, C, C, 1, 1, OBTE_EPI_NONE, nullptr, nullptr, s, (void*)(A + L.hpre), M * 4 * C * 2));
-            TRY(obte_dropout_rows_bf16(pr, x1r, x1r, d->out_rows, Mm, C, d->dropout_p, d->dropout_seed, SITE_RESID, s));
-        } else {
-            TRY(gemm(yr, d->proj_w, x1r, Mm, C, C, C, C, 1, 1, OBTE_EPI_ADD, x1r, nullptr, s, (void*)(A + L.hpre), M * 4 * C * 2));   // (split-K workspace: the MLP's regions are not written yet)
-        }
-    } else {
-        TRY(gemm(yat, d->proj_w, x1, M, C, C, C, C, 1, 1, OBTE_EPI_ADD, x, nullptr, s, nullptr, 0, d->dropout_p, d->dropout_seed, SITE_RESID));
-        if (d->out_rows) {
-            obte_bf16* x1r = (obte_bf16*)(A + L.x1r);
-            TRY(obte_rows_gather_bf16(x1, d->out_rows, x1r, d->n_out_rows, M, C, s));
-            Mm = d->n_out_rows; x1m = x1r;
-        }
+    return run(plus_residual(xWt(a.rows_attn_out, d->proj_w, a.rows_x1, f.Mm, C, C), a.rows_x1), s, a.splitk_ws, a.splitk_ws_bytes);
+}
+
+// out = x1 + dropout(gelu(ln_2(x1) W_fc^T) W_mlp^T) on the Mm rows of x1m
+int fwd_mlp(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, const obte_bf16* x1m, obte_bf16* y_out, obte_stream s) {
+    const int C = d->n_embd;
+    TRY(obte_layernorm_fwd(x1m, d->ln2_w, a.h2, a.mean2, a.rstd2, f.Mm, C, 1e-5f, s));
+    obte_gemm_args fc = xWt(a.h2, d->fc_w, a.hpre, f.Mm, 4 * C, C);
+    fc.epilogue = OBTE_EPI_GELU; fc.d2 = a.hact;
+    TRY(run(fc, s));
+    // rows form: [Mm, C] over K = 4C is a handful of tiles — split-K, with the tail of the (M-row) hpre region its Mm rows leave unused as workspace
+    const int64_t used = align256(f.Mm * 4 * C * 2);
+    int64_t tail_bytes = f.M * 4 * C * 2 - used;
+    if (!f.rows || tail_bytes < (int64_t)(2 * f.Mm * C * 4)) tail_bytes = 0;
+    void* tail = tail_bytes ? (char*)a.hpre + used : nullptr;
+    return run(plus_residual(xWt(a.hact, d->mlp_w, y_out, f.Mm, C, 4 * C), x1m, d->dropout_p, d->dropout_seed, SITE_MLP), s, tail, tail_bytes);
+}
+
+// ---- backward --------------------------------------------------------------------------------------------------------------------------
+
+struct Grads {   // the caller's six gradient buffers and how they are written
+    obte_bf16 *ln1_w, *attn_w, *proj_w, *ln2_w, *fc_w, *mlp_w;
+    bool acc;      // the four matrices: dW += ... straight into the .grad buffers
+    int acc_ln;    // the two LayerNorm weights likewise
+};
+
+// dx = resid + LN'(dh) over `rows` rows, dw by the descriptor's mode (fp32 partials across micro-batches, or the workspace);
+// masked != null: dropout(dx) under (seed, site) written there as well
+int ln_bwd(const obte_block_desc* d, const Grads& g, const WsLayout& w, const obte_bf16* dh, const obte_bf16* x, const obte_bf16* weight,
+           const float* mean, const float* rstd, const obte_bf16* resid, obte_bf16* dx, obte_bf16* dw, float* partials, int64_t rows,
+           obte_stream s, obte_bf16* masked = nullptr, uint64_t seed = 0, int site = 0) {
+    const int C = d->n_embd, lnp = d->ln_partial_mode;
+    if (masked) return obte_layernorm_bwd_dropout(dh, x, weight, mean, rstd, resid, dx, masked, dw, lnp ? partials : w.lnws, rows, C, lnp, g.acc_ln,
+                                                  d->dropout_p, seed, site, s);
+    if (lnp) return obte_layernorm_bwd_partial(dh, x, weight, mean, rstd, resid, dx, dw, partials, rows, C, lnp, s);
+    return obte_layernorm_bwd_acc(dh, x, weight, mean, rstd, resid, dx, dw, w.lnws, rows, C, g.acc_ln, s);
+}
+
+// out = x1 + dropout(hact W_mlp^T): dhpre, dh2 (in w.dh) and, unless a grouped launch takes them, dW_mlp and dW_fc.
+// *dy_mlp: dy under the (seed, site 3) mask — [Mm, C], element (i, c) of the compact output in the rows form, as in the forward
+int bwd_mlp(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, const WsLayout& w, const Grads& g, const obte_bf16* dy, const obte_bf16** dy_mlp, obte_stream s) {
+    const int C = d->n_embd;
+    *dy_mlp = dy;
+    if (f.drop && d->dy_masked) {   // handed over by the block above: its last LayerNorm backward wrote dropout(dx) under this block's mask
+        *dy_mlp = d->dy_masked;
+    } else if (f.drop) {
+        TRY(obte_dropout_bf16(dy, w.dym, f.Mm * C, C, d->dropout_p, d->dropout_seed, SITE_MLP, s));
+        *dy_mlp = w.dym;
     }
-    TRY(obte_layernorm_fwd(x1m, d->ln2_w, h2, mean2, rstd2, Mm, C, 1e-5f, s));
-    TRY(gemm(h2, d->fc_w, hpre, Mm, 4 * C, C, C, C, 1, 1, OBTE_EPI_GELU, nullptr, hact, s));
-    // rows form: [n, C] over K = 4C is a handful of tiles — split-K, with the unused tail of the (M-row) hpre region as its workspace
-    void* fws = nullptr;
-    int64_t fws_bytes = 0;
-    if (d->out_rows) {
-        const int64_t used = align256(Mm * 4 * C * 2);
-        fws = (void*)(A + L.hpre + used);
-        fws_bytes = M * 4 * C * 2 - used;
-        if (fws_bytes < (int64_t)(2 * Mm * C * 4)) { fws = nullptr; fws_bytes = 0; }
+    obte_gemm_args dgelu = dyW(*dy_mlp, d->mlp_w, w.dhpre, f.Mm, 4 * C, C);   // dhpre = (dy W_mlp) * gelu'(h): hpre holds the derivative
+    dgelu.epilogue = OBTE_EPI_GELU_BWD; dgelu.aux = a.hpre;
+    TRY(run(dgelu, s));
+    const obte_gemm_args dw_mlp = aTb(*dy_mlp, a.hact, g.mlp_w, C, 4 * C, f.Mm, g.acc);   // dW_mlp = dy^T hact
+    const obte_gemm_args dw_fc = aTb(w.dhpre, a.h2, g.fc_w, 4 * C, C, f.Mm, g.acc);       // dW_fc = dhpre^T h2
+    const bool own = !f.grouped && !f.pair_mlp;
+    if (own) TRY(run(dw_mlp, s, w.gemmws, w.gemmws_bytes));
+    TRY(run(dyW(w.dhpre, d->fc_w, w.dh, f.Mm, C, 4 * C), s, f.rows ? w.gemmws : nullptr, f.rows ? w.gemmws_bytes : 0));   // dh2 = dhpre W_fc (rows form: few tiles over K = 4C, split-K)
+    if (own) TRY(run(dw_fc, s, w.gemmws, w.gemmws_bytes));
+    if (f.pair_mlp) {
+        const obte_gemm_args pair[2] = {dw_fc, dw_mlp};
+        TRY(obte_gemm_grouped_bf16(pair, 2, s));
     }
-    TRY(gemm(hact, d->mlp_w, y_out, Mm, C, 4 * C, 4 * C, 4 * C, 1, 1, OBTE_EPI_ADD, x1m, nullptr, s, fws, fws_bytes, d->dropout_p, d->dropout_seed, SITE_MLP));
     return OBTE_OK;
 }
 
-extern "C" int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,
-                                  obte_bf16* dx, obte_bf16* dln1_w, obte_bf16* dattn_w, obte_bf16* dproj_w, obte_bf16* dln2_w,
-                                  obte_bf16* dfc_w, obte_bf16* dmlp_w, int accumulate_matrices, obte_stream s);
+// dx1 = dy + LN2'(dh2), then the attention projection: x1 = x + dropout(y W_proj^T), so it sees dx1 under the (seed, site 2) mask
+// (*dx1_proj) — with dropout on, the LayerNorm backward writes that masked copy beside dx1.  dy_attn = dx1 W_proj goes, where
+// structure 7 takes the shape, with the softmax backward's delta = rowsum(dy_attn o y) formed in its epilogue (*delta_ready; the
+// attention backward's prep launch would otherwise read both tensors again to form it); dW_proj = dx1^T y unless grouped below
+int bwd_ln2_proj_full(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, const WsLayout& w, const Grads& g, const obte_bf16* dy,
+                      const obte_bf16** dx1_proj, bool* delta_ready, obte_stream s) {
+    const int C = d->n_embd;
+    TRY(ln_bwd(d, g, w, w.dh, a.x1, d->ln2_w, a.mean2, a.rstd2, dy, w.dx1, g.ln2_w, d->ln2_partials, f.M, s,
+               f.drop ? w.dym2 : nullptr, d->dropout_seed, SITE_RESID));
+    *dx1_proj = f.drop ? w.dym2 : w.dx1;
+    const obte_gemm_args dgrad = dyW(*dx1_proj, d->proj_w, w.dyattn, f.M, C, C);
+    const int rc = obte_gemm_rowdot_bf16(&dgrad, a.y, w.delta, d->T, C / d->n_head, s);
+    if (rc == OBTE_OK) *delta_ready = true;
+    else if (rc == OBTE_ROWDOT_NOT_TAKEN) TRY(obte_gemm_bf16(&dgrad, s));
+    else return rc;
+    if (!f.grouped) TRY(run(aTb(*dx1_proj, a.y, g.proj_w, C, C, f.M, g.acc), s, w.gemmws, w.gemmws_bytes));
+    return OBTE_OK;
+}
 
-extern "C" int obte_block_bwd(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,
-                              obte_bf16* dx, obte_bf16* dln1_w, obte_bf16* dattn_w, obte_bf16* dproj_w, obte_bf16* dln2_w,
-                              obte_bf16* dfc_w, obte_bf16* dmlp_w, obte_stream s) {
-    return obte_block_bwd_acc(d, x, dy, act, ws, dx, dln1_w, dattn_w, dproj_w, dln2_w, dfc_w, dmlp_w, 0, s);
+// rows form: d x1 at the wanted rows, scattered into zeros for ln_1; the projection's two gradients contract over / are formed for
+// those rows only.  A dense mask: d(attention output) scattered for the full attention backward.
+int bwd_ln2_proj_rows(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, const WsLayout& w, const Grads& g, const obte_bf16* dy, obte_stream s) {
+    const int C = d->n_embd;
+    TRY(ln_bwd(d, g, w, w.dh, a.rows_x1, d->ln2_w, a.mean2, a.rstd2, dy, w.dx1_rows, g.ln2_w, d->ln2_partials, f.Mm, s));
+    TRY(obte_rows_scatter_bf16(w.dx1_rows, d->out_rows, w.dx1, f.Mm, f.M, C, s));
+    const obte_bf16* dxp = w.dx1_rows;
+    if (f.drop) {   // under the projection's mask: element (rows[i], c)
+        TRY(obte_dropout_rows_bf16(w.dx1_rows, nullptr, w.dx1_rows_masked, d->out_rows, f.Mm, C, d->dropout_p, d->dropout_seed, SITE_RESID, s));
+        dxp = w.dx1_rows_masked;
+    }
+    TRY(run(dyW(dxp, d->proj_w, w.dy_attn_rows, f.Mm, C, C), s, w.gemmws, w.gemmws_bytes));
+    TRY(run(aTb(dxp, a.rows_attn_out, g.proj_w, C, C, f.Mm, g.acc), s, w.gemmws, w.gemmws_bytes));   // dW_proj = dx1^T y over the wanted rows
+    if (!f.rows_attn) TRY(obte_rows_scatter_bf16(w.dy_attn_rows, d->out_rows, w.dyattn, f.Mm, f.M, C, s));   // (dx1_rows, in dyattn, has been read by both products)
+    return OBTE_OK;
+}
+
+// attention with the queries at the wanted rows: everything on the query side is the gathered set; then c_attn's backward
+// by thirds: dK / dV of every position against W's k and v rows, dQ of the wanted rows against its q rows
+int bwd_attention_rows(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, const WsLayout& w, const Grads& g, obte_attn_bwd_args ab, obte_stream s) {
+    const int C = d->n_embd;
+    const obte_attn_rows ar = attn_rows_tables(d, a);
+    ab.o = a.rows_attn_out; ab.d_o = w.dy_attn_rows;
+    TRY(obte_attn_bwd_rows(&ab, &ar, a.rows_q, w.dq_rows, s));
+    const obte_bf16* dkv = w.dqkv + C;
+    obte_gemm_args dh1 = dyW(dkv, d->attn_w + (int64_t)C * C, w.dh, f.M, C, 2 * C);   // dh1 = [dK dV] W_kv
+    dh1.lda = 3 * C;
+    TRY(run(dh1, s));
+    TRY(run(dyW(w.dq_rows, d->attn_w, w.dh1_rows, f.Mm, C, C), s, w.gemmws, w.gemmws_bytes));   //       + dQ W_q at the wanted rows
+    TRY(obte_rows_add_bf16(w.dh1_rows, d->out_rows, w.dh, f.Mm, C, s));
+    TRY(obte_rows_gather_bf16(a.h1, d->out_rows, w.h1_rows, f.Mm, f.M, C, s));
+    obte_gemm_args dw_kv = aTb(dkv, a.h1, g.attn_w + (int64_t)C * C, 2 * C, C, f.M, g.acc);   // dW_kv = [dK dV]^T ln_1(x)
+    dw_kv.lda = 3 * C;
+    TRY(run(dw_kv, s, w.gemmws, w.gemmws_bytes));
+    return run(aTb(w.dq_rows, w.h1_rows, g.attn_w, C, C, f.Mm, g.acc), s, w.gemmws, w.gemmws_bytes);   // dW_q = dQ^T ln_1(x) over the wanted rows
+}
+
+// dqkv from d(attention output) (inverse RoPE in the epilogue)
+int bwd_attention(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, const WsLayout& w, const Grads& g, bool delta_ready, obte_stream s) {
+    const int C = d->n_embd, H = d->n_head;
+    obte_attn_bwd_args ab = {};
+    ab.qkv = a.qkv; ab.o = a.y; ab.d_o = w.dyattn; ab.lse = a.lse; ab.delta = w.delta; ab.dqkv = w.dqkv;
+    ab.rope_cos = d->rope_cos; ab.rope_sin = d->rope_sin;
+    ab.key_ranges = d->key_ranges; ab.mask = d->mask; ab.mask_sb = d->mask_sb; ab.mask_sh = d->mask_sh; ab.mask_sq = d->mask_sq;
+    ab.query_bounds = d->query_bounds; ab.ranges_exact = d->ranges_exact;
+    ab.B = d->B; ab.T = d->T; ab.n_head = H; ab.head_dim = C / H; ab.scale = 8.0f / (float)C;
+    ab.dropout_p = d->dropout_p; ab.dropout_seed = d->dropout_seed;
+    ab.drop_bits = (f.drop && !f.rows_attn) ? a.dropbits : nullptr;
+    if (w.attnws) { ab.ws = w.attnws; ab.ws_bytes = w.attnws_bytes; }
+    if (f.rows_attn) return bwd_attention_rows(d, f, a, w, g, ab, s);
+    return delta_ready ? obte_attn_bwd_delta_ready(&ab, s) : obte_attn_bwd(&ab, s);
+}
+
+// c_attn's backward from the whole dqkv (the attention on every position): dh1 = dqkv W_attn and dW_attn = dqkv^T h1 as their own
+// launches, or ONE grid: the block's four weight gradients (K = tokens, full K per tile) and, on the CUs those tiles leave idle, dh1 (K = 3C)
+int bwd_c_attn(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, const WsLayout& w, const Grads& g, const obte_bf16* dy_mlp,
+               const obte_bf16* dx1_proj, obte_stream s) {
+    const int C = d->n_embd;
+    const obte_gemm_args dh1 = dyW(w.dqkv, d->attn_w, w.dh, f.M, C, 3 * C);
+    const obte_gemm_args dw_attn = aTb(w.dqkv, a.h1, g.attn_w, 3 * C, C, f.M, g.acc);
+    if (!f.grouped) {
+        TRY(run(dh1, s));
+        return run(dw_attn, s, w.gemmws, w.gemmws_bytes);
+    }
+    const obte_gemm_args gs[5] = {aTb(w.dhpre, a.h2, g.fc_w, 4 * C, C, f.M, g.acc), aTb(dy_mlp, a.hact, g.mlp_w, C, 4 * C, f.M, g.acc), dw_attn,
+                                  aTb(dx1_proj, a.y, g.proj_w, C, C, f.M, g.acc), dh1};
+    return obte_gemm_grouped_bf16(gs, 5, s);
+}
+
+}  // namespace
+
+extern "C" int64_t obte_block_act_bytes(int64_t B, int64_t T, int32_t n_embd, int32_t n_head) { return ActLayout(B, T, n_embd, n_head).total; }
+extern "C" int64_t obte_block_act_bytes_p(int64_t B, int64_t T, int32_t n_embd, int32_t n_head, float dropout_p) {
+    return ActLayout(B, T, n_embd, n_head, dropout_p > 0.f).total;
+}
+extern "C" int64_t obte_block_bwd_ws_bytes(int64_t B, int64_t T, int32_t n_embd, int32_t n_head) { return WsLayout(B, T, n_embd, n_head).total; }
+
+extern "C" int obte_block_fwd(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* act, obte_stream s) {
+    TRY(check_desc("obte_block_fwd", d));
+    OBTE_REQUIRE(x && y_out && act, "obte_block_fwd: null pointer");
+    const BlockForm f = resolve(d);
+    const ActLayout a(d->B, d->T, d->n_embd, d->n_head, true, act);
+    TRY(fwd_attention(d, f, a, x, s));
+    // the attention projection, x1 = x + dropout(y W_proj^T), and the MLP half: on every position, or (rows form) on the wanted positions only
+    const int C = d->n_embd;
+    if (f.rows) TRY(fwd_proj_rows(d, f, a, x, s));
+    else TRY(run(plus_residual(xWt(a.y, d->proj_w, a.x1, f.M, C, C), x, d->dropout_p, d->dropout_seed, SITE_RESID), s));
+    return fwd_mlp(d, f, a, f.rows ? a.rows_x1 : a.x1, y_out, s);
 }
 
 extern "C" int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,
                                   obte_bf16* dx, obte_bf16* dln1_w, obte_bf16* dattn_w, obte_bf16* dproj_w, obte_bf16* dln2_w,
                                   obte_bf16* dfc_w, obte_bf16* dmlp_w, int accumulate_matrices, obte_stream s) {
-    // accumulate_matrices: bit 0 = the four matrices, bit 1 = the two LayerNorm weights: dW += ... straight into the .grad buffers
-    const int acc_ln = (accumulate_matrices & 2) ? 1 : 0;
-    accumulate_matrices &= 1;
-    const int wepi = accumulate_matrices ? OBTE_EPI_ADD : OBTE_EPI_NONE;
     TRY(check_desc("obte_block_bwd", d));
     OBTE_REQUIRE(x && dy && act && ws && dx && dln1_w && dattn_w && dproj_w && dln2_w && dfc_w && dmlp_w, "obte_block_bwd: null pointer");
-    const int C = d->n_embd, H = d->n_head, hs = C / H;
-    const int64_t M = d->B * d->T;
-    const ActLayout L(d->B, d->T, C, H);
-    const WsLayout W(d->B, d->T, C, H);
-    const char* A = (const char*)act;
-    char* S = (char*)ws;
-    const float *mean1 = (const float*)(A + L.mean1), *rstd1 = (const float*)(A + L.rstd1), *mean2 = (const float*)(A + L.mean2),
-                *rstd2 = (const float*)(A + L.rstd2), *lse = (const float*)(A + L.lse);
-    const obte_bf16 *h1 = (const obte_bf16*)(A + L.h1), *qkv = (const obte_bf16*)(A + L.qkv), *yat = (const obte_bf16*)(A + L.y),
-                    *x1 = (const obte_bf16*)(A + L.x1), *h2 = (const obte_bf16*)(A + L.h2), *hpre = (const obte_bf16*)(A + L.hpre),
-                    *hact = (const obte_bf16*)(A + L.hact);
-    obte_bf16 *dhpre = (obte_bf16*)(S + W.dhpre), *dh = (obte_bf16*)(S + W.dh), *dx1 = (obte_bf16*)(S + W.dx1),
-              *dyattn = (obte_bf16*)(S + W.dyattn), *dqkv = (obte_bf16*)(S + W.dqkv);
-    float *delta = (float*)(S + W.delta), *lnws = (float*)(S + W.lnws);
-    void* gws = W.gemmws_bytes > 0 ? (void*)(S + W.gemmws) : nullptr;
-
-    obte_bf16* dym = (obte_bf16*)(S + W.dym);
-    obte_bf16* dym2 = (obte_bf16*)(S + W.dym2);
-    const bool drop = d->dropout_p > 0.f;
-    // rows form (the model's last block): only the attention half's two weight gradients are left for the grouped launch — 64
-    // tiles of K = M that keep a quarter of the chip busy for the whole launch while the input gradient's 512 short tiles finish on
-    // the rest in a fifth of the time (686 us for what three balanced launches do in ~430: round-5 profile) — so they go out as
-    // their own split-K launches with the tuned plans.  OBTE_GROUPED_LAST=1 restores the grouped form (A/B timing).
-    static const bool grouped_last = [] { const char* e = getenv("OBTE_GROUPED_LAST"); return e && e[0] == '1'; }();
-    const bool grouped_ok = use_grouped_wgrad(C, M);
-    const bool grouped = grouped_ok && (d->out_rows == nullptr || (grouped_last && !rows_proj(d)));   // (the projection on the wanted rows is its own pair of launches)
-    // rows form: the MLP half ran on Mm = n_out_rows positions (dy is [Mm, C]); its two weight gradients contract over those rows
-    // and go out as their own launches, the grouped launch keeps the attention half's
-    const bool rows_form = d->out_rows != nullptr;
-    const bool rows_p = rows_proj(d);   // (implies rows_form, no dropout, and — below — the ungrouped form of the attention half)
-    const bool r_attn = rows_attn(d);   // (implies rows_p: the attention's queries were the wanted rows only)
-    const bool q_split = rows_qsplit(d);   // (implies r_attn: c_attn ran by its output thirds)
-    const int64_t Mm = rows_form ? d->n_out_rows : M;
-    const obte_bf16* x1m = rows_form ? (const obte_bf16*)(A + L.x1r) : x1;
-    const bool grouped_mlp = grouped && !rows_form;
-    // MLP: out = x1 + dropout(hact W_mlp^T): the projection sees dy masked by the same (seed, site 3) mask
-    const obte_bf16* dy_mlp = dy;
-    if (drop && d->dy_masked) {   // handed over by the block above: its last LayerNorm backward wrote dropout(dx) under this block's mask
-        dy_mlp = d->dy_masked;
-    } else if (drop) {   // (rows form: dy and the mask of site 3 are [Mm, C] — element (i, c) of the compact output, as in the forward)
-        TRY(obte_dropout_bf16(dy, dym, Mm * C, C, d->dropout_p, d->dropout_seed, SITE_MLP, s));
-        dy_mlp = dym;
-    }
-    TRY(gemm(dy_mlp, d->mlp_w, dhpre, Mm, 4 * C, C, C, 4 * C, 1, 0, OBTE_EPI_GELU_BWD, hpre, nullptr, s));      // dhpre = (dy W_mlp) * gelu'(h): hpre holds the derivative
-    // rows form with enough rows for the grouped kernel's K: the MLP half's two weight gradients (K = Mm) share one launch below
-    const bool pair_mlp = rows_form && grouped_ok && Mm >= 256;
-    if (!grouped_mlp && !pair_mlp) TRY(gemm(dy_mlp, hact, dmlp_w, C, 4 * C, Mm, C, 4 * C, 0, 0, wepi, accumulate_matrices ? dmlp_w : nullptr, nullptr, s, gws, W.gemmws_bytes));               // dW_mlp = dy^T hact
-    TRY(gemm(dhpre, d->fc_w, dh, Mm, C, 4 * C, 4 * C, C, 1, 0, OBTE_EPI_NONE, nullptr, nullptr, s, rows_form ? gws : nullptr, rows_form ? W.gemmws_bytes : 0));   // dh2 = dhpre W_fc (rows form: few tiles over K = 4C, split-K)
-    if (!grouped_mlp && !pair_mlp) TRY(gemm(dhpre, h2, dfc_w, 4 * C, C, Mm, 4 * C, C, 0, 0, wepi, accumulate_matrices ? dfc_w : nullptr, nullptr, s, gws, W.gemmws_bytes));               // dW_fc = dhpre^T h2
-    if (pair_mlp) {
-        obte_gemm_args gp[2] = {};
-        auto putp = [&](int i, const obte_bf16* a, const obte_bf16* b, obte_bf16* dw, int64_t m, int64_t n) {
-            gp[i].a = a; gp[i].b = b; gp[i].d = dw; gp[i].aux = accumulate_matrices ? dw : nullptr;
-            gp[i].M = m; gp[i].N = n; gp[i].K = Mm; gp[i].lda = m; gp[i].ldb = n; gp[i].ldd = n;
-            gp[i].a_kmajor = 0; gp[i].b_kmajor = 0; gp[i].epilogue = wepi; gp[i].alpha = 1.0f;
-        };
-        putp(0, dhpre, h2, dfc_w, 4 * C, C);
-        putp(1, dy_mlp, hact, dmlp_w, C, 4 * C);
-        TRY(obte_gemm_grouped_bf16(gp, 2, s));
-    }
     const int lnp = d->ln_partial_mode;
-    if (lnp) OBTE_REQUIRE(d->ln1_partials && d->ln2_partials && lnp >= OBTE_LN_PARTIAL_FIRST && lnp <= OBTE_LN_PARTIAL_LAST,
-                          "obte_block_bwd: ln_partial_mode needs both partial buffers and a valid mode");
-    // dx1 = dy + LN2'(dh2); attention: x1 = x + dropout(y W_proj^T), so its projection sees dx1 under the (seed, site 2) mask:
-    // with dropout on, the LayerNorm backward writes that masked copy beside dx1 (it used to be a pass of its own)
-    const obte_bf16* dx1_proj = dx1;
-    if (drop && !rows_form) {
-        TRY(obte_layernorm_bwd_dropout(dh, x1, d->ln2_w, mean2, rstd2, dy, dx1, dym2, dln2_w, lnp ? d->ln2_partials : lnws, M, C, lnp, acc_ln,
-                                       d->dropout_p, d->dropout_seed, SITE_RESID, s));
-        dx1_proj = dym2;
-    } else if (rows_form) {   // d x1 at the wanted rows ([Mm, C], staged in dyattn — free until the projection's input gradient), then scattered into zeros
-        obte_bf16* dx1r = dyattn;
-        if (lnp) TRY(obte_layernorm_bwd_partial(dh, x1m, d->ln2_w, mean2, rstd2, dy, dx1r, dln2_w, d->ln2_partials, Mm, C, lnp, s));
-        else TRY(obte_layernorm_bwd_acc(dh, x1m, d->ln2_w, mean2, rstd2, dy, dx1r, dln2_w, lnws, Mm, C, acc_ln, s));
-        TRY(obte_rows_scatter_bf16(dx1r, d->out_rows, dx1, Mm, M, C, s));
-        if (drop && !rows_p) {   // the attention projection sees d x1 under the (seed, site 2) mask, which is defined on whole activations
-            TRY(obte_dropout_bf16(dx1, dym2, M * C, C, d->dropout_p, d->dropout_seed, SITE_RESID, s));
-            dx1_proj = dym2;
-        }
-        if (rows_p) {   // the projection ran on the wanted rows: its two gradients contract over / are formed for those rows only
-            const obte_bf16* yr = x1;                                   // the gathered attention output (forward)
-            obte_bf16* dyr = dym;                                       // d(attention output) at the wanted rows (dym: the MLP half's products above were its last readers)
-            const obte_bf16* dxp = dx1r;
-            if (drop) {   // d x1 of the wanted rows under the projection's mask (element (rows[i], c)), staged in dym2 (free: dq below is written after)
-                TRY(obte_dropout_rows_bf16(dx1r, nullptr, dym2, d->out_rows, Mm, C, d->dropout_p, d->dropout_seed, SITE_RESID, s));
-                dxp = dym2;
-            }
-            TRY(gemm(dxp, d->proj_w, dyr, Mm, C, C, C, C, 1, 0, OBTE_EPI_NONE, nullptr, nullptr, s, gws, W.gemmws_bytes));
-            TRY(gemm(dxp, yr, dproj_w, C, C, Mm, C, C, 0, 0, wepi, accumulate_matrices ? dproj_w : nullptr, nullptr, s, gws, W.gemmws_bytes));   // dW_proj = dx1^T y over the wanted rows
-            if (!r_attn) TRY(obte_rows_scatter_bf16(dyr, d->out_rows, dyattn, Mm, M, C, s));   // (dx1r, staged in dyattn, has been read by both products; rows_attn: the attention backward takes the gathered rows as they are)
-        }
-    } else if (lnp) {
-        TRY(obte_layernorm_bwd_partial(dh, x1, d->ln2_w, mean2, rstd2, dy, dx1, dln2_w, d->ln2_partials, M, C, lnp, s));
-    } else {
-        TRY(obte_layernorm_bwd_acc(dh, x1, d->ln2_w, mean2, rstd2, dy, dx1, dln2_w, lnws, M, C, acc_ln, s));
-    }
-    bool delta_ready = false;
-    if (!rows_p) {   // dy_attn = dx1 W_proj — where structure 7 takes the shape, with the softmax backward's delta = rowsum(dy_attn o y) formed in
-                     // its epilogue (the attention backward's prep launch would otherwise read both tensors again to form it)
-        obte_gemm_args g = {};
-        g.a = dx1_proj; g.b = d->proj_w; g.d = dyattn; g.M = M; g.N = C; g.K = C; g.lda = C; g.ldb = C; g.ldd = C;
-        g.a_kmajor = 1; g.b_kmajor = 0; g.epilogue = OBTE_EPI_NONE; g.alpha = 1.0f;
-        const int rcd = obte_gemm_rowdot_bf16(&g, yat, delta, d->T, hs, s);
-        if (rcd == OBTE_OK) delta_ready = true;
-        else if (rcd == OBTE_ROWDOT_NOT_TAKEN) TRY(obte_gemm_bf16(&g, s));
-        else return rcd;
-    }
-    if (!grouped && !rows_p) TRY(gemm(dx1_proj, yat, dproj_w, C, C, M, C, C, 0, 0, wepi, accumulate_matrices ? dproj_w : nullptr, nullptr, s, gws, W.gemmws_bytes));                       // dW_proj = dx1^T y
-    obte_attn_bwd_args ab = {};
-    ab.qkv = qkv; ab.o = yat; ab.d_o = dyattn; ab.lse = lse; ab.delta = delta; ab.dqkv = dqkv;
-    ab.rope_cos = d->rope_cos; ab.rope_sin = d->rope_sin;
-    ab.key_ranges = d->key_ranges; ab.mask = d->mask; ab.mask_sb = d->mask_sb; ab.mask_sh = d->mask_sh; ab.mask_sq = d->mask_sq;
-    ab.query_bounds = d->query_bounds;
-    ab.ranges_exact = d->ranges_exact;
-    ab.B = d->B; ab.T = d->T; ab.n_head = H; ab.head_dim = hs; ab.scale = 8.0f / (float)C;
-    ab.dropout_p = d->dropout_p; ab.dropout_seed = d->dropout_seed;
-    ab.drop_bits = (d->dropout_p > 0.f && !r_attn) ? (const uint32_t*)(A + L.dropbits) : nullptr;
-    if (W.attnws_bytes > 0) { ab.ws = (void*)(S + W.attnws); ab.ws_bytes = W.attnws_bytes; }
-    if (r_attn) {   // queries at the wanted rows: everything on the query side is the gathered set (forward: Q rows in the region of the
-                    // full attention output, the rows' output in the region of the full x1; the tables of the row set in the buffer's tail)
-        obte_attn_rows ar = {};
-        ar.q_off = (const int32_t*)(A + L.r_off); ar.q_blk_off = (const int32_t*)(A + L.r_boff); ar.q_pos = (const int32_t*)(A + L.r_pos); ar.n = d->n_out_rows;
-        ar.key_ranges = d->key_ranges ? (const int32_t*)(A + L.r_kr) : nullptr;
-        ar.query_bounds = d->key_ranges ? (const int32_t*)(A + L.r_qb) : nullptr;
-        ab.o = x1; ab.d_o = dym;
-        obte_bf16* dqr = dym2;
-        TRY(obte_attn_bwd_rows(&ab, &ar, yat, dqr, s));
-        if (q_split) {   // c_attn's backward by thirds: dK / dV of every position against W's k and v rows, dQ of the wanted rows against its q rows
-            const obte_bf16* dkv = dqkv + C;
-            const obte_bf16* w_kv = d->attn_w + (int64_t)C * C;
-            obte_bf16* tmp = dym;        // (d(attention output) of the wanted rows has been read by the attention backward)
-            obte_bf16* h1r = dyattn;     // (d x1 of the wanted rows has been read by the projection's products)
-            TRY(gemm(dkv, w_kv, dh, M, C, 2 * C, 3 * (int64_t)C, C, 1, 0, OBTE_EPI_NONE, nullptr, nullptr, s));                                   // dh1 = [dK dV] W_kv
-            TRY(gemm(dqr, d->attn_w, tmp, Mm, C, C, C, C, 1, 0, OBTE_EPI_NONE, nullptr, nullptr, s, gws, W.gemmws_bytes));                         //       + dQ W_q at the wanted rows
-            TRY(obte_rows_add_bf16(tmp, d->out_rows, dh, Mm, C, s));
-            TRY(obte_rows_gather_bf16(h1, d->out_rows, h1r, Mm, M, C, s));
-            obte_bf16* dw_kv = dattn_w + (int64_t)C * C;
-            TRY(gemm(dkv, h1, dw_kv, 2 * C, C, M, 3 * (int64_t)C, C, 0, 0, wepi, accumulate_matrices ? dw_kv : nullptr, nullptr, s, gws, W.gemmws_bytes));   // dW_kv = [dK dV]^T ln_1(x)
-            TRY(gemm(dqr, h1r, dattn_w, C, C, Mm, C, C, 0, 0, wepi, accumulate_matrices ? dattn_w : nullptr, nullptr, s, gws, W.gemmws_bytes));             // dW_q = dQ^T ln_1(x) over the wanted rows
-        } else {
-            TRY(obte_rows_fill_strided_bf16(dqr, (const int32_t*)(A + L.r_inv), dqkv, M, 3 * (int64_t)C, C, s));   // dqkv's q third: the rows' dQ, zeros elsewhere
-        }
-    } else {
-        TRY(delta_ready ? obte_attn_bwd_delta_ready(&ab, s) : obte_attn_bwd(&ab, s));
-    }
-    // OBTE_GROUPED_DGRAD=0 keeps dh1 = dqkv W_attn as its own launch (A/B timing)
-    const char* gd = getenv("OBTE_GROUPED_DGRAD");
-    const bool group_dgrad = grouped && !(gd && gd[0] == '0');
-    if (!group_dgrad && !q_split) TRY(gemm(dqkv, d->attn_w, dh, M, C, 3 * C, 3 * C, C, 1, 0, OBTE_EPI_NONE, nullptr, nullptr, s));             // dh1 = dqkv W_attn
-    if (!grouped && !q_split) TRY(gemm(dqkv, h1, dattn_w, 3 * C, C, M, 3 * C, C, 0, 0, wepi, accumulate_matrices ? dattn_w : nullptr, nullptr, s, gws, W.gemmws_bytes));               // dW_attn = dqkv^T h1
-    if (grouped) {
-        // One grid: dW_fc = dhpre^T h2, dW_mlp = dy^T hact, dW_attn = dqkv^T h1, dW_proj = dx1^T y (K = tokens, full K
-        // per tile) and, on the CUs those tiles leave idle, dh1 = dqkv W_attn (K = 3C).
-        obte_gemm_args gs[5] = {};
-        auto put = [&](int i, const obte_bf16* a, const obte_bf16* b, obte_bf16* dw, int64_t m, int64_t n) {
-            gs[i].a = a; gs[i].b = b; gs[i].d = dw; gs[i].aux = accumulate_matrices ? dw : nullptr;
-            gs[i].M = m; gs[i].N = n; gs[i].K = M; gs[i].lda = m; gs[i].ldb = n; gs[i].ldd = n;
-            gs[i].a_kmajor = 0; gs[i].b_kmajor = 0; gs[i].epilogue = wepi; gs[i].alpha = 1.0f;
-        };
-        int np = 0;
-        if (grouped_mlp) {
-            put(np++, dhpre, h2, dfc_w, 4 * C, C);
-            put(np++, dy_mlp, hact, dmlp_w, C, 4 * C);
-        }
-        put(np++, dqkv, h1, dattn_w, 3 * C, C);
-        put(np++, dx1_proj, yat, dproj_w, C, C);
-        if (group_dgrad) {
-            gs[np].a = dqkv; gs[np].b = d->attn_w; gs[np].d = dh; gs[np].M = M; gs[np].N = C; gs[np].K = 3 * C;
-            gs[np].lda = 3 * C; gs[np].ldb = C; gs[np].ldd = C; gs[np].a_kmajor = 1; gs[np].b_kmajor = 0;
-            gs[np].epilogue = OBTE_EPI_NONE; gs[np].alpha = 1.0f;
-            ++np;
-        }
-        TRY(obte_gemm_grouped_bf16(gs, np, s));
-    }
+    OBTE_REQUIRE(!lnp || (d->ln1_partials && d->ln2_partials && lnp >= OBTE_LN_PARTIAL_FIRST && lnp <= OBTE_LN_PARTIAL_LAST),
+                 "obte_block_bwd: ln_partial_mode needs both partial buffers and a valid mode");
+    // accumulate_matrices: bit 0 = the four matrices, bit 1 = the two LayerNorm weights
+    const Grads g = {dln1_w, dattn_w, dproj_w, dln2_w, dfc_w, dmlp_w, (accumulate_matrices & 1) != 0, (accumulate_matrices & 2) ? 1 : 0};
+    const BlockForm f = resolve(d);
+    const ActLayout a(d->B, d->T, d->n_embd, d->n_head, true, act);   // (only read here)
+    const WsLayout w(d->B, d->T, d->n_embd, d->n_head, ws);
+    const obte_bf16 *dy_mlp = nullptr, *dx1_proj = nullptr;   // the two incoming gradients as their projections see them (under the dropout masks)
+    bool delta_ready = false;   // what obte_gemm_rowdot_bf16 answered: a run-time result, not part of the form
+    TRY(bwd_mlp(d, f, a, w, g, dy, &dy_mlp, s));
+    TRY(f.rows ? bwd_ln2_proj_rows(d, f, a, w, g, dy, s) : bwd_ln2_proj_full(d, f, a, w, g, dy, &dx1_proj, &delta_ready, s));
+    TRY(bwd_attention(d, f, a, w, g, delta_ready, s));
+    if (!f.rows_attn) TRY(bwd_c_attn(d, f, a, w, g, dy_mlp, dx1_proj, s));
     // dx = dx1 + LN1'(dh1); with dropout and a block below, also dropout(dx) under that block's (seed, site 3) mask
-    if (drop && d->dx_masked)
-        TRY(obte_layernorm_bwd_dropout(dh, x, d->ln1_w, mean1, rstd1, dx1, dx, d->dx_masked, dln1_w, lnp ? d->ln1_partials : lnws, M, C, lnp, acc_ln,
-                                       d->dropout_p, d->dx_mask_seed, SITE_MLP, s));
-    else if (lnp) TRY(obte_layernorm_bwd_partial(dh, x, d->ln1_w, mean1, rstd1, dx1, dx, dln1_w, d->ln1_partials, M, C, lnp, s));
-    else TRY(obte_layernorm_bwd_acc(dh, x, d->ln1_w, mean1, rstd1, dx1, dx, dln1_w, lnws, M, C, acc_ln, s));
-    return OBTE_OK;
+    return ln_bwd(d, g, w, w.dh, x, d->ln1_w, a.mean1, a.rstd1, w.dx1, dx, g.ln1_w, d->ln1_partials, f.M, s,
+                  f.drop ? d->dx_masked : nullptr, d->dx_mask_seed, SITE_MLP);
+}
+
+extern "C" int obte_block_bwd(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,
+                              obte_bf16* dx, obte_bf16* dln1_w, obte_bf16* dattn_w, obte_bf16* dproj_w, obte_bf16* dln2_w,
+                              obte_bf16* dfc_w, obte_bf16* dmlp_w, obte_stream s) {
+    return obte_block_bwd_acc(d, x, dy, act, ws, dx, dln1_w, dattn_w, dproj_w, dln2_w, dfc_w, dmlp_w, 0, s);
 }

@@ -62,14 +62,12 @@ struct obte_attn_rows {
     int64_t n;
 };
 // obte_attn_rows_prep fills the five arrays from the ascending row list (global rows b T + position) and the full-size key ranges
-// (null: no mask; the masks are symmetric, SURVEY fact 5: a key's queries are the positions of its own range) and, for the
-// backward's scatter, inv [B T]: the gathered index of every row or -1.
+// (null: no mask; the masks are symmetric, SURVEY fact 5: a key's queries are the positions of its own range) and inv [B T]: the
+// gathered index of every row or -1 (block.cpp ActLayout::r_inv: nothing reads it any more).
 int obte_attn_rows_prep(const int64_t* rows, int64_t n, int64_t B, int64_t T, const int32_t* key_ranges_full, int32_t* q_off, int32_t* q_blk_off,
                         int32_t* q_pos, int32_t* key_ranges_rows, int32_t* query_bounds_rows, int32_t* inv, obte_stream s);
 int obte_attn_fwd_rows(const obte_attn_fwd_args* a, const obte_attn_rows* r, const obte_bf16* q, obte_stream s);   // a->o, a->lse: gathered
 int obte_attn_bwd_rows(const obte_attn_bwd_args* a, const obte_attn_rows* r, const obte_bf16* q, obte_bf16* dq, obte_stream s);   // a->o, d_o, lse, delta: gathered; a->dqkv: dK, dV thirds
-// dst[m, 0:cols] (row stride ld) = src[inv[m]] (cols wide, dense) or zeros where inv[m] < 0; and the strided gather dst[i] = src[rows[i], 0:cols]
-int obte_rows_fill_strided_bf16(const obte_bf16* src, const int32_t* inv, obte_bf16* dst, int64_t total_rows, int64_t ld, int32_t cols, obte_stream s);
 // out[i] = (aux ? aux[i] : 0) + dropout(in[i]) on gathered rows: the mask element of (i, c) is (rows[i], c) of the whole activation
 int obte_dropout_rows_bf16(const obte_bf16* in, const obte_bf16* aux, obte_bf16* out, const int64_t* rows, int64_t n_rows, int32_t cols, float p,
                            uint64_t seed, int32_t site, obte_stream s);
@@ -77,7 +75,6 @@ int obte_dropout_rows_bf16(const obte_bf16* in, const obte_bf16* aux, obte_bf16*
 int obte_rope_cols_bf16(obte_bf16* x, int64_t ld, int32_t ncols, const float* cos_t, const float* sin_t, int64_t rows, int64_t T, const int32_t* pos,
                         int32_t head_dim, obte_stream s);
 int obte_rows_add_bf16(const obte_bf16* src, const int64_t* rows, obte_bf16* dst, int64_t n_rows, int32_t cols, obte_stream s);
-int obte_rows_gather_strided_bf16(const obte_bf16* src, int64_t ld, const int64_t* rows, obte_bf16* dst, int64_t n_rows, int32_t cols, obte_stream s);
 
 // device status word (lib.cpp): pinned host memory kernels OR failure bits into; null if it could not be allocated
 int32_t* obte_status_word();

@@ -771,8 +771,7 @@ def test_block_rows_form_without_a_mask_and_with_whole_sequences_left_out(monkey
     """The rows form's attention runs its QUERIES at the listed positions only (csrc/block.cpp rows_attn; keys and values of every
     position): here without any mask (the kernels' no-mask mode over a gathered query set), with a batch element that has NO listed
     row at all and one whose rows fill more than one 256-query block — against the oracle's full block picked at those rows, and
-    against the same call with the full attention (OBTE_ROWS_ATTN=0 is read once per process, so the comparison is to the oracle and
-    to the HIP full block)."""
+    against the same call with the full attention."""
     B = 3
     hs = C // H
     cfg = R.RefConfig(block_size=T, vocab_size=256, n_layer=1, n_head=H, n_embd=C)
