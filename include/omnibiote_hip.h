@@ -34,8 +34,9 @@ enum {
 
 int obte_abi_version(void);
 const char* obte_last_error(void);
-/* sizeof of the public argument structs in declaration order (gemm, attn_fwd, attn_bwd, mt, block_desc): lets a
- * binding written in another language verify its struct layout at load time.  Returns the number of structs. */
+/* sizeof of the public argument structs (gemm, attn_fwd, attn_bwd, mt, block_desc, mt_master — new structs are appended, an
+ * index never moves): lets a binding written in another language verify its struct layout at load time.  Returns the number
+ * of structs. */
 int obte_struct_sizes(int64_t* out, int cap);
 
 /* ---- device status (failures a kernel detects after it was launched) --------------------------------------------
@@ -361,6 +362,32 @@ int obte_sumsq_multi_bf16_each(const obte_mt_args* t, float* out, obte_stream s)
  * reference's step for step; scalars (1 - lr*wd, lr/bias_correction1, sqrt(bias_correction2)) are formed in double like
  * Python does. */
 int obte_adamw_multi_bf16_ref(const obte_mt_args* t, double beta1, double beta2, double eps, const float* clip_coef, obte_stream s);
+
+/* ---- the same step WITH FP32 STATE: beyond the reference (train_encoder.py:195-199,316 keep bf16 parameters as the only copy
+ * of the weights and bf16 moments; SURVEY fact 7: no fp32 master weights) --------------------------------------------------
+ * The optimizer owns an fp32 master copy of every weight and fp32 moments; the model's bf16 parameter is an output:
+ * p = bf16(master), round to nearest even, written each step and never read.  The arithmetic is torch.optim.AdamW's on fp32
+ * tensors, op for op (obte_adamw_multi_bf16_ref's sequence without its roundings to bf16), on the gradient g * clip_coef[0]
+ * formed in fp32 (clip_coef: device fp32 or NULL = no clipping).  lr and weight_decay travel as doubles; 1 - lr*wd,
+ * lr / bias_correction1, sqrt(bias_correction2), 1 - beta are formed in double and rounded to fp32 once, as Python forms them.
+ * 28 bytes per parameter and step (g, master, m, v read; p, master, m, v written).  Off by default in the harness
+ * (FusedAdamW(master_weights=True), --master_weights). */
+typedef struct {
+    obte_bf16* p[OBTE_MT_MAX]; const obte_bf16* g[OBTE_MT_MAX]; float* master[OBTE_MT_MAX]; float* m[OBTE_MT_MAX]; float* v[OBTE_MT_MAX];
+    int64_t n[OBTE_MT_MAX]; double lr[OBTE_MT_MAX]; double weight_decay[OBTE_MT_MAX]; int32_t step[OBTE_MT_MAX];
+    int32_t count;
+} obte_mt_master_args;
+int obte_adamw_multi_master(const obte_mt_master_args* t, double beta1, double beta2, double eps, const float* clip_coef, obte_stream s);
+/* clip_grad_norm_ (train_encoder.py:316) with a sum that does not depend on workgroup arrival order — what fp32 state needs for
+ * two runs, and two data-parallel replicas, to stay bitwise equal (the atomic forms above differ in the last bits of the fp32
+ * sum from run to run, which the bf16 modes round away).  obte_sumsq_multi_bf16_partials writes ONE fp32 partial per workgroup,
+ * partials[0 .. obte_sumsq_multi_partials_count(t)), no atomics, nothing accumulated: the caller owns the buffer and hands each
+ * launch its own stretch of it.  Only g, n and count of t are read.  The count is negative for an invalid t. */
+int64_t obte_sumsq_multi_partials_count(const obte_mt_args* t);
+int obte_sumsq_multi_bf16_partials(const obte_mt_args* t, float* partials, obte_stream s);
+/* One small launch over the partials of ALL launches, added in index order: out[0] = norm_sq, out[1] = the coefficient
+ * min(1, max_norm / (sqrt(norm_sq) + 1e-6)) (device fp32 [2]); out + 1 is what the step takes as clip_coef. */
+int obte_clip_coef_from_partials(const float* partials, int64_t n_partials, float max_norm, float* out, obte_stream s);
 
 /* ---- whole transformer block (training/model.py:170-181), forward and backward, dropout 0 --------------------
  * One host call enqueues every kernel of the block, so Python crosses the boundary once per block and pass.

@@ -58,6 +58,7 @@ class BlockDesc(C.Structure):
 
 LN_PARTIAL_FIRST, LN_PARTIAL_MORE, LN_PARTIAL_LAST = 1, 2, 3
 MT_MAX = 32
+MT_CHUNK = 16384   # elements one workgroup of a multi-tensor launch serves (csrc/elementwise.hip)
 
 
 class MtArgs(C.Structure):
@@ -65,6 +66,12 @@ class MtArgs(C.Structure):
                 ("n", C.c_int64 * MT_MAX), ("lr", C.c_float * MT_MAX), ("weight_decay", C.c_float * MT_MAX),
                 ("step", C.c_int32 * MT_MAX), ("count", C.c_int32),
                 ("lr64", C.c_double * MT_MAX), ("weight_decay64", C.c_double * MT_MAX)]
+
+
+class MtMasterArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p * MT_MAX), ("g", C.c_void_p * MT_MAX), ("master", C.c_void_p * MT_MAX), ("m", C.c_void_p * MT_MAX),
+                ("v", C.c_void_p * MT_MAX), ("n", C.c_int64 * MT_MAX), ("lr", C.c_double * MT_MAX), ("weight_decay", C.c_double * MT_MAX),
+                ("step", C.c_int32 * MT_MAX), ("count", C.c_int32)]
 
 
 EPI_NONE, EPI_GELU, EPI_ADD, EPI_GELU_BWD, EPI_ADD_DROPOUT, EPI_ROPE_QK = 0, 1, 2, 3, 4, 5
@@ -120,6 +127,10 @@ SYMBOLS = {
     "obte_sumsq_multi_bf16": (C.c_int, [C.POINTER(MtArgs), C.c_void_p, c_stream]),
     "obte_sumsq_multi_bf16_each": (C.c_int, [C.POINTER(MtArgs), C.c_void_p, c_stream]),
     "obte_adamw_multi_bf16_ref": (C.c_int, [C.POINTER(MtArgs), C.c_double, C.c_double, C.c_double, C.c_void_p, c_stream]),
+    "obte_adamw_multi_master": (C.c_int, [C.POINTER(MtMasterArgs), C.c_double, C.c_double, C.c_double, C.c_void_p, c_stream]),
+    "obte_sumsq_multi_partials_count": (C.c_int64, [C.POINTER(MtArgs)]),
+    "obte_sumsq_multi_bf16_partials": (C.c_int, [C.POINTER(MtArgs), C.c_void_p, c_stream]),
+    "obte_clip_coef_from_partials": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, c_stream]),
     "obte_block_act_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "obte_block_act_bytes_p": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_float]),
     "obte_block_bwd_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
@@ -164,7 +175,7 @@ def lib():
                 fn.argtypes = args
             sizes = (C.c_int64 * 8)()
             n = l.obte_struct_sizes(sizes, 8)
-            mine = [C.sizeof(GemmArgs), C.sizeof(AttnFwdArgs), C.sizeof(AttnBwdArgs), C.sizeof(MtArgs), C.sizeof(BlockDesc)]
+            mine = [C.sizeof(GemmArgs), C.sizeof(AttnFwdArgs), C.sizeof(AttnBwdArgs), C.sizeof(MtArgs), C.sizeof(BlockDesc), C.sizeof(MtMasterArgs)]
             if n != len(mine) or list(sizes[:n]) != mine:
                 raise HipLibraryError(f"struct layout mismatch between _lib.py {mine} and {LIB_PATH} {list(sizes[:n])}")
             _lib = l

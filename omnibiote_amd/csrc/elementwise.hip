@@ -600,6 +600,111 @@ int mt_build(const obte_mt_args* a, float beta1, float beta2, MtTable* t, const 
     return blocks;
 }
 
+// ---- fp32 master weights and moments behind the bf16 parameters (beyond the reference: its regime keeps no fp32 state) ----
+// torch.optim.AdamW on fp32 tensors, op for op: adamw_multi_ref_kernel's sequence with every intermediate rounding to bf16
+// removed (same fma placement, contraction off), fed the bf16 gradient scaled by the clip coefficient in fp32.  The bf16
+// parameter is WRITE-ONLY: p = bf16(master), round to nearest even.  Per lane and trip 8 elements: one 16-byte piece of g, two
+// each of master, m and v, all seven loads in front of the first store (vmcnt retires in issue order: a load issued behind a store
+// would wait for it); 28 bytes per parameter and step.
+struct MtMasterTable {
+    bf16* p[OBTE_MT_MAX]; const bf16* g[OBTE_MT_MAX]; float* w[OBTE_MT_MAX]; float* m[OBTE_MT_MAX]; float* v[OBTE_MT_MAX];
+    int64_t n[OBTE_MT_MAX];
+    float decay[OBTE_MT_MAX]; float step_size[OBTE_MT_MAX]; float bc2s[OBTE_MT_MAX];   // formed in double on the host, rounded to fp32 once
+    int first[OBTE_MT_MAX + 1];
+    int count;
+};
+
+__global__ __launch_bounds__(256) void adamw_multi_master_kernel(MtMasterTable t, float b2, float w1, float w2, float eps, const float* __restrict__ clip) {
+#pragma clang fp contract(off)
+    int ti = 0;
+    while (ti + 1 < t.count && (int)blockIdx.x >= t.first[ti + 1]) ++ti;
+    const int64_t base = (int64_t)(blockIdx.x - t.first[ti]) * MT_CHUNK;
+    const int64_t end = min(base + (int64_t)MT_CHUNK, t.n[ti]);
+    const float decay = t.decay[ti], neg_step = -t.step_size[ti], bc2s = t.bc2s[ti];
+    const float cc = clip ? clip[0] : 1.0f;
+    bf16* p = t.p[ti]; const bf16* g = t.g[ti]; float* w = t.w[ti]; float* m = t.m[ti]; float* v = t.v[ti];
+    for (int64_t i = base + threadIdx.x * 8; i < end; i += 256 * 8) {
+        const bf16x8 gg = *reinterpret_cast<const bf16x8*>(g + i);
+        f32x4 ww[2], mm[2], vv[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            ww[h] = *reinterpret_cast<const f32x4*>(w + i + 4 * h);
+            mm[h] = *reinterpret_cast<const f32x4*>(m + i + 4 * h);
+            vv[h] = *reinterpret_cast<const f32x4*>(v + i + 4 * h);
+        }
+        bf16x8 pp;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int h = j >> 2, k = j & 3;
+            const float gj = bf2f(gg[j]) * cc;                    // clip_grad_norm_'s scaling of an fp32 gradient (1.0f without clipping: exact)
+            float pj = ww[h][k] * decay;                          // param.mul_(1 - lr*wd)
+            const float m0 = mm[h][k];
+            const float mj = __builtin_fmaf(w1, gj - m0, m0);     // exp_avg.lerp_(g, 1 - beta1)
+            float vj = vv[h][k] * b2;                             // exp_avg_sq.mul_(beta2)
+            const float wg = w2 * gj;
+            vj = __builtin_fmaf(wg, gj, vj);                      //           .addcmul_(g, g, 1 - beta2)
+            float d = sqrtf(vj);
+            d = d / bc2s;
+            d = d + eps;
+            const float num = neg_step * mj;
+            const float upd = num / d;
+            pj = pj + upd;                                        // param.addcdiv_(exp_avg, denom, -step_size)
+            ww[h][k] = pj; mm[h][k] = mj; vv[h][k] = vj;
+            pp[j] = f2bf(pj);
+        }
+        *reinterpret_cast<bf16x8*>(p + i) = pp;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            *reinterpret_cast<f32x4*>(w + i + 4 * h) = ww[h];
+            *reinterpret_cast<f32x4*>(m + i + 4 * h) = mm[h];
+            *reinterpret_cast<f32x4*>(v + i + 4 * h) = vv[h];
+        }
+    }
+}
+
+// The sum of squares in a FIXED order (sumsq_multi_kernel ends in an atomicAdd: its fp32 sum depends on which workgroup arrives
+// first, invisible behind the bf16 modes' rounding of the coefficient, visible in fp32 state): workgroup b writes ITS partial to
+// partials[b] — 64 squares per lane in order, the wave tree, the four waves in order — and clip_coef_kernel below adds the partials
+// of every launch in index order.  Two runs, and two DDP replicas, then form the same coefficient to the last bit.
+__global__ __launch_bounds__(256) void sumsq_multi_partials_kernel(MtTable t, float* __restrict__ partials) {
+    __shared__ float red[4];
+    const int ti = mt_find(t, blockIdx.x);
+    const int64_t base = (int64_t)(blockIdx.x - t.first[ti]) * MT_CHUNK;
+    const int64_t end = min(base + (int64_t)MT_CHUNK, t.n[ti]);
+    const bf16* g = t.g[ti];
+    float s = 0.f;
+    for (int64_t i = base + threadIdx.x * 8; i < end; i += 256 * 8) {
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(g + i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float f = bf2f(v[j]); s += f * f; }
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// One workgroup: lane l adds partials l, l + 256, ... in that order (in double: this stage then adds no rounding of its own to
+// the 78 * 2^-24 worst case of a partial), the 256 lane sums go through a fixed tree; out[0] = norm_sq, out[1] = the coefficient
+// of clip_grad_norm_ (train_encoder.py:316), min(1, max_norm / (sqrt(norm_sq) + 1e-6)), formed in fp32 as torch forms it.
+__global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ partials, int64_t n, float max_norm, float* __restrict__ out) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) s += (double)partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+#pragma unroll
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm_sq = (float)red[0];
+        out[0] = norm_sq;
+        out[1] = fminf(1.0f, (1.0f / (sqrtf(norm_sq) + 1e-6f)) * max_norm);   // torch: max_norm / tensor is tensor.reciprocal() * max_norm
+    }
+}
+
 inline unsigned stream_grid(int64_t work_items, int per_block) {
     int64_t b = cdiv64(work_items, per_block);
     return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -894,6 +999,54 @@ extern "C" int obte_sumsq_multi_bf16_each(const obte_mt_args* a, float* out, obt
     if (blocks < 0) return blocks;
     hipLaunchKernelGGL(sumsq_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, t, out, 1);
     OBTE_CHECK_LAUNCH("obte_sumsq_multi_bf16_each");
+    return OBTE_OK;
+}
+
+extern "C" int obte_adamw_multi_master(const obte_mt_master_args* a, double beta1, double beta2, double eps, const float* clip_coef, obte_stream s) {
+    const char* who = "obte_adamw_multi_master";
+    OBTE_REQUIRE(a && a->count >= 1 && a->count <= OBTE_MT_MAX, "%s: count must be 1..%d", who, OBTE_MT_MAX);
+    MtMasterTable t;
+    t.count = a->count;
+    int blocks = 0;
+    for (int i = 0; i < a->count; ++i) {
+        OBTE_REQUIRE(a->p[i] && a->g[i] && a->master[i] && a->m[i] && a->v[i], "%s: tensor %d: null pointer", who, i);
+        OBTE_REQUIRE(a->n[i] > 0 && a->n[i] % 8 == 0 && a->step[i] >= 1, "%s: tensor %d: n must be a positive multiple of 8, step >= 1", who, i);
+        t.p[i] = (bf16*)a->p[i]; t.g[i] = (const bf16*)a->g[i]; t.w[i] = a->master[i]; t.m[i] = a->m[i]; t.v[i] = a->v[i];
+        t.n[i] = a->n[i];
+        const double st = (double)a->step[i];   // every scalar in double, rounded to fp32 once: as Python forms them for torch's fp32 kernels
+        t.decay[i] = (float)(1.0 - a->lr[i] * a->weight_decay[i]);
+        t.step_size[i] = (float)(a->lr[i] / (1.0 - pow(beta1, st)));
+        t.bc2s[i] = (float)sqrt(1.0 - pow(beta2, st));
+        t.first[i] = blocks;
+        blocks += (int)cdiv64(a->n[i], MT_CHUNK);
+    }
+    t.first[a->count] = blocks;
+    hipLaunchKernelGGL(adamw_multi_master_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, t, (float)beta2, (float)(1.0 - beta1),
+                       (float)(1.0 - beta2), (float)eps, clip_coef);
+    OBTE_CHECK_LAUNCH(who);
+    return OBTE_OK;
+}
+
+extern "C" int64_t obte_sumsq_multi_partials_count(const obte_mt_args* a) {
+    MtTable t;
+    return mt_build(a, 0.9f, 0.999f, &t, "obte_sumsq_multi_partials_count", false);
+}
+
+extern "C" int obte_sumsq_multi_bf16_partials(const obte_mt_args* a, float* partials, obte_stream s) {
+    OBTE_REQUIRE(partials, "obte_sumsq_multi_bf16_partials: null output");
+    MtTable t;
+    const int blocks = mt_build(a, 0.9f, 0.999f, &t, "obte_sumsq_multi_bf16_partials", false);
+    if (blocks < 0) return blocks;
+    hipLaunchKernelGGL(sumsq_multi_partials_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, t, partials);
+    OBTE_CHECK_LAUNCH("obte_sumsq_multi_bf16_partials");
+    return OBTE_OK;
+}
+
+extern "C" int obte_clip_coef_from_partials(const float* partials, int64_t n_partials, float max_norm, float* out, obte_stream s) {
+    OBTE_REQUIRE(partials && out && n_partials >= 1, "obte_clip_coef_from_partials: null pointer or no partials");
+    OBTE_REQUIRE(max_norm > 0.f, "obte_clip_coef_from_partials: max_norm must be positive (got %g)", (double)max_norm);
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, partials, n_partials, max_norm, out);
+    OBTE_CHECK_LAUNCH("obte_clip_coef_from_partials");
     return OBTE_OK;
 }
 

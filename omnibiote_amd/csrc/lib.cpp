@@ -16,7 +16,7 @@ extern "C" int obte_abi_version(void) { return 1; }
 // sizeof of every public argument struct, in header order, so that a binding can check its own layout
 extern "C" int obte_struct_sizes(int64_t* out, int cap) {
     const int64_t v[] = {(int64_t)sizeof(obte_gemm_args), (int64_t)sizeof(obte_attn_fwd_args), (int64_t)sizeof(obte_attn_bwd_args),
-                         (int64_t)sizeof(obte_mt_args), (int64_t)sizeof(obte_block_desc)};
+                         (int64_t)sizeof(obte_mt_args), (int64_t)sizeof(obte_block_desc), (int64_t)sizeof(obte_mt_master_args)};
     const int n = (int)(sizeof(v) / sizeof(v[0]));
     for (int i = 0; i < n && i < cap; ++i) out[i] = v[i];
     return n;

@@ -21,6 +21,8 @@ Changed on purpose (same mathematics, MI355X-first mechanics):
   * loss: fused CE forward+backward kernel (one pass over the logits); the per-step scalars (loss, token count) are
     reduced with one small device all-reduce instead of two pickled gloo all_gather_object calls (:335,354);
   * clip + AdamW run as fused kernels without a host sync (the clip coefficient stays on the device).
+Added beyond the reference, off by default: ``--master_weights`` — fp32 master weights and fp32 moments behind the bf16 parameters
+(FusedAdamW(master_weights=True)); the masters travel inside the optimizer checkpoint and ``--resume_from`` restores them.
 Data: with ``--base_dir`` pointing at the reference's directory layout (``genbank/train``, ``uniref100/train`` ... of
 ``.npy`` token shards, train_encoder.py:70-99) batches come from ``omnibiote_amd.loader`` (same packing and mixing as the
 reference loader, loader thread + bounded queue, pinned-memory copies on their own stream); otherwise from synthetic rows
@@ -91,20 +93,163 @@ class FusedAdamW(torch.optim.Optimizer):
     """AdamW over bf16 parameters with bf16 moments (the reference's pure-bf16 regime) on the fused HIP kernels.
     ``step(max_norm=...)`` also applies clip_grad_norm_ semantics (train_encoder.py:316) without a host sync: the
     squared norm is accumulated on the device and the coefficient min(1, max_norm/(norm+1e-6)) is consumed by the
-    update kernel directly."""
+    update kernel directly.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, rounding: str = "reference"):
+    ``master_weights=True`` (off by default; NOT the reference's regime, which keeps no fp32 state): the optimizer owns an fp32
+    master copy of every weight and fp32 moments, runs torch.optim.AdamW's fp32 arithmetic on them (obte_adamw_multi_master) and
+    writes ``p = bf16(master)`` each step, so updates smaller than half a bf16 step of the weight are kept instead of rounded
+    away.  The parameters stay bf16: the model, DDP and the checkpoints see what they see without it."""
+
+    _MASTER_KEYS = ("master", "exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, rounding: str = "reference",
+                 master_weights: bool = False):
         """rounding="reference" (default): every tensor op of torch.optim.AdamW's bf16 update is rounded to bf16 exactly
         where the reference's optimizer rounds it (obte_adamw_multi_bf16_ref), so trajectories track the reference's;
-        "single": fp32 arithmetic per element with one rounding per state (more accurate, not the reference's numbers)."""
+        "single": fp32 arithmetic per element with one rounding per state (more accurate, not the reference's numbers).
+        master_weights=True has one arithmetic of its own: rounding must then be left at its default."""
         assert rounding in ("reference", "single")
+        if master_weights and rounding != "reference":
+            raise ValueError("FusedAdamW(master_weights=True) has one arithmetic (torch.optim.AdamW on fp32 state): "
+                             f"leave rounding at its default (got rounding={rounding!r})")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.rounding = rounding
+        self.master_weights = bool(master_weights)
         self._norm_sq = None
+        self._partials = None        # master mode: one fp32 partial sum of squares per workgroup, and [norm_sq, coefficient]
+        self._clip_out = None
+        self._seen_version = {}      # master mode: each parameter's _version as the last step (or load_state_dict) left it
+        self._warned_foreign = False
+
+    # ---- fp32 state through state_dict() / load_state_dict() -----------------------------------------------------------------
+    def load_state_dict(self, state_dict):
+        """torch.optim.Optimizer.load_state_dict casts every floating-point state tensor to the PARAMETER's dtype, which would
+        round the fp32 masters and moments to bf16.  In master mode they are taken from the given state dict as they are (fp32,
+        bit for bit).  A state dict written by the bf16 modes is converted with a warning: moments upcast exactly, masters
+        seeded from the live parameters.  A master-mode state dict is refused by a bf16-mode optimizer (it would drop the
+        masters silently).  The parameters' versions are recorded as they are NOW, so load the model first, as run() does."""
+        import warnings
+        from itertools import chain
+        saved = state_dict["state"]
+        has_master = any(isinstance(v, dict) and "master" in v for v in saved.values())
+        if not self.master_weights:
+            if has_master:
+                raise ValueError("this optimizer state was written with master_weights=True (fp32 master weights and moments); "
+                                 "loading it into FusedAdamW(master_weights=False) would drop the masters: build the optimizer "
+                                 "with master_weights=True (--master_weights)")
+            return super().load_state_dict(state_dict)
+        super().load_state_dict(state_dict)   # validates the groups, restores their hyper-parameters and every step count
+        saved_ids = chain.from_iterable(g["params"] for g in state_dict["param_groups"])
+        params = chain.from_iterable(g["params"] for g in self.param_groups)
+        converted = 0
+        self._seen_version = {}
+        for k, p in zip(saved_ids, params):
+            src = saved.get(k)
+            if not src:
+                continue
+            st = self.state[p]
+            for key in ("exp_avg", "exp_avg_sq"):
+                st[key] = src[key].to(device=p.device, dtype=torch.float32, copy=True)
+            if "master" in src:
+                st["master"] = src["master"].to(device=p.device, dtype=torch.float32, copy=True)
+            else:
+                st["master"] = p.detach().float()
+                converted += 1
+            self._seen_version[p] = p._version
+        if converted:
+            warnings.warn(f"FusedAdamW(master_weights=True): the loaded optimizer state holds no master weights (written by a "
+                          f"bf16 mode): {converted} masters seeded from the current bf16 parameters, moments upcast to fp32")
+
+    def reseed_masters(self, params=None):
+        """Take the masters of `params` (default: all) from the bf16 parameters as they are now.  For writes that torch's version
+        counter does not see (``p.data.copy_(...)``, a kernel writing through a raw pointer): writes through torch proper
+        (``p.copy_`` under no_grad, ``model.load_state_dict``) are noticed by step() itself."""
+        for p in (params if params is not None else [p for g in self.param_groups for p in g["params"]]):
+            st = self.state.get(p)
+            if st and "master" in st:
+                st["master"].copy_(p.detach())
+                self._seen_version[p] = p._version
+
+    def _step_master(self, max_norm, clip_coef):
+        import ctypes as C
+        import warnings
+        from . import _lib as L
+        lib = L.lib()
+        stream = torch.cuda.current_stream().cuda_stream
+        batches, stepped, foreign = [], [], 0   # (MtMasterArgs, MtArgs, betas, eps)
+        for group in self.param_groups:
+            ps = [p for p in group["params"] if p.grad is not None]
+            lr, wd = float(group["lr"]), float(group["weight_decay"])
+            for i in range(0, len(ps), L.MT_MAX):
+                chunk = ps[i:i + L.MT_MAX]
+                a, ga = L.MtMasterArgs(), L.MtArgs()
+                a.count = ga.count = len(chunk)
+                for j, p in enumerate(chunk):
+                    if p.dtype != torch.bfloat16 or p.numel() % 8 or not p.is_cuda:
+                        raise RuntimeError("FusedAdamW needs bf16 GPU parameters with numel % 8 == 0")
+                    st = self.state[p]
+                    if not st:
+                        st["step"] = 0
+                        st["master"] = p.detach().float()
+                        st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32)
+                        st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
+                    elif self._seen_version.get(p) != p._version:
+                        # the kernel writes p through a raw pointer, which does not count as a version: a different one means
+                        # torch wrote the parameter (model.load_state_dict, a manual copy_) and the master no longer stands for it
+                        st["master"].copy_(p.detach())
+                        foreign += 1
+                    st["step"] += 1
+                    a.p[j], a.g[j] = p.data_ptr(), p.grad.data_ptr()
+                    a.master[j], a.m[j], a.v[j] = st["master"].data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+                    a.n[j], a.lr[j], a.weight_decay[j], a.step[j] = p.numel(), lr, wd, st["step"]
+                    ga.g[j], ga.n[j] = a.g[j], a.n[j]
+                stepped.extend(chunk)
+                batches.append((a, ga, group["betas"], group["eps"]))
+        if foreign and not self._warned_foreign:
+            self._warned_foreign = True
+            warnings.warn(f"FusedAdamW(master_weights=True): {foreign} parameters were written outside the optimizer since its last "
+                          "step; their fp32 masters were re-seeded from the bf16 parameters (this warning is given once)")
+        if not batches:
+            return None
+        clip_ptr, norm_sq = None, None
+        if max_norm is not None:
+            # the fixed-order norm: one partial per workgroup, every launch its own stretch, one small kernel adds them in index
+            # order and forms the coefficient on the device (no atomics: two runs and two replicas get the same bits)
+            dev = torch.device("cuda", torch.cuda.current_device())
+            counts = [int(lib.obte_sumsq_multi_partials_count(C.byref(ga))) for _, ga, _, _ in batches]
+            if min(counts) < 0:
+                L.check(min(counts), "obte_sumsq_multi_partials_count")
+            total = sum(counts)
+            if self._partials is None or self._partials.device != dev or self._partials.numel() < total:
+                self._partials = torch.empty(total, dtype=torch.float32, device=dev)
+            if self._clip_out is None or self._clip_out.device != dev:
+                self._clip_out = torch.empty(2, dtype=torch.float32, device=dev)
+            off = 0
+            for (_, ga, _, _), c in zip(batches, counts):
+                L.check(lib.obte_sumsq_multi_bf16_partials(C.byref(ga), self._partials.data_ptr() + 4 * off, stream), "obte_sumsq_multi_bf16_partials")
+                off += c
+            L.check(lib.obte_clip_coef_from_partials(self._partials.data_ptr(), total, float(max_norm), self._clip_out.data_ptr(), stream),
+                    "obte_clip_coef_from_partials")
+            clip_ptr = self._clip_out.data_ptr() + 4
+        elif clip_coef is not None:
+            if clip_coef.dtype != torch.float32 or not clip_coef.is_cuda or clip_coef.numel() != 1:
+                raise ValueError("clip_coef must be one fp32 element on the GPU")
+            clip_ptr = clip_coef.data_ptr()
+        for a, _, (b1, b2), eps in batches:
+            L.check(lib.obte_adamw_multi_master(C.byref(a), b1, b2, eps, clip_ptr, stream), "obte_adamw_multi_master")
+        for p in stepped:
+            self._seen_version[p] = p._version
+        return None if max_norm is None else self._clip_out[0].clone()
 
     @torch.no_grad()
-    def step(self, max_norm: Optional[float] = None):
-        """Multi-tensor launches: <= 32 tensors per kernel (per parameter group, since betas/eps are per group)."""
+    def step(self, max_norm: Optional[float] = None, clip_coef: Optional[torch.Tensor] = None):
+        """Multi-tensor launches: <= 32 tensors per kernel (per parameter group, since betas/eps are per group).
+        clip_coef (master mode only, instead of max_norm): one fp32 element on the device that the update kernel multiplies
+        every gradient by — a coefficient the caller formed."""
+        if clip_coef is not None and (max_norm is not None or not self.master_weights):
+            raise ValueError("clip_coef is for master_weights=True and replaces max_norm")
+        if self.master_weights:
+            return self._step_master(max_norm, clip_coef)
         import ctypes as C
         from . import _lib as L
         from . import ops
@@ -608,8 +753,13 @@ def build_model(args, device, dtype=torch.bfloat16, vocab_size: int = 2 ** 16):
     return m
 
 
-def build_optimizer(model, args, total_iters: int, fused: bool = True):
-    """train_encoder.py:195-201."""
+def build_optimizer(model, args, total_iters: int, fused: bool = True, master_weights: Optional[bool] = None):
+    """train_encoder.py:195-201.  master_weights (default: args.master_weights): fp32 master weights and moments behind the bf16
+    parameters (FusedAdamW(master_weights=True): beyond the reference, off by default)."""
+    if master_weights is None:
+        master_weights = bool(getattr(args, "master_weights", False))
+    if master_weights and not fused:
+        raise ValueError("--master_weights needs the fused HIP optimizer (--device cuda): there is no CPU path for it")
     lr = args.lr * np.sqrt(args.batch_size) / 32
     params = list(model.parameters())
     betas = (args.beta1, args.beta2)
@@ -619,7 +769,7 @@ def build_optimizer(model, args, total_iters: int, fused: bool = True):
         from .mup_compat import mu_param_groups
         groups = mu_param_groups(params, lr, args.weight_decay)
     if fused:
-        opt = FusedAdamW(groups, lr=lr, betas=betas, eps=args.epsilon, weight_decay=args.weight_decay)
+        opt = FusedAdamW(groups, lr=lr, betas=betas, eps=args.epsilon, weight_decay=args.weight_decay, master_weights=master_weights)
     else:
         opt = torch.optim.AdamW(groups, lr=lr, betas=betas, eps=args.epsilon, weight_decay=args.weight_decay)
     sched = torch.optim.lr_scheduler.LinearLR(opt, start_factor=1.0, end_factor=0.0, total_iters=max(total_iters, 1))
@@ -716,6 +866,10 @@ def parse_args(argv=None):
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                    help="torch.distributed backend: nccl (= RCCL over xGMI, the production path) or gloo (plumbing runs: "
                         "BASELINE config 1; gradients then cross the host)")
+    p.add_argument("--master_weights", action="store_true", default=False,
+                   help="fp32 master weights and fp32 moments behind the bf16 parameters (12 instead of 4 bytes of optimizer state per "
+                        "parameter; beyond the reference's pure-bf16 regime, so loss curves no longer track the reference's step for "
+                        "step); they travel in the optimizer checkpoint and --resume_from restores them")
     p.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                    help="cpu only exercises the harness plumbing: the model itself has no CPU path and says so at the first forward")
     return p.parse_args(argv)
