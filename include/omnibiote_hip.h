@@ -124,9 +124,19 @@ enum {
     OBTE_EPI_ROPE_QK = 5,   /* d = packed c_attn output with RoPE applied to its q and k thirds (model.py:102-108): N = 3C,
                                pairs (2j,2j+1) of each head rotated by (rope_cos, rope_sin)[row % rope_T][j], fp32 [T, hs/2];
                                all-zero sin = the reference's cos-only bf16 mode */
-    OBTE_EPI_ADD_DROPOUT = 4 /* d = bf16(aux + dropout(bf16(acc)))   resid_dropout / mlp dropout (model.py:151,167);
+    OBTE_EPI_ADD_DROPOUT = 4, /* d = bf16(aux + dropout(bf16(acc)))   resid_dropout / mlp dropout (model.py:151,167);
                                 element (m,n) is dropout element (row m, col n) of (dropout_seed, dropout_site) */
+    OBTE_EPI_ACC32 = 8      /* the weight-gradient layout only (a_kmajor = b_kmajor = 0, ldd == N): the contribution c = fl32(alpha*acc),
+                               formed before any rounding to bf16, goes into the caller's persistent fp32 [M,N] buffer acc32 by
+                               acc32_mode — OBTE_ACC32_FIRST: acc32 = c; _MORE: acc32 = fl32(acc32 + c); _LAST: the same add, then
+                               d = bf16(acc32).  d is written by _LAST only (it may be NULL otherwise).  The product is rounded before
+                               the add (no fused multiply-add) and split-K slabs are summed in split order first, so the buffer is
+                               defined bit for bit.  Gradient accumulation over micro-batches (train_encoder.py:284-311, autograd's
+                               `grad += new` rounds to bf16 after every micro-batch) with ONE rounding per optimizer step.  (7 is taken
+                               by an internal epilogue.) */
 };
+/* the protocol of a gradient summed in fp32 over the passes of one optimizer step (the values of OBTE_LN_PARTIAL_*) */
+enum { OBTE_ACC32_FIRST = 1, OBTE_ACC32_MORE = 2, OBTE_ACC32_LAST = 3 };
 typedef struct {
     const obte_bf16* a; const obte_bf16* b; obte_bf16* d;
     const obte_bf16* aux;   /* [M,N] ld = ldd, for EPI_ADD / EPI_GELU_BWD */
@@ -138,12 +148,14 @@ typedef struct {
     float alpha;
     float dropout_p; int32_t dropout_site; uint64_t dropout_seed;   /* EPI_ADD_DROPOUT only */
     const float* rope_cos; const float* rope_sin; int64_t rope_T; int32_t rope_head_dim;   /* EPI_ROPE_QK only */
+    float* acc32; int32_t acc32_mode;   /* EPI_ACC32 only: fp32 [M,N] and OBTE_ACC32_*; NULL / 0 with every other epilogue */
 } obte_gemm_args;
 int obte_gemm_bf16(const obte_gemm_args* g, obte_stream s);
 /* Same, with a caller-owned scratch buffer that enables split-K (fp32 partial tiles summed in a fixed order by a
  * second kernel) when the output has too few tiles to fill 256 CUs — the weight-gradient shapes.
  * obte_gemm_workspace_bytes returns the size that lets the library split as it prefers (0 = no split wanted);
- * a NULL or smaller workspace simply disables the split.  Split-K needs epilogue NONE or ADD and ldd == N. */
+ * a NULL or smaller workspace simply disables the split.  Split-K needs epilogue NONE, ADD or ACC32 and ldd == N (ACC32: the
+ * reduce kernel does acc32 (+)= alpha * the sum of the slabs, and the bf16 write of OBTE_ACC32_LAST). */
 int64_t obte_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int obte_gemm_bf16_ws(const obte_gemm_args* g, void* workspace, int64_t workspace_bytes, obte_stream s);
 /* Tuned plans.  The library holds five GEMM structures (variant 1: 128x128 tiles, two workgroups per CU; 2: the K-tile ring,
@@ -154,17 +166,19 @@ int obte_gemm_bf16_ws(const obte_gemm_args* g, void* workspace, int64_t workspac
  * (tile quantisation against 256 CUs, K length, where the operands are served from).  A host-side tuner times the candidates once
  * per (layout, epilogue, M, N, K) and records the winner here; it is also the only way to force a structure.  obte_gemm_plan_set
  * refuses a plan whose structure has no kernel for that tile width, layout, epilogue and split.  A call uses the plan of its shape
- * (ADD, ROPE_QK: else the NONE plan; ADD_DROPOUT: else the ADD plan; else one whose one differing dimension is within 20 %, its
+ * (ADD, ACC32, ROPE_QK: else the NONE plan; ADD_DROPOUT: else the ADD plan; else one whose one differing dimension is within 20 %, its
  * split count trimmed to one round of 256 CUs), or a built-in heuristic on structure 2.  A split-K plan without a workspace that
  * holds it runs the heuristic without split; where a structure cannot run the plan as given it falls back: 7 (edge tiles, fewer
- * tiles than CUs, K < 256, a large output) to 3 at one split; 3 and 4 (fewer than two K-tiles per split) to 2 at the same width. */
+ * tiles than CUs, K < 256, a large output) to 3 at one split; 3 and 4 (fewer than two K-tiles per split) to 2 at the same width.
+ * ACC32 exists on structures 2 (128 and 256 wide), 3 and 4; a plan of structure 1 or 7 borrowed for it runs the heuristic. */
 int obte_gemm_plan_set(int a_kmajor, int b_kmajor, int epilogue, int64_t M, int64_t N, int64_t K, int variant, int bn,
                        int splits);
 int obte_gemm_plan_clear(void);
 
 /* Grouped launch: `count` (1..OBTE_GROUP_MAX) independent GEMMs in a single grid of 256x256 tiles, each tile running its
  * full K (>= 128) — no split-K workspace, no reduce launches.  The problems may MIX layouts (a_kmajor / b_kmajor per
- * problem), alpha and the two admissible epilogues (OBTE_EPI_NONE overwrite, OBTE_EPI_ADD accumulate into aux == d): tiles
+ * problem), alpha and the three admissible epilogues (OBTE_EPI_NONE overwrite, OBTE_EPI_ADD accumulate into aux == d,
+ * OBTE_EPI_ACC32 in the weight-gradient layout: the block's four fp32-summed weight gradients beside a plain dh1): tiles
  * are dealt so that every XCD gets its share of the long-K problems first.  Replaces, in one call, the four weight-gradient
  * products autograd issues for the nn.Linear layers of one block (training/model.py:102,151,163,166 under loss.backward(),
  * train_encoder.py:462: dW_mlp, dW_fc, dW_proj, dW_attn, K = tokens) together with the c_attn input gradient (K = 3C) on
@@ -271,6 +285,15 @@ int obte_embedding_bwd(const int64_t* idx, const int32_t* order, const obte_bf16
 /* accumulate != 0: dwte holds an existing gradient; only the touched rows are read-modified-written (no memset). */
 int obte_embedding_bwd_acc(const int64_t* idx, const int32_t* order, const obte_bf16* dout, obte_bf16* dwte,
                            void* ws, int64_t rows, int cols, int64_t vocab, int accumulate, obte_stream s);
+/* The same scatter-add into a persistent fp32 [vocab, cols] buffer over the passes of one optimizer step (OBTE_ACC32_*; p = 0: no
+ * dropout): the rows' fp32 sums go into acc32 before any rounding.  FIRST zeroes the buffer, then stores the touched rows; MORE
+ * adds into the touched rows; LAST adds, then dwte = bf16(acc32) over the whole buffer.  dwte is written by LAST only (NULL else). */
+int obte_embedding_bwd_acc32(const int64_t* idx, const int32_t* order, const obte_bf16* dout, float* acc32, obte_bf16* dwte,
+                             void* ws, int64_t rows, int cols, int64_t vocab, int mode, float p, uint64_t seed, obte_stream s);
+/* acc32 (+)= src elementwise by mode (OBTE_ACC32_*; FIRST: acc32 = src), src == NULL: a zero contribution; LAST: then
+ * out = bf16(acc32) (out is not read or written otherwise).  n % 8 == 0.  The form for a gradient the fused epilogues cannot
+ * take, the embedding's final conversion, and the flush of a weight whose backward node did not run in a pass. */
+int obte_acc32_add_bf16(float* acc32, const obte_bf16* src, obte_bf16* out, int64_t n, int mode, obte_stream s);
 /* dout is the gradient of the DROPPED embedding output: the same mask (p, seed, site 0) is re-applied while summing */
 int obte_embedding_bwd_dropout(const int64_t* idx, const int32_t* order, const obte_bf16* dout, obte_bf16* dwte,
                                void* ws, int64_t rows, int cols, int64_t vocab, int accumulate, float p, uint64_t seed,
@@ -424,6 +447,10 @@ typedef struct {
      *   dy_masked      in : dropout(dy) under this block's (dropout_seed, site 3) mask, same shape as dy (NULL: computed here);
      *   dx_masked      out: dropout(dx) under (dx_mask_seed, site 3) — the seed of the block BELOW — [B*T, C] (NULL: not written). */
     const obte_bf16* dy_masked; obte_bf16* dx_masked; uint64_t dx_mask_seed;
+    /* backward only, optional: the four weight-matrix gradients summed over micro-batches in caller-owned fp32 buffers of the
+     * weights' shapes (OBTE_EPI_ACC32 in every form of the backward); w_acc32_mode 0 = off, else OBTE_ACC32_*.  With FIRST / MORE
+     * dattn_w / dproj_w / dfc_w / dmlp_w are not written; LAST writes bf16(buffer) there.  accumulate_matrices bit 0 must be clear. */
+    float *attn_w_acc32, *proj_w_acc32, *fc_w_acc32, *mlp_w_acc32; int32_t w_acc32_mode;
 } obte_block_desc;
 int64_t obte_block_act_bytes(int64_t B, int64_t T, int32_t n_embd, int32_t n_head);
 /* the same for a known dropout probability: with p = 0 the buffer ends before the attention dropout's keep bits (the largest

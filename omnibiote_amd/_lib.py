@@ -22,7 +22,8 @@ class GemmArgs(C.Structure):
                 ("lda", C.c_int64), ("ldb", C.c_int64), ("ldd", C.c_int64),
                 ("a_kmajor", C.c_int32), ("b_kmajor", C.c_int32), ("epilogue", C.c_int32), ("alpha", C.c_float),
                 ("dropout_p", C.c_float), ("dropout_site", C.c_int32), ("dropout_seed", C.c_uint64),
-                ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p), ("rope_T", C.c_int64), ("rope_head_dim", C.c_int32)]
+                ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p), ("rope_T", C.c_int64), ("rope_head_dim", C.c_int32),
+                ("acc32", C.c_void_p), ("acc32_mode", C.c_int32)]
 
 
 class AttnFwdArgs(C.Structure):
@@ -53,10 +54,13 @@ class BlockDesc(C.Structure):
                 ("dropout_p", C.c_float), ("dropout_seed", C.c_uint64), ("query_bounds", C.c_void_p),
                 ("ln1_partials", C.c_void_p), ("ln2_partials", C.c_void_p), ("ln_partial_mode", C.c_int32),
                 ("ranges_exact", C.c_void_p), ("out_rows", C.c_void_p), ("n_out_rows", C.c_int64),
-                ("dy_masked", C.c_void_p), ("dx_masked", C.c_void_p), ("dx_mask_seed", C.c_uint64)]
+                ("dy_masked", C.c_void_p), ("dx_masked", C.c_void_p), ("dx_mask_seed", C.c_uint64),
+                ("attn_w_acc32", C.c_void_p), ("proj_w_acc32", C.c_void_p), ("fc_w_acc32", C.c_void_p), ("mlp_w_acc32", C.c_void_p),
+                ("w_acc32_mode", C.c_int32)]
 
 
 LN_PARTIAL_FIRST, LN_PARTIAL_MORE, LN_PARTIAL_LAST = 1, 2, 3
+ACC32_FIRST, ACC32_MORE, ACC32_LAST = 1, 2, 3   # a gradient summed in fp32 over the passes of one optimizer step (OBTE_ACC32_*)
 MT_MAX = 32
 MT_CHUNK = 16384   # elements one workgroup of a multi-tensor launch serves (csrc/elementwise.hip)
 
@@ -75,6 +79,7 @@ class MtMasterArgs(C.Structure):
 
 
 EPI_NONE, EPI_GELU, EPI_ADD, EPI_GELU_BWD, EPI_ADD_DROPOUT, EPI_ROPE_QK = 0, 1, 2, 3, 4, 5
+EPI_ACC32 = 8
 SITE_EMBED, SITE_ATTN, SITE_RESID, SITE_MLP, SITE_USER = 0, 1, 2, 3, 7
 
 # name -> (restype, argtypes); every symbol include/omnibiote_hip.h declares
@@ -113,6 +118,8 @@ SYMBOLS = {
     "obte_embedding_bwd_ws_bytes": (C.c_int64, [C.c_int64, C.c_int]),
     "obte_embedding_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_int64, c_stream]),
     "obte_embedding_bwd_acc": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_int64, C.c_int, c_stream]),
+    "obte_embedding_bwd_acc32": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_uint64, c_stream]),
+    "obte_acc32_add_bf16": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int, c_stream]),
     "obte_key_ranges_from_tokens": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_void_p, c_stream]),
     "obte_token_order_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "obte_token_order": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, c_stream]),

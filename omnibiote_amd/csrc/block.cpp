@@ -125,10 +125,14 @@ obte_gemm_args product(const obte_bf16* a, const obte_bf16* b, obte_bf16* out, i
 obte_gemm_args xWt(const obte_bf16* x, const obte_bf16* w, obte_bf16* out, int64_t m, int64_t n, int64_t k) { return product(x, w, out, m, n, k, 1, 1); }
 // out[m, n] = dy[m, k] w[k, n]
 obte_gemm_args dyW(const obte_bf16* dy, const obte_bf16* w, obte_bf16* out, int64_t m, int64_t n, int64_t k) { return product(dy, w, out, m, n, k, 1, 0); }
-// dw[m, n] (+)= a[k, m]^T b[k, n]: a weight gradient over k rows, overwritten or accumulated in place
-obte_gemm_args aTb(const obte_bf16* a, const obte_bf16* b, obte_bf16* dw, int64_t m, int64_t n, int64_t k, bool accumulate) {
-    obte_gemm_args g = product(a, b, dw, m, n, k, 0, 0);
-    if (accumulate) { g.epilogue = OBTE_EPI_ADD; g.aux = dw; }
+// How one weight gradient is delivered: overwritten, accumulated in place in bf16, or summed into the caller's fp32 buffer of the weight's
+// shape over the passes of a step (acc32 + mode OBTE_ACC32_*: dw is then written by the last pass only)
+struct Wgrad { obte_bf16* dw; bool accumulate; float* acc32; int mode; };
+// dw[m, n] (+)= a[k, m]^T b[k, n]: a weight gradient over k rows; row0: the first of the weight's rows this product forms (c_attn by thirds)
+obte_gemm_args aTb(const obte_bf16* a, const obte_bf16* b, const Wgrad& w, int64_t m, int64_t n, int64_t k, int64_t row0 = 0) {
+    obte_gemm_args g = product(a, b, w.dw ? w.dw + row0 * n : nullptr, m, n, k, 0, 0);
+    if (w.mode) { g.epilogue = OBTE_EPI_ACC32; g.acc32 = w.acc32 + row0 * n; g.acc32_mode = w.mode; }
+    else if (w.accumulate) { g.epilogue = OBTE_EPI_ADD; g.aux = g.d; }
     return g;
 }
 // out = resid + [dropout under (seed, site)] (the product): the residual adds of the forward
@@ -282,9 +286,9 @@ int fwd_mlp(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, co
 // ---- backward --------------------------------------------------------------------------------------------------------------------------
 
 struct Grads {   // the caller's six gradient buffers and how they are written
-    obte_bf16 *ln1_w, *attn_w, *proj_w, *ln2_w, *fc_w, *mlp_w;
-    bool acc;      // the four matrices: dW += ... straight into the .grad buffers
-    int acc_ln;    // the two LayerNorm weights likewise
+    obte_bf16 *ln1_w, *ln2_w;
+    Wgrad attn_w, proj_w, fc_w, mlp_w;   // the four matrices: overwritten, dW += ... straight into the .grad buffers, or summed in fp32
+    int acc_ln;    // the two LayerNorm weights accumulated in place
 };
 
 // dx = resid + LN'(dh) over `rows` rows, dw by the descriptor's mode (fp32 partials across micro-batches, or the workspace);
@@ -313,8 +317,8 @@ int bwd_mlp(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, co
     obte_gemm_args dgelu = dyW(*dy_mlp, d->mlp_w, w.dhpre, f.Mm, 4 * C, C);   // dhpre = (dy W_mlp) * gelu'(h): hpre holds the derivative
     dgelu.epilogue = OBTE_EPI_GELU_BWD; dgelu.aux = a.hpre;
     TRY(run(dgelu, s));
-    const obte_gemm_args dw_mlp = aTb(*dy_mlp, a.hact, g.mlp_w, C, 4 * C, f.Mm, g.acc);   // dW_mlp = dy^T hact
-    const obte_gemm_args dw_fc = aTb(w.dhpre, a.h2, g.fc_w, 4 * C, C, f.Mm, g.acc);       // dW_fc = dhpre^T h2
+    const obte_gemm_args dw_mlp = aTb(*dy_mlp, a.hact, g.mlp_w, C, 4 * C, f.Mm);   // dW_mlp = dy^T hact
+    const obte_gemm_args dw_fc = aTb(w.dhpre, a.h2, g.fc_w, 4 * C, C, f.Mm);       // dW_fc = dhpre^T h2
     const bool own = !f.grouped && !f.pair_mlp;
     if (own) TRY(run(dw_mlp, s, w.gemmws, w.gemmws_bytes));
     TRY(run(dyW(w.dhpre, d->fc_w, w.dh, f.Mm, C, 4 * C), s, f.rows ? w.gemmws : nullptr, f.rows ? w.gemmws_bytes : 0));   // dh2 = dhpre W_fc (rows form: few tiles over K = 4C, split-K)
@@ -341,7 +345,7 @@ int bwd_ln2_proj_full(const obte_block_desc* d, const BlockForm& f, const ActLay
     if (rc == OBTE_OK) *delta_ready = true;
     else if (rc == OBTE_ROWDOT_NOT_TAKEN) TRY(obte_gemm_bf16(&dgrad, s));
     else return rc;
-    if (!f.grouped) TRY(run(aTb(*dx1_proj, a.y, g.proj_w, C, C, f.M, g.acc), s, w.gemmws, w.gemmws_bytes));
+    if (!f.grouped) TRY(run(aTb(*dx1_proj, a.y, g.proj_w, C, C, f.M), s, w.gemmws, w.gemmws_bytes));
     return OBTE_OK;
 }
 
@@ -357,7 +361,7 @@ int bwd_ln2_proj_rows(const obte_block_desc* d, const BlockForm& f, const ActLay
         dxp = w.dx1_rows_masked;
     }
     TRY(run(dyW(dxp, d->proj_w, w.dy_attn_rows, f.Mm, C, C), s, w.gemmws, w.gemmws_bytes));
-    TRY(run(aTb(dxp, a.rows_attn_out, g.proj_w, C, C, f.Mm, g.acc), s, w.gemmws, w.gemmws_bytes));   // dW_proj = dx1^T y over the wanted rows
+    TRY(run(aTb(dxp, a.rows_attn_out, g.proj_w, C, C, f.Mm), s, w.gemmws, w.gemmws_bytes));   // dW_proj = dx1^T y over the wanted rows
     if (!f.rows_attn) TRY(obte_rows_scatter_bf16(w.dy_attn_rows, d->out_rows, w.dyattn, f.Mm, f.M, C, s));   // (dx1_rows, in dyattn, has been read by both products)
     return OBTE_OK;
 }
@@ -376,10 +380,10 @@ int bwd_attention_rows(const obte_block_desc* d, const BlockForm& f, const ActLa
     TRY(run(dyW(w.dq_rows, d->attn_w, w.dh1_rows, f.Mm, C, C), s, w.gemmws, w.gemmws_bytes));   //       + dQ W_q at the wanted rows
     TRY(obte_rows_add_bf16(w.dh1_rows, d->out_rows, w.dh, f.Mm, C, s));
     TRY(obte_rows_gather_bf16(a.h1, d->out_rows, w.h1_rows, f.Mm, f.M, C, s));
-    obte_gemm_args dw_kv = aTb(dkv, a.h1, g.attn_w + (int64_t)C * C, 2 * C, C, f.M, g.acc);   // dW_kv = [dK dV]^T ln_1(x)
+    obte_gemm_args dw_kv = aTb(dkv, a.h1, g.attn_w, 2 * C, C, f.M, C);   // dW_kv = [dK dV]^T ln_1(x)
     dw_kv.lda = 3 * C;
     TRY(run(dw_kv, s, w.gemmws, w.gemmws_bytes));
-    return run(aTb(w.dq_rows, w.h1_rows, g.attn_w, C, C, f.Mm, g.acc), s, w.gemmws, w.gemmws_bytes);   // dW_q = dQ^T ln_1(x) over the wanted rows
+    return run(aTb(w.dq_rows, w.h1_rows, g.attn_w, C, C, f.Mm), s, w.gemmws, w.gemmws_bytes);   // dW_q = dQ^T ln_1(x) over the wanted rows
 }
 
 // dqkv from d(attention output) (inverse RoPE in the epilogue)
@@ -404,13 +408,13 @@ int bwd_c_attn(const obte_block_desc* d, const BlockForm& f, const ActLayout& a,
                const obte_bf16* dx1_proj, obte_stream s) {
     const int C = d->n_embd;
     const obte_gemm_args dh1 = dyW(w.dqkv, d->attn_w, w.dh, f.M, C, 3 * C);
-    const obte_gemm_args dw_attn = aTb(w.dqkv, a.h1, g.attn_w, 3 * C, C, f.M, g.acc);
+    const obte_gemm_args dw_attn = aTb(w.dqkv, a.h1, g.attn_w, 3 * C, C, f.M);
     if (!f.grouped) {
         TRY(run(dh1, s));
         return run(dw_attn, s, w.gemmws, w.gemmws_bytes);
     }
-    const obte_gemm_args gs[5] = {aTb(w.dhpre, a.h2, g.fc_w, 4 * C, C, f.M, g.acc), aTb(dy_mlp, a.hact, g.mlp_w, C, 4 * C, f.M, g.acc), dw_attn,
-                                  aTb(dx1_proj, a.y, g.proj_w, C, C, f.M, g.acc), dh1};
+    const obte_gemm_args gs[5] = {aTb(w.dhpre, a.h2, g.fc_w, 4 * C, C, f.M), aTb(dy_mlp, a.hact, g.mlp_w, C, 4 * C, f.M), dw_attn,
+                                  aTb(dx1_proj, a.y, g.proj_w, C, C, f.M), dh1};
     return obte_gemm_grouped_bf16(gs, 5, s);
 }
 
@@ -439,12 +443,19 @@ extern "C" int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, 
                                   obte_bf16* dx, obte_bf16* dln1_w, obte_bf16* dattn_w, obte_bf16* dproj_w, obte_bf16* dln2_w,
                                   obte_bf16* dfc_w, obte_bf16* dmlp_w, int accumulate_matrices, obte_stream s) {
     TRY(check_desc("obte_block_bwd", d));
-    OBTE_REQUIRE(x && dy && act && ws && dx && dln1_w && dattn_w && dproj_w && dln2_w && dfc_w && dmlp_w, "obte_block_bwd: null pointer");
+    const bool mats_unwritten = d->w_acc32_mode == OBTE_ACC32_FIRST || d->w_acc32_mode == OBTE_ACC32_MORE;   // (the fp32 sums take them: may be null)
+    OBTE_REQUIRE(x && dy && act && ws && dx && dln1_w && dln2_w && (mats_unwritten || (dattn_w && dproj_w && dfc_w && dmlp_w)), "obte_block_bwd: null pointer");
     const int lnp = d->ln_partial_mode;
     OBTE_REQUIRE(!lnp || (d->ln1_partials && d->ln2_partials && lnp >= OBTE_LN_PARTIAL_FIRST && lnp <= OBTE_LN_PARTIAL_LAST),
                  "obte_block_bwd: ln_partial_mode needs both partial buffers and a valid mode");
+    const int wm = d->w_acc32_mode;
+    OBTE_REQUIRE(!wm || (d->attn_w_acc32 && d->proj_w_acc32 && d->fc_w_acc32 && d->mlp_w_acc32 && wm >= OBTE_ACC32_FIRST && wm <= OBTE_ACC32_LAST &&
+                         !(accumulate_matrices & 1)),
+                 "obte_block_bwd: w_acc32_mode needs the four fp32 buffers, a valid mode and accumulate_matrices bit 0 clear");
     // accumulate_matrices: bit 0 = the four matrices, bit 1 = the two LayerNorm weights
-    const Grads g = {dln1_w, dattn_w, dproj_w, dln2_w, dfc_w, dmlp_w, (accumulate_matrices & 1) != 0, (accumulate_matrices & 2) ? 1 : 0};
+    const bool acc = (accumulate_matrices & 1) != 0;
+    const Grads g = {dln1_w, dln2_w, Wgrad{dattn_w, acc, d->attn_w_acc32, wm}, Wgrad{dproj_w, acc, d->proj_w_acc32, wm},
+                     Wgrad{dfc_w, acc, d->fc_w_acc32, wm}, Wgrad{dmlp_w, acc, d->mlp_w_acc32, wm}, (accumulate_matrices & 2) ? 1 : 0};
     const BlockForm f = resolve(d);
     const ActLayout a(d->B, d->T, d->n_embd, d->n_head, true, act);   // (only read here)
     const WsLayout w(d->B, d->T, d->n_embd, d->n_head, ws);

@@ -107,10 +107,21 @@ __device__ __forceinline__ void embed_store_row(bf16* dst, const float (&acc)[8]
     }
     *reinterpret_cast<bf16x8*>(dst) = o;
 }
-
+// The fp32-destination form (obte_embedding_bwd_acc32): the row's fp32 sum goes into the persistent fp32 buffer before any rounding
 template <bool ACC>
+__device__ __forceinline__ void embed_store_row(float* dst, const float (&acc)[8]) {
+    f32x4 lo = f32x4{acc[0], acc[1], acc[2], acc[3]}, hi = f32x4{acc[4], acc[5], acc[6], acc[7]};
+    if (ACC) {
+        lo += *reinterpret_cast<const f32x4*>(dst);
+        hi += *reinterpret_cast<const f32x4*>(dst + 4);
+    }
+    *reinterpret_cast<f32x4*>(dst) = lo;
+    *reinterpret_cast<f32x4*>(dst + 4) = hi;
+}
+
+template <bool ACC, class DST = bf16>
 __global__ __launch_bounds__(128) void embed_bwd_chunk_kernel(const int64_t* __restrict__ idx, const int32_t* __restrict__ order,
-                                                               const bf16* __restrict__ dout, bf16* __restrict__ dwte,
+                                                               const bf16* __restrict__ dout, DST* __restrict__ dwte,
                                                                float* __restrict__ slab, int64_t rows, int cols, int64_t vocab, DropCfg dc) {
     __shared__ int32_t s_row[EMB_CHUNK];
     __shared__ int64_t s_tok[EMB_CHUNK + 2];  // [0] = token before the chunk (or -1), [1..n] chunk, [n+1] = token after (or -1)
@@ -164,9 +175,9 @@ __global__ __launch_bounds__(128) void embed_bwd_chunk_kernel(const int64_t* __r
     }
 }
 
-template <bool ACC>
+template <bool ACC, class DST = bf16>
 __global__ __launch_bounds__(128) void embed_bwd_span_kernel(const int64_t* __restrict__ idx, const int32_t* __restrict__ order,
-                                                              bf16* __restrict__ dwte, const float* __restrict__ slab,
+                                                              DST* __restrict__ dwte, const float* __restrict__ slab,
                                                               int64_t rows, int cols, int64_t nchunks, int64_t vocab) {
     const int64_t c = blockIdx.x;
     const int64_t p0 = c * EMB_CHUNK;
@@ -192,6 +203,37 @@ __global__ __launch_bounds__(128) void embed_bwd_span_kernel(const int64_t* __re
             if (clamp_tok(idx[order[q1 - 1]], vocab) != last) break;  // the run ended inside chunk cc
         }
         embed_store_row<ACC>(dwte + last * cols + col, acc);
+    }
+}
+
+// acc32 (+)= src by mode (OBTE_ACC32_*), src null: a zero contribution; LAST: out = bf16(acc32).  Eight elements per thread.
+__global__ __launch_bounds__(256) void acc32_add_kernel(float* __restrict__ acc32, const bf16* __restrict__ src, bf16* __restrict__ out,
+                                                         int64_t n8, int mode) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+        float v[8];
+        if (src) {
+            const bf16x8 sv = *reinterpret_cast<const bf16x8*>(src + i * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = bf2f(sv[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = 0.f;
+        }
+        if (mode != OBTE_ACC32_FIRST) {
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(acc32 + i * 8), hi = *reinterpret_cast<const f32x4*>(acc32 + i * 8 + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { v[j] += lo[j]; v[4 + j] += hi[j]; }
+        }
+        if (src || mode == OBTE_ACC32_FIRST) {   // (a zero contribution to an existing sum leaves it as it is)
+            *reinterpret_cast<f32x4*>(acc32 + i * 8) = f32x4{v[0], v[1], v[2], v[3]};
+            *reinterpret_cast<f32x4*>(acc32 + i * 8 + 4) = f32x4{v[4], v[5], v[6], v[7]};
+        }
+        if (mode == OBTE_ACC32_LAST) {
+            bf16x8 o;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = f2bf(v[j]);
+            *reinterpret_cast<bf16x8*>(out + i * 8) = o;
+        }
     }
 }
 
@@ -818,6 +860,48 @@ extern "C" int obte_embedding_bwd_dropout(const int64_t* idx, const int32_t* ord
         hipLaunchKernelGGL(embed_bwd_span_kernel<false>, dim3((unsigned)nchunks), dim3(128), 0, st, idx, order, (bf16*)dwte,
                            (const float*)ws, rows, cols, nchunks, vocab);
     OBTE_CHECK_LAUNCH("obte_embedding_bwd(span)");
+    return OBTE_OK;
+}
+
+extern "C" int obte_acc32_add_bf16(float* acc32, const obte_bf16* src, obte_bf16* out, int64_t n, int mode, obte_stream s) {
+    OBTE_REQUIRE(acc32 && n > 0 && n % 8 == 0, "obte_acc32_add_bf16: null buffer or n not a positive multiple of 8");
+    OBTE_REQUIRE(mode >= OBTE_ACC32_FIRST && mode <= OBTE_ACC32_LAST && (mode != OBTE_ACC32_LAST || out), "obte_acc32_add_bf16: bad mode, or LAST without out");
+    if (!src && mode == OBTE_ACC32_MORE) return OBTE_OK;   // nothing to add, nothing to write
+    hipLaunchKernelGGL(acc32_add_kernel, dim3(stream_grid(n / 8, 256)), dim3(256), 0, (hipStream_t)s, acc32, (const bf16*)src, (bf16*)out, n / 8, mode);
+    OBTE_CHECK_LAUNCH("obte_acc32_add_bf16");
+    return OBTE_OK;
+}
+
+extern "C" int obte_embedding_bwd_acc32(const int64_t* idx, const int32_t* order, const obte_bf16* dout, float* acc32, obte_bf16* dwte,
+                                        void* ws, int64_t rows, int cols, int64_t vocab, int mode, float p, uint64_t seed, obte_stream s) {
+    OBTE_REQUIRE(idx && order && dout && acc32 && ws, "obte_embedding_bwd_acc32: null pointer");
+    OBTE_REQUIRE(mode >= OBTE_ACC32_FIRST && mode <= OBTE_ACC32_LAST && (mode != OBTE_ACC32_LAST || dwte), "obte_embedding_bwd_acc32: bad mode, or LAST without dwte");
+    if (check_p("obte_embedding_bwd_acc32", p)) return OBTE_EINVAL;
+    const DropCfg dc = make_drop(p, seed, OBTE_SITE_EMBED);
+    OBTE_REQUIRE(rows > 0 && cols > 0 && cols % 8 == 0 && vocab > 0, "obte_embedding_bwd_acc32: bad shape");
+    OBTE_REQUIRE(rows < (1ll << 31), "obte_embedding_bwd_acc32: too many rows");
+    hipStream_t st = (hipStream_t)s;
+    const bool first = mode == OBTE_ACC32_FIRST;
+    if (first && hipMemsetAsync(acc32, 0, (size_t)vocab * cols * sizeof(float), st) != hipSuccess) {
+        obte_set_error("obte_embedding_bwd_acc32: memset failed");
+        return OBTE_ELAUNCH;
+    }
+    const int64_t nchunks = cdiv64(rows, EMB_CHUNK);
+    if (first)
+        hipLaunchKernelGGL((embed_bwd_chunk_kernel<false, float>), dim3((unsigned)nchunks), dim3(128), 0, st, idx, order, (const bf16*)dout, acc32, (float*)ws,
+                           rows, cols, vocab, dc);
+    else
+        hipLaunchKernelGGL((embed_bwd_chunk_kernel<true, float>), dim3((unsigned)nchunks), dim3(128), 0, st, idx, order, (const bf16*)dout, acc32, (float*)ws,
+                           rows, cols, vocab, dc);
+    OBTE_CHECK_LAUNCH("obte_embedding_bwd_acc32(chunk)");
+    if (first)
+        hipLaunchKernelGGL((embed_bwd_span_kernel<false, float>), dim3((unsigned)nchunks), dim3(128), 0, st, idx, order, acc32, (const float*)ws, rows, cols,
+                           nchunks, vocab);
+    else
+        hipLaunchKernelGGL((embed_bwd_span_kernel<true, float>), dim3((unsigned)nchunks), dim3(128), 0, st, idx, order, acc32, (const float*)ws, rows, cols,
+                           nchunks, vocab);
+    OBTE_CHECK_LAUNCH("obte_embedding_bwd_acc32(span)");
+    if (mode == OBTE_ACC32_LAST) return obte_acc32_add_bf16(acc32, nullptr, dwte, vocab * (int64_t)cols, OBTE_ACC32_LAST, s);
     return OBTE_OK;
 }
 

@@ -16,7 +16,7 @@ int gemm_no_form(int s, int bn, bool ak, bool bk, int epi, bool split) {
 }
 
 static int validate_args(const obte_gemm_args* g) {
-    OBTE_REQUIRE(g && g->a && g->b && g->d, "obte_gemm_bf16: null pointer");
+    OBTE_REQUIRE(g && g->a && g->b && (g->d || (g->epilogue == OBTE_EPI_ACC32 && g->acc32_mode != OBTE_ACC32_LAST)), "obte_gemm_bf16: null pointer");
     OBTE_REQUIRE(g->M > 0 && g->N > 0 && g->K > 0, "obte_gemm_bf16: empty problem M=%lld N=%lld K=%lld",
                  (long long)g->M, (long long)g->N, (long long)g->K);
     OBTE_REQUIRE(g->lda % 8 == 0 && g->ldb % 8 == 0 && g->ldd % 8 == 0 && g->N % 8 == 0,
@@ -34,7 +34,13 @@ static int validate_args(const obte_gemm_args* g) {
                          (g->N / 3) % g->rope_head_dim == 0,
                      "obte_gemm_bf16: EPI_ROPE_QK needs cos/sin tables, T, head_dim %% 8 == 0 and N = 3 * n_head * head_dim");
     if (g->epilogue == OBTE_EPI_GELU) OBTE_REQUIRE(g->d2, "obte_gemm_bf16: GELU epilogue needs d2");
-    if (g->epilogue != OBTE_EPI_NONE && g->epilogue != OBTE_EPI_ADD) OBTE_REQUIRE(g->alpha == 1.0f, "obte_gemm_bf16: alpha != 1 only with EPI_NONE / EPI_ADD");
+    if (g->epilogue == OBTE_EPI_ACC32)
+        OBTE_REQUIRE(g->acc32 && g->acc32_mode >= OBTE_ACC32_FIRST && g->acc32_mode <= OBTE_ACC32_LAST && !g->a_kmajor && !g->b_kmajor && g->ldd == g->N,
+                     "obte_gemm_bf16: EPI_ACC32 needs the fp32 buffer, a mode (OBTE_ACC32_*), the weight-gradient layout (a_kmajor = b_kmajor = 0) and ldd == N");
+    else
+        OBTE_REQUIRE(!g->acc32 && g->acc32_mode == 0, "obte_gemm_bf16: acc32 / acc32_mode belong to EPI_ACC32");
+    if (g->epilogue != OBTE_EPI_NONE && g->epilogue != OBTE_EPI_ADD && g->epilogue != OBTE_EPI_ACC32)
+        OBTE_REQUIRE(g->alpha == 1.0f, "obte_gemm_bf16: alpha != 1 only with EPI_NONE / EPI_ADD / EPI_ACC32");
     return OBTE_OK;
 }
 
@@ -81,6 +87,8 @@ static bool runs_as_given(const Plan& pl, const obte_gemm_args* g) {
 }
 static bool fall_back(Plan& pl, const obte_gemm_args* g) {   // false: nothing to fall back to (the launcher reports the missing form)
     switch (pl.structure) {
+        case 1: if (g->epilogue != OBTE_EPI_ACC32) return false;      // (a NONE plan borrowed for the fp32 sum, which structure 1 lacks)
+                pl = make_plan(g->M, g->N, g->K, false); return true;
         case 7: pl = Plan{3, 256, 1}; return true;                    // the same main loop, one tile per workgroup
         case 3: case 4: pl.structure = 2; return true;               // the K-tile ring at the same width and split
         case 2: if (pl.bn != 192) return false;                      // the 192-wide tile: the heuristic, no split
@@ -110,14 +118,14 @@ static bool lookup_plan(const obte_gemm_args* g, Plan* out, bool* near_match) {
     std::lock_guard<std::mutex> lk(g_plan_mu);
     const int lay = layout_of(g);
     auto it = g_plans.find(PlanKey(lay, g->epilogue, g->M, g->N, g->K));
-    if (it == g_plans.end() && g->epilogue == OBTE_EPI_ADD)   // accumulate-into-grad reuses the plan tuned for the plain form
+    if (it == g_plans.end() && (g->epilogue == OBTE_EPI_ADD || g->epilogue == OBTE_EPI_ACC32))   // accumulate-into-grad (bf16 or fp32) reuses the plan tuned for the plain form
         it = g_plans.find(PlanKey(lay, OBTE_EPI_NONE, g->M, g->N, g->K));
     if (it == g_plans.end() && g->epilogue == OBTE_EPI_ROPE_QK)       // the c_attn projection: plan of the plain form
         it = g_plans.find(PlanKey(lay, OBTE_EPI_NONE, g->M, g->N, g->K));
     if (it == g_plans.end() && g->epilogue == OBTE_EPI_ADD_DROPOUT)   // same main loop as the residual-add form
         it = g_plans.find(PlanKey(lay, OBTE_EPI_ADD, g->M, g->N, g->K));
     if (it == g_plans.end()) {   // a near match: an entry with the same layout and epilogue (ADD: NONE's)
-        const int epi = g->epilogue == OBTE_EPI_ADD ? OBTE_EPI_NONE : g->epilogue;
+        const int epi = (g->epilogue == OBTE_EPI_ADD || g->epilogue == OBTE_EPI_ACC32) ? OBTE_EPI_NONE : g->epilogue;
         for (auto jt = g_plans.begin(); jt != g_plans.end(); ++jt)
             if (std::get<0>(jt->first) == lay && std::get<1>(jt->first) == epi && serves(jt->first, g->M, g->N, g->K)) {
                 it = jt;
@@ -134,7 +142,7 @@ static bool lookup_plan(const obte_gemm_args* g, Plan* out, bool* near_match) {
 // count trimmed to one round; no split without a workspace that holds it; splits that would be empty dropped; then, while the plan's
 // structure cannot run it as given, its fallback.
 static Plan resolve(const obte_gemm_args* g, const void* workspace, int64_t workspace_bytes) {
-    const bool can_split = workspace && (g->epilogue == OBTE_EPI_NONE || g->epilogue == OBTE_EPI_ADD) && g->ldd == g->N;
+    const bool can_split = workspace && (g->epilogue == OBTE_EPI_NONE || g->epilogue == OBTE_EPI_ADD || g->epilogue == OBTE_EPI_ACC32) && g->ldd == g->N;
     Plan pl;
     bool near_match = false;
     if (!lookup_plan(g, &pl, &near_match)) pl = make_plan(g->M, g->N, g->K, can_split);
@@ -171,6 +179,7 @@ static void fill_params(const obte_gemm_args* g, void* workspace, const Plan& pl
     p.alpha = g->alpha;
     p.rope_cos = g->rope_cos; p.rope_sin = g->rope_sin; p.rope_T = g->rope_T; p.rope_hs = g->rope_head_dim;
     p.drop = make_drop(g->epilogue == OBTE_EPI_ADD_DROPOUT ? g->dropout_p : 0.f, g->dropout_seed, (uint32_t)g->dropout_site);
+    p.acc32 = g->acc32; p.acc32_mode = g->acc32_mode;
 #ifdef OBTE_DEBUG_HOOKS
     {   // timing-only diagnostics of the debug build (results are wrong): zero-record descriptors drop every LDS-DMA / no stores
         static int noload = -1, nostore = -1, exit_now = -1;
@@ -193,8 +202,8 @@ static void fill_params(const obte_gemm_args* g, void* workspace, const Plan& pl
 // Profiler record kind, as bench.py decodes it: a single launch 4 x layout + epilogue + 1000 x structure (a split-K reduce is inside the
 // same record); a grouped launch (last: its last problem) 32, + 1 if its first and last problems differ in layout, + 2 if it accumulates.
 static int prof_kind(const obte_gemm_args* g, int structure, const obte_gemm_args* last = nullptr) {
-    if (last) return 32 + (layout_of(last) != layout_of(g) ? 1 : 0) + (g->epilogue == OBTE_EPI_ADD ? 2 : 0);
-    return 4 * layout_of(g) + g->epilogue + 1000 * structure;
+    if (last) return 32 + (layout_of(last) != layout_of(g) ? 1 : 0) + ((g->epilogue == OBTE_EPI_ADD || g->epilogue == OBTE_EPI_ACC32) ? 2 : 0);
+    return 4 * layout_of(g) + (g->epilogue == OBTE_EPI_ACC32 ? OBTE_EPI_ADD : g->epilogue) + 1000 * structure;   // (the fp32 sum is recorded as the accumulate form it replaces)
 }
 
 // The grouped and the row-dot launches pass no dropout and no RoPE tables, whatever the descriptor holds (their epilogues read neither)
@@ -264,9 +273,9 @@ static void debug_gemm_report(const GemmParams& p, int variant, int epi, hipStre
 extern "C" int obte_gemm_plan_set(int a_kmajor, int b_kmajor, int epilogue, int64_t M, int64_t N, int64_t K, int variant,
                                   int bn, int splits) {
     static const char* const forms[] = {nullptr, "the first structure is 128 wide, no split-K",
-                                        "the K-tile ring is 128, 192 or 256 wide, split-K with epilogue NONE or ADD",
-                                        "the four-half-stage structure is 256 wide, split-K with epilogue NONE or ADD",
-                                        "the two-workgroups-per-CU structure is 128 wide, split-K with epilogue NONE or ADD", nullptr, nullptr,
+                                        "the K-tile ring is 128, 192 or 256 wide, split-K with epilogue NONE, ADD or ACC32; ACC32 in the weight-gradient layout",
+                                        "the four-half-stage structure is 256 wide, split-K with epilogue NONE, ADD or ACC32; ACC32 in the weight-gradient layout",
+                                        "the two-workgroups-per-CU structure is 128 wide, split-K with epilogue NONE, ADD or ACC32; ACC32 in the weight-gradient layout", nullptr, nullptr,
                                         "the persistent continuous-ring structure is 256 wide, no split-K, x W^T and dy W layouts with their epilogues"};
     OBTE_REQUIRE(variant >= 1 && variant <= 7 && forms[variant] && (bn == 128 || bn == 256 || bn == 192) && splits >= 1 && splits <= 64,
                  "obte_gemm_plan_set: bad plan");
@@ -313,7 +322,8 @@ extern "C" int obte_gemm_bf16_ws(const obte_gemm_args* g, void* workspace, int64
 #ifdef OBTE_DEBUG_HOOKS
     if (rc == OBTE_OK && p.dbg_times && pl.structure >= 2 && pl.structure <= 4) debug_gemm_report(p, pl.structure, g->epilogue, st);   // (7 reports itself)
 #endif
-    if (rc == OBTE_OK && p.splits > 1) rc = obte_gemm_splitk_reduce(p, g->epilogue == OBTE_EPI_ADD ? p.aux : nullptr, st);
+    if (rc == OBTE_OK && p.splits > 1)
+        rc = g->epilogue == OBTE_EPI_ACC32 ? obte_gemm_splitk_reduce_acc32(p, st) : obte_gemm_splitk_reduce(p, g->epilogue == OBTE_EPI_ADD ? p.aux : nullptr, st);
     obte_prof_end(prof, st);
     return rc;
 }
@@ -344,7 +354,7 @@ extern "C" int obte_gemm_rowdot_bf16(const obte_gemm_args* g, const obte_bf16* o
     return rc;
 }
 
-// Grouped launch (see gemm_v3_group_kernel).  Each problem: any layout, epilogue NONE or ADD, K >= 128.
+// Grouped launch (see gemm_v3_group_kernel).  Each problem: any layout, epilogue NONE or ADD, K >= 128; or ACC32 in its one layout.
 extern "C" int obte_gemm_grouped_bf16(const obte_gemm_args* gs, int count, obte_stream s) {
     OBTE_REQUIRE(gs && count >= 1 && count <= GROUP_MAX, "obte_gemm_grouped_bf16: count must be 1..%d", GROUP_MAX);
     GroupParams gp;
@@ -355,7 +365,7 @@ extern "C" int obte_gemm_grouped_bf16(const obte_gemm_args* gs, int count, obte_
     double flop = 0.0;
     for (int i = 0; i < count; ++i) {
         const obte_gemm_args* g = gs + i;
-        OBTE_REQUIRE(g->epilogue == OBTE_EPI_NONE || g->epilogue == OBTE_EPI_ADD, "obte_gemm_grouped_bf16: epilogue must be NONE or ADD");
+        OBTE_REQUIRE(g->epilogue == OBTE_EPI_NONE || g->epilogue == OBTE_EPI_ADD || g->epilogue == OBTE_EPI_ACC32, "obte_gemm_grouped_bf16: epilogue must be NONE or ADD (or ACC32, the fp32 sum of a weight gradient)");
         { const int vrc = validate_args(g); if (vrc != OBTE_OK) return vrc; }
         OBTE_REQUIRE(g->K >= 128, "obte_gemm_grouped_bf16: K must be >= 128 (K=%lld)", (long long)g->K);
         OBTE_REQUIRE(cdiv64(g->M, BM) * cdiv64(g->N, 256) < (1ll << 24), "obte_gemm_grouped_bf16: too many tiles");
@@ -363,7 +373,7 @@ extern "C" int obte_gemm_grouped_bf16(const obte_gemm_args* gs, int count, obte_
         fill_params(g, nullptr, Plan{3, 256, 1}, p);
         no_drop_no_rope(p);
         if (g->epilogue == OBTE_EPI_NONE) p.aux = nullptr;
-        gp.layout[i] = layout_of(g);
+        gp.layout[i] = g->epilogue == OBTE_EPI_ACC32 ? 4 : layout_of(g);   // (ACC32: the weight-gradient layout with the fp32 epilogue)
         gp.first_wg[i] = wg;
         wg += p.tiles_m * p.tiles_n;
         if (in_class0 && p.k_per_split == gp.g[0].k_per_split) class0 = wg; else in_class0 = false;

@@ -26,6 +26,17 @@
 
 namespace obte_gemm_v2 {
 
+// OBTE_EPI_ACC32's arithmetic, each operation rounded on its own (a fused multiply-add would round alpha * acc + old once and the
+// buffer's bits would depend on what the compiler fused): c = fl32(alpha * acc), sum = fl32(old + c)
+__device__ __forceinline__ f32x4 acc32_term(f32x4 acc, float alpha) {
+#pragma clang fp contract(off)
+    return acc * alpha;
+}
+__device__ __forceinline__ f32x4 acc32_sum(f32x4 old, f32x4 c) {
+#pragma clang fp contract(off)
+    return old + c;
+}
+
 // Tile epilogue shared by both main-loop structures: stage the accumulators through LDS, apply EPI, write 16-B pieces.
 template <int EPI, bool SPLIT, int BN>
 __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[BN / 32][4], char* smem, int wave, int lane,
@@ -57,6 +68,67 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[
                 const int64_t n = n0 + wn * NW + half * 64 + c4 * 4;
                 if (m < p.store_rows && n < p.N)
                     *reinterpret_cast<f32x4*>(out + m * p.N + n) = *reinterpret_cast<const f32x4*>(stg + row * EPI_LD_F32 + c4 * 16);
+            }
+        }
+        return;
+    }
+
+    if (EPI == OBTE_EPI_ACC32) {
+        // The weight gradient summed in fp32 over the passes of a step: the split-K staging above (64 columns at a time, 16-byte fp32
+        // row chunks), with a read-modify-write of the caller's [M, N] fp32 buffer in place of the slab store and, on the last pass,
+        // the bf16 gradient written from the sum already in registers.  acc32_mode is uniform (one problem, one mode).  ldd == N
+        // (host-checked): one offset serves acc32 and d.  Interior tiles issue the eight loads of a batch before its first store
+        // (vmcnt retires in order: a load behind a store waits for the store) and address with one 64-bit tile origin plus 32-bit
+        // in-tile offsets, as the bf16 path below; two batches per half keep the loaded chunks to 32 registers beside the accumulators.
+        char* stg = smem + wave * (64 * EPI_LD_F32);
+        const int mode = p.acc32_mode;
+        const bool interior = m0 + BM <= p.store_rows && n0 + tile_n <= p.N;
+        const int64_t tile_o = m0 * p.N + n0;
+        const uint32_t n32 = (uint32_t)p.N;
+        const uint32_t off_l = (uint32_t)(wm * 64 + (lane >> 4)) * n32 + (uint32_t)(wn * NW + (lane & 15) * 4);
+#pragma unroll
+        for (int half = 0; half < NJ / 4; ++half) {
+            if (half) __syncthreads();
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi)
+                    *reinterpret_cast<f32x4*>(stg + (mi * 16 + em) * EPI_LD_F32 + (ni * 16 + en) * 4) = acc[half * 4 + ni][mi];
+            __syncthreads();
+            if (interior) {
+#pragma unroll
+                for (int b8 = 0; b8 < 2; ++b8) {
+                    f32x4 old[8];
+                    if (mode != OBTE_ACC32_FIRST) {
+#pragma unroll
+                        for (int i = 0; i < 8; ++i)
+                            old[i] = *reinterpret_cast<const f32x4*>(p.acc32 + tile_o + (int64_t)(off_l + (uint32_t)(half * 64) + (uint32_t)((b8 * 8 + i) * 4) * n32));
+                    }
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int it = b8 * 8 + i;
+                        const int64_t o = tile_o + (int64_t)(off_l + (uint32_t)(half * 64) + (uint32_t)(it * 4) * n32);
+                        f32x4 v = acc32_term(*reinterpret_cast<const f32x4*>(stg + (it * 4 + (lane >> 4)) * EPI_LD_F32 + (lane & 15) * 16), p.alpha);
+                        if (mode != OBTE_ACC32_FIRST) v = acc32_sum(old[i], v);
+                        *reinterpret_cast<f32x4*>(p.acc32 + o) = v;
+                        if (mode == OBTE_ACC32_LAST) *reinterpret_cast<bf16x4*>(p.d + o) = __builtin_convertvector(v, bf16x4);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int it = 0; it < 16; ++it) {
+                    const int row = it * 4 + (lane >> 4);
+                    const int c4 = lane & 15;
+                    const int64_t m = m0 + wm * 64 + row;
+                    const int64_t n = n0 + wn * NW + half * 64 + c4 * 4;
+                    if (m < p.store_rows && n < p.N) {
+                        const int64_t o = m * p.N + n;
+                        f32x4 v = acc32_term(*reinterpret_cast<const f32x4*>(stg + row * EPI_LD_F32 + c4 * 16), p.alpha);
+                        if (mode != OBTE_ACC32_FIRST) v = acc32_sum(*reinterpret_cast<const f32x4*>(p.acc32 + o), v);
+                        *reinterpret_cast<f32x4*>(p.acc32 + o) = v;
+                        if (mode == OBTE_ACC32_LAST) *reinterpret_cast<bf16x4*>(p.d + o) = __builtin_convertvector(v, bf16x4);
+                    }
+                }
             }
         }
         return;
@@ -388,6 +460,8 @@ OBTE_INST(true, false, 256)
 OBTE_INST(false, true, 256)
 OBTE_INST(false, false, 256)
 #undef OBTE_INST
+template __global__ void gemm_v2_kernel<false, false, OBTE_EPI_ACC32, false, 128>(GemmParams);   // (the weight-gradient layout only)
+template __global__ void gemm_v2_kernel<false, false, OBTE_EPI_ACC32, false, 256>(GemmParams);
 // BN = 192: k-contiguous operands only (the forward projections), no split-K.  For outputs whose width is a multiple of 192 but
 // leaves the 256-wide tiling a ragged last round — c_attn at the small config: N = 3072 is 384 tiles of 256 x 256 = 1.5 rounds of
 // the 256 CUs, and 512 tiles of 256 x 192 = two full ones (a quarter less work per round).
@@ -546,7 +620,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_v3_kernel(GemmParams p) {
 // 128 tiles of K = 3 n_embd): problems come in two classes — class 0 = the leading problems with the longest K,
 // class 1 = the rest — and when both class sizes divide by 8 every XCD receives its share of class 0 first, then
 // its share of class 1, so the short tiles start on the CUs that got no long one and behind the first finishers.
-// Layout and accumulate/overwrite are per problem (uniform branches; aux == null means overwrite).
+// Layout and accumulate/overwrite are per problem (uniform branches; aux == null means overwrite); a problem with OBTE_EPI_ACC32 (the
+// weight-gradient layout) is dealt as a layout of its own.
 // (GroupParams: gemm_common.h)
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_v3_group_kernel(GroupParams gp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -567,7 +642,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_v3_group_kernel(GroupParams 
         case 0: v3_tile<false, false, OBTE_EPI_ADD, false>(gp.g[i], local, smem); break;
         case 1: v3_tile<false, true, OBTE_EPI_ADD, false>(gp.g[i], local, smem); break;
         case 2: v3_tile<true, false, OBTE_EPI_ADD, false>(gp.g[i], local, smem); break;
-        default: v3_tile<true, true, OBTE_EPI_ADD, false>(gp.g[i], local, smem); break;
+        case 3: v3_tile<true, true, OBTE_EPI_ADD, false>(gp.g[i], local, smem); break;
+        default: v3_tile<false, false, OBTE_EPI_ACC32, false>(gp.g[i], local, smem); break;   // 4: a weight gradient summed in fp32 over passes
     }
 }
 
@@ -584,6 +660,7 @@ OBTE_INST3(true, false)
 OBTE_INST3(false, true)
 OBTE_INST3(false, false)
 #undef OBTE_INST3
+template __global__ void gemm_v3_kernel<false, false, OBTE_EPI_ACC32, false>(GemmParams);
 
 // ---- fourth structure: 256x128 tile, FOUR waves, ring of THREE half K-tiles (24 KiB each), TWO workgroups per CU ------------
 // What the K = 1024 shapes of the block lose (measured with the timing-only hooks on c_fc + GELU, 8192 x 4096 x 1024: 96 us
@@ -763,6 +840,7 @@ OBTE_INST4(true, false)
 OBTE_INST4(false, true)
 OBTE_INST4(false, false)
 #undef OBTE_INST4
+template __global__ void gemm_v4_kernel<false, false, OBTE_EPI_ACC32, false>(GemmParams);
 
 // d[m][n] = bf16(alpha * sum_s slab[s][m][n]) in split order
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, bf16* __restrict__ d, const bf16* aux,
@@ -785,6 +863,22 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 }
 
+// OBTE_EPI_ACC32 after a split-K launch: c = fl32(alpha * sum_s slab[s][m][n]) in split order, acc32 (+)= c by mode, d = bf16(acc32) on LAST
+__global__ __launch_bounds__(256) void splitk_reduce_acc32_kernel(const float* __restrict__ slab, float* __restrict__ acc32, bf16* __restrict__ d,
+                                                                   int64_t MN4, int64_t MN, int splits, float alpha, int mode) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < MN4; i += (int64_t)gridDim.x * 256) {
+        f32x4 s = *reinterpret_cast<const f32x4*>(slab + i * 4);
+        for (int k = 1; k < splits; ++k) {
+            const f32x4 t = *reinterpret_cast<const f32x4*>(slab + k * MN + i * 4);
+            s += t;
+        }
+        f32x4 v = acc32_term(s, alpha);
+        if (mode != OBTE_ACC32_FIRST) v = acc32_sum(*reinterpret_cast<const f32x4*>(acc32 + i * 4), v);
+        *reinterpret_cast<f32x4*>(acc32 + i * 4) = v;
+        if (mode == OBTE_ACC32_LAST) *reinterpret_cast<bf16x4*>(d + i * 4) = __builtin_convertvector(v, bf16x4);
+    }
+}
+
 }  // namespace obte_gemm_v2
 using namespace obte_gemm_v2;
 
@@ -796,6 +890,17 @@ int obte_gemm_splitk_reduce(const GemmParams& p, const bf16* aux, hipStream_t st
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)p.slab, p.d, aux, mn / 4, mn, p.splits, p.alpha);
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) { obte_set_error("obte_gemm_bf16(split-K reduce): %s", hipGetErrorString(e_)); return OBTE_ELAUNCH; }
+    return OBTE_OK;
+}
+
+int obte_gemm_splitk_reduce_acc32(const GemmParams& p, hipStream_t st) {
+    const int64_t mn = p.M * p.N;
+    int64_t blocks = cdiv64(mn / 4, 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(splitk_reduce_acc32_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)p.slab, p.acc32, p.d, mn / 4, mn, p.splits, p.alpha,
+                       p.acc32_mode);
+    hipError_t e_ = hipGetLastError();
+    if (e_ != hipSuccess) { obte_set_error("obte_gemm_bf16(split-K reduce, fp32 sum): %s", hipGetErrorString(e_)); return OBTE_ELAUNCH; }
     return OBTE_OK;
 }
 

@@ -35,6 +35,7 @@ struct GemmParams {
     float alpha;
     DropCfg drop;
     const float* rope_cos; const float* rope_sin; int64_t rope_T; int rope_hs;
+    float* acc32; int acc32_mode;   // OBTE_EPI_ACC32: the fp32 [M, N] sum over the passes of a step and OBTE_ACC32_*
 };
 
 #ifdef OBTE_DEBUG_HOOKS
@@ -136,11 +137,12 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 // ---- the GEMM family's host interface: capability table, launch helper, dispatcher, one launcher per structure --------------------
 // Does structure S at tile width BN have a kernel for (layout, epilogue, split-K)?  A split-K form runs epilogue NONE into fp32 slabs;
-// the reduce kernel applies ADD.  Each structure file instantiates exactly these forms and its dispatcher reaches no other;
+// the reduce kernel applies ADD / ACC32.  ACC32 (the fp32 sum of a weight gradient over passes) exists in the weight-gradient layout only,
+// on the structures that share tile_epilogue.  Each structure file instantiates exactly these forms and its dispatcher reaches no other;
 // obte_gemm_plan_set validates plans against the same answer and the plan resolver (gemm.cpp) falls back from it.
 constexpr bool gemm_has_form(int s, int bn, bool ak, bool bk, int epi, bool split) {
     const bool abi = epi >= OBTE_EPI_NONE && epi <= OBTE_EPI_ROPE_QK;                          // the six epilogues of the public ABI
-    const bool ring = abi && (!split || epi == OBTE_EPI_NONE || epi == OBTE_EPI_ADD);
+    const bool ring = (abi && (!split || epi == OBTE_EPI_NONE || epi == OBTE_EPI_ADD)) || (epi == OBTE_EPI_ACC32 && !ak && !bk);
     switch (s) {
         case 1: return bn == 128 && abi && !split;                                             // gemm_bf16_v1.hip
         case 2: return bn == 192 ? ak && bk && abi && !split && epi != OBTE_EPI_GELU_BWD         // gemm_bf16_v2.hip
@@ -189,6 +191,7 @@ int gemm_dispatch_epi(int epi, bool split, F& f) {
         case OBTE_EPI_ADD_DROPOUT: return gemm_form<S, BN, AK, BK, OBTE_EPI_ADD_DROPOUT, false>(f);
         case OBTE_EPI_ROPE_QK: return gemm_form<S, BN, AK, BK, OBTE_EPI_ROPE_QK, false>(f);
         case OBTE_EPI_ROWDOT: return gemm_form<S, BN, AK, BK, OBTE_EPI_ROWDOT, false>(f);
+        case OBTE_EPI_ACC32: return gemm_form<S, BN, AK, BK, OBTE_EPI_ACC32, false>(f);
     }
     return gemm_no_form(S, BN, AK, BK, epi, false);
 }
@@ -217,4 +220,5 @@ int obte_gemm_v3_launch(const obte_gemm_v2::GemmParams& p, bool ak, bool bk, int
 int obte_gemm_v4_launch(const obte_gemm_v2::GemmParams& p, bool ak, bool bk, int epi, hipStream_t st);
 int obte_gemm_v7_launch(const obte_gemm_v2::GemmParams& p, bool ak, bool bk, int epi, hipStream_t st);                     // gemm_bf16_v7.hip
 int obte_gemm_splitk_reduce(const obte_gemm_v2::GemmParams& p, const bf16* aux, hipStream_t st);   // after a split-K launch: p.d = alpha x the sum of the slabs (+ aux)
+int obte_gemm_splitk_reduce_acc32(const obte_gemm_v2::GemmParams& p, hipStream_t st);              // the same for OBTE_EPI_ACC32: p.acc32 (+)= alpha x the sum, p.d on LAST
 int obte_gemm_group_launch(const obte_gemm_v2::GroupParams& gp, hipStream_t st);

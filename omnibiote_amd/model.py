@@ -109,6 +109,12 @@ def _require_hip(t: torch.Tensor, what: str) -> None:
 #       total is bf16(sum in fp32) — closer to the exact gradient than autograd's running bf16 sum, not bitwise equal to it.
 #   store: who owns those fp32 buffers (one ``LnPartialStore`` per TrainStep; a process-wide default for bare uses of the
 #       context manager).
+#   acc32_mode: every WEIGHT gradient (the blocks' four matrices, the readout, the embedding) summed in fp32 over the passes of one
+#       optimizer step, opt-in: each weight has a persistent fp32 buffer of its own shape in ``acc32_store`` (a ``Fp32GradStore``);
+#       the pass with L.ACC32_FIRST stores its contribution there before any rounding to bf16, L.ACC32_MORE adds, L.ACC32_LAST
+#       adds and hands bf16(buffer) to autograd — ``param.grad`` stays None until then and is rounded once.  0 = off.  Replaces
+#       ``accumulate`` (both at once is an error); the LayerNorm weights go with ``ln_mode``, which the harness starts at the
+#       first pass in this mode.
 import contextvars
 import os
 
@@ -130,6 +136,29 @@ class LnPartialStore:
         bufs = self._bufs
         self._bufs[key] = (weakref.ref(param, lambda _r, k=key: bufs.pop(k, None)), buf)
         return buf
+
+
+class Fp32GradStore:
+    """fp32 buffers of the weights whose gradients are summed in fp32 over the passes of a step (GradPolicy.acc32_mode), one of
+    the parameter's shape each, keyed by the parameter's identity with a weak reference like LnPartialStore: never an attribute
+    of the parameter or the module (4 bytes per parameter of scratch that no checkpoint or pickle of the model may carry), and
+    released when the parameter dies.  Scratch within one optimizer step: the first pass overwrites, nothing reads it later."""
+
+    def __init__(self):
+        self._bufs = {}   # id(weight) -> (weak reference to it, buffer)
+
+    def get(self, param):
+        key = id(param)
+        ent = self._bufs.get(key)
+        if ent is not None and ent[0]() is param and ent[1].device == param.device and ent[1].shape == param.shape:
+            return ent[1]
+        buf = torch.empty(param.shape, dtype=torch.float32, device=param.device)
+        bufs = self._bufs
+        self._bufs[key] = (weakref.ref(param, lambda _r, k=key: bufs.pop(k, None)), buf)
+        return buf
+
+    def __len__(self):
+        return len(self._bufs)
 
 
 class BackwardOrder:
@@ -160,13 +189,20 @@ class BackwardOrder:
 
 class GradPolicy:
     """Immutable snapshot of the switches above; what an autograd node keeps in ``ctx.pol``."""
-    __slots__ = ("accumulate", "ln_mode", "store", "order")
+    __slots__ = ("accumulate", "ln_mode", "store", "order", "acc32_mode", "acc32_store")
 
-    def __init__(self, accumulate: bool = False, ln_mode: int = 0, store: Optional[LnPartialStore] = None, order: Optional[BackwardOrder] = None):
+    def __init__(self, accumulate: bool = False, ln_mode: int = 0, store: Optional[LnPartialStore] = None, order: Optional[BackwardOrder] = None,
+                 acc32_mode: int = 0, acc32_store: Optional[Fp32GradStore] = None):
+        if acc32_mode and accumulate:
+            raise ValueError("GradPolicy: acc32_mode (the fp32 sum) replaces accumulate (the bf16 sum in param.grad)")
+        if acc32_mode not in (0, L.ACC32_FIRST, L.ACC32_MORE, L.ACC32_LAST):
+            raise ValueError(f"GradPolicy: acc32_mode must be 0 or L.ACC32_*, got {acc32_mode}")
         object.__setattr__(self, "accumulate", bool(accumulate))
         object.__setattr__(self, "ln_mode", int(ln_mode))
         object.__setattr__(self, "store", store)
         object.__setattr__(self, "order", order)
+        object.__setattr__(self, "acc32_mode", int(acc32_mode))
+        object.__setattr__(self, "acc32_store", acc32_store)
 
     def __setattr__(self, *a):
         raise AttributeError("GradPolicy is immutable: enter accumulate_grads_inplace(...) for different switches")
@@ -175,6 +211,7 @@ class GradPolicy:
 _NO_POLICY = GradPolicy()
 _policy = contextvars.ContextVar("obte_grad_policy", default=_NO_POLICY)
 _default_store = LnPartialStore()
+_default_acc32_store = Fp32GradStore()
 _embedding_order = contextvars.ContextVar("obte_embedding_order", default=None)
 
 
@@ -185,10 +222,13 @@ def current_grad_policy() -> GradPolicy:
 
 class accumulate_grads_inplace:
     """``with accumulate_grads_inplace(enabled, ln_partial_mode, store=...)``: graphs BUILT inside deliver their gradients
-    that way when they run backward (inside the block or later, on whatever thread)."""
+    that way when they run backward (inside the block or later, on whatever thread).  acc32_mode (L.ACC32_*) + acc32_store: the
+    weight gradients are summed in fp32 instead (``enabled`` must then be False)."""
 
-    def __init__(self, enabled: bool = True, ln_partial_mode: int = 0, store: Optional[LnPartialStore] = None, order: Optional[BackwardOrder] = None):
-        self.pol = GradPolicy(enabled, ln_partial_mode, store if store is not None else _default_store, order)
+    def __init__(self, enabled: bool = True, ln_partial_mode: int = 0, store: Optional[LnPartialStore] = None, order: Optional[BackwardOrder] = None,
+                 acc32_mode: int = 0, acc32_store: Optional[Fp32GradStore] = None):
+        self.pol = GradPolicy(enabled, ln_partial_mode, store if store is not None else _default_store, order, acc32_mode,
+                              (acc32_store if acc32_store is not None else _default_acc32_store) if acc32_mode else None)
 
     def __enter__(self):
         self.token = _policy.set(self.pol)
@@ -231,6 +271,13 @@ def _grad_slot(param, pol: Optional[GradPolicy] = None):
     if g is None or g.dtype != param.dtype or not g.is_contiguous() or g.shape != param.shape:
         return None
     return g
+
+
+def _acc32(param, pol: Optional[GradPolicy]):
+    """(fp32 buffer of ``param``, mode) as the ops take them when the node's policy sums weight gradients in fp32, else (None, 0)."""
+    if pol is None or not pol.acc32_mode:
+        return None, 0
+    return (pol.acc32_store if pol.acc32_store is not None else _default_acc32_store).get(param), pol.acc32_mode
 
 
 def _ord_wait(pol: Optional[GradPolicy], key) -> None:
@@ -287,15 +334,16 @@ class _LinearFn(torch.autograd.Function):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         dx = dw = None
         _ord_wait(ctx.pol, id(ctx.w_param))
+        a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
         if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
-            dx, dw = ops.linear_bwd(dy2, x2, w, alpha=ctx.alpha, accumulate_into=_grad_slot(ctx.w_param, ctx.pol))
+            dx, dw = ops.linear_bwd(dy2, x2, w, alpha=ctx.alpha, accumulate_into=_grad_slot(ctx.w_param, ctx.pol), acc32=a32, acc32_mode=a32_mode)
             _ord_done(ctx.pol, id(ctx.w_param))
             return dx.view_as(x), dw, None
         if ctx.needs_input_grad[0]:
             dx = ops.linear_dgrad(dy2, w, alpha=ctx.alpha).view_as(x)
         if ctx.needs_input_grad[1]:
             slot = _grad_slot(ctx.w_param, ctx.pol)
-            dw = ops.linear_wgrad(dy2, x2, alpha=ctx.alpha, accumulate_into=slot)
+            dw = ops.linear_wgrad(dy2, x2, alpha=ctx.alpha, accumulate_into=slot, acc32=a32, acc32_mode=a32_mode)
             if slot is not None:
                 dw = None
         _ord_done(ctx.pol, id(ctx.w_param))
@@ -321,7 +369,8 @@ class _LinearGeluFn(torch.autograd.Function):
         dh = dact.reshape(-1, dact.shape[-1]) * der            # bf16(dact * gelu'(h)), as OBTE_EPI_GELU_BWD forms it
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         _ord_wait(ctx.pol, id(ctx.w_param))
-        dx, dw = ops.linear_bwd(dh.contiguous(), x2, w, accumulate_into=_grad_slot(ctx.w_param, ctx.pol))
+        a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
+        dx, dw = ops.linear_bwd(dh.contiguous(), x2, w, accumulate_into=_grad_slot(ctx.w_param, ctx.pol), acc32=a32, acc32_mode=a32_mode)
         _ord_done(ctx.pol, id(ctx.w_param))
         return dx.view_as(x), dw
 
@@ -347,9 +396,31 @@ class _ReadoutRowsGradFn(torch.autograd.Function):
         emb_rows, w, dl = ctx.saved_tensors
         _ord_wait(ctx.pol, id(ctx.w_param))
         slot = _grad_slot(ctx.w_param, ctx.pol)
-        dx, dw = ops.linear_bwd(dl, emb_rows.contiguous(), w, alpha=ctx.alpha, accumulate_into=slot)
+        a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
+        dx, dw = ops.linear_bwd(dl, emb_rows.contiguous(), w, alpha=ctx.alpha, accumulate_into=slot, acc32=a32, acc32_mode=a32_mode)
         _ord_done(ctx.pol, id(ctx.w_param))
         return dx, dw, None, None
+
+
+class _Acc32FlushFn(torch.autograd.Function):
+    """Backward-only node for a weight whose own node does not run in a pass while its gradient is summed in fp32 (the readout
+    weight in a pass with nothing masked): the zero contribution by the pass's mode — FIRST zeroes the buffer, MORE leaves it,
+    LAST hands bf16(buffer), the total of the other passes, to autograd (and through it to DDP's reducer).  forward() returns a
+    zero scalar to add to whatever the pass runs backward from."""
+
+    @staticmethod
+    def forward(ctx, w):
+        ctx.w_param = w
+        ctx.pol = current_grad_policy()
+        return torch.zeros((), dtype=torch.float32, device=w.device)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        _ord_wait(ctx.pol, id(ctx.w_param))
+        a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
+        dw = ops.acc32_add_(a32, None, a32_mode)
+        _ord_done(ctx.pol, id(ctx.w_param))
+        return dw
 
 
 class _EmbeddingFn(torch.autograd.Function):
@@ -367,8 +438,9 @@ class _EmbeddingFn(torch.autograd.Function):
     def backward(ctx, dout):
         (idx,) = ctx.saved_tensors
         _ord_wait(ctx.pol, id(ctx.w_param))
+        a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
         dw = ops.embedding_bwd(idx.contiguous(), dout.contiguous(), ctx.vocab, accumulate_into=_grad_slot(ctx.w_param, ctx.pol),
-                               dropout_p=ctx.drop[0], dropout_seed=ctx.drop[1], order=ctx.order)
+                               dropout_p=ctx.drop[0], dropout_seed=ctx.drop[1], order=ctx.order, acc32=a32, acc32_mode=a32_mode)
         _ord_done(ctx.pol, id(ctx.w_param))
         return None, dw, None, None, None
 
@@ -433,7 +505,9 @@ class _BlockFn(torch.autograd.Function):
         dy_masked = ctx.handoff.take(ctx.index, dy, ctx.drop) if (ctx.drop[0] > 0 and ctx.handoff is not None) else None
         res = ops.block_bwd(x, dy, act, tuple(params), (rope_cos, rope_sin), ctx.n_head, ctx.mask,
                             accumulate_into=slots, dropout_p=ctx.drop[0], dropout_seed=ctx.drop[1], ln_partials=lnp,
-                            ln_partial_mode=pol.ln_mode, out_rows=ctx.out_rows, dy_masked=dy_masked, dx_mask_seed=ctx.below_seed)
+                            ln_partial_mode=pol.ln_mode, out_rows=ctx.out_rows, dy_masked=dy_masked, dx_mask_seed=ctx.below_seed,
+                            acc32=tuple(_acc32(ctx.w_params[i], pol)[0] for i in (1, 2, 4, 5)) if pol.acc32_mode else None,
+                            acc32_mode=pol.acc32_mode)
         dx, grads = res[0], res[1]
         if ctx.below_seed is not None:
             ctx.handoff.put(ctx.index - 1, dx, res[2], ctx.drop[0], ctx.below_seed)

@@ -102,15 +102,51 @@ def layernorm_bwd(dy, x, w, mean, rstd, dresid=None, accumulate_into=None, parti
 
 
 # --------------------------------------------------------------------------------------------------------- GEMM
+def _check_acc32(acc32, acc32_mode, shape, name="acc32"):
+    """The fp32 buffer of a gradient summed over the passes of a step (L.ACC32_*): the gradient's shape, persistent, caller-owned."""
+    if acc32_mode not in (L.ACC32_FIRST, L.ACC32_MORE, L.ACC32_LAST):
+        raise ValueError(f"acc32_mode must be L.ACC32_FIRST, _MORE or _LAST with an acc32 buffer, got {acc32_mode}")
+    _need(acc32, name, torch.float32)
+    if tuple(acc32.shape) != tuple(shape):
+        raise RuntimeError(f"{name}: expected the gradient's shape {tuple(shape)}, got {tuple(acc32.shape)}")
+
+
+def acc32_add_(acc32, src, mode, out=None):
+    """acc32 (+)= src by mode (L.ACC32_*; FIRST: acc32 = src); src None: a zero contribution.  LAST returns bf16(acc32) (in
+    ``out`` when given), the others None.  The unfused form of the fp32 gradient sum (obte_acc32_add_bf16): for a gradient
+    the fused epilogues cannot take, and the flush of a weight whose backward node did not run in a pass."""
+    _check_acc32(acc32, mode, acc32.shape)
+    n = acc32.numel()
+    if src is not None:
+        _need(src, "src"); assert src.numel() == n
+    if mode == L.ACC32_LAST:
+        out = torch.empty(acc32.shape, dtype=bf16, device=acc32.device) if out is None else out
+        _need(out, "out"); assert out.numel() == n
+    else:
+        out = None
+    L.check(L.lib().obte_acc32_add_bf16(_ptr(acc32), _ptr(src), _ptr(out), n, int(mode), _stream()), "obte_acc32_add_bf16")
+    return out
+
+
 def gemm(a, b, M, N, K, a_kmajor=True, b_kmajor=True, epilogue=L.EPI_NONE, aux=None, alpha=1.0, out=None, dropout=None,
-         rope=None):
+         rope=None, acc32=None, acc32_mode=0):
     """D[M,N] = epilogue(alpha * sum_k A(m,k) B(n,k)); see include/omnibiote_hip.h.  Returns d, or (d, d2) for
-    the GELU epilogue."""
+    the GELU epilogue.  EPI_ACC32 (acc32 fp32 [M,N] + acc32_mode): d is formed by L.ACC32_LAST only, else None is returned."""
     _need(a, "a"); _need(b, "b")
     lda = K if a_kmajor else M
     ldb = K if b_kmajor else N
     assert a.numel() == M * K, (a.shape, M, K)
     assert b.numel() == N * K, (b.shape, N, K)
+    if epilogue == L.EPI_ACC32:
+        _check_acc32(acc32, acc32_mode, (M, N))
+        assert not a_kmajor and not b_kmajor, "EPI_ACC32: the weight-gradient layout only"
+        if acc32_mode != L.ACC32_LAST:
+            g = L.GemmArgs(_ptr(a), _ptr(b), None, None, None, M, N, K, lda, ldb, N, 0, 0, epilogue, float(alpha), 0.0, 0, 0)
+            g.acc32, g.acc32_mode = _ptr(acc32), int(acc32_mode)
+            _gemm_launch(g, M, N, K, True, a.device)
+            return None
+    else:
+        assert acc32 is None and not acc32_mode, "acc32 / acc32_mode go with EPI_ACC32"
     d = out if out is not None else torch.empty((M, N), dtype=bf16, device=a.device)
     _need(d, "d"); assert d.numel() == M * N
     d2 = None
@@ -126,31 +162,57 @@ def gemm(a, b, M, N, K, a_kmajor=True, b_kmajor=True, epilogue=L.EPI_NONE, aux=N
         _need(cos, "cos", torch.float32); _need(sin, "sin", torch.float32)
         assert cos.shape[0] >= rT and cos.shape[-1] == rhs // 2
         g.rope_cos, g.rope_sin, g.rope_T, g.rope_head_dim = _ptr(cos), _ptr(sin), rT, rhs
-    ws_bytes = int(L.lib().obte_gemm_workspace_bytes(M, N, K)) if (epilogue in (L.EPI_NONE, L.EPI_ADD) and M * N <= (1 << 23)) else 0
+    if epilogue == L.EPI_ACC32:
+        g.acc32, g.acc32_mode = _ptr(acc32), int(acc32_mode)
+    _gemm_launch(g, M, N, K, epilogue in (L.EPI_NONE, L.EPI_ADD, L.EPI_ACC32), a.device)
+    return (d, d2) if d2 is not None else d
+
+
+def _gemm_launch(g, M, N, K, may_split, device):
+    ws_bytes = int(L.lib().obte_gemm_workspace_bytes(M, N, K)) if (may_split and M * N <= (1 << 23)) else 0
     if ws_bytes > 0:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
         L.check(L.lib().obte_gemm_bf16_ws(C.byref(g), _ptr(ws), ws_bytes, _stream()), "obte_gemm_bf16_ws")
     else:
         L.check(L.lib().obte_gemm_bf16(C.byref(g), _stream()), "obte_gemm_bf16")
-    return (d, d2) if d2 is not None else d
 
 
 def gemm_grouped(problems):
     """Up to six GEMMs in a single launch (obte_gemm_grouped_bf16).  ``problems`` is a list of dicts with keys
     a, b, M, N, K, out and optionally a_kmajor / b_kmajor (default False: the weight-gradient layout) and accumulate
-    (out += alpha A B in place) / alpha.  Put the problems with the longest K first.  Returns the outs."""
+    (out += alpha A B in place) / alpha.  A problem in the weight-gradient layout may carry acc32 (fp32 [M,N]) + acc32_mode
+    (L.ACC32_*) instead: summed into that buffer (EPI_ACC32), ``out`` needed and written by L.ACC32_LAST only (None otherwise).
+    Put the problems with the longest K first.  Returns the outs."""
     assert 1 <= len(problems) <= 6
     arr = (L.GemmArgs * len(problems))()
+    outs = []
     for i, q in enumerate(problems):
-        a, b, M, N, K, out = q["a"], q["b"], q["M"], q["N"], q["K"], q["out"]
+        a, b, M, N, K, out = q["a"], q["b"], q["M"], q["N"], q["K"], q.get("out")
         ak, bk, acc = bool(q.get("a_kmajor", False)), bool(q.get("b_kmajor", False)), bool(q.get("accumulate", False))
-        _need(a, "a"); _need(b, "b"); _need(out, "out")
-        assert a.numel() == M * K and b.numel() == N * K and out.numel() == M * N
+        acc32, mode = q.get("acc32"), int(q.get("acc32_mode", 0) or 0)
+        _need(a, "a"); _need(b, "b")
+        assert a.numel() == M * K and b.numel() == N * K
+        epi = L.EPI_ADD if acc else L.EPI_NONE
+        if acc32 is not None or mode:
+            _check_acc32(acc32, mode, (M, N))
+            assert not ak and not bk and not acc, "acc32: the weight-gradient layout, no bf16 accumulation"
+            epi = L.EPI_ACC32
+            if mode != L.ACC32_LAST:
+                out = None
+            elif out is None:
+                out = torch.empty((M, N), dtype=bf16, device=a.device)
+        if out is not None:
+            _need(out, "out"); assert out.numel() == M * N
+        else:
+            assert epi == L.EPI_ACC32, "out is needed"
         arr[i] = L.GemmArgs(_ptr(a), _ptr(b), _ptr(out), _ptr(out) if acc else None, None, M, N, K,
                             K if ak else M, K if bk else N, N, int(ak), int(bk),
-                            L.EPI_ADD if acc else L.EPI_NONE, float(q.get("alpha", 1.0)), 0.0, 0, 0)
+                            epi, float(q.get("alpha", 1.0)), 0.0, 0, 0)
+        if epi == L.EPI_ACC32:
+            arr[i].acc32, arr[i].acc32_mode = _ptr(acc32), mode
+        outs.append(out)
     L.check(L.lib().obte_gemm_grouped_bf16(arr, len(problems), _stream()), "obte_gemm_grouped_bf16")
-    return [q["out"] for q in problems]
+    return outs
 
 
 def linear_fwd(x2d, w, epilogue=L.EPI_NONE, aux=None, alpha=1.0, dropout=None):
@@ -179,11 +241,16 @@ def linear_dgrad(dy2d, w, epilogue=L.EPI_NONE, aux=None, alpha=1.0):
     return gemm(dy2d, w, M, K, N, True, False, epilogue, aux, alpha)
 
 
-def linear_wgrad(dy2d, x2d, alpha=1.0, accumulate_into=None):
-    """dW = dy^T x for dy [M,N], x [M,K] -> [N,K].  accumulate_into: add into this tensor in place (alpha must be 1)."""
+def linear_wgrad(dy2d, x2d, alpha=1.0, accumulate_into=None, acc32=None, acc32_mode=0):
+    """dW = dy^T x for dy [M,N], x [M,K] -> [N,K].  accumulate_into: add into this tensor in place (alpha must be 1).
+    acc32 (fp32 [N,K]) + acc32_mode (L.ACC32_*): the contribution alpha dy^T x goes into that buffer before any rounding to
+    bf16; returns None for FIRST / MORE and bf16(acc32), the total, for LAST."""
     M, N = dy2d.shape
     K = x2d.shape[1]
     assert x2d.shape[0] == M
+    if acc32 is not None or acc32_mode:
+        assert accumulate_into is None, "acc32 replaces accumulate_into"
+        return gemm(dy2d, x2d, N, K, M, False, False, L.EPI_ACC32, None, alpha, acc32=acc32, acc32_mode=acc32_mode)
     if accumulate_into is not None:
         return gemm(dy2d, x2d, N, K, M, False, False, L.EPI_ADD, accumulate_into, alpha, out=accumulate_into)
     return gemm(dy2d, x2d, N, K, M, False, False, L.EPI_NONE, None, alpha)
@@ -203,16 +270,22 @@ def linear_bwd_pair_is_grouped(M, N, K) -> bool:
     return os.environ.get("OBTE_GROUPED_LM", "") == "1" and M >= 128 and N >= 128
 
 
-def linear_bwd(dy2d, x2d, w, alpha=1.0, accumulate_into=None):
-    """Both gradients of y = alpha x W^T: dx = alpha dy W, dW = alpha dy^T x (added into ``accumulate_into`` when given).
+def linear_bwd(dy2d, x2d, w, alpha=1.0, accumulate_into=None, acc32=None, acc32_mode=0):
+    """Both gradients of y = alpha x W^T: dx = alpha dy W, dW = alpha dy^T x (added into ``accumulate_into`` when given; summed
+    into the fp32 buffer ``acc32`` by ``acc32_mode`` as in linear_wgrad: dW is then None for FIRST / MORE, the total for LAST).
     Returns (dx, dW or None).  One grouped launch when linear_bwd_pair_is_grouped, else the two single launches."""
     M, N = dy2d.shape
     K = x2d.shape[1]
     if not linear_bwd_pair_is_grouped(M, N, K):
         dx = linear_dgrad(dy2d, w, alpha=alpha)
-        dw = linear_wgrad(dy2d, x2d, alpha=alpha, accumulate_into=accumulate_into)
+        dw = linear_wgrad(dy2d, x2d, alpha=alpha, accumulate_into=accumulate_into, acc32=acc32, acc32_mode=acc32_mode)
         return dx, (None if accumulate_into is not None else dw)
     dx = torch.empty((M, K), dtype=bf16, device=dy2d.device)
+    if acc32 is not None or acc32_mode:
+        assert accumulate_into is None, "acc32 replaces accumulate_into"
+        outs = gemm_grouped([dict(a=dy2d, b=w, M=M, N=K, K=N, out=dx, a_kmajor=True, alpha=alpha),
+                             dict(a=dy2d, b=x2d, M=N, N=K, K=M, acc32=acc32, acc32_mode=acc32_mode, alpha=alpha)])
+        return dx, outs[1]
     dw = accumulate_into if accumulate_into is not None else torch.empty((N, K), dtype=bf16, device=dy2d.device)
     gemm_grouped([dict(a=dy2d, b=w, M=M, N=K, K=N, out=dx, a_kmajor=True, alpha=alpha),
                   dict(a=dy2d, b=x2d, M=N, N=K, K=M, out=dw, accumulate=accumulate_into is not None, alpha=alpha)])
@@ -338,10 +411,12 @@ def embedding_fwd(idx, wte, dropout_p=0.0, dropout_seed=0):
     return out
 
 
-def embedding_bwd(idx, dout, vocab, accumulate_into=None, dropout_p=0.0, dropout_seed=0, order=None):
+def embedding_bwd(idx, dout, vocab, accumulate_into=None, dropout_p=0.0, dropout_seed=0, order=None, acc32=None, acc32_mode=0):
     """accumulate_into: an existing dense (vocab, C) gradient; the touched rows are updated in place
     (bf16(old + bf16(sum))), nothing else is read or written.  order: a stable argsort of idx.reshape(-1) as int32, if
-    the caller has one already (the harness sorts a whole optimizer step's ids in one call)."""
+    the caller has one already (the harness sorts a whole optimizer step's ids in one call).
+    acc32 (fp32 (vocab, C)) + acc32_mode (L.ACC32_*): the rows' fp32 sums go into that buffer before any rounding (FIRST zeroes it
+    first); returns None for FIRST / MORE and bf16(acc32) for LAST."""
     _need(idx, "idx", torch.int64); _need(dout, "dout")
     rows, Cc = idx.numel(), dout.shape[-1]
     if order is None:
@@ -352,6 +427,13 @@ def embedding_bwd(idx, dout, vocab, accumulate_into=None, dropout_p=0.0, dropout
     else:
         _need(order, "order", torch.int32); assert order.numel() == rows
     ws = torch.empty(max(int(L.lib().obte_embedding_bwd_ws_bytes(rows, Cc)), 16), dtype=torch.uint8, device=dout.device)
+    if acc32 is not None or acc32_mode:
+        assert accumulate_into is None, "acc32 replaces accumulate_into"
+        _check_acc32(acc32, acc32_mode, (vocab, Cc))
+        dwte = torch.empty((vocab, Cc), dtype=bf16, device=dout.device) if acc32_mode == L.ACC32_LAST else None
+        L.check(L.lib().obte_embedding_bwd_acc32(_ptr(idx), _ptr(order), _ptr(dout), _ptr(acc32), _ptr(dwte), _ptr(ws), rows, Cc, vocab,
+                                                  int(acc32_mode), float(dropout_p), int(dropout_seed), _stream()), "obte_embedding_bwd_acc32")
+        return dwte
     if accumulate_into is not None:
         _need(accumulate_into, "grad"); assert tuple(accumulate_into.shape) == (vocab, Cc)
         L.check(L.lib().obte_embedding_bwd_dropout(_ptr(idx), _ptr(order), _ptr(dout), _ptr(accumulate_into), _ptr(ws), rows, Cc,
@@ -491,16 +573,18 @@ def sumsq_(g, out):
 
 # -------------------------------------------------------------------------------------------------------- block
 def _block_desc(B, T, Cc, H, params, rope, mask: MaskSpec, dropout_p=0.0, dropout_seed=0, ln_partials=None, ln_partial_mode=0, out_rows=None,
-                dy_masked=None, dx_masked=None, dx_mask_seed=0):
+                dy_masked=None, dx_masked=None, dx_mask_seed=0, acc32=None, acc32_mode=0):
     ln1, attn_w, proj_w, ln2, fc_w, mlp_w = params
     p1, p2 = ln_partials if ln_partials is not None else (None, None)
     if out_rows is not None:
         _need(out_rows, "out_rows", torch.int64)
         assert 0 < out_rows.numel() <= B * T, "the rows form of the block: a non-empty list of positions"
+    a32 = acc32 if acc32_mode else (None, None, None, None)   # the four matrices' fp32 sums: attn, proj, fc, mlp
     return L.BlockDesc(B, T, Cc, H, _ptr(ln1), _ptr(attn_w), _ptr(proj_w), _ptr(ln2), _ptr(fc_w), _ptr(mlp_w),
                        _ptr(rope[0]), _ptr(rope[1]), _ptr(mask.ranges), _ptr(mask.dense), mask.sb, mask.sh, mask.sq,
                        float(dropout_p), int(dropout_seed), _ptr(mask.qbounds), _ptr(p1), _ptr(p2), int(ln_partial_mode), _ptr(mask.exact),
-                       _ptr(out_rows), 0 if out_rows is None else out_rows.numel(), _ptr(dy_masked), _ptr(dx_masked), int(dx_mask_seed))
+                       _ptr(out_rows), 0 if out_rows is None else out_rows.numel(), _ptr(dy_masked), _ptr(dx_masked), int(dx_mask_seed),
+                       _ptr(a32[0]), _ptr(a32[1]), _ptr(a32[2]), _ptr(a32[3]), int(acc32_mode))
 
 
 def block_fwd(x, params, rope, H, mask: MaskSpec, dropout_p=0.0, dropout_seed=0, out_rows=None):
@@ -522,7 +606,7 @@ def block_fwd(x, params, rope, H, mask: MaskSpec, dropout_p=0.0, dropout_seed=0,
 
 
 def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None, dropout_p=0.0, dropout_seed=0, ln_partials=None,
-              ln_partial_mode=0, out_rows=None, dy_masked=None, dx_mask_seed=None):
+              ln_partial_mode=0, out_rows=None, dy_masked=None, dx_mask_seed=None, acc32=None, acc32_mode=0):
     """accumulate_into: optional list of 6 tensors-or-None (same order as params).  When the four matrix entries are all
     given, their gradients are added into those tensors in place and the corresponding returned grads are None; the
     same, independently, for the two LayerNorm weights (entries 0 and 3).
@@ -530,13 +614,22 @@ def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None,
     calls in those fp32 buffers instead (see layernorm_bwd); their returned grads are None except with LN_PARTIAL_LAST.
     Dropout hand-off between blocks (include/omnibiote_hip.h, obte_block_desc::dy_masked): dy_masked = dropout(dy) under THIS
     block's (seed, site 3) mask if the block above already wrote it; dx_mask_seed = the seed of the block BELOW: then
-    dropout(dx) under that block's mask is written too and returned as a third value (else None)."""
+    dropout(dx) under that block's mask is written too and returned as a third value (else None).
+    acc32=(attn, proj, fc, mlp) fp32 buffers of those four weights' shapes + acc32_mode (L.ACC32_*): the four matrix gradients are
+    summed into them over calls, before any rounding to bf16 (include/omnibiote_hip.h, OBTE_EPI_ACC32); their returned grads are
+    None for FIRST / MORE and bf16(buffer) for LAST.  The LayerNorm weights keep ln_partials."""
     _need(x, "x"); _need(dy, "dy")
     B, T, Cc = x.shape
     assert dy.numel() == (B * T if out_rows is None else out_rows.numel()) * Cc, "dy: one row per (wanted) position"
     ws = torch.empty(int(L.lib().obte_block_bwd_ws_bytes(B, T, Cc, H)), dtype=torch.uint8, device=x.device)
     dx = torch.empty_like(x)
     acc = accumulate_into is not None and all(accumulate_into[i] is not None for i in (1, 2, 4, 5))
+    if acc32 is not None or acc32_mode:
+        assert not acc, "acc32 replaces accumulate_into for the four matrices"
+        assert acc32 is not None and len(acc32) == 4
+        for t, i in zip(acc32, (1, 2, 4, 5)):
+            _check_acc32(t, acc32_mode, params[i].shape)
+    w32_none = acc32_mode in (L.ACC32_FIRST, L.ACC32_MORE)
     acc_ln = (not ln_partial_mode) and accumulate_into is not None and all(accumulate_into[i] is not None for i in (0, 3))
     if ln_partial_mode:
         for t in ln_partials:
@@ -548,17 +641,19 @@ def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None,
             g = accumulate_into[i]
             _need(g, "grad"); assert g.shape == w.shape
             grads.append(g)
+        elif w32_none and i in (1, 2, 4, 5):
+            grads.append(None)        # (not written before the last pass)
         else:
             grads.append(torch.empty_like(w))
     dx_masked = torch.empty_like(x) if (dx_mask_seed is not None and dropout_p > 0.0) else None
     if dy_masked is not None:
         _need(dy_masked, "dy_masked"); assert dy_masked.numel() == dy.numel() and dropout_p > 0.0
     d = _block_desc(B, T, Cc, H, params, rope, mask, dropout_p, dropout_seed, ln_partials, ln_partial_mode, out_rows=out_rows,
-                    dy_masked=dy_masked, dx_masked=dx_masked, dx_mask_seed=dx_mask_seed or 0)
+                    dy_masked=dy_masked, dx_masked=dx_masked, dx_mask_seed=dx_mask_seed or 0, acc32=acc32, acc32_mode=acc32_mode)
     L.check(L.lib().obte_block_bwd_acc(C.byref(d), _ptr(x), _ptr(dy), _ptr(act), _ptr(ws), _ptr(dx), *[_ptr(g) for g in grads],
                                         int(acc) + 2 * int(acc_ln), _stream()), "obte_block_bwd")
     ln_none = ln_partial_mode in (L.LN_PARTIAL_FIRST, L.LN_PARTIAL_MORE)
-    grads = [None if ((acc and i in (1, 2, 4, 5)) or ((acc_ln or ln_none) and i in (0, 3))) else g for i, g in enumerate(grads)]
+    grads = [None if (((acc or w32_none) and i in (1, 2, 4, 5)) or ((acc_ln or ln_none) and i in (0, 3))) else g for i, g in enumerate(grads)]
     if dx_mask_seed is not None:
         return dx, grads, dx_masked
     return dx, grads

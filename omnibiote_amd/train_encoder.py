@@ -22,7 +22,9 @@ Changed on purpose (same mathematics, MI355X-first mechanics):
     reduced with one small device all-reduce instead of two pickled gloo all_gather_object calls (:335,354);
   * clip + AdamW run as fused kernels without a host sync (the clip coefficient stays on the device).
 Added beyond the reference, off by default: ``--master_weights`` — fp32 master weights and fp32 moments behind the bf16 parameters
-(FusedAdamW(master_weights=True)); the masters travel inside the optimizer checkpoint and ``--resume_from`` restores them.
+(FusedAdamW(master_weights=True)); the masters travel inside the optimizer checkpoint and ``--resume_from`` restores them;
+``--fp32_grad_accum`` — every weight gradient summed over the micro-batches of a step in fp32 and rounded to bf16 once
+(TrainStep(grad_accum="fp32")) instead of after every micro-batch, as autograd's ``grad += new`` does (:284-311).
 Data: with ``--base_dir`` pointing at the reference's directory layout (``genbank/train``, ``uniref100/train`` ... of
 ``.npy`` token shards, train_encoder.py:70-99) batches come from ``omnibiote_amd.loader`` (same packing and mixing as the
 reference loader, loader thread + bounded queue, pinned-memory copies on their own stream); otherwise from synthetic rows
@@ -314,8 +316,16 @@ class TrainStep:
                  loss_impl: str = "fused", mask_impl: str = "ranges", sync_every_micro_step: bool = False,
                  max_grad_norm: float = 1.0, lm_head_impl: str = "masked", pipeline_streams: int = 1,
                  fused_loss_fn: Optional[Callable] = None, micro_batches_per_pass: int = 1, backward_order: str = "layer",
-                 rows_forward: bool = True):
-        """fused_loss_fn: ``(logits, targets, mlm_mask, n_accum) -> (loss, dlogits)`` used by loss_impl="fused" instead of
+                 rows_forward: bool = True, grad_accum: str = "bf16"):
+        """grad_accum: "bf16" (default) — the reference's arithmetic: every micro-batch's weight gradient is rounded to bf16 and
+        added to a bf16 running sum (autograd's ``grad += new``; here the wgrad epilogues do it in place).  "fp32" (beyond the
+        reference, --fp32_grad_accum): over the passes of a step every weight gradient is summed in a persistent fp32 buffer of
+        the weight's shape (model.Fp32GradStore, owned by this object: +4 bytes per parameter) from the contributions BEFORE
+        their rounding to bf16 — pass 0 stores, the middle passes add, the last adds and hands bf16(sum) to autograd.
+        ``param.grad`` is None until then; the optimizer, clipping, DDP buckets and checkpoints see bf16 gradients rounded once.
+        A step of a single pass runs the plain path.  Refused (ValueError, never a silent bf16 sum) with sync_every_micro_step,
+        OBTE_NO_INPLACE_ACCUM=1 / OBTE_NO_LN_PARTIALS=1, a stub or torch loss and activation checkpointing.
+        fused_loss_fn: ``(logits, targets, mlm_mask, n_accum) -> (loss, dlogits)`` used by loss_impl="fused" instead of
         the HIP kernel (ops.masked_ce) — lets the CPU multi-process tests drive the product scheduling (in-place
         accumulation, no_sync, hand-delivered d(logits)) with a stub model and a torch loss."""
         self.fused_loss_fn = fused_loss_fn
@@ -369,6 +379,30 @@ class TrainStep:
         self._host_bufs = {}
         self._order_ws = {}
         self._ln_store = None
+        if grad_accum not in ("bf16", "fp32"):
+            raise ValueError(f'grad_accum must be "bf16" or "fp32", got {grad_accum!r}')
+        self.grad_accum = grad_accum
+        self._acc32_store = None
+        self._acc32_mode = 0         # of the pass being built (0: the bf16 path)
+        if grad_accum == "fp32":
+            if sync_every_micro_step:
+                raise ValueError('grad_accum="fp32" (--fp32_grad_accum) cannot be combined with sync_every_micro_step=True: the gradient exists '
+                                 "only after the last micro-batch, there is nothing to exchange before it")
+            if loss_impl != "fused" or fused_loss_fn is not None:
+                raise ValueError('grad_accum="fp32" (--fp32_grad_accum) needs the HIP model and loss (loss_impl="fused", no fused_loss_fn): a '
+                                 "stub model or a torch loss delivers its gradients through autograd's bf16 `grad += new`")
+            core = model.module if hasattr(model, "module") else model
+            if int(getattr(getattr(core, "config", None), "checkpoint_freq", 0) or 0) > 0:
+                raise ValueError('grad_accum="fp32" (--fp32_grad_accum) cannot be combined with checkpoint_freq > 0: a recomputed block captures '
+                                 "its gradient policy on the autograd thread, outside the step's context, and would sum in bf16 unnoticed")
+            self._refuse_env_switches()
+
+    @staticmethod
+    def _refuse_env_switches() -> None:
+        for var in ("OBTE_NO_INPLACE_ACCUM", "OBTE_NO_LN_PARTIALS"):
+            if os.environ.get(var) == "1":
+                raise ValueError(f'grad_accum="fp32" (--fp32_grad_accum) cannot be combined with {var}=1: that switch sends gradients through '
+                                 "autograd's bf16 `grad += new`")
 
     @staticmethod
     def _no_inplace() -> bool:
@@ -377,7 +411,15 @@ class TrainStep:
         passes are then ordered as wholes (backward_order="pass": one event after the entire backward)."""
         return os.environ.get("OBTE_NO_INPLACE_ACCUM") == "1"
 
-    def _inplace(self, enabled: bool, ln_partial_mode: int = 0):
+    def _inplace(self, enabled: bool, ln_partial_mode: int = 0, acc32_mode: int = 0):
+        if acc32_mode:   # every gradient of the model summed in fp32 over the passes: the weights' buffers and the LayerNorm partials
+            from .model import Fp32GradStore, LnPartialStore, accumulate_grads_inplace
+            if self._ln_store is None:
+                self._ln_store = LnPartialStore()
+            if self._acc32_store is None:
+                self._acc32_store = Fp32GradStore()   # this step object's own fp32 gradient sums
+            return accumulate_grads_inplace(False, acc32_mode, store=self._ln_store, order=self._order, acc32_mode=acc32_mode,
+                                            acc32_store=self._acc32_store)
         if self.loss_impl != "fused" or self._no_inplace():   # CPU-oracle tests / A-B switch (whole-pass ordering then: __call__)
             return contextlib.nullcontext()
         from .model import LnPartialStore, accumulate_grads_inplace
@@ -470,6 +512,16 @@ class TrainStep:
         w = torch.cat([torch.full((r.numel(),), 1.0 / r.numel(), dtype=torch.float32, device=r.device) for _, r in keep])
         return rows, w
 
+    def _zero_pass_backward(self, emb, core):
+        """The backward of a pass with nothing masked: zero gradients for every parameter.  The readout's own node does not run in
+        such a pass; with the fp32 sum its weight takes the zero contribution by the pass's mode instead (model._Acc32FlushFn:
+        the first pass zeroes the buffer, the last hands the other passes' total to autograd and DDP's reducer)."""
+        if self._acc32_mode:
+            from .model import _Acc32FlushFn
+            (emb.sum() * 0 + _Acc32FlushFn.apply(core.lm_head.weight)).backward()
+        else:
+            (emb.sum() * 0 + core.lm_head.weight.sum() * 0).backward()
+
     def _dense_logits_sparse_backward(self, x, y, mk, attn_mask, n_accum, k: int = 1):
         """lm_head_impl="dense": full logits in the forward, backward over the masked rows (see __init__)."""
         from . import ops
@@ -486,7 +538,7 @@ class TrainStep:
         del logits
         self._order_backward(whole_pass=dl is None)
         if dl is None:    # nothing masked: zero gradients for every parameter (the reference would produce 0/0 = NaN here)
-            (emb.sum() * 0 + core.lm_head.weight.sum() * 0).backward()
+            self._zero_pass_backward(emb, core)
             return torch.zeros((), dtype=torch.float32, device=x.device)
         emb_rows = emb.reshape(-1, emb.shape[-1]).index_select(0, rows)
         wm = float(core.lm_head.output_mult) / float(core.lm_head.width_mult())
@@ -506,7 +558,7 @@ class TrainStep:
             # DDP's reducer would wait for it forever when this is the synchronising micro-batch
             emb = self.model(x, attn_mask=attn_mask, return_embeddings=True)
             self._order_backward(whole_pass=True)
-            (emb.sum() * 0 + core.lm_head.weight.sum() * 0).backward()
+            self._zero_pass_backward(emb, core)
             return torch.zeros((), dtype=torch.float32, device=x.device)
         if self.rows_forward:
             # the model is told which positions are wanted: the last block's MLP half and ln_f run on them alone (model.forward(rows=))
@@ -607,6 +659,9 @@ class TrainStep:
         core_model = self.model.module if hasattr(self.model, "module") else self.model
         k = self.per_pass if (sparse_rows and n_accum % self.per_pass == 0) else 1
         n_pass, span = n_accum // k, k * self.mini          # passes through the model, rows per pass
+        fp32_sum = self.grad_accum == "fp32" and n_pass >= 2   # (a single pass: the plain path, its gradient is rounded once anyway)
+        if fp32_sum:
+            self._refuse_env_switches()
         emb_orders = None
         if input_ids.is_cuda and self.loss_impl == "fused" and self.fused_loss_fn is None and hasattr(core_model, "transformer"):
             # the embedding backward sums gradient rows in sorted-token order: ONE segmented sort for all micro-batches of
@@ -673,8 +728,10 @@ class TrainStep:
                 ln_mode = 0
                 if n_pass > 2 and not self.sync_every and j >= 1:
                     ln_mode = 1 if j == 1 else (3 if last else 2)
+                # grad_accum="fp32": every weight gradient, the LayerNorm weights included, from pass 0 on — first / more / last
+                self._acc32_mode = (1 if j == 0 else (3 if last else 2)) if fp32_sum else 0
                 # (the last pass too when no reducer is attached: nothing observes its gradients before the optimizer does)
-                with ctx, ctx_order, self._inplace(not (last and hasattr(self.model, "no_sync")) and not self.sync_every, ln_mode):
+                with ctx, ctx_order, self._inplace(not (last and hasattr(self.model, "no_sync")) and not self.sync_every, ln_mode, self._acc32_mode):
                     mk = mask[j * span:(j + 1) * span]
                     if sparse_rows and self.lm_head_impl == "masked":
                         partial[self._slot] += self._masked_rows_loss_backward(x, y, mk, attn_mask, n_accum, k)
@@ -870,6 +927,10 @@ def parse_args(argv=None):
                    help="fp32 master weights and fp32 moments behind the bf16 parameters (12 instead of 4 bytes of optimizer state per "
                         "parameter; beyond the reference's pure-bf16 regime, so loss curves no longer track the reference's step for "
                         "step); they travel in the optimizer checkpoint and --resume_from restores them")
+    p.add_argument("--fp32_grad_accum", action="store_true", default=False,
+                   help="sum every weight gradient over the micro-batches of a step in fp32 and round it to bf16 once, instead of after "
+                        "every micro-batch (+4 bytes per parameter of scratch; beyond the reference's arithmetic, like --master_weights, whose "
+                        "fp32 masters it feeds with a gradient rounded once); not with --checkpoint_freq > 0")
     p.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                    help="cpu only exercises the harness plumbing: the model itself has no CPU path and says so at the first forward")
     return p.parse_args(argv)
@@ -1053,7 +1114,8 @@ def run(args):
     total_iters = int(args.token_budget / (world * batch_size * args.ctx_len))
     opt, sched = build_optimizer(m, args, total_iters, fused=on_gpu)
     step = TrainStep(model, opt, sched, mini_batch_size=args.mini_batch_size, n_head=args.n_head, use_padding=args.use_padding,
-                     pipeline_streams=getattr(args, "pipeline_streams", 1), micro_batches_per_pass=getattr(args, "micro_batches_per_pass", 1))
+                     pipeline_streams=getattr(args, "pipeline_streams", 1), micro_batches_per_pass=getattr(args, "micro_batches_per_pass", 1),
+                     grad_accum="fp32" if getattr(args, "fp32_grad_accum", False) else "bf16")
     rng = np.random.default_rng(1234 + rank)
     next_batch, source, close_source = make_batch_source(args, batch_size, device, rng)
     test_sources = make_test_sources(args, device, rng)
