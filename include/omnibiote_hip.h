@@ -126,7 +126,7 @@ enum {
                                all-zero sin = the reference's cos-only bf16 mode */
     OBTE_EPI_ADD_DROPOUT = 4, /* d = bf16(aux + dropout(bf16(acc)))   resid_dropout / mlp dropout (model.py:151,167);
                                 element (m,n) is dropout element (row m, col n) of (dropout_seed, dropout_site) */
-    OBTE_EPI_ACC32 = 8      /* the weight-gradient layout only (a_kmajor = b_kmajor = 0, ldd == N): the contribution c = fl32(alpha*acc),
+    OBTE_EPI_ACC32 = 8,     /* the weight-gradient layout only (a_kmajor = b_kmajor = 0, ldd == N): the contribution c = fl32(alpha*acc),
                                formed before any rounding to bf16, goes into the caller's persistent fp32 [M,N] buffer acc32 by
                                acc32_mode — OBTE_ACC32_FIRST: acc32 = c; _MORE: acc32 = fl32(acc32 + c); _LAST: the same add, then
                                d = bf16(acc32).  d is written by _LAST only (it may be NULL otherwise).  The product is rounded before
@@ -134,13 +134,17 @@ enum {
                                defined bit for bit.  Gradient accumulation over micro-batches (train_encoder.py:284-311, autograd's
                                `grad += new` rounds to bf16 after every micro-batch) with ONE rounding per optimizer step.  (7 is taken
                                by an internal epilogue.) */
+    OBTE_EPI_GELU_ACT = 9   /* d = bf16(gelu_erf_1.41421(bf16(acc))): EPI_GELU's d2, bit for bit, and nothing else — no derivative is
+                               formed or stored (a forward nobody will differentiate: model.eval() / torch.no_grad()).  d2 is not read.
+                               The x W^T layout only (a_kmajor = b_kmajor = 1), alpha == 1, no split-K.  d leaves through ordinary
+                               stores: the next product reads it at once. */
 };
 /* the protocol of a gradient summed in fp32 over the passes of one optimizer step (the values of OBTE_LN_PARTIAL_*) */
 enum { OBTE_ACC32_FIRST = 1, OBTE_ACC32_MORE = 2, OBTE_ACC32_LAST = 3 };
 typedef struct {
     const obte_bf16* a; const obte_bf16* b; obte_bf16* d;
     const obte_bf16* aux;   /* [M,N] ld = ldd, for EPI_ADD / EPI_GELU_BWD */
-    obte_bf16* d2;          /* [M,N] ld = ldd, for EPI_GELU */
+    obte_bf16* d2;          /* [M,N] ld = ldd, for EPI_GELU (not EPI_GELU_ACT) */
     int64_t M, N, K;
     int64_t lda, ldb, ldd;
     int32_t a_kmajor, b_kmajor;
@@ -170,7 +174,9 @@ int obte_gemm_bf16_ws(const obte_gemm_args* g, void* workspace, int64_t workspac
  * split count trimmed to one round of 256 CUs), or a built-in heuristic on structure 2.  A split-K plan without a workspace that
  * holds it runs the heuristic without split; where a structure cannot run the plan as given it falls back: 7 (edge tiles, fewer
  * tiles than CUs, K < 256, a large output) to 3 at one split; 3 and 4 (fewer than two K-tiles per split) to 2 at the same width.
- * ACC32 exists on structures 2 (128 and 256 wide), 3 and 4; a plan of structure 1 or 7 borrowed for it runs the heuristic. */
+ * ACC32 exists on structures 2 (128 and 256 wide), 3 and 4; a plan of structure 1 or 7 borrowed for it runs the heuristic.
+ * GELU_ACT exists wherever GELU does in the x W^T layout (1; 2 at 128, 192 and 256; 3; 4; 7); a call uses its own plan, else the
+ * GELU plan of its shape (the same main loop). */
 int obte_gemm_plan_set(int a_kmajor, int b_kmajor, int epilogue, int64_t M, int64_t N, int64_t K, int variant, int bn,
                        int splits);
 int obte_gemm_plan_clear(void);
@@ -458,6 +464,20 @@ int64_t obte_block_act_bytes(int64_t B, int64_t T, int32_t n_embd, int32_t n_hea
 int64_t obte_block_act_bytes_p(int64_t B, int64_t T, int32_t n_embd, int32_t n_head, float dropout_p);
 int64_t obte_block_bwd_ws_bytes(int64_t B, int64_t T, int32_t n_embd, int32_t n_head);
 int obte_block_fwd(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y, void* act, obte_stream s);
+/* The forward of a block nobody will differentiate (model.eval() / torch.no_grad(): the reference's evaluation scripts and the
+ * trainer's evaluate()): the kernel sequence of obte_block_fwd's full form with c_fc through OBTE_EPI_GELU_ACT, every value of y
+ * bit for bit that of obte_block_fwd, and nothing kept.  The full form only: out_rows != NULL returns OBTE_EUNSUPPORTED (the rows
+ * form stays with obte_block_fwd).  Every mask representation (none, key ranges, a dense mask with or without key_ranges /
+ * ranges_exact bounds) and dropout_p > 0 (a model in train() mode under no_grad; the (seed, site) masks of obte_block_fwd, and no
+ * keep bits are written) are served.  The backward-only descriptor fields are ignored: query_bounds, ln1_partials / ln2_partials /
+ * ln_partial_mode, dy_masked / dx_masked / dx_mask_seed, the four *_w_acc32 / w_acc32_mode.
+ * ws: obte_block_infer_ws_bytes() bytes (0 for a shape the block entry points reject), at most 8 * B*T * n_embd * 2 + 4096, against
+ * 15 of those units in obte_block_act_bytes(); 256-byte aligned; its contents are irrelevant before and after the call, so ONE
+ * buffer serves every block of a forward.  A smaller ws_bytes returns OBTE_EINVAL.
+ * y MAY ALIAS x: the residual x is last read by the attention projection's epilogue (into the workspace) and y is written by the
+ * last product only. */
+int64_t obte_block_infer_ws_bytes(int64_t B, int64_t T, int32_t n_embd, int32_t n_head);
+int obte_block_fwd_infer(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y, void* ws, int64_t ws_bytes, obte_stream s);
 /* grads of the six parameters are written (not accumulated) to d*_w; dx to dx. */
 int obte_block_bwd(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,
                    obte_bf16* dx, obte_bf16* dln1_w, obte_bf16* dattn_w, obte_bf16* dproj_w, obte_bf16* dln2_w,

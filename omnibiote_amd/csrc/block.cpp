@@ -25,6 +25,8 @@
 //                  their dropout masks                output)); dym: d(attention output) rows, then dQ W_q rows; dym2: masked dx1
 //                                                     rows, then dQ rows
 // The reuses are named members of ActLayout / WsLayout, each with the moment from which its region is free.
+// obte_block_fwd_infer is the full form's forward for a caller who will never run the backward: the same products, nothing kept
+// (InferLayout: seven [M, C] units instead of fifteen), c_fc's activation without its derivative.
 #include "common.h"
 
 namespace {
@@ -110,6 +112,29 @@ struct WsLayout {
         if (gemmws_bytes == 0) gemmws = nullptr;
         if (attnws_bytes == 0) attnws = nullptr;
         dx1_rows = h1_rows = dyattn; dy_attn_rows = dh1_rows = dym; dx1_rows_masked = dq_rows = dym2;
+    }
+};
+
+// The workspace of a forward nobody will differentiate (obte_block_fwd_infer): nothing outlives the call, so a region is reused as soon
+// as its last reader has been enqueued — seven [M, C] bf16 units and the small fp32 rows, against the fifteen of ActLayout.
+struct InferLayout {
+    obte_bf16 *qkv, *h1, *att, *x1;
+    float *mean, *rstd, *lse;   // written by the LayerNorm and attention kernels, read by nobody; ln_2 overwrites ln_1's statistics
+    int64_t total;
+    obte_bf16* hact;            // = qkv: gelu(c_fc) [M, 4C] over the [M, 3C] qkv and the unit behind it (the attention was qkv's last reader)
+    obte_bf16* h2;              // = h1: ln_2(x1) (c_attn was h1's last reader)
+    InferLayout(int64_t B, int64_t T, int C, int H, const void* base = nullptr) {
+        const int64_t M = B * T;
+        uintptr_t o = (uintptr_t)base;
+        auto take = [&](int64_t bytes) { void* r = (void*)o; o += align256(bytes); return r; };
+        qkv = (obte_bf16*)take(M * 4 * C * 2);
+        h1 = (obte_bf16*)take(M * C * 2);
+        att = (obte_bf16*)take(M * C * 2);
+        x1 = (obte_bf16*)take(M * C * 2);
+        mean = (float*)take(M * 4); rstd = (float*)take(M * 4);
+        lse = (float*)take(B * H * T * 4);
+        total = (int64_t)(o - (uintptr_t)base);
+        hact = qkv; h2 = h1;
     }
 };
 
@@ -437,6 +462,46 @@ extern "C" int obte_block_fwd(const obte_block_desc* d, const obte_bf16* x, obte
     if (f.rows) TRY(fwd_proj_rows(d, f, a, x, s));
     else TRY(run(plus_residual(xWt(a.y, d->proj_w, a.x1, f.M, C, C), x, d->dropout_p, d->dropout_seed, SITE_RESID), s));
     return fwd_mlp(d, f, a, f.rows ? a.rows_x1 : a.x1, y_out, s);
+}
+
+// ---- forward without a backward ---------------------------------------------------------------------------------------------------------
+// obte_block_fwd's full form, product for product (the same plans, the same dropout masks), with the activation-only c_fc epilogue; no
+// keep bits for a backward that will not come.  x is last read by the attention projection's residual add and y_out is written by the
+// last product alone, so the two may be one buffer.
+extern "C" int64_t obte_block_infer_ws_bytes(int64_t B, int64_t T, int32_t n_embd, int32_t n_head) {
+    if (B <= 0 || T <= 0 || n_head <= 0 || n_embd <= 0 || n_embd % n_head != 0 || n_embd % 64 != 0 || n_embd > 4096) return 0;
+    const int hs = n_embd / n_head;
+    if (hs != 64 && hs != 128) return 0;
+    return InferLayout(B, T, n_embd, n_head).total;
+}
+
+extern "C" int obte_block_fwd_infer(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* ws, int64_t ws_bytes, obte_stream s) {
+    TRY(check_desc("obte_block_fwd_infer", d));
+    if (d->out_rows) {
+        obte_set_error("obte_block_fwd_infer: the rows form (out_rows) stays with obte_block_fwd");
+        return OBTE_EUNSUPPORTED;
+    }
+    OBTE_REQUIRE(x && y_out && ws, "obte_block_fwd_infer: null pointer");
+    const int C = d->n_embd, H = d->n_head, hs = C / H;
+    const int64_t M = d->B * d->T;
+    const InferLayout w(d->B, d->T, C, H, ws);
+    OBTE_REQUIRE(ws_bytes >= w.total, "obte_block_fwd_infer: workspace of %lld bytes, obte_block_infer_ws_bytes() asks for %lld", (long long)ws_bytes, (long long)w.total);
+    TRY(obte_layernorm_fwd(x, d->ln1_w, w.h1, w.mean, w.rstd, M, C, 1e-5f, s));
+    obte_gemm_args qkv = xWt(w.h1, d->attn_w, w.qkv, M, 3 * C, C);
+    qkv.epilogue = OBTE_EPI_ROPE_QK; qkv.rope_cos = d->rope_cos; qkv.rope_sin = d->rope_sin; qkv.rope_T = d->T; qkv.rope_head_dim = hs;
+    TRY(run(qkv, s));
+    obte_attn_fwd_args af = {};
+    af.qkv = w.qkv; af.o = w.att; af.lse = w.lse; af.key_ranges = d->key_ranges; af.mask = d->mask;
+    af.mask_sb = d->mask_sb; af.mask_sh = d->mask_sh; af.mask_sq = d->mask_sq; af.ranges_exact = d->ranges_exact;
+    af.B = d->B; af.T = d->T; af.n_head = H; af.head_dim = hs; af.scale = 8.0f / (float)C;  // model.py:119
+    af.dropout_p = d->dropout_p; af.dropout_seed = d->dropout_seed;
+    TRY(obte_attn_fwd(&af, s));
+    TRY(run(plus_residual(xWt(w.att, d->proj_w, w.x1, M, C, C), x, d->dropout_p, d->dropout_seed, SITE_RESID), s));
+    TRY(obte_layernorm_fwd(w.x1, d->ln2_w, w.h2, w.mean, w.rstd, M, C, 1e-5f, s));
+    obte_gemm_args fc = xWt(w.h2, d->fc_w, w.hact, M, 4 * C, C);
+    fc.epilogue = OBTE_EPI_GELU_ACT;
+    TRY(run(fc, s));
+    return run(plus_residual(xWt(w.hact, d->mlp_w, y_out, M, C, 4 * C), w.x1, d->dropout_p, d->dropout_seed, SITE_MLP), s);
 }
 
 extern "C" int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,

@@ -185,6 +185,31 @@ __device__ __forceinline__ void gelu_ref_both2(f32x2_t x, f32x2_t& act, f32x2_t&
     der = half_cdf + (x * gauss) * (0.5641895835477563f / OBTE_GELU_C);
 }
 
+// The activation alone (OBTE_EPI_GELU_ACT): gelu_ref_both2's operations in its order up to act, so the two agree bit for bit
+__device__ __forceinline__ f32x2_t gelu_ref_act2(f32x2_t x) {
+    constexpr float K2 = 1.2011224087864498f / OBTE_GELU_C;
+    constexpr float P2 = 0.3275911f / 1.2011224087864498f;
+    const f32x2_t w = x * K2;
+    const f32x2_t t2 = w * w;
+    const f32x2_t gauss = {__builtin_amdgcn_exp2f(-t2[0]), __builtin_amdgcn_exp2f(-t2[1])};
+    const f32x2_t t = {__builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(w[0]), P2, 1.0f)),
+                       __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(w[1]), P2, 1.0f))};
+    const f32x2_t q = 0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f)));
+    const f32x2_t e_abs = 1.0f - q * (t * gauss);
+    const f32x2_t e = {__builtin_copysignf(e_abs[0], x[0]), __builtin_copysignf(e_abs[1], x[1])};
+    const f32x2_t half_cdf = e * 0.5f + 0.5f;
+    return x * half_cdf;
+}
+// eight staged bf16 values through it
+__device__ __forceinline__ bf16x8 gelu_act8(bf16x8 v) {
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {
+        const f32x2_t act = gelu_ref_act2(f32x2_t{bf2f(v[j]), bf2f(v[j + 1])});
+        v[j] = f2bf(act[0]); v[j + 1] = f2bf(act[1]);
+    }
+    return v;
+}
+
 // ---- dropout: counter-based keep decision -------------------------------------------------------------------
 // keep(row, col) is a pure function of (seed, site, row, col), so forward and backward regenerate the same mask with no
 // mask tensor in memory, and a host-side restatement (oracle/omnibiote_ref.py dropout_keep) reproduces it bit for bit.

@@ -34,6 +34,7 @@ static int validate_args(const obte_gemm_args* g) {
                          (g->N / 3) % g->rope_head_dim == 0,
                      "obte_gemm_bf16: EPI_ROPE_QK needs cos/sin tables, T, head_dim %% 8 == 0 and N = 3 * n_head * head_dim");
     if (g->epilogue == OBTE_EPI_GELU) OBTE_REQUIRE(g->d2, "obte_gemm_bf16: GELU epilogue needs d2");
+    if (g->epilogue == OBTE_EPI_GELU_ACT) OBTE_REQUIRE(g->a_kmajor && g->b_kmajor, "obte_gemm_bf16: EPI_GELU_ACT exists in the x W^T layout only (a_kmajor = b_kmajor = 1)");
     if (g->epilogue == OBTE_EPI_ACC32)
         OBTE_REQUIRE(g->acc32 && g->acc32_mode >= OBTE_ACC32_FIRST && g->acc32_mode <= OBTE_ACC32_LAST && !g->a_kmajor && !g->b_kmajor && g->ldd == g->N,
                      "obte_gemm_bf16: EPI_ACC32 needs the fp32 buffer, a mode (OBTE_ACC32_*), the weight-gradient layout (a_kmajor = b_kmajor = 0) and ldd == N");
@@ -124,6 +125,8 @@ static bool lookup_plan(const obte_gemm_args* g, Plan* out, bool* near_match) {
         it = g_plans.find(PlanKey(lay, OBTE_EPI_NONE, g->M, g->N, g->K));
     if (it == g_plans.end() && g->epilogue == OBTE_EPI_ADD_DROPOUT)   // same main loop as the residual-add form
         it = g_plans.find(PlanKey(lay, OBTE_EPI_ADD, g->M, g->N, g->K));
+    if (it == g_plans.end() && g->epilogue == OBTE_EPI_GELU_ACT)      // the activation alone: the main loop of the two-output form
+        it = g_plans.find(PlanKey(lay, OBTE_EPI_GELU, g->M, g->N, g->K));
     if (it == g_plans.end()) {   // a near match: an entry with the same layout and epilogue (ADD: NONE's)
         const int epi = (g->epilogue == OBTE_EPI_ADD || g->epilogue == OBTE_EPI_ACC32) ? OBTE_EPI_NONE : g->epilogue;
         for (auto jt = g_plans.begin(); jt != g_plans.end(); ++jt)

@@ -267,6 +267,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmParams p) {
                     v[j] = f2bf(der[0]); v[j + 1] = f2bf(der[1]);
                 }
                 *reinterpret_cast<bf16x8*>(p.d2 + o) = g;
+            } else if (EPI == OBTE_EPI_GELU_ACT) {
+                v = gelu_act8(v);   // the activation alone (a forward without a backward)
             } else if (EPI == OBTE_EPI_ADD) {
                 const bf16x8 r = *reinterpret_cast<const bf16x8*>(p.aux + o);
 #pragma unroll

@@ -220,6 +220,8 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[
                     v[j] = f2bf(der[0]); v[j + 1] = f2bf(der[1]);
                 }
                 *reinterpret_cast<bf16x8*>(p.d2 + o) = g;
+            } else if (EPI == OBTE_EPI_GELU_ACT) {
+                v = gelu_act8(v);   // the activation alone (a forward without a backward): one output, stored as any other d
             } else if (EPI == OBTE_EPI_ADD) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = f2bf(bf2f(r[it][j]) + bf2f(v[j]));
@@ -275,6 +277,8 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[
                     v[j] = f2bf(der[0]); v[j + 1] = f2bf(der[1]);
                 }
                 *reinterpret_cast<bf16x8*>(p.d2 + o) = g;
+            } else if (EPI == OBTE_EPI_GELU_ACT) {
+                v = gelu_act8(v);
             } else if (EPI == OBTE_EPI_ADD) {
                 if (p.aux) {   // uniform; null only inside a mixed group (a problem without accumulation)
                     const bf16x8 r = *reinterpret_cast<const bf16x8*>(p.aux + o);
@@ -452,6 +456,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_v2_kernel(GemmParams p) {
     template __global__ void gemm_v2_kernel<AK, BK, OBTE_EPI_ADD_DROPOUT, false, BN>(GemmParams);   \
     template __global__ void gemm_v2_kernel<AK, BK, OBTE_EPI_ROPE_QK, false, BN>(GemmParams);
 OBTE_INST(true, true, 128)
+template __global__ void gemm_v2_kernel<true, true, OBTE_EPI_GELU_ACT, false, 128>(GemmParams);   // (x W^T only)
+template __global__ void gemm_v2_kernel<true, true, OBTE_EPI_GELU_ACT, false, 256>(GemmParams);
 OBTE_INST(true, false, 128)
 OBTE_INST(false, true, 128)
 OBTE_INST(false, false, 128)
@@ -466,7 +472,7 @@ template __global__ void gemm_v2_kernel<false, false, OBTE_EPI_ACC32, false, 256
 // leaves the 256-wide tiling a ragged last round — c_attn at the small config: N = 3072 is 384 tiles of 256 x 256 = 1.5 rounds of
 // the 256 CUs, and 512 tiles of 256 x 192 = two full ones (a quarter less work per round).
 #define OBTE_INST192(EPI) template __global__ void gemm_v2_kernel<true, true, EPI, false, 192>(GemmParams);
-OBTE_INST192(OBTE_EPI_NONE) OBTE_INST192(OBTE_EPI_GELU) OBTE_INST192(OBTE_EPI_ADD) OBTE_INST192(OBTE_EPI_ADD_DROPOUT) OBTE_INST192(OBTE_EPI_ROPE_QK)
+OBTE_INST192(OBTE_EPI_NONE) OBTE_INST192(OBTE_EPI_GELU) OBTE_INST192(OBTE_EPI_ADD) OBTE_INST192(OBTE_EPI_ADD_DROPOUT) OBTE_INST192(OBTE_EPI_ROPE_QK) OBTE_INST192(OBTE_EPI_GELU_ACT)
 #undef OBTE_INST192
 
 // ---- third structure: 256x256 tile, ring of FOUR half K-tiles (32 k each, 32 KiB), loads three half-steps ahead ----
@@ -661,6 +667,7 @@ OBTE_INST3(false, true)
 OBTE_INST3(false, false)
 #undef OBTE_INST3
 template __global__ void gemm_v3_kernel<false, false, OBTE_EPI_ACC32, false>(GemmParams);
+template __global__ void gemm_v3_kernel<true, true, OBTE_EPI_GELU_ACT, false>(GemmParams);   // (x W^T only)
 
 // ---- fourth structure: 256x128 tile, FOUR waves, ring of THREE half K-tiles (24 KiB each), TWO workgroups per CU ------------
 // What the K = 1024 shapes of the block lose (measured with the timing-only hooks on c_fc + GELU, 8192 x 4096 x 1024: 96 us
@@ -841,6 +848,7 @@ OBTE_INST4(false, true)
 OBTE_INST4(false, false)
 #undef OBTE_INST4
 template __global__ void gemm_v4_kernel<false, false, OBTE_EPI_ACC32, false>(GemmParams);
+template __global__ void gemm_v4_kernel<true, true, OBTE_EPI_GELU_ACT, false>(GemmParams);   // (x W^T only)
 
 // d[m][n] = bf16(alpha * sum_s slab[s][m][n]) in split order
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, bf16* __restrict__ d, const bf16* aux,

@@ -44,7 +44,7 @@ __device__ __forceinline__ void tile_origin(const GemmParams& p, int v, int64_t&
 template <bool A_KMAJOR, bool B_KMAJOR, int EPI>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_v7_kernel(GemmParams p) {
     constexpr int NJ = 8;
-    constexpr int S_ST = EPI == OBTE_EPI_GELU ? 32 : 16;                            // stores of one epilogue per wave
+    constexpr int S_ST = EPI == OBTE_EPI_GELU ? 32 : 16;                            // stores of one epilogue per wave (GELU has two outputs; GELU_ACT one)
     constexpr int WAIT_LAX = (((8 + S_ST) >> 4) << 14) | 0x0070 | ((8 + S_ST) & 15);   // s_waitcnt vmcnt(8 + S) lgkmcnt(0)
     constexpr bool READS = EPI == OBTE_EPI_ADD || EPI == OBTE_EPI_GELU_BWD || EPI == OBTE_EPI_ADD_DROPOUT || EPI == OBTE_EPI_ROWDOT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -186,6 +186,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_v7_kernel(GemmParams p) {
                     if (p.store_rows == 0) asm volatile("" :: "v"(gact)); else
 #endif
                     *reinterpret_cast<bf16x8*>(p.d2 + o) = gact;
+                } else if (EPI == OBTE_EPI_GELU_ACT) {
+                    v = gelu_act8(v);   // the activation alone: one output, so S_ST = 16 above, and an ordinary store (NT is GELU's)
                 } else if (EPI == OBTE_EPI_ADD) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] = f2bf(bf2f(raux[mi][it][j]) + bf2f(v[j]));

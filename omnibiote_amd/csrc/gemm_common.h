@@ -143,6 +143,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 constexpr bool gemm_has_form(int s, int bn, bool ak, bool bk, int epi, bool split) {
     const bool abi = epi >= OBTE_EPI_NONE && epi <= OBTE_EPI_ROPE_QK;                          // the six epilogues of the public ABI
     const bool ring = (abi && (!split || epi == OBTE_EPI_NONE || epi == OBTE_EPI_ADD)) || (epi == OBTE_EPI_ACC32 && !ak && !bk);
+    if (epi == OBTE_EPI_GELU_ACT)                                                              // the activation alone: wherever x W^T has GELU
+        return ak && bk && !split && (s == 1 ? bn == 128 : s == 2 ? bn == 128 || bn == 192 || bn == 256 : s == 3 || s == 7 ? bn == 256 : s == 4 && bn == 128);
     switch (s) {
         case 1: return bn == 128 && abi && !split;                                             // gemm_bf16_v1.hip
         case 2: return bn == 192 ? ak && bk && abi && !split && epi != OBTE_EPI_GELU_BWD         // gemm_bf16_v2.hip
@@ -192,6 +194,7 @@ int gemm_dispatch_epi(int epi, bool split, F& f) {
         case OBTE_EPI_ROPE_QK: return gemm_form<S, BN, AK, BK, OBTE_EPI_ROPE_QK, false>(f);
         case OBTE_EPI_ROWDOT: return gemm_form<S, BN, AK, BK, OBTE_EPI_ROWDOT, false>(f);
         case OBTE_EPI_ACC32: return gemm_form<S, BN, AK, BK, OBTE_EPI_ACC32, false>(f);
+        case OBTE_EPI_GELU_ACT: return gemm_form<S, BN, AK, BK, OBTE_EPI_GELU_ACT, false>(f);
     }
     return gemm_no_form(S, BN, AK, BK, epi, false);
 }

@@ -566,6 +566,12 @@ def _active_p(module: nn.Module, p: float) -> float:
     return p if module.training else 0.0
 
 
+def _no_gradient_possible(*tensors) -> bool:
+    """No gradient can be asked of a call on these tensors: autograd is off, or none of them requires one.  Such a forward keeps
+    nothing for a backward (ops.block_infer, EPI_GELU_ACT) unless OBTE_INFER=0 selects the training forward (same results)."""
+    return not torch.is_grad_enabled() or not any(t.requires_grad for t in tensors)
+
+
 # ------------------------------------------------------------------------------------------------------- modules
 class LayerNorm(nn.Module):
     """LayerNorm with optional bias (model.py:63-72).  The reference always builds it with bias=False."""
@@ -644,7 +650,12 @@ class MLP(nn.Module):
     def forward(self, x):
         _require_hip(x, "MLP")
         p = _active_p(self, self.dropout.p)
-        y = _LinearFn.apply(_LinearGeluFn.apply(x, self.c_fc.weight), self.c_proj.weight, 1.0)
+        if _no_gradient_possible(x, self.c_fc.weight) and ops.infer_enabled():   # the activation alone: no derivative for a backward that cannot come
+            h = ops.linear_fwd(x.reshape(-1, x.shape[-1]).contiguous(), self.c_fc.weight, epilogue=L.EPI_GELU_ACT)
+            h = h.view(*x.shape[:-1], self.c_fc.weight.shape[0])
+        else:
+            h = _LinearGeluFn.apply(x, self.c_fc.weight)
+        y = _LinearFn.apply(h, self.c_proj.weight, 1.0)
         return _DropoutFn.apply(y, p, _new_seed(), L.SITE_MLP) if p > 0 else y
 
 
@@ -658,8 +669,11 @@ class Block(nn.Module):
         if config.bias:
             raise NotImplementedError("bias=True is not used by the reference (model.py:191) and not implemented")
 
-    def forward(self, x, attn_mask=None, out_rows=None, below_seed=None, seed=None, handoff=None, index=0):
-        """below_seed, seed, handoff, index (internal, OmniBioTA.forward): the dropout seed the block BELOW uses in this forward —
+    def forward(self, x, attn_mask=None, out_rows=None, below_seed=None, seed=None, handoff=None, index=0, infer=None):
+        """infer (internal, OmniBioTA.forward): a one-element list that holds the workspace of the forward call's blocks on the
+        path that keeps nothing for a backward (allocated by the first block that takes it); with it, and autograd off, the block
+        writes its output over x (the caller's x is the previous block's output or the fresh embedding).  A direct call leaves x alone.
+        below_seed, seed, handoff, index (internal, OmniBioTA.forward): the dropout seed the block BELOW uses in this forward —
         this block's backward then also writes its dx under that block's MLP-projection mask (ops.block_bwd) and leaves it in
         `handoff` (the forward call's _GradHandOff) for block index - 1; `seed` is this block's own, drawn by the caller so that it
         can hand it on (None: drawn here).
@@ -682,6 +696,17 @@ class Block(nn.Module):
             seed = _new_seed() if seed is None else seed
         else:
             seed = 0
+        params = (self.ln_1.weight, self.attn.c_attn.weight, self.attn.c_proj.weight, self.ln_2.weight, self.mlp.c_fc.weight, self.mlp.c_proj.weight)
+        if out_rows is None and _no_gradient_possible(x, *params) and ops.infer_enabled():
+            # nobody can differentiate this call: the forward that saves nothing (the rows form stays with obte_block_fwd)
+            x = x.contiguous()
+            ws = infer[0] if infer is not None else None
+            if ws is None:
+                ws = ops.block_infer_workspace(B, T, C, self.attn.n_head, x.device)
+                if infer is not None:
+                    infer[0] = ws
+            over = infer is not None and not torch.is_grad_enabled()
+            return ops.block_infer(x, params, (cos, sin), self.attn.n_head, mask, p, seed, ws=ws, out=x if over else None)
         return _BlockFn.apply(x, self.ln_1.weight, self.attn.c_attn.weight, self.attn.c_proj.weight, self.ln_2.weight,
                               self.mlp.c_fc.weight, self.mlp.c_proj.weight, cos, sin, self.attn.n_head, mask, p, seed, out_rows,
                               below_seed if p > 0 else None, handoff if p > 0 else None, index)
@@ -784,6 +809,7 @@ class OmniBioTA(nn.Module):
         # leaves it in this call's hand-off object (nothing of this lives on the modules or in the process)
         below = None
         handoff = _GradHandOff()
+        infer = [None]   # the workspace of the blocks that run without a backward to come: one per call, filled by the first of them
         for i, block in enumerate(self.transformer.h):
             last_rows = rows if (rows is not None and i == n_blocks - 1) else None
             if self.config.checkpoint_freq > 0 and i % self.config.checkpoint_freq == 0:
@@ -792,7 +818,7 @@ class OmniBioTA(nn.Module):
             else:
                 bp = _active_p(block, block.attn.dropout)
                 seed = _new_seed() if bp > 0 else None
-                x = block(x, attn_mask=mask, out_rows=last_rows, below_seed=below, seed=seed, handoff=handoff, index=i)
+                x = block(x, attn_mask=mask, out_rows=last_rows, below_seed=below, seed=seed, handoff=handoff, index=i, infer=infer)
                 below = seed
         emb = self.transformer.ln_f(x)
         if return_embeddings:

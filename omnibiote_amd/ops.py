@@ -131,7 +131,7 @@ def acc32_add_(acc32, src, mode, out=None):
 def gemm(a, b, M, N, K, a_kmajor=True, b_kmajor=True, epilogue=L.EPI_NONE, aux=None, alpha=1.0, out=None, dropout=None,
          rope=None, acc32=None, acc32_mode=0):
     """D[M,N] = epilogue(alpha * sum_k A(m,k) B(n,k)); see include/omnibiote_hip.h.  Returns d, or (d, d2) for
-    the GELU epilogue.  EPI_ACC32 (acc32 fp32 [M,N] + acc32_mode): d is formed by L.ACC32_LAST only, else None is returned."""
+    the GELU epilogue (EPI_GELU_ACT: d alone, the activation).  EPI_ACC32 (acc32 fp32 [M,N] + acc32_mode): d is formed by L.ACC32_LAST only, else None is returned."""
     _need(a, "a"); _need(b, "b")
     lda = K if a_kmajor else M
     ldb = K if b_kmajor else N
@@ -152,6 +152,8 @@ def gemm(a, b, M, N, K, a_kmajor=True, b_kmajor=True, epilogue=L.EPI_NONE, aux=N
     d2 = None
     if epilogue == L.EPI_GELU:
         d2 = torch.empty((M, N), dtype=bf16, device=a.device)
+    if epilogue == L.EPI_GELU_ACT:
+        assert a_kmajor and b_kmajor, "EPI_GELU_ACT: the x W^T layout only"
     if epilogue in (L.EPI_ADD, L.EPI_GELU_BWD, L.EPI_ADD_DROPOUT):
         _need(aux, "aux"); assert aux.numel() == M * N
     dp, dseed, dsite = dropout if dropout is not None else (0.0, 0, 0)   # (p, seed, site) for EPI_ADD_DROPOUT
@@ -603,6 +605,41 @@ def block_fwd(x, params, rope, H, mask: MaskSpec, dropout_p=0.0, dropout_seed=0,
     d = _block_desc(B, T, Cc, H, params, rope, mask, dropout_p, dropout_seed, out_rows=out_rows)
     L.check(L.lib().obte_block_fwd(C.byref(d), _ptr(x), _ptr(y), _ptr(act), _stream()), "obte_block_fwd")
     return y, act
+
+
+def infer_enabled() -> bool:
+    """OBTE_INFER=0: a forward nobody can differentiate runs the training forward (block_fwd, the two-output GELU epilogue)
+    instead of block_infer / EPI_GELU_ACT.  Same results.  Read per call."""
+    return os.environ.get("OBTE_INFER", "") != "0"
+
+
+def block_infer_workspace(B, T, Cc, H, device) -> torch.Tensor:
+    """The scratch of block_infer for this shape: contents irrelevant before and after, so one buffer serves every block of a forward."""
+    nbytes = int(L.lib().obte_block_infer_ws_bytes(B, T, Cc, H))
+    if nbytes <= 0:
+        raise RuntimeError(f"block_infer: unsupported shape (B {B}, T {T}, n_embd {Cc}, n_head {H}): head size 64 or 128, "
+                           "n_embd a multiple of 64 and <= 4096")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def block_infer(x, params, rope, H, mask: MaskSpec, dropout_p=0.0, dropout_seed=0, ws=None, out=None):
+    """One transformer block forward with nothing kept for a backward (obte_block_fwd_infer): y, bit for bit block_fwd's.
+    ws: a buffer from block_infer_workspace for this shape (allocated here when None).  out: where y goes; it may be x itself."""
+    _need(x, "x")
+    B, T, Cc = x.shape
+    for i, w in enumerate(params):
+        _need(w, f"param{i}")
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert rope[0].shape[0] >= T
+    if ws is None:
+        ws = block_infer_workspace(B, T, Cc, H, x.device)
+    else:
+        _need(ws, "ws", torch.uint8)
+    y = torch.empty_like(x) if out is None else out
+    _need(y, "out"); assert y.shape == x.shape
+    d = _block_desc(B, T, Cc, H, params, rope, mask, dropout_p, dropout_seed)
+    L.check(L.lib().obte_block_fwd_infer(C.byref(d), _ptr(x), _ptr(y), _ptr(ws), ws.numel(), _stream()), "obte_block_fwd_infer")
+    return y
 
 
 def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None, dropout_p=0.0, dropout_seed=0, ln_partials=None,

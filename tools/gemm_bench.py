@@ -17,6 +17,7 @@ C, V = 1024, 65536
 SHAPES = {
     # name: (kind, M, N, K)
     "fwd_qkv": ("nt", M, 3 * C, C), "fwd_proj": ("nt_add", M, C, C), "fwd_fc": ("nt_gelu", M, 4 * C, C),
+    "fwd_fc_act": ("nt_geluact", M, 4 * C, C),   # c_fc of a forward without a backward: the activation alone
     "fwd_mlp": ("nt_add", M, C, 4 * C), "fwd_lm": ("nt", M, V, C),
     "dg_mlp": ("nn_gelubwd", M, 4 * C, C), "dg_fc": ("nn", M, C, 4 * C), "dg_proj": ("nn", M, C, C),
     "dg_qkv": ("nn", M, C, 3 * C), "dg_lm": ("nn", M, C, V),
@@ -33,7 +34,7 @@ def run(name, reps, structure=0, bn=0, splits=1):
     b = torch.randn(n * k, device=dev, generator=g).to(torch.bfloat16)
     aux = torch.randn(m * n, device=dev, generator=g).to(torch.bfloat16) if ("add" in kind or "gelubwd" in kind) else None
     ak, bk = kind.startswith("nt") or kind.startswith("nn"), kind.startswith("nt")
-    epi = {"nt": L.EPI_NONE, "nn": L.EPI_NONE, "tn": L.EPI_NONE, "nt_add": L.EPI_ADD, "nt_gelu": L.EPI_GELU, "nn_gelubwd": L.EPI_GELU_BWD}[kind]
+    epi = {"nt": L.EPI_NONE, "nn": L.EPI_NONE, "tn": L.EPI_NONE, "nt_add": L.EPI_ADD, "nt_gelu": L.EPI_GELU, "nt_geluact": L.EPI_GELU_ACT, "nn_gelubwd": L.EPI_GELU_BWD}[kind]
     out = torch.empty(m * n, device=dev, dtype=torch.bfloat16)
     if structure:
         s = splits if epi in (L.EPI_NONE, L.EPI_ADD) else 1
