@@ -210,11 +210,12 @@ int obte_dropout_bf16(const obte_bf16* in, obte_bf16* out, int64_t n, int64_t co
 int obte_rope_qk_inplace(obte_bf16* qkv, const float* cos_t, const float* sin_t, int64_t B, int64_t T,
                          int n_head, int head_dim, int inverse, obte_stream s);
 
-/* ---- fused attention (training/model.py:115-148): softmax(q k^T * scale + mask) v, non-causal -------------
+/* ---- fused attention (training/model.py:115-148): softmax(q k^T * scale + mask) v ---------------------------
  * q,k,v are read from the packed [B*T, 3C] qkv buffer (row stride 3C; head h at column h*hs, k at +C, v at
  * +2C) and o is written as [B*T, C] (heads side by side: the "merge heads" copy of model.py:148 is free).
  * Mask, one of:  none;  key ranges int32 [B,T,2] = [k_start,k_end) per query (the block-diagonal masks of
- * train_encoder.py:25-57);  dense additive bf16 with element strides (mask_sb, mask_sh, mask_sq; key stride 1;
+ * train_encoder.py:25-57; with the backward's query_bounds beside them any mask whose rows and columns are single runs: causal and
+ * document-causal attention are such range masks, obte_causal_bounds builds their tables);  dense additive bf16 with element strides (mask_sb, mask_sh, mask_sq; key stride 1;
  * mask_sh = 0 for the reference's expand() view).  lse: fp32 [B,H,T] (natural log, of the scaled scores).
  * head_dim in {64,128}.  */
 typedef struct {
@@ -240,7 +241,11 @@ typedef struct {
     const int32_t* key_ranges; const obte_bf16* mask; int64_t mask_sb, mask_sh, mask_sq;
     int64_t B, T; int32_t n_head, head_dim; float scale;
     float dropout_p; uint64_t dropout_seed;     /* must equal the forward call's */
-    const int32_t* query_bounds;                /* nullable; with a dense mask: int32 [B,T,2] per KEY, see obte_mask_bounds */
+    /* nullable, int32 [B,T,2] per KEY.  With a dense mask: the loop bounds of obte_mask_bounds.  With key_ranges and no mask: the
+     * [q_start,q_end) of the queries that see each key — the second table of an ASYMMETRIC range mask (obte_causal_bounds); it must
+     * describe the same (query, key) pairs as key_ranges, every row and every column one contiguous run.  NULL with key_ranges:
+     * the mask is symmetric (the reference's document masks) and a key's queries are the positions of its own key range. */
+    const int32_t* query_bounds;
     const int32_t* ranges_exact;                /* nullable; with mask + key_ranges + query_bounds: obte_mask_bounds' flag */
     /* optional scratch of obte_attn_bwd_ws_bytes() bytes: with it, head_dim 128, no dense mask and either dropout_p = 0 or the
      * forward's keep bits in drop_bits, the backward runs as ONE kernel that forms each score tile once (five MFMA products per tile instead of the seven of the
@@ -427,7 +432,10 @@ typedef struct {
     const float *rope_cos, *rope_sin;                                   /* [T, hs/2] */
     const int32_t* key_ranges; const obte_bf16* mask; int64_t mask_sb, mask_sh, mask_sq;
     float dropout_p; uint64_t dropout_seed;   /* one seed per block call; sites 1-3 derive from it.  p = 0: no dropout */
-    const int32_t* query_bounds;              /* nullable: obte_mask_bounds output for a dense mask (backward only) */
+    /* nullable.  With a dense mask: obte_mask_bounds' output (backward only).  With key_ranges and no mask: the per-key table of an
+     * asymmetric range mask (obte_attn_bwd_args::query_bounds; obte_causal_bounds) — read by the backward and, with out_rows, by the
+     * forward too (the rows form derives each key's gathered queries from it); NULL: the range mask is symmetric. */
+    const int32_t* query_bounds;
     /* backward only, optional: the two LayerNorm weight gradients accumulated over micro-batches in caller-owned fp32
      * partial buffers (see obte_layernorm_bwd_partial); ln_partial_mode 0 = off, else OBTE_LN_PARTIAL_*.  With FIRST / MORE
      * dln1_w / dln2_w are not written. */
@@ -469,7 +477,8 @@ int obte_block_fwd(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y, v
  * bit for bit that of obte_block_fwd, and nothing kept.  The full form only: out_rows != NULL returns OBTE_EUNSUPPORTED (the rows
  * form stays with obte_block_fwd).  Every mask representation (none, key ranges, a dense mask with or without key_ranges /
  * ranges_exact bounds) and dropout_p > 0 (a model in train() mode under no_grad; the (seed, site) masks of obte_block_fwd, and no
- * keep bits are written) are served.  The backward-only descriptor fields are ignored: query_bounds, ln1_partials / ln2_partials /
+ * keep bits are written) are served — a causal model's pair of tables included: the forward of a range mask reads key_ranges alone.
+ * The backward-only descriptor fields are ignored: query_bounds, ln1_partials / ln2_partials /
  * ln_partial_mode, dy_masked / dx_masked / dx_mask_seed, the four *_w_acc32 / w_acc32_mode.
  * ws: obte_block_infer_ws_bytes() bytes (0 for a shape the block entry points reject), at most 8 * B*T * n_embd * 2 + 4096, against
  * 15 of those units in obte_block_act_bytes(); 256-byte aligned; its contents are irrelevant before and after the call, so ONE
@@ -495,6 +504,15 @@ int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, const obte_
  * a zeroed [total_rows, cols]; rows ascending and distinct).  cols % 8 == 0.  Used by the rows form of the block above. */
 int obte_rows_gather_bf16(const obte_bf16* src, const int64_t* rows, obte_bf16* dst, int64_t n_rows, int64_t total_rows, int32_t cols, obte_stream s);
 int obte_rows_scatter_bf16(const obte_bf16* src, const int64_t* rows, obte_bf16* dst, int64_t n_rows, int64_t total_rows, int32_t cols, obte_stream s);
+
+/* The pair of tables of a causal mask, optionally under a document mask: what key_ranges / query_bounds of the attention argument
+ * structs and of obte_block_desc take for an autoregressive model (training/model.py:115-130, is_causal=True).
+ * doc_ranges: NULL, or int32 [B,T,2], a SYMMETRIC range mask [lo,hi) per position (obte_key_ranges_from_tokens' output).
+ *   key_ranges[b,q]   = [lo_q, min(hi_q, q + 1))     (NULL doc_ranges: [0, q + 1))
+ *   query_bounds[b,k] = [max(lo_k, k), hi_k)         (NULL doc_ranges: [k, T))
+ * An empty result is written as [x, x).  Both outputs int32 [B,T,2], distinct from each other and from doc_ranges.
+ * 1 <= B < 2^31, 1 <= T < 2^24.  One elementwise launch on the caller's stream; integers with one right answer. */
+int obte_causal_bounds(const int32_t* doc_ranges, int64_t B, int64_t T, int32_t* key_ranges, int32_t* query_bounds, obte_stream s);
 
 #ifdef __cplusplus
 }

@@ -147,6 +147,7 @@ SYMBOLS = {
     "obte_block_fwd_infer": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
     "obte_block_bwd": (C.c_int, [C.POINTER(BlockDesc)] + [C.c_void_p] * 11 + [c_stream]),
     "obte_block_bwd_acc": (C.c_int, [C.POINTER(BlockDesc)] + [C.c_void_p] * 11 + [C.c_int, c_stream]),
+    "obte_causal_bounds": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, c_stream]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 // Fused attention for the OmniBioTE block (training/model.py:115-148), forward and backward, on CDNA4 MFMA
-// (v_mfma_f32_32x32x16_bf16).  softmax(q k^T * scale + mask) v, non-causal, scale = 8/n_embd passed in.
+// (v_mfma_f32_32x32x16_bf16).  softmax(q k^T * scale + mask) v, scale = 8/n_embd passed in; causal attention is a range mask
+// (the pair of tables obte_causal_bounds builds: key_ranges[q] = [0, q + 1), query_bounds[k] = [k, T)), not a kernel variant.
 //
 // Data layout: q, k, v are read in place from the packed c_attn output [B*T, 3C] (row stride 3C, head h at
 // column h*D); o is written as [B*T, C], so the reference's transpose(1,2).contiguous() copy never exists.
@@ -15,8 +16,15 @@
 // Masks: none | per-query key ranges [k_start,k_end) (block-diagonal document masks; KV tiles outside the
 // workgroup's union range are skipped) | dense additive bf16 (any strides, stride-0 heads allowed).
 // Backward is two kernels without atomics (bitwise reproducible): dQ per query block, dK/dV per key block,
-// each recomputing P from the saved log-sum-exp.  The dK/dV kernel, in range mode, uses the symmetry of the
-// reference's masks (query t may see key u  <=>  query u may see key t).
+// each recomputing P from the saved log-sum-exp.  The dK/dV kernel, in range mode, reads the per-KEY table query_bounds
+// ([q_start, q_end) of the queries that see each key) when the caller hands one — any mask whose rows AND columns are single
+// runs, causal and document-causal masks included; without it the mask is taken to be symmetric (query t may see key u  <=>
+// query u may see key t: the reference's document masks) and the key's own key range serves as its query range.
+// The query-major kernels (forward, dQ) only ever read key_ranges, so the pair form changes nothing for them: a workgroup skips
+// the key tiles outside the union of its queries' ranges — under a causal mask the tiles above its last query.  The keep-bit
+// words of dropout (drop_bits) exist for the (key, 32-query slice) pairs of the tiles the forward ran; the key-major kernels may
+// read a word of a skipped tile when their own union range is wider (the callers zero the buffer, so it is defined), and
+// whatever it says changes nothing: every probability of such a pair is an exact zero by the key's query range.
 #include "attn_common.h"
 
 namespace {
@@ -431,7 +439,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnParams& p, char* smem
                 sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<D>(Kt, 32 * mt, s, lane), qf[s], sc, 0, 0, 0);
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<D>(Vt, 32 * mt, s, lane), dof[s], dp, 0, 0, 0);
             }
-            // 32 keys that every query of the wave may see (the inside of a document): no per-element range test
+            // 32 keys that every query of the wave may see (the inside of a document; below the diagonal of a causal mask): no per-element range test
             auto ds_rows = [&](auto checked) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -537,7 +545,7 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const AttnParams& p, char* sm
 
     int r_lo = 0, r_hi = Tq;   // the query range of this key first (see the forward)
     if (MODE == MASK_RANGES) {
-        const int32_t* src = p.query_bounds ? p.query_bounds : p.key_ranges;   // no per-key table: symmetric mask
+        const int32_t* src = p.query_bounds ? p.query_bounds : p.key_ranges;   // no per-key table: symmetric mask, the key's own range
         r_lo = src[(b * T + key_c) * 2];
         r_hi = src[(b * T + key_c) * 2 + 1];
     } else if (MODE == MASK_DENSE && p.query_bounds) {
@@ -555,7 +563,7 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const AttnParams& p, char* sm
         const int64_t row0 = (int64_t)bid_.blk * (32 * NW);
         dmv.issue(p.qkv + (b * T + row0) * ld + 2 * C + hd * D, (((int64_t)T - row0) * ld - (2 * C + hd * D)) * 2, Vblk, wave);
     }
-    // by symmetry of the mask, the queries that see this key are the keys this position sees as a query
+    // the queries that see this key: its entry of the per-key table, or (symmetric masks) the keys this position sees as a query
     int qs = 0, qe = Tq;
     if (MODE == MASK_RANGES) {
         qs = max(r_lo, 0);
@@ -660,7 +668,7 @@ __device__ __forceinline__ void attn_bwd_dkdv_body(const AttnParams& p, char* sm
         if (!(p.dbg_skip & 1))
 #endif
         {
-            // 32 queries that every key of the wave is seen by (the inside of a document): no per-element range test
+            // 32 queries that every key of the wave is seen by (the inside of a document; below the diagonal of a causal mask): no per-element range test
             auto p_ds_rows = [&](auto checked) {
                 // Dropout: the 32 bits that decide (query, key pair) are shared by the two lanes that hold the pair's keys, and here
                 // every lane is ONE key against 16 queries — so the even lane of a pair hashes the queries of register groups
@@ -1112,7 +1120,7 @@ static int attn_bwd_impl(const obte_attn_bwd_args* a, int delta_ready, obte_stre
     OBTE_REQUIRE((a->rope_cos == nullptr) == (a->rope_sin == nullptr), "obte_attn_bwd: pass both RoPE tables or neither");
     AttnParams p = {};
     p.qkv = (const bf16*)a->qkv; p.o_in = (const bf16*)a->o; p.d_o = (const bf16*)a->d_o; p.lse_in = a->lse; p.delta = a->delta;
-    p.dqkv = (bf16*)a->dqkv; p.rope_cos = a->rope_cos; p.rope_sin = a->rope_sin; p.query_bounds = a->mask ? a->query_bounds : nullptr;
+    p.dqkv = (bf16*)a->dqkv; p.rope_cos = a->rope_cos; p.rope_sin = a->rope_sin; p.query_bounds = a->query_bounds;   // range mode: the per-key table of an asymmetric mask (null: symmetric)
     p.key_ranges = a->key_ranges; p.mask = (const bf16*)a->mask; p.mask_sb = a->mask_sb; p.mask_sh = a->mask_sh; p.mask_sq = a->mask_sq;
     p.B = a->B; p.T = a->T; p.H = a->n_head; p.scale = a->scale;
     p.q_src = p.qkv; p.q_ld = 3 * (int64_t)a->n_head * a->head_dim; p.dq_dst = p.dqkv; p.dq_ld = p.q_ld; p.stat_hs = a->T;   // the queries are the rows of qkv
@@ -1127,7 +1135,6 @@ static int attn_bwd_impl(const obte_attn_bwd_args* a, int delta_ready, obte_stre
     const int64_t fused_ws = a->head_dim == 128 ? fused_bwd_ws_bytes(a->B, a->T, a->n_head) : 0;   // 0: the one-kernel form does not apply
     if (mode != MASK_DENSE && a->head_dim == 128 && (p.drop.thresh16 == 0 || p.drop_bits_in) && a->ws && attn_bwd_mode() == 0 && fused_ws > 0 &&
         a->ws_bytes >= fused_ws && a->T * 3 * a->n_head * 128 * 2 < (1ll << 31)) {   // (its per-lane byte offsets are 32-bit)
-        if (mode == MASK_RANGES) p.query_bounds = nullptr;   // a range mask without a dense tensor: symmetric (the key's own range)
         rc = launch_bwd_fused(p, mode, a->ws, (hipStream_t)s);
     } else if (mode == MASK_DENSE && a->key_ranges && a->query_bounds && a->ranges_exact)
         rc = a->head_dim == 128 ? launch_bwd_gated<128>(p, a->ranges_exact, (hipStream_t)s) : launch_bwd_gated<64>(p, a->ranges_exact, (hipStream_t)s);
@@ -1250,8 +1257,8 @@ __device__ __forceinline__ int64_t rows_lower_bound(const int64_t* rows, int64_t
     return lo;
 }
 // thread i < B + 1: q_off; thread j < n: position and key range of gathered row j; thread m < B T: inverse index and, with a mask, the
-// gathered rows that see key m (the positions of the key's own range: symmetric masks)
-__global__ __launch_bounds__(256) void attn_rows_prep_kernel(const int64_t* rows, int64_t n, int64_t B, int64_t T, const int32_t* kr_full,
+// gathered rows that see key m (the positions of qb_full's entry for the key, or without that table of the key's own range: symmetric masks)
+__global__ __launch_bounds__(256) void attn_rows_prep_kernel(const int64_t* rows, int64_t n, int64_t B, int64_t T, const int32_t* kr_full, const int32_t* qb_full,
                                                               int32_t* q_off, int32_t* q_blk_off, int32_t* q_pos, int32_t* kr_rows, int32_t* qb_rows, int32_t* inv) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i <= B) q_off[i] = (int32_t)rows_lower_bound(rows, n, i * T);   // (q_blk_off: attn_rows_blocks_kernel, once q_off is complete)
@@ -1265,7 +1272,8 @@ __global__ __launch_bounds__(256) void attn_rows_prep_kernel(const int64_t* rows
         inv[i] = (at < n && rows[at] == i) ? (int32_t)at : -1;
         if (kr_full) {
             const int64_t b = i / T, base = rows_lower_bound(rows, n, b * T);
-            const int64_t qs = max((int64_t)kr_full[2 * i], (int64_t)0), qe = min((int64_t)kr_full[2 * i + 1], T);
+            const int32_t* src = qb_full ? qb_full : kr_full;
+            const int64_t qs = max((int64_t)src[2 * i], (int64_t)0), qe = min((int64_t)src[2 * i + 1], T);
             qb_rows[2 * i] = (int32_t)(rows_lower_bound(rows, n, b * T + qs) - base);
             qb_rows[2 * i + 1] = qe > qs ? (int32_t)(rows_lower_bound(rows, n, b * T + qe) - base) : qb_rows[2 * i];
         }
@@ -1299,12 +1307,13 @@ __global__ __launch_bounds__(256) void attn_rows_blocks_kernel(const int32_t* q_
 }
 }  // namespace
 
-int obte_attn_rows_prep(const int64_t* rows, int64_t n, int64_t B, int64_t T, const int32_t* key_ranges_full, int32_t* q_off, int32_t* q_blk_off,
-                        int32_t* q_pos, int32_t* key_ranges_rows, int32_t* query_bounds_rows, int32_t* inv, obte_stream s) {
+int obte_attn_rows_prep(const int64_t* rows, int64_t n, int64_t B, int64_t T, const int32_t* key_ranges_full, const int32_t* query_bounds_full,
+                        int32_t* q_off, int32_t* q_blk_off, int32_t* q_pos, int32_t* key_ranges_rows, int32_t* query_bounds_rows, int32_t* inv, obte_stream s) {
     OBTE_REQUIRE(rows && n > 0 && n <= B * T && q_off && q_blk_off && q_pos && inv, "obte_attn_rows_prep: bad arguments");
     OBTE_REQUIRE(!key_ranges_full || (key_ranges_rows && query_bounds_rows), "obte_attn_rows_prep: a mask needs both output tables");
+    OBTE_REQUIRE(key_ranges_full || !query_bounds_full, "obte_attn_rows_prep: query bounds without key ranges");
     hipLaunchKernelGGL(attn_rows_prep_kernel, dim3((unsigned)cdiv64(B * T + 1, 256)), dim3(256), 0, (hipStream_t)s, rows, n, B, T, key_ranges_full,
-                       q_off, q_blk_off, q_pos, key_ranges_rows, query_bounds_rows, inv);
+                       query_bounds_full, q_off, q_blk_off, q_pos, key_ranges_rows, query_bounds_rows, inv);
     OBTE_CHECK_LAUNCH("obte_attn_rows_prep");
     hipLaunchKernelGGL(attn_rows_blocks_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, q_off, q_blk_off, B);
     OBTE_CHECK_LAUNCH("obte_attn_rows_prep(blocks)");

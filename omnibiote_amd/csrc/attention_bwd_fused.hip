@@ -23,6 +23,32 @@
 // cdna_hip_programming.md Guideline 16, R1: write-through (sc1) stores of the tile, every storing wave's vmcnt(0), the
 // workgroup's barrier, one lane's agent-scope add on the slice's counter; the consumer polls the counter with sc1 loads
 // (the poll of the NEXT hand-off is issued an iteration ahead) and reads the tile with sc1 loads.  Spins are bounded.
+//
+// ASYMMETRIC RANGE MASKS (a causal mask: obte_causal_bounds).  The kernel and its prep launch read ONE table, the per-key query
+// range (p.query_bounds, or for a symmetric mask the key's own key range): a key's [qs, qe) decides its slice sweep, the range test
+// of its score chain and the `inside` fast path, so nothing here assumes that the mask is symmetric.  The chain order was written
+// with ragged document masks in mind, where the key blocks' slice ranges are short and mostly disjoint; a causal mask gives ranges
+// of DIFFERENT LENGTHS WITH A COMMON END — key block k sweeps slices [8 k, nsl), n_k = nsl - 8 k of them, from its own rotation
+// rot_k = k n_k / nkb.  The argument, worked through for that pattern before it ran:
+//   (1) One order.  Member k of slice s visits it at its own time tau_k(s) = (s - 8 k - rot_k) mod n_k, a function of the published
+//       table alone (every workgroup evaluates it for the OTHER members with their n, their rot: the loop over k2 in the prologue).
+//       All members therefore sort the same pairs (tau_k(s), k); the pairs are distinct (k is), so the places 0 .. cnt - 1 are a
+//       permutation, whatever the lengths.  Nothing in it uses equal n or a common begin.
+//   (2) No cycle.  Workgroup k publishes its contribution to the slice it visited at time tau during its iteration tau + 1 (after
+//       the loop for its last one).  That step needs (a) its own iteration tau, and (b) the contributions of the members placed
+//       before it: pairs (tau2, k2) < (tau, k) lexicographically.  Both are strictly smaller in the lexicographic order on
+//       (time, key block), which is well founded: the pending step with the smallest pair never waits for a pending one.  This
+//       holds for any family of ranges; unequal lengths only mean that a short workgroup (key block nkb - 1: 8 slices) runs out of
+//       pairs early and leaves.
+//   (3) Waiting.  With the workgroups of a (batch, head) abreast, a wait is for a pair with a SMALLER time, already published —
+//       except ties (equal tau, lower k first), which cost the later member one hand-off latency.  Example nkb = 4, nsl = 32:
+//       rot = 0, 6, 8, 6; slice 24 is visited at times 24, 10, 0, 2 by key blocks 0..3 (chain 2, 3, 1, 0), slice 31 at 31, 17, 7, 1
+//       (chain 3, 2, 1, 0): the members arrive 2 to 14 iterations apart.  Key block 0 is never placed before a member it would have
+//       to wait for: it visits slice s at time s, and a member with a larger time is placed AFTER it.
+//   (4) What does not carry over is the balance: "all workgroups of a (batch, head) start and finish together" is false under a
+//       causal mask (key block k runs nsl - 8 k iterations).  That is the triangle's own imbalance, not the protocol's; no
+//       workgroup waits for a longer one, because a longer one's later visits are placed after the shorter one's.
+// So the protocol is kept as it is, and obte_attn_bwd hands an asymmetric mask's per-key table to this kernel.
 #include "attn_common.h"
 
 namespace {

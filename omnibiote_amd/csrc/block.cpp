@@ -241,7 +241,7 @@ obte_attn_rows attn_rows_tables(const obte_block_desc* d, const ActLayout& a) {
 int fwd_attention_rows(const obte_block_desc* d, const BlockForm& f, const ActLayout& a, obte_attn_fwd_args af, obte_stream s) {
     const int C = d->n_embd;
     const obte_attn_rows ar = attn_rows_tables(d, a);   // (filled once per call: the backward reads them)
-    TRY(obte_attn_rows_prep(d->out_rows, d->n_out_rows, d->B, d->T, d->key_ranges, a.r_off, a.r_boff, a.r_pos, a.r_kr, a.r_qb, a.r_inv, s));
+    TRY(obte_attn_rows_prep(d->out_rows, d->n_out_rows, d->B, d->T, d->key_ranges, d->query_bounds, a.r_off, a.r_boff, a.r_pos, a.r_kr, a.r_qb, a.r_inv, s));
     TRY(obte_rows_gather_bf16(a.h1, d->out_rows, a.rows_h1, f.Mm, f.M, C, s));
     TRY(run(xWt(a.rows_h1, d->attn_w, a.rows_q, f.Mm, C, C), s, a.splitk_ws, a.splitk_ws_bytes));
     TRY(obte_rope_cols_bf16(a.rows_q, C, C, d->rope_cos, d->rope_sin, f.Mm, d->T, a.r_pos, af.head_dim, s));

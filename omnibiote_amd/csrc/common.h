@@ -62,10 +62,11 @@ struct obte_attn_rows {
     int64_t n;
 };
 // obte_attn_rows_prep fills the five arrays from the ascending row list (global rows b T + position) and the full-size key ranges
-// (null: no mask; the masks are symmetric, SURVEY fact 5: a key's queries are the positions of its own range) and inv [B T]: the
+// (null: no mask), the optional full-size per-key query bounds (null: the mask is symmetric, SURVEY fact 5 — a key's queries are the
+// positions of its own range; given: any mask with single-run rows and columns, a causal one included) and inv [B T]: the
 // gathered index of every row or -1 (block.cpp ActLayout::r_inv: nothing reads it any more).
-int obte_attn_rows_prep(const int64_t* rows, int64_t n, int64_t B, int64_t T, const int32_t* key_ranges_full, int32_t* q_off, int32_t* q_blk_off,
-                        int32_t* q_pos, int32_t* key_ranges_rows, int32_t* query_bounds_rows, int32_t* inv, obte_stream s);
+int obte_attn_rows_prep(const int64_t* rows, int64_t n, int64_t B, int64_t T, const int32_t* key_ranges_full, const int32_t* query_bounds_full,
+                        int32_t* q_off, int32_t* q_blk_off, int32_t* q_pos, int32_t* key_ranges_rows, int32_t* query_bounds_rows, int32_t* inv, obte_stream s);
 int obte_attn_fwd_rows(const obte_attn_fwd_args* a, const obte_attn_rows* r, const obte_bf16* q, obte_stream s);   // a->o, a->lse: gathered
 int obte_attn_bwd_rows(const obte_attn_bwd_args* a, const obte_attn_rows* r, const obte_bf16* q, obte_bf16* dq, obte_stream s);   // a->o, d_o, lse, delta: gathered; a->dqkv: dK, dV thirds
 // out[i] = (aux ? aux[i] : 0) + dropout(in[i]) on gathered rows: the mask element of (i, c) is (rows[i], c) of the whole activation

@@ -1,7 +1,8 @@
 // The integer prelude of an optimizer step, for callers of the C ABI that have no tensor library at hand:
 //   obte_key_ranges_from_tokens   token ids -> the per-query [k_start, k_end) of the reference's document mask
 //   obte_token_order              token ids -> the stable argsort obte_embedding_bwd* takes as `order`
-// Both results are integers with exactly one right answer; neither kernel lets the arrival order of atomics decide where
+//   obte_causal_bounds            (a document range mask, or nothing) -> the pair of tables of the causal mask under it
+// All results are integers with exactly one right answer; neither kernel lets the arrival order of atomics decide where
 // anything lands (the only atomics are the LDS counters of the digit histogram), no workgroup waits on another, and every loop
 // has a bound known at launch.
 #include "common.h"
@@ -325,5 +326,35 @@ extern "C" int obte_token_order(const int64_t* ids, int64_t segments, int64_t se
                            (const uint32_t*)hist, last ? (uint32_t*)nullptr : kbuf[pass & 1], last ? order : ibuf[pass & 1], sh);
         OBTE_CHECK_LAUNCH("obte_token_order(scatter)");
     }
+    return OBTE_OK;
+}
+
+// =============================================================================================== causal bounds
+// Elementwise: thread i owns position (b, t) as a QUERY (its key range, cut at t + 1) and as a KEY (the queries that see it: from
+// t on, to the end of its document).  One 8-byte store per table and position.  An empty result is written as [x, x).
+__global__ __launch_bounds__(256) void causal_bounds_kernel(const int32_t* __restrict__ doc, int64_t n, int T, int32_t* __restrict__ kr,
+                                                            int32_t* __restrict__ qb) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int t = (int)(i % T);
+    int lo = 0, hi = T;
+    if (doc) {
+        const int2 d = *reinterpret_cast<const int2*>(doc + 2 * i);
+        lo = max(d.x, 0); hi = min(d.y, T);
+    }
+    const int k_lo = lo, k_hi = min(hi, t + 1);   // as a query: the keys of its document up to itself
+    const int q_lo = max(lo, t), q_hi = hi;       // as a key: the queries of its document from itself on
+    *reinterpret_cast<int2*>(kr + 2 * i) = make_int2(k_lo, k_hi > k_lo ? k_hi : k_lo);
+    *reinterpret_cast<int2*>(qb + 2 * i) = make_int2(q_lo, q_hi > q_lo ? q_hi : q_lo);
+}
+
+extern "C" int obte_causal_bounds(const int32_t* doc_ranges, int64_t B, int64_t T, int32_t* key_ranges, int32_t* query_bounds, obte_stream s) {
+    OBTE_REQUIRE(key_ranges && query_bounds, "obte_causal_bounds: null pointer");
+    OBTE_REQUIRE(B > 0 && B < (1ll << 31) && T > 0 && T < (1ll << 24), "obte_causal_bounds: bad shape (1 <= B < 2^31, 1 <= T < 2^24)");
+    OBTE_REQUIRE(doc_ranges != key_ranges && doc_ranges != query_bounds && key_ranges != query_bounds, "obte_causal_bounds: the tables must not alias");
+    const int64_t n = B * T;
+    OBTE_REQUIRE((n + 255) / 256 < (1ll << 31), "obte_causal_bounds: B * T too large for one launch");
+    hipLaunchKernelGGL(causal_bounds_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)s, doc_ranges, n, (int)T, key_ranges, query_bounds);
+    OBTE_CHECK_LAUNCH("obte_causal_bounds");
     return OBTE_OK;
 }

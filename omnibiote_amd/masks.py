@@ -16,6 +16,12 @@ One documented difference: positions that the reference leaves fully masked (the
 ``--use_padding`` mode) get the empty range here.  The reference's softmax over an all -1e9 row degenerates to a
 uniform average of V there; the range kernels return 0.  Those positions are PAD: they are excluded from the loss
 (train_encoder.py:278) and no other position attends to them, so neither the loss nor any gradient changes.
+
+Causal attention (``OmniBioTAConfig.autoregressive``, model.py:115-130 of the reference) is a range mask too, but not a symmetric
+one: ``RangeMask.causal`` / ``from_tokens(causal=True)`` carry a second table, ``query_bounds`` — for every KEY the ``[q_start,
+q_end)`` of the queries that see it — which the key-major backward kernels read where a symmetric mask lets them use the key's own
+range.  On the GPU both tables come from one launch (``obte_causal_bounds``, csrc/prelude.hip); the tensor-op form gives the same
+integers.
 """
 from __future__ import annotations
 
@@ -25,12 +31,42 @@ EOS_TOKEN = 3   # training/loader.py:4
 MASKED_VALUE = -1e9
 
 
-class RangeMask:
-    """key_ranges: int32 (B, T, 2), [k_start, k_end) of the keys each query may attend to."""
+def _causal_pair(doc_ranges, B: int, T: int, device):
+    """Tensor-op form of obte_causal_bounds: (key_ranges, query_bounds) of the causal mask, under the symmetric range mask
+    ``doc_ranges`` (int32 (B, T, 2)) if one is given.  Empty results are [x, x)."""
+    t = torch.arange(T, device=device, dtype=torch.int32).view(1, T).expand(B, T)
+    if doc_ranges is None:
+        lo, hi = torch.zeros_like(t), torch.full_like(t, T)
+    else:
+        lo, hi = doc_ranges[..., 0].clamp(min=0), doc_ranges[..., 1].clamp(max=T)
+    k_hi = torch.maximum(torch.minimum(hi, t + 1), lo)
+    q_lo = torch.maximum(lo, t)
+    q_hi = torch.maximum(hi, q_lo)
+    return torch.stack([lo, k_hi], dim=2).contiguous(), torch.stack([q_lo, q_hi], dim=2).contiguous()
 
-    def __init__(self, key_ranges: torch.Tensor):
+
+def _causal_under(doc_ranges, B: int, T: int, device) -> "RangeMask":
+    device = torch.device(device)
+    if device.type == "cuda" and B * T > 0:
+        from . import ops
+        if ops.prelude_hip():   # one launch (obte_causal_bounds) for both tables; same integers as the tensor ops
+            return RangeMask(*ops.causal_bounds(doc_ranges, B, T, device))
+    return RangeMask(*_causal_pair(doc_ranges, B, T, device))
+
+
+class RangeMask:
+    """key_ranges: int32 (B, T, 2), [k_start, k_end) of the keys each query may attend to.
+    query_bounds (optional, int32 (B, T, 2)): [q_start, q_end) of the queries that see each key — the same set of (query, key)
+    pairs told by column, for a mask that is not symmetric (a causal one); every row and every column must be one contiguous run.
+    None: the mask is symmetric (the reference's document masks) and the kernels use a key's own key range."""
+
+    def __init__(self, key_ranges: torch.Tensor, query_bounds: torch.Tensor = None):
         assert key_ranges.dtype == torch.int32 and key_ranges.dim() == 3 and key_ranges.shape[-1] == 2
         self.key_ranges = key_ranges.contiguous()
+        if query_bounds is not None:
+            assert query_bounds.dtype == torch.int32 and query_bounds.shape == key_ranges.shape and query_bounds.device == key_ranges.device
+            query_bounds = query_bounds.contiguous()
+        self.query_bounds = query_bounds
 
     @property
     def shape(self):
@@ -38,15 +74,25 @@ class RangeMask:
         return (B, T, T)
 
     def to(self, device):
-        return RangeMask(self.key_ranges.to(device))
+        return RangeMask(self.key_ranges.to(device), None if self.query_bounds is None else self.query_bounds.to(device))
 
     @staticmethod
-    def from_tokens(input_ids: torch.Tensor, eos_token: int = EOS_TOKEN, padding: bool = False, group: int = 0) -> "RangeMask":
-        """``group`` > 0: ``input_ids`` stacks several mini-batches of ``group`` rows each (the reference builds one
+    def causal(B: int, T: int, device="cpu") -> "RangeMask":
+        """The causal mask of an autoregressive model: query q sees keys [0, q + 1), key k is seen by queries [k, T)."""
+        return _causal_under(None, B, T, device)
+
+    @staticmethod
+    def from_tokens(input_ids: torch.Tensor, eos_token: int = EOS_TOKEN, padding: bool = False, group: int = 0, causal: bool = False) -> "RangeMask":
+        """``causal``: the document mask AND the causal one — query q sees the keys of its document up to itself (the pair of
+        tables; document-packed causal rows).
+        ``group`` > 0: ``input_ids`` stacks several mini-batches of ``group`` rows each (the reference builds one
         mask per mini-batch, and its row-0 exception applies to the first row of EACH mini-batch) — one pass of tensor
         ops for a whole optimizer step's rows instead of one per micro-step."""
         B, T = input_ids.shape
         dev = input_ids.device
+        if causal:
+            doc = RangeMask.from_tokens(input_ids, eos_token, padding, group)
+            return _causal_under(doc.key_ranges, B, T, dev)
         if input_ids.is_cuda and input_ids.dtype == torch.int64 and input_ids.numel() > 0:
             from . import ops
             if ops.prelude_hip():   # one launch (obte_key_ranges_from_tokens) instead of the tensor ops below; same integers

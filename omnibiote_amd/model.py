@@ -18,9 +18,15 @@ Contract notes (each mirrors a reference behaviour):
     into the kernels with a counter-based mask: same distribution and scaling as nn.Dropout, but necessarily a
     different random stream than PyTorch's generator.  Each forward draws its seeds from torch's CPU generator, so
     ``torch.manual_seed`` makes runs reproducible and activation checkpointing recomputes identical masks.
+  * ``OmniBioTAConfig.autoregressive`` follows the reference, quirk included (model.py:115-146): without an ``attn_mask`` the
+    attention is causal (SDPA's is_causal=True / the tril ``bias``) — here the causal RANGE mask, a pair of int32 tables that
+    ``OmniBioTA.forward`` builds once per call (one launch, shared by all layers); WITH an ``attn_mask`` the reference applies that
+    mask alone and is NOT causal (is_causal=False), and so is this module, with a warning.  A caller who wants a document mask
+    and causality passes ``masks.RangeMask.from_tokens(ids, causal=True)``, under either setting of the flag.
 """
 from __future__ import annotations
 
+import warnings
 import weakref
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -89,6 +95,26 @@ def _require_hip(t: torch.Tensor, what: str) -> None:
         raise RuntimeError(f"{what}: parameters/activations must be torch.bfloat16 (the reference trains and evaluates "
                            f"in bf16: train_encoder.py:21,170); got {t.dtype}. Call model.to(torch.bfloat16).")
     L.lib()  # raises HipLibraryError if the shared library is missing
+
+
+def _warn_mask_not_causal() -> None:
+    """One place, so that Python's default filter shows it once per process."""
+    warnings.warn("autoregressive=True with an explicit attn_mask: the mask alone is applied and the attention is NOT causal, as in "
+                  "the reference (model.py:131-145, is_causal=False). Pass masks.RangeMask.from_tokens(ids, causal=True) for a "
+                  "document mask and causality.", UserWarning)
+
+
+def _autoregressive_mask(autoregressive: bool, attn_mask, B: int, T: int, device):
+    """What an autoregressive module attends under (the reference's rule): no mask given -> the causal range mask, built here;
+    a mask given -> that mask alone.  ``attn_mask`` may already be a resolved ops.MaskSpec (OmniBioTA.forward hands its blocks one)."""
+    if not autoregressive:
+        return attn_mask
+    if attn_mask is None:
+        from .masks import RangeMask
+        return RangeMask.causal(B, T, device)
+    if not isinstance(attn_mask, ops.MaskSpec):
+        _warn_mask_not_causal()
+    return attn_mask
 
 
 # ------------------------------------------------------------------------------------------ in-place grad accumulation
@@ -604,7 +630,8 @@ class SelfAttention(nn.Module):
         self.register_buffer("freqs_cis", precompute_freqs_cis(self.n_embd // self.n_head, config.block_size))
         if not self.flash:
             # state_dict parity with the reference's non-flash modules (model.py:92-96); the buffer is unused here:
-            # both settings run the same fused kernel, which is exact attention either way.
+            # both settings run the same fused kernel, which is exact attention either way, and the causal mask of an
+            # autoregressive model is a pair of range tables (masks.RangeMask.causal), not this T x T matrix.
             self.register_buffer("bias", torch.tril(torch.ones(config.block_size, config.block_size))
                                  .view(1, 1, config.block_size, config.block_size))
         self._rope_key = None
@@ -627,9 +654,8 @@ class SelfAttention(nn.Module):
 
     def forward(self, x, attn_mask=None):
         _require_hip(x, "SelfAttention")
-        if self.autoregressive:
-            raise NotImplementedError("autoregressive=True is not used by the encoder (model.py:192) and not implemented")
         B, T, C = x.size()
+        attn_mask = _autoregressive_mask(self.autoregressive, attn_mask, B, T, x.device)
         mask = ops.MaskSpec.from_user(attn_mask, B, T, self.n_head, x.device)
         cos, sin = self.rope()
         p = _active_p(self, self.dropout)
@@ -683,11 +709,10 @@ class Block(nn.Module):
         dropout mask of the MLP projection is drawn for the (n, n_embd) output)."""
         _require_hip(x, "Block")
         _require_hip(self.attn.c_attn.weight, "Block parameters")
-        if self.attn.autoregressive:
-            raise NotImplementedError("autoregressive=True is not used by the encoder and not implemented")
         B, T, C = x.shape
         if out_rows is not None:
             _check_rows(out_rows, B * T, 1)
+        attn_mask = _autoregressive_mask(self.attn.autoregressive, attn_mask, B, T, x.device)
         mask = ops.MaskSpec.from_user(attn_mask, B, T, self.attn.n_head, x.device)
         cos, sin = self.attn.rope()
         # one dropout probability per block, as in the reference (config.dropout feeds all three nn.Dropout modules)
@@ -778,7 +803,8 @@ class OmniBioTA(nn.Module):
     def forward(self, idx, attn_mask=None, return_embeddings=False, rows=None):
         """idx (b, t) int64 -> logits (b, t, vocab) or, with return_embeddings, emb (b, t, n_embd)
         (model.py:225-254).  ``attn_mask``: None, the reference's additive (b, n_head, t, t) tensor (any strides,
-        expand() views included), or a ``masks.RangeMask`` (per-query key ranges; the fast path).
+        expand() views included), or a ``masks.RangeMask`` (per-query key ranges; the fast path).  With
+        ``config.autoregressive`` and no mask the attention is causal; with a mask it is that mask alone (the reference's rule).
         ``rows`` (an extension, not in the reference; int64 (n,), ascending positions of the flattened (b*t) batch): the
         caller needs the result at those positions only — a masked-LM loss looks at ~15 % of them (train_encoder.py:304) —
         and gets (n, n_embd) embeddings or (n, vocab) logits.  Nothing after the last block's attention mixes positions, so
@@ -791,6 +817,8 @@ class OmniBioTA(nn.Module):
         if not idx.is_cuda:
             raise RuntimeError("OmniBioTA.forward: idx must be on the GPU")
         b = idx.shape[0]
+        # autoregressive: the causal pair of tables, built once per call for all layers (nothing kept on a module)
+        attn_mask = _autoregressive_mask(self.config.autoregressive, attn_mask, b, t, idx.device)
         mask = ops.MaskSpec.from_user(attn_mask, b, t, self.config.n_head, idx.device)
         p = _active_p(self, self.transformer.drop.p)
         # a training harness that sorts the token ids of a whole optimizer step in one call (the embedding backward sums
@@ -838,3 +866,9 @@ class OmniBioTA(nn.Module):
         elif method == "max":
             return emb.max(dim=1)[0]
         return emb
+
+
+def next_token_loss(logits, idx):
+    """Mean cross entropy of position t's logits against token t + 1 over every row's first T - 1 positions — the loss of an
+    autoregressive model on its own input (ops.next_token_loss: obte_masked_ce_rows with a row list).  Differentiable."""
+    return ops.next_token_loss(logits, idx)

@@ -314,7 +314,9 @@ class MaskSpec:
     def __init__(self, ranges=None, dense=None, qbounds=None, exact=None):
         """With ``dense``: ``ranges`` / ``qbounds`` are the optional loop bounds of obte_mask_bounds (per query / per key);
         the dense values still decide every weight — unless ``exact`` (obte_mask_bounds' device flag) says the mask IS a
-        range mask, in which case the range kernels serve it (include/omnibiote_hip.h, obte_mask_bounds)."""
+        range mask, in which case the range kernels serve it (include/omnibiote_hip.h, obte_mask_bounds).
+        Without ``dense``: ``ranges`` is the mask, and ``qbounds`` the per-key table of an asymmetric one (a causal mask:
+        masks.RangeMask.query_bounds); None: symmetric."""
         self.ranges, self.dense, self.qbounds, self.exact = ranges, dense, qbounds, exact
         self.sb = self.sh = self.sq = 0
         if dense is not None:
@@ -345,7 +347,12 @@ class MaskSpec:
             _need(r, "key_ranges", torch.int32)
             if tuple(r.shape) != (B, T, 2):
                 raise RuntimeError(f"key_ranges must be (B,T,2)=({B},{T},2), got {tuple(r.shape)}")
-            return MaskSpec(ranges=r)
+            qb = getattr(attn_mask, "query_bounds", None)
+            if qb is not None:
+                _need(qb, "query_bounds", torch.int32)
+                if tuple(qb.shape) != (B, T, 2):
+                    raise RuntimeError(f"query_bounds must be (B,T,2)=({B},{T},2), got {tuple(qb.shape)}")
+            return MaskSpec(ranges=r, qbounds=qb)
         m = attn_mask
         if not isinstance(m, torch.Tensor):
             raise TypeError("attn_mask must be None, a tensor or a RangeMask")
@@ -467,6 +474,25 @@ def key_ranges_from_tokens(ids, eos_token: int = 3, padding: bool = False, group
     return out
 
 
+def causal_bounds(doc_ranges=None, B: Optional[int] = None, T: Optional[int] = None, device=None):
+    """(key_ranges, query_bounds), int32 (B, T, 2) each: the causal mask's pair of tables (obte_causal_bounds), under the symmetric
+    range mask ``doc_ranges`` (int32 (B, T, 2), e.g. key_ranges_from_tokens' output) if one is given — then B, T and the device
+    are its own.  masks.RangeMask.causal / from_tokens(causal=True) are the tensor-op form of the same function."""
+    if doc_ranges is not None:
+        _need(doc_ranges, "doc_ranges", torch.int32)
+        if doc_ranges.dim() != 3 or doc_ranges.shape[-1] != 2 or doc_ranges.numel() == 0:
+            raise RuntimeError(f"doc_ranges: expected a non-empty (B, T, 2) tensor, got {tuple(doc_ranges.shape)}")
+        if (B is not None and B != doc_ranges.shape[0]) or (T is not None and T != doc_ranges.shape[1]):
+            raise RuntimeError(f"doc_ranges {tuple(doc_ranges.shape)} does not match B {B}, T {T}")
+        B, T, device = doc_ranges.shape[0], doc_ranges.shape[1], doc_ranges.device
+    elif B is None or T is None or device is None or B <= 0 or T <= 0:
+        raise RuntimeError("causal_bounds: without doc_ranges, B >= 1, T >= 1 and the device are needed")
+    kr = torch.empty((B, T, 2), dtype=torch.int32, device=device)
+    qb = torch.empty((B, T, 2), dtype=torch.int32, device=device)
+    L.check(L.lib().obte_causal_bounds(_ptr(doc_ranges), B, T, _ptr(kr), _ptr(qb), _stream()), "obte_causal_bounds")
+    return kr, qb
+
+
 def token_order_workspace(segments: int, seg_len: int, vocab: int, device) -> torch.Tensor:
     nbytes = int(L.lib().obte_token_order_ws_bytes(segments, seg_len, vocab))
     if nbytes <= 0:
@@ -558,6 +584,36 @@ def masked_ce_rows(logits, targets, rows, n_accum: int, row_weights: Optional[to
     L.check(L.lib().obte_masked_ce_rows(_ptr(logits), _ptr(targets), _ptr(rows), None, row_scale, _ptr(row_weights),
                                         _ptr(row_loss), _ptr(dl), n, M, V, _stream()), "obte_masked_ce_rows")
     return row_loss.sum(), dl
+
+
+class _NextTokenLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, rows):
+        loss, dl = masked_ce_rows(logits, targets, rows, 1)
+        ctx.save_for_backward(dl, rows)
+        ctx.shape = logits.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dl, rows = ctx.saved_tensors
+        V = ctx.shape[-1]
+        d = torch.zeros(ctx.shape, dtype=dl.dtype, device=dl.device)
+        d.view(-1, V).index_copy_(0, rows, dl * dloss.to(dl.dtype))
+        return d, None, None
+
+
+def next_token_loss(logits, idx):
+    """Mean cross entropy of position t's logits against token t + 1, over the first T - 1 positions of every row: the loss of
+    an autoregressive model (``OmniBioTAConfig.autoregressive``) on its own input.  logits bf16 (B, T, V), idx int64 (B, T),
+    T >= 2.  obte_masked_ce_rows on the row list {b T + t : t < T - 1}; differentiable with respect to the logits."""
+    _need(logits, "logits"); _need(idx, "idx", torch.int64)
+    B, T = idx.shape
+    if logits.dim() != 3 or tuple(logits.shape[:2]) != (B, T) or T < 2:
+        raise RuntimeError(f"next_token_loss: logits (B, T, V) and idx (B, T) with T >= 2, got {tuple(logits.shape)} and {tuple(idx.shape)}")
+    targets = torch.roll(idx, shifts=-1, dims=1).contiguous().reshape(-1)      # (the wrapped last column is not a listed row)
+    rows = (torch.arange(B, device=idx.device).view(B, 1) * T + torch.arange(T - 1, device=idx.device).view(1, T - 1)).reshape(-1)
+    return _NextTokenLossFn.apply(logits.contiguous(), targets, rows)
 
 
 def adamw_step_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, clip_coef=None):
