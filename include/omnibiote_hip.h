@@ -56,12 +56,13 @@ int obte_device_status(int clear);
 int obte_fault_inject(int what);
 
 /* ---- opt-in launch profiler (measurement only; off by default) ----------------------------------------------
- * While enabled, every obte_gemm_bf16 / obte_attn_fwd / obte_attn_bwd call is bracketed by two hipEvents on the
+ * While enabled, every obte_gemm_bf16 / obte_attn_fwd / obte_attn_bwd / obte_attn_decode call is bracketed by two hipEvents on the
  * caller's stream.  obte_profile_collect synchronises those events and returns up to cap records:
  * ms[i] = elapsed milliseconds, dims[3*i..] = (M,N,K) for a GEMM or (B*H, T, head_dim) for attention,
  * kind[i] = a_kmajor*8 + b_kmajor*4 + epilogue + 1000 * kernel structure (1 gemm_bf16_kernel, 2 gemm_v2_kernel,
  * 3 gemm_v3_kernel, 4 gemm_v4_kernel, 7 gemm_v7_kernel) for a GEMM, its split-K reduce inside the same record; 32 + 1 (the first
- * and last problems differ in layout) + 2 (accumulate) for a grouped launch; 100 = attention forward, 101 = attention backward; the HBM-bound
+ * and last problems differ in layout) + 2 (accumulate) for a grouped launch; 100 = attention forward, 101 = attention backward, 102 = obte_attn_decode
+ * over (B*H, n_keys, head_dim), its combine launch inside the same record; the HBM-bound
  * kernels record (rows, cols, flag): 110 LayerNorm forward, 111 LayerNorm backward (flag = residual gradient added),
  * 112 masked CE over (n_rows, vocab), 113 AdamW over (elements, 1, 1).
  * Returns the number of records written (records are cleared). */
@@ -513,6 +514,52 @@ int obte_rows_scatter_bf16(const obte_bf16* src, const int64_t* rows, obte_bf16*
  * An empty result is written as [x, x).  Both outputs int32 [B,T,2], distinct from each other and from doc_ranges.
  * 1 <= B < 2^31, 1 <= T < 2^24.  One elementwise launch on the caller's stream; integers with one right answer. */
 int obte_causal_bounds(const int32_t* doc_ranges, int64_t B, int64_t T, int32_t* key_ranges, int32_t* query_bounds, obte_stream s);
+
+/* ---- autoregressive generation: key/value cache and one-query attention -------------------------------------------
+ * Beyond the reference: its model is nanoGPT with generate() struck out (the header of training/model.py), so an autoregressive model
+ * (model.py:115-130, is_causal=True) could only produce a next token by running the whole prefix again.  Here a new position costs
+ * its own projections and one read of the cache.  No new struct: plain arguments, the conventions of this header (caller-owned
+ * buffers, the caller's stream, no allocation, no synchronisation).
+ *
+ * The cache of ONE layer is a single buffer of obte_kv_cache_bytes() bytes (0 for a shape the entry points reject): K as bf16
+ * [B, H, T_max, hs] — the rotated keys exactly as the attention kernels read them from the packed qkv — and V behind it in the same
+ * shape.  head_dim in {64, 128}; 16-byte aligned.
+ * obte_kv_cache_store copies the k and v thirds of qkv — the packed [B*t, 3C] activation after RoPE — into positions
+ * [pos0, pos0 + t) of every (b, h): bit for bit, 16 bytes per lane, no other position touched.  pos0 + t <= T_max, else OBTE_EINVAL.
+ * A prompt: t = its length, pos0 = 0; a generated position: t = 1. */
+int64_t obte_kv_cache_bytes(int64_t B, int64_t T_max, int32_t n_head, int32_t head_dim);
+int obte_kv_cache_store(const obte_bf16* qkv, int64_t B, int64_t t, int32_t n_head, int32_t head_dim, obte_bf16* cache, int64_t T_max,
+                        int64_t pos0, obte_stream s);
+/* softmax(q k^T * scale) v for ONE query per (b, h) over cache positions [0, n_keys), 1 <= n_keys <= T_max.  The query of (b, h) is
+ * read at q + b*q_ld + h*hs (q_ld = 3C reads the q third of a packed row in place; q_ld = C a dense [B, C]); o is bf16 [B, C], heads
+ * side by side; lse (nullable) fp32 [B, H], the natural log of the sum of the exponentials of the scaled scores, as obte_attn_fwd
+ * defines it.  B * n_head <= 65535.
+ * The keys are split over `splits` workgroups per (b, h): each writes an fp32 partial (m, l, acc[hs]) to ws and a second small
+ * launch combines them in split order — no atomics, no flags, no hand-off between workgroups: two launches of the same call give the
+ * same bytes.  With one split the kernel writes o and lse itself, there is no second launch and ws may be NULL.  splits = 0: the
+ * library's choice, obte_attn_decode_splits(), a pure function of its arguments; 1 .. OBTE_ATTN_DECODE_MAX_SPLITS forces a count
+ * (a split that receives no keys is legal and contributes exactly nothing).  ws: obte_attn_decode_ws_bytes() bytes serve any count.
+ * Cache positions >= n_keys never reach the result, whatever bit patterns they hold (NaN included): a cache may be reused for a
+ * shorter sequence without clearing it.  fp32 scores, fp32 online softmax, fp32 probabilities in the P V sum; the cache is read once. */
+#define OBTE_ATTN_DECODE_MAX_SPLITS 64
+int64_t obte_attn_decode_ws_bytes(int64_t B, int32_t n_head, int32_t head_dim);
+int obte_attn_decode_splits(int64_t B, int32_t n_head, int32_t head_dim, int64_t n_keys);
+int obte_attn_decode(const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max, int64_t n_keys,
+                     int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws, int64_t ws_bytes, obte_stream s);
+/* The block over a prompt: obte_block_fwd_infer (every value of y bit for bit its y, the same workspace, obte_block_infer_ws_bytes)
+ * plus obte_kv_cache_store of the workspace's qkv at pos0 = 0; d->T <= T_max.  The descriptor means what it means there (a causal
+ * model hands its pair of tables; out_rows != NULL returns OBTE_EUNSUPPORTED). */
+int obte_block_fwd_prefill(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y, void* ws, int64_t ws_bytes, obte_bf16* kv_cache,
+                           int64_t T_max, obte_stream s);
+/* The block on ONE new position per batch row, every row at position pos (0 <= pos < T_max): x and y are [B, C], y may alias x.
+ * d->T must be 1.  d->rope_cos / rope_sin are the FULL tables, at least pos + 1 rows.  key_ranges, mask, query_bounds, out_rows must
+ * be NULL and dropout_p 0, else OBTE_EUNSUPPORTED: the new position sees every cached one.  The sequence: LayerNorm, c_attn with RoPE
+ * at row pos of the tables, obte_kv_cache_store(t = 1, pos0 = pos), obte_attn_decode(n_keys = pos + 1), then obte_block_fwd_infer's
+ * projection + residual, LayerNorm, c_fc with OBTE_EPI_GELU_ACT and c_proj + residual; the products through obte_gemm_bf16 at M = B.
+ * ws: obte_block_decode_ws_bytes() bytes (0 for a shape the block rejects), 256-byte aligned, contents irrelevant before and after. */
+int64_t obte_block_decode_ws_bytes(int64_t B, int32_t n_embd, int32_t n_head);
+int obte_block_decode(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y, obte_bf16* kv_cache, int64_t T_max, int64_t pos, void* ws,
+                      int64_t ws_bytes, obte_stream s);
 
 #ifdef __cplusplus
 }

@@ -81,6 +81,7 @@ class MtMasterArgs(C.Structure):
 EPI_NONE, EPI_GELU, EPI_ADD, EPI_GELU_BWD, EPI_ADD_DROPOUT, EPI_ROPE_QK = 0, 1, 2, 3, 4, 5
 EPI_ACC32 = 8
 EPI_GELU_ACT = 9   # the activation alone: EPI_GELU's d2 as d, for a forward nobody will differentiate
+ATTN_DECODE_MAX_SPLITS = 64   # OBTE_ATTN_DECODE_MAX_SPLITS
 SITE_EMBED, SITE_ATTN, SITE_RESID, SITE_MLP, SITE_USER = 0, 1, 2, 3, 7
 
 # name -> (restype, argtypes); every symbol include/omnibiote_hip.h declares
@@ -148,6 +149,15 @@ SYMBOLS = {
     "obte_block_bwd": (C.c_int, [C.POINTER(BlockDesc)] + [C.c_void_p] * 11 + [c_stream]),
     "obte_block_bwd_acc": (C.c_int, [C.POINTER(BlockDesc)] + [C.c_void_p] * 11 + [C.c_int, c_stream]),
     "obte_causal_bounds": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, c_stream]),
+    "obte_kv_cache_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "obte_kv_cache_store": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, c_stream]),
+    "obte_attn_decode_ws_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "obte_attn_decode_splits": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
+    "obte_attn_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                   C.c_float, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_fwd_prefill": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_decode_ws_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "obte_block_decode": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
 }
 
 _lib = None

@@ -1,0 +1,293 @@
+// Autoregressive generation: the key/value cache and attention for ONE query per (batch, head) (include/omnibiote_hip.h,
+// "autoregressive generation"; extends training/model.py:115-130, whose generate() the reference struck out).
+//
+// The cache of one layer is K [B, H, T_max, hs] followed by V in the same shape, bf16: a (b, h)'s keys are hs * 2 bytes apart, so a
+// step streams them as one contiguous run.  obte_kv_cache_store copies the k and v thirds of a packed qkv activation there.
+//
+// obte_attn_decode is bound by the read of the cache: 4 hs bytes per key against 4 hs flops.  No MFMA, no LDS staging:
+//   - grid (split, b H + h); a workgroup of 4 waves owns the keys [k0, k1) of its split.  hs / 8 lanes share one key, each holding 16
+//     bytes (8 dims) of its K row and of its V row: a wave's load instruction covers 1 KiB of consecutive rows, and the lane that
+//     multiplies dims 8c .. 8c+7 of q by K is the one that accumulates those dims of P V.  UNROLL keys per lane group are loaded (K and
+//     V: 2 UNROLL 16-byte loads in flight per lane) before the first of them is used.
+//   - q sits in 8 fp32 registers per lane with scale * log2(e) folded in; a score is 8 FMAs and a DPP sum over the key's lanes.  Every
+//     lane group runs its own online softmax (m, l, acc[8] in fp32, exp2 domain): nothing crosses lanes inside the loop but the score.
+//   - the groups of a wave merge by lane exchange, the waves through LDS in wave order; the workgroup writes o / lse itself (one split)
+//     or an fp32 partial (acc[hs], m, l) to the workspace, which a second launch combines in split order.  No atomics, no flags.
+//   - a key at or beyond k1 never enters: its loads are redirected to the split's last key, its score is -inf, its weight an exact 0
+//     and its V a selected 0, so whatever the cache holds past n_keys (NaN patterns included) cannot reach the result.  A lane group,
+//     a wave or a split without any key carries (m = -inf, l = 0, acc = 0); every merge rescales against a maximum made finite first,
+//     so exp2(-inf - -inf) is never formed.
+#include "common.h"
+
+namespace {
+
+constexpr int DEC_WAVES = 4;     // waves per workgroup
+constexpr int DEC_UNROLL = 4;    // keys per lane group whose loads are in flight together (K and V: 8 loads of 16 bytes per lane)
+constexpr int DEC_CHUNK = 64;    // split boundaries are multiples of this many keys (16 KiB of K at head size 128)
+constexpr int DEC_PAD = 4;       // a partial is hs + 4 floats (acc[hs], m, l, 2 unused): 16-byte aligned rows
+
+__device__ __forceinline__ void unpack8(u32x4 r, float* f) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        f[2 * j] = __builtin_bit_cast(float, r[j] << 16);
+        f[2 * j + 1] = __builtin_bit_cast(float, r[j] & 0xFFFF0000u);
+    }
+}
+
+// sum over the LPR (8 or 16) consecutive lanes that share a key: every one of them gets the total
+template <int LPR>
+__device__ __forceinline__ float group_sum(float v) {
+    v += dpp_moved<0xB1>(v);          // quad_perm [1,0,3,2]
+    v += dpp_moved<0x4E>(v);          // quad_perm [2,3,0,1]
+    v += dpp_moved<0x141>(v);         // row_half_mirror: 8 lanes
+    if (LPR == 16) v += dpp_moved<0x140>(v);   // row_mirror: 16 lanes
+    return v;
+}
+
+struct Part { float m, l, acc[8]; };   // one online-softmax state, exp2 domain: sum_k exp2(s_k - m) (1, v_k) for the 8 dims of a lane
+
+// a += b with both rescaled to the common maximum; an empty side (m = -inf, l = 0, acc = 0) adds exactly nothing
+__device__ __forceinline__ void merge(Part& a, const Part& b) {
+    const float m = fmaxf(a.m, b.m);
+    const float ms = m == -INFINITY ? 0.f : m;
+    const float wa = __builtin_amdgcn_exp2f(a.m - ms), wb = __builtin_amdgcn_exp2f(b.m - ms);
+    a.m = m;
+    a.l = a.l * wa + b.l * wb;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a.acc[j] = a.acc[j] * wa + b.acc[j] * wb;
+}
+
+// UNROLL keys of one lane group.  TAIL: some of them may lie at or beyond k1.
+template <int LPR, bool TAIL>
+__device__ __forceinline__ void decode_keys(Part& st, const float* qf, const bf16* kb, const bf16* vb, int hs, int key0, int kstride, int k1, int chunk) {
+    u32x4 kr[DEC_UNROLL], vr[DEC_UNROLL];
+    bool ok[DEC_UNROLL];
+#pragma unroll
+    for (int u = 0; u < DEC_UNROLL; ++u) {
+        const int key = key0 + u * kstride;
+        ok[u] = !TAIL || key < k1;
+        const int64_t off = (int64_t)(ok[u] ? key : k1 - 1) * hs + chunk * 8;   // (k1 - 1 >= k0: a workgroup with no key never gets here)
+        kr[u] = *(const u32x4*)(kb + off);
+        vr[u] = *(const u32x4*)(vb + off);
+    }
+    float sc[DEC_UNROLL];
+    float mx = st.m;
+#pragma unroll
+    for (int u = 0; u < DEC_UNROLL; ++u) {
+        float kf[8];
+        unpack8(kr[u], kf);
+        float d = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d = __builtin_fmaf(qf[j], kf[j], d);
+        d = group_sum<LPR>(d);
+        sc[u] = ok[u] ? d : -INFINITY;
+        mx = fmaxf(mx, sc[u]);
+    }
+    const float ms = (TAIL && mx == -INFINITY) ? 0.f : mx;
+    const float alpha = __builtin_amdgcn_exp2f(st.m - ms);
+    st.m = mx;
+    st.l *= alpha;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) st.acc[j] *= alpha;
+#pragma unroll
+    for (int u = 0; u < DEC_UNROLL; ++u) {
+        const float p = ok[u] ? __builtin_amdgcn_exp2f(sc[u] - ms) : 0.f;
+        float vf[8];
+        unpack8(ok[u] ? vr[u] : u32x4{0u, 0u, 0u, 0u}, vf);
+        st.l += p;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) st.acc[j] = __builtin_fmaf(p, vf[j], st.acc[j]);
+    }
+}
+
+// HS: 64 or 128.  grid (splits, B * H), DEC_WAVES * 64 threads.  per: keys per split (a multiple of DEC_CHUNK).
+// splits == 1: o and lse are final.  Else part[(bh * splits + split) * (HS + DEC_PAD)] = (acc[HS], m, l).
+template <int HS>
+__global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16* __restrict__ q, int64_t q_ld, const bf16* __restrict__ cache,
+                                                                      bf16* __restrict__ o, float* __restrict__ lse, float* __restrict__ part,
+                                                                      int H, int64_t T_max, int64_t v_off, int n_keys, int per, float qscale) {
+    constexpr int LPR = HS / 8;        // lanes per key
+    constexpr int G = 64 / LPR;        // keys per wave and load
+    const int split = blockIdx.x, splits = gridDim.x, bh = blockIdx.y;
+    const int b = bh / H, h = bh % H;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int chunk = lane % LPR, grp = lane / LPR;
+    const int k0 = min(split * per, n_keys), k1 = min(k0 + per, n_keys);
+
+    float qf[8];
+    unpack8(*(const u32x4*)(q + b * q_ld + h * HS + chunk * 8), qf);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) qf[j] *= qscale;
+
+    const bf16* kb = cache + (int64_t)bh * T_max * HS;
+    const bf16* vb = kb + v_off;
+    Part st;
+    st.m = -INFINITY; st.l = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) st.acc[j] = 0.f;
+
+    constexpr int KSTRIDE = DEC_WAVES * G;              // keys between two of a lane group's UNROLL keys
+    constexpr int ROUND = KSTRIDE * DEC_UNROLL;         // keys of one workgroup round
+    const int full_end = k0 + (k1 - k0) / ROUND * ROUND;
+    int base = k0;
+    for (; base < full_end; base += ROUND) decode_keys<LPR, false>(st, qf, kb, vb, HS, base + wave * G + grp, KSTRIDE, k1, chunk);
+    if (base < k1) decode_keys<LPR, true>(st, qf, kb, vb, HS, base + wave * G + grp, KSTRIDE, k1, chunk);   // (workgroup-uniform)
+
+    // the lane groups of a wave: exchange with the lane LPR, 2 LPR, .. 32 away (the same dims of another key's state)
+#pragma unroll
+    for (int off = LPR; off < 64; off <<= 1) {
+        Part other;
+        other.m = __shfl_xor(st.m, off, 64); other.l = __shfl_xor(st.l, off, 64);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) other.acc[j] = __shfl_xor(st.acc[j], off, 64);
+        // both partners must add in one order for the result to be the same on each: the lower lane's state first
+        if (lane & off) { Part t = other; merge(t, st); st = t; }
+        else merge(st, other);
+    }
+    // the waves, through LDS, in wave order
+    __shared__ float lds[DEC_WAVES][LPR][10];
+    if (lane < LPR) {
+        lds[wave][lane][0] = st.m; lds[wave][lane][1] = st.l;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) lds[wave][lane][2 + j] = st.acc[j];
+    }
+    __syncthreads();
+    if (threadIdx.x >= LPR) return;
+    Part tot;
+    tot.m = lds[0][lane][0]; tot.l = lds[0][lane][1];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tot.acc[j] = lds[0][lane][2 + j];
+#pragma unroll
+    for (int w = 1; w < DEC_WAVES; ++w) {
+        Part p;
+        p.m = lds[w][lane][0]; p.l = lds[w][lane][1];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) p.acc[j] = lds[w][lane][2 + j];
+        merge(tot, p);
+    }
+    if (splits == 1) {   // n_keys >= 1: l > 0
+        const float inv = 1.0f / tot.l;
+        bf16x8 out;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) out[j] = f2bf(tot.acc[j] * inv);
+        *(bf16x8*)(o + ((int64_t)bh * HS + lane * 8)) = out;
+        if (lse && lane == 0) lse[bh] = (tot.m + __builtin_amdgcn_logf(tot.l)) * 0.6931471805599453f;   // v_log_f32 is log2
+        return;
+    }
+    float* pr = part + ((int64_t)bh * splits + split) * (HS + DEC_PAD);
+    *(f32x4*)(pr + lane * 8) = f32x4{tot.acc[0], tot.acc[1], tot.acc[2], tot.acc[3]};
+    *(f32x4*)(pr + lane * 8 + 4) = f32x4{tot.acc[4], tot.acc[5], tot.acc[6], tot.acc[7]};
+    if (lane == 0) { pr[HS] = tot.m; pr[HS + 1] = tot.l; }
+}
+
+// grid B * H, HS threads: thread d sums dim d of the partials in split order against their common maximum.  At least one split holds a
+// key (n_keys >= 1), so the maximum is finite and an empty split's weight is exp2(-inf) = 0.
+template <int HS>
+__global__ __launch_bounds__(HS) void attn_decode_combine_kernel(const float* __restrict__ part, bf16* __restrict__ o, float* __restrict__ lse, int splits) {
+    const int bh = blockIdx.x, d = threadIdx.x;
+    const float* pr = part + (int64_t)bh * splits * (HS + DEC_PAD);
+    float m = -INFINITY;
+    for (int s = 0; s < splits; ++s) m = fmaxf(m, pr[s * (HS + DEC_PAD) + HS]);
+    float l = 0.f, acc = 0.f;
+    for (int s = 0; s < splits; ++s) {
+        const float* p = pr + s * (HS + DEC_PAD);
+        const float w = __builtin_amdgcn_exp2f(p[HS] - m);
+        l += p[HS + 1] * w;
+        acc += p[d] * w;
+    }
+    o[(int64_t)bh * HS + d] = f2bf(acc / l);
+    if (lse && d == 0) lse[bh] = (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;
+}
+
+// one thread per 16 bytes: item = ((row * 2 + which) * C + column) / 8 of the k (which = 0) and v thirds of qkv
+__global__ __launch_bounds__(256) void kv_cache_store_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ cache, int64_t items, int t, int H, int hs,
+                                                             int64_t T_max, int64_t pos0, int64_t v_off) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= items) return;
+    const int C = H * hs, cpr = C / 8;             // 16-byte items per third of a row
+    const int c8 = (int)(i % cpr);
+    const int64_t rw = i / cpr;
+    const int which = (int)(rw & 1);
+    const int64_t row = rw >> 1;                   // b * t + ti
+    const int64_t b = row / t, ti = row % t;
+    const int col = c8 * 8, h = col / hs, e = col % hs;
+    const u32x4 v = *(const u32x4*)(qkv + row * 3 * C + (1 + which) * C + col);
+    *(u32x4*)(cache + which * v_off + ((b * H + h) * T_max + pos0 + ti) * hs + e) = v;
+}
+
+bool shape_ok(int64_t B, int64_t T_max, int32_t n_head, int32_t head_dim) {
+    return B > 0 && B < (1ll << 31) && T_max > 0 && T_max < (1ll << 24) && n_head > 0 && n_head <= 1024 && (head_dim == 64 || head_dim == 128) &&
+           B * n_head < (1ll << 31);
+}
+
+}  // namespace
+
+extern "C" int64_t obte_kv_cache_bytes(int64_t B, int64_t T_max, int32_t n_head, int32_t head_dim) {
+    return shape_ok(B, T_max, n_head, head_dim) ? 2 * B * n_head * T_max * head_dim * 2 : 0;
+}
+
+extern "C" int obte_kv_cache_store(const obte_bf16* qkv, int64_t B, int64_t t, int32_t n_head, int32_t head_dim, obte_bf16* cache, int64_t T_max,
+                                   int64_t pos0, obte_stream s) {
+    OBTE_REQUIRE(qkv && cache, "obte_kv_cache_store: null pointer");
+    OBTE_REQUIRE(shape_ok(B, T_max, n_head, head_dim), "obte_kv_cache_store: bad shape (head_dim 64 or 128)");
+    OBTE_REQUIRE(t > 0 && pos0 >= 0 && pos0 + t <= T_max, "obte_kv_cache_store: positions [%lld, %lld) do not fit T_max = %lld", (long long)pos0,
+                 (long long)(pos0 + t), (long long)T_max);
+    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)cache) & 15) == 0, "obte_kv_cache_store: qkv and cache must be 16-byte aligned");
+    const int64_t items = B * t * 2 * n_head * head_dim / 8;
+    OBTE_REQUIRE(cdiv64(items, 256) < (1ll << 31), "obte_kv_cache_store: too many rows for one launch");
+    hipLaunchKernelGGL(kv_cache_store_kernel, dim3((unsigned)cdiv64(items, 256)), dim3(256), 0, (hipStream_t)s, (const bf16*)qkv, (bf16*)cache, items, (int)t,
+                       n_head, head_dim, T_max, pos0, B * n_head * T_max * head_dim);
+    OBTE_CHECK_LAUNCH("obte_kv_cache_store");
+    return OBTE_OK;
+}
+
+extern "C" int64_t obte_attn_decode_ws_bytes(int64_t B, int32_t n_head, int32_t head_dim) {
+    return shape_ok(B, 1, n_head, head_dim) ? B * n_head * OBTE_ATTN_DECODE_MAX_SPLITS * (int64_t)(head_dim + DEC_PAD) * 4 : 0;
+}
+
+// The default split count.  A split is worth its workgroup (and the combine launch behind it) only with DEC_MIN_KEYS keys of its own, and
+// more than DEC_TARGET_WGS workgroups in all buy nothing: every CU has one (the decode section, has the measurements).
+constexpr int64_t DEC_TARGET_WGS = 256;   // 1 per CU
+constexpr int64_t DEC_MIN_KEYS = 256;
+extern "C" int obte_attn_decode_splits(int64_t B, int32_t n_head, int32_t head_dim, int64_t n_keys) {
+    if (!shape_ok(B, 1, n_head, head_dim) || n_keys < 1) return 1;
+    const int64_t by_fill = cdiv64(DEC_TARGET_WGS, B * n_head), by_keys = n_keys / DEC_MIN_KEYS;
+    int64_t n = by_fill < by_keys ? by_fill : by_keys;
+    if (n > OBTE_ATTN_DECODE_MAX_SPLITS) n = OBTE_ATTN_DECODE_MAX_SPLITS;
+    return n < 1 ? 1 : (int)n;
+}
+
+extern "C" int obte_attn_decode(const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max, int64_t n_keys,
+                                int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws, int64_t ws_bytes, obte_stream s) {
+    OBTE_REQUIRE(q && cache && o, "obte_attn_decode: null pointer");
+    OBTE_REQUIRE(shape_ok(B, T_max, n_head, head_dim) && B * n_head <= 65535, "obte_attn_decode: bad shape (head_dim 64 or 128, B * n_head <= 65535)");
+    OBTE_REQUIRE(n_keys >= 1 && n_keys <= T_max, "obte_attn_decode: n_keys = %lld outside [1, T_max = %lld]", (long long)n_keys, (long long)T_max);
+    OBTE_REQUIRE(q_ld >= (int64_t)n_head * head_dim && q_ld % 8 == 0, "obte_attn_decode: q_ld must be a multiple of 8 and at least n_head * head_dim");
+    OBTE_REQUIRE((((uintptr_t)q | (uintptr_t)cache | (uintptr_t)o) & 15) == 0, "obte_attn_decode: q, cache and o must be 16-byte aligned");
+    OBTE_REQUIRE(splits >= 0 && splits <= OBTE_ATTN_DECODE_MAX_SPLITS, "obte_attn_decode: splits = %d outside [0, %d]", splits, OBTE_ATTN_DECODE_MAX_SPLITS);
+    if (splits == 0) splits = obte_attn_decode_splits(B, n_head, head_dim, n_keys);
+    if (splits > 1) {
+        const int64_t need = B * n_head * splits * (int64_t)(head_dim + DEC_PAD) * 4;
+        OBTE_REQUIRE(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0, "obte_attn_decode: %d splits need a 16-byte aligned workspace of %lld bytes, got %lld",
+                     splits, (long long)need, (long long)(ws ? ws_bytes : 0));
+    }
+    const int per = (int)(cdiv64(cdiv64(n_keys, splits), DEC_CHUNK) * DEC_CHUNK);
+    const hipStream_t st = (hipStream_t)s;
+    const int BH = (int)(B * n_head);
+    const float qscale = scale * 1.4426950408889634f;
+    const int64_t v_off = B * n_head * T_max * head_dim;
+    const int prof = obte_prof_begin(st, 102, BH, n_keys, head_dim);   // cache bytes read = 4 * BH * n_keys * head_dim
+    const dim3 grid((unsigned)splits, (unsigned)BH), block(DEC_WAVES * 64);
+    if (head_dim == 128) {
+        hipLaunchKernelGGL(attn_decode_kernel<128>, grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max, v_off,
+                           (int)n_keys, per, qscale);
+        if (splits > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(BH), dim3(128), 0, st, (const float*)ws, (bf16*)o, lse, splits);
+    } else {
+        hipLaunchKernelGGL(attn_decode_kernel<64>, grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max, v_off,
+                           (int)n_keys, per, qscale);
+        if (splits > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(BH), dim3(64), 0, st, (const float*)ws, (bf16*)o, lse, splits);
+    }
+    obte_prof_end(prof, st);
+    OBTE_CHECK_LAUNCH("obte_attn_decode");
+    return OBTE_OK;
+}

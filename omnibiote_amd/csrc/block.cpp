@@ -26,7 +26,9 @@
 //                                                     rows, then dQ rows
 // The reuses are named members of ActLayout / WsLayout, each with the moment from which its region is free.
 // obte_block_fwd_infer is the full form's forward for a caller who will never run the backward: the same products, nothing kept
-// (InferLayout: seven [M, C] units instead of fifteen), c_fc's activation without its derivative.
+// (InferLayout: seven [M, C] units instead of fifteen), c_fc's activation without its derivative.  obte_block_fwd_prefill is that call with
+// the rotated keys and the values also copied into a layer's key/value cache, obte_block_decode the same sequence on ONE new position per
+// row whose attention reads that cache (csrc/attention_decode.hip): the three share infer_sequence() below.
 #include "common.h"
 
 namespace {
@@ -475,33 +477,95 @@ extern "C" int64_t obte_block_infer_ws_bytes(int64_t B, int64_t T, int32_t n_emb
     return InferLayout(B, T, n_embd, n_head).total;
 }
 
-extern "C" int obte_block_fwd_infer(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* ws, int64_t ws_bytes, obte_stream s) {
-    TRY(check_desc("obte_block_fwd_infer", d));
-    if (d->out_rows) {
-        obte_set_error("obte_block_fwd_infer: the rows form (out_rows) stays with obte_block_fwd");
-        return OBTE_EUNSUPPORTED;
-    }
-    OBTE_REQUIRE(x && y_out && ws, "obte_block_fwd_infer: null pointer");
+namespace {
+
+// The one sequence of a forward nobody will differentiate, on M rows laid out in `w`: obte_block_fwd_infer (the attention over the call's
+// own positions), obte_block_fwd_prefill (the same, and the rotated keys and the values kept) and obte_block_decode (one new position per
+// row against the cache).  rope_cos / rope_sin / rope_T: what c_attn's epilogue rotates by (position = row % rope_T).
+struct InferAttention {
+    obte_bf16* kv_cache; int64_t T_max;   // prefill and decode: the layer's cache (null: obte_block_fwd_infer)
+    int64_t pos;                          // decode: the position of the new row (< 0: the attention of the call's own T positions)
+    void* dec_ws; int64_t dec_ws_bytes;   // decode: obte_attn_decode's workspace
+};
+int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const InferLayout& w, int64_t M, const float* rope_cos,
+                   const float* rope_sin, int64_t rope_T, const InferAttention& at, obte_stream s) {
     const int C = d->n_embd, H = d->n_head, hs = C / H;
-    const int64_t M = d->B * d->T;
-    const InferLayout w(d->B, d->T, C, H, ws);
-    OBTE_REQUIRE(ws_bytes >= w.total, "obte_block_fwd_infer: workspace of %lld bytes, obte_block_infer_ws_bytes() asks for %lld", (long long)ws_bytes, (long long)w.total);
     TRY(obte_layernorm_fwd(x, d->ln1_w, w.h1, w.mean, w.rstd, M, C, 1e-5f, s));
     obte_gemm_args qkv = xWt(w.h1, d->attn_w, w.qkv, M, 3 * C, C);
-    qkv.epilogue = OBTE_EPI_ROPE_QK; qkv.rope_cos = d->rope_cos; qkv.rope_sin = d->rope_sin; qkv.rope_T = d->T; qkv.rope_head_dim = hs;
+    qkv.epilogue = OBTE_EPI_ROPE_QK; qkv.rope_cos = rope_cos; qkv.rope_sin = rope_sin; qkv.rope_T = rope_T; qkv.rope_head_dim = hs;
     TRY(run(qkv, s));
-    obte_attn_fwd_args af = {};
-    af.qkv = w.qkv; af.o = w.att; af.lse = w.lse; af.key_ranges = d->key_ranges; af.mask = d->mask;
-    af.mask_sb = d->mask_sb; af.mask_sh = d->mask_sh; af.mask_sq = d->mask_sq; af.ranges_exact = d->ranges_exact;
-    af.B = d->B; af.T = d->T; af.n_head = H; af.head_dim = hs; af.scale = 8.0f / (float)C;  // model.py:119
-    af.dropout_p = d->dropout_p; af.dropout_seed = d->dropout_seed;
-    TRY(obte_attn_fwd(&af, s));
+    const float scale = 8.0f / (float)C;  // model.py:119
+    if (at.pos >= 0) {   // the new position of every row joins the cache, then attends over positions 0 .. pos
+        TRY(obte_kv_cache_store(w.qkv, d->B, 1, H, hs, at.kv_cache, at.T_max, at.pos, s));
+        TRY(obte_attn_decode(w.qkv, 3 * (int64_t)C, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos + 1, H, hs, scale, 0, at.dec_ws, at.dec_ws_bytes, s));
+    } else {
+        obte_attn_fwd_args af = {};
+        af.qkv = w.qkv; af.o = w.att; af.lse = w.lse; af.key_ranges = d->key_ranges; af.mask = d->mask;
+        af.mask_sb = d->mask_sb; af.mask_sh = d->mask_sh; af.mask_sq = d->mask_sq; af.ranges_exact = d->ranges_exact;
+        af.B = d->B; af.T = d->T; af.n_head = H; af.head_dim = hs; af.scale = scale;
+        af.dropout_p = d->dropout_p; af.dropout_seed = d->dropout_seed;
+        TRY(obte_attn_fwd(&af, s));
+        if (at.kv_cache) TRY(obte_kv_cache_store(w.qkv, d->B, d->T, H, hs, at.kv_cache, at.T_max, 0, s));   // (c_fc's activation overwrites qkv below)
+    }
     TRY(run(plus_residual(xWt(w.att, d->proj_w, w.x1, M, C, C), x, d->dropout_p, d->dropout_seed, SITE_RESID), s));
     TRY(obte_layernorm_fwd(w.x1, d->ln2_w, w.h2, w.mean, w.rstd, M, C, 1e-5f, s));
     obte_gemm_args fc = xWt(w.h2, d->fc_w, w.hact, M, 4 * C, C);
     fc.epilogue = OBTE_EPI_GELU_ACT;
     TRY(run(fc, s));
     return run(plus_residual(xWt(w.hact, d->mlp_w, y_out, M, C, 4 * C), w.x1, d->dropout_p, d->dropout_seed, SITE_MLP), s);
+}
+
+// obte_block_fwd_infer and obte_block_fwd_prefill: the same checks, the same workspace
+int infer_or_prefill(const char* who, const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* ws, int64_t ws_bytes, obte_bf16* kv_cache,
+                     int64_t T_max, bool prefill, obte_stream s) {
+    TRY(check_desc(who, d));
+    if (d->out_rows) {
+        obte_set_error("%s: the rows form (out_rows) stays with obte_block_fwd", who);
+        return OBTE_EUNSUPPORTED;
+    }
+    OBTE_REQUIRE(x && y_out && ws && (!prefill || kv_cache), "%s: null pointer", who);
+    OBTE_REQUIRE(!prefill || d->T <= T_max, "%s: %lld positions do not fit T_max = %lld", who, (long long)d->T, (long long)T_max);
+    const InferLayout w(d->B, d->T, d->n_embd, d->n_head, ws);
+    OBTE_REQUIRE(ws_bytes >= w.total, "%s: workspace of %lld bytes, obte_block_infer_ws_bytes() asks for %lld", who, (long long)ws_bytes, (long long)w.total);
+    const InferAttention at = {prefill ? kv_cache : nullptr, T_max, -1, nullptr, 0};
+    return infer_sequence(d, x, y_out, w, d->B * d->T, d->rope_cos, d->rope_sin, d->T, at, s);
+}
+
+}  // namespace
+
+extern "C" int obte_block_fwd_infer(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* ws, int64_t ws_bytes, obte_stream s) {
+    return infer_or_prefill("obte_block_fwd_infer", d, x, y_out, ws, ws_bytes, nullptr, 0, false, s);
+}
+
+extern "C" int obte_block_fwd_prefill(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* ws, int64_t ws_bytes, obte_bf16* kv_cache,
+                                      int64_t T_max, obte_stream s) {
+    return infer_or_prefill("obte_block_fwd_prefill", d, x, y_out, ws, ws_bytes, kv_cache, T_max, true, s);
+}
+
+// ---- one new position per row against the cache ---------------------------------------------------------------------------------------------
+// InferLayout at T = 1 (M = B rows) with obte_attn_decode's partials behind it
+extern "C" int64_t obte_block_decode_ws_bytes(int64_t B, int32_t n_embd, int32_t n_head) {
+    const int64_t base = obte_block_infer_ws_bytes(B, 1, n_embd, n_head);
+    return base > 0 ? base + align256(obte_attn_decode_ws_bytes(B, n_head, n_embd / n_head)) : 0;
+}
+
+extern "C" int obte_block_decode(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, int64_t pos, void* ws,
+                                 int64_t ws_bytes, obte_stream s) {
+    TRY(check_desc("obte_block_decode", d));
+    OBTE_REQUIRE(d->T == 1, "obte_block_decode: one new position per row (T = 1), got T = %lld", (long long)d->T);
+    if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
+        obte_set_error("obte_block_decode: key_ranges, mask, query_bounds, out_rows and dropout_p must be NULL / 0 (the new position sees every cached one)");
+        return OBTE_EUNSUPPORTED;
+    }
+    OBTE_REQUIRE(x && y_out && kv_cache && ws, "obte_block_decode: null pointer");
+    OBTE_REQUIRE(pos >= 0 && pos < T_max, "obte_block_decode: position %lld outside the cache's [0, %lld)", (long long)pos, (long long)T_max);
+    const int C = d->n_embd, H = d->n_head, hs = C / H;
+    const InferLayout w(d->B, 1, C, H, ws);
+    const int64_t dec_bytes = obte_attn_decode_ws_bytes(d->B, H, hs), need = w.total + align256(dec_bytes);
+    OBTE_REQUIRE(ws_bytes >= need, "obte_block_decode: workspace of %lld bytes, obte_block_decode_ws_bytes() asks for %lld", (long long)ws_bytes, (long long)need);
+    const InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, dec_bytes};
+    const int64_t row = pos * (hs / 2);   // the tables' row `pos`: with rope_T = 1 every row of the product is rotated by it
+    return infer_sequence(d, x, y_out, w, d->B, d->rope_cos + row, d->rope_sin + row, 1, at, s);
 }
 
 extern "C" int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,

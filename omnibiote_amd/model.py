@@ -778,6 +778,49 @@ class MuReadout(_MuReadoutBase):
         return _LinearFn.apply(x, self.weight, float(self.output_mult) / float(wm))
 
 
+def sample_next(logits, temperature=1.0, top_k=None, generator=None):
+    """The next token of every row from its (B, vocab) logits: nanoGPT's sampling step.  ``top_k == 1`` or ``temperature == 0`` is the
+    argmax; otherwise the logits are divided by the temperature, everything below the row's k-th largest is excluded, and the token
+    is drawn from the softmax with ``torch.multinomial`` under ``generator``.  Ordinary torch on any device; returns (B,) int64."""
+    if logits.dim() != 2:
+        raise ValueError(f"sample_next: logits must be (B, vocab), got {tuple(logits.shape)}")
+    if top_k is not None and top_k < 1:
+        raise ValueError(f"sample_next: top_k must be at least 1, got {top_k}")
+    if temperature < 0:
+        raise ValueError(f"sample_next: temperature must not be negative, got {temperature}")
+    if top_k == 1 or temperature == 0:
+        return torch.argmax(logits, dim=-1)
+    logits = logits.float() / temperature
+    if top_k is not None:
+        v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
+        logits = logits.masked_fill(logits < v[:, [-1]], float("-inf"))
+    probs = torch.softmax(logits, dim=-1)
+    return torch.multinomial(probs, num_samples=1, generator=generator).squeeze(1)
+
+
+class KVCache:
+    """The rotated keys and the values of every layer of ``model`` for ``batch`` sequences of up to ``max_len`` positions
+    (default and at most ``config.block_size``): one buffer per layer (include/omnibiote_hip.h, obte_kv_cache_bytes), the workspace of
+    a decode step, and ``pos``, the number of positions filled — a host integer, the same for every row.  ``OmniBioTA.prefill``
+    starts it over (nothing is cleared: positions beyond ``pos`` are never read), ``decode_step`` advances it."""
+
+    def __init__(self, model, batch, max_len=None):
+        cfg = model.config
+        if not cfg.autoregressive:
+            raise ValueError("KVCache: the model is not autoregressive (config.autoregressive): an encoder has no next token")
+        max_len = cfg.block_size if max_len is None else int(max_len)
+        if not 1 <= max_len <= cfg.block_size:
+            raise ValueError(f"KVCache: max_len {max_len} outside [1, block_size = {cfg.block_size}]")
+        if batch < 1:
+            raise ValueError(f"KVCache: batch must be at least 1, got {batch}")
+        wte = model.transformer.wte.weight
+        _require_hip(wte, "KVCache")
+        self.batch, self.max_len, self.pos = int(batch), max_len, 0
+        hs = cfg.n_embd // cfg.n_head
+        self.layers = [ops.kv_cache_buffer(self.batch, max_len, cfg.n_head, hs, wte.device) for _ in model.transformer.h]
+        self.decode_ws = ops.block_decode_workspace(self.batch, cfg.n_embd, cfg.n_head, wte.device)
+
+
 class OmniBioTA(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -866,6 +909,97 @@ class OmniBioTA(nn.Module):
         elif method == "max":
             return emb.max(dim=1)[0]
         return emb
+
+    # ---- generation (beyond the reference, whose model.py strikes nanoGPT's generate() out) -----------------------------------------
+    # Dropout is never applied on these paths, whatever ``training`` says: a sample is drawn from the model, not from a thinned one.
+    def _block_params(self, block):
+        return (block.ln_1.weight, block.attn.c_attn.weight, block.attn.c_proj.weight, block.ln_2.weight, block.mlp.c_fc.weight,
+                block.mlp.c_proj.weight)
+
+    def _check_generation(self, what, batch, cache=None):
+        if not self.config.autoregressive:
+            raise ValueError(f"OmniBioTA.{what}: the model is not autoregressive (config.autoregressive): an encoder has no next token")
+        if cache is not None and cache.batch != batch:
+            raise ValueError(f"OmniBioTA.{what}: the cache was built for batch size {cache.batch}, got {batch}")
+
+    @torch.no_grad()
+    def prefill(self, idx, cache):
+        """The prompt ``idx`` (B, T0) through every block under the causal mask, its keys and values left in ``cache`` (started
+        over: ``cache.pos = T0``); returns the logits of the last position, (B, vocab).  ln_f and the readout run on that row alone."""
+        if idx.dim() != 2:
+            raise ValueError(f"OmniBioTA.prefill: idx must be (B, T0), got {tuple(idx.shape)}")
+        b, t = idx.shape
+        self._check_generation("prefill", b, cache)
+        if t == 0:
+            raise ValueError("OmniBioTA.prefill: the prompt is empty")
+        if t > cache.max_len:
+            raise ValueError(f"OmniBioTA.prefill: a prompt of {t} tokens does not fit the cache's {cache.max_len} positions")
+        wte = self.transformer.wte.weight
+        _require_hip(wte, "OmniBioTA")
+        if not idx.is_cuda:
+            raise RuntimeError("OmniBioTA.prefill: idx must be on the GPU")
+        mask = ops.MaskSpec.from_user(_autoregressive_mask(True, None, b, t, idx.device), b, t, self.config.n_head, idx.device)
+        x = ops.embedding_fwd(idx.contiguous(), wte)
+        ws = ops.block_infer_workspace(b, t, self.config.n_embd, self.config.n_head, idx.device)
+        for block, kv in zip(self.transformer.h, cache.layers):
+            ops.block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, kv, cache.max_len, ws=ws, out=x)
+        cache.pos = t
+        return self.lm_head(self.transformer.ln_f(x[:, -1].contiguous()))
+
+    @torch.no_grad()
+    def decode_step(self, tokens, cache):
+        """One new token per row, ``tokens`` (B,) int64, at position ``cache.pos`` of every row: its keys and values join the cache
+        and the logits of the token after it come back, (B, vocab).  O(1) in projections, one read of the cache per layer."""
+        if tokens.dim() != 1:
+            raise ValueError(f"OmniBioTA.decode_step: tokens must be (B,), got {tuple(tokens.shape)}")
+        b = tokens.shape[0]
+        self._check_generation("decode_step", b, cache)
+        if cache.pos == 0:
+            raise ValueError("OmniBioTA.decode_step: the cache is empty: prefill a prompt first")
+        if cache.pos >= cache.max_len:
+            raise ValueError(f"OmniBioTA.decode_step: the cache's {cache.max_len} positions are full")
+        wte = self.transformer.wte.weight
+        if not tokens.is_cuda:
+            raise RuntimeError("OmniBioTA.decode_step: tokens must be on the GPU")
+        x = ops.embedding_fwd(tokens.contiguous(), wte)
+        for block, kv in zip(self.transformer.h, cache.layers):
+            ops.block_decode(x, self._block_params(block), block.attn.rope(), self.config.n_head, kv, cache.max_len, cache.pos,
+                             ws=cache.decode_ws, out=x)
+        cache.pos += 1
+        return self.lm_head(self.transformer.ln_f(x))
+
+    @torch.no_grad()
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None):
+        """nanoGPT's generate(): ``idx`` (B, T0) int64 continued by up to ``max_new_tokens`` sampled tokens (``sample_next``); returns
+        (B, T0 + n) int64.  The prompt runs once (``prefill``), every new token costs one ``decode_step``.  Where nanoGPT crops the
+        context to block_size, this raises: T0 + max_new_tokens must fit.  ``eos_token``: a row that has produced it keeps producing
+        it, and generation stops once every row has — the loop's only host synchronisation (none when ``eos_token is None``).
+        Dropout is not applied, whatever ``self.training`` says."""
+        self._check_generation("generate", idx.shape[0] if idx.dim() == 2 else 0)
+        if idx.dim() != 2:
+            raise ValueError(f"OmniBioTA.generate: idx must be (B, T0), got {tuple(idx.shape)}")
+        b, t0 = idx.shape
+        if t0 == 0:
+            raise ValueError("OmniBioTA.generate: the prompt is empty")
+        if max_new_tokens < 0 or t0 + max_new_tokens > self.config.block_size:
+            raise ValueError(f"OmniBioTA.generate: {t0} prompt tokens + {max_new_tokens} new ones exceed block_size = {self.config.block_size}")
+        if max_new_tokens == 0:
+            return idx.clone()
+        cache = KVCache(self, b, t0 + max_new_tokens)
+        out = [idx]
+        logits = self.prefill(idx, cache)
+        done = None
+        for i in range(max_new_tokens):
+            nxt = sample_next(logits, temperature, top_k, generator)
+            if eos_token is not None:
+                if done is not None:
+                    nxt = torch.where(done, torch.full_like(nxt, eos_token), nxt)
+                done = (nxt == eos_token) if done is None else (done | (nxt == eos_token))
+            out.append(nxt.unsqueeze(1))
+            if i + 1 == max_new_tokens or (eos_token is not None and bool(done.all())):
+                break
+            logits = self.decode_step(nxt, cache)
+        return torch.cat(out, dim=1)
 
 
 def next_token_loss(logits, idx):

@@ -698,6 +698,89 @@ def block_infer(x, params, rope, H, mask: MaskSpec, dropout_p=0.0, dropout_seed=
     return y
 
 
+# --------------------------------------------------------------------------------------------------- generation
+def kv_cache_buffer(B, T_max, H, hs, device) -> torch.Tensor:
+    """One layer's key/value cache (K [B, H, T_max, hs], then V, bf16) as the flat bf16 tensor the entry points take."""
+    nbytes = int(L.lib().obte_kv_cache_bytes(B, T_max, H, hs))
+    if nbytes <= 0:
+        raise RuntimeError(f"kv_cache_buffer: unsupported shape (B {B}, T_max {T_max}, n_head {H}, head size {hs}): head size 64 or 128")
+    return torch.empty(nbytes // 2, dtype=bf16, device=device)
+
+
+def kv_cache_store(qkv, B, t, H, hs, cache, T_max, pos0):
+    """Copy the k and v thirds of the packed, rotated qkv [B*t, 3C] into positions [pos0, pos0 + t) of the cache (obte_kv_cache_store)."""
+    _need(qkv, "qkv"); _need(cache, "cache")
+    assert qkv.numel() == B * t * 3 * H * hs and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, hs)
+    L.check(L.lib().obte_kv_cache_store(_ptr(qkv), B, t, H, hs, _ptr(cache), T_max, pos0, _stream()), "obte_kv_cache_store")
+    return cache
+
+
+def attn_decode(q, cache, B, T_max, n_keys, H, hs, scale, splits=0, q_ld=None, ws=None):
+    """One query per (b, h) over cache positions [0, n_keys) (obte_attn_decode): (o (B, C) bf16, lse (B, H) fp32).  q: any bf16 tensor
+    whose row b holds the query of head h at b * q_ld + h * hs (q_ld defaults to its last dimension: 3C reads a packed row in place).
+    splits: 0 = the library's choice, else a forced count."""
+    _need(q, "q"); _need(cache, "cache")
+    q_ld = q.shape[-1] if q_ld is None else q_ld
+    assert q.numel() >= (B - 1) * q_ld + H * hs and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, hs)
+    o = torch.empty((B, H * hs), dtype=bf16, device=q.device)
+    lse = torch.empty((B, H), dtype=torch.float32, device=q.device)
+    if ws is None:
+        ws = torch.empty(int(L.lib().obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=q.device)
+    L.check(L.lib().obte_attn_decode(_ptr(q), q_ld, _ptr(cache), _ptr(o), _ptr(lse), B, T_max, n_keys, H, hs, float(scale), int(splits),
+                                     _ptr(ws), ws.numel(), _stream()), "obte_attn_decode")
+    return o, lse
+
+
+def block_prefill(x, params, rope, H, mask: MaskSpec, cache, T_max, ws=None, out=None):
+    """block_infer (y bit for bit its y, the same workspace) that also leaves the block's rotated keys and its values in positions
+    [0, T) of `cache` (obte_block_fwd_prefill).  No dropout on a generation path."""
+    _need(x, "x"); _need(cache, "cache")
+    B, T, Cc = x.shape
+    for i, w in enumerate(params):
+        _need(w, f"param{i}")
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert rope[0].shape[0] >= T and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, Cc // H)
+    if ws is None:
+        ws = block_infer_workspace(B, T, Cc, H, x.device)
+    else:
+        _need(ws, "ws", torch.uint8)
+    y = torch.empty_like(x) if out is None else out
+    _need(y, "out"); assert y.shape == x.shape
+    d = _block_desc(B, T, Cc, H, params, rope, mask)
+    L.check(L.lib().obte_block_fwd_prefill(C.byref(d), _ptr(x), _ptr(y), _ptr(ws), ws.numel(), _ptr(cache), T_max, _stream()),
+            "obte_block_fwd_prefill")
+    return y
+
+
+def block_decode_workspace(B, Cc, H, device) -> torch.Tensor:
+    nbytes = int(L.lib().obte_block_decode_ws_bytes(B, Cc, H))
+    if nbytes <= 0:
+        raise RuntimeError(f"block_decode: unsupported shape (B {B}, n_embd {Cc}, n_head {H}): head size 64 or 128, "
+                           "n_embd a multiple of 64 and <= 4096")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def block_decode(x, params, rope, H, cache, T_max, pos, ws=None, out=None):
+    """One new position per batch row, every row at position `pos`, against the cache (obte_block_decode): x (B, C) -> y (B, C).
+    rope: the FULL tables (at least pos + 1 rows).  out may be x itself."""
+    _need(x, "x"); _need(cache, "cache")
+    B, Cc = x.shape
+    for i, w in enumerate(params):
+        _need(w, f"param{i}")
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert rope[0].shape[0] > pos and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, Cc // H)
+    if ws is None:
+        ws = block_decode_workspace(B, Cc, H, x.device)
+    else:
+        _need(ws, "ws", torch.uint8)
+    y = torch.empty_like(x) if out is None else out
+    _need(y, "out"); assert y.shape == x.shape
+    d = _block_desc(B, 1, Cc, H, params, rope, MaskSpec())
+    L.check(L.lib().obte_block_decode(C.byref(d), _ptr(x), _ptr(y), _ptr(cache), T_max, pos, _ptr(ws), ws.numel(), _stream()),
+            "obte_block_decode")
+    return y
+
+
 def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None, dropout_p=0.0, dropout_seed=0, ln_partials=None,
               ln_partial_mode=0, out_rows=None, dy_masked=None, dx_mask_seed=None, acc32=None, acc32_mode=0):
     """accumulate_into: optional list of 6 tensors-or-None (same order as params).  When the four matrix entries are all

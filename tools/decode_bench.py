@@ -1,0 +1,186 @@
+"""Autoregressive generation on the small config (8 layers, 1024 wide, 8 heads of 128; bf16): what a generated token costs.
+
+For every batch size B and context length ctx (the new token attends over ctx positions):
+  1. time per generated token: OmniBioTA.decode_step against a key/value cache that holds ctx - 1 positions, versus what the code
+     offered before the cache existed for the same token: model(idx)[:, -1] under no_grad over the whole ctx-token prefix.  Both
+     contenders alternate in one process over --rounds rounds after warm-up; device events around windows of --steps decode steps
+     (the full forward: as many calls as fit ~--baseline_ms, at least 3).  Median and [min - max] over the rounds.
+  2. obte_attn_decode alone over one cache per layer in turn (the set a real step walks through: n_layer caches), for the library's own
+     split count and for every forced count of --sweep: time, and the cache bytes one call must read (2 B H ctx hs 2) over that time as
+     a share of 6.3 TB/s.  A set of caches that fits the 256 MB Infinity Cache is not an HBM measurement: `served_from` says which.
+  3. the launch profiler's split of a decode step: attention (kind 102), the projections (the GEMM kinds), the rest (LayerNorm, the
+     cache store, the embedding, the readout's LayerNorm, and every gap between launches).
+One JSON line per (B, ctx).
+
+    python tools/decode_bench.py [--batches 1,8,64] [--contexts 128,1024,2048] [--rounds 5] [--steps 300]
+"""
+import argparse
+import contextlib
+import io
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_RATE = 6.3e12           # achievable HBM bytes/s of an MI355X
+INFINITY_CACHE = 256 << 20
+
+
+def summary(v, nd=2):
+    return {"median": round(statistics.median(v), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
+
+
+def timed(fn, n):
+    """microseconds per call of fn over a window of n calls between two device events"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / n * 1e3
+
+
+def build(block_size, dev):
+    """the small config as an autoregressive model, muP base shapes set as the trainer sets them (train_encoder.build_model)"""
+    import warnings
+    from omnibiote_amd.model import OmniBioTA, OmniBioTAConfig
+    from omnibiote_amd.mup_compat import set_base_shapes
+
+    def make(n_embd, n_head):
+        c = OmniBioTAConfig()
+        c.block_size, c.vocab_size, c.n_layer, c.n_head, c.n_embd, c.dropout, c.flash = block_size, 2 ** 16, 8, n_head, n_embd, 0.0, True
+        c.autoregressive = True
+        return OmniBioTA(c)
+    torch.manual_seed(0)
+    with contextlib.redirect_stdout(io.StringIO()), warnings.catch_warnings():
+        warnings.simplefilter("ignore")          # "Casting complex values to real": the reference's cos-only RoPE regime
+        m = make(1024, 8)
+        set_base_shapes(m, make(24, 3), delta=make(48, 12))
+        m.to(torch.bfloat16)
+    return m.to(dev).eval()
+
+
+def token_time(m, B, ctx, rounds, steps, baseline_ms, dev):
+    from omnibiote_amd.model import KVCache
+    g = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    idx = torch.randint(4, m.config.vocab_size, (B, ctx), device=dev, generator=g)
+    cache = KVCache(m, B, ctx)
+    if ctx > 1:
+        m.prefill(idx[:, :ctx - 1], cache)
+    last = idx[:, -1].contiguous()
+
+    def step():                      # the same position every time: the context stays ctx long
+        cache.pos = ctx - 1
+        m.decode_step(last, cache)
+
+    def full():
+        with torch.no_grad():
+            m(idx)[:, -1]
+    for _ in range(3):
+        step()
+    full()
+    n_full = max(3, min(steps, int(baseline_ms * 1e3 / max(timed(full, 1), 1.0))))
+    us = {"decode_step": [], "full_forward": []}
+    for r in range(rounds):
+        for leg in (("decode_step", "full_forward") if r % 2 == 0 else ("full_forward", "decode_step")):
+            us[leg].append(timed(step, steps) if leg == "decode_step" else timed(full, n_full))
+    return us, cache, last, n_full
+
+
+def attention_alone(m, cache, B, ctx, rounds, steps, sweep, dev):
+    from omnibiote_amd import _lib
+    H, C = m.config.n_head, m.config.n_embd
+    hs = C // H
+    q = torch.randn(B, 3 * C, device=dev, generator=torch.Generator(device=dev).manual_seed(1)).to(torch.bfloat16)
+    ws = torch.empty(int(_lib.lib().obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=dev)
+    default = int(_lib.lib().obte_attn_decode_splits(B, H, hs, ctx))
+    counts = [0] + [s for s in sweep if s == 1 or s * 64 <= max(ctx, 64)]
+    o = torch.empty(B, C, device=dev, dtype=torch.bfloat16)
+    lse = torch.empty(B, H, device=dev, dtype=torch.float32)
+    state = {"i": 0}
+    fn, stream = _lib.lib().obte_attn_decode, torch.cuda.current_stream().cuda_stream
+    ptrs = [kv.data_ptr() for kv in cache.layers]
+
+    def call(splits):          # the C entry point itself on preallocated outputs: the host side of a call is a few microseconds
+        state["i"] += 1
+        rc = fn(q.data_ptr(), 3 * C, ptrs[state["i"] % len(ptrs)], o.data_ptr(), lse.data_ptr(), B, cache.max_len, ctx, H, hs, 8.0 / C, splits,
+                ws.data_ptr(), ws.numel(), stream)
+        if rc != 0:
+            _lib.check(rc, "obte_attn_decode")
+    us = {s: [] for s in counts}
+    for s in counts:
+        for _ in range(8):
+            call(s)
+    for r in range(rounds):
+        for s in (counts if r % 2 == 0 else counts[::-1]):
+            us[s].append(timed(lambda: call(s), steps))
+    nbytes = 2 * B * H * ctx * hs * 2
+    set_bytes = nbytes * len(cache.layers)
+    med = {s: statistics.median(v) for s, v in us.items()}
+    return {"default_splits": default, "cache_bytes_per_call": nbytes, "set_bytes": set_bytes,
+            "served_from": "HBM" if set_bytes > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)",
+            "us": {("default" if s == 0 else str(s)): summary(v) for s, v in us.items()},
+            "share_of_6.3TBps": {("default" if s == 0 else str(s)): round(nbytes / (med[s] * 1e-6) / HBM_RATE, 3) for s in counts},
+            "default_over_one_split": round(med[0] / med[1], 3)}
+
+
+def step_split(m, cache, last, ctx, n_steps):
+    """the launch profiler over n_steps decode steps: per-step microseconds in attention, in the projections, and the rest"""
+    import ctypes as C
+    from omnibiote_amd import _lib
+    lib = _lib.lib()
+
+    def step():
+        cache.pos = ctx - 1
+        m.decode_step(last, cache)
+    lib.obte_profile_enable(1)
+    total = timed(step, n_steps)
+    cap = 16384
+    ms, dims, kind = (C.c_double * cap)(), (C.c_int64 * (3 * cap))(), (C.c_int32 * cap)()
+    n = lib.obte_profile_collect(ms, dims, kind, cap)
+    lib.obte_profile_enable(0)
+    attn = sum(ms[i] for i in range(n) if kind[i] == 102) * 1e3 / n_steps
+    proj = sum(ms[i] for i in range(n) if kind[i] % 1000 < 100) * 1e3 / n_steps
+    rest = max(total - attn - proj, 0.0)
+    return {"us_per_step_under_the_profiler": round(total, 1), "attention_us": round(attn, 1), "projections_us": round(proj, 1),
+            "rest_us": round(rest, 1), "share": {"attention": round(attn / total, 3), "projections": round(proj / total, 3),
+                                                  "rest": round(rest / total, 3)}}
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--batches", default="1,8,64")
+    p.add_argument("--contexts", default="128,1024,2048")
+    p.add_argument("--rounds", type=int, default=5)
+    p.add_argument("--steps", type=int, default=300, help="decode steps (and attention calls) per timed window")
+    p.add_argument("--baseline_ms", type=float, default=400.0, help="the full forward's window: as many calls as fit, at least 3")
+    p.add_argument("--sweep", default="1,2,4,8,16,32,64", help="forced split counts for obte_attn_decode alone")
+    a = p.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    contexts = [int(c) for c in a.contexts.split(",")]
+    m = build(max(contexts), dev)
+    sweep = [int(s) for s in a.sweep.split(",")]
+    for B in [int(b) for b in a.batches.split(",")]:
+        for ctx in contexts:
+            us, cache, last, n_full = token_time(m, B, ctx, a.rounds, a.steps, a.baseline_ms, dev)
+            d, f = statistics.median(us["decode_step"]), statistics.median(us["full_forward"])
+            out = {"B": B, "context": ctx, "windows": {"decode_steps": a.steps, "full_forwards": n_full, "rounds": a.rounds},
+                   "us_per_token": {k: summary(v, 1) for k, v in us.items()}, "full_forward_over_decode_step": round(f / d, 1),
+                   "tokens_per_s_decode": round(B / d * 1e6),
+                   "attn_decode": attention_alone(m, cache, B, ctx, a.rounds, a.steps, sweep, dev),
+                   "step_split": step_split(m, cache, last, ctx, 20)}
+            print(json.dumps(out), flush=True)
+            del cache
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
