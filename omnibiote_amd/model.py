@@ -145,9 +145,10 @@ import contextvars
 import os
 
 
-class LnPartialStore:
-    """fp32 partial-sum buffers of LayerNorm weights, keyed by the parameter's identity (not an attribute of the parameter:
-    whole-object pickles of the model — the reference's checkpoint format — must not carry 2 MB of scratch per weight)."""
+class _ParamKeyedStore:
+    """fp32 scratch buffers keyed by a parameter's identity (not an attribute of the parameter or the module: whole-object pickles
+    of the model — the reference's checkpoint format — must not carry them), one weak reference per entry, released when the
+    parameter dies.  A subclass supplies the buffer (``_new``) and whether an existing one still serves (``_fits``)."""
 
     def __init__(self):
         self._bufs = {}   # id(weight) -> (weak reference to it, buffer)
@@ -155,36 +156,37 @@ class LnPartialStore:
     def get(self, param):
         key = id(param)
         ent = self._bufs.get(key)
-        if ent is not None and ent[0]() is param and ent[1].device == param.device and \
-                ent[1].numel() == L.lib().obte_layernorm_bwd_ws_rows() * param.numel():
+        if ent is not None and ent[0]() is param and ent[1].device == param.device and self._fits(ent[1], param):
             return ent[1]
-        buf = ops.ln_partials_buffer(param.numel(), param.device)
-        bufs = self._bufs
-        self._bufs[key] = (weakref.ref(param, lambda _r, k=key: bufs.pop(k, None)), buf)
-        return buf
-
-
-class Fp32GradStore:
-    """fp32 buffers of the weights whose gradients are summed in fp32 over the passes of a step (GradPolicy.acc32_mode), one of
-    the parameter's shape each, keyed by the parameter's identity with a weak reference like LnPartialStore: never an attribute
-    of the parameter or the module (4 bytes per parameter of scratch that no checkpoint or pickle of the model may carry), and
-    released when the parameter dies.  Scratch within one optimizer step: the first pass overwrites, nothing reads it later."""
-
-    def __init__(self):
-        self._bufs = {}   # id(weight) -> (weak reference to it, buffer)
-
-    def get(self, param):
-        key = id(param)
-        ent = self._bufs.get(key)
-        if ent is not None and ent[0]() is param and ent[1].device == param.device and ent[1].shape == param.shape:
-            return ent[1]
-        buf = torch.empty(param.shape, dtype=torch.float32, device=param.device)
+        buf = self._new(param)
         bufs = self._bufs
         self._bufs[key] = (weakref.ref(param, lambda _r, k=key: bufs.pop(k, None)), buf)
         return buf
 
     def __len__(self):
         return len(self._bufs)
+
+
+class LnPartialStore(_ParamKeyedStore):
+    """fp32 partial-sum buffers of LayerNorm weights (2 MB of scratch per weight)."""
+
+    def _new(self, param):
+        return ops.ln_partials_buffer(param.numel(), param.device)
+
+    def _fits(self, buf, param):
+        return buf.numel() == L.lib().obte_layernorm_bwd_ws_rows() * param.numel()
+
+
+class Fp32GradStore(_ParamKeyedStore):
+    """fp32 buffers of the weights whose gradients are summed in fp32 over the passes of a step (GradPolicy.acc32_mode), one of
+    the parameter's shape each (4 bytes per parameter).  Scratch within one optimizer step: the first pass overwrites, nothing
+    reads it later."""
+
+    def _new(self, param):
+        return torch.empty(param.shape, dtype=torch.float32, device=param.device)
+
+    def _fits(self, buf, param):
+        return buf.shape == param.shape
 
 
 class BackwardOrder:
@@ -306,14 +308,21 @@ def _acc32(param, pol: Optional[GradPolicy]):
     return (pol.acc32_store if pol.acc32_store is not None else _default_acc32_store).get(param), pol.acc32_mode
 
 
-def _ord_wait(pol: Optional[GradPolicy], key) -> None:
-    if pol is not None and pol.order is not None:
-        pol.order.wait(key)
+class _ordered:
+    """``with _ordered(pol, key)``: a node's update of the parameter group ``key`` under the policy's BackwardOrder, if it has one —
+    wait for the previous pass's update of the group on entry, record this one's event on leaving (not when the body raised)."""
+    __slots__ = ("order", "key")
 
+    def __init__(self, pol: Optional[GradPolicy], key):
+        self.order, self.key = (pol.order if pol is not None else None), key
 
-def _ord_done(pol: Optional[GradPolicy], key) -> None:
-    if pol is not None and pol.order is not None:
-        pol.order.done(key)
+    def __enter__(self):
+        if self.order is not None:
+            self.order.wait(self.key)
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.order is not None and exc_type is None:
+            self.order.done(self.key)
 
 
 # ------------------------------------------------------------------------------------------------- autograd glue
@@ -330,14 +339,11 @@ class _LayerNormFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w, mean, rstd = ctx.saved_tensors
         pol = ctx.pol
-        _ord_wait(pol, id(ctx.w_param))
-        if pol.ln_mode:
-            dx, dw = ops.layernorm_bwd(dy.contiguous(), x.contiguous(), w, mean, rstd, partials=_ln_partials(ctx.w_param, pol),
-                                       partial_mode=pol.ln_mode)
-        else:
-            dx, dw = ops.layernorm_bwd(dy.contiguous(), x.contiguous(), w, mean, rstd, accumulate_into=_grad_slot(ctx.w_param, pol))
-        _ord_done(pol, id(ctx.w_param))
-        return dx, dw
+        with _ordered(pol, id(ctx.w_param)):
+            if pol.ln_mode:
+                return ops.layernorm_bwd(dy.contiguous(), x.contiguous(), w, mean, rstd, partials=_ln_partials(ctx.w_param, pol),
+                                         partial_mode=pol.ln_mode)
+            return ops.layernorm_bwd(dy.contiguous(), x.contiguous(), w, mean, rstd, accumulate_into=_grad_slot(ctx.w_param, pol))
 
 
 class _LinearFn(torch.autograd.Function):
@@ -359,20 +365,18 @@ class _LinearFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         dx = dw = None
-        _ord_wait(ctx.pol, id(ctx.w_param))
-        a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
-            dx, dw = ops.linear_bwd(dy2, x2, w, alpha=ctx.alpha, accumulate_into=_grad_slot(ctx.w_param, ctx.pol), acc32=a32, acc32_mode=a32_mode)
-            _ord_done(ctx.pol, id(ctx.w_param))
-            return dx.view_as(x), dw, None
-        if ctx.needs_input_grad[0]:
-            dx = ops.linear_dgrad(dy2, w, alpha=ctx.alpha).view_as(x)
-        if ctx.needs_input_grad[1]:
-            slot = _grad_slot(ctx.w_param, ctx.pol)
-            dw = ops.linear_wgrad(dy2, x2, alpha=ctx.alpha, accumulate_into=slot, acc32=a32, acc32_mode=a32_mode)
-            if slot is not None:
-                dw = None
-        _ord_done(ctx.pol, id(ctx.w_param))
+        with _ordered(ctx.pol, id(ctx.w_param)):
+            a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
+            if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
+                dx, dw = ops.linear_bwd(dy2, x2, w, alpha=ctx.alpha, accumulate_into=_grad_slot(ctx.w_param, ctx.pol), acc32=a32, acc32_mode=a32_mode)
+                return dx.view_as(x), dw, None
+            if ctx.needs_input_grad[0]:
+                dx = ops.linear_dgrad(dy2, w, alpha=ctx.alpha).view_as(x)
+            if ctx.needs_input_grad[1]:
+                slot = _grad_slot(ctx.w_param, ctx.pol)
+                dw = ops.linear_wgrad(dy2, x2, alpha=ctx.alpha, accumulate_into=slot, acc32=a32, acc32_mode=a32_mode)
+                if slot is not None:
+                    dw = None
         return dx, dw, None
 
 
@@ -394,10 +398,9 @@ class _LinearGeluFn(torch.autograd.Function):
         x, w, der = ctx.saved_tensors
         dh = dact.reshape(-1, dact.shape[-1]) * der            # bf16(dact * gelu'(h)), as OBTE_EPI_GELU_BWD forms it
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        _ord_wait(ctx.pol, id(ctx.w_param))
-        a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
-        dx, dw = ops.linear_bwd(dh.contiguous(), x2, w, accumulate_into=_grad_slot(ctx.w_param, ctx.pol), acc32=a32, acc32_mode=a32_mode)
-        _ord_done(ctx.pol, id(ctx.w_param))
+        with _ordered(ctx.pol, id(ctx.w_param)):
+            a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
+            dx, dw = ops.linear_bwd(dh.contiguous(), x2, w, accumulate_into=_grad_slot(ctx.w_param, ctx.pol), acc32=a32, acc32_mode=a32_mode)
         return dx.view_as(x), dw
 
 
@@ -420,11 +423,10 @@ class _ReadoutRowsGradFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss):
         emb_rows, w, dl = ctx.saved_tensors
-        _ord_wait(ctx.pol, id(ctx.w_param))
-        slot = _grad_slot(ctx.w_param, ctx.pol)
-        a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
-        dx, dw = ops.linear_bwd(dl, emb_rows.contiguous(), w, alpha=ctx.alpha, accumulate_into=slot, acc32=a32, acc32_mode=a32_mode)
-        _ord_done(ctx.pol, id(ctx.w_param))
+        with _ordered(ctx.pol, id(ctx.w_param)):
+            slot = _grad_slot(ctx.w_param, ctx.pol)
+            a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
+            dx, dw = ops.linear_bwd(dl, emb_rows.contiguous(), w, alpha=ctx.alpha, accumulate_into=slot, acc32=a32, acc32_mode=a32_mode)
         return dx, dw, None, None
 
 
@@ -442,11 +444,9 @@ class _Acc32FlushFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss):
-        _ord_wait(ctx.pol, id(ctx.w_param))
-        a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
-        dw = ops.acc32_add_(a32, None, a32_mode)
-        _ord_done(ctx.pol, id(ctx.w_param))
-        return dw
+        with _ordered(ctx.pol, id(ctx.w_param)):
+            a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
+            return ops.acc32_add_(a32, None, a32_mode)
 
 
 class _EmbeddingFn(torch.autograd.Function):
@@ -463,11 +463,10 @@ class _EmbeddingFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         (idx,) = ctx.saved_tensors
-        _ord_wait(ctx.pol, id(ctx.w_param))
-        a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
-        dw = ops.embedding_bwd(idx.contiguous(), dout.contiguous(), ctx.vocab, accumulate_into=_grad_slot(ctx.w_param, ctx.pol),
-                               dropout_p=ctx.drop[0], dropout_seed=ctx.drop[1], order=ctx.order, acc32=a32, acc32_mode=a32_mode)
-        _ord_done(ctx.pol, id(ctx.w_param))
+        with _ordered(ctx.pol, id(ctx.w_param)):
+            a32, a32_mode = _acc32(ctx.w_param, ctx.pol)
+            dw = ops.embedding_bwd(idx.contiguous(), dout.contiguous(), ctx.vocab, accumulate_into=_grad_slot(ctx.w_param, ctx.pol),
+                                   dropout_p=ctx.drop[0], dropout_seed=ctx.drop[1], order=ctx.order, acc32=a32, acc32_mode=a32_mode)
         return None, dw, None, None, None
 
 
@@ -523,21 +522,20 @@ class _BlockFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, act, rope_cos, rope_sin, *params = ctx.saved_tensors
         pol = ctx.pol
-        _ord_wait(pol, id(ctx.w_params[0]))   # one group per block: its six weights are updated by this one call
-        slots = [_grad_slot(w, pol) for w in ctx.w_params]
-        lnp = (_ln_partials(ctx.w_params[0], pol), _ln_partials(ctx.w_params[3], pol)) if pol.ln_mode else None
-        dy = dy.contiguous()
-        # dropout: the block above may have left dropout(dy) under this block's MLP-projection mask (one pass less per block)
-        dy_masked = ctx.handoff.take(ctx.index, dy, ctx.drop) if (ctx.drop[0] > 0 and ctx.handoff is not None) else None
-        res = ops.block_bwd(x, dy, act, tuple(params), (rope_cos, rope_sin), ctx.n_head, ctx.mask,
-                            accumulate_into=slots, dropout_p=ctx.drop[0], dropout_seed=ctx.drop[1], ln_partials=lnp,
-                            ln_partial_mode=pol.ln_mode, out_rows=ctx.out_rows, dy_masked=dy_masked, dx_mask_seed=ctx.below_seed,
-                            acc32=tuple(_acc32(ctx.w_params[i], pol)[0] for i in (1, 2, 4, 5)) if pol.acc32_mode else None,
-                            acc32_mode=pol.acc32_mode)
-        dx, grads = res[0], res[1]
-        if ctx.below_seed is not None:
-            ctx.handoff.put(ctx.index - 1, dx, res[2], ctx.drop[0], ctx.below_seed)
-        _ord_done(pol, id(ctx.w_params[0]))
+        with _ordered(pol, id(ctx.w_params[0])):   # one group per block: its six weights are updated by this one call
+            slots = [_grad_slot(w, pol) for w in ctx.w_params]
+            lnp = (_ln_partials(ctx.w_params[0], pol), _ln_partials(ctx.w_params[3], pol)) if pol.ln_mode else None
+            dy = dy.contiguous()
+            # dropout: the block above may have left dropout(dy) under this block's MLP-projection mask (one pass less per block)
+            dy_masked = ctx.handoff.take(ctx.index, dy, ctx.drop) if (ctx.drop[0] > 0 and ctx.handoff is not None) else None
+            res = ops.block_bwd(x, dy, act, tuple(params), (rope_cos, rope_sin), ctx.n_head, ctx.mask,
+                                accumulate_into=slots, dropout_p=ctx.drop[0], dropout_seed=ctx.drop[1], ln_partials=lnp,
+                                ln_partial_mode=pol.ln_mode, out_rows=ctx.out_rows, dy_masked=dy_masked, dx_mask_seed=ctx.below_seed,
+                                acc32=tuple(_acc32(ctx.w_params[i], pol)[0] for i in (1, 2, 4, 5)) if pol.acc32_mode else None,
+                                acc32_mode=pol.acc32_mode)
+            dx, grads = res[0], res[1]
+            if ctx.below_seed is not None:
+                ctx.handoff.put(ctx.index - 1, dx, res[2], ctx.drop[0], ctx.below_seed)
         return (dx, *grads, None, None, None, None, None, None, None, None, None, None)
 
 

@@ -39,6 +39,8 @@ import contextlib
 import math
 import os
 import time
+from collections import namedtuple
+from types import SimpleNamespace
 from typing import Callable, Dict, Iterable, List, Optional
 
 import numpy as np
@@ -309,8 +311,91 @@ class FusedAdamW(torch.optim.Optimizer):
 
 
 # --------------------------------------------------------------------------------------------------- train step
+# What one TrainStep call does, resolved once at its top (resolve_step_plan) from the object's public attributes AS THEY ARE AT THAT
+# CALL — callers reassign them on a live object between steps — and the call's own facts; plain Python values only.  rows: of the
+# batch, a multiple of the micro-batch; n_accum micro-batches in n_pass passes of k micro-batches (span rows) each; sparse_rows: one
+# of the two row-compact readouts (`readout`; they need the HIP kernels); fp32_sum: every weight gradient summed in fp32 over the
+# passes; ns: streams in flight; has_reducer: the model is DDP-wrapped (no_sync); layer_order: side passes order their backward per
+# parameter group (model.BackwardOrder); bf16 path: inplace — a gradient policy is entered at all, ln_partials — LayerNorm weight
+# gradients as fp32 partial sums from pass 1 on; emb_sort: one segmented id sort per step for the embedding backward.
+StepPlan = namedtuple("StepPlan", "rows n_accum sparse_rows readout rows_forward mask_impl k n_pass span fp32_sum pipelined ns has_reducer "
+                                  "layer_order sync_every inplace ln_partials emb_sort")
+# Pass j of a plan (pass_record).  isolate_last: the last pass of a DDP-wrapped model, on the caller's stream after everything, else
+# `side`: on side stream `slot`; ordered: a BackwardOrder is attached; join_side: its backward waits for every side stream instead of
+# the previous backward; delivery: the arguments (accumulate, ln_mode, acc32_mode) of model.accumulate_grads_inplace, or None — no
+# policy entered (autograd's own `grad += new`).
+PassRecord = namedtuple("PassRecord", "j last isolate_last side slot no_sync ordered join_side delivery")
+# The corrupted batch of one step; rows / targets: per micro-batch, the masked positions and (host prelude only) their labels, or None
+_Batch = namedtuple("_Batch", "masked_ids mask rows targets")
+
+
+def resolve_step_plan(s, rows: int, on_gpu: bool, has_reducer: bool, has_transformer: bool, env=os.environ) -> StepPlan:
+    """s: a TrainStep, or anything with its public attributes.  env: the two A/B switches are read here, once per call.
+    OBTE_NO_INPLACE_ACCUM=1: every gradient is delivered through autograd's AccumulateGrad (`grad += new`, issued by the engine AFTER
+    a node's backward returned), so no per-group event a node records can cover it: pipelined passes are then ordered as wholes.
+    OBTE_NO_LN_PARTIALS=1: no fp32 LayerNorm partial sums."""
+    stub = s.fused_loss_fn is not None          # a stub model / torch loss (CPU tests) takes the generic graph
+    no_inplace = env.get("OBTE_NO_INPLACE_ACCUM") == "1"
+    fused = s.loss_impl == "fused"
+    rows = rows // s.mini * s.mini
+    n_accum = rows // s.mini
+    sparse_rows = s.lm_head_impl in ("dense", "masked") and fused and not stub
+    k = s.per_pass if (sparse_rows and n_accum % s.per_pass == 0) else 1
+    n_pass = n_accum // k
+    pipelined = s.pipeline_streams >= 2 and on_gpu and fused and n_pass > 2 and not s.sync_every
+    return StepPlan(rows=rows, n_accum=n_accum, sparse_rows=sparse_rows, readout=s.lm_head_impl, rows_forward=s.rows_forward,
+                    mask_impl=s.mask_impl, k=k, n_pass=n_pass, span=k * s.mini,
+                    fp32_sum=s.grad_accum == "fp32" and n_pass >= 2,   # (a single pass: the plain path, its gradient is rounded once anyway)
+                    pipelined=pipelined, ns=s.pipeline_streams if pipelined else 1, has_reducer=has_reducer,
+                    layer_order=s.backward_order == "layer" and not stub and not no_inplace, sync_every=bool(s.sync_every),
+                    inplace=fused and not no_inplace,
+                    ln_partials=n_pass > 2 and not s.sync_every and not stub and env.get("OBTE_NO_LN_PARTIALS") != "1",
+                    emb_sort=on_gpu and fused and not stub and has_transformer)
+
+
+def pass_record(plan: StepPlan, j: int) -> PassRecord:
+    """Pass j of the plan; the ONE place that decides how a pass delivers its gradients.
+    bf16 path: all but the last pass of a DDP-wrapped model accumulate in place — nobody observes the per-micro-batch gradients,
+    so the wgrad epilogues add into param.grad themselves (the last pass too when no reducer is attached: nothing observes its
+    gradients before the optimizer does).  LayerNorm weights: pass 0 delivers through autograd (there is no .grad yet), 1 .. n-2
+    carry fp32 partial sums (first / more), the last folds them in and delivers the total through autograd.
+    fp32 sum: every weight gradient, the LayerNorm weights included, from pass 0 on — first / more / last."""
+    from . import _lib as L
+    last = j == plan.n_pass - 1
+    isolate_last = last and plan.has_reducer
+    side = plan.pipelined and not isolate_last
+    if plan.fp32_sum:
+        ln_mode, acc32_mode = ((L.LN_PARTIAL_FIRST, L.ACC32_FIRST) if j == 0 else
+                               (L.LN_PARTIAL_LAST, L.ACC32_LAST) if last else (L.LN_PARTIAL_MORE, L.ACC32_MORE))
+        delivery = (False, ln_mode, acc32_mode)
+    elif not plan.inplace:
+        delivery = None
+    else:
+        ln_mode = 0
+        if plan.ln_partials and j >= 1:
+            ln_mode = L.LN_PARTIAL_FIRST if j == 1 else (L.LN_PARTIAL_LAST if last else L.LN_PARTIAL_MORE)
+        delivery = (not isolate_last and not plan.sync_every, ln_mode, 0)
+    return PassRecord(j=j, last=last, isolate_last=isolate_last, side=side, slot=(j % plan.ns) if side else 0,
+                      no_sync=plan.has_reducer and not last and not plan.sync_every, ordered=side and plan.layer_order,
+                      join_side=plan.pipelined and isolate_last, delivery=delivery)
+
+
+def _pass_rows(batch: _Batch, j: int, k: int, rows_per_mb: int):
+    """Masked positions of pass j (micro-batches j*k .. j*k + k-1) as row indices into the pass's k * mini rows; for k > 1 the
+    weight 1 / (masked tokens of its own micro-batch) of each; their labels in the same order when the host prelude shipped them."""
+    lists = batch.rows[j * k:(j + 1) * k]
+    tgts = batch.targets[j * k:(j + 1) * k] if batch.targets is not None else None
+    keep = [i for i, r in enumerate(lists) if r.numel() > 0]
+    if k == 1 or not keep:
+        return lists[0], None, None if tgts is None else tgts[0]
+    rows = torch.cat([lists[i] + i * rows_per_mb for i in keep])
+    w = torch.cat([torch.full((lists[i].numel(),), 1.0 / lists[i].numel(), dtype=torch.float32, device=rows.device) for i in keep])
+    return rows, w, None if tgts is None else torch.cat([tgts[i] for i in keep])
+
+
 class TrainStep:
     """One optimizer step of train_encoder.py:241-323 over a (rows, ctx_len) batch of this rank's rows."""
+    _warned_no_host_copy = False
 
     def __init__(self, model, optimizer, scheduler=None, *, mini_batch_size: int, n_head: int, use_padding: bool = False,
                  loss_impl: str = "fused", mask_impl: str = "ranges", sync_every_micro_step: bool = False,
@@ -352,8 +437,6 @@ class TrainStep:
         #     translation of the reference's graph (logits.backward(dlogits)); kept for A/B and for callers of model(x).
         assert lm_head_impl in ("dense", "dense_full", "masked")
         self.lm_head_impl = lm_head_impl
-        self._dlogits = {}
-        self._all_ranges = None
         # pipeline_streams = 2: micro-batches alternate between two HIP streams so that the forward of micro-batch j+1
         # runs beside the backward of micro-batch j (kernel tails and half-filled grids of one fill with work of the
         # other).  The backward passes stay strictly ordered (an event per micro-batch), so every gradient buffer sees
@@ -370,20 +453,18 @@ class TrainStep:
         # lm_head_impl="masked": hand the list of masked positions to model.forward(rows=...) so that everything after the last
         # block's attention (its MLP half, ln_f, the readout) is computed for those positions only; False: forward(return_
         # embeddings=True) on every position, rows gathered afterwards (the reference's forward contract to the letter)
-        self.rows_forward = bool(rows_forward) and hasattr(model.module if hasattr(model, "module") else model, "transformer")
-        self._order = None           # the BackwardOrder of the pass being built
-        self._prev_order_events = None
+        self.rows_forward = bool(rows_forward) and hasattr(self._core, "transformer")
+        # caches that outlive a call (nothing that describes a pass does)
         self._streams = None
-        self._slot = 0
-        self._prev_bwd_done = None
         self._host_bufs = {}
         self._order_ws = {}
+        self._dlogits = {}
         self._ln_store = None
+        self._acc32_store = None
+        self._mask_rows_host = None   # the last call's per-micro-batch masked-row lists (read by tests)
         if grad_accum not in ("bf16", "fp32"):
             raise ValueError(f'grad_accum must be "bf16" or "fp32", got {grad_accum!r}')
         self.grad_accum = grad_accum
-        self._acc32_store = None
-        self._acc32_mode = 0         # of the pass being built (0: the bf16 path)
         if grad_accum == "fp32":
             if sync_every_micro_step:
                 raise ValueError('grad_accum="fp32" (--fp32_grad_accum) cannot be combined with sync_every_micro_step=True: the gradient exists '
@@ -391,11 +472,15 @@ class TrainStep:
             if loss_impl != "fused" or fused_loss_fn is not None:
                 raise ValueError('grad_accum="fp32" (--fp32_grad_accum) needs the HIP model and loss (loss_impl="fused", no fused_loss_fn): a '
                                  "stub model or a torch loss delivers its gradients through autograd's bf16 `grad += new`")
-            core = model.module if hasattr(model, "module") else model
-            if int(getattr(getattr(core, "config", None), "checkpoint_freq", 0) or 0) > 0:
+            if int(getattr(getattr(self._core, "config", None), "checkpoint_freq", 0) or 0) > 0:
                 raise ValueError('grad_accum="fp32" (--fp32_grad_accum) cannot be combined with checkpoint_freq > 0: a recomputed block captures '
                                  "its gradient policy on the autograd thread, outside the step's context, and would sum in bf16 unnoticed")
             self._refuse_env_switches()
+
+    @property
+    def _core(self):
+        """The model itself, out of a DDP wrapper."""
+        return self.model.module if hasattr(self.model, "module") else self.model
 
     @staticmethod
     def _refuse_env_switches() -> None:
@@ -404,30 +489,21 @@ class TrainStep:
                 raise ValueError(f'grad_accum="fp32" (--fp32_grad_accum) cannot be combined with {var}=1: that switch sends gradients through '
                                  "autograd's bf16 `grad += new`")
 
-    @staticmethod
-    def _no_inplace() -> bool:
-        """OBTE_NO_INPLACE_ACCUM=1 (A/B switch): every gradient is delivered through autograd's AccumulateGrad (`grad += new`,
-        issued by the engine AFTER a node's backward returned), so no per-group event a node records can cover it: pipelined
-        passes are then ordered as wholes (backward_order="pass": one event after the entire backward)."""
-        return os.environ.get("OBTE_NO_INPLACE_ACCUM") == "1"
+    def _resolve(self, n_rows: int, on_gpu: bool) -> StepPlan:
+        return resolve_step_plan(self, n_rows, on_gpu, hasattr(self.model, "no_sync"), hasattr(self._core, "transformer"))
 
-    def _inplace(self, enabled: bool, ln_partial_mode: int = 0, acc32_mode: int = 0):
-        if acc32_mode:   # every gradient of the model summed in fp32 over the passes: the weights' buffers and the LayerNorm partials
-            from .model import Fp32GradStore, LnPartialStore, accumulate_grads_inplace
-            if self._ln_store is None:
-                self._ln_store = LnPartialStore()
-            if self._acc32_store is None:
-                self._acc32_store = Fp32GradStore()   # this step object's own fp32 gradient sums
-            return accumulate_grads_inplace(False, acc32_mode, store=self._ln_store, order=self._order, acc32_mode=acc32_mode,
-                                            acc32_store=self._acc32_store)
-        if self.loss_impl != "fused" or self._no_inplace():   # CPU-oracle tests / A-B switch (whole-pass ordering then: __call__)
+    def _delivery(self, rec: PassRecord, order):
+        """The gradient policy of the pass (pass_record decided it) over this object's own fp32 stores."""
+        if rec.delivery is None:   # CPU-oracle tests / A-B switch
             return contextlib.nullcontext()
-        from .model import LnPartialStore, accumulate_grads_inplace
-        if self.fused_loss_fn is not None or os.environ.get("OBTE_NO_LN_PARTIALS") == "1":   # stub models / A-B switch
-            ln_partial_mode = 0
+        from .model import Fp32GradStore, LnPartialStore, accumulate_grads_inplace
+        accumulate, ln_mode, acc32_mode = rec.delivery
         if self._ln_store is None:
-            self._ln_store = LnPartialStore()     # this step object's own fp32 LayerNorm partial sums
-        return accumulate_grads_inplace(enabled, ln_partial_mode, store=self._ln_store, order=self._order)
+            self._ln_store = LnPartialStore()     # fp32 LayerNorm partial sums
+        if acc32_mode and self._acc32_store is None:
+            self._acc32_store = Fp32GradStore()   # fp32 gradient sums
+        return accumulate_grads_inplace(accumulate, ln_mode, store=self._ln_store, order=order, acc32_mode=acc32_mode,
+                                        acc32_store=self._acc32_store if acc32_mode else None)
 
     def _token_order_ws(self, segments: int, seg_len: int, vocab: int, dev) -> torch.Tensor:
         """The workspace of ops.token_order: allocated once per shape and reused (every use is on the caller's stream)."""
@@ -440,30 +516,37 @@ class TrainStep:
             ws = self._order_ws[key] = ops.token_order_workspace(segments, seg_len, vocab, dev)
         return ws
 
-    def _mask(self, tokens: torch.Tensor, dtype, j: int = -1, k: int = 1):
+    def _embedding_orders(self, plan: StepPlan, masked_ids):
+        """The embedding backward sums gradient rows in sorted-token order: ONE segmented sort for all passes of the step instead
+        of a radix sort (four launches) per pass.  None: every forward sorts its own ids."""
+        if not plan.emb_sort:
+            return None
+        from . import ops
+        seg = masked_ids.reshape(plan.n_pass, -1)
+        if not ops.prelude_hip():
+            return torch.sort(seg, dim=1, stable=True).indices.to(torch.int32)
+        seg = seg.contiguous()
+        vocab = self._core.transformer.wte.weight.shape[0]
+        return ops.token_order(seg, vocab, ws=self._token_order_ws(plan.n_pass, seg.shape[1], vocab, seg.device))
+
+    def _mask(self, plan: StepPlan, ranges, j: int, dtype):
+        """The attention mask of pass j out of the key ranges built once per optimizer step for every micro-batch."""
         from . import masks
-        if j >= 0 and self._all_ranges is not None:   # built once per optimizer step for every micro-batch
-            rm = masks.RangeMask(self._all_ranges[j * k * self.mini:(j + 1) * k * self.mini])
-        else:
-            rm = masks.RangeMask.from_tokens(tokens, padding=self.use_padding)
-        if self.mask_impl == "ranges":
+        rm = masks.RangeMask(ranges[j * plan.span:(j + 1) * plan.span])
+        if plan.mask_impl == "ranges":
             return rm
-        B, T = tokens.shape
         return rm.dense(dtype).unsqueeze(1).expand(-1, self.n_head, -1, -1)   # train_encoder.py:292
 
-    def _loss_backward(self, logits, targets, mask, n_accum):
-        if self.loss_impl == "fused" and self.fused_loss_fn is not None:
-            loss, dlogits = self.fused_loss_fn(logits, targets, mask, n_accum)
-            if logits.is_cuda:
-                self._order_backward()
-            logits.backward(dlogits)
-            return loss.detach()
+    def _loss_backward(self, rec: PassRecord, chain, logits, targets, mask, n_accum):
         if self.loss_impl == "fused":
-            from . import ops
-            if self._slot not in self._dlogits:   # one reusable d(logits) buffer per stream in flight
-                self._dlogits[self._slot] = ops.DLogitsBuffer()
-            loss, dlogits = ops.masked_ce(logits, targets, mask, n_accum, reuse=self._dlogits[self._slot])
-            self._order_backward()
+            if self.fused_loss_fn is not None:
+                loss, dlogits = self.fused_loss_fn(logits, targets, mask, n_accum)
+            else:
+                from . import ops
+                if rec.slot not in self._dlogits:   # one reusable d(logits) buffer per stream in flight
+                    self._dlogits[rec.slot] = ops.DLogitsBuffer()
+                loss, dlogits = ops.masked_ce(logits, targets, mask, n_accum, reuse=self._dlogits[rec.slot])
+            self._order_backward(rec, chain)
             logits.backward(dlogits)
             return loss.detach()
         # the reference's own three lines (train_encoder.py:301-305)
@@ -473,117 +556,71 @@ class TrainStep:
         loss.backward()
         return loss.detach().float()
 
-    def _order_backward(self, whole_pass: bool = False):
+    def _order_backward(self, rec: PassRecord, chain, whole_pass: bool = False):
         """Pipelined micro-batches: this backward may start only after the previous micro-batch's backward finished.
         whole_pass: wait for the previous backward as a whole even under per-group ordering — for a graph whose gradients
         reach the readout weight through AccumulateGrad instead of a node that carries the BackwardOrder (the zero
         gradients of a pass with nothing masked)."""
-        if getattr(self, "_join_side_streams", False):   # the isolated last pass of a DDP-wrapped model: everything before it is done
-            self._join_side_streams = False
+        if rec.join_side:   # the isolated last pass of a DDP-wrapped model: everything before it is done
             for st in self._streams:
                 torch.cuda.current_stream().wait_stream(st)
             return
-        if self._order is not None and not whole_pass:   # per-group events instead (model.BackwardOrder); _prev_bwd_done is its fallback
+        if chain.order is not None and not whole_pass:   # per-group events instead (model.BackwardOrder); prev_done is its fallback
             return
-        if self._prev_bwd_done is not None:
-            torch.cuda.current_stream().wait_event(self._prev_bwd_done)
+        if chain.prev_done is not None:
+            torch.cuda.current_stream().wait_event(chain.prev_done)
 
-    def _pass_targets(self, j: int, k: int):
-        """The labels of the masked positions of pass j in _pass_rows' order, when the host prelude shipped them; else None."""
-        lists = getattr(self, "_mask_targets_host", None)
-        if lists is None:
-            return None
-        lists = lists[j * k:(j + 1) * k]
-        if k == 1:
-            return lists[0]
-        keep = [t for t in lists if t.numel() > 0]
-        return torch.cat(keep) if keep else lists[0]
-
-    def _pass_rows(self, j: int, k: int, rows_per_mb: int):
-        """Masked positions of pass j (micro-batches j*k .. j*k + k-1) as row indices into the pass's k * mini rows, and —
-        for k > 1 — the weight 1 / (masked tokens of its own micro-batch) of each."""
-        lists = self._mask_rows_host[j * k:(j + 1) * k]
-        if k == 1:
-            return lists[0], None
-        keep = [(i, r) for i, r in enumerate(lists) if r.numel() > 0]
-        if not keep:
-            return lists[0], None
-        rows = torch.cat([r + i * rows_per_mb for i, r in keep])
-        w = torch.cat([torch.full((r.numel(),), 1.0 / r.numel(), dtype=torch.float32, device=r.device) for _, r in keep])
-        return rows, w
-
-    def _zero_pass_backward(self, emb, core):
-        """The backward of a pass with nothing masked: zero gradients for every parameter.  The readout's own node does not run in
-        such a pass; with the fp32 sum its weight takes the zero contribution by the pass's mode instead (model._Acc32FlushFn:
-        the first pass zeroes the buffer, the last hands the other passes' total to autograd and DDP's reducer)."""
-        if self._acc32_mode:
-            from .model import _Acc32FlushFn
-            (emb.sum() * 0 + _Acc32FlushFn.apply(core.lm_head.weight)).backward()
-        else:
-            (emb.sum() * 0 + core.lm_head.weight.sum() * 0).backward()
-
-    def _dense_logits_sparse_backward(self, x, y, mk, attn_mask, n_accum, k: int = 1):
-        """lm_head_impl="dense": full logits in the forward, backward over the masked rows (see __init__)."""
+    def _rows_loss_backward(self, plan: StepPlan, rec: PassRecord, chain, batch: _Batch, x, y, attn_mask):
+        """The two row-compact readouts (see __init__): the CE kernel turns logits into d(logits) rows of the masked positions — the
+        row indices come from the host-side MLM draw, no device sync — and the two backward products contract over those rows.
+        "dense": logits of every position in the forward, as model.py:253 computes them.  "masked" (SURVEY.md §8f rank 1): logits
+        for the listed rows alone ([n_masked, V]), forward included."""
         from . import ops
-        from .model import _ReadoutRowsGradFn
-        emb = self.model(x, attn_mask=attn_mask, return_embeddings=True)
-        core = self.model.module if hasattr(self.model, "module") else self.model
-        rows, weights = self._pass_rows(self._mb, k, self.mini * x.shape[1])
-        with torch.no_grad():
-            logits = core.lm_head(emb)                     # (B, T, V): every position, as model.py:253 computes them
-            if rows.numel() == 0:
-                loss, dl = None, None
-            else:
-                loss, dl = ops.masked_ce_rows(logits, y.reshape(-1), rows, n_accum, row_weights=weights)
-        del logits
-        self._order_backward(whole_pass=dl is None)
-        if dl is None:    # nothing masked: zero gradients for every parameter (the reference would produce 0/0 = NaN here)
-            self._zero_pass_backward(emb, core)
-            return torch.zeros((), dtype=torch.float32, device=x.device)
-        emb_rows = emb.reshape(-1, emb.shape[-1]).index_select(0, rows)
-        wm = float(core.lm_head.output_mult) / float(core.lm_head.width_mult())
-        _ReadoutRowsGradFn.apply(emb_rows, core.lm_head.weight, wm, dl).backward()
-        return loss.detach()
-
-    def _masked_rows_loss_backward(self, x, y, mk, attn_mask, n_accum, k: int = 1):
-        """lm_head_impl="masked" (SURVEY.md §8f rank 1): readout + CE on the masked rows only, forward included.  The row
-        indices come from the host-side MLM draw (no device sync); logits exist for the listed rows alone ([n_masked, V]),
-        the CE kernel turns them into d(logits) rows, and the two backward products are those of the "dense" path."""
-        from . import ops
-        from .model import _ReadoutRowsGradFn
-        core = self.model.module if hasattr(self.model, "module") else self.model
-        rows, weights = self._pass_rows(self._mb, k, self.mini * x.shape[1])
+        from .model import _Acc32FlushFn, _ReadoutRowsGradFn
+        core = self._core
+        rows, weights, tg = _pass_rows(batch, rec.j, plan.k, self.mini * x.shape[1])
         if rows.numel() == 0:
-            # nothing masked in this pass: still hand EVERY parameter a (zero) gradient — lm_head included — or
-            # DDP's reducer would wait for it forever when this is the synchronising micro-batch
+            # nothing masked in this pass (the reference would produce 0/0 = NaN here): still hand EVERY parameter a (zero)
+            # gradient — lm_head included — or DDP's reducer would wait for it forever when this is the synchronising pass.
+            # The readout's own node does not run in such a pass; with the fp32 sum its weight takes the zero contribution by
+            # the pass's mode instead (model._Acc32FlushFn: the first pass zeroes the buffer, the last hands the other passes'
+            # total to autograd and DDP's reducer).
             emb = self.model(x, attn_mask=attn_mask, return_embeddings=True)
-            self._order_backward(whole_pass=True)
-            self._zero_pass_backward(emb, core)
+            self._order_backward(rec, chain, whole_pass=True)
+            head = _Acc32FlushFn.apply(core.lm_head.weight) if plan.fp32_sum else core.lm_head.weight.sum() * 0
+            (emb.sum() * 0 + head).backward()
             return torch.zeros((), dtype=torch.float32, device=x.device)
-        if self.rows_forward:
+        dense = plan.readout == "dense"
+        if not dense and plan.rows_forward:
             # the model is told which positions are wanted: the last block's MLP half and ln_f run on them alone (model.forward(rows=))
             emb_rows = self.model(x, attn_mask=attn_mask, return_embeddings=True, rows=rows)
         else:
             emb = self.model(x, attn_mask=attn_mask, return_embeddings=True)
-            emb_rows = emb.reshape(-1, emb.shape[-1]).index_select(0, rows)
+            emb_rows = None if dense else emb.reshape(-1, emb.shape[-1]).index_select(0, rows)
         with torch.no_grad():
-            logits = core.lm_head(emb_rows)                # (n_masked, V): model.py:253 on the rows the loss keeps (:304)
-            tg = self._pass_targets(self._mb, k)
-            loss, dl = ops.masked_ce_rows(logits, tg if tg is not None else y.reshape(-1).index_select(0, rows), None, n_accum, row_weights=weights)
+            if dense:
+                logits = core.lm_head(emb)                     # (B, T, V)
+                loss, dl = ops.masked_ce_rows(logits, y.reshape(-1), rows, plan.n_accum, row_weights=weights)
+            else:
+                logits = core.lm_head(emb_rows)                # (n_masked, V): the rows the loss keeps (train_encoder.py:304)
+                loss, dl = ops.masked_ce_rows(logits, tg if tg is not None else y.reshape(-1).index_select(0, rows), None, plan.n_accum,
+                                              row_weights=weights)
         del logits
-        self._order_backward()
+        self._order_backward(rec, chain)
+        if dense:
+            emb_rows = emb.reshape(-1, emb.shape[-1]).index_select(0, rows)
         wm = float(core.lm_head.output_mult) / float(core.lm_head.width_mult())
         _ReadoutRowsGradFn.apply(emb_rows, core.lm_head.weight, wm, dl).backward()
         return loss.detach()
 
-    def _host_prelude(self, input_ids, ids_host, rows, n_accum, want_rows):
+    def _host_prelude(self, plan: StepPlan, input_ids, ids_host) -> _Batch:
         """The MLM corruption with every host-side input at hand (train_encoder.py:273-279): the Bernoulli draw AND the
         PAD/EOS exclusions are evaluated on the host copy of the batch, so the final mask — and from it the per-micro-batch
         lists of masked positions — is known without a device round trip.  Mask and lists go to the GPU through reused
         pinned buffers as asynchronous copies; the host never waits for the device here (the `.cpu()` of the device-side
         form stalls the host until the previous optimizer step has drained: 1.5-2 ms of idle GPU per step)."""
         dev = input_ids.device
-        T = input_ids.shape[1]
+        rows, n_accum, T = plan.rows, plan.n_accum, input_ids.shape[1]
         ids_h = np.asarray(ids_host)[:rows]
         draw = np.random.binomial(1, 0.15, (rows, T))                                  # same call, same stream as mlm_corrupt
         mask_h = (draw != 0) & (ids_h != PAD_TOKEN) & (ids_h != EOS_TOKEN)
@@ -600,8 +637,8 @@ class TrainStep:
             st["done"].synchronize()        # the previous step's copies out of these pinned buffers (long finished)
         st["mask_pin"].numpy()[...] = mask_h
         st["mask_dev"].copy_(st["mask_pin"], non_blocking=True)
-        lists = None
-        if want_rows:
+        lists = targets = None
+        if plan.sparse_rows:
             per = mask_h.reshape(n_accum, -1)
             idx = [np.flatnonzero(per[j]) for j in range(n_accum)]
             sizes = [len(v) for v in idx]
@@ -615,10 +652,70 @@ class TrainStep:
                 st["tgt_dev"][:total].copy_(st["tgt_pin"][:total], non_blocking=True)
             off = np.concatenate([[0], np.cumsum(sizes)])
             lists = [st["rows_dev"][int(off[j]):int(off[j + 1])] for j in range(n_accum)]
-            self._mask_targets_host = [st["tgt_dev"][int(off[j]):int(off[j + 1])] for j in range(n_accum)]
+            targets = [st["tgt_dev"][int(off[j]):int(off[j + 1])] for j in range(n_accum)]
         st["done"] = torch.cuda.current_stream().record_event()
         mask = st["mask_dev"]
-        return input_ids.masked_fill(mask, MASK_TOKEN), mask, lists
+        return _Batch(input_ids.masked_fill(mask, MASK_TOKEN), mask, lists, targets)
+
+    def _prepare_batch(self, plan: StepPlan, input_ids, mlm_mask, input_ids_host) -> _Batch:
+        """The corrupted ids, the mask and — for the row-compact readouts — the masked positions per micro-batch, from the host
+        prelude, the host Bernoulli draw (mlm_corrupt) or the caller's mlm_mask."""
+        if mlm_mask is None and input_ids_host is not None and input_ids.is_cuda:
+            return self._host_prelude(plan, input_ids, input_ids_host)
+        if mlm_mask is None:
+            masked_ids, mask = mlm_corrupt(input_ids)
+        else:
+            mask = mlm_mask[:plan.rows].to(input_ids.device) & (input_ids != PAD_TOKEN) & (input_ids != EOS_TOKEN)
+            masked_ids = input_ids.masked_fill(mask, MASK_TOKEN)
+        lists = None
+        if plan.sparse_rows:
+            # per-micro-batch row indices of the masked positions; mlm_corrupt drew the mask on the host, but PAD/EOS
+            # exclusions were applied on the device, so fetch the final mask once per optimizer step (one small D2H copy)
+            if input_ids.is_cuda and mlm_mask is None and not TrainStep._warned_no_host_copy:
+                TrainStep._warned_no_host_copy = True
+                import warnings
+                warnings.warn("TrainStep: no input_ids_host given — the masked-row lists of the default readout path need a "
+                              "blocking device-to-host copy per optimizer step (pass the loader's host copy of the batch to avoid it)")
+            mh = mask.reshape(plan.n_accum, -1).cpu()
+            lists = [torch.nonzero(mh[j], as_tuple=False).reshape(-1).to(input_ids.device) for j in range(mh.shape[0])]
+        return _Batch(masked_ids, mask, lists, None)
+
+    def _fork_streams(self, plan: StepPlan):
+        """The caller's stream when the step is pipelined, its side streams made to wait for it; else None."""
+        if not plan.pipelined:
+            return None
+        main = torch.cuda.current_stream()
+        if self._streams is None or len(self._streams) != plan.ns:
+            self._streams = [torch.cuda.Stream() for _ in range(plan.ns)]
+            # gradients are produced on the side streams by design; the engine's cross-stream sync is what we want
+            warn_off = getattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch", None)
+            if warn_off is not None:
+                warn_off(False)
+        for st in self._streams:
+            st.wait_stream(main)
+        return main
+
+    def _run_pass(self, plan: StepPlan, rec: PassRecord, chain, batch: _Batch, input_ids, ranges, emb_orders, dtype):
+        """Forward, loss and backward of one pass on the current stream; its share of the step's loss."""
+        from .model import BackwardOrder, embedding_order
+        sl = slice(rec.j * plan.span, (rec.j + 1) * plan.span)
+        x, y = batch.masked_ids[sl], input_ids[sl]
+        attn_mask = self._mask(plan, ranges, rec.j, dtype)
+        ctx = self.model.no_sync() if rec.no_sync else contextlib.nullcontext()
+        # this pass's slice of the step-wide id sort, for its embedding backward
+        ctx_order = embedding_order(emb_orders[rec.j]) if emb_orders is not None else contextlib.nullcontext()
+        chain.order = BackwardOrder(chain.prev_events, chain.prev_done) if rec.ordered else None
+        with ctx, ctx_order, self._delivery(rec, chain.order):
+            if plan.sparse_rows:
+                loss = self._rows_loss_backward(plan, rec, chain, batch, x, y, attn_mask)
+            else:
+                logits = self.model(x, attn_mask=attn_mask)
+                loss = self._loss_backward(rec, chain, logits, y, batch.mask[sl], plan.n_accum)
+                del logits
+        if rec.side:
+            chain.prev_done = torch.cuda.current_stream().record_event()
+            chain.prev_events = chain.order.events if chain.order is not None else None
+        return loss
 
     def __call__(self, input_ids: torch.Tensor, mlm_mask: Optional[torch.Tensor] = None, input_ids_host=None) -> Dict[str, torch.Tensor]:
         """mlm_mask (optional, bool (rows, T)): the positions to corrupt instead of the host Bernoulli draw of
@@ -628,130 +725,35 @@ class TrainStep:
         NEEDED for the sync-free path of the default readout (lm_head_impl="dense" / "masked" list the masked rows per
         micro-batch): without it the final mask comes back from the device once per optimizer step — a blocking D2H copy that
         waits for the previous step to drain (a one-time warning says so)."""
-        rows = input_ids.shape[0] // self.mini * self.mini
-        input_ids = input_ids[:rows]
-        n_accum = rows // self.mini
-        self.optimizer.zero_grad(set_to_none=True)
-        # the two row-compact readouts need the HIP kernels; a stub model / torch loss (CPU tests) takes the generic graph
-        sparse_rows = self.lm_head_impl in ("dense", "masked") and self.loss_impl == "fused" and self.fused_loss_fn is None
-        self._mask_targets_host = None   # set by the host prelude when it runs (labels of the masked positions)
-        if mlm_mask is None and input_ids_host is not None and input_ids.is_cuda:
-            masked_ids, mask, lists = self._host_prelude(input_ids, input_ids_host, rows, n_accum, sparse_rows)
-            if sparse_rows:
-                self._mask_rows_host = lists
-        else:
-            if mlm_mask is None:
-                masked_ids, mask = mlm_corrupt(input_ids)
-            else:
-                mask = mlm_mask[:rows].to(input_ids.device) & (input_ids != PAD_TOKEN) & (input_ids != EOS_TOKEN)
-                masked_ids = input_ids.masked_fill(mask, MASK_TOKEN)
-            if sparse_rows:
-                # per-micro-batch row indices of the masked positions; mlm_corrupt drew the mask on the host, but PAD/EOS
-                # exclusions were applied on the device, so fetch the final mask once per optimizer step (one small D2H copy)
-                if input_ids.is_cuda and mlm_mask is None and not getattr(TrainStep, "_warned_no_host_copy", False):
-                    TrainStep._warned_no_host_copy = True
-                    import warnings
-                    warnings.warn("TrainStep: no input_ids_host given — the masked-row lists of the default readout path need a "
-                                  "blocking device-to-host copy per optimizer step (pass the loader's host copy of the batch to avoid it)")
-                mh = mask.reshape(rows // self.mini, -1).cpu()
-                self._mask_rows_host = [torch.nonzero(mh[j], as_tuple=False).reshape(-1).to(input_ids.device) for j in range(mh.shape[0])]
-        dtype = next(self.model.parameters()).dtype
-        core_model = self.model.module if hasattr(self.model, "module") else self.model
-        k = self.per_pass if (sparse_rows and n_accum % self.per_pass == 0) else 1
-        n_pass, span = n_accum // k, k * self.mini          # passes through the model, rows per pass
-        fp32_sum = self.grad_accum == "fp32" and n_pass >= 2   # (a single pass: the plain path, its gradient is rounded once anyway)
-        if fp32_sum:
-            self._refuse_env_switches()
-        emb_orders = None
-        if input_ids.is_cuda and self.loss_impl == "fused" and self.fused_loss_fn is None and hasattr(core_model, "transformer"):
-            # the embedding backward sums gradient rows in sorted-token order: ONE segmented sort for all micro-batches of
-            # the step instead of a radix sort (four launches) per micro-batch
-            from . import ops
-            if ops.prelude_hip():
-                seg = masked_ids.reshape(n_pass, -1).contiguous()
-                vocab = core_model.transformer.wte.weight.shape[0]
-                emb_orders = ops.token_order(seg, vocab, ws=self._token_order_ws(n_pass, seg.shape[1], vocab, seg.device))
-            else:
-                emb_orders = torch.sort(masked_ids.reshape(n_pass, -1), dim=1, stable=True).indices.to(torch.int32)
-        cum_loss = torch.zeros((), dtype=torch.float32, device=input_ids.device)
         from . import masks
-        self._all_ranges = masks.RangeMask.from_tokens(input_ids, padding=self.use_padding, group=self.mini).key_ranges
-        pipelined = (self.pipeline_streams >= 2 and input_ids.is_cuda and self.loss_impl == "fused" and n_pass > 2
-                     and not self.sync_every)
-        main = torch.cuda.current_stream() if input_ids.is_cuda else None
-        if pipelined:
-            if self._streams is None or len(self._streams) != self.pipeline_streams:
-                self._streams = [torch.cuda.Stream() for _ in range(self.pipeline_streams)]
-                # gradients are produced on the side streams by design; the engine's cross-stream sync is what we want
-                warn_off = getattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch", None)
-                if warn_off is not None:
-                    warn_off(False)
-            for st in self._streams:
-                st.wait_stream(main)
-        ns = self.pipeline_streams if pipelined else 1
-        partial = [cum_loss] + [torch.zeros_like(cum_loss) for _ in range(ns - 1)]
-        self._prev_bwd_done = None
-        self._prev_order_events = None
-        for j in range(n_pass):
-            self._mb = j
-            x = masked_ids[j * span:(j + 1) * span]
-            y = input_ids[j * span:(j + 1) * span]
-            last = j == n_pass - 1
-            # the last pass of a DDP-wrapped model (the reducer's hooks and bucket all-reduces) runs on the caller's stream, after
-            # everything; without a reducer it is a pass like the others and the caller's stream joins the side streams afterwards
-            isolate_last = last and hasattr(self.model, "no_sync")
-            side = pipelined and not isolate_last
-            if pipelined and isolate_last:
-                # its forward still runs beside the previous backward passes (it only reads weights); the caller's stream joins
-                # the side streams right before its backward (_order_backward)
-                self._join_side_streams = True
-                self._prev_bwd_done = None
-            self._slot = (j % ns) if side else 0
-            self._order = None
-            if side and self.backward_order == "layer" and self.fused_loss_fn is None and not self._no_inplace():
-                from .model import BackwardOrder
-                self._order = BackwardOrder(self._prev_order_events, self._prev_bwd_done)
-            with (torch.cuda.stream(self._streams[j % ns]) if side else contextlib.nullcontext()):
-                attn_mask = self._mask(y, dtype, j, k)
-                ctx = contextlib.nullcontext()
-                if hasattr(self.model, "no_sync") and not last and not self.sync_every:
-                    ctx = self.model.no_sync()
-                if emb_orders is not None:    # this pass's slice of the step-wide id sort, for its embedding backward
-                    from .model import embedding_order
-                    ctx_order = embedding_order(emb_orders[j])
-                else:
-                    ctx_order = contextlib.nullcontext()
-                # all but the last pass: nobody observes the per-micro-batch gradients, so the big matrices are
-                # accumulated by the wgrad epilogues themselves (model.accumulate_grads_inplace)
-                # LayerNorm weight gradients: pass 0 delivers through autograd (there is no .grad yet), 1 .. n-2 carry
-                # fp32 partial sums (first / more), the last one folds them in and delivers the total through autograd
-                ln_mode = 0
-                if n_pass > 2 and not self.sync_every and j >= 1:
-                    ln_mode = 1 if j == 1 else (3 if last else 2)
-                # grad_accum="fp32": every weight gradient, the LayerNorm weights included, from pass 0 on — first / more / last
-                self._acc32_mode = (1 if j == 0 else (3 if last else 2)) if fp32_sum else 0
-                # (the last pass too when no reducer is attached: nothing observes its gradients before the optimizer does)
-                with ctx, ctx_order, self._inplace(not (last and hasattr(self.model, "no_sync")) and not self.sync_every, ln_mode, self._acc32_mode):
-                    mk = mask[j * span:(j + 1) * span]
-                    if sparse_rows and self.lm_head_impl == "masked":
-                        partial[self._slot] += self._masked_rows_loss_backward(x, y, mk, attn_mask, n_accum, k)
-                    elif sparse_rows:
-                        partial[self._slot] += self._dense_logits_sparse_backward(x, y, mk, attn_mask, n_accum, k)
-                    else:
-                        logits = self.model(x, attn_mask=attn_mask)
-                        partial[self._slot] += self._loss_backward(logits, y, mk, n_accum)
-                        del logits
-                if side:
-                    self._prev_bwd_done = torch.cuda.current_stream().record_event()
-                    self._prev_order_events = self._order.events if self._order is not None else None
+        plan = self._resolve(input_ids.shape[0], input_ids.is_cuda)
+        input_ids = input_ids[:plan.rows]
+        self.optimizer.zero_grad(set_to_none=True)
+        batch = self._prepare_batch(plan, input_ids, mlm_mask, input_ids_host)
+        self._mask_rows_host = batch.rows
+        if plan.fp32_sum:
+            self._refuse_env_switches()
+        dtype = next(self.model.parameters()).dtype
+        emb_orders = self._embedding_orders(plan, batch.masked_ids)
+        ranges = masks.RangeMask.from_tokens(input_ids, padding=self.use_padding, group=self.mini).key_ranges
+        partial = [torch.zeros((), dtype=torch.float32, device=input_ids.device) for _ in range(plan.ns)]   # the loss, summed per stream
+        main = self._fork_streams(plan)
+        # what links the backward passes of this call's side passes: the event after the previous one, that pass's per-group events,
+        # and the BackwardOrder of the pass being built
+        chain = SimpleNamespace(prev_done=None, prev_events=None, order=None)
+        for rec in (pass_record(plan, j) for j in range(plan.n_pass)):
+            # an isolated last pass: its forward still runs beside the previous backward passes (it only reads weights); the
+            # caller's stream joins the side streams right before its backward (_order_backward)
+            with (torch.cuda.stream(self._streams[rec.slot]) if rec.side else contextlib.nullcontext()):
+                partial[rec.slot] += self._run_pass(plan, rec, chain, batch, input_ids, ranges, emb_orders, dtype)
         if input_ids.is_cuda and hasattr(self.model, "_obte_timed_hook"):   # measurement only (comm.TimedHook): the step's last backward ends here
             self.backward_end_event = torch.cuda.Event(enable_timing=True)
             self.backward_end_event.record()
-        if pipelined:
+        cum_loss = partial[0]
+        if plan.pipelined:
             for st in self._streams:   # (a no-op after an isolated last pass: that one already waited for them)
                 main.wait_stream(st)
-            cum_loss = partial[0] + partial[1]
-            for extra in partial[2:]:
+            for extra in partial[1:]:
                 cum_loss = cum_loss + extra
         if isinstance(self.optimizer, FusedAdamW):
             self.optimizer.step(max_norm=self.max_grad_norm)

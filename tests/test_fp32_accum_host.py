@@ -14,19 +14,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_store_is_keyed_by_identity_and_releases_a_buffer_when_its_parameter_dies():
-    from omnibiote_amd.model import Fp32GradStore
-    store = Fp32GradStore()
-    p, q = torch.nn.Parameter(torch.zeros(6, 8, dtype=torch.bfloat16)), torch.nn.Parameter(torch.zeros(3, 8, dtype=torch.bfloat16))
-    bp, bq = store.get(p), store.get(q)
-    assert bp.dtype == torch.float32 and bp.shape == p.shape and bq.shape == q.shape and bp.device == p.device
-    assert store.get(p) is bp and store.get(q) is bq and len(store) == 2
-    assert not hasattr(p, "acc32") and "acc32" not in vars(p) and not [k for k in vars(p) if "32" in k]
-    del p
-    gc.collect()
-    assert len(store) == 1 and store.get(q) is bq
-    del q
-    gc.collect()
-    assert len(store) == 0
+    from omnibiote_amd.model import Fp32GradStore, LnPartialStore
+    for cls in (Fp32GradStore, LnPartialStore):     # one keyed-by-identity base, two kinds of buffer
+        store = cls()
+        p, q = torch.nn.Parameter(torch.zeros(6, 8, dtype=torch.bfloat16)), torch.nn.Parameter(torch.zeros(3, 8, dtype=torch.bfloat16))
+        bp, bq = store.get(p), store.get(q)
+        assert bp.dtype == torch.float32 and bp.device == p.device
+        if cls is Fp32GradStore:
+            assert bp.shape == p.shape and bq.shape == q.shape
+        else:                                       # per-workgroup partial sums of the weight's elements
+            assert bp.numel() % p.numel() == 0 and bq.numel() * p.numel() == bp.numel() * q.numel()
+        assert store.get(p) is bp and store.get(q) is bq and len(store) == 2
+        assert not hasattr(p, "acc32") and "acc32" not in vars(p) and not [k for k in vars(p) if "32" in k]
+        del p
+        gc.collect()
+        assert len(store) == 1 and store.get(q) is bq
+        del q
+        gc.collect()
+        assert len(store) == 0
 
 
 def test_a_pickle_of_the_model_holds_no_fp32_buffer():

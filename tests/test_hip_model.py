@@ -768,6 +768,38 @@ def test_pipelined_step_with_dropout_is_bitwise_the_single_stream_step():
         assert torch.equal(out[1][1][k], out[2][1][k]), "weight " + k
 
 
+def test_settings_switched_on_a_live_train_step_give_the_step_of_a_fresh_one():
+    """TrainStep resolves its plan per call: a benchmark reassigns pipeline_streams, per_pass and lm_head_impl on a live object
+    between steps.  After every step of such a walk the model's parameters (and gradients) must equal, bit for bit, those of an
+    identically initialised model whose every step is run by a FRESH TrainStep built with that step's settings — nothing of an
+    earlier step's plan may linger on the object.  6 micro-batches of 1 row: 6 passes at k = 1 (first / more / last LayerNorm
+    partials, both stream slots), 3 passes at k = 2."""
+    from omnibiote_amd import train_encoder as TE
+    C, H, Lyr, V, T, rows, mini = 128, 2, 2, 512, 64, 6, 1
+    w = R.hash_weights(R.RefConfig(block_size=T, vocab_size=V, n_layer=Lyr, n_head=H, n_embd=C))
+    host = TE.synthetic_rows(rows, T, V, np.random.default_rng(21), single_document=False)
+    ids = torch.from_numpy(host).to(DEV)
+    walk = [(2, 1, "masked"), (1, 1, "masked"), (2, 1, "masked"), (2, 2, "masked"), (2, 2, "dense"), (2, 1, "dense"), (2, 1, "masked")]
+    ma, mb = _tiny_model(w, C, H, Lyr, V, T), _tiny_model(w, C, H, Lyr, V, T)
+    oa, ob = TE.FusedAdamW(ma.parameters(), lr=1e-3), TE.FusedAdamW(mb.parameters(), lr=1e-3)
+    live = TE.TrainStep(ma, oa, None, mini_batch_size=mini, n_head=H, pipeline_streams=walk[0][0], micro_batches_per_pass=walk[0][1],
+                        lm_head_impl=walk[0][2])
+    start = ma.lm_head.weight.detach().clone()
+    for it, (streams, k, impl) in enumerate(walk):
+        live.pipeline_streams, live.per_pass, live.lm_head_impl = streams, k, impl
+        fresh = TE.TrainStep(mb, ob, None, mini_batch_size=mini, n_head=H, pipeline_streams=streams, micro_batches_per_pass=k, lm_head_impl=impl)
+        losses = []
+        for step in (live, fresh):
+            np.random.seed(40 + it)
+            losses.append(step(ids, input_ids_host=host)["loss"].item())
+        torch.cuda.synchronize()
+        assert losses[0] == losses[1], (it, losses)
+        for (n, a), b in zip(ma.named_parameters(), mb.parameters()):
+            assert torch.equal(a.grad, b.grad), f"step {it} {(streams, k, impl)}: grad {n}"
+            assert torch.equal(a.detach(), b.detach()), f"step {it} {(streams, k, impl)}: weight {n}"
+    assert not torch.equal(ma.lm_head.weight.detach(), start)   # (the steps did move the weights)
+
+
 def test_dropout_masked_gradient_handoff_between_blocks(monkeypatch):
     """With dropout on, a block's backward also writes its dx under the MLP-projection mask of the block below (one stand-alone
     mask pass less per block).  The hand-off must be taken (3 of 4 blocks here: the top block has nobody above it) and change
