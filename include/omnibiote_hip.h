@@ -61,7 +61,7 @@ int obte_fault_inject(int what);
  * ms[i] = elapsed milliseconds, dims[3*i..] = (M,N,K) for a GEMM or (B*H, T, head_dim) for attention,
  * kind[i] = a_kmajor*8 + b_kmajor*4 + epilogue + 1000 * kernel structure (1 gemm_bf16_kernel, 2 gemm_v2_kernel,
  * 3 gemm_v3_kernel, 4 gemm_v4_kernel, 7 gemm_v7_kernel) for a GEMM, its split-K reduce inside the same record; 32 + 1 (the first
- * and last problems differ in layout) + 2 (accumulate) for a grouped launch; 100 = attention forward, 101 = attention backward, 102 = obte_attn_decode
+ * and last problems differ in layout) + 2 (accumulate) for a grouped launch; 100 = attention forward, 101 = attention backward, 102 = obte_attn_decode / obte_attn_decode_rows
  * over (B*H, n_keys, head_dim), its combine launch inside the same record; the HBM-bound
  * kernels record (rows, cols, flag): 110 LayerNorm forward, 111 LayerNorm backward (flag = residual gradient added),
  * 112 masked CE over (n_rows, vocab), 113 AdamW over (elements, 1, 1).
@@ -560,6 +560,9 @@ int obte_block_fwd_prefill(const obte_block_desc* d, const obte_bf16* x, obte_bf
 int64_t obte_block_decode_ws_bytes(int64_t B, int32_t n_embd, int32_t n_head);
 int obte_block_decode(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y, obte_bf16* kv_cache, int64_t T_max, int64_t pos, void* ws,
                       int64_t ws_bytes, obte_stream s);
+
+/* Generation from prompts of different lengths — one cache position per row, read on the device — is declared in
+ * omnibiote_hip_rows.h beside this file: the same ABI version, the same library, no new struct. */
 
 #ifdef __cplusplus
 }

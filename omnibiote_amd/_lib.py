@@ -160,6 +160,16 @@ SYMBOLS = {
     "obte_block_decode": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
 }
 
+# generation with one cache position per row (include/omnibiote_hip_rows.h): a table of its own, bound by lib() in the same loop —
+# SYMBOLS is, name for name and in order, what include/omnibiote_hip.h declares
+SYMBOLS_ROWS = {
+    "obte_kv_cache_rope_store_rows": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_attn_decode_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                        C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_decode_rows": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                         c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -187,7 +197,7 @@ def lib():
                 l = C.CDLL(LIB_PATH)
             except OSError as e:
                 raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-            for name, (res, args) in SYMBOLS.items():
+            for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -17,6 +17,13 @@
 //     and its V a selected 0, so whatever the cache holds past n_keys (NaN patterns included) cannot reach the result.  A lane group,
 //     a wave or a split without any key carries (m = -inf, l = 0, acc = 0); every merge rescales against a maximum made finite first,
 //     so exp2(-inf - -inf) is never formed.
+//
+// The rows forms (obte_kv_cache_rope_store_rows, obte_attn_decode_rows): one position / key count PER ROW, an int32 the kernels read on
+// the device, for a batch whose rows stand at different positions.  A value outside the host's bound makes the row inactive: nothing
+// of it is stored, none of its cache is read, its attention output is exact zeros and its lse -inf — an out-of-range device value is
+// memory-safe without a status word, and a negative one parks a finished row.  The attention kernel is the one above with ROWS = true:
+// a workgroup derives its key range from its own row's count by the host's formula, so a row of n keys under s splits is partitioned
+// (and summed) exactly as obte_attn_decode partitions n keys under s splits.
 #include "common.h"
 
 namespace {
@@ -102,16 +109,24 @@ __device__ __forceinline__ void decode_keys(Part& st, const float* qf, const bf1
 
 // HS: 64 or 128.  grid (splits, B * H), DEC_WAVES * 64 threads.  per: keys per split (a multiple of DEC_CHUNK).
 // splits == 1: o and lse are final.  Else part[(bh * splits + split) * (HS + DEC_PAD)] = (acc[HS], m, l).
-template <int HS>
+// ROWS: row b has rows_n[b] + rows_off keys if that lies in [1, n_keys] (n_keys: the host's bound), else none (an inactive row: no
+// key is loaded, the state stays (m = -inf, l = 0, acc = 0)); per is formed here from the row's own count.
+template <int HS, bool ROWS>
 __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16* __restrict__ q, int64_t q_ld, const bf16* __restrict__ cache,
                                                                       bf16* __restrict__ o, float* __restrict__ lse, float* __restrict__ part,
-                                                                      int H, int64_t T_max, int64_t v_off, int n_keys, int per, float qscale) {
+                                                                      int H, int64_t T_max, int64_t v_off, int n_keys, int per, float qscale,
+                                                                      const int32_t* __restrict__ rows_n, int rows_off) {
     constexpr int LPR = HS / 8;        // lanes per key
     constexpr int G = 64 / LPR;        // keys per wave and load
     const int split = blockIdx.x, splits = gridDim.x, bh = blockIdx.y;
     const int b = bh / H, h = bh % H;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int chunk = lane % LPR, grp = lane / LPR;
+    if (ROWS) {
+        const int64_t n = (int64_t)rows_n[b] + rows_off;
+        n_keys = (n >= 1 && n <= n_keys) ? (int)n : 0;
+        per = ((n_keys + splits - 1) / splits + DEC_CHUNK - 1) / DEC_CHUNK * DEC_CHUNK;
+    }
     const int k0 = min(split * per, n_keys), k1 = min(k0 + per, n_keys);
 
     float qf[8];
@@ -165,13 +180,14 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16*
         for (int j = 0; j < 8; ++j) p.acc[j] = lds[w][lane][2 + j];
         merge(tot, p);
     }
-    if (splits == 1) {   // n_keys >= 1: l > 0
-        const float inv = 1.0f / tot.l;
+    if (splits == 1) {   // n_keys >= 1: l > 0; an inactive row (ROWS): l = 0, o = 0 and lse = -inf
+        const float inv = (ROWS && tot.l == 0.f) ? 0.f : 1.0f / tot.l;
         bf16x8 out;
 #pragma unroll
         for (int j = 0; j < 8; ++j) out[j] = f2bf(tot.acc[j] * inv);
         *(bf16x8*)(o + ((int64_t)bh * HS + lane * 8)) = out;
-        if (lse && lane == 0) lse[bh] = (tot.m + __builtin_amdgcn_logf(tot.l)) * 0.6931471805599453f;   // v_log_f32 is log2
+        if (lse && lane == 0)
+            lse[bh] = (ROWS && tot.l == 0.f) ? -INFINITY : (tot.m + __builtin_amdgcn_logf(tot.l)) * 0.6931471805599453f;   // v_log_f32 is log2
         return;
     }
     float* pr = part + ((int64_t)bh * splits + split) * (HS + DEC_PAD);
@@ -180,23 +196,25 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16*
     if (lane == 0) { pr[HS] = tot.m; pr[HS + 1] = tot.l; }
 }
 
-// grid B * H, HS threads: thread d sums dim d of the partials in split order against their common maximum.  At least one split holds a
-// key (n_keys >= 1), so the maximum is finite and an empty split's weight is exp2(-inf) = 0.
+// grid B * H, HS threads: thread d sums dim d of the partials in split order against their common maximum.  With a key in at least one
+// split (n_keys >= 1) the maximum is finite and an empty split's weight is exp2(-inf) = 0.  An inactive row of the rows form has no key
+// in any split: the maximum is made finite first, every weight is 0, and l = 0 gives o = 0 and lse = -inf.
 template <int HS>
 __global__ __launch_bounds__(HS) void attn_decode_combine_kernel(const float* __restrict__ part, bf16* __restrict__ o, float* __restrict__ lse, int splits) {
     const int bh = blockIdx.x, d = threadIdx.x;
     const float* pr = part + (int64_t)bh * splits * (HS + DEC_PAD);
     float m = -INFINITY;
     for (int s = 0; s < splits; ++s) m = fmaxf(m, pr[s * (HS + DEC_PAD) + HS]);
+    const float ms = m == -INFINITY ? 0.f : m;
     float l = 0.f, acc = 0.f;
     for (int s = 0; s < splits; ++s) {
         const float* p = pr + s * (HS + DEC_PAD);
-        const float w = __builtin_amdgcn_exp2f(p[HS] - m);
+        const float w = __builtin_amdgcn_exp2f(p[HS] - ms);
         l += p[HS + 1] * w;
         acc += p[d] * w;
     }
-    o[(int64_t)bh * HS + d] = f2bf(acc / l);
-    if (lse && d == 0) lse[bh] = (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;
+    o[(int64_t)bh * HS + d] = f2bf(l == 0.f ? 0.f : acc / l);
+    if (lse && d == 0) lse[bh] = l == 0.f ? -INFINITY : (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;
 }
 
 // one thread per 16 bytes: item = ((row * 2 + which) * C + column) / 8 of the k (which = 0) and v thirds of qkv
@@ -213,6 +231,41 @@ __global__ __launch_bounds__(256) void kv_cache_store_kernel(const bf16* __restr
     const int col = c8 * 8, h = col / hs, e = col % hs;
     const u32x4 v = *(const u32x4*)(qkv + row * 3 * C + (1 + which) * C + col);
     *(u32x4*)(cache + which * v_off + ((b * H + h) * T_max + pos0 + ti) * hs + e) = v;
+}
+
+// One decode step's rotate-and-store, one thread per 16 bytes of the packed qkv [B, 3C]: item = (b * 3 + third) * C / 8 + c8.  Row b at
+// position p = pos[b], 0 <= p <= max_pos (any other value: the row is left alone).  The q and k thirds are rotated in place by row p of
+// the tables, in the arithmetic of the GEMM epilogue OBTE_EPI_ROPE_QK (fp32 on the bf16 values, the same expression: the same bits);
+// the rotated k and the v go to cache position p of the item's head.
+__global__ __launch_bounds__(256) void kv_cache_rope_store_rows_kernel(bf16* __restrict__ qkv, const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                                       const int32_t* __restrict__ pos, int max_pos, bf16* __restrict__ cache, int64_t items,
+                                                                       int H, int hs, int64_t T_max, int64_t v_off) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= items) return;
+    const int C = H * hs, cpr = C / 8;             // 16-byte items per third of a row
+    const int c8 = (int)(i % cpr);
+    const int64_t rw = i / cpr;
+    const int third = (int)(rw % 3);
+    const int64_t b = rw / 3;
+    const int p = pos[b];
+    if (p < 0 || p > max_pos) return;
+    const int col = c8 * 8, h = col / hs, e = col % hs;
+    bf16* ptr = qkv + b * 3 * C + third * C + col;
+    bf16x8 v = *reinterpret_cast<const bf16x8*>(ptr);
+    if (third < 2) {
+        const f32x4 c = *reinterpret_cast<const f32x4*>(cos_t + (int64_t)p * (hs / 2) + e / 2);
+        const f32x4 sn = *reinterpret_cast<const f32x4*>(sin_t + (int64_t)p * (hs / 2) + e / 2);
+        bf16x8 r;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float xe = bf2f(v[2 * j]), xo = bf2f(v[2 * j + 1]);
+            r[2 * j] = f2bf(xe * c[j] - xo * sn[j]);
+            r[2 * j + 1] = f2bf(xe * sn[j] + xo * c[j]);
+        }
+        v = r;
+        *reinterpret_cast<bf16x8*>(ptr) = v;
+    }
+    if (third > 0) *reinterpret_cast<bf16x8*>(cache + (third - 1) * v_off + ((b * H + h) * T_max + p) * hs + e) = v;
 }
 
 bool shape_ok(int64_t B, int64_t T_max, int32_t n_head, int32_t head_dim) {
@@ -279,15 +332,74 @@ extern "C" int obte_attn_decode(const obte_bf16* q, int64_t q_ld, const obte_bf1
     const int prof = obte_prof_begin(st, 102, BH, n_keys, head_dim);   // cache bytes read = 4 * BH * n_keys * head_dim
     const dim3 grid((unsigned)splits, (unsigned)BH), block(DEC_WAVES * 64);
     if (head_dim == 128) {
-        hipLaunchKernelGGL(attn_decode_kernel<128>, grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max, v_off,
-                           (int)n_keys, per, qscale);
+        hipLaunchKernelGGL((attn_decode_kernel<128, false>), grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max,
+                           v_off, (int)n_keys, per, qscale, (const int32_t*)nullptr, 0);
         if (splits > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(BH), dim3(128), 0, st, (const float*)ws, (bf16*)o, lse, splits);
     } else {
-        hipLaunchKernelGGL(attn_decode_kernel<64>, grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max, v_off,
-                           (int)n_keys, per, qscale);
+        hipLaunchKernelGGL((attn_decode_kernel<64, false>), grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max,
+                           v_off, (int)n_keys, per, qscale, (const int32_t*)nullptr, 0);
         if (splits > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(BH), dim3(64), 0, st, (const float*)ws, (bf16*)o, lse, splits);
     }
     obte_prof_end(prof, st);
     OBTE_CHECK_LAUNCH("obte_attn_decode");
     return OBTE_OK;
+}
+
+// ---- one position / key count per row ---------------------------------------------------------------------------------------------------
+extern "C" int obte_kv_cache_rope_store_rows(obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos, int64_t max_pos, int64_t B,
+                                             int32_t n_head, int32_t head_dim, obte_bf16* cache, int64_t T_max, obte_stream s) {
+    OBTE_REQUIRE(qkv && rope_cos && rope_sin && pos && cache, "obte_kv_cache_rope_store_rows: null pointer");
+    OBTE_REQUIRE(shape_ok(B, T_max, n_head, head_dim), "obte_kv_cache_rope_store_rows: bad shape (head_dim 64 or 128)");
+    OBTE_REQUIRE(max_pos >= 0 && max_pos < T_max, "obte_kv_cache_rope_store_rows: max_pos = %lld outside [0, T_max = %lld)", (long long)max_pos, (long long)T_max);
+    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)cache | (uintptr_t)rope_cos | (uintptr_t)rope_sin) & 15) == 0 && ((uintptr_t)pos & 3) == 0,
+                 "obte_kv_cache_rope_store_rows: qkv, cache and the tables must be 16-byte aligned, pos 4-byte aligned");
+    const int64_t items = B * 3 * n_head * head_dim / 8;
+    OBTE_REQUIRE(cdiv64(items, 256) < (1ll << 31), "obte_kv_cache_rope_store_rows: too many rows for one launch");
+    hipLaunchKernelGGL(kv_cache_rope_store_rows_kernel, dim3((unsigned)cdiv64(items, 256)), dim3(256), 0, (hipStream_t)s, (bf16*)qkv, rope_cos, rope_sin, pos,
+                       (int)max_pos, (bf16*)cache, items, n_head, head_dim, T_max, B * n_head * T_max * head_dim);
+    OBTE_CHECK_LAUNCH("obte_kv_cache_rope_store_rows");
+    return OBTE_OK;
+}
+
+// obte_attn_decode_rows with row b's count read as n_keys[b] + key_off (csrc/block.cpp hands the positions and 1: no launch to form pos + 1)
+int obte_attn_decode_rows_off(const char* who, const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max,
+                              const int32_t* n_keys, int32_t key_off, int64_t max_keys, int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws,
+                              int64_t ws_bytes, obte_stream s) {
+    OBTE_REQUIRE(q && cache && o && n_keys, "%s: null pointer", who);
+    OBTE_REQUIRE(shape_ok(B, T_max, n_head, head_dim) && B * n_head <= 65535, "%s: bad shape (head_dim 64 or 128, B * n_head <= 65535)", who);
+    OBTE_REQUIRE(max_keys >= 1 && max_keys <= T_max, "%s: max_keys = %lld outside [1, T_max = %lld]", who, (long long)max_keys, (long long)T_max);
+    OBTE_REQUIRE(q_ld >= (int64_t)n_head * head_dim && q_ld % 8 == 0, "%s: q_ld must be a multiple of 8 and at least n_head * head_dim", who);
+    OBTE_REQUIRE((((uintptr_t)q | (uintptr_t)cache | (uintptr_t)o) & 15) == 0 && ((uintptr_t)n_keys & 3) == 0,
+                 "%s: q, cache and o must be 16-byte aligned, n_keys 4-byte aligned", who);
+    OBTE_REQUIRE(splits >= 0 && splits <= OBTE_ATTN_DECODE_MAX_SPLITS, "%s: splits = %d outside [0, %d]", who, splits, OBTE_ATTN_DECODE_MAX_SPLITS);
+    if (splits == 0) splits = obte_attn_decode_splits(B, n_head, head_dim, max_keys);
+    if (splits > 1) {
+        const int64_t need = B * n_head * splits * (int64_t)(head_dim + DEC_PAD) * 4;
+        OBTE_REQUIRE(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0, "%s: %d splits need a 16-byte aligned workspace of %lld bytes, got %lld", who, splits,
+                     (long long)need, (long long)(ws ? ws_bytes : 0));
+    }
+    const hipStream_t st = (hipStream_t)s;
+    const int BH = (int)(B * n_head);
+    const float qscale = scale * 1.4426950408889634f;
+    const int64_t v_off = B * n_head * T_max * head_dim;
+    const int prof = obte_prof_begin(st, 102, BH, max_keys, head_dim);   // (the bound: a row reads 4 * n_keys[b] * head_dim bytes per head)
+    const dim3 grid((unsigned)splits, (unsigned)BH), block(DEC_WAVES * 64);
+    if (head_dim == 128) {
+        hipLaunchKernelGGL((attn_decode_kernel<128, true>), grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max,
+                           v_off, (int)max_keys, 0, qscale, n_keys, key_off);
+        if (splits > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(BH), dim3(128), 0, st, (const float*)ws, (bf16*)o, lse, splits);
+    } else {
+        hipLaunchKernelGGL((attn_decode_kernel<64, true>), grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max,
+                           v_off, (int)max_keys, 0, qscale, n_keys, key_off);
+        if (splits > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(BH), dim3(64), 0, st, (const float*)ws, (bf16*)o, lse, splits);
+    }
+    obte_prof_end(prof, st);
+    OBTE_CHECK_LAUNCH(who);
+    return OBTE_OK;
+}
+
+extern "C" int obte_attn_decode_rows(const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max,
+                                     const int32_t* n_keys, int64_t max_keys, int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws,
+                                     int64_t ws_bytes, obte_stream s) {
+    return obte_attn_decode_rows_off("obte_attn_decode_rows", q, q_ld, cache, o, lse, B, T_max, n_keys, 0, max_keys, n_head, head_dim, scale, splits, ws, ws_bytes, s);
 }

@@ -486,16 +486,22 @@ struct InferAttention {
     obte_bf16* kv_cache; int64_t T_max;   // prefill and decode: the layer's cache (null: obte_block_fwd_infer)
     int64_t pos;                          // decode: the position of the new row (< 0: the attention of the call's own T positions)
     void* dec_ws; int64_t dec_ws_bytes;   // decode: obte_attn_decode's workspace
+    const int32_t* pos_rows = nullptr;    // decode, one position per row (obte_block_decode_rows): device int32 [B]; pos is then their bound,
+                                          // c_attn stays unrotated and the rotation joins the cache store (rope_cos / rope_sin: the FULL tables)
 };
 int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const InferLayout& w, int64_t M, const float* rope_cos,
                    const float* rope_sin, int64_t rope_T, const InferAttention& at, obte_stream s) {
     const int C = d->n_embd, H = d->n_head, hs = C / H;
     TRY(obte_layernorm_fwd(x, d->ln1_w, w.h1, w.mean, w.rstd, M, C, 1e-5f, s));
     obte_gemm_args qkv = xWt(w.h1, d->attn_w, w.qkv, M, 3 * C, C);
-    qkv.epilogue = OBTE_EPI_ROPE_QK; qkv.rope_cos = rope_cos; qkv.rope_sin = rope_sin; qkv.rope_T = rope_T; qkv.rope_head_dim = hs;
+    if (!at.pos_rows) { qkv.epilogue = OBTE_EPI_ROPE_QK; qkv.rope_cos = rope_cos; qkv.rope_sin = rope_sin; qkv.rope_T = rope_T; qkv.rope_head_dim = hs; }
     TRY(run(qkv, s));
     const float scale = 8.0f / (float)C;  // model.py:119
-    if (at.pos >= 0) {   // the new position of every row joins the cache, then attends over positions 0 .. pos
+    if (at.pos_rows) {   // row b at its own position: rotated and stored by one launch, then over its own pos[b] + 1 keys
+        TRY(obte_kv_cache_rope_store_rows(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.T_max, s));
+        TRY(obte_attn_decode_rows_off("obte_block_decode_rows", w.qkv, 3 * (int64_t)C, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos_rows, 1, at.pos + 1, H, hs,
+                                      scale, 0, at.dec_ws, at.dec_ws_bytes, s));
+    } else if (at.pos >= 0) {   // the new position of every row joins the cache, then attends over positions 0 .. pos
         TRY(obte_kv_cache_store(w.qkv, d->B, 1, H, hs, at.kv_cache, at.T_max, at.pos, s));
         TRY(obte_attn_decode(w.qkv, 3 * (int64_t)C, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos + 1, H, hs, scale, 0, at.dec_ws, at.dec_ws_bytes, s));
     } else {
@@ -566,6 +572,26 @@ extern "C" int obte_block_decode(const obte_block_desc* d, const obte_bf16* x, o
     const InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, dec_bytes};
     const int64_t row = pos * (hs / 2);   // the tables' row `pos`: with rope_T = 1 every row of the product is rotated by it
     return infer_sequence(d, x, y_out, w, d->B, d->rope_cos + row, d->rope_sin + row, 1, at, s);
+}
+
+extern "C" int obte_block_decode_rows(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, const int32_t* pos,
+                                      int64_t max_pos, void* ws, int64_t ws_bytes, obte_stream s) {
+    TRY(check_desc("obte_block_decode_rows", d));
+    OBTE_REQUIRE(d->T == 1, "obte_block_decode_rows: one new position per row (T = 1), got T = %lld", (long long)d->T);
+    if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
+        obte_set_error("obte_block_decode_rows: key_ranges, mask, query_bounds, out_rows and dropout_p must be NULL / 0 (the new position sees every cached one)");
+        return OBTE_EUNSUPPORTED;
+    }
+    OBTE_REQUIRE(x && y_out && kv_cache && pos && ws, "obte_block_decode_rows: null pointer");
+    OBTE_REQUIRE(max_pos >= 0 && max_pos < T_max, "obte_block_decode_rows: max_pos = %lld outside the cache's [0, %lld)", (long long)max_pos, (long long)T_max);
+    const int C = d->n_embd, H = d->n_head, hs = C / H;
+    const InferLayout w(d->B, 1, C, H, ws);
+    const int64_t dec_bytes = obte_attn_decode_ws_bytes(d->B, H, hs), need = w.total + align256(dec_bytes);
+    OBTE_REQUIRE(ws_bytes >= need, "obte_block_decode_rows: workspace of %lld bytes, obte_block_decode_ws_bytes() asks for %lld", (long long)ws_bytes,
+                 (long long)need);
+    InferAttention at = {kv_cache, T_max, max_pos, (char*)ws + w.total, dec_bytes};
+    at.pos_rows = pos;
+    return infer_sequence(d, x, y_out, w, d->B, d->rope_cos, d->rope_sin, 1, at, s);
 }
 
 extern "C" int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,

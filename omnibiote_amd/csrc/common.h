@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/omnibiote_hip.h"
+#include "../../include/omnibiote_hip_rows.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -76,6 +77,11 @@ int obte_dropout_rows_bf16(const obte_bf16* in, const obte_bf16* aux, obte_bf16*
 int obte_rope_cols_bf16(obte_bf16* x, int64_t ld, int32_t ncols, const float* cos_t, const float* sin_t, int64_t rows, int64_t T, const int32_t* pos,
                         int32_t head_dim, obte_stream s);
 int obte_rows_add_bf16(const obte_bf16* src, const int64_t* rows, obte_bf16* dst, int64_t n_rows, int32_t cols, obte_stream s);
+// obte_attn_decode_rows with row b's key count read as n_keys[b] + key_off (csrc/block.cpp hands a step's positions and 1); who: the
+// entry point named in an error
+int obte_attn_decode_rows_off(const char* who, const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max,
+                              const int32_t* n_keys, int32_t key_off, int64_t max_keys, int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws,
+                              int64_t ws_bytes, obte_stream s);
 
 // device status word (lib.cpp): pinned host memory kernels OR failure bits into; null if it could not be allocated
 int32_t* obte_status_word();

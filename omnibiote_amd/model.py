@@ -796,11 +796,49 @@ def sample_next(logits, temperature=1.0, top_k=None, generator=None):
     return torch.multinomial(probs, num_samples=1, generator=generator).squeeze(1)
 
 
+def _check_lengths(what, lengths, batch, t0):
+    """``lengths`` as a list of ``batch`` ints in [1, t0], or a ValueError naming ``what``"""
+    try:
+        lens = [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    except TypeError:
+        raise ValueError(f"OmniBioTA.{what}: lengths must be a sequence of {batch} integers") from None
+    if len(lens) != batch:
+        raise ValueError(f"OmniBioTA.{what}: {len(lens)} lengths for a batch of {batch} rows")
+    if min(lens) < 1 or max(lens) > t0:
+        raise ValueError(f"OmniBioTA.{what}: every length must lie in [1, T0 = {t0}], got {lens}")
+    return lens
+
+
+def ragged_output(idx, lengths, tokens, valid, pad_token):
+    """The result of a ragged ``generate``: row b is its prompt ``idx[b, :lengths[b]]``, then the tokens of the steps it was still
+    running at — ``tokens[b, i]`` where ``valid[b, i]``, a prefix of the row — then ``pad_token``.  idx (B, T0) int64, lengths (B,)
+    integers, tokens (B, S) int64, valid (B, S) bool.  Returns (out (B, max(lengths) + S) int64, out_lengths (B,) int64).  Ordinary torch
+    on any device, no host synchronisation beyond the width (a host integer the caller already has)."""
+    b, steps = tokens.shape
+    lens = torch.as_tensor(lengths, dtype=torch.int64).to(idx.device).view(b, 1)
+    longest = max(lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)
+    n_new = valid.sum(dim=1, keepdim=True).to(torch.int64)
+    col = torch.arange(longest + steps, device=idx.device).view(1, -1)
+    out = torch.full((b, longest + steps), int(pad_token), dtype=torch.int64, device=idx.device)
+    out[:, :longest] = torch.where(col[:, :longest] < lens, idx[:, :longest], out[:, :longest])
+    if steps > 0:
+        at = col - lens                                                 # the step whose token stands in this column
+        new = tokens.gather(1, at.clamp(0, steps - 1))
+        out = torch.where((at >= 0) & (at < n_new), new, out)
+    return out, (lens + n_new).view(b)
+
+
 class KVCache:
     """The rotated keys and the values of every layer of ``model`` for ``batch`` sequences of up to ``max_len`` positions
     (default and at most ``config.block_size``): one buffer per layer (include/omnibiote_hip.h, obte_kv_cache_bytes), the workspace of
     a decode step, and ``pos``, the number of positions filled — a host integer, the same for every row.  ``OmniBioTA.prefill``
-    starts it over (nothing is cleared: positions beyond ``pos`` are never read), ``decode_step`` advances it."""
+    starts it over (nothing is cleared: positions beyond ``pos`` are never read), ``decode_step`` advances it.
+
+    After a prefill with ``lengths`` the rows stand at different positions: ``positions`` is then an int32 (B,) device tensor, row b's
+    next position (the kernels read it there; a negative value parks a finished row: it stores nothing and attends to nothing), and
+    ``max_pos`` the host's upper bound on it; ``decode_step`` advances both.  In this mode ``pos`` says nothing about a single row: it
+    is kept equal to ``max_pos``, the positions filled in the longest row.  ``positions is None`` is the uniform mode above.  The three
+    are set together by ``prefill`` and ``decode_step``; code that sets one by hand sets the others to match."""
 
     def __init__(self, model, batch, max_len=None):
         cfg = model.config
@@ -814,6 +852,7 @@ class KVCache:
         wte = model.transformer.wte.weight
         _require_hip(wte, "KVCache")
         self.batch, self.max_len, self.pos = int(batch), max_len, 0
+        self.positions, self.max_pos = None, 0
         hs = cfg.n_embd // cfg.n_head
         self.layers = [ops.kv_cache_buffer(self.batch, max_len, cfg.n_head, hs, wte.device) for _ in model.transformer.h]
         self.decode_ws = ops.block_decode_workspace(self.batch, cfg.n_embd, cfg.n_head, wte.device)
@@ -921,9 +960,15 @@ class OmniBioTA(nn.Module):
             raise ValueError(f"OmniBioTA.{what}: the cache was built for batch size {cache.batch}, got {batch}")
 
     @torch.no_grad()
-    def prefill(self, idx, cache):
+    def prefill(self, idx, cache, lengths=None):
         """The prompt ``idx`` (B, T0) through every block under the causal mask, its keys and values left in ``cache`` (started
-        over: ``cache.pos = T0``); returns the logits of the last position, (B, vocab).  ln_f and the readout run on that row alone."""
+        over: ``cache.pos = T0``); returns the logits of the last position, (B, vocab).  ln_f and the readout run on that row alone.
+
+        ``lengths`` (a host sequence of B ints, 1 <= len_b <= T0): the prompts are right-padded, columns >= len_b of row b hold any
+        valid id.  The same kernels run over T0 — under the causal mask a real position never sees a later one, so the padding reaches
+        nothing, and the cache positions it fills are overwritten by the row's own new tokens before they are read.  Row b's logits
+        come from position len_b - 1; ``cache.positions`` = lengths and ``cache.max_pos`` = ``cache.pos`` = max(lengths) put ``decode_step`` on the
+        one-position-per-row path."""
         if idx.dim() != 2:
             raise ValueError(f"OmniBioTA.prefill: idx must be (B, T0), got {tuple(idx.shape)}")
         b, t = idx.shape
@@ -932,6 +977,7 @@ class OmniBioTA(nn.Module):
             raise ValueError("OmniBioTA.prefill: the prompt is empty")
         if t > cache.max_len:
             raise ValueError(f"OmniBioTA.prefill: a prompt of {t} tokens does not fit the cache's {cache.max_len} positions")
+        lens = None if lengths is None else _check_lengths("prefill", lengths, b, t)
         wte = self.transformer.wte.weight
         _require_hip(wte, "OmniBioTA")
         if not idx.is_cuda:
@@ -942,24 +988,41 @@ class OmniBioTA(nn.Module):
         for block, kv in zip(self.transformer.h, cache.layers):
             ops.block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, kv, cache.max_len, ws=ws, out=x)
         cache.pos = t
-        return self.lm_head(self.transformer.ln_f(x[:, -1].contiguous()))
+        if lens is None:
+            cache.positions, cache.max_pos = None, 0
+            return self.lm_head(self.transformer.ln_f(x[:, -1].contiguous()))
+        cache.positions, cache.max_pos = torch.tensor(lens, dtype=torch.int32, device=idx.device), max(lens)
+        cache.pos = cache.max_pos                                       # (kept in step with max_pos while positions is set)
+        last = x[torch.arange(b, device=idx.device), (cache.positions - 1).long()]          # (B, C): row b at its own last position
+        return self.lm_head(self.transformer.ln_f(last.contiguous()))
 
     @torch.no_grad()
     def decode_step(self, tokens, cache):
         """One new token per row, ``tokens`` (B,) int64, at position ``cache.pos`` of every row: its keys and values join the cache
-        and the logits of the token after it come back, (B, vocab).  O(1) in projections, one read of the cache per layer."""
+        and the logits of the token after it come back, (B, vocab).  O(1) in projections, one read of the cache per layer.
+        After a prefill with ``lengths`` row b's token goes to position ``cache.positions[b]``, read on the device; the positions of
+        the rows not parked (>= 0) then advance by one there, ``cache.max_pos`` on the host.  A parked row's logits mean nothing."""
         if tokens.dim() != 1:
             raise ValueError(f"OmniBioTA.decode_step: tokens must be (B,), got {tuple(tokens.shape)}")
         b = tokens.shape[0]
         self._check_generation("decode_step", b, cache)
         if cache.pos == 0:
             raise ValueError("OmniBioTA.decode_step: the cache is empty: prefill a prompt first")
-        if cache.pos >= cache.max_len:
+        rows = cache.positions is not None
+        if (cache.max_pos if rows else cache.pos) >= cache.max_len:
             raise ValueError(f"OmniBioTA.decode_step: the cache's {cache.max_len} positions are full")
         wte = self.transformer.wte.weight
         if not tokens.is_cuda:
             raise RuntimeError("OmniBioTA.decode_step: tokens must be on the GPU")
         x = ops.embedding_fwd(tokens.contiguous(), wte)
+        if rows:
+            for block, kv in zip(self.transformer.h, cache.layers):
+                ops.block_decode_rows(x, self._block_params(block), block.attn.rope(), self.config.n_head, kv, cache.max_len, cache.positions,
+                                      cache.max_pos, ws=cache.decode_ws, out=x)
+            cache.positions = cache.positions + (cache.positions >= 0)      # int32 + bool: int32 (a new tensor: the launches above read the old one)
+            cache.max_pos += 1
+            cache.pos = cache.max_pos
+            return self.lm_head(self.transformer.ln_f(x))
         for block, kv in zip(self.transformer.h, cache.layers):
             ops.block_decode(x, self._block_params(block), block.attn.rope(), self.config.n_head, kv, cache.max_len, cache.pos,
                              ws=cache.decode_ws, out=x)
@@ -967,18 +1030,27 @@ class OmniBioTA(nn.Module):
         return self.lm_head(self.transformer.ln_f(x))
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None):
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None, lengths=None, pad_token=None):
         """nanoGPT's generate(): ``idx`` (B, T0) int64 continued by up to ``max_new_tokens`` sampled tokens (``sample_next``); returns
         (B, T0 + n) int64.  The prompt runs once (``prefill``), every new token costs one ``decode_step``.  Where nanoGPT crops the
         context to block_size, this raises: T0 + max_new_tokens must fit.  ``eos_token``: a row that has produced it keeps producing
         it, and generation stops once every row has — the loop's only host synchronisation (none when ``eos_token is None``).
-        Dropout is not applied, whatever ``self.training`` says."""
+        Dropout is not applied, whatever ``self.training`` says.
+
+        ``lengths`` (a host sequence of B ints, 1 <= len_b <= T0): prompts of different lengths, right-padded in ``idx``.  Every row
+        gets up to ``max_new_tokens`` new tokens directly behind its own prompt; max(lengths) + max_new_tokens must fit block_size.
+        Returns ``(out, out_lengths)``: out (B, max(lengths) + steps taken) int64, row b its prompt, its new tokens, then ``pad_token``
+        (default: ``eos_token`` if given, else 0); out_lengths (B,) int64.  With ``eos_token`` a row that produced it is parked — its
+        out_lengths ends with the EOS — and the loop stops once every row is: the same single host synchronisation as above."""
         self._check_generation("generate", idx.shape[0] if idx.dim() == 2 else 0)
         if idx.dim() != 2:
             raise ValueError(f"OmniBioTA.generate: idx must be (B, T0), got {tuple(idx.shape)}")
         b, t0 = idx.shape
         if t0 == 0:
             raise ValueError("OmniBioTA.generate: the prompt is empty")
+        if lengths is not None:
+            return self._generate_ragged(idx, _check_lengths("generate", lengths, b, t0), max_new_tokens, temperature, top_k, generator, eos_token,
+                                         pad_token)
         if max_new_tokens < 0 or t0 + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {t0} prompt tokens + {max_new_tokens} new ones exceed block_size = {self.config.block_size}")
         if max_new_tokens == 0:
@@ -998,6 +1070,34 @@ class OmniBioTA(nn.Module):
                 break
             logits = self.decode_step(nxt, cache)
         return torch.cat(out, dim=1)
+
+    def _generate_ragged(self, idx, lens, max_new_tokens, temperature, top_k, generator, eos_token, pad_token):
+        longest = max(lens)
+        if max_new_tokens < 0 or longest + max_new_tokens > self.config.block_size:
+            raise ValueError(f"OmniBioTA.generate: {longest} prompt tokens (the longest row) + {max_new_tokens} new ones exceed "
+                             f"block_size = {self.config.block_size}")
+        pad = pad_token if pad_token is not None else (eos_token if eos_token is not None else 0)
+        idx = idx[:, :longest]                                          # columns every row counts as padding
+        b = idx.shape[0]
+        if max_new_tokens == 0:
+            none = torch.zeros((b, 0), dtype=torch.int64, device=idx.device)
+            return ragged_output(idx, lens, none, none.bool(), pad)
+        cache = KVCache(self, b, longest + max_new_tokens)
+        logits = self.prefill(idx, cache, lengths=lens)
+        tokens, valid = [], []
+        done = torch.zeros(b, dtype=torch.bool, device=idx.device)
+        for i in range(max_new_tokens):
+            nxt = sample_next(logits, temperature, top_k, generator)
+            tokens.append(nxt)
+            valid.append(~done)                                         # a row's token counts if the row was running when it was drawn
+            if eos_token is not None:
+                done = done | (nxt == eos_token)
+            if i + 1 == max_new_tokens or (eos_token is not None and bool(done.all())):
+                break
+            if eos_token is not None:                                   # park the finished rows: they store nothing and read nothing
+                cache.positions = torch.where(done, torch.full_like(cache.positions, -1), cache.positions)
+            logits = self.decode_step(nxt, cache)
+        return ragged_output(idx, lens, torch.stack(tokens, dim=1), torch.stack(valid, dim=1), pad)
 
 
 def next_token_loss(logits, idx):

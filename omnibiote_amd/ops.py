@@ -781,6 +781,63 @@ def block_decode(x, params, rope, H, cache, T_max, pos, ws=None, out=None):
     return y
 
 
+# ---- one cache position per row: a batch whose rows stand at different positions (include/omnibiote_hip_rows.h, the row convention) ----
+def _need_rows(t, name, B):
+    _need(t, name, torch.int32)
+    if t.shape != (B,):
+        raise ValueError(f"{name}: expected shape ({B},), got {tuple(t.shape)}")
+
+
+def kv_cache_rope_store_rows(qkv, rope, pos, max_pos, B, H, hs, cache, T_max):
+    """One decode step's rotate-and-store (obte_kv_cache_rope_store_rows): the q and k thirds of row b of the unrotated packed qkv
+    [B, 3C] are rotated in place by row pos[b] of the FULL tables, the rotated k and the v written to cache position pos[b].  pos: int32
+    (B,) on the device; a row whose value lies outside [0, max_pos] is left alone."""
+    _need(qkv, "qkv"); _need(cache, "cache"); _need_rows(pos, "pos", B)
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert qkv.numel() == B * 3 * H * hs and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, hs)
+    assert rope[0].shape[0] > max_pos and rope[1].shape[0] > max_pos
+    L.check(L.lib().obte_kv_cache_rope_store_rows(_ptr(qkv), _ptr(rope[0]), _ptr(rope[1]), _ptr(pos), int(max_pos), B, H, hs, _ptr(cache), T_max,
+                                                  _stream()), "obte_kv_cache_rope_store_rows")
+    return qkv
+
+
+def attn_decode_rows(q, cache, B, T_max, n_keys, max_keys, H, hs, scale, splits=0, q_ld=None, ws=None):
+    """attn_decode with one key count per row (obte_attn_decode_rows): n_keys int32 (B,) on the device, row b over cache positions
+    [0, n_keys[b]); a row whose count lies outside [1, max_keys] gives zeros and lse = -inf.  splits = 0: the library's choice at max_keys."""
+    _need(q, "q"); _need(cache, "cache"); _need_rows(n_keys, "n_keys", B)
+    q_ld = q.shape[-1] if q_ld is None else q_ld
+    assert q.numel() >= (B - 1) * q_ld + H * hs and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, hs)
+    o = torch.empty((B, H * hs), dtype=bf16, device=q.device)
+    lse = torch.empty((B, H), dtype=torch.float32, device=q.device)
+    if ws is None:
+        ws = torch.empty(int(L.lib().obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=q.device)
+    L.check(L.lib().obte_attn_decode_rows(_ptr(q), q_ld, _ptr(cache), _ptr(o), _ptr(lse), B, T_max, _ptr(n_keys), int(max_keys), H, hs, float(scale),
+                                          int(splits), _ptr(ws), ws.numel(), _stream()), "obte_attn_decode_rows")
+    return o, lse
+
+
+def block_decode_rows(x, params, rope, H, cache, T_max, pos, max_pos, ws=None, out=None):
+    """block_decode with row b at position pos[b] (obte_block_decode_rows): pos int32 (B,) on the device, read there; max_pos the host's
+    bound on it (a row outside [0, max_pos] stores nothing and attends to nothing).  rope: the FULL tables.  out may be x itself."""
+    _need(x, "x"); _need(cache, "cache")
+    B, Cc = x.shape
+    _need_rows(pos, "pos", B)
+    for i, w in enumerate(params):
+        _need(w, f"param{i}")
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert rope[0].shape[0] > max_pos and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, Cc // H)
+    if ws is None:
+        ws = block_decode_workspace(B, Cc, H, x.device)
+    else:
+        _need(ws, "ws", torch.uint8)
+    y = torch.empty_like(x) if out is None else out
+    _need(y, "out"); assert y.shape == x.shape
+    d = _block_desc(B, 1, Cc, H, params, rope, MaskSpec())
+    L.check(L.lib().obte_block_decode_rows(C.byref(d), _ptr(x), _ptr(y), _ptr(cache), T_max, _ptr(pos), int(max_pos), _ptr(ws), ws.numel(), _stream()),
+            "obte_block_decode_rows")
+    return y
+
+
 def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None, dropout_p=0.0, dropout_seed=0, ln_partials=None,
               ln_partial_mode=0, out_rows=None, dy_masked=None, dx_mask_seed=None, acc32=None, acc32_mode=0):
     """accumulate_into: optional list of 6 tensors-or-None (same order as params).  When the four matrix entries are all

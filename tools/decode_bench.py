@@ -13,6 +13,13 @@ For every batch size B and context length ctx (the new token attends over ctx po
 One JSON line per (B, ctx).
 
     python tools/decode_bench.py [--batches 1,8,64] [--contexts 128,1024,2048] [--rounds 5] [--steps 300]
+
+--ragged: the one-position-per-row step (a cache prefilled with ``lengths``: obte_block_decode_rows) instead of the above, at
+B x ctx in {8 x 2048, 64 x 2048} unless --batches / --contexts say otherwise.  Two contenders alternate in one process over the same
+windows and rounds: the rows path with every row at position ctx - 1, and the uniform path at that position (the same cache, the same
+token).  Then one ragged batch, the rows' positions spread evenly over [ctx / 4, ctx).  One JSON line per (B, ctx).
+
+    python tools/decode_bench.py --ragged [--rounds 5] [--steps 300]
 """
 import argparse
 import contextlib
@@ -94,6 +101,42 @@ def token_time(m, B, ctx, rounds, steps, baseline_ms, dev):
     return us, cache, last, n_full
 
 
+def ragged_time(m, B, ctx, rounds, steps, dev):
+    from omnibiote_amd.model import KVCache
+    g = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    idx = torch.randint(4, m.config.vocab_size, (B, ctx), device=dev, generator=g)
+    cache = KVCache(m, B, ctx)
+    m.prefill(idx[:, :ctx - 1], cache)
+    last = idx[:, -1].contiguous()
+    equal = torch.full((B,), ctx - 1, dtype=torch.int32, device=dev)
+    spread = torch.linspace(ctx // 4, ctx - 1, B, device=dev).to(torch.int32)
+
+    def uniform():                   # the same position every time: the context stays ctx long
+        cache.positions, cache.max_pos, cache.pos = None, 0, ctx - 1
+        m.decode_step(last, cache)
+
+    def rows(at):
+        def step():
+            cache.positions, cache.max_pos, cache.pos = at, ctx - 1, ctx - 1
+            m.decode_step(last, cache)
+        return step
+    legs = {"rows_equal": rows(equal), "uniform": uniform}
+    for fn in list(legs.values()) + [rows(spread)]:
+        for _ in range(3):
+            fn()
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for leg in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            us[leg].append(timed(legs[leg], steps))
+    us["rows_spread"] = [timed(rows(spread), steps) for _ in range(rounds)]
+    u = us["uniform"]
+    gap = statistics.median(us["rows_equal"]) - statistics.median(u)
+    return {"B": B, "context": ctx, "windows": {"decode_steps": steps, "rounds": rounds},
+            "us_per_token": {k: summary(v, 1) for k, v in us.items()},
+            "rows_equal_minus_uniform_us": round(gap, 1), "uniform_spread_us": round(max(u) - min(u), 1),
+            "spread_positions": [int(spread.min()), int(spread.max())]}
+
+
 def attention_alone(m, cache, B, ctx, rounds, steps, sweep, dev):
     from omnibiote_amd import _lib
     H, C = m.config.n_head, m.config.n_embd
@@ -156,8 +199,9 @@ def step_split(m, cache, last, ctx, n_steps):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--batches", default="1,8,64")
-    p.add_argument("--contexts", default="128,1024,2048")
+    p.add_argument("--batches", default=None, help="default 1,8,64 (--ragged: 8,64)")
+    p.add_argument("--contexts", default=None, help="default 128,1024,2048 (--ragged: 2048)")
+    p.add_argument("--ragged", action="store_true", help="the one-position-per-row step against the uniform step")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300, help="decode steps (and attention calls) per timed window")
     p.add_argument("--baseline_ms", type=float, default=400.0, help="the full forward's window: as many calls as fit, at least 3")
@@ -165,11 +209,16 @@ def main():
     a = p.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
-    contexts = [int(c) for c in a.contexts.split(",")]
+    contexts = [int(c) for c in (a.contexts or ("2048" if a.ragged else "128,1024,2048")).split(",")]
+    batches = [int(b) for b in (a.batches or ("8,64" if a.ragged else "1,8,64")).split(",")]
     m = build(max(contexts), dev)
     sweep = [int(s) for s in a.sweep.split(",")]
-    for B in [int(b) for b in a.batches.split(",")]:
+    for B in batches:
         for ctx in contexts:
+            if a.ragged:
+                print(json.dumps(ragged_time(m, B, ctx, a.rounds, a.steps, dev)), flush=True)
+                torch.cuda.empty_cache()
+                continue
             us, cache, last, n_full = token_time(m, B, ctx, a.rounds, a.steps, a.baseline_ms, dev)
             d, f = statistics.median(us["decode_step"]), statistics.median(us["full_forward"])
             out = {"B": B, "context": ctx, "windows": {"decode_steps": a.steps, "full_forwards": n_full, "rounds": a.rounds},
