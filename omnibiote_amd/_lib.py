@@ -170,6 +170,14 @@ SYMBOLS_ROWS = {
                                          c_stream]),
 }
 
+# the weight-streaming product for small M (include/omnibiote_hip_small_m.h): again a table of its own
+SYMBOLS_SMALL_M = {
+    "obte_linear_small_m_bf16": (C.c_int, [C.POINTER(GemmArgs), c_stream]),
+    "obte_small_m_max_set": (C.c_int, [C.c_int]),
+    "obte_small_m_max": (C.c_int, []),
+}
+SMALL_M_MAX_ROWS = 64   # the largest M obte_linear_small_m_bf16 takes
+
 _lib = None
 _lock = threading.Lock()
 
@@ -197,7 +205,7 @@ def lib():
                 l = C.CDLL(LIB_PATH)
             except OSError as e:
                 raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-            for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()):
+            for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

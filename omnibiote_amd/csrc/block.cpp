@@ -492,6 +492,10 @@ struct InferAttention {
 int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const InferLayout& w, int64_t M, const float* rope_cos,
                    const float* rope_sin, int64_t rope_T, const InferAttention& at, obte_stream s) {
     const int C = d->n_embd, H = d->n_head, hs = C / H;
+    // a decode call (M = B rows) of at most obte_small_m_max() rows: its four products on the weight-streaming kernel (gemm_small_m.hip),
+    // the same epilogues; every other call on the tile structures at every M
+    const bool stream_w = (at.pos >= 0 || at.pos_rows) && M <= obte_small_m_max();
+    auto run = [stream_w](const obte_gemm_args& g, obte_stream st) { return stream_w ? obte_linear_small_m_bf16(&g, st) : obte_gemm_bf16_ws(&g, nullptr, 0, st); };
     TRY(obte_layernorm_fwd(x, d->ln1_w, w.h1, w.mean, w.rstd, M, C, 1e-5f, s));
     obte_gemm_args qkv = xWt(w.h1, d->attn_w, w.qkv, M, 3 * C, C);
     if (!at.pos_rows) { qkv.epilogue = OBTE_EPI_ROPE_QK; qkv.rope_cos = rope_cos; qkv.rope_sin = rope_sin; qkv.rope_T = rope_T; qkv.rope_head_dim = hs; }

@@ -959,6 +959,14 @@ class OmniBioTA(nn.Module):
         if cache is not None and cache.batch != batch:
             raise ValueError(f"OmniBioTA.{what}: the cache was built for batch size {cache.batch}, got {batch}")
 
+    def _readout_rows(self, x):
+        """The readout of a generation step's (B, C) rows: at most ops' small_m_max of them, bf16 on the GPU, through the
+        weight-streaming product with MuReadout.forward's alpha; anything else through the module."""
+        w = self.lm_head.weight
+        if x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.shape[0] <= L.lib().obte_small_m_max():
+            return ops.linear_small_m(x, w, alpha=float(self.lm_head.output_mult) / float(self.lm_head.width_mult()))
+        return self.lm_head(x)
+
     @torch.no_grad()
     def prefill(self, idx, cache, lengths=None):
         """The prompt ``idx`` (B, T0) through every block under the causal mask, its keys and values left in ``cache`` (started
@@ -990,11 +998,11 @@ class OmniBioTA(nn.Module):
         cache.pos = t
         if lens is None:
             cache.positions, cache.max_pos = None, 0
-            return self.lm_head(self.transformer.ln_f(x[:, -1].contiguous()))
+            return self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()))
         cache.positions, cache.max_pos = torch.tensor(lens, dtype=torch.int32, device=idx.device), max(lens)
         cache.pos = cache.max_pos                                       # (kept in step with max_pos while positions is set)
         last = x[torch.arange(b, device=idx.device), (cache.positions - 1).long()]          # (B, C): row b at its own last position
-        return self.lm_head(self.transformer.ln_f(last.contiguous()))
+        return self._readout_rows(self.transformer.ln_f(last.contiguous()))
 
     @torch.no_grad()
     def decode_step(self, tokens, cache):
@@ -1022,12 +1030,12 @@ class OmniBioTA(nn.Module):
             cache.positions = cache.positions + (cache.positions >= 0)      # int32 + bool: int32 (a new tensor: the launches above read the old one)
             cache.max_pos += 1
             cache.pos = cache.max_pos
-            return self.lm_head(self.transformer.ln_f(x))
+            return self._readout_rows(self.transformer.ln_f(x))
         for block, kv in zip(self.transformer.h, cache.layers):
             ops.block_decode(x, self._block_params(block), block.attn.rope(), self.config.n_head, kv, cache.max_len, cache.pos,
                              ws=cache.decode_ws, out=x)
         cache.pos += 1
-        return self.lm_head(self.transformer.ln_f(x))
+        return self._readout_rows(self.transformer.ln_f(x))
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None, lengths=None, pad_token=None):

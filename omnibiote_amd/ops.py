@@ -6,6 +6,7 @@ stream.  Nothing here synchronises the host.  PyTorch is plumbing only: allocati
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional, Tuple
@@ -223,6 +224,42 @@ def linear_fwd(x2d, w, epilogue=L.EPI_NONE, aux=None, alpha=1.0, dropout=None):
     N = w.shape[0]
     assert w.shape[1] == K
     return gemm(x2d, w, M, N, K, True, True, epilogue, aux, alpha, dropout=dropout)
+
+
+def linear_small_m(x2d, w, epilogue=L.EPI_NONE, aux=None, alpha=1.0, rope=None, out=None):
+    """y = epilogue(alpha * x W^T) for x [M, K] of 1 <= M <= 64 rows, W [N, K] (obte_linear_small_m_bf16): the weight-streaming kernel,
+    which reads W once.  Epilogues EPI_NONE, EPI_ADD (aux [M, N], may be ``out``), EPI_GELU_ACT, EPI_ROPE_QK (rope = (cos, sin, T,
+    head_dim)), in gemm()'s arithmetic.  x2d may be a row-strided view (stride 1 along K); so may ``out`` and ``aux``, with ONE row
+    stride between them, a multiple of 8."""
+    _need(x2d, "x", contiguous=False); _need(w, "w")
+    M, K = x2d.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and x2d.stride(1) == 1
+    d = out if out is not None else torch.empty((M, N), dtype=bf16, device=x2d.device)
+    _need(d, "out", contiguous=False); assert d.shape == (M, N) and d.stride(1) == 1
+    if epilogue == L.EPI_ADD:
+        _need(aux, "aux", contiguous=False); assert aux.shape == (M, N) and aux.stride(1) == 1 and (M == 1 or aux.stride(0) == d.stride(0))
+    g = L.GemmArgs(_ptr(x2d), _ptr(w), _ptr(d), _ptr(aux), None, M, N, K, x2d.stride(0) if M > 1 else K, K, d.stride(0) if M > 1 else N,
+                   1, 1, epilogue, float(alpha), 0.0, 0, 0)
+    if epilogue == L.EPI_ROPE_QK:
+        cos, sin, rT, rhs = rope
+        _need(cos, "cos", torch.float32); _need(sin, "sin", torch.float32)
+        assert cos.shape[0] >= rT and cos.shape[-1] == rhs // 2
+        g.rope_cos, g.rope_sin, g.rope_T, g.rope_head_dim = _ptr(cos), _ptr(sin), rT, rhs
+    L.check(L.lib().obte_linear_small_m_bf16(C.byref(g), _stream()), "obte_linear_small_m_bf16")
+    return d
+
+
+@contextlib.contextmanager
+def small_m_max(m: int):
+    """Within the block, decode steps and last-position readouts of at most ``m`` rows (0..64, 0: none) take the weight-streaming
+    product (obte_small_m_max_set: process-wide); the previous value comes back on exit.  The default is 64, or 0 under OBTE_SMALL_M=0."""
+    prev = L.lib().obte_small_m_max_set(int(m))
+    L.check(min(prev, 0), "obte_small_m_max_set")
+    try:
+        yield
+    finally:
+        L.lib().obte_small_m_max_set(prev)
 
 
 def dropout(x, p, seed, site=L.SITE_USER, out=None):

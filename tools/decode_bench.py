@@ -20,6 +20,16 @@ windows and rounds: the rows path with every row at position ctx - 1, and the un
 token).  Then one ragged batch, the rows' positions spread evenly over [ctx / 4, ctx).  One JSON line per (B, ctx).
 
     python tools/decode_bench.py --ragged [--rounds 5] [--steps 300]
+
+--small-m: the weight-streaming product for M <= 64 (obte_linear_small_m_bf16) against the tile structures (obte_gemm_bf16), both
+alternating in one process over the same windows and rounds.  (a) the product alone, the C entry points on preallocated buffers: the
+five shapes of the small config at M = 1, 8, 16, 32, 64, each call on the next of eight distinct copies of a block weight (three of the
+readout's 134 MB) as a decode step walks its layers; `served_from` says whether the set of copies exceeds the 256 MB Infinity Cache, and
+the readout's bytes over its time are given as a share of 6.3 TB/s.  One JSON line per shape.  (b) decode_step with small_m_max at the
+library's default against 0 at B x ctx in {1 x 2048, 8 x 2048, 64 x 1024, 64 x 2048}, the rows step at 8 x 2048 (every row at ctx - 1)
+the same way, and the launch profiler's split of a step on the new path.  One JSON line per (B, ctx).
+
+    python tools/decode_bench.py --small-m [--rounds 5] [--steps 300]
 """
 import argparse
 import contextlib
@@ -197,11 +207,95 @@ def step_split(m, cache, last, ctx, n_steps):
                                                   "rest": round(rest / total, 3)}}
 
 
+SMALL_M_SHAPES = (("c_attn", 3072, 1024, 8), ("proj", 1024, 1024, 8), ("fc", 4096, 1024, 8), ("mlp", 1024, 4096, 8), ("readout", 65536, 1024, 3))
+SMALL_M_ROWS = (1, 8, 16, 32, 64)
+
+
+def small_m_products(rounds, steps, dev):
+    import ctypes as C
+    from omnibiote_amd import _lib
+    lib, stream = _lib.lib(), torch.cuda.current_stream().cuda_stream
+    gen = torch.Generator(device=dev).manual_seed(5)
+    for name, N, K, copies in SMALL_M_SHAPES:
+        ws = [torch.randn(N, K, device=dev, generator=gen).mul_(0.02).to(torch.bfloat16) for _ in range(copies)]
+        set_bytes = copies * N * K * 2
+        out = {"product": name, "N": N, "K": K, "weight_copies": copies, "set_bytes": set_bytes,
+               "served_from": "HBM" if set_bytes > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)", "M": {}}
+        for M in SMALL_M_ROWS:
+            x = torch.randn(M, K, device=dev, generator=gen).to(torch.bfloat16)
+            d = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+            args = [_lib.GemmArgs(x.data_ptr(), w.data_ptr(), d.data_ptr(), None, None, M, N, K, K, K, N, 1, 1, _lib.EPI_NONE, 1.0, 0.0, 0, 0) for w in ws]
+            state = {"i": 0}
+
+            def call(fn, what):
+                state["i"] += 1
+                rc = fn(C.byref(args[state["i"] % copies]), stream)
+                if rc != 0:
+                    _lib.check(rc, what)
+            legs = {"small_m": lambda: call(lib.obte_linear_small_m_bf16, "obte_linear_small_m_bf16"), "tile": lambda: call(lib.obte_gemm_bf16, "obte_gemm_bf16")}
+            for fn in legs.values():
+                for _ in range(8):
+                    fn()
+            us = {k: [] for k in legs}
+            for r in range(rounds):
+                for leg in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+                    us[leg].append(timed(legs[leg], steps))
+            med = {k: statistics.median(v) for k, v in us.items()}
+            row = {"us": {k: summary(v) for k, v in us.items()}, "tile_over_small_m": round(med["tile"] / med["small_m"], 2),
+                   "small_m_minus_tile_us": round(med["small_m"] - med["tile"], 2), "tile_spread_us": round(max(us["tile"]) - min(us["tile"]), 2),
+                   "weight_bytes_share_of_6.3TBps": round(N * K * 2 / (med["small_m"] * 1e-6) / HBM_RATE, 3)}
+            out["M"][str(M)] = row
+        print(json.dumps(out), flush=True)
+        del ws
+        torch.cuda.empty_cache()
+
+
+def small_m_tokens(m, B, ctx, rounds, steps, dev, ragged=False):
+    """decode_step at the library's default small_m_max against 0, alternating; then the profiler's split of a step on the default"""
+    from omnibiote_amd import _lib, ops
+    from omnibiote_amd.model import KVCache
+    default = _lib.lib().obte_small_m_max()
+    g = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    idx = torch.randint(4, m.config.vocab_size, (B, ctx), device=dev, generator=g)
+    cache = KVCache(m, B, ctx)
+    m.prefill(idx[:, :ctx - 1], cache)
+    last = idx[:, -1].contiguous()
+    equal = torch.full((B,), ctx - 1, dtype=torch.int32, device=dev)
+
+    def step():                      # the same position every time: the context stays ctx long
+        cache.positions, cache.max_pos, cache.pos = (equal, ctx - 1, ctx - 1) if ragged else (None, 0, ctx - 1)
+        m.decode_step(last, cache)
+
+    def under(limit):
+        def leg():
+            with ops.small_m_max(limit):
+                return timed(step, steps)
+        return leg
+    legs = {"small_m_default": under(default), "small_m_0": under(0)}
+    for limit in (default, 0):
+        with ops.small_m_max(limit):
+            for _ in range(3):
+                step()
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for leg in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            us[leg].append(legs[leg]())
+    med = {k: statistics.median(v) for k, v in us.items()}
+    out = {"B": B, "context": ctx, "step": "rows (every row at ctx - 1)" if ragged else "uniform", "small_m_max_default": default,
+           "windows": {"decode_steps": steps, "rounds": rounds}, "us_per_token": {k: summary(v, 1) for k, v in us.items()},
+           "off_over_default": round(med["small_m_0"] / med["small_m_default"], 2),
+           "tokens_per_s_default": round(B / med["small_m_default"] * 1e6)}
+    if not ragged:
+        out["step_split_default"] = step_split(m, cache, last, ctx, 20)
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batches", default=None, help="default 1,8,64 (--ragged: 8,64)")
     p.add_argument("--contexts", default=None, help="default 128,1024,2048 (--ragged: 2048)")
     p.add_argument("--ragged", action="store_true", help="the one-position-per-row step against the uniform step")
+    p.add_argument("--small-m", action="store_true", help="the weight-streaming product against the tile structures: alone, and in a decode step")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300, help="decode steps (and attention calls) per timed window")
     p.add_argument("--baseline_ms", type=float, default=400.0, help="the full forward's window: as many calls as fit, at least 3")
@@ -209,6 +303,13 @@ def main():
     a = p.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
+    if a.small_m:
+        small_m_products(a.rounds, a.steps, dev)
+        m = build(2048, dev)
+        for B, ctx, ragged in ((1, 2048, False), (8, 2048, False), (8, 2048, True), (64, 1024, False), (64, 2048, False)):
+            print(json.dumps(small_m_tokens(m, B, ctx, a.rounds, a.steps, dev, ragged)), flush=True)
+            torch.cuda.empty_cache()
+        return
     contexts = [int(c) for c in (a.contexts or ("2048" if a.ragged else "128,1024,2048")).split(",")]
     batches = [int(b) for b in (a.batches or ("8,64" if a.ragged else "1,8,64")).split(",")]
     m = build(max(contexts), dev)
