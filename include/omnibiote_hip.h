@@ -9,6 +9,15 @@
  *     caller's stream (a hipStream_t passed as void*; NULL = the null stream).
  *   - bf16 tensors are passed as uint16_t* (bit pattern of bfloat16), dense row-major unless a stride
  *     argument says otherwise.  "rows" always means tokens (B*T).
+ *   - alignment: the kernels move 16 bytes per lane.  Every bf16 buffer (inputs, outputs, each tensor of a multi-tensor call)
+ *     must start on a 16-byte boundary, and with it every row (hence cols / ld % 8 == 0).  So must the fp32 buffers that are
+ *     accessed four values at a time: the RoPE tables of obte_rope_qk_inplace and of OBTE_EPI_ROPE_QK, every acc32 buffer, the
+ *     split-K and embedding-backward workspaces, the attention backward's scratch, the fp32 master weights and moments.  8 bytes
+ *     for the tables written or read as (start, end) pairs by the integer prelude (obte_key_ranges_from_tokens,
+ *     obte_causal_bounds) and for the RoPE tables of obte_attn_bwd.  Every other fp32 / integer buffer (statistics, lse, delta, losses,
+ *     the range tables as the attention kernels read them, a dense mask) needs its element's alignment only; larger
+ *     requirements (a 256-byte aligned workspace) are stated where they apply.  A pointer that misses its alignment is refused
+ *     with OBTE_EINVAL before anything is launched, and obte_last_error() names the argument.
  *   - re-entrant: callable from any thread (autograd's backward workers call in without the GIL).  Process-wide state is
  *     the thread-local error string plus two mutex-protected tables: the tuned GEMM plan table (obte_gemm_plan_set /
  *     _clear; read by every GEMM launch) and the opt-in launch profiler's records (obte_profile_*).  Nothing else persists

@@ -1075,6 +1075,8 @@ extern "C" int obte_attn_fwd(const obte_attn_fwd_args* a, obte_stream s) {
     int rc = check_common("obte_attn_fwd", a->qkv, a->B, a->T, a->n_head, a->head_dim, a->key_ranges, a->mask);
     if (rc) return rc;
     OBTE_REQUIRE(a->o && a->lse, "obte_attn_fwd: null output");
+    OBTE_REQUIRE_ALIGNED("obte_attn_fwd", a->qkv, "qkv", 16);
+    OBTE_REQUIRE_ALIGNED("obte_attn_fwd", a->o, "o", 16);
     AttnParams p = {};
     p.qkv = (const bf16*)a->qkv; p.o = (bf16*)a->o; p.lse = a->lse;
     p.key_ranges = a->key_ranges; p.mask = (const bf16*)a->mask; p.mask_sb = a->mask_sb; p.mask_sh = a->mask_sh; p.mask_sq = a->mask_sq;
@@ -1118,6 +1120,13 @@ static int attn_bwd_impl(const obte_attn_bwd_args* a, int delta_ready, obte_stre
     if (rc) return rc;
     OBTE_REQUIRE(a->o && a->d_o && a->lse && a->delta && a->dqkv, "obte_attn_bwd: null pointer");
     OBTE_REQUIRE((a->rope_cos == nullptr) == (a->rope_sin == nullptr), "obte_attn_bwd: pass both RoPE tables or neither");
+    OBTE_REQUIRE_ALIGNED("obte_attn_bwd", a->qkv, "qkv", 16);
+    OBTE_REQUIRE_ALIGNED("obte_attn_bwd", a->o, "o", 16);
+    OBTE_REQUIRE_ALIGNED("obte_attn_bwd", a->d_o, "d_o", 16);
+    OBTE_REQUIRE_ALIGNED("obte_attn_bwd", a->dqkv, "dqkv", 16);
+    OBTE_REQUIRE_ALIGNED("obte_attn_bwd", a->ws, "ws", 16);
+    OBTE_REQUIRE_ALIGNED("obte_attn_bwd", a->rope_cos, "rope_cos", 8);
+    OBTE_REQUIRE_ALIGNED("obte_attn_bwd", a->rope_sin, "rope_sin", 8);
     AttnParams p = {};
     p.qkv = (const bf16*)a->qkv; p.o_in = (const bf16*)a->o; p.d_o = (const bf16*)a->d_o; p.lse_in = a->lse; p.delta = a->delta;
     p.dqkv = (bf16*)a->dqkv; p.rope_cos = a->rope_cos; p.rope_sin = a->rope_sin; p.query_bounds = a->query_bounds;   // range mode: the per-key table of an asymmetric mask (null: symmetric)

@@ -30,6 +30,10 @@ void obte_set_error(const char* fmt, ...);
             return OBTE_EINVAL;                     \
         }                                           \
     } while (0)
+// The alignment the kernels' vector accesses need (include/omnibiote_hip.h, conventions): checked before any launch; a null
+// (optional) pointer passes.  name: the argument as the header spells it.
+#define OBTE_REQUIRE_ALIGNED(who, ptr, name, bytes)                                                                     \
+    OBTE_REQUIRE((reinterpret_cast<uintptr_t>(ptr) & (uintptr_t)((bytes) - 1)) == 0, "%s: %s must be %d-byte aligned", who, name, (int)(bytes))
 #define OBTE_CHECK_LAUNCH(name)                                                           \
     do {                                                                                  \
         hipError_t e_ = hipGetLastError();                                                \

@@ -628,6 +628,9 @@ int mt_build(const obte_mt_args* a, float beta1, float beta2, MtTable* t, const 
     for (int i = 0; i < a->count; ++i) {
         OBTE_REQUIRE(a->g[i] && a->n[i] > 0 && a->n[i] % 8 == 0, "%s: tensor %d: null gradient or n not a multiple of 8", who, i);
         if (need_state) OBTE_REQUIRE(a->p[i] && a->m[i] && a->v[i] && a->step[i] >= 1, "%s: tensor %d: null state or step < 1", who, i);
+        const void* const ptrs[4] = {a->g[i], a->p[i], a->m[i], a->v[i]};
+        static const char* const names[4] = {"g", "p", "m", "v"};
+        for (int f = 0; f < (need_state ? 4 : 1); ++f) OBTE_REQUIRE(((uintptr_t)ptrs[f] & 15) == 0, "%s: tensor %d: %s must be 16-byte aligned", who, i, names[f]);
         t->p[i] = (bf16*)a->p[i]; t->g[i] = (const bf16*)a->g[i]; t->m[i] = (bf16*)a->m[i]; t->v[i] = (bf16*)a->v[i];
         t->n[i] = a->n[i]; t->lr[i] = a->lr[i]; t->wd[i] = a->weight_decay[i];
         const int st = a->step[i] < 1 ? 1 : a->step[i];
@@ -757,6 +760,9 @@ inline unsigned stream_grid(int64_t work_items, int per_block) {
 extern "C" int obte_rope_qk_inplace(obte_bf16* qkv, const float* cos_t, const float* sin_t, int64_t B, int64_t T,
                                     int n_head, int head_dim, int inverse, obte_stream s) {
     OBTE_REQUIRE(qkv && cos_t && sin_t, "obte_rope_qk_inplace: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_rope_qk_inplace", qkv, "qkv", 16);
+    OBTE_REQUIRE_ALIGNED("obte_rope_qk_inplace", cos_t, "cos_t", 16);
+    OBTE_REQUIRE_ALIGNED("obte_rope_qk_inplace", sin_t, "sin_t", 16);
     OBTE_REQUIRE(B > 0 && T > 0 && n_head > 0 && head_dim % 8 == 0, "obte_rope_qk_inplace: head_dim must be a multiple of 8");
     const int C = n_head * head_dim;
     const int64_t rows = B * T, total = rows * (2 * C / 8);
@@ -777,6 +783,8 @@ static int check_p(const char* who, float p) {
 extern "C" int obte_embedding_fwd_dropout(const int64_t* idx, const obte_bf16* wte, obte_bf16* out, int64_t rows, int cols,
                                           int64_t vocab, float p, uint64_t seed, obte_stream s) {
     OBTE_REQUIRE(idx && wte && out, "obte_embedding_fwd: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_embedding_fwd", wte, "wte", 16);
+    OBTE_REQUIRE_ALIGNED("obte_embedding_fwd", out, "out", 16);
     OBTE_REQUIRE(rows >= 0 && cols > 0 && cols % 8 == 0 && vocab > 0, "obte_embedding_fwd: cols must be a multiple of 8");
     if (check_p("obte_embedding_fwd", p)) return OBTE_EINVAL;
     if (rows == 0) return OBTE_OK;
@@ -819,6 +827,8 @@ __global__ __launch_bounds__(256) void dropout_rows_kernel(const bf16* __restric
 
 extern "C" int obte_dropout_bf16(const obte_bf16* in, obte_bf16* out, int64_t n, int64_t cols, float p, uint64_t seed, int32_t site,
                                  obte_stream s) {
+    OBTE_REQUIRE_ALIGNED("obte_dropout_bf16", in, "in", 16);
+    OBTE_REQUIRE_ALIGNED("obte_dropout_bf16", out, "out", 16);
     OBTE_REQUIRE(in && out && n > 0 && n % 8 == 0, "obte_dropout_bf16: null pointer or n not a positive multiple of 8");
     OBTE_REQUIRE(cols > 0 && cols % 8 == 0 && n % cols == 0 && cols < (1ll << 32), "obte_dropout_bf16: cols must be a multiple of 8 that divides n");
     if (check_p("obte_dropout_bf16", p)) return OBTE_EINVAL;
@@ -836,6 +846,9 @@ extern "C" int obte_embedding_bwd_dropout(const int64_t* idx, const int32_t* ord
                                           void* ws, int64_t rows, int cols, int64_t vocab, int accumulate, float p, uint64_t seed,
                                           obte_stream s) {
     OBTE_REQUIRE(idx && order && dout && dwte && ws, "obte_embedding_bwd: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_embedding_bwd", dout, "dout", 16);
+    OBTE_REQUIRE_ALIGNED("obte_embedding_bwd", dwte, "dwte", 16);
+    OBTE_REQUIRE_ALIGNED("obte_embedding_bwd", ws, "ws", 16);
     if (check_p("obte_embedding_bwd", p)) return OBTE_EINVAL;
     const DropCfg dc = make_drop(p, seed, OBTE_SITE_EMBED);
     OBTE_REQUIRE(rows > 0 && cols > 0 && cols % 8 == 0 && vocab > 0, "obte_embedding_bwd: bad shape");
@@ -864,6 +877,9 @@ extern "C" int obte_embedding_bwd_dropout(const int64_t* idx, const int32_t* ord
 }
 
 extern "C" int obte_acc32_add_bf16(float* acc32, const obte_bf16* src, obte_bf16* out, int64_t n, int mode, obte_stream s) {
+    OBTE_REQUIRE_ALIGNED("obte_acc32_add_bf16", acc32, "acc32", 16);
+    OBTE_REQUIRE_ALIGNED("obte_acc32_add_bf16", src, "src", 16);
+    OBTE_REQUIRE_ALIGNED("obte_acc32_add_bf16", out, "out", 16);
     OBTE_REQUIRE(acc32 && n > 0 && n % 8 == 0, "obte_acc32_add_bf16: null buffer or n not a positive multiple of 8");
     OBTE_REQUIRE(mode >= OBTE_ACC32_FIRST && mode <= OBTE_ACC32_LAST && (mode != OBTE_ACC32_LAST || out), "obte_acc32_add_bf16: bad mode, or LAST without out");
     if (!src && mode == OBTE_ACC32_MORE) return OBTE_OK;   // nothing to add, nothing to write
@@ -875,6 +891,10 @@ extern "C" int obte_acc32_add_bf16(float* acc32, const obte_bf16* src, obte_bf16
 extern "C" int obte_embedding_bwd_acc32(const int64_t* idx, const int32_t* order, const obte_bf16* dout, float* acc32, obte_bf16* dwte,
                                         void* ws, int64_t rows, int cols, int64_t vocab, int mode, float p, uint64_t seed, obte_stream s) {
     OBTE_REQUIRE(idx && order && dout && acc32 && ws, "obte_embedding_bwd_acc32: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_embedding_bwd_acc32", dout, "dout", 16);
+    OBTE_REQUIRE_ALIGNED("obte_embedding_bwd_acc32", acc32, "acc32", 16);
+    OBTE_REQUIRE_ALIGNED("obte_embedding_bwd_acc32", dwte, "dwte", 16);
+    OBTE_REQUIRE_ALIGNED("obte_embedding_bwd_acc32", ws, "ws", 16);
     OBTE_REQUIRE(mode >= OBTE_ACC32_FIRST && mode <= OBTE_ACC32_LAST && (mode != OBTE_ACC32_LAST || dwte), "obte_embedding_bwd_acc32: bad mode, or LAST without dwte");
     if (check_p("obte_embedding_bwd_acc32", p)) return OBTE_EINVAL;
     const DropCfg dc = make_drop(p, seed, OBTE_SITE_EMBED);
@@ -919,6 +939,8 @@ extern "C" int obte_masked_ce_fwd_bwd_reuse(const obte_bf16* logits, const int64
                                             const uint8_t* prev_mask, const float* grad_scale, float row_scale, float* row_loss,
                                             obte_bf16* dlogits, int64_t rows, int64_t vocab, obte_stream s) {
     OBTE_REQUIRE(logits && target && mlm_mask && grad_scale && dlogits, "obte_masked_ce_fwd_bwd: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_masked_ce_fwd_bwd", logits, "logits", 16);
+    OBTE_REQUIRE_ALIGNED("obte_masked_ce_fwd_bwd", dlogits, "dlogits", 16);
     OBTE_REQUIRE(rows > 0 && rows < (1ll << 31) && vocab > 0 && vocab % 8 == 0, "obte_masked_ce_fwd_bwd: vocab must be a multiple of 8");
     hipLaunchKernelGGL(masked_ce_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)s, (const bf16*)logits, target, mlm_mask,
                        prev_mask, grad_scale, row_scale, row_loss, (bf16*)dlogits, vocab, (const int64_t*)nullptr, (const float*)nullptr);
@@ -943,6 +965,8 @@ __global__ __launch_bounds__(256) void rows_copy_kernel(const bf16* __restrict__
 }  // namespace
 extern "C" int obte_rows_gather_bf16(const obte_bf16* src, const int64_t* rows, obte_bf16* dst, int64_t n_rows, int64_t total_rows, int32_t cols, obte_stream s) {
     OBTE_REQUIRE(src && rows && dst, "obte_rows_gather_bf16: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_rows_gather_bf16", src, "src", 16);
+    OBTE_REQUIRE_ALIGNED("obte_rows_gather_bf16", dst, "dst", 16);
     OBTE_REQUIRE(n_rows > 0 && total_rows > 0 && cols > 0 && cols % 8 == 0, "obte_rows_gather_bf16: need n_rows, total_rows > 0 and cols %% 8 == 0");
     hipLaunchKernelGGL(rows_copy_kernel, dim3((unsigned)cdiv64(n_rows, 4)), dim3(256), 0, (hipStream_t)s, (const bf16*)src, rows, (bf16*)dst, n_rows, total_rows, cols, 0);
     OBTE_CHECK_LAUNCH("obte_rows_gather_bf16");
@@ -950,6 +974,8 @@ extern "C" int obte_rows_gather_bf16(const obte_bf16* src, const int64_t* rows, 
 }
 extern "C" int obte_rows_scatter_bf16(const obte_bf16* src, const int64_t* rows, obte_bf16* dst, int64_t n_rows, int64_t total_rows, int32_t cols, obte_stream s) {
     OBTE_REQUIRE(src && rows && dst, "obte_rows_scatter_bf16: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_rows_scatter_bf16", src, "src", 16);
+    OBTE_REQUIRE_ALIGNED("obte_rows_scatter_bf16", dst, "dst", 16);
     OBTE_REQUIRE(n_rows > 0 && n_rows <= total_rows && cols > 0 && cols % 8 == 0, "obte_rows_scatter_bf16: need 0 < n_rows <= total_rows and cols %% 8 == 0");
     if (hipMemsetAsync(dst, 0, (size_t)total_rows * cols * 2, (hipStream_t)s) != hipSuccess) { obte_set_error("obte_rows_scatter_bf16: memset failed"); return OBTE_ELAUNCH; }
     hipLaunchKernelGGL(rows_copy_kernel, dim3((unsigned)cdiv64(n_rows, 4)), dim3(256), 0, (hipStream_t)s, (const bf16*)src, rows, (bf16*)dst, n_rows, total_rows, cols, 1);
@@ -961,6 +987,8 @@ extern "C" int obte_masked_ce_rows(const obte_bf16* logits, const int64_t* targe
                                    float row_scale, const float* row_scale_vec, float* row_loss, obte_bf16* dlogits_rows, int64_t n_rows,
                                    int64_t total_rows, int64_t vocab, obte_stream s) {
     OBTE_REQUIRE(logits && target && dlogits_rows && row_loss, "obte_masked_ce_rows: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_masked_ce_rows", logits, "logits", 16);
+    OBTE_REQUIRE_ALIGNED("obte_masked_ce_rows", dlogits_rows, "dlogits_rows", 16);
     OBTE_REQUIRE(n_rows > 0 && n_rows <= total_rows && total_rows < (1ll << 31) && vocab > 0 && vocab % 8 == 0,
                  "obte_masked_ce_rows: need 0 < n_rows <= total_rows and vocab %% 8 == 0");
     OBTE_REQUIRE(row_index || n_rows == total_rows, "obte_masked_ce_rows: without a row list, logits and target hold exactly the n_rows listed rows");
@@ -1018,6 +1046,10 @@ extern "C" int obte_adamw_bf16(obte_bf16* p, const obte_bf16* g, obte_bf16* m, o
                                float beta1, float beta2, float eps, float weight_decay, int32_t step,
                                const float* clip_coef, obte_stream s) {
     OBTE_REQUIRE(p && g && m && v, "obte_adamw_bf16: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_adamw_bf16", p, "p", 16);
+    OBTE_REQUIRE_ALIGNED("obte_adamw_bf16", g, "g", 16);
+    OBTE_REQUIRE_ALIGNED("obte_adamw_bf16", m, "m", 16);
+    OBTE_REQUIRE_ALIGNED("obte_adamw_bf16", v, "v", 16);
     OBTE_REQUIRE(n > 0 && n % 8 == 0 && step >= 1, "obte_adamw_bf16: n must be a positive multiple of 8, step >= 1");
     const float bc1 = 1.0f - powf(beta1, (float)step);
     const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
@@ -1029,6 +1061,7 @@ extern "C" int obte_adamw_bf16(obte_bf16* p, const obte_bf16* g, obte_bf16* m, o
 
 extern "C" int obte_sumsq_bf16(const obte_bf16* g, int64_t n, float* out, obte_stream s) {
     OBTE_REQUIRE(g && out, "obte_sumsq_bf16: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_sumsq_bf16", g, "g", 16);
     OBTE_REQUIRE(n > 0 && n % 8 == 0, "obte_sumsq_bf16: n must be a positive multiple of 8");
     hipLaunchKernelGGL(sumsq_kernel, dim3(stream_grid(n / 8, 256)), dim3(256), 0, (hipStream_t)s, (const bf16*)g, n / 8, out);
     OBTE_CHECK_LAUNCH("obte_sumsq_bf16");
@@ -1094,6 +1127,9 @@ extern "C" int obte_adamw_multi_master(const obte_mt_master_args* a, double beta
     int blocks = 0;
     for (int i = 0; i < a->count; ++i) {
         OBTE_REQUIRE(a->p[i] && a->g[i] && a->master[i] && a->m[i] && a->v[i], "%s: tensor %d: null pointer", who, i);
+        const void* const ptrs[5] = {a->p[i], a->g[i], a->master[i], a->m[i], a->v[i]};
+        static const char* const names[5] = {"p", "g", "master", "m", "v"};
+        for (int f = 0; f < 5; ++f) OBTE_REQUIRE(((uintptr_t)ptrs[f] & 15) == 0, "%s: tensor %d: %s must be 16-byte aligned", who, i, names[f]);
         OBTE_REQUIRE(a->n[i] > 0 && a->n[i] % 8 == 0 && a->step[i] >= 1, "%s: tensor %d: n must be a positive multiple of 8, step >= 1", who, i);
         t.p[i] = (bf16*)a->p[i]; t.g[i] = (const bf16*)a->g[i]; t.w[i] = a->master[i]; t.m[i] = a->m[i]; t.v[i] = a->v[i];
         t.n[i] = a->n[i];

@@ -17,6 +17,14 @@ int gemm_no_form(int s, int bn, bool ak, bool bk, int epi, bool split) {
 
 static int validate_args(const obte_gemm_args* g) {
     OBTE_REQUIRE(g && g->a && g->b && (g->d || (g->epilogue == OBTE_EPI_ACC32 && g->acc32_mode != OBTE_ACC32_LAST)), "obte_gemm_bf16: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_gemm_bf16", g->a, "a", 16);
+    OBTE_REQUIRE_ALIGNED("obte_gemm_bf16", g->b, "b", 16);
+    OBTE_REQUIRE_ALIGNED("obte_gemm_bf16", g->d, "d", 16);
+    OBTE_REQUIRE_ALIGNED("obte_gemm_bf16", g->aux, "aux", 16);
+    OBTE_REQUIRE_ALIGNED("obte_gemm_bf16", g->d2, "d2", 16);
+    OBTE_REQUIRE_ALIGNED("obte_gemm_bf16", g->rope_cos, "rope_cos", 16);
+    OBTE_REQUIRE_ALIGNED("obte_gemm_bf16", g->rope_sin, "rope_sin", 16);
+    OBTE_REQUIRE_ALIGNED("obte_gemm_bf16", g->acc32, "acc32", 16);
     OBTE_REQUIRE(g->M > 0 && g->N > 0 && g->K > 0, "obte_gemm_bf16: empty problem M=%lld N=%lld K=%lld",
                  (long long)g->M, (long long)g->N, (long long)g->K);
     OBTE_REQUIRE(g->lda % 8 == 0 && g->ldb % 8 == 0 && g->ldd % 8 == 0 && g->N % 8 == 0,
@@ -311,6 +319,7 @@ extern "C" int64_t obte_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
 }
 
 extern "C" int obte_gemm_bf16_ws(const obte_gemm_args* g, void* workspace, int64_t workspace_bytes, obte_stream s) {
+    OBTE_REQUIRE_ALIGNED("obte_gemm_bf16", workspace, "workspace", 16);
     { const int vrc = validate_args(g); if (vrc != OBTE_OK) return vrc; }
     hipStream_t st = (hipStream_t)s;
     const Plan pl = resolve(g, workspace, workspace_bytes);

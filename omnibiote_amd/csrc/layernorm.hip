@@ -331,6 +331,9 @@ extern "C" int obte_layernorm_bwd_ws_rows(void) { return LN_BWD_MAX_BLOCKS; }
 extern "C" int obte_layernorm_fwd(const obte_bf16* x, const obte_bf16* w, obte_bf16* y, float* mean, float* rstd,
                                   int64_t rows, int cols, float eps, obte_stream s) {
     OBTE_REQUIRE(x && w && y && mean && rstd, "obte_layernorm_fwd: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_layernorm_fwd", x, "x", 16);
+    OBTE_REQUIRE_ALIGNED("obte_layernorm_fwd", w, "w", 16);
+    OBTE_REQUIRE_ALIGNED("obte_layernorm_fwd", y, "y", 16);
     OBTE_REQUIRE(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 4096, "obte_layernorm_fwd: cols must be a multiple of 8 and <= 4096 (got %d)", cols);
     if (rows == 0) return OBTE_OK;
     const dim3 grid((unsigned)cdiv64(rows, 4)), block(256);
@@ -361,6 +364,12 @@ static int ln_bwd_impl(const obte_bf16* dy, const obte_bf16* x, const obte_bf16*
                        const obte_bf16* dresid, obte_bf16* dx, obte_bf16* dw, float* ws, int64_t rows, int cols, int accumulate_dw,
                        int ws_acc, bool reduce, bool clear_tail, obte_stream s, obte_bf16* dx_drop = nullptr, DropCfg dc = DropCfg{0, 0, 0, 1.0f}) {
     OBTE_REQUIRE(dy && x && w && mean && rstd && dx && ws && (dw || !reduce), "obte_layernorm_bwd: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_layernorm_bwd", dy, "dy", 16);
+    OBTE_REQUIRE_ALIGNED("obte_layernorm_bwd", x, "x", 16);
+    OBTE_REQUIRE_ALIGNED("obte_layernorm_bwd", w, "w", 16);
+    OBTE_REQUIRE_ALIGNED("obte_layernorm_bwd", dresid, "dresid", 16);
+    OBTE_REQUIRE_ALIGNED("obte_layernorm_bwd", dx, "dx", 16);
+    OBTE_REQUIRE_ALIGNED("obte_layernorm_bwd", dx_drop, "dx_dropped", 16);
     OBTE_REQUIRE(rows > 0 && cols > 0 && cols % 8 == 0 && cols <= 4096, "obte_layernorm_bwd: bad shape rows=%lld cols=%d", (long long)rows, cols);
     // (one thread-safe static for the two A/B switches: the backward runs on autograd's worker threads)
     struct LnCfg { int blocks_cap, pipe_on; };

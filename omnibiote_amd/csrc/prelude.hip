@@ -129,6 +129,8 @@ __global__ __launch_bounds__(KR_THREADS) void key_ranges_kernel(const int64_t* _
 extern "C" int obte_key_ranges_from_tokens(const int64_t* ids, int64_t B, int64_t T, int64_t eos_token, int padding, int64_t group,
                                            int32_t* key_ranges, obte_stream s) {
     OBTE_REQUIRE(ids && key_ranges, "obte_key_ranges_from_tokens: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_key_ranges_from_tokens", ids, "ids", 8);
+    OBTE_REQUIRE_ALIGNED("obte_key_ranges_from_tokens", key_ranges, "key_ranges", 8);
     OBTE_REQUIRE(B > 0 && B < (1ll << 31) && T > 0 && T < (1ll << 24), "obte_key_ranges_from_tokens: bad shape (1 <= B < 2^31, 1 <= T < 2^24)");
     OBTE_REQUIRE(group >= 0, "obte_key_ranges_from_tokens: group must be >= 0");
     hipLaunchKernelGGL(key_ranges_kernel, dim3((unsigned)B), dim3(KR_THREADS), 0, (hipStream_t)s, ids, (int)T, eos_token,
@@ -350,6 +352,9 @@ __global__ __launch_bounds__(256) void causal_bounds_kernel(const int32_t* __res
 
 extern "C" int obte_causal_bounds(const int32_t* doc_ranges, int64_t B, int64_t T, int32_t* key_ranges, int32_t* query_bounds, obte_stream s) {
     OBTE_REQUIRE(key_ranges && query_bounds, "obte_causal_bounds: null pointer");
+    OBTE_REQUIRE_ALIGNED("obte_causal_bounds", doc_ranges, "doc_ranges", 8);
+    OBTE_REQUIRE_ALIGNED("obte_causal_bounds", key_ranges, "key_ranges", 8);
+    OBTE_REQUIRE_ALIGNED("obte_causal_bounds", query_bounds, "query_bounds", 8);
     OBTE_REQUIRE(B > 0 && B < (1ll << 31) && T > 0 && T < (1ll << 24), "obte_causal_bounds: bad shape (1 <= B < 2^31, 1 <= T < 2^24)");
     OBTE_REQUIRE(doc_ranges != key_ranges && doc_ranges != query_bounds && key_ranges != query_bounds, "obte_causal_bounds: the tables must not alias");
     const int64_t n = B * T;
