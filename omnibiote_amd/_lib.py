@@ -178,6 +178,12 @@ SYMBOLS_SMALL_M = {
 }
 SMALL_M_MAX_ROWS = 64   # the largest M obte_linear_small_m_bf16 takes
 
+# next-token sampling on the device (include/omnibiote_hip_sample.h): a table of its own as well
+SYMBOLS_SAMPLE = {
+    "obte_sample_logits_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                          c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -205,7 +211,7 @@ def lib():
                 l = C.CDLL(LIB_PATH)
             except OSError as e:
                 raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-            for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()):
+            for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items()):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

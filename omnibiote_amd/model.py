@@ -776,24 +776,63 @@ class MuReadout(_MuReadoutBase):
         return _LinearFn.apply(x, self.weight, float(self.output_mult) / float(wm))
 
 
-def sample_next(logits, temperature=1.0, top_k=None, generator=None):
+def _check_top_p(what, top_p):
+    if top_p is not None and not 0 < top_p <= 1:
+        raise ValueError(f"{what}: top_p must lie in (0, 1], got {top_p}")
+
+
+def sample_next(logits, temperature=1.0, top_k=None, generator=None, top_p=None):
     """The next token of every row from its (B, vocab) logits: nanoGPT's sampling step.  ``top_k == 1`` or ``temperature == 0`` is the
     argmax; otherwise the logits are divided by the temperature, everything below the row's k-th largest is excluded, and the token
-    is drawn from the softmax with ``torch.multinomial`` under ``generator``.  Ordinary torch on any device; returns (B,) int64."""
+    is drawn from the softmax with ``torch.multinomial`` under ``generator``.  ``top_p`` in (0, 1] (nucleus sampling, after top-k, by
+    the rule of ``sampling.sample_reference``): of what is left, walking the distinct values downwards, everything below the first
+    value at which the running probability reaches ``top_p`` is excluded too, ties kept whole.  Ordinary torch on any device; returns
+    (B,) int64."""
     if logits.dim() != 2:
         raise ValueError(f"sample_next: logits must be (B, vocab), got {tuple(logits.shape)}")
     if top_k is not None and top_k < 1:
         raise ValueError(f"sample_next: top_k must be at least 1, got {top_k}")
     if temperature < 0:
         raise ValueError(f"sample_next: temperature must not be negative, got {temperature}")
+    _check_top_p("sample_next", top_p)
     if top_k == 1 or temperature == 0:
         return torch.argmax(logits, dim=-1)
+    raw = logits
     logits = logits.float() / temperature
     if top_k is not None:
         v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
         logits = logits.masked_fill(logits < v[:, [-1]], float("-inf"))
+    if top_p is not None and top_p < 1:
+        # the distinct values' masses from a descending sort, in float64 on the logits as given (the reference's arithmetic)
+        x = raw.double().masked_fill(torch.isneginf(logits), float("-inf"))
+        sv, _ = torch.sort(x, dim=-1, descending=True)
+        csum = torch.exp((sv - sv[:, :1]) / temperature).cumsum(dim=-1)
+        end = torch.ones_like(sv, dtype=torch.bool)
+        end[:, :-1] = sv[:, :-1] != sv[:, 1:]                            # the last entry of every run of one value
+        at = (end & (csum >= top_p * csum[:, -1:])).to(torch.uint8).argmax(dim=-1, keepdim=True)
+        logits = logits.masked_fill(x < sv.gather(1, at), float("-inf"))
     probs = torch.softmax(logits, dim=-1)
     return torch.multinomial(probs, num_samples=1, generator=generator).squeeze(1)
+
+
+def _next_tokens(what, logits, temperature, top_k, top_p, generator, u):
+    """one step's tokens: ``sample_next`` (u is None: the torch sampler), or one launch of the device sampler against this step's
+    uniforms ``u`` (B,) — False: greedy, nothing was drawn"""
+    if u is None:
+        return sample_next(logits, temperature, top_k, generator, top_p)
+    if not (logits.is_cuda and logits.dtype == torch.bfloat16):
+        raise ValueError(f"OmniBioTA.{what}: sampler='device' needs bf16 logits on the GPU, got {logits.dtype} on {logits.device}")
+    return ops.sample_logits(logits, None if u is False else u, temperature, top_k, top_p)
+
+
+def _device_uniforms(sampler, steps, batch, temperature, top_k, device, generator):
+    """None for the torch sampler; for the device sampler the uniforms of a whole call, (steps, batch) drawn once (False when the
+    setting is greedy and nothing is drawn)"""
+    if sampler == "torch":
+        return None
+    if top_k == 1 or temperature == 0:
+        return [False] * steps
+    return torch.rand((steps, batch), device=device, generator=generator)
 
 
 def _check_lengths(what, lengths, batch, t0):
@@ -1038,7 +1077,8 @@ class OmniBioTA(nn.Module):
         return self._readout_rows(self.transformer.ln_f(x))
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None, lengths=None, pad_token=None):
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None, lengths=None, pad_token=None, top_p=None,
+                 sampler="torch"):
         """nanoGPT's generate(): ``idx`` (B, T0) int64 continued by up to ``max_new_tokens`` sampled tokens (``sample_next``); returns
         (B, T0 + n) int64.  The prompt runs once (``prefill``), every new token costs one ``decode_step``.  Where nanoGPT crops the
         context to block_size, this raises: T0 + max_new_tokens must fit.  ``eos_token``: a row that has produced it keeps producing
@@ -1049,7 +1089,14 @@ class OmniBioTA(nn.Module):
         gets up to ``max_new_tokens`` new tokens directly behind its own prompt; max(lengths) + max_new_tokens must fit block_size.
         Returns ``(out, out_lengths)``: out (B, max(lengths) + steps taken) int64, row b its prompt, its new tokens, then ``pad_token``
         (default: ``eos_token`` if given, else 0); out_lengths (B,) int64.  With ``eos_token`` a row that produced it is parked — its
-        out_lengths ends with the EOS — and the loop stops once every row is: the same single host synchronisation as above."""
+        out_lengths ends with the EOS — and the loop stops once every row is: the same single host synchronisation as above.
+
+        ``top_p``: nucleus sampling (``sample_next``).  ``sampler``: "torch" (``sample_next`` under ``generator``, as ever) or "device":
+        the uniforms of the whole call are drawn once, ``torch.rand((max_new_tokens, B), generator=generator)``, and every step's
+        tokens come from one launch on the step's bf16 logits (``ops.sample_logits``: the same rule, another random stream)."""
+        if sampler not in ("torch", "device"):
+            raise ValueError(f"OmniBioTA.generate: sampler must be 'torch' or 'device', got {sampler!r}")
+        _check_top_p("OmniBioTA.generate", top_p)
         self._check_generation("generate", idx.shape[0] if idx.dim() == 2 else 0)
         if idx.dim() != 2:
             raise ValueError(f"OmniBioTA.generate: idx must be (B, T0), got {tuple(idx.shape)}")
@@ -1058,7 +1105,7 @@ class OmniBioTA(nn.Module):
             raise ValueError("OmniBioTA.generate: the prompt is empty")
         if lengths is not None:
             return self._generate_ragged(idx, _check_lengths("generate", lengths, b, t0), max_new_tokens, temperature, top_k, generator, eos_token,
-                                         pad_token)
+                                         pad_token, top_p, sampler)
         if max_new_tokens < 0 or t0 + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {t0} prompt tokens + {max_new_tokens} new ones exceed block_size = {self.config.block_size}")
         if max_new_tokens == 0:
@@ -1066,9 +1113,10 @@ class OmniBioTA(nn.Module):
         cache = KVCache(self, b, t0 + max_new_tokens)
         out = [idx]
         logits = self.prefill(idx, cache)
+        us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
         done = None
         for i in range(max_new_tokens):
-            nxt = sample_next(logits, temperature, top_k, generator)
+            nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i])
             if eos_token is not None:
                 if done is not None:
                     nxt = torch.where(done, torch.full_like(nxt, eos_token), nxt)
@@ -1079,7 +1127,7 @@ class OmniBioTA(nn.Module):
             logits = self.decode_step(nxt, cache)
         return torch.cat(out, dim=1)
 
-    def _generate_ragged(self, idx, lens, max_new_tokens, temperature, top_k, generator, eos_token, pad_token):
+    def _generate_ragged(self, idx, lens, max_new_tokens, temperature, top_k, generator, eos_token, pad_token, top_p=None, sampler="torch"):
         longest = max(lens)
         if max_new_tokens < 0 or longest + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {longest} prompt tokens (the longest row) + {max_new_tokens} new ones exceed "
@@ -1092,10 +1140,11 @@ class OmniBioTA(nn.Module):
             return ragged_output(idx, lens, none, none.bool(), pad)
         cache = KVCache(self, b, longest + max_new_tokens)
         logits = self.prefill(idx, cache, lengths=lens)
+        us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
         tokens, valid = [], []
         done = torch.zeros(b, dtype=torch.bool, device=idx.device)
         for i in range(max_new_tokens):
-            nxt = sample_next(logits, temperature, top_k, generator)
+            nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i])
             tokens.append(nxt)
             valid.append(~done)                                         # a row's token counts if the row was running when it was drawn
             if eos_token is not None:

@@ -262,6 +262,32 @@ def small_m_max(m: int):
         L.lib().obte_small_m_max_set(prev)
 
 
+def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, return_kept=False):
+    """The next token of every row of ``logits`` (B, V) bf16, V <= 65536, in one launch (obte_sample_logits_bf16; the rule:
+    include/omnibiote_hip_sample.h, restated in plain torch by sampling.sample_reference): temperature, top-k, top-p, softmax and the
+    draw against ``u`` (B,) float32 uniforms.  ``u is None``, ``temperature == 0`` or ``top_k == 1``: the lowest index of the row maximum.
+    logits may be a row-strided view: last-dimension stride 1, row stride a multiple of 8.  Returns (B,) int64, with
+    ``return_kept`` also the size of every row's kept set, (B,) int32."""
+    _need(logits, "logits", contiguous=False)
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"sample_logits: logits must be (B, V) with B, V >= 1, got {tuple(logits.shape)}")
+    B, V = logits.shape
+    if logits.stride(1) != 1 and V > 1:
+        raise RuntimeError("sample_logits: logits must have stride 1 along the vocabulary")
+    ld = logits.stride(0) if B > 1 else (V + 7) // 8 * 8
+    if u is not None:
+        _need(u, "u", torch.float32)
+        if u.shape != (B,):
+            raise ValueError(f"sample_logits: u must be ({B},), got {tuple(u.shape)}")
+    if top_k is not None and top_k < 1:
+        raise ValueError(f"sample_logits: top_k must be at least 1, got {top_k}")
+    token = torch.empty(B, dtype=torch.int64, device=logits.device)
+    kept = torch.empty(B, dtype=torch.int32, device=logits.device) if return_kept else None
+    L.check(L.lib().obte_sample_logits_bf16(_ptr(logits), ld, B, V, _ptr(u), float(temperature), 0 if top_k is None else min(int(top_k), 2 ** 31 - 1),
+                                            1.0 if top_p is None else float(top_p), _ptr(token), _ptr(kept), _stream()), "obte_sample_logits_bf16")
+    return (token, kept) if return_kept else token
+
+
 def dropout(x, p, seed, site=L.SITE_USER, out=None):
     """out = dropout(x) with the library's counter-based mask: x is read as a matrix [numel / last dim, last dim] and
     element (row, col) decides (include/omnibiote_hip.h, dropout); x may alias out."""

@@ -1,0 +1,120 @@
+"""What choosing the next token costs: the torch sampler (model.sample_next) against the device sampler (ops.sample_logits, one launch of
+obte_sample_logits_bf16), both alternating in one process over the same windows and rounds.  Vocabulary 65 536, B in {1, 8, 64};
+settings: greedy; plain (T = 0.8); top_k = 200; top_p = 0.9; top_k = 200 with top_p = 0.9 (T = 0.8 throughout).
+
+  (a) the sampler alone on one fixed (B, 65536) bf16 tensor of logits (randn * 2) — at most 8 MB, so the logits stay cache-resident in
+      every window: this is the sampler's own cost, not a read of cold logits.  The device sampler's uniforms are drawn once outside
+      the window, as generate() draws them once per call; the torch sampler draws inside multinomial.
+  (b) a generated token: decode_step + the sampler on the step's own logits at B x 2048 on the small config (8 layers, 1024 wide), the
+      cache holding 2047 positions, the same position every time.
+Device events around windows of --steps calls, --rounds rounds after warm-up; median [min - max] in microseconds.  One JSON line per
+(part, B).
+
+    python tools/sample_bench.py [--batches 1,8,64] [--rounds 5] [--steps 300] [--part a|b|ab]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+VOCAB = 2 ** 16
+SETTINGS = (("greedy", dict(temperature=0.8, top_k=1)), ("plain", dict(temperature=0.8)), ("top_k=200", dict(temperature=0.8, top_k=200)),
+            ("top_p=0.9", dict(temperature=0.8, top_p=0.9)), ("top_k=200,top_p=0.9", dict(temperature=0.8, top_k=200, top_p=0.9)))
+
+
+def summary(v, nd=1):
+    return {"median": round(statistics.median(v), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
+
+
+def alternate(legs, rounds, steps, warm=5):
+    from decode_bench import timed
+    for fn in legs.values():
+        for _ in range(warm):
+            fn()
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for leg in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            us[leg].append(timed(legs[leg], steps))
+    out = {k: summary(v) for k, v in us.items()}
+    t, d = us["torch"], us["device"]
+    out["torch_over_device"] = round(statistics.median(t) / statistics.median(d), 2)
+    out["device_slower_beyond_both_spreads"] = statistics.median(d) - statistics.median(t) > (max(t) - min(t)) + (max(d) - min(d))
+    return out
+
+
+def samplers(logits_of, B, dev, kw, gen):
+    from omnibiote_amd import ops
+    from omnibiote_amd.model import sample_next
+    u = torch.rand(B, device=dev, generator=gen)
+    greedy = kw.get("top_k") == 1
+
+    def torch_leg():
+        return sample_next(logits_of(), kw["temperature"], kw.get("top_k"), gen, kw.get("top_p"))
+
+    def device_leg():
+        return ops.sample_logits(logits_of(), None if greedy else u, kw["temperature"], kw.get("top_k"), kw.get("top_p"))
+    return {"torch": torch_leg, "device": device_leg}
+
+
+def sampler_alone(B, rounds, steps, dev):
+    gen = torch.Generator(device=dev).manual_seed(B)
+    logits = (torch.randn(B, VOCAB, device=dev, generator=gen) * 2).to(torch.bfloat16)
+    out = {"part": "sampler alone", "B": B, "V": VOCAB, "logits_bytes": logits.numel() * 2, "logits": "cache-resident (one fixed tensor)",
+           "windows": {"calls": steps, "rounds": rounds}, "us": {}}
+    for name, kw in SETTINGS:
+        out["us"][name] = alternate(samplers(lambda: logits, B, dev, kw, gen), rounds, steps)
+    return out
+
+
+def generated_token(m, B, ctx, rounds, steps, dev):
+    from omnibiote_amd.model import KVCache
+    gen = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    idx = torch.randint(4, m.config.vocab_size, (B, ctx), device=dev, generator=gen)
+    cache = KVCache(m, B, ctx)
+    m.prefill(idx[:, :ctx - 1], cache)
+    last = idx[:, -1].contiguous()
+
+    def step():                      # the same position every time: the context stays ctx long
+        cache.pos = ctx - 1
+        return m.decode_step(last, cache)
+    out = {"part": "decode_step + sampler", "B": B, "context": ctx, "windows": {"steps": steps, "rounds": rounds}, "us": {}}
+    from decode_bench import timed
+    for _ in range(3):
+        step()
+    out["decode_step_alone_us"] = summary([timed(step, steps) for _ in range(rounds)])
+    for name, kw in SETTINGS:
+        out["us"][name] = alternate(samplers(step, B, dev, kw, gen), rounds, steps, warm=3)
+    return out
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--batches", default="1,8,64")
+    p.add_argument("--context", type=int, default=2048)
+    p.add_argument("--rounds", type=int, default=5)
+    p.add_argument("--steps", type=int, default=300)
+    p.add_argument("--part", default="ab", choices=("a", "b", "ab"))
+    a = p.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    batches = [int(b) for b in a.batches.split(",")]
+    if "a" in a.part:
+        for B in batches:
+            print(json.dumps(sampler_alone(B, a.rounds, a.steps, dev)), flush=True)
+    if "b" in a.part:
+        from decode_bench import build
+        m = build(a.context, dev)
+        for B in batches:
+            print(json.dumps(generated_token(m, B, a.context, a.rounds, a.steps, dev)), flush=True)
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
