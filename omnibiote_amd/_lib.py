@@ -184,6 +184,18 @@ SYMBOLS_SAMPLE = {
                                           c_stream]),
 }
 
+# n new positions per row against a filled cache (include/omnibiote_hip_extend.h): a table of its own as well
+ATTN_EXTEND_MAX_SPLITS = 32   # OBTE_ATTN_EXTEND_MAX_SPLITS
+SYMBOLS_EXTEND = {
+    "obte_attn_extend_splits": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
+    "obte_attn_extend_ws_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "obte_kv_cache_rope_store_chunk": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_attn_extend": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                   C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_extend_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "obte_block_extend": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -211,7 +223,8 @@ def lib():
                 l = C.CDLL(LIB_PATH)
             except OSError as e:
                 raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-            for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items()):
+            for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
+                                            + list(SYMBOLS_EXTEND.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -871,13 +871,15 @@ class KVCache:
     """The rotated keys and the values of every layer of ``model`` for ``batch`` sequences of up to ``max_len`` positions
     (default and at most ``config.block_size``): one buffer per layer (include/omnibiote_hip.h, obte_kv_cache_bytes), the workspace of
     a decode step, and ``pos``, the number of positions filled — a host integer, the same for every row.  ``OmniBioTA.prefill``
-    starts it over (nothing is cleared: positions beyond ``pos`` are never read), ``decode_step`` advances it.
+    starts it over (nothing is cleared: positions beyond ``pos`` are never read), ``decode_step`` advances it by one token per row,
+    ``extend`` by several, ``rewind`` steps back.
 
     After a prefill with ``lengths`` the rows stand at different positions: ``positions`` is then an int32 (B,) device tensor, row b's
     next position (the kernels read it there; a negative value parks a finished row: it stores nothing and attends to nothing), and
     ``max_pos`` the host's upper bound on it; ``decode_step`` advances both.  In this mode ``pos`` says nothing about a single row: it
     is kept equal to ``max_pos``, the positions filled in the longest row.  ``positions is None`` is the uniform mode above.  The three
-    are set together by ``prefill`` and ``decode_step``; code that sets one by hand sets the others to match."""
+    are set together by ``prefill`` and ``decode_step``; code that sets one by hand sets the others to match.  ``min_pos``, where it
+    exists, is a host-side lower bound on the shortest row that is not parked; only ``rewind`` reads it, and does without it if need be."""
 
     def __init__(self, model, batch, max_len=None):
         cfg = model.config
@@ -895,6 +897,38 @@ class KVCache:
         hs = cfg.n_embd // cfg.n_head
         self.layers = [ops.kv_cache_buffer(self.batch, max_len, cfg.n_head, hs, wte.device) for _ in model.transformer.h]
         self.decode_ws = ops.block_decode_workspace(self.batch, cfg.n_embd, cfg.n_head, wte.device)
+        self.extend_ws = None   # OmniBioTA.extend's workspace: allocated by the first call, replaced when a call needs more bytes
+
+    def rewind(self, n):
+        """Step back by ``n`` positions: ``pos -= n``, and after a prefill with ``lengths`` the rows not parked step back by ``n`` each,
+        ``max_pos`` and ``pos`` with them.  This is what a caller does with rejected draft tokens: ``extend`` the cache by the drafted
+        block, keep the accepted prefix, rewind the rest.  No kernel of the library runs and nothing is cleared — positions beyond
+        ``pos`` are never read, and the next tokens overwrite them.  With ``positions`` set, the one elementwise update of that tensor
+        is queued on the stream and the host does not wait for it: a draft-and-verify loop (extend by k, rewind by fewer) never
+        synchronises here.  ValueError if a row would be left with fewer than one position."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"KVCache.rewind: n must not be negative, got {n}")
+        if self.positions is None:
+            if self.pos - n < 1:
+                raise ValueError(f"KVCache.rewind: {n} positions back from {self.pos} leaves fewer than one")
+            self.pos -= n
+            return
+        # The shortest active row, bounded from below on the host (prefill sets ``min_pos``, extend and this advance it; decode steps and
+        # parked rows only leave it too low, which is safe): while the bound allows the step nothing waits for the device.  Only where it
+        # does not — or on a cache whose positions were set by hand — are the positions themselves read, which synchronises.
+        low = getattr(self, "min_pos", 0)
+        if self.max_pos - n < 1:
+            raise ValueError(f"KVCache.rewind: {n} positions back leaves a row with fewer than one")
+        if low - n < 1:
+            active = [p for p in self.positions.tolist() if p >= 0]
+            low = min(active) if active else n + 1
+            if low - n < 1:
+                raise ValueError(f"KVCache.rewind: {n} positions back leaves a row with fewer than one")
+        self.positions = self.positions - n * (self.positions >= 0).to(torch.int32)   # (parked rows, < 0, stay as they are)
+        self.min_pos = low - n
+        self.max_pos -= n
+        self.pos = self.max_pos
 
 
 class OmniBioTA(nn.Module):
@@ -1007,7 +1041,7 @@ class OmniBioTA(nn.Module):
         return self.lm_head(x)
 
     @torch.no_grad()
-    def prefill(self, idx, cache, lengths=None):
+    def prefill(self, idx, cache, lengths=None, chunk=None):
         """The prompt ``idx`` (B, T0) through every block under the causal mask, its keys and values left in ``cache`` (started
         over: ``cache.pos = T0``); returns the logits of the last position, (B, vocab).  ln_f and the readout run on that row alone.
 
@@ -1015,9 +1049,16 @@ class OmniBioTA(nn.Module):
         valid id.  The same kernels run over T0 — under the causal mask a real position never sees a later one, so the padding reaches
         nothing, and the cache positions it fills are overwritten by the row's own new tokens before they are read.  Row b's logits
         come from position len_b - 1; ``cache.positions`` = lengths and ``cache.max_pos`` = ``cache.pos`` = max(lengths) put ``decode_step`` on the
-        one-position-per-row path."""
+        one-position-per-row path.
+
+        ``chunk`` (an int >= 1; None or >= T0: the call above, bit for bit): the first ``chunk`` columns go through the prefill kernels,
+        every further ``chunk`` of them through ``extend``'s block path at uniform positions (right padding stays harmless under the
+        causal rule), each embedded on its own — the activation workspace is sized by the chunk, no (B, T0, C) tensor exists — and
+        row b's last hidden state is picked up in the chunk that holds it.  The cache ends in the same state."""
         if idx.dim() != 2:
             raise ValueError(f"OmniBioTA.prefill: idx must be (B, T0), got {tuple(idx.shape)}")
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError(f"OmniBioTA.prefill: chunk must be at least 1, got {chunk}")
         b, t = idx.shape
         self._check_generation("prefill", b, cache)
         if t == 0:
@@ -1029,6 +1070,8 @@ class OmniBioTA(nn.Module):
         _require_hip(wte, "OmniBioTA")
         if not idx.is_cuda:
             raise RuntimeError("OmniBioTA.prefill: idx must be on the GPU")
+        if chunk is not None and int(chunk) < t:
+            return self._prefill_chunked(idx, cache, lens, int(chunk))
         mask = ops.MaskSpec.from_user(_autoregressive_mask(True, None, b, t, idx.device), b, t, self.config.n_head, idx.device)
         x = ops.embedding_fwd(idx.contiguous(), wte)
         ws = ops.block_infer_workspace(b, t, self.config.n_embd, self.config.n_head, idx.device)
@@ -1039,9 +1082,98 @@ class OmniBioTA(nn.Module):
             cache.positions, cache.max_pos = None, 0
             return self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()))
         cache.positions, cache.max_pos = torch.tensor(lens, dtype=torch.int32, device=idx.device), max(lens)
+        cache.min_pos = min(lens)                                       # (KVCache.rewind's host-side lower bound)
         cache.pos = cache.max_pos                                       # (kept in step with max_pos while positions is set)
         last = x[torch.arange(b, device=idx.device), (cache.positions - 1).long()]          # (B, C): row b at its own last position
         return self._readout_rows(self.transformer.ln_f(last.contiguous()))
+
+    def _extend_ws(self, cache, device, *ns):
+        """The workspace of ``n`` new positions per row for every ``n`` of ``ns``, kept on the cache object and replaced when a call
+        needs more BYTES than it has.  The size is not monotone in n — the attention partials shrink where the default split count drops
+        (n = 65 asks for less than n = 64 at small B * H) — so the buffer's own size is compared, never the n that made it."""
+        need = max(ops.block_extend_ws_bytes(cache.batch, n, self.config.n_embd, self.config.n_head) for n in ns)
+        ws = getattr(cache, "extend_ws", None)
+        if ws is None or ws.numel() < need:
+            cache.extend_ws = ws = None   # (the old buffer goes before the new one comes)
+            cache.extend_ws = torch.empty(need, dtype=torch.uint8, device=device)
+        return cache.extend_ws
+
+    def _extend_hidden(self, tokens, cache, pos, pos_rows):
+        """``tokens`` (B, n) through every block against the cache at positions ``pos`` (or ``pos_rows``) on: the hidden states (B, n, C)"""
+        ws = self._extend_ws(cache, tokens.device, tokens.shape[1])
+        x = ops.embedding_fwd(tokens.contiguous(), self.transformer.wte.weight)
+        for block, kv in zip(self.transformer.h, cache.layers):
+            ops.block_extend(x, self._block_params(block), block.attn.rope(), self.config.n_head, kv, cache.max_len, pos, pos_rows=pos_rows, ws=ws, out=x)
+        return x
+
+    def _prefill_chunked(self, idx, cache, lens, chunk):
+        b, t = idx.shape
+        dev = idx.device
+        # one buffer for every chunk size to come (the last chunk may be shorter and still ask for more bytes); it is at least the
+        # prefill kernels' workspace for the first chunk's rows, so it serves them too
+        ws = self._extend_ws(cache, dev, *{min(chunk, t - start) for start in range(0, t, chunk)})
+        last_at = [t - 1] * b if lens is None else [n - 1 for n in lens]
+        last = torch.empty((b, self.config.n_embd), dtype=torch.bfloat16, device=dev)
+        for start in range(0, t, chunk):
+            n = min(chunk, t - start)
+            part = idx[:, start:start + n]
+            if start == 0:
+                mask = ops.MaskSpec.from_user(_autoregressive_mask(True, None, b, n, dev), b, n, self.config.n_head, dev)
+                x = ops.embedding_fwd(part.contiguous(), self.transformer.wte.weight)
+                for block, kv in zip(self.transformer.h, cache.layers):
+                    ops.block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, kv, cache.max_len, ws=ws, out=x)
+            else:
+                x = self._extend_hidden(part, cache, start, None)
+            rows = [r for r in range(b) if start <= last_at[r] < start + n]
+            if rows:
+                rt = torch.tensor(rows, device=dev)
+                last[rt] = x[rt, torch.tensor([last_at[r] - start for r in rows], device=dev)]
+        cache.pos = t
+        if lens is None:
+            cache.positions, cache.max_pos = None, 0
+        else:
+            cache.positions, cache.max_pos = torch.tensor(lens, dtype=torch.int32, device=dev), max(lens)
+            cache.min_pos = min(lens)
+            cache.pos = cache.max_pos
+        return self._readout_rows(self.transformer.ln_f(last))
+
+    @torch.no_grad()
+    def extend(self, tokens, cache, logits="last"):
+        """``tokens`` (B, n) int64: n new tokens per row in one call, row b's at positions ``cache.pos .. cache.pos + n - 1`` (after a
+        prefill with ``lengths``: ``cache.positions[b] + j``, read on the device).  Their keys and values join the cache; position j's
+        logits predict token j + 1.  Returns (B, vocab), the logits behind the last token, for ``logits="last"`` or (B, n, vocab) for
+        ``"all"`` — what verifying a block of drafted tokens or scoring a continuation needs.  ``pos`` / ``positions`` / ``max_pos`` advance
+        by n; parked rows stay parked.  n == 1 is ``decode_step``.  ``KVCache.rewind`` steps back over tokens that are not kept."""
+        if tokens.dim() != 2:
+            raise ValueError(f"OmniBioTA.extend: tokens must be (B, n), got {tuple(tokens.shape)}")
+        b, n = tokens.shape
+        if n == 0:
+            raise ValueError("OmniBioTA.extend: no tokens (n = 0)")
+        if logits not in ("last", "all"):
+            raise ValueError(f"OmniBioTA.extend: logits must be 'last' or 'all', got {logits!r}")
+        self._check_generation("extend", b, cache)
+        if cache.pos == 0:
+            raise ValueError("OmniBioTA.extend: the cache is empty: prefill a prompt first")
+        rows = cache.positions is not None
+        at = cache.max_pos if rows else cache.pos
+        if at + n > cache.max_len:
+            raise ValueError(f"OmniBioTA.extend: the cache's {cache.max_len} positions are full: {n} more from {at} do not fit")
+        if n == 1:
+            out = self.decode_step(tokens[:, 0], cache)
+            return out if logits == "last" else out.unsqueeze(1)
+        if not tokens.is_cuda:
+            raise RuntimeError("OmniBioTA.extend: tokens must be on the GPU")
+        x = self._extend_hidden(tokens, cache, at, cache.positions if rows else None)
+        if rows:
+            cache.positions = cache.positions + n * (cache.positions >= 0).to(torch.int32)   # (a new tensor: the launches above read the old one)
+            cache.max_pos += n
+            cache.min_pos = getattr(cache, "min_pos", 0) + n
+            cache.pos = cache.max_pos
+        else:
+            cache.pos += n
+        if logits == "last":
+            return self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()))
+        return self._readout_rows(self.transformer.ln_f(x.view(b * n, -1))).view(b, n, -1)
 
     @torch.no_grad()
     def decode_step(self, tokens, cache):

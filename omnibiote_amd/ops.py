@@ -901,6 +901,78 @@ def block_decode_rows(x, params, rope, H, cache, T_max, pos, max_pos, ws=None, o
     return y
 
 
+# ---- n new positions per row against a filled cache (include/omnibiote_hip_extend.h) ----
+def kv_cache_rope_store_chunk(qkv, rope, pos, max_pos, B, n, H, hs, cache, T_max):
+    """The rows form's rotate-and-store of a chunk (obte_kv_cache_rope_store_chunk): the q and k thirds of rows b * n + j of the unrotated
+    packed qkv [B * n, 3C] are rotated in place by row pos[b] + j of the FULL tables, the rotated k and the v written to cache position
+    pos[b] + j.  pos: int32 (B,) on the device; a row whose value lies outside [0, max_pos] is left alone."""
+    _need(qkv, "qkv"); _need(cache, "cache"); _need_rows(pos, "pos", B)
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert qkv.numel() == B * n * 3 * H * hs and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, hs)
+    assert rope[0].shape[0] >= max_pos + n and rope[1].shape[0] >= max_pos + n
+    L.check(L.lib().obte_kv_cache_rope_store_chunk(_ptr(qkv), _ptr(rope[0]), _ptr(rope[1]), _ptr(pos), int(max_pos), B, n, H, hs, _ptr(cache), T_max,
+                                                   _stream()), "obte_kv_cache_rope_store_chunk")
+    return qkv
+
+
+def attn_extend(q, cache, B, T_max, n, pos, H, hs, scale, splits=0, q_ld=None, ws=None, pos_rows=None, out=None, lse=None):
+    """n queries per (b, h) at positions p_b .. p_b + n - 1, query j over cache positions [0, p_b + j + 1) (obte_attn_extend):
+    (o (B * n, C) bf16, lse (B, H, n) fp32).  The chunk's own keys and values are in the cache already.  p_b = pos for every row, or
+    pos_rows[b] (int32 (B,) on the device, pos then its bound; a row outside [0, pos] gives zeros and lse = -inf).  q: any bf16 tensor
+    whose row b * n + j holds the query of head h at (b * n + j) * q_ld + h * hs (q_ld defaults to its last dimension).  splits: 0 = the
+    library's choice, else a forced count.  out / lse: where the results go (allocated here when None)."""
+    _need(q, "q", contiguous=False); _need(cache, "cache")
+    if pos_rows is not None:
+        _need_rows(pos_rows, "pos_rows", B)
+    q_ld = q.shape[-1] if q_ld is None else q_ld
+    assert n >= 1 and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, hs)
+    o = torch.empty((B * n, H * hs), dtype=bf16, device=q.device) if out is None else out
+    lse = torch.empty((B, H, n), dtype=torch.float32, device=q.device) if lse is None else lse
+    if ws is None:
+        ws = torch.empty(max(int(L.lib().obte_attn_extend_ws_bytes(B, H, hs, n, int(splits))), 16), dtype=torch.uint8, device=q.device)
+    L.check(L.lib().obte_attn_extend(_ptr(q), q_ld, _ptr(cache), _ptr(o), _ptr(lse), B, T_max, n, int(pos), _ptr(pos_rows), H, hs, float(scale),
+                                     int(splits), _ptr(ws), ws.numel(), _stream()), "obte_attn_extend")
+    return o, lse
+
+
+def block_extend_ws_bytes(B, n, Cc, H) -> int:
+    """obte_block_extend_ws_bytes, an unsupported shape raised.  NOT monotone in n (the attention partials follow the default split
+    count, which drops as n grows): a buffer kept for reuse is judged by its bytes, not by the n it was made for."""
+    nbytes = int(L.lib().obte_block_extend_ws_bytes(B, n, Cc, H))
+    if nbytes <= 0:
+        raise RuntimeError(f"block_extend: unsupported shape (B {B}, n {n}, n_embd {Cc}, n_head {H}): head size 64 or 128, "
+                           "n_embd a multiple of 64 and <= 4096")
+    return nbytes
+
+
+def block_extend_workspace(B, n, Cc, H, device) -> torch.Tensor:
+    return torch.empty(block_extend_ws_bytes(B, n, Cc, H), dtype=torch.uint8, device=device)
+
+
+def block_extend(x, params, rope, H, cache, T_max, pos, pos_rows=None, ws=None, out=None):
+    """n new positions per batch row against the cache (obte_block_extend): x (B, n, C) -> y (B, n, C).  Row b's positions start at
+    `pos`, or at pos_rows[b] (int32 (B,) on the device, read there; pos is then the host's bound on it, and a row outside [0, pos] stores
+    nothing and attends to nothing).  rope: the FULL tables (at least pos + n rows).  out may be x itself."""
+    _need(x, "x"); _need(cache, "cache")
+    B, n, Cc = x.shape
+    if pos_rows is not None:
+        _need_rows(pos_rows, "pos_rows", B)
+    for i, w in enumerate(params):
+        _need(w, f"param{i}")
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert rope[0].shape[0] >= pos + n and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, Cc // H)
+    if ws is None:
+        ws = block_extend_workspace(B, n, Cc, H, x.device)
+    else:
+        _need(ws, "ws", torch.uint8)
+    y = torch.empty_like(x) if out is None else out
+    _need(y, "out"); assert y.shape == x.shape
+    d = _block_desc(B, n, Cc, H, params, rope, MaskSpec())
+    L.check(L.lib().obte_block_extend(C.byref(d), _ptr(x), _ptr(y), _ptr(cache), T_max, int(pos), _ptr(pos_rows), _ptr(ws), ws.numel(), _stream()),
+            "obte_block_extend")
+    return y
+
+
 def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None, dropout_p=0.0, dropout_seed=0, ln_partials=None,
               ln_partial_mode=0, out_rows=None, dy_masked=None, dx_mask_seed=None, acc32=None, acc32_mode=0):
     """accumulate_into: optional list of 6 tensors-or-None (same order as params).  When the four matrix entries are all
