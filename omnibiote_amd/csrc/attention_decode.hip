@@ -18,8 +18,8 @@
 //     a wave or a split without any key carries (m = -inf, l = 0, acc = 0); every merge rescales against a maximum made finite first,
 //     so exp2(-inf - -inf) is never formed.
 //
-// The rows forms (obte_kv_cache_rope_store_rows, obte_attn_decode_rows): one position / key count PER ROW, an int32 the kernels read on
-// the device, for a batch whose rows stand at different positions.  A value outside the host's bound makes the row inactive: nothing
+// The rows forms (obte_kv_cache_rope_store_rows and its n-positions form obte_kv_cache_rope_store_chunk, one kernel; obte_attn_decode_rows):
+// one position / key count PER ROW, an int32 the kernels read on the device, for a batch whose rows stand at different positions.  A value outside the host's bound makes the row inactive: nothing
 // of it is stored, none of its cache is read, its attention output is exact zeros and its lse -inf — an out-of-range device value is
 // memory-safe without a status word, and a negative one parks a finished row.  The attention kernel is the one above with ROWS = true:
 // a workgroup derives its key range from its own row's count by the host's formula, so a row of n keys under s splits is partitioned
@@ -233,44 +233,57 @@ __global__ __launch_bounds__(256) void kv_cache_store_kernel(const bf16* __restr
     *(u32x4*)(cache + which * v_off + ((b * H + h) * T_max + pos0 + ti) * hs + e) = v;
 }
 
-// One decode step's rotate-and-store, one thread per 16 bytes of the packed qkv [B, 3C]: item = (b * 3 + third) * C / 8 + c8.  Row b at
-// position p = pos[b], 0 <= p <= max_pos (any other value: the row is left alone).  The q and k thirds are rotated in place by row p of
-// the tables, in the arithmetic of the GEMM epilogue OBTE_EPI_ROPE_QK (fp32 on the bf16 values, the same expression: the same bits);
-// the rotated k and the v go to cache position p of the item's head.
-__global__ __launch_bounds__(256) void kv_cache_rope_store_rows_kernel(bf16* __restrict__ qkv, const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                                                                       const int32_t* __restrict__ pos, int max_pos, bf16* __restrict__ cache, int64_t items,
-                                                                       int H, int hs, int64_t T_max, int64_t v_off) {
+// The rows form's rotate-and-store of a chunk, one thread per 16 bytes of the packed qkv [B n, 3C]: item = (row * 3 + third) * C / 8 + c8,
+// row = b n + j at position p = pos[b] + j (0 <= pos[b] <= max_pos; any other value: the row is left alone).  The q and k thirds are rotated
+// in place by row p of the tables, in the arithmetic of the GEMM epilogue OBTE_EPI_ROPE_QK (fp32 on the bf16 values, the same expression:
+// the same bits); the rotated k and the v go to cache position p of the item's head.  n = 1 is one decode step (obte_kv_cache_rope_store_rows).
+// Both entry points bound B n below 2^31: a row index divides in 32 bits.
+__global__ __launch_bounds__(256) void kv_cache_rope_store_chunk_kernel(bf16* __restrict__ qkv, const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                                        const int32_t* __restrict__ pos, int max_pos, int n, bf16* __restrict__ cache, int64_t items,
+                                                                        int H, int hs, int64_t T_max, int64_t v_off) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= items) return;
-    const int C = H * hs, cpr = C / 8;             // 16-byte items per third of a row
+    const int C = H * hs, cpr = C / 8;
     const int c8 = (int)(i % cpr);
     const int64_t rw = i / cpr;
     const int third = (int)(rw % 3);
-    const int64_t b = rw / 3;
-    const int p = pos[b];
-    if (p < 0 || p > max_pos) return;
+    const int row = (int)(rw / 3), b = row / n;
+    const int p0 = pos[b];
+    if (p0 < 0 || p0 > max_pos) return;
+    const int64_t p = (int64_t)p0 + (row - b * n);
     const int col = c8 * 8, h = col / hs, e = col % hs;
-    bf16* ptr = qkv + b * 3 * C + third * C + col;
+    bf16* ptr = qkv + (int64_t)row * 3 * C + third * C + col;
     bf16x8 v = *reinterpret_cast<const bf16x8*>(ptr);
     if (third < 2) {
-        const f32x4 c = *reinterpret_cast<const f32x4*>(cos_t + (int64_t)p * (hs / 2) + e / 2);
-        const f32x4 sn = *reinterpret_cast<const f32x4*>(sin_t + (int64_t)p * (hs / 2) + e / 2);
-        bf16x8 r;
+        const f32x4 c = *reinterpret_cast<const f32x4*>(cos_t + p * (hs / 2) + e / 2);
+        const f32x4 sn = *reinterpret_cast<const f32x4*>(sin_t + p * (hs / 2) + e / 2);
+        bf16x8 rt;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float xe = bf2f(v[2 * j]), xo = bf2f(v[2 * j + 1]);
-            r[2 * j] = f2bf(xe * c[j] - xo * sn[j]);
-            r[2 * j + 1] = f2bf(xe * sn[j] + xo * c[j]);
+            rt[2 * j] = f2bf(xe * c[j] - xo * sn[j]);
+            rt[2 * j + 1] = f2bf(xe * sn[j] + xo * c[j]);
         }
-        v = r;
+        v = rt;
         *reinterpret_cast<bf16x8*>(ptr) = v;
     }
-    if (third > 0) *reinterpret_cast<bf16x8*>(cache + (third - 1) * v_off + ((b * H + h) * T_max + p) * hs + e) = v;
+    if (third > 0) *reinterpret_cast<bf16x8*>(cache + (third - 1) * v_off + (((int64_t)b * H + h) * T_max + p) * hs + e) = v;
 }
 
 bool shape_ok(int64_t B, int64_t T_max, int32_t n_head, int32_t head_dim) {
     return B > 0 && B < (1ll << 31) && T_max > 0 && T_max < (1ll << 24) && n_head > 0 && n_head <= 1024 && (head_dim == 64 || head_dim == 128) &&
            B * n_head < (1ll << 31);
+}
+
+// the launch behind obte_kv_cache_rope_store_chunk and obte_kv_cache_rope_store_rows (n_new = 1), each after its own argument checks
+int rope_store_launch(const char* who, obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos_rows, int64_t max_pos, int64_t B,
+                      int64_t n_new, int32_t n_head, int32_t head_dim, obte_bf16* cache, int64_t T_max, obte_stream s) {
+    const int64_t items = B * n_new * 3 * n_head * head_dim / 8;
+    OBTE_REQUIRE(cdiv64(items, 256) < (1ll << 31), "%s: too many rows for one launch", who);
+    hipLaunchKernelGGL(kv_cache_rope_store_chunk_kernel, dim3((unsigned)cdiv64(items, 256)), dim3(256), 0, (hipStream_t)s, (bf16*)qkv, rope_cos, rope_sin, pos_rows,
+                       (int)max_pos, (int)n_new, (bf16*)cache, items, n_head, head_dim, T_max, B * n_head * T_max * head_dim);
+    OBTE_CHECK_LAUNCH(who);
+    return OBTE_OK;
 }
 
 }  // namespace
@@ -310,42 +323,69 @@ extern "C" int obte_attn_decode_splits(int64_t B, int32_t n_head, int32_t head_d
     return n < 1 ? 1 : (int)n;
 }
 
-extern "C" int obte_attn_decode(const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max, int64_t n_keys,
-                                int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws, int64_t ws_bytes, obte_stream s) {
-    OBTE_REQUIRE(q && cache && o, "obte_attn_decode: null pointer");
-    OBTE_REQUIRE(shape_ok(B, T_max, n_head, head_dim) && B * n_head <= 65535, "obte_attn_decode: bad shape (head_dim 64 or 128, B * n_head <= 65535)");
-    OBTE_REQUIRE(n_keys >= 1 && n_keys <= T_max, "obte_attn_decode: n_keys = %lld outside [1, T_max = %lld]", (long long)n_keys, (long long)T_max);
-    OBTE_REQUIRE(q_ld >= (int64_t)n_head * head_dim && q_ld % 8 == 0, "obte_attn_decode: q_ld must be a multiple of 8 and at least n_head * head_dim");
-    OBTE_REQUIRE((((uintptr_t)q | (uintptr_t)cache | (uintptr_t)o) & 15) == 0, "obte_attn_decode: q, cache and o must be 16-byte aligned");
-    OBTE_REQUIRE(splits >= 0 && splits <= OBTE_ATTN_DECODE_MAX_SPLITS, "obte_attn_decode: splits = %d outside [0, %d]", splits, OBTE_ATTN_DECODE_MAX_SPLITS);
+// obte_attn_decode (rows_n null: every row over the keys [0, n_keys)) and obte_attn_decode_rows_off (ROWS: row b over rows_n[b] + key_off keys,
+// n_keys the host's bound on that, the kernel forming `per` from the row's own count): the same checks, the same launch
+template <int HS, bool ROWS>
+static void launch_decode(const dim3& grid, hipStream_t st, const bf16* q, int64_t q_ld, const bf16* cache, bf16* o, float* lse, float* ws, int H, int64_t T_max,
+                          int64_t v_off, int n_keys, int per, float qscale, const int32_t* rows_n, int key_off) {
+    hipLaunchKernelGGL((attn_decode_kernel<HS, ROWS>), grid, dim3(DEC_WAVES * 64), 0, st, q, q_ld, cache, o, lse, ws, H, T_max, v_off, n_keys, per, qscale, rows_n, key_off);
+    if (grid.x > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<HS>, dim3(grid.y), dim3(HS), 0, st, (const float*)ws, o, lse, (int)grid.x);
+}
+
+template <bool ROWS>
+static int attn_decode_checked(const char* who, const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max,
+                               int64_t n_keys, const int32_t* rows_n, int32_t key_off, int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws,
+                               int64_t ws_bytes, obte_stream s) {
+    OBTE_REQUIRE(q && cache && o && (!ROWS || rows_n), "%s: null pointer", who);
+    OBTE_REQUIRE(shape_ok(B, T_max, n_head, head_dim) && B * n_head <= 65535, "%s: bad shape (head_dim 64 or 128, B * n_head <= 65535)", who);
+    OBTE_REQUIRE(n_keys >= 1 && n_keys <= T_max, "%s: %s = %lld outside [1, T_max = %lld]", who, ROWS ? "max_keys" : "n_keys", (long long)n_keys, (long long)T_max);
+    OBTE_REQUIRE(q_ld >= (int64_t)n_head * head_dim && q_ld % 8 == 0, "%s: q_ld must be a multiple of 8 and at least n_head * head_dim", who);
+    OBTE_REQUIRE((((uintptr_t)q | (uintptr_t)cache | (uintptr_t)o) & 15) == 0 && ((uintptr_t)rows_n & 3) == 0,
+                 "%s: q, cache and o must be 16-byte aligned, a per-row n_keys 4-byte aligned", who);
+    OBTE_REQUIRE(splits >= 0 && splits <= OBTE_ATTN_DECODE_MAX_SPLITS, "%s: splits = %d outside [0, %d]", who, splits, OBTE_ATTN_DECODE_MAX_SPLITS);
     if (splits == 0) splits = obte_attn_decode_splits(B, n_head, head_dim, n_keys);
     if (splits > 1) {
         const int64_t need = B * n_head * splits * (int64_t)(head_dim + DEC_PAD) * 4;
-        OBTE_REQUIRE(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0, "obte_attn_decode: %d splits need a 16-byte aligned workspace of %lld bytes, got %lld",
-                     splits, (long long)need, (long long)(ws ? ws_bytes : 0));
+        OBTE_REQUIRE(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0, "%s: %d splits need a 16-byte aligned workspace of %lld bytes, got %lld", who, splits,
+                     (long long)need, (long long)(ws ? ws_bytes : 0));
     }
-    const int per = (int)(cdiv64(cdiv64(n_keys, splits), DEC_CHUNK) * DEC_CHUNK);
+    const int per = ROWS ? 0 : (int)(cdiv64(cdiv64(n_keys, splits), DEC_CHUNK) * DEC_CHUNK);
     const hipStream_t st = (hipStream_t)s;
     const int BH = (int)(B * n_head);
     const float qscale = scale * 1.4426950408889634f;
     const int64_t v_off = B * n_head * T_max * head_dim;
-    const int prof = obte_prof_begin(st, 102, BH, n_keys, head_dim);   // cache bytes read = 4 * BH * n_keys * head_dim
-    const dim3 grid((unsigned)splits, (unsigned)BH), block(DEC_WAVES * 64);
-    if (head_dim == 128) {
-        hipLaunchKernelGGL((attn_decode_kernel<128, false>), grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max,
-                           v_off, (int)n_keys, per, qscale, (const int32_t*)nullptr, 0);
-        if (splits > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(BH), dim3(128), 0, st, (const float*)ws, (bf16*)o, lse, splits);
-    } else {
-        hipLaunchKernelGGL((attn_decode_kernel<64, false>), grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max,
-                           v_off, (int)n_keys, per, qscale, (const int32_t*)nullptr, 0);
-        if (splits > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(BH), dim3(64), 0, st, (const float*)ws, (bf16*)o, lse, splits);
-    }
+    const int prof = obte_prof_begin(st, 102, BH, n_keys, head_dim);   // cache bytes read = 4 * BH * n_keys * head_dim (ROWS: the bound, a row reads its own count)
+    const dim3 grid((unsigned)splits, (unsigned)BH);
+    if (head_dim == 128)
+        launch_decode<128, ROWS>(grid, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max, v_off, (int)n_keys, per, qscale, rows_n, key_off);
+    else
+        launch_decode<64, ROWS>(grid, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max, v_off, (int)n_keys, per, qscale, rows_n, key_off);
     obte_prof_end(prof, st);
-    OBTE_CHECK_LAUNCH("obte_attn_decode");
+    OBTE_CHECK_LAUNCH(who);
     return OBTE_OK;
 }
 
+extern "C" int obte_attn_decode(const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max, int64_t n_keys,
+                                int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws, int64_t ws_bytes, obte_stream s) {
+    return attn_decode_checked<false>("obte_attn_decode", q, q_ld, cache, o, lse, B, T_max, n_keys, nullptr, 0, n_head, head_dim, scale, splits, ws, ws_bytes, s);
+}
+
 // ---- one position / key count per row ---------------------------------------------------------------------------------------------------
+// The rotate-and-store of n_new positions per row, row b's from pos_rows[b] on (include/omnibiote_hip_extend.h; its shape rule is
+// obte_attn_extend's: B * n_head <= 65535, n_new < 2^20, B * n_new < 2^31) ...
+extern "C" int obte_kv_cache_rope_store_chunk(obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos_rows, int64_t max_pos, int64_t B,
+                                              int64_t n_new, int32_t n_head, int32_t head_dim, obte_bf16* cache, int64_t T_max, obte_stream s) {
+    OBTE_REQUIRE(qkv && rope_cos && rope_sin && pos_rows && cache, "obte_kv_cache_rope_store_chunk: null pointer");
+    OBTE_REQUIRE(shape_ok(B, T_max, n_head, head_dim) && B * n_head <= 65535 && n_new > 0 && n_new < (1ll << 20) && B * n_new < (1ll << 31),
+                 "obte_kv_cache_rope_store_chunk: bad shape (head_dim 64 or 128, n_new >= 1)");
+    OBTE_REQUIRE(max_pos >= 0 && max_pos + n_new <= T_max, "obte_kv_cache_rope_store_chunk: positions up to %lld + %lld do not fit T_max = %lld", (long long)max_pos,
+                 (long long)n_new, (long long)T_max);
+    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)cache | (uintptr_t)rope_cos | (uintptr_t)rope_sin) & 15) == 0 && ((uintptr_t)pos_rows & 3) == 0,
+                 "obte_kv_cache_rope_store_chunk: qkv, cache and the tables must be 16-byte aligned, pos_rows 4-byte aligned");
+    return rope_store_launch("obte_kv_cache_rope_store_chunk", qkv, rope_cos, rope_sin, pos_rows, max_pos, B, n_new, n_head, head_dim, cache, T_max, s);
+}
+
+// ... and of one: a decode step (include/omnibiote_hip_rows.h).  Its own checks, the same kernel at n = 1.
 extern "C" int obte_kv_cache_rope_store_rows(obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos, int64_t max_pos, int64_t B,
                                              int32_t n_head, int32_t head_dim, obte_bf16* cache, int64_t T_max, obte_stream s) {
     OBTE_REQUIRE(qkv && rope_cos && rope_sin && pos && cache, "obte_kv_cache_rope_store_rows: null pointer");
@@ -353,49 +393,14 @@ extern "C" int obte_kv_cache_rope_store_rows(obte_bf16* qkv, const float* rope_c
     OBTE_REQUIRE(max_pos >= 0 && max_pos < T_max, "obte_kv_cache_rope_store_rows: max_pos = %lld outside [0, T_max = %lld)", (long long)max_pos, (long long)T_max);
     OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)cache | (uintptr_t)rope_cos | (uintptr_t)rope_sin) & 15) == 0 && ((uintptr_t)pos & 3) == 0,
                  "obte_kv_cache_rope_store_rows: qkv, cache and the tables must be 16-byte aligned, pos 4-byte aligned");
-    const int64_t items = B * 3 * n_head * head_dim / 8;
-    OBTE_REQUIRE(cdiv64(items, 256) < (1ll << 31), "obte_kv_cache_rope_store_rows: too many rows for one launch");
-    hipLaunchKernelGGL(kv_cache_rope_store_rows_kernel, dim3((unsigned)cdiv64(items, 256)), dim3(256), 0, (hipStream_t)s, (bf16*)qkv, rope_cos, rope_sin, pos,
-                       (int)max_pos, (bf16*)cache, items, n_head, head_dim, T_max, B * n_head * T_max * head_dim);
-    OBTE_CHECK_LAUNCH("obte_kv_cache_rope_store_rows");
-    return OBTE_OK;
+    return rope_store_launch("obte_kv_cache_rope_store_rows", qkv, rope_cos, rope_sin, pos, max_pos, B, 1, n_head, head_dim, cache, T_max, s);
 }
 
 // obte_attn_decode_rows with row b's count read as n_keys[b] + key_off (csrc/block.cpp hands the positions and 1: no launch to form pos + 1)
 int obte_attn_decode_rows_off(const char* who, const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max,
                               const int32_t* n_keys, int32_t key_off, int64_t max_keys, int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws,
                               int64_t ws_bytes, obte_stream s) {
-    OBTE_REQUIRE(q && cache && o && n_keys, "%s: null pointer", who);
-    OBTE_REQUIRE(shape_ok(B, T_max, n_head, head_dim) && B * n_head <= 65535, "%s: bad shape (head_dim 64 or 128, B * n_head <= 65535)", who);
-    OBTE_REQUIRE(max_keys >= 1 && max_keys <= T_max, "%s: max_keys = %lld outside [1, T_max = %lld]", who, (long long)max_keys, (long long)T_max);
-    OBTE_REQUIRE(q_ld >= (int64_t)n_head * head_dim && q_ld % 8 == 0, "%s: q_ld must be a multiple of 8 and at least n_head * head_dim", who);
-    OBTE_REQUIRE((((uintptr_t)q | (uintptr_t)cache | (uintptr_t)o) & 15) == 0 && ((uintptr_t)n_keys & 3) == 0,
-                 "%s: q, cache and o must be 16-byte aligned, n_keys 4-byte aligned", who);
-    OBTE_REQUIRE(splits >= 0 && splits <= OBTE_ATTN_DECODE_MAX_SPLITS, "%s: splits = %d outside [0, %d]", who, splits, OBTE_ATTN_DECODE_MAX_SPLITS);
-    if (splits == 0) splits = obte_attn_decode_splits(B, n_head, head_dim, max_keys);
-    if (splits > 1) {
-        const int64_t need = B * n_head * splits * (int64_t)(head_dim + DEC_PAD) * 4;
-        OBTE_REQUIRE(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0, "%s: %d splits need a 16-byte aligned workspace of %lld bytes, got %lld", who, splits,
-                     (long long)need, (long long)(ws ? ws_bytes : 0));
-    }
-    const hipStream_t st = (hipStream_t)s;
-    const int BH = (int)(B * n_head);
-    const float qscale = scale * 1.4426950408889634f;
-    const int64_t v_off = B * n_head * T_max * head_dim;
-    const int prof = obte_prof_begin(st, 102, BH, max_keys, head_dim);   // (the bound: a row reads 4 * n_keys[b] * head_dim bytes per head)
-    const dim3 grid((unsigned)splits, (unsigned)BH), block(DEC_WAVES * 64);
-    if (head_dim == 128) {
-        hipLaunchKernelGGL((attn_decode_kernel<128, true>), grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max,
-                           v_off, (int)max_keys, 0, qscale, n_keys, key_off);
-        if (splits > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(BH), dim3(128), 0, st, (const float*)ws, (bf16*)o, lse, splits);
-    } else {
-        hipLaunchKernelGGL((attn_decode_kernel<64, true>), grid, block, 0, st, (const bf16*)q, q_ld, (const bf16*)cache, (bf16*)o, lse, (float*)ws, n_head, T_max,
-                           v_off, (int)max_keys, 0, qscale, n_keys, key_off);
-        if (splits > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(BH), dim3(64), 0, st, (const float*)ws, (bf16*)o, lse, splits);
-    }
-    obte_prof_end(prof, st);
-    OBTE_CHECK_LAUNCH(who);
-    return OBTE_OK;
+    return attn_decode_checked<true>(who, q, q_ld, cache, o, lse, B, T_max, max_keys, n_keys, key_off, n_head, head_dim, scale, splits, ws, ws_bytes, s);
 }
 
 extern "C" int obte_attn_decode_rows(const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max,

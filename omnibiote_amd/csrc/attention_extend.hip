@@ -1,6 +1,6 @@
 // Continuing a filled key/value cache by n new positions per row in one call (include/omnibiote_hip_extend.h): the attention of n queries
-// per (batch, head) at positions p .. p + n - 1 over cache positions [0, p + j + 1), causal inside the chunk, and the rows form's
-// rotate-and-store of a chunk.  The cache layout is attention_decode.hip's: K [B, H, T_max, hs], then V.
+// per (batch, head) at positions p .. p + n - 1 over cache positions [0, p + j + 1), causal inside the chunk.  The cache layout is
+// attention_decode.hip's: K [B, H, T_max, hs], then V; the rows form's rotate-and-store of a chunk stands there with the other cache stores.
 //
 // obte_attn_extend:
 //   - grid (split, 32-query tile, b H + h), 4 waves.  The keys a query tile can see are [0, p + min(n, 32 (tile + 1))); a split owns a
@@ -257,41 +257,6 @@ __global__ __launch_bounds__(64) void attn_extend_combine_kernel(const float* __
     ext_finish<D>(st, wl, o, lse, b, bh, hd, C, n, j0, nq, lane);
 }
 
-// The rows form's rotate-and-store of a chunk, one thread per 16 bytes of the packed qkv [B n, 3C]: item = (row * 3 + third) * C / 8 + c8,
-// row = b n + j at position p = pos[b] + j (0 <= pos[b] <= max_pos; any other value: the row is left alone).  kv_cache_rope_store_rows_kernel's
-// arithmetic (attention_decode.hip), which is the GEMM epilogue OBTE_EPI_ROPE_QK's: the same expression, the same bits.
-__global__ __launch_bounds__(256) void kv_cache_rope_store_chunk_kernel(bf16* __restrict__ qkv, const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                                                                        const int32_t* __restrict__ pos, int max_pos, int n, bf16* __restrict__ cache, int64_t items,
-                                                                        int H, int hs, int64_t T_max, int64_t v_off) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= items) return;
-    const int C = H * hs, cpr = C / 8;
-    const int c8 = (int)(i % cpr);
-    const int64_t rw = i / cpr;
-    const int third = (int)(rw % 3);
-    const int64_t row = rw / 3, b = row / n;
-    const int p0 = pos[b];
-    if (p0 < 0 || p0 > max_pos) return;
-    const int64_t p = (int64_t)p0 + row % n;
-    const int col = c8 * 8, h = col / hs, e = col % hs;
-    bf16* ptr = qkv + row * 3 * C + third * C + col;
-    bf16x8 v = *reinterpret_cast<const bf16x8*>(ptr);
-    if (third < 2) {
-        const f32x4 c = *reinterpret_cast<const f32x4*>(cos_t + p * (hs / 2) + e / 2);
-        const f32x4 sn = *reinterpret_cast<const f32x4*>(sin_t + p * (hs / 2) + e / 2);
-        bf16x8 rt;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float xe = bf2f(v[2 * j]), xo = bf2f(v[2 * j + 1]);
-            rt[2 * j] = f2bf(xe * c[j] - xo * sn[j]);
-            rt[2 * j + 1] = f2bf(xe * sn[j] + xo * c[j]);
-        }
-        v = rt;
-        *reinterpret_cast<bf16x8*>(ptr) = v;
-    }
-    if (third > 0) *reinterpret_cast<bf16x8*>(cache + (third - 1) * v_off + ((b * H + h) * T_max + p) * hs + e) = v;
-}
-
 bool shape_ok(int64_t B, int32_t n_head, int32_t head_dim, int64_t n_new) {
     return B > 0 && n_new > 0 && n_new < (1ll << 20) && n_head > 0 && n_head <= 1024 && (head_dim == 64 || head_dim == 128) && B * n_head <= 65535 &&
            B * n_new < (1ll << 31);
@@ -326,22 +291,6 @@ extern "C" int64_t obte_attn_extend_ws_bytes(int64_t B, int32_t n_head, int32_t 
     if (!shape_ok(B, n_head, head_dim, n_new) || splits < 0 || splits > OBTE_ATTN_EXTEND_MAX_SPLITS) return 0;
     const int64_t sp = splits > 0 ? splits : splits_bound(B, n_head, n_new);
     return B * n_head * tiles_of(n_new) * sp * part_floats(head_dim) * 4;
-}
-
-extern "C" int obte_kv_cache_rope_store_chunk(obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos_rows, int64_t max_pos, int64_t B,
-                                              int64_t n_new, int32_t n_head, int32_t head_dim, obte_bf16* cache, int64_t T_max, obte_stream s) {
-    OBTE_REQUIRE(qkv && rope_cos && rope_sin && pos_rows && cache, "obte_kv_cache_rope_store_chunk: null pointer");
-    OBTE_REQUIRE(shape_ok(B, n_head, head_dim, n_new) && T_max > 0 && T_max < (1ll << 24), "obte_kv_cache_rope_store_chunk: bad shape (head_dim 64 or 128, n_new >= 1)");
-    OBTE_REQUIRE(max_pos >= 0 && max_pos + n_new <= T_max, "obte_kv_cache_rope_store_chunk: positions up to %lld + %lld do not fit T_max = %lld", (long long)max_pos,
-                 (long long)n_new, (long long)T_max);
-    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)cache | (uintptr_t)rope_cos | (uintptr_t)rope_sin) & 15) == 0 && ((uintptr_t)pos_rows & 3) == 0,
-                 "obte_kv_cache_rope_store_chunk: qkv, cache and the tables must be 16-byte aligned, pos_rows 4-byte aligned");
-    const int64_t items = B * n_new * 3 * n_head * head_dim / 8;
-    OBTE_REQUIRE(cdiv64(items, 256) < (1ll << 31), "obte_kv_cache_rope_store_chunk: too many rows for one launch");
-    hipLaunchKernelGGL(kv_cache_rope_store_chunk_kernel, dim3((unsigned)cdiv64(items, 256)), dim3(256), 0, (hipStream_t)s, (bf16*)qkv, rope_cos, rope_sin, pos_rows,
-                       (int)max_pos, (int)n_new, (bf16*)cache, items, n_head, head_dim, T_max, B * n_head * T_max * head_dim);
-    OBTE_CHECK_LAUNCH("obte_kv_cache_rope_store_chunk");
-    return OBTE_OK;
 }
 
 template <int D>

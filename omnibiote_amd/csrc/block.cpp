@@ -484,12 +484,13 @@ namespace {
 // own positions), obte_block_fwd_prefill (the same, and the rotated keys and the values kept), obte_block_decode (one new position per
 // row against the cache) and obte_block_extend (n new positions per row against it).  rope_cos / rope_sin / rope_T: what c_attn's epilogue rotates by (position = row % rope_T).
 struct InferAttention {
-    obte_bf16* kv_cache; int64_t T_max;   // prefill and decode: the layer's cache (null: obte_block_fwd_infer)
-    int64_t pos;                          // decode: the position of the new row (< 0: the attention of the call's own T positions)
-    void* dec_ws; int64_t dec_ws_bytes;   // decode: obte_attn_decode's workspace
-    const int32_t* pos_rows = nullptr;    // decode, one position per row (obte_block_decode_rows): device int32 [B]; pos is then their bound,
-                                          // c_attn stays unrotated and the rotation joins the cache store (rope_cos / rope_sin: the FULL tables)
-    int64_t n_new = 0;                    // > 0: obte_block_extend, n_new new positions per row from pos (or pos_rows[b]) on; dec_ws: obte_attn_extend's
+    obte_bf16* kv_cache; int64_t T_max;   // the layer's cache (null: obte_block_fwd_infer)
+    int64_t pos;                          // against the cache: every row's first new position
+    void* dec_ws; int64_t dec_ws_bytes;   // against the cache: the workspace of obte_attn_decode (decode) or obte_attn_extend
+    const int32_t* pos_rows = nullptr;    // one position per row: device int32 [B]; pos is then their bound, c_attn stays unrotated and the rotation
+                                          // joins the cache store (rope_cos / rope_sin: the FULL tables)
+    int64_t n_new = 0;                    // > 0: against the cache, n_new new positions per row; 0: the attention of the call's own T positions
+    bool decode = false;                  // n_new == 1 on the one-query launchers (obte_block_decode, obte_block_decode_rows)
 };
 int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const InferLayout& w, int64_t M, const float* rope_cos,
                    const float* rope_sin, int64_t rope_T, const InferAttention& at, obte_stream s) {
@@ -497,25 +498,24 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
     // a call against the cache — decode (M = B rows) or extend (M = B * n_new rows) — of at most obte_small_m_max() rows: its four
     // products on the weight-streaming kernel (gemm_small_m.hip), the same epilogues; every other call (prefill, the forward-only block,
     // a larger extend) on the tile structures at every M
-    const bool stream_w = (at.pos >= 0 || at.pos_rows) && M <= obte_small_m_max();
+    const bool stream_w = at.n_new > 0 && M <= obte_small_m_max();
     auto run = [stream_w](const obte_gemm_args& g, obte_stream st) { return stream_w ? obte_linear_small_m_bf16(&g, st) : obte_gemm_bf16_ws(&g, nullptr, 0, st); };
     TRY(obte_layernorm_fwd(x, d->ln1_w, w.h1, w.mean, w.rstd, M, C, 1e-5f, s));
     obte_gemm_args qkv = xWt(w.h1, d->attn_w, w.qkv, M, 3 * C, C);
     if (!at.pos_rows) { qkv.epilogue = OBTE_EPI_ROPE_QK; qkv.rope_cos = rope_cos; qkv.rope_sin = rope_sin; qkv.rope_T = rope_T; qkv.rope_head_dim = hs; }
     TRY(run(qkv, s));
     const float scale = 8.0f / (float)C;  // model.py:119
-    if (at.n_new > 0) {   // n_new positions per row join the cache, then each attends over the positions up to its own
-        if (at.pos_rows) TRY(obte_kv_cache_rope_store_chunk(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, s));
-        else TRY(obte_kv_cache_store(w.qkv, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, at.pos, s));
-        TRY(obte_attn_extend(w.qkv, 3 * (int64_t)C, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.n_new, at.pos, at.pos_rows, H, hs, scale, 0, at.dec_ws,
-                             at.dec_ws_bytes, s));
-    } else if (at.pos_rows) {   // row b at its own position: rotated and stored by one launch, then over its own pos[b] + 1 keys
-        TRY(obte_kv_cache_rope_store_rows(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.T_max, s));
-        TRY(obte_attn_decode_rows_off("obte_block_decode_rows", w.qkv, 3 * (int64_t)C, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos_rows, 1, at.pos + 1, H, hs,
-                                      scale, 0, at.dec_ws, at.dec_ws_bytes, s));
-    } else if (at.pos >= 0) {   // the new position of every row joins the cache, then attends over positions 0 .. pos
-        TRY(obte_kv_cache_store(w.qkv, d->B, 1, H, hs, at.kv_cache, at.T_max, at.pos, s));
-        TRY(obte_attn_decode(w.qkv, 3 * (int64_t)C, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos + 1, H, hs, scale, 0, at.dec_ws, at.dec_ws_bytes, s));
+    if (at.n_new > 0) {   // n_new positions per row join the cache (the rows form rotates them as it stores), then each attends over those up to its own
+        const int64_t q_ld = 3 * (int64_t)C;
+        if (!at.pos_rows) TRY(obte_kv_cache_store(w.qkv, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, at.pos, s));
+        else if (at.decode) TRY(obte_kv_cache_rope_store_rows(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.T_max, s));
+        else TRY(obte_kv_cache_rope_store_chunk(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, s));
+        if (!at.decode)
+            TRY(obte_attn_extend(w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.n_new, at.pos, at.pos_rows, H, hs, scale, 0, at.dec_ws, at.dec_ws_bytes, s));
+        else if (at.pos_rows)   // row b over its own pos_rows[b] + 1 keys
+            TRY(obte_attn_decode_rows_off("obte_block_decode_rows", w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos_rows, 1, at.pos + 1, H, hs, scale, 0,
+                                          at.dec_ws, at.dec_ws_bytes, s));
+        else TRY(obte_attn_decode(w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos + 1, H, hs, scale, 0, at.dec_ws, at.dec_ws_bytes, s));
     } else {
         obte_attn_fwd_args af = {};
         af.qkv = w.qkv; af.o = w.att; af.lse = w.lse; af.key_ranges = d->key_ranges; af.mask = d->mask;
@@ -560,7 +560,46 @@ extern "C" int obte_block_fwd_prefill(const obte_block_desc* d, const obte_bf16*
     return infer_or_prefill("obte_block_fwd_prefill", d, x, y_out, ws, ws_bytes, kv_cache, T_max, true, s);
 }
 
-// ---- one new position per row against the cache ---------------------------------------------------------------------------------------------
+// ---- new positions per row against the cache --------------------------------------------------------------------------------------------
+namespace {
+
+// obte_block_decode, obte_block_decode_rows and obte_block_extend: d->T new positions per row, every row's from `pos` on or (rows) row b's from
+// pos_rows[b] on, read on the device, with `pos` the host's bound on it.  decode: the one-position launchers (obte_kv_cache_rope_store_rows,
+// obte_attn_decode / _rows and their workspace behind InferLayout) instead of obte_attn_extend's.
+int cached_step(const char* who, const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, int64_t pos,
+                const int32_t* pos_rows, bool rows, bool decode, void* ws, int64_t ws_bytes, obte_stream s) {
+    TRY(check_desc(who, d));
+    OBTE_REQUIRE(!decode || d->T == 1, "%s: one new position per row (T = 1), got T = %lld", who, (long long)d->T);
+    if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
+        obte_set_error("%s: key_ranges, mask, query_bounds, out_rows and dropout_p must be NULL / 0 (a new position sees every cached one up to itself)", who);
+        return OBTE_EUNSUPPORTED;
+    }
+    OBTE_REQUIRE(x && y_out && kv_cache && ws && (!rows || pos_rows), "%s: null pointer", who);
+    const int64_t n = d->T;
+    if (!(pos >= 0 && pos + n <= T_max)) {   // one condition, said in each caller's terms
+        if (!decode)
+            obte_set_error("%s: positions [%lld, %lld) (d->T = %lld new ones) do not fit the cache's [0, %lld)", who, (long long)pos, (long long)(pos + n),
+                           (long long)n, (long long)T_max);
+        else
+            obte_set_error(rows ? "%s: max_pos = %lld outside the cache's [0, %lld)" : "%s: position %lld outside the cache's [0, %lld)", who, (long long)pos,
+                           (long long)T_max);
+        return OBTE_EINVAL;
+    }
+    const int C = d->n_embd, H = d->n_head, hs = C / H;
+    const int64_t att_bytes = decode ? obte_attn_decode_ws_bytes(d->B, H, hs) : obte_attn_extend_ws_bytes(d->B, H, hs, n, 0);
+    OBTE_REQUIRE(decode || att_bytes > 0, "%s: bad shape (B * n_head <= 65535)", who);
+    const InferLayout w(d->B, n, C, H, ws);
+    const int64_t need = w.total + align256(att_bytes);
+    OBTE_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes, obte_block_%s_ws_bytes() asks for %lld", who, (long long)ws_bytes, decode ? "decode" : "extend",
+                 (long long)need);
+    const InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, att_bytes, rows ? pos_rows : nullptr, n, decode};
+    // uniform: c_attn rotates row b n + j by the tables' row pos + j (rope_T = n on the tables advanced by pos rows); rows form: the FULL tables
+    const int64_t row = at.pos_rows ? 0 : pos * (hs / 2);
+    return infer_sequence(d, x, y_out, w, d->B * n, d->rope_cos + row, d->rope_sin + row, n, at, s);
+}
+
+}  // namespace
+
 // InferLayout at T = 1 (M = B rows) with obte_attn_decode's partials behind it
 extern "C" int64_t obte_block_decode_ws_bytes(int64_t B, int32_t n_embd, int32_t n_head) {
     const int64_t base = obte_block_infer_ws_bytes(B, 1, n_embd, n_head);
@@ -569,45 +608,15 @@ extern "C" int64_t obte_block_decode_ws_bytes(int64_t B, int32_t n_embd, int32_t
 
 extern "C" int obte_block_decode(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, int64_t pos, void* ws,
                                  int64_t ws_bytes, obte_stream s) {
-    TRY(check_desc("obte_block_decode", d));
-    OBTE_REQUIRE(d->T == 1, "obte_block_decode: one new position per row (T = 1), got T = %lld", (long long)d->T);
-    if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
-        obte_set_error("obte_block_decode: key_ranges, mask, query_bounds, out_rows and dropout_p must be NULL / 0 (the new position sees every cached one)");
-        return OBTE_EUNSUPPORTED;
-    }
-    OBTE_REQUIRE(x && y_out && kv_cache && ws, "obte_block_decode: null pointer");
-    OBTE_REQUIRE(pos >= 0 && pos < T_max, "obte_block_decode: position %lld outside the cache's [0, %lld)", (long long)pos, (long long)T_max);
-    const int C = d->n_embd, H = d->n_head, hs = C / H;
-    const InferLayout w(d->B, 1, C, H, ws);
-    const int64_t dec_bytes = obte_attn_decode_ws_bytes(d->B, H, hs), need = w.total + align256(dec_bytes);
-    OBTE_REQUIRE(ws_bytes >= need, "obte_block_decode: workspace of %lld bytes, obte_block_decode_ws_bytes() asks for %lld", (long long)ws_bytes, (long long)need);
-    const InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, dec_bytes};
-    const int64_t row = pos * (hs / 2);   // the tables' row `pos`: with rope_T = 1 every row of the product is rotated by it
-    return infer_sequence(d, x, y_out, w, d->B, d->rope_cos + row, d->rope_sin + row, 1, at, s);
+    return cached_step("obte_block_decode", d, x, y_out, kv_cache, T_max, pos, nullptr, false, true, ws, ws_bytes, s);
 }
 
 extern "C" int obte_block_decode_rows(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, const int32_t* pos,
                                       int64_t max_pos, void* ws, int64_t ws_bytes, obte_stream s) {
-    TRY(check_desc("obte_block_decode_rows", d));
-    OBTE_REQUIRE(d->T == 1, "obte_block_decode_rows: one new position per row (T = 1), got T = %lld", (long long)d->T);
-    if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
-        obte_set_error("obte_block_decode_rows: key_ranges, mask, query_bounds, out_rows and dropout_p must be NULL / 0 (the new position sees every cached one)");
-        return OBTE_EUNSUPPORTED;
-    }
-    OBTE_REQUIRE(x && y_out && kv_cache && pos && ws, "obte_block_decode_rows: null pointer");
-    OBTE_REQUIRE(max_pos >= 0 && max_pos < T_max, "obte_block_decode_rows: max_pos = %lld outside the cache's [0, %lld)", (long long)max_pos, (long long)T_max);
-    const int C = d->n_embd, H = d->n_head, hs = C / H;
-    const InferLayout w(d->B, 1, C, H, ws);
-    const int64_t dec_bytes = obte_attn_decode_ws_bytes(d->B, H, hs), need = w.total + align256(dec_bytes);
-    OBTE_REQUIRE(ws_bytes >= need, "obte_block_decode_rows: workspace of %lld bytes, obte_block_decode_ws_bytes() asks for %lld", (long long)ws_bytes,
-                 (long long)need);
-    InferAttention at = {kv_cache, T_max, max_pos, (char*)ws + w.total, dec_bytes};
-    at.pos_rows = pos;
-    return infer_sequence(d, x, y_out, w, d->B, d->rope_cos, d->rope_sin, 1, at, s);
+    return cached_step("obte_block_decode_rows", d, x, y_out, kv_cache, T_max, max_pos, pos, true, true, ws, ws_bytes, s);
 }
 
-// ---- n new positions per row against the cache (include/omnibiote_hip_extend.h) --------------------------------------------------------------
-// InferLayout at T = n_new (M = B n_new rows) with obte_attn_extend's partials behind it
+// InferLayout at T = n_new (M = B n_new rows) with obte_attn_extend's partials behind it (include/omnibiote_hip_extend.h)
 extern "C" int64_t obte_block_extend_ws_bytes(int64_t B, int64_t n_new, int32_t n_embd, int32_t n_head) {
     const int64_t base = obte_block_infer_ws_bytes(B, n_new, n_embd, n_head);
     const int64_t part = base > 0 ? obte_attn_extend_ws_bytes(B, n_head, n_embd / n_head, n_new, 0) : 0;
@@ -616,27 +625,7 @@ extern "C" int64_t obte_block_extend_ws_bytes(int64_t B, int64_t n_new, int32_t 
 
 extern "C" int obte_block_extend(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, int64_t pos,
                                  const int32_t* pos_rows, void* ws, int64_t ws_bytes, obte_stream s) {
-    TRY(check_desc("obte_block_extend", d));
-    if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
-        obte_set_error("obte_block_extend: key_ranges, mask, query_bounds, out_rows and dropout_p must be NULL / 0 (a new position sees every cached one up to itself)");
-        return OBTE_EUNSUPPORTED;
-    }
-    OBTE_REQUIRE(x && y_out && kv_cache && ws, "obte_block_extend: null pointer");
-    const int64_t n = d->T;
-    OBTE_REQUIRE(pos >= 0 && pos + n <= T_max, "obte_block_extend: positions [%lld, %lld) (d->T = %lld new ones) do not fit the cache's [0, %lld)", (long long)pos,
-                 (long long)(pos + n), (long long)n, (long long)T_max);
-    const int C = d->n_embd, H = d->n_head, hs = C / H;
-    const int64_t ext_bytes = obte_attn_extend_ws_bytes(d->B, H, hs, n, 0);
-    OBTE_REQUIRE(ext_bytes > 0, "obte_block_extend: bad shape (B * n_head <= 65535)");
-    const InferLayout w(d->B, n, C, H, ws);
-    const int64_t need = w.total + align256(ext_bytes);
-    OBTE_REQUIRE(ws_bytes >= need, "obte_block_extend: workspace of %lld bytes, obte_block_extend_ws_bytes() asks for %lld", (long long)ws_bytes, (long long)need);
-    InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, ext_bytes};
-    at.pos_rows = pos_rows;
-    at.n_new = n;
-    // uniform: c_attn rotates row b n + j by the tables' row pos + j (rope_T = n on the tables advanced by pos rows); rows form: the FULL tables
-    const int64_t row = pos_rows ? 0 : pos * (hs / 2);
-    return infer_sequence(d, x, y_out, w, d->B * n, d->rope_cos + row, d->rope_sin + row, n, at, s);
+    return cached_step("obte_block_extend", d, x, y_out, kv_cache, T_max, pos, pos_rows, pos_rows != nullptr, false, ws, ws_bytes, s);
 }
 
 extern "C" int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,

@@ -867,19 +867,85 @@ def ragged_output(idx, lengths, tokens, valid, pad_token):
     return out, (lens + n_new).view(b)
 
 
-class KVCache:
-    """The rotated keys and the values of every layer of ``model`` for ``batch`` sequences of up to ``max_len`` positions
-    (default and at most ``config.block_size``): one buffer per layer (include/omnibiote_hip.h, obte_kv_cache_bytes), the workspace of
-    a decode step, and ``pos``, the number of positions filled — a host integer, the same for every row.  ``OmniBioTA.prefill``
-    starts it over (nothing is cleared: positions beyond ``pos`` are never read), ``decode_step`` advances it by one token per row,
-    ``extend`` by several, ``rewind`` steps back.
+class CachePositions:
+    """Where a key/value cache of ``batch`` rows and ``max_len`` positions stands, and the only code that moves it: host integers and one
+    device tensor, no buffer, so it can be built and driven without a GPU (``KVCache`` adds the buffers).
 
-    After a prefill with ``lengths`` the rows stand at different positions: ``positions`` is then an int32 (B,) device tensor, row b's
-    next position (the kernels read it there; a negative value parks a finished row: it stores nothing and attends to nothing), and
-    ``max_pos`` the host's upper bound on it; ``decode_step`` advances both.  In this mode ``pos`` says nothing about a single row: it
-    is kept equal to ``max_pos``, the positions filled in the longest row.  ``positions is None`` is the uniform mode above.  The three
-    are set together by ``prefill`` and ``decode_step``; code that sets one by hand sets the others to match.  ``min_pos``, where it
-    exists, is a host-side lower bound on the shortest row that is not parked; only ``rewind`` reads it, and does without it if need be."""
+    ``pos``: the positions filled, a host integer.  Uniform mode (``positions is None``): the same for every row.  After a prefill with
+    ``lengths`` the rows stand at different positions: ``positions`` is then an int32 (B,) device tensor, row b's next position (the
+    kernels read it there; a negative value parks a finished row: it stores nothing and attends to nothing), ``pos`` the host's upper
+    bound on it — the longest row — and ``min_pos`` a host-side lower bound on the shortest row that is not parked (0: unknown; only
+    ``rewind`` reads it).  ``reset``, ``advance``, ``park`` and ``rewind`` are the only writers of the three."""
+
+    def __init__(self, batch, max_len):
+        self.batch, self.max_len = int(batch), int(max_len)
+        self.reset(0)
+
+    @property
+    def max_pos(self):
+        """the host's bound on ``positions`` (0 in uniform mode)"""
+        return self.pos if self.positions is not None else 0
+
+    def reset(self, pos, positions=None, min_pos=0):
+        """The state after a prefill, or set by hand: ``pos`` positions filled; ``positions`` a ready int32 (B,) tensor on the kernels'
+        device with ``pos`` its upper bound, ``min_pos`` a lower bound on its active rows.  Host assignments only, nothing is copied."""
+        self.pos, self.positions, self.min_pos = int(pos), positions, int(min_pos)
+
+    def require_room(self, what, n, detail=False):
+        """ValueError in ``OmniBioTA.what``'s name unless ``n`` more positions fit"""
+        if self.pos + n > self.max_len:
+            tail = f": {n} more from {self.pos} do not fit" if detail else ""
+            raise ValueError(f"OmniBioTA.{what}: the cache's {self.max_len} positions are full{tail}")
+
+    def advance(self, n):
+        """``n`` more positions are filled in every row that is not parked.  ``positions`` becomes a new tensor (launches already queued
+        read the old one); the update is queued on the stream and nothing waits for it."""
+        self.pos += n
+        if self.positions is not None:
+            self.positions = torch.add(self.positions, self.positions >= 0, alpha=n)   # int32 + n * bool: int32; parked rows (< 0) stay
+            self.min_pos += n
+
+    def park(self, done):
+        """Park the rows where ``done`` (bool (B,)) holds: they store nothing and read nothing from here on.  Rows mode only."""
+        self.positions = torch.where(done, torch.full_like(self.positions, -1), self.positions)
+
+    def rewind(self, n):
+        """Step back by ``n`` positions: ``pos -= n``, and after a prefill with ``lengths`` the rows not parked step back by ``n`` each.
+        This is what a caller does with rejected draft tokens: ``extend`` the cache by the drafted block, keep the accepted prefix, rewind
+        the rest.  No kernel of the library runs and nothing is cleared — positions beyond ``pos`` are never read, and the next tokens
+        overwrite them.  With ``positions`` set, the one elementwise update of that tensor is queued on the stream and the host does not
+        wait for it: a draft-and-verify loop (extend by k, rewind by fewer) never synchronises here.  ValueError if a row would be left
+        with fewer than one position."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"KVCache.rewind: n must not be negative, got {n}")
+        if self.positions is None:
+            if self.pos - n < 1:
+                raise ValueError(f"KVCache.rewind: {n} positions back from {self.pos} leaves fewer than one")
+            self.pos -= n
+            return
+        # The shortest active row, bounded from below on the host (reset sets ``min_pos``, advance and this move it; parked rows only leave
+        # it too low, which is safe): while the bound allows the step nothing waits for the device.  Only where it does not — or on a
+        # cache whose positions were set without a bound — are the positions themselves read, which synchronises.
+        low = self.min_pos
+        if self.pos - n < 1:
+            raise ValueError(f"KVCache.rewind: {n} positions back leaves a row with fewer than one")
+        if low - n < 1:
+            active = [p for p in self.positions.tolist() if p >= 0]
+            low = min(active) if active else n + 1
+            if low - n < 1:
+                raise ValueError(f"KVCache.rewind: {n} positions back leaves a row with fewer than one")
+        self.positions = self.positions - n * (self.positions >= 0).to(torch.int32)   # (parked rows, < 0, stay as they are)
+        self.min_pos = low - n
+        self.pos -= n
+
+
+class KVCache(CachePositions):
+    """The rotated keys and the values of every layer of ``model`` for ``batch`` sequences of up to ``max_len`` positions
+    (default and at most ``config.block_size``): one buffer per layer (include/omnibiote_hip.h, obte_kv_cache_bytes), the workspaces of
+    a decode step and of ``extend``, and where the rows stand (``CachePositions``).  ``OmniBioTA.prefill`` starts it over (nothing is
+    cleared: positions beyond ``pos`` are never read), ``decode_step`` advances it by one token per row, ``extend`` by several,
+    ``rewind`` steps back."""
 
     def __init__(self, model, batch, max_len=None):
         cfg = model.config
@@ -892,43 +958,11 @@ class KVCache:
             raise ValueError(f"KVCache: batch must be at least 1, got {batch}")
         wte = model.transformer.wte.weight
         _require_hip(wte, "KVCache")
-        self.batch, self.max_len, self.pos = int(batch), max_len, 0
-        self.positions, self.max_pos = None, 0
+        super().__init__(batch, max_len)
         hs = cfg.n_embd // cfg.n_head
         self.layers = [ops.kv_cache_buffer(self.batch, max_len, cfg.n_head, hs, wte.device) for _ in model.transformer.h]
         self.decode_ws = ops.block_decode_workspace(self.batch, cfg.n_embd, cfg.n_head, wte.device)
         self.extend_ws = None   # OmniBioTA.extend's workspace: allocated by the first call, replaced when a call needs more bytes
-
-    def rewind(self, n):
-        """Step back by ``n`` positions: ``pos -= n``, and after a prefill with ``lengths`` the rows not parked step back by ``n`` each,
-        ``max_pos`` and ``pos`` with them.  This is what a caller does with rejected draft tokens: ``extend`` the cache by the drafted
-        block, keep the accepted prefix, rewind the rest.  No kernel of the library runs and nothing is cleared — positions beyond
-        ``pos`` are never read, and the next tokens overwrite them.  With ``positions`` set, the one elementwise update of that tensor
-        is queued on the stream and the host does not wait for it: a draft-and-verify loop (extend by k, rewind by fewer) never
-        synchronises here.  ValueError if a row would be left with fewer than one position."""
-        n = int(n)
-        if n < 0:
-            raise ValueError(f"KVCache.rewind: n must not be negative, got {n}")
-        if self.positions is None:
-            if self.pos - n < 1:
-                raise ValueError(f"KVCache.rewind: {n} positions back from {self.pos} leaves fewer than one")
-            self.pos -= n
-            return
-        # The shortest active row, bounded from below on the host (prefill sets ``min_pos``, extend and this advance it; decode steps and
-        # parked rows only leave it too low, which is safe): while the bound allows the step nothing waits for the device.  Only where it
-        # does not — or on a cache whose positions were set by hand — are the positions themselves read, which synchronises.
-        low = getattr(self, "min_pos", 0)
-        if self.max_pos - n < 1:
-            raise ValueError(f"KVCache.rewind: {n} positions back leaves a row with fewer than one")
-        if low - n < 1:
-            active = [p for p in self.positions.tolist() if p >= 0]
-            low = min(active) if active else n + 1
-            if low - n < 1:
-                raise ValueError(f"KVCache.rewind: {n} positions back leaves a row with fewer than one")
-        self.positions = self.positions - n * (self.positions >= 0).to(torch.int32)   # (parked rows, < 0, stay as they are)
-        self.min_pos = low - n
-        self.max_pos -= n
-        self.pos = self.max_pos
 
 
 class OmniBioTA(nn.Module):
@@ -1048,7 +1082,7 @@ class OmniBioTA(nn.Module):
         ``lengths`` (a host sequence of B ints, 1 <= len_b <= T0): the prompts are right-padded, columns >= len_b of row b hold any
         valid id.  The same kernels run over T0 — under the causal mask a real position never sees a later one, so the padding reaches
         nothing, and the cache positions it fills are overwritten by the row's own new tokens before they are read.  Row b's logits
-        come from position len_b - 1; ``cache.positions`` = lengths and ``cache.max_pos`` = ``cache.pos`` = max(lengths) put ``decode_step`` on the
+        come from position len_b - 1; ``cache.positions`` = lengths and ``cache.pos`` = max(lengths) put ``decode_step`` on the
         one-position-per-row path.
 
         ``chunk`` (an int >= 1; None or >= T0: the call above, bit for bit): the first ``chunk`` columns go through the prefill kernels,
@@ -1077,24 +1111,27 @@ class OmniBioTA(nn.Module):
         ws = ops.block_infer_workspace(b, t, self.config.n_embd, self.config.n_head, idx.device)
         for block, kv in zip(self.transformer.h, cache.layers):
             ops.block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, kv, cache.max_len, ws=ws, out=x)
-        cache.pos = t
+        self._prefilled(cache, t, lens, idx.device)
         if lens is None:
-            cache.positions, cache.max_pos = None, 0
             return self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()))
-        cache.positions, cache.max_pos = torch.tensor(lens, dtype=torch.int32, device=idx.device), max(lens)
-        cache.min_pos = min(lens)                                       # (KVCache.rewind's host-side lower bound)
-        cache.pos = cache.max_pos                                       # (kept in step with max_pos while positions is set)
         last = x[torch.arange(b, device=idx.device), (cache.positions - 1).long()]          # (B, C): row b at its own last position
         return self._readout_rows(self.transformer.ln_f(last.contiguous()))
+
+    @staticmethod
+    def _prefilled(cache, t, lens, device):
+        """the cache's state behind a prompt of ``t`` columns: uniform, or row b at ``lens[b]`` (the tensor the kernels read is made here)"""
+        if lens is None:
+            cache.reset(t)
+        else:
+            cache.reset(max(lens), torch.tensor(lens, dtype=torch.int32, device=device), min(lens))
 
     def _extend_ws(self, cache, device, *ns):
         """The workspace of ``n`` new positions per row for every ``n`` of ``ns``, kept on the cache object and replaced when a call
         needs more BYTES than it has.  The size is not monotone in n — the attention partials shrink where the default split count drops
         (n = 65 asks for less than n = 64 at small B * H) — so the buffer's own size is compared, never the n that made it."""
         need = max(ops.block_extend_ws_bytes(cache.batch, n, self.config.n_embd, self.config.n_head) for n in ns)
-        ws = getattr(cache, "extend_ws", None)
-        if ws is None or ws.numel() < need:
-            cache.extend_ws = ws = None   # (the old buffer goes before the new one comes)
+        if cache.extend_ws is None or cache.extend_ws.numel() < need:
+            cache.extend_ws = None   # (the old buffer goes before the new one comes)
             cache.extend_ws = torch.empty(need, dtype=torch.uint8, device=device)
         return cache.extend_ws
 
@@ -1128,13 +1165,7 @@ class OmniBioTA(nn.Module):
             if rows:
                 rt = torch.tensor(rows, device=dev)
                 last[rt] = x[rt, torch.tensor([last_at[r] - start for r in rows], device=dev)]
-        cache.pos = t
-        if lens is None:
-            cache.positions, cache.max_pos = None, 0
-        else:
-            cache.positions, cache.max_pos = torch.tensor(lens, dtype=torch.int32, device=dev), max(lens)
-            cache.min_pos = min(lens)
-            cache.pos = cache.max_pos
+        self._prefilled(cache, t, lens, dev)
         return self._readout_rows(self.transformer.ln_f(last))
 
     @torch.no_grad()
@@ -1142,7 +1173,7 @@ class OmniBioTA(nn.Module):
         """``tokens`` (B, n) int64: n new tokens per row in one call, row b's at positions ``cache.pos .. cache.pos + n - 1`` (after a
         prefill with ``lengths``: ``cache.positions[b] + j``, read on the device).  Their keys and values join the cache; position j's
         logits predict token j + 1.  Returns (B, vocab), the logits behind the last token, for ``logits="last"`` or (B, n, vocab) for
-        ``"all"`` — what verifying a block of drafted tokens or scoring a continuation needs.  ``pos`` / ``positions`` / ``max_pos`` advance
+        ``"all"`` — what verifying a block of drafted tokens or scoring a continuation needs.  ``pos`` / ``positions`` advance
         by n; parked rows stay parked.  n == 1 is ``decode_step``.  ``KVCache.rewind`` steps back over tokens that are not kept."""
         if tokens.dim() != 2:
             raise ValueError(f"OmniBioTA.extend: tokens must be (B, n), got {tuple(tokens.shape)}")
@@ -1154,23 +1185,14 @@ class OmniBioTA(nn.Module):
         self._check_generation("extend", b, cache)
         if cache.pos == 0:
             raise ValueError("OmniBioTA.extend: the cache is empty: prefill a prompt first")
-        rows = cache.positions is not None
-        at = cache.max_pos if rows else cache.pos
-        if at + n > cache.max_len:
-            raise ValueError(f"OmniBioTA.extend: the cache's {cache.max_len} positions are full: {n} more from {at} do not fit")
+        cache.require_room("extend", n, detail=True)
         if n == 1:
             out = self.decode_step(tokens[:, 0], cache)
             return out if logits == "last" else out.unsqueeze(1)
         if not tokens.is_cuda:
             raise RuntimeError("OmniBioTA.extend: tokens must be on the GPU")
-        x = self._extend_hidden(tokens, cache, at, cache.positions if rows else None)
-        if rows:
-            cache.positions = cache.positions + n * (cache.positions >= 0).to(torch.int32)   # (a new tensor: the launches above read the old one)
-            cache.max_pos += n
-            cache.min_pos = getattr(cache, "min_pos", 0) + n
-            cache.pos = cache.max_pos
-        else:
-            cache.pos += n
+        x = self._extend_hidden(tokens, cache, cache.pos, cache.positions)
+        cache.advance(n)
         if logits == "last":
             return self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()))
         return self._readout_rows(self.transformer.ln_f(x.view(b * n, -1))).view(b, n, -1)
@@ -1180,32 +1202,23 @@ class OmniBioTA(nn.Module):
         """One new token per row, ``tokens`` (B,) int64, at position ``cache.pos`` of every row: its keys and values join the cache
         and the logits of the token after it come back, (B, vocab).  O(1) in projections, one read of the cache per layer.
         After a prefill with ``lengths`` row b's token goes to position ``cache.positions[b]``, read on the device; the positions of
-        the rows not parked (>= 0) then advance by one there, ``cache.max_pos`` on the host.  A parked row's logits mean nothing."""
+        the rows not parked (>= 0) then advance by one there, ``cache.pos`` on the host.  A parked row's logits mean nothing."""
         if tokens.dim() != 1:
             raise ValueError(f"OmniBioTA.decode_step: tokens must be (B,), got {tuple(tokens.shape)}")
         b = tokens.shape[0]
         self._check_generation("decode_step", b, cache)
         if cache.pos == 0:
             raise ValueError("OmniBioTA.decode_step: the cache is empty: prefill a prompt first")
-        rows = cache.positions is not None
-        if (cache.max_pos if rows else cache.pos) >= cache.max_len:
-            raise ValueError(f"OmniBioTA.decode_step: the cache's {cache.max_len} positions are full")
+        cache.require_room("decode_step", 1)
         wte = self.transformer.wte.weight
         if not tokens.is_cuda:
             raise RuntimeError("OmniBioTA.decode_step: tokens must be on the GPU")
         x = ops.embedding_fwd(tokens.contiguous(), wte)
-        if rows:
-            for block, kv in zip(self.transformer.h, cache.layers):
-                ops.block_decode_rows(x, self._block_params(block), block.attn.rope(), self.config.n_head, kv, cache.max_len, cache.positions,
-                                      cache.max_pos, ws=cache.decode_ws, out=x)
-            cache.positions = cache.positions + (cache.positions >= 0)      # int32 + bool: int32 (a new tensor: the launches above read the old one)
-            cache.max_pos += 1
-            cache.pos = cache.max_pos
-            return self._readout_rows(self.transformer.ln_f(x))
+        # rows mode: every row at its own position, read on the device, with pos the host's bound on it
+        step, at = (ops.block_decode, (cache.pos,)) if cache.positions is None else (ops.block_decode_rows, (cache.positions, cache.pos))
         for block, kv in zip(self.transformer.h, cache.layers):
-            ops.block_decode(x, self._block_params(block), block.attn.rope(), self.config.n_head, kv, cache.max_len, cache.pos,
-                             ws=cache.decode_ws, out=x)
-        cache.pos += 1
+            step(x, self._block_params(block), block.attn.rope(), self.config.n_head, kv, cache.max_len, *at, ws=cache.decode_ws, out=x)
+        cache.advance(1)
         return self._readout_rows(self.transformer.ln_f(x))
 
     @torch.no_grad()
@@ -1284,7 +1297,7 @@ class OmniBioTA(nn.Module):
             if i + 1 == max_new_tokens or (eos_token is not None and bool(done.all())):
                 break
             if eos_token is not None:                                   # park the finished rows: they store nothing and read nothing
-                cache.positions = torch.where(done, torch.full_like(cache.positions, -1), cache.positions)
+                cache.park(done)
             logits = self.decode_step(nxt, cache)
         return ragged_output(idx, lens, torch.stack(tokens, dim=1), torch.stack(valid, dim=1), pad)
 

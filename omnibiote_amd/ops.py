@@ -744,20 +744,36 @@ def block_infer_workspace(B, T, Cc, H, device) -> torch.Tensor:
 def block_infer(x, params, rope, H, mask: MaskSpec, dropout_p=0.0, dropout_seed=0, ws=None, out=None):
     """One transformer block forward with nothing kept for a backward (obte_block_fwd_infer): y, bit for bit block_fwd's.
     ws: a buffer from block_infer_workspace for this shape (allocated here when None).  out: where y goes; it may be x itself."""
+    return _block_call(x, params, rope, H, ws, out, block_infer_workspace, lambda d, y, w: L.check(
+        L.lib().obte_block_fwd_infer(d, _ptr(x), _ptr(y), _ptr(w), w.numel(), _stream()), "obte_block_fwd_infer"), mask, dropout_p, dropout_seed)
+
+
+def _block_call(x, params, rope, H, ws, out, new_ws, call, mask=None, dropout_p=0.0, dropout_seed=0, cache=None, T_max=0, rows=None, at=0, one=False):
+    """What block_infer, block_prefill, block_decode, block_decode_rows and block_extend share: the checks of x (B, T, C — or, ``one``, (B, C)
+    at T = 1), the cache, ``rows`` (a per-row int32 tensor and its name), the parameters and the tables (``at`` + T rows of them), the
+    workspace (``new_ws(B, T, C, H, device)`` when ws is None) and the output (x's like when out is None), then ``call(d, y, ws)`` with the
+    descriptor by reference.  Returns y."""
     _need(x, "x")
-    B, T, Cc = x.shape
+    if cache is not None:
+        _need(cache, "cache")
+    if one:
+        (B, Cc), T = x.shape, 1
+    else:
+        B, T, Cc = x.shape
+    if rows is not None:
+        _need_rows(*rows, B)
     for i, w in enumerate(params):
         _need(w, f"param{i}")
     _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
-    assert rope[0].shape[0] >= T
+    assert rope[0].shape[0] >= at + T and (cache is None or cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, Cc // H))
     if ws is None:
-        ws = block_infer_workspace(B, T, Cc, H, x.device)
+        ws = new_ws(B, T, Cc, H, x.device)
     else:
         _need(ws, "ws", torch.uint8)
     y = torch.empty_like(x) if out is None else out
     _need(y, "out"); assert y.shape == x.shape
-    d = _block_desc(B, T, Cc, H, params, rope, mask, dropout_p, dropout_seed)
-    L.check(L.lib().obte_block_fwd_infer(C.byref(d), _ptr(x), _ptr(y), _ptr(ws), ws.numel(), _stream()), "obte_block_fwd_infer")
+    d = _block_desc(B, T, Cc, H, params, rope, MaskSpec() if mask is None else mask, dropout_p, dropout_seed)
+    call(C.byref(d), y, ws)
     return y
 
 
@@ -782,37 +798,33 @@ def attn_decode(q, cache, B, T_max, n_keys, H, hs, scale, splits=0, q_ld=None, w
     """One query per (b, h) over cache positions [0, n_keys) (obte_attn_decode): (o (B, C) bf16, lse (B, H) fp32).  q: any bf16 tensor
     whose row b holds the query of head h at b * q_ld + h * hs (q_ld defaults to its last dimension: 3C reads a packed row in place).
     splits: 0 = the library's choice, else a forced count."""
+    return _attn_decode_call(q, cache, B, T_max, H, hs, q_ld, ws, None, lambda q_ld, o, lse, w: L.check(
+        L.lib().obte_attn_decode(_ptr(q), q_ld, _ptr(cache), _ptr(o), _ptr(lse), B, T_max, n_keys, H, hs, float(scale), int(splits), _ptr(w), w.numel(),
+                                 _stream()), "obte_attn_decode"))
+
+
+def _attn_decode_call(q, cache, B, T_max, H, hs, q_ld, ws, rows, call):
+    """What attn_decode and attn_decode_rows (``rows``: its per-row counts) share: the checks, the default q_ld and workspace, the outputs,
+    then ``call(q_ld, o, lse, ws)``.  Returns (o, lse)."""
     _need(q, "q"); _need(cache, "cache")
+    if rows is not None:
+        _need_rows(rows, "n_keys", B)
     q_ld = q.shape[-1] if q_ld is None else q_ld
     assert q.numel() >= (B - 1) * q_ld + H * hs and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, hs)
     o = torch.empty((B, H * hs), dtype=bf16, device=q.device)
     lse = torch.empty((B, H), dtype=torch.float32, device=q.device)
     if ws is None:
         ws = torch.empty(int(L.lib().obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=q.device)
-    L.check(L.lib().obte_attn_decode(_ptr(q), q_ld, _ptr(cache), _ptr(o), _ptr(lse), B, T_max, n_keys, H, hs, float(scale), int(splits),
-                                     _ptr(ws), ws.numel(), _stream()), "obte_attn_decode")
+    call(q_ld, o, lse, ws)
     return o, lse
 
 
 def block_prefill(x, params, rope, H, mask: MaskSpec, cache, T_max, ws=None, out=None):
     """block_infer (y bit for bit its y, the same workspace) that also leaves the block's rotated keys and its values in positions
     [0, T) of `cache` (obte_block_fwd_prefill).  No dropout on a generation path."""
-    _need(x, "x"); _need(cache, "cache")
-    B, T, Cc = x.shape
-    for i, w in enumerate(params):
-        _need(w, f"param{i}")
-    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
-    assert rope[0].shape[0] >= T and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, Cc // H)
-    if ws is None:
-        ws = block_infer_workspace(B, T, Cc, H, x.device)
-    else:
-        _need(ws, "ws", torch.uint8)
-    y = torch.empty_like(x) if out is None else out
-    _need(y, "out"); assert y.shape == x.shape
-    d = _block_desc(B, T, Cc, H, params, rope, mask)
-    L.check(L.lib().obte_block_fwd_prefill(C.byref(d), _ptr(x), _ptr(y), _ptr(ws), ws.numel(), _ptr(cache), T_max, _stream()),
-            "obte_block_fwd_prefill")
-    return y
+    return _block_call(x, params, rope, H, ws, out, block_infer_workspace, lambda d, y, w: L.check(
+        L.lib().obte_block_fwd_prefill(d, _ptr(x), _ptr(y), _ptr(w), w.numel(), _ptr(cache), T_max, _stream()), "obte_block_fwd_prefill"),
+        mask, cache=cache, T_max=T_max)
 
 
 def block_decode_workspace(B, Cc, H, device) -> torch.Tensor:
@@ -826,22 +838,13 @@ def block_decode_workspace(B, Cc, H, device) -> torch.Tensor:
 def block_decode(x, params, rope, H, cache, T_max, pos, ws=None, out=None):
     """One new position per batch row, every row at position `pos`, against the cache (obte_block_decode): x (B, C) -> y (B, C).
     rope: the FULL tables (at least pos + 1 rows).  out may be x itself."""
-    _need(x, "x"); _need(cache, "cache")
-    B, Cc = x.shape
-    for i, w in enumerate(params):
-        _need(w, f"param{i}")
-    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
-    assert rope[0].shape[0] > pos and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, Cc // H)
-    if ws is None:
-        ws = block_decode_workspace(B, Cc, H, x.device)
-    else:
-        _need(ws, "ws", torch.uint8)
-    y = torch.empty_like(x) if out is None else out
-    _need(y, "out"); assert y.shape == x.shape
-    d = _block_desc(B, 1, Cc, H, params, rope, MaskSpec())
-    L.check(L.lib().obte_block_decode(C.byref(d), _ptr(x), _ptr(y), _ptr(cache), T_max, pos, _ptr(ws), ws.numel(), _stream()),
-            "obte_block_decode")
-    return y
+    return _block_call(x, params, rope, H, ws, out, _decode_ws, lambda d, y, w: L.check(
+        L.lib().obte_block_decode(d, _ptr(x), _ptr(y), _ptr(cache), T_max, pos, _ptr(w), w.numel(), _stream()), "obte_block_decode"),
+        cache=cache, T_max=T_max, at=pos, one=True)
+
+
+def _decode_ws(B, T, Cc, H, device):
+    return block_decode_workspace(B, Cc, H, device)
 
 
 # ---- one cache position per row: a batch whose rows stand at different positions (include/omnibiote_hip_rows.h, the row convention) ----
@@ -867,38 +870,17 @@ def kv_cache_rope_store_rows(qkv, rope, pos, max_pos, B, H, hs, cache, T_max):
 def attn_decode_rows(q, cache, B, T_max, n_keys, max_keys, H, hs, scale, splits=0, q_ld=None, ws=None):
     """attn_decode with one key count per row (obte_attn_decode_rows): n_keys int32 (B,) on the device, row b over cache positions
     [0, n_keys[b]); a row whose count lies outside [1, max_keys] gives zeros and lse = -inf.  splits = 0: the library's choice at max_keys."""
-    _need(q, "q"); _need(cache, "cache"); _need_rows(n_keys, "n_keys", B)
-    q_ld = q.shape[-1] if q_ld is None else q_ld
-    assert q.numel() >= (B - 1) * q_ld + H * hs and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, hs)
-    o = torch.empty((B, H * hs), dtype=bf16, device=q.device)
-    lse = torch.empty((B, H), dtype=torch.float32, device=q.device)
-    if ws is None:
-        ws = torch.empty(int(L.lib().obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=q.device)
-    L.check(L.lib().obte_attn_decode_rows(_ptr(q), q_ld, _ptr(cache), _ptr(o), _ptr(lse), B, T_max, _ptr(n_keys), int(max_keys), H, hs, float(scale),
-                                          int(splits), _ptr(ws), ws.numel(), _stream()), "obte_attn_decode_rows")
-    return o, lse
+    return _attn_decode_call(q, cache, B, T_max, H, hs, q_ld, ws, n_keys, lambda q_ld, o, lse, w: L.check(
+        L.lib().obte_attn_decode_rows(_ptr(q), q_ld, _ptr(cache), _ptr(o), _ptr(lse), B, T_max, _ptr(n_keys), int(max_keys), H, hs, float(scale),
+                                      int(splits), _ptr(w), w.numel(), _stream()), "obte_attn_decode_rows"))
 
 
 def block_decode_rows(x, params, rope, H, cache, T_max, pos, max_pos, ws=None, out=None):
     """block_decode with row b at position pos[b] (obte_block_decode_rows): pos int32 (B,) on the device, read there; max_pos the host's
     bound on it (a row outside [0, max_pos] stores nothing and attends to nothing).  rope: the FULL tables.  out may be x itself."""
-    _need(x, "x"); _need(cache, "cache")
-    B, Cc = x.shape
-    _need_rows(pos, "pos", B)
-    for i, w in enumerate(params):
-        _need(w, f"param{i}")
-    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
-    assert rope[0].shape[0] > max_pos and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, Cc // H)
-    if ws is None:
-        ws = block_decode_workspace(B, Cc, H, x.device)
-    else:
-        _need(ws, "ws", torch.uint8)
-    y = torch.empty_like(x) if out is None else out
-    _need(y, "out"); assert y.shape == x.shape
-    d = _block_desc(B, 1, Cc, H, params, rope, MaskSpec())
-    L.check(L.lib().obte_block_decode_rows(C.byref(d), _ptr(x), _ptr(y), _ptr(cache), T_max, _ptr(pos), int(max_pos), _ptr(ws), ws.numel(), _stream()),
-            "obte_block_decode_rows")
-    return y
+    return _block_call(x, params, rope, H, ws, out, _decode_ws, lambda d, y, w: L.check(
+        L.lib().obte_block_decode_rows(d, _ptr(x), _ptr(y), _ptr(cache), T_max, _ptr(pos), int(max_pos), _ptr(w), w.numel(), _stream()),
+        "obte_block_decode_rows"), cache=cache, T_max=T_max, rows=(pos, "pos"), at=max_pos, one=True)
 
 
 # ---- n new positions per row against a filled cache (include/omnibiote_hip_extend.h) ----
@@ -953,24 +935,9 @@ def block_extend(x, params, rope, H, cache, T_max, pos, pos_rows=None, ws=None, 
     """n new positions per batch row against the cache (obte_block_extend): x (B, n, C) -> y (B, n, C).  Row b's positions start at
     `pos`, or at pos_rows[b] (int32 (B,) on the device, read there; pos is then the host's bound on it, and a row outside [0, pos] stores
     nothing and attends to nothing).  rope: the FULL tables (at least pos + n rows).  out may be x itself."""
-    _need(x, "x"); _need(cache, "cache")
-    B, n, Cc = x.shape
-    if pos_rows is not None:
-        _need_rows(pos_rows, "pos_rows", B)
-    for i, w in enumerate(params):
-        _need(w, f"param{i}")
-    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
-    assert rope[0].shape[0] >= pos + n and cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, Cc // H)
-    if ws is None:
-        ws = block_extend_workspace(B, n, Cc, H, x.device)
-    else:
-        _need(ws, "ws", torch.uint8)
-    y = torch.empty_like(x) if out is None else out
-    _need(y, "out"); assert y.shape == x.shape
-    d = _block_desc(B, n, Cc, H, params, rope, MaskSpec())
-    L.check(L.lib().obte_block_extend(C.byref(d), _ptr(x), _ptr(y), _ptr(cache), T_max, int(pos), _ptr(pos_rows), _ptr(ws), ws.numel(), _stream()),
-            "obte_block_extend")
-    return y
+    return _block_call(x, params, rope, H, ws, out, block_extend_workspace, lambda d, y, w: L.check(
+        L.lib().obte_block_extend(d, _ptr(x), _ptr(y), _ptr(cache), T_max, int(pos), _ptr(pos_rows), _ptr(w), w.numel(), _stream()), "obte_block_extend"),
+        cache=cache, T_max=T_max, rows=None if pos_rows is None else (pos_rows, "pos_rows"), at=pos)
 
 
 def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None, dropout_p=0.0, dropout_seed=0, ln_partials=None,

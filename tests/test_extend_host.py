@@ -1,11 +1,10 @@
 """Host-side tests (no GPU) of continuing a filled key/value cache by several positions per row (include/omnibiote_hip_extend.h): the
 symbol table against the header, the pins of the ABI, the default split rule of obte_attn_extend, the workspace sizes, every argument
 check that returns before a launch, and the validation of OmniBioTA.extend / KVCache.rewind / prefill(chunk=) on a CPU model with a
-stand-in cache."""
+cache's position state alone, and that state's own transitions."""
 import ctypes as C
 import os
 import re
-from types import SimpleNamespace
 
 import pytest
 import torch
@@ -155,9 +154,13 @@ def _cpu_model(autoregressive=True, block_size=32):
     return OmniBioTA(c)
 
 
-def _fake(pos=8, batch=2, max_len=32, positions=None, max_pos=0):
-    """what prefill / decode_step / generate know of a cache, and nothing this feature adds"""
-    return SimpleNamespace(batch=batch, max_len=max_len, pos=pos, positions=positions, max_pos=max_pos, layers=[None], decode_ws=None)
+def _fake(pos=8, batch=2, max_len=32, positions=None, min_pos=0):
+    """a cache's position state (the host-only class KVCache is built on) with no buffer behind it"""
+    from omnibiote_amd.model import CachePositions
+    c = CachePositions(batch, max_len)
+    c.reset(pos, positions, min_pos)
+    c.layers, c.decode_ws, c.extend_ws = [None], None, None
+    return c
 
 
 def test_extend_validates_before_any_device_work():
@@ -176,7 +179,7 @@ def test_extend_validates_before_any_device_work():
     with pytest.raises(ValueError, match="positions are full"):
         m.extend(tok, _fake(pos=29))                                                     # 29 + 4 > 32
     with pytest.raises(ValueError, match="positions are full"):
-        m.extend(tok, _fake(pos=29, positions=torch.tensor([20, 29], dtype=torch.int32), max_pos=29))
+        m.extend(tok, _fake(pos=29, positions=torch.tensor([20, 29], dtype=torch.int32)))
     with pytest.raises(ValueError, match="logits"):
         m.extend(tok, _fake(), logits="first")
     with pytest.raises(ValueError, match="autoregressive"):
@@ -200,7 +203,7 @@ def test_rewind():
     with pytest.raises(ValueError, match="negative"):
         KVCache.rewind(c, -1)
     assert c.pos == 1
-    r = _fake(pos=12, positions=torch.tensor([7, -1, 12], dtype=torch.int32), max_pos=12, batch=3)
+    r = _fake(pos=12, positions=torch.tensor([7, -1, 12], dtype=torch.int32), batch=3)
     KVCache.rewind(r, 5)
     assert r.positions.tolist() == [2, -1, 7] and r.positions.dtype == torch.int32 and r.max_pos == r.pos == 7
     KVCache.rewind(r, 1)
@@ -225,8 +228,7 @@ def test_rewind_waits_for_the_device_only_where_the_host_bound_does_not_settle_i
         def __ge__(self, other):
             return self.t >= other
 
-    r = _fake(pos=20, positions=Positions([12, -1, 20]), max_pos=20, batch=3)
-    r.min_pos = 12                                                                       # as prefill(lengths=) and extend leave it
+    r = _fake(pos=20, positions=Positions([12, -1, 20]), batch=3, min_pos=12)            # as prefill(lengths=) and extend leave it
     first = r.positions
     KVCache.rewind(r, 5)
     assert first.reads == 0 and r.positions.t.tolist() == [7, -1, 15] and r.min_pos == 7 and r.max_pos == r.pos == 15
@@ -259,20 +261,93 @@ def test_extend_workspace_is_judged_by_its_bytes():
     assert m._extend_ws(c, "cpu", 66, 64).numel() == max(need(66), need(64))             # prefill(chunk=66) on 130 tokens: one buffer for both
 
 
-def test_prefill_and_decode_step_read_no_new_cache_field():
+def test_prefill_and_decode_step_fail_first_at_the_device():
     m = _cpu_model()
     idx = torch.zeros(2, 8, dtype=torch.int64)
     with pytest.raises(ValueError, match="chunk"):
         m.prefill(idx, _fake(pos=0), chunk=0)
     with pytest.raises(ValueError, match="chunk"):
         m.prefill(idx, _fake(pos=0), chunk=-3)
-    # the existing paths on a stand-in that has none of the new attributes: their old first device-side failure, no AttributeError
+    # every path on a cache state without buffers: its first device-side failure, no AttributeError
     for kw in (dict(), dict(chunk=None), dict(chunk=8), dict(chunk=100), dict(chunk=4), dict(lengths=[3, 8])):
         with pytest.raises(RuntimeError, match="MI355X|GPU"):
             m.prefill(idx, _fake(pos=0), **kw)
     with pytest.raises(RuntimeError, match="GPU"):
         m.decode_step(torch.zeros(2, dtype=torch.int64), _fake())
     with pytest.raises(RuntimeError, match="GPU"):
-        m.decode_step(torch.zeros(2, dtype=torch.int64), _fake(positions=torch.tensor([3, 8], dtype=torch.int32), max_pos=8))
+        m.decode_step(torch.zeros(2, dtype=torch.int64), _fake(positions=torch.tensor([3, 8], dtype=torch.int32)))
     with pytest.raises(RuntimeError, match="GPU"):                                       # n == 1 is decode_step
         m.extend(torch.zeros(2, 1, dtype=torch.int64), _fake())
+
+
+# ------------------------------------------------------------------------------------------------------- the position state
+def _i32(*v):
+    return torch.tensor(v, dtype=torch.int32)
+
+
+def _state(c):
+    return c.pos, None if c.positions is None else c.positions.tolist(), c.min_pos, c.max_pos
+
+
+def test_cache_positions_uniform():
+    from omnibiote_amd.model import CachePositions
+    c = CachePositions(2, 32)
+    assert (c.batch, c.max_len) == (2, 32) and _state(c) == (0, None, 0, 0)
+    c.reset(8)
+    assert _state(c) == (8, None, 0, 0)                                                  # max_pos: 0 in uniform mode
+    c.advance(5)
+    c.advance(1)
+    assert _state(c) == (14, None, 0, 0)
+    c.rewind(6)
+    assert _state(c) == (8, None, 0, 0)
+    with pytest.raises(AttributeError):
+        c.max_pos = 3                                                                    # read-only: pos is the one bound
+
+
+def test_cache_positions_rows():
+    from omnibiote_amd.model import CachePositions
+    c = CachePositions(3, 32)
+    at = _i32(7, 3, 12)
+    c.reset(12, at, min_pos=3)
+    assert c.positions is at and _state(c) == (12, [7, 3, 12], 3, 12)                    # the ready tensor is taken as it is; max_pos is pos
+    c.advance(4)
+    assert c.positions is not at and at.tolist() == [7, 3, 12]                           # a new tensor: queued launches read the old one
+    assert c.positions.dtype == torch.int32 and _state(c) == (16, [11, 7, 16], 7, 16)
+    c.advance(1)                                                                         # a decode step moves min_pos too
+    assert c.positions.dtype == torch.int32 and _state(c) == (17, [12, 8, 17], 8, 17)
+    before = c.positions
+    c.park(torch.tensor([False, True, False]))
+    assert c.positions is not before and c.positions.dtype == torch.int32 and _state(c) == (17, [12, -1, 17], 8, 17)
+    c.advance(3)                                                                         # a parked row stays parked
+    assert _state(c) == (20, [15, -1, 20], 11, 20)
+    c.reset(5)                                                                           # back to uniform
+    assert _state(c) == (5, None, 0, 0)
+
+
+@pytest.mark.parametrize("positions", [None, (7, 3, 12), (7, -1, 12)])
+@pytest.mark.parametrize("n", [1, 2, 9])
+def test_advance_then_rewind_is_the_identity(positions, n):
+    from omnibiote_amd.model import CachePositions
+    c = CachePositions(3, 64)
+    if positions is None:
+        c.reset(12)
+    else:
+        c.reset(12, _i32(*positions), min_pos=3)
+    was = _state(c)
+    c.advance(n)
+    assert c.pos == 12 + n
+    c.rewind(n)
+    assert _state(c) == was and (c.positions is None or c.positions.dtype == torch.int32)
+
+
+def test_require_room_words_the_error_per_caller():
+    from omnibiote_amd.model import CachePositions
+    c = CachePositions(2, 32)
+    c.reset(29, _i32(20, 29))
+    c.require_room("extend", 3, detail=True)
+    c.require_room("decode_step", 1)
+    with pytest.raises(ValueError, match=r"OmniBioTA\.extend: the cache's 32 positions are full: 4 more from 29 do not fit"):
+        c.require_room("extend", 4, detail=True)
+    c.advance(3)
+    with pytest.raises(ValueError, match=r"OmniBioTA\.decode_step: the cache's 32 positions are full$"):
+        c.require_room("decode_step", 1)

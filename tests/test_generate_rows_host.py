@@ -4,7 +4,6 @@ the assembly of a ragged generate()'s result as a pure function on CPU tensors."
 import ctypes as C
 import os
 import re
-import types
 
 import pytest
 import torch
@@ -106,11 +105,13 @@ def _cpu_model(block_size=32):
     return OmniBioTA(c)
 
 
-def _fake_cache(batch=2, max_len=32, **over):
+def _fake_cache(batch=2, max_len=32, pos=0, positions=None):
     """what prefill / decode_step look at before any device work (a KVCache itself allocates on the GPU)"""
-    f = dict(batch=batch, max_len=max_len, pos=0, positions=None, max_pos=0, layers=[], decode_ws=None)
-    f.update(over)
-    return types.SimpleNamespace(**f)
+    from omnibiote_amd.model import CachePositions
+    c = CachePositions(batch, max_len)
+    c.reset(pos, positions)
+    c.layers, c.decode_ws, c.extend_ws = [], None, None
+    return c
 
 
 def test_lengths_are_validated_before_any_device_work():
@@ -138,14 +139,14 @@ def test_lengths_are_validated_before_any_device_work():
 def test_decode_step_refuses_a_full_ragged_cache():
     m = _cpu_model()
     tok = torch.zeros(2, dtype=torch.int64)
-    full = _fake_cache(pos=8, positions=torch.tensor([20, 32], dtype=torch.int32), max_pos=32)
+    full = _fake_cache(pos=32, positions=torch.tensor([20, 32], dtype=torch.int32))
     with pytest.raises(ValueError, match="full"):
         m.decode_step(tok, full)
     # the uniform rule is untouched: `pos`, not `max_pos`, decides there
     with pytest.raises(ValueError, match="full"):
         m.decode_step(tok, _fake_cache(pos=32))
     with pytest.raises(RuntimeError, match="GPU"):                 # room left: the next thing it notices is the CPU tensor
-        m.decode_step(tok, _fake_cache(pos=8, positions=torch.tensor([20, 31], dtype=torch.int32), max_pos=31))
+        m.decode_step(tok, _fake_cache(pos=31, positions=torch.tensor([20, 31], dtype=torch.int32)))
 
 
 def test_generate_without_new_tokens_returns_the_padded_prompts():

@@ -516,7 +516,7 @@ def test_extend_after_a_ragged_prefill(Cc):
     d = (got - want).abs()
     print(f"extend after a ragged prefill, C={Cc}: max {d.max().item():.4g} mean {d.mean().item():.4g}")
     assert torch.isfinite(got).all() and d.max().item() <= 5e-3 and d.mean().item() <= 1e-3, (d.max().item(), d.mean().item())
-    cache.positions = torch.where(_i32((0, 1)) == 0, _i32((-1, -1)), cache.positions)      # park row 0
+    cache.park(_i32((0, 1)) == 0)                                                          # park row 0
     m.extend(tok[:, :3], cache)
     assert cache.positions.tolist() == [-1, LENS[1] + 9] and cache.max_pos == max(LENS) + 9
     cache.rewind(2)

@@ -122,12 +122,12 @@ def ragged_time(m, B, ctx, rounds, steps, dev):
     spread = torch.linspace(ctx // 4, ctx - 1, B, device=dev).to(torch.int32)
 
     def uniform():                   # the same position every time: the context stays ctx long
-        cache.positions, cache.max_pos, cache.pos = None, 0, ctx - 1
+        cache.reset(ctx - 1)
         m.decode_step(last, cache)
 
     def rows(at):
         def step():
-            cache.positions, cache.max_pos, cache.pos = at, ctx - 1, ctx - 1
+            cache.reset(ctx - 1, at)
             m.decode_step(last, cache)
         return step
     legs = {"rows_equal": rows(equal), "uniform": uniform}
@@ -263,7 +263,7 @@ def small_m_tokens(m, B, ctx, rounds, steps, dev, ragged=False):
     equal = torch.full((B,), ctx - 1, dtype=torch.int32, device=dev)
 
     def step():                      # the same position every time: the context stays ctx long
-        cache.positions, cache.max_pos, cache.pos = (equal, ctx - 1, ctx - 1) if ragged else (None, 0, ctx - 1)
+        cache.reset(ctx - 1, equal if ragged else None)
         m.decode_step(last, cache)
 
     def under(limit):
