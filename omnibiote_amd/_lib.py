@@ -196,6 +196,14 @@ SYMBOLS_EXTEND = {
     "obte_block_extend": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
 }
 
+# speculative decoding, the verification of a block of drafted tokens (include/omnibiote_hip_spec.h): a table of its own as well
+SPEC_VERIFY_MAX_K = 31   # the most drafted tokens per row obte_spec_verify_bf16 takes
+SYMBOLS_SPEC = {
+    "obte_spec_verify_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "obte_spec_verify_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -224,7 +232,7 @@ def lib():
             except OSError as e:
                 raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
             for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
-                                            + list(SYMBOLS_EXTEND.items())):
+                                            + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -9,6 +9,7 @@
 #include "../../include/omnibiote_hip_small_m.h"
 #include "../../include/omnibiote_hip_sample.h"
 #include "../../include/omnibiote_hip_extend.h"
+#include "../../include/omnibiote_hip_spec.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

@@ -875,7 +875,7 @@ class CachePositions:
     ``lengths`` the rows stand at different positions: ``positions`` is then an int32 (B,) device tensor, row b's next position (the
     kernels read it there; a negative value parks a finished row: it stores nothing and attends to nothing), ``pos`` the host's upper
     bound on it — the longest row — and ``min_pos`` a host-side lower bound on the shortest row that is not parked (0: unknown; only
-    ``rewind`` reads it).  ``reset``, ``advance``, ``park`` and ``rewind`` are the only writers of the three."""
+    ``rewind`` reads it).  ``reset``, ``advance``, ``park``, ``rewind`` and ``rewind_rows`` are the only writers of the three."""
 
     def __init__(self, batch, max_len):
         self.batch, self.max_len = int(batch), int(max_len)
@@ -938,6 +938,35 @@ class CachePositions:
         self.positions = self.positions - n * (self.positions >= 0).to(torch.int32)   # (parked rows, < 0, stay as they are)
         self.min_pos = low - n
         self.pos -= n
+
+    def rewind_rows(self, back, now=None):
+        """Step every row back by its own count: ``back`` is a host sequence of B non-negative ints, what a draft-and-verify loop knows
+        once it has read how many drafted tokens stand in each row.  Rows not parked step back by ``back[b]``, parked rows stay parked;
+        ``pos`` becomes the new maximum over the rows not parked and ``min_pos`` their new minimum, both exact.  Rows mode only.
+        ``now``: the rows' positions as the caller knows them, a host sequence of B ints (negative: parked) — with it nothing is read
+        from the device and nothing waits; without it ``positions`` is read, which synchronises.  As in ``rewind`` no kernel of the
+        library runs, nothing is cleared, and the one elementwise update of ``positions`` is queued on the stream.  ValueError if a
+        row would keep fewer than one position, or in uniform mode."""
+        if self.positions is None:
+            raise ValueError("KVCache.rewind_rows: the cache is in uniform mode (no prefill with lengths): use rewind")
+        try:
+            back = [int(n) for n in (back.tolist() if isinstance(back, torch.Tensor) else back)]
+        except TypeError:
+            raise ValueError(f"KVCache.rewind_rows: back must be a sequence of {self.batch} integers") from None
+        if len(back) != self.batch:
+            raise ValueError(f"KVCache.rewind_rows: {len(back)} counts for a cache of {self.batch} rows")
+        if min(back) < 0:
+            raise ValueError(f"KVCache.rewind_rows: counts must not be negative, got {back}")
+        now = self.positions.tolist() if now is None else [int(p) for p in now]
+        if len(now) != self.batch:
+            raise ValueError(f"KVCache.rewind_rows: {len(now)} positions for a cache of {self.batch} rows")
+        left = [p - n for p, n in zip(now, back) if p >= 0]
+        if left and min(left) < 1:
+            raise ValueError(f"KVCache.rewind_rows: {back} positions back from {now} leaves a row with fewer than one")
+        step = torch.tensor(back, dtype=torch.int32).to(self.positions.device, non_blocking=True)
+        self.positions = self.positions - step * (self.positions >= 0).to(torch.int32)   # (parked rows, < 0, stay as they are)
+        if left:                                                        # (every row parked: the bounds stay, nothing reads them)
+            self.pos, self.min_pos = max(left), min(left)
 
 
 class KVCache(CachePositions):
@@ -1300,6 +1329,153 @@ class OmniBioTA(nn.Module):
                 cache.park(done)
             logits = self.decode_step(nxt, cache)
         return ragged_output(idx, lens, torch.stack(tokens, dim=1), torch.stack(valid, dim=1), pad)
+
+    @torch.no_grad()
+    def draft_and_verify(self, draft, pending, cache, draft_cache, k, uniforms=None, temperature=1.0, top_k=None, top_p=None):
+        """One round of speculative decoding, everything but the step back.  ``pending`` (B,) int64 is every row's last emitted token,
+        in neither cache yet; ``cache`` (this model's) and ``draft_cache`` (``draft``'s) stand at the same per-row positions.  The draft
+        runs k ``decode_step``s, drawing x_0 .. x_{k-1} with ``ops.sample_logits`` from its logits q_0 .. q_{k-1}, and one more that
+        only ingests x_{k-1}; this model runs ``extend([pending, x_0 .. x_{k-1}], logits="all")``; ``ops.spec_verify`` decides.  Both
+        caches then hold k + 1 new positions per row.  ``uniforms``: None (greedy: the draft proposes its argmax, q is not kept) or the
+        round's ``(draws (k, B), u_accept (B, k), u_draw (B,))`` float32 on the device.  Returns ``(x (B, k) int64, n_accept (B,) int32,
+        token (B,) int64)`` on the device; nothing waits for them.  The caller reads n_accept and steps both caches back by
+        ``k - n_accept[b]`` (``rewind_rows``): row b has emitted x_0 .. x_{a-1} and ``token``, its new pending token."""
+        b = pending.shape[0]
+        greedy = uniforms is None or temperature == 0 or top_k == 1
+        draws, u_accept, u_draw = (None, None, None) if greedy else uniforms
+        q = None if greedy else torch.empty((b, k, self.config.vocab_size), dtype=torch.bfloat16, device=pending.device)
+        xs, tok = [], pending
+        for j in range(k):
+            ql = draft.decode_step(tok, draft_cache)
+            if q is not None:
+                q[:, j] = ql
+            tok = ops.sample_logits(ql, None if greedy else draws[j], temperature, top_k, top_p)
+            xs.append(tok)
+        draft.decode_step(tok, draft_cache)                             # x_{k-1} joins the draft's cache as it joins the target's below
+        x = torch.stack(xs, dim=1)
+        p = self.extend(torch.cat([pending.unsqueeze(1), x], dim=1), cache, logits="all")
+        n_accept, token = ops.spec_verify(p, q, x, u_accept, u_draw, temperature, top_k, top_p)
+        return x, n_accept, token
+
+    @torch.no_grad()
+    def generate_speculative(self, idx, max_new_tokens, draft, k=4, temperature=1.0, top_k=None, top_p=None, generator=None, eos_token=None,
+                             lengths=None, pad_token=None, return_stats=False):
+        """``generate`` by draft and verify: ``draft`` — any autoregressive OmniBioTA on the same device with the same vocabulary, a smaller
+        model in practice, this model itself for a self-check — proposes ``k`` tokens per round (1 <= k <= 31), this model scores them in
+        one ``extend`` and ``ops.spec_verify`` keeps a prefix of them and adds one token of its own, so that every emitted token is
+        distributed as this model's own sampling under ``temperature`` / ``top_k`` / ``top_p`` would have it (the rule:
+        ``sampling.verify_reference``; with ``top_k == 1`` or ``temperature == 0`` the output is this model's greedy stream up to the
+        two paths' rounding).  A round (``draft_and_verify``) emits between 1 and k + 1 tokens per row.
+
+        Both models get a ``KVCache`` of their own with one position per row; ``lengths``, ``eos_token`` and ``pad_token`` as in
+        ``generate``.  The last round may write k positions it does not keep: longest prompt + max_new_tokens + k must fit the
+        block_size of both models.  All uniforms come from ``generator`` on the device, one ``torch.rand`` per round, so a seeded call
+        is repeatable.  One host synchronisation per round (how many tokens stood, and where an EOS lies) and one for the first token
+        when ``eos_token`` is given; rows that have their ``max_new_tokens`` or have emitted ``eos_token`` are parked, and the loop ends
+        when every row is.
+
+        Returns (B, T0 + max_new_tokens) int64, a row that emitted ``eos_token`` filled with it to the end; with ``lengths``
+        ``(out, out_lengths)`` as ``generate`` does (``ragged_output``).  ``return_stats`` appends a dict of host ints: ``rounds``, and
+        over all rows and rounds ``drafted`` (k per running row) and ``accepted`` (the drafted tokens that stood)."""
+        what = "generate_speculative"
+        _check_top_p(f"OmniBioTA.{what}", top_p)
+        self._check_generation(what, idx.shape[0] if idx.dim() == 2 else 0)
+        if not isinstance(draft, OmniBioTA) or not draft.config.autoregressive:
+            raise ValueError(f"OmniBioTA.{what}: draft must be an autoregressive OmniBioTA")
+        if draft.config.vocab_size != self.config.vocab_size:
+            raise ValueError(f"OmniBioTA.{what}: the draft's vocab_size {draft.config.vocab_size} is not this model's {self.config.vocab_size}")
+        if draft.transformer.wte.weight.device != self.transformer.wte.weight.device:
+            raise ValueError(f"OmniBioTA.{what}: the draft is on {draft.transformer.wte.weight.device}, this model on {self.transformer.wte.weight.device}")
+        if idx.dim() != 2:
+            raise ValueError(f"OmniBioTA.{what}: idx must be (B, T0), got {tuple(idx.shape)}")
+        b, t0 = idx.shape
+        if t0 == 0:
+            raise ValueError(f"OmniBioTA.{what}: the prompt is empty")
+        if not 1 <= int(k) <= L.SPEC_VERIFY_MAX_K:
+            raise ValueError(f"OmniBioTA.{what}: k must lie in [1, {L.SPEC_VERIFY_MAX_K}], got {k}")
+        k = int(k)
+        if temperature < 0:
+            raise ValueError(f"OmniBioTA.{what}: temperature must not be negative, got {temperature}")
+        if top_k is not None and top_k < 1:
+            raise ValueError(f"OmniBioTA.{what}: top_k must be at least 1, got {top_k}")
+        lens = [t0] * b if lengths is None else _check_lengths(what, lengths, b, t0)
+        longest = max(lens)
+        block = min(self.config.block_size, draft.config.block_size)
+        if max_new_tokens < 0 or longest + max_new_tokens + k > block:
+            raise ValueError(f"OmniBioTA.{what}: {longest} prompt tokens (the longest row) + {max_new_tokens} new ones + k = {k} drafted exceed "
+                             f"block_size = {block} (the smaller of the two models')")
+        pad = pad_token if pad_token is not None else (eos_token if eos_token is not None else 0)
+        idx = idx[:, :longest]
+        dev = idx.device
+        stats = dict(rounds=0, drafted=0, accepted=0)
+
+        def result(tokens, counts):
+            if lengths is None:
+                out = (torch.cat([idx, tokens], dim=1),)
+            else:
+                valid = torch.arange(tokens.shape[1], device=dev).view(1, -1) < torch.tensor(counts, device=dev).view(-1, 1)
+                out = ragged_output(idx, lens, tokens, valid, pad)
+            out = out + (stats,) if return_stats else out
+            return out[0] if len(out) == 1 else out
+
+        if max_new_tokens == 0:
+            return result(torch.zeros((b, 0), dtype=torch.int64, device=dev), [0] * b)
+        greedy = top_k == 1 or temperature == 0
+        cache, draft_cache = KVCache(self, b, longest + max_new_tokens + k), KVCache(draft, b, longest + max_new_tokens + k)
+        logits = self.prefill(idx, cache, lengths=lens)
+        draft.prefill(idx, draft_cache, lengths=lens)
+        pending = ops.sample_logits(logits, None if greedy else torch.rand(b, device=dev, generator=generator), temperature, top_k, top_p)
+        # the host's account: where the rows stand in both caches (-1: parked), what each has emitted and where in `cols` it lies
+        at = list(lens)
+        cols, width = [pending.unsqueeze(1)], 1
+        where = [[0] for _ in range(b)]
+        first = pending.tolist() if eos_token is not None else None
+        done = [max_new_tokens == 1 or (first is not None and first[r] == eos_token) for r in range(b)]
+        newly = list(done)
+        col = torch.arange(k + 1, device=dev).view(1, -1)
+        while not all(done):
+            if any(newly):                                              # park what the last round finished: it stores and reads nothing
+                mask = torch.tensor(newly, device=dev)
+                cache.park(mask)
+                draft_cache.park(mask)
+                at = [-1 if d else p for p, d in zip(at, done)]
+            us = None
+            if not greedy:
+                r = torch.rand(b * (2 * k + 1), device=dev, generator=generator)
+                us = r[:k * b].view(k, b), r[k * b:2 * k * b].view(b, k), r[2 * k * b:]
+            x, n_accept, token = self.draft_and_verify(draft, pending, cache, draft_cache, k, us, temperature, top_k, top_p)
+            a_dev = n_accept.long().unsqueeze(1)
+            emitted = torch.cat([x, token.unsqueeze(1)], dim=1).scatter(1, a_dev, token.unsqueeze(1))   # x_0 .. x_{a-1}, token, (stale)
+            if eos_token is None:
+                read = [(a, k + 1) for a in n_accept.tolist()]         # the round's host synchronisation
+            else:
+                hit = (emitted == eos_token) & (col <= a_dev)
+                eos_at = torch.where(hit.any(dim=1), hit.to(torch.uint8).argmax(dim=1), torch.full((b,), k + 1, device=dev))
+                read = torch.stack([a_dev.squeeze(1), eos_at], dim=1).tolist()   # the round's host synchronisation
+            stats["rounds"] += 1
+            back, now, newly = [0] * b, [p + k + 1 if p >= 0 else -1 for p in at], [False] * b
+            for r in range(b):
+                if done[r]:
+                    continue
+                a, e = read[r]
+                n = min(a + 1, e + 1, max_new_tokens - len(where[r]))   # tokens of this round that count
+                stats["drafted"] += k
+                stats["accepted"] += a
+                where[r] += range(width, width + n)
+                back[r] = k + 1 - n                                     # the pending token and the first n - 1 of this round's stay
+                newly[r] = done[r] = len(where[r]) >= max_new_tokens or e < n
+            cache.rewind_rows(back, now)
+            draft_cache.rewind_rows(back, now)
+            at = [p - n if p >= 0 else -1 for p, n in zip(now, back)]
+            cols.append(emitted)
+            width += k + 1
+            pending = token
+        counts = [len(w) for w in where]
+        steps = max_new_tokens if lengths is None else max(counts)
+        fill = eos_token if lengths is None and eos_token is not None else pad
+        every = torch.cat(cols + [torch.full((b, 1), int(fill), dtype=torch.int64, device=dev)], dim=1)
+        gather = torch.tensor([w[:steps] + [width] * (steps - len(w)) for w in where], device=dev)
+        return result(every.gather(1, gather), counts)
 
 
 def next_token_loss(logits, idx):

@@ -288,6 +288,57 @@ def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, retur
     return (token, kept) if return_kept else token
 
 
+def spec_verify(p, q, draft, u_accept=None, u_draw=None, temperature=1.0, top_k=None, top_p=None):
+    """Speculative decoding's verification in two launches (obte_spec_verify_bf16; the rule: include/omnibiote_hip_spec.h, restated in
+    plain torch by sampling.verify_reference).  ``p`` (B, k + 1, V) bf16: the target's logits behind the pending token and behind each of
+    the k drafted tokens ``draft`` (B, k) int64; ``q`` (B, k, V) bf16: the logits the draft drew them from; ``u_accept`` (B, k) and
+    ``u_draw`` (B,) float32 uniforms.  1 <= k <= 31, V <= 65536.  Without uniforms, with ``temperature == 0`` or ``top_k == 1`` the call is
+    greedy — a drafted token stands while it is the lowest index of the target row's maximum — and ``q`` may be None.  p and q may be
+    row-strided views: last-dimension stride 1, row stride a multiple of 8, rows evenly spaced.  Returns ``(n_accept (B,) int32, token
+    (B,) int64)``: how many drafted tokens stand and the token behind them."""
+    _need(p, "p", contiguous=False)
+    if p.dim() != 3 or p.shape[0] < 1 or p.shape[1] < 2 or p.shape[2] < 1:
+        raise ValueError(f"spec_verify: p must be (B, k + 1, V) with B, k, V >= 1, got {tuple(p.shape)}")
+    B, k, V = p.shape[0], p.shape[1] - 1, p.shape[2]
+
+    def row_stride(t, rows, name):
+        if t.stride(2) != 1 and V > 1:
+            raise RuntimeError(f"spec_verify: {name} must have stride 1 along the vocabulary")
+        ld = t.stride(1) if rows > 1 else t.stride(0)
+        if B > 1 and rows > 1 and t.stride(0) != rows * ld:
+            raise RuntimeError(f"spec_verify: the rows of {name} must be evenly spaced (stride(0) == {rows} * stride(1))")
+        return ld if B * rows > 1 else (V + 7) // 8 * 8
+
+    ld_p = row_stride(p, k + 1, "p")
+    ld_q = 0
+    if q is not None:
+        _need(q, "q", contiguous=False)
+        if q.shape != (B, k, V):
+            raise ValueError(f"spec_verify: q must be ({B}, {k}, {V}), got {tuple(q.shape)}")
+        ld_q = row_stride(q, k, "q")
+    _need(draft, "draft", torch.int64)
+    if draft.shape != (B, k):
+        raise ValueError(f"spec_verify: draft must be ({B}, {k}), got {tuple(draft.shape)}")
+    if (u_accept is None) != (u_draw is None):
+        raise ValueError("spec_verify: u_accept and u_draw come together (both None: greedy)")
+    if u_accept is not None:
+        _need(u_accept, "u_accept", torch.float32); _need(u_draw, "u_draw", torch.float32)
+        if u_accept.shape != (B, k) or u_draw.shape != (B,):
+            raise ValueError(f"spec_verify: u_accept must be ({B}, {k}) and u_draw ({B},), got {tuple(u_accept.shape)} and {tuple(u_draw.shape)}")
+    if top_k is not None and top_k < 1:
+        raise ValueError(f"spec_verify: top_k must be at least 1, got {top_k}")
+    if q is None and not (u_accept is None or temperature == 0 or top_k == 1):
+        raise ValueError("spec_verify: q is None: only a greedy call goes without the draft's logits")
+    n_accept = torch.empty(B, dtype=torch.int32, device=p.device)
+    token = torch.empty(B, dtype=torch.int64, device=p.device)
+    ws_bytes = max(int(L.lib().obte_spec_verify_ws_bytes(B, min(k, L.SPEC_VERIFY_MAX_K))), 8)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
+    L.check(L.lib().obte_spec_verify_bf16(_ptr(p), ld_p, _ptr(q), ld_q, _ptr(draft), B, k, V, _ptr(u_accept), _ptr(u_draw), float(temperature),
+                                          0 if top_k is None else min(int(top_k), 2 ** 31 - 1), 1.0 if top_p is None else float(top_p),
+                                          _ptr(n_accept), _ptr(token), _ptr(ws), ws_bytes, _stream()), "obte_spec_verify_bf16")
+    return n_accept, token
+
+
 def dropout(x, p, seed, site=L.SITE_USER, out=None):
     """out = dropout(x) with the library's counter-based mask: x is read as a matrix [numel / last dim, last dim] and
     element (row, col) decides (include/omnibiote_hip.h, dropout); x may alias out."""

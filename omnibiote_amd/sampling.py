@@ -80,16 +80,96 @@ def sample_reference(logits, u, temperature=1.0, top_k=None, top_p=None, n_kept=
             at = reach.to(torch.uint8).argmax(dim=1, keepdim=True)                       # the first such run
             kept = kept & (xs >= sv.gather(1, at))
     wk = torch.where(kept, w, torch.zeros_like(w))
+    token, cdf = _draw(wk, u)
+    count = kept.sum(dim=1)
+    token = torch.where(count > 0, token, torch.zeros_like(token))
+    out = token, count, cdf
+    return tuple(t[0] for t in out) if one else out
+
+
+def _draw(wk, u):
+    """(token, cumulative distribution) of every row of the weights ``wk`` (B, V) float64, not normalised, zero outside the kept set: the
+    first index whose cumulative probability exceeds u; u >= 1: the last entry of non-zero weight; u < 0 or NaN: the first.  A row of
+    zeros gives token 0 and a distribution of zeros."""
+    b, v = wk.shape
+    col = torch.arange(v, device=wk.device).unsqueeze(0)
     csum = wk.cumsum(dim=1)
     total = csum[:, -1:]
     cdf = torch.where(total > 0, csum / torch.where(total > 0, total, torch.ones_like(total)), torch.zeros_like(csum))
-    uu = _per_row(u, b, dev, torch.float64).unsqueeze(1)
+    uu = _per_row(u, b, wk.device, torch.float64).unsqueeze(1)
     uu = torch.where(uu > 0, uu, torch.zeros_like(uu))                                   # u < 0 or NaN: the first
     over = (cdf > uu) & (wk > 0)
     first = torch.where(over, col, v).min(dim=1).values
     last = torch.where(wk > 0, col, -1).max(dim=1).values                                # u >= 1: the last of non-zero weight
-    token = torch.where((first < v) & (uu.squeeze(1) < 1), first, last).clamp(min=0)
-    count = kept.sum(dim=1)
-    token = torch.where(count > 0, token, torch.zeros_like(token))
-    out = token, count, cdf
+    return torch.where((first < v) & (uu.squeeze(1) < 1), first, last).clamp(min=0), cdf
+
+
+def verify_distributions(p, q, temperature=1.0, top_k=None, top_p=None, n_kept_p=None, n_kept_q=None):
+    """(P (B, k + 1, V), Q (B, k, V)) float64: the distribution ``sample_reference`` draws from on every row of the target's logits ``p``
+    (B, k + 1, V) and of the draft's ``q`` (B, k, V) — its kept set, ties kept whole, and its normalised weights (zeros for a row with
+    nothing to sample).  ``n_kept_p`` (B, k + 1) / ``n_kept_q`` (B, k): the kept sets rebuilt from those counts, as ``sample_reference``
+    does with ``n_kept``."""
+    def dist(x, n):
+        b, r, v = x.shape
+        cdf = sample_reference(x.reshape(b * r, v), 0.5, temperature, top_k, top_p, None if n is None else torch.as_tensor(n).reshape(b * r))[2]
+        return torch.diff(cdf, dim=1, prepend=torch.zeros(b * r, 1, dtype=torch.float64, device=cdf.device)).view(b, r, v)
+    return dist(p, n_kept_p), dist(q, n_kept_q)
+
+
+def verify_reference(p, q, draft, u_accept=None, u_draw=None, temperature=1.0, top_k=None, top_p=None, n_kept_p=None, n_kept_q=None):
+    """Speculative decoding's accept / reject rule in plain torch, in float64, on any device: what obte_spec_verify_bf16
+    (include/omnibiote_hip_spec.h) implements.  ``p`` (B, k + 1, V): the target's logits behind the pending token and behind each drafted
+    token; ``q`` (B, k, V): the logits the draft drew from; ``draft`` (B, k) integers; ``u_accept`` (B, k) and ``u_draw`` (B,) uniforms.  One
+    batch row — (k + 1, V), (k, V), (k,), (k,) and a number — gives scalars and (V,).
+
+    With P_j and Q_j what ``sample_reference`` makes of p[j] and q[j] under the same temperature, top_k and top_p:
+      accept   walking j = 0, 1, ...: x_j stands while u_accept[j] < P_j(x_j) / Q_j(x_j).  P_j(x_j) == 0 — outside the target's kept set, or
+               outside [0, V) — never stands; otherwise Q_j(x_j) == 0 stands; a u_accept that is NaN or negative counts as 0.
+      token    a = the number that stand.  a == k: the draw of ``sample_reference(p[k], u_draw, ...)``.  a < k: the first index whose
+               cumulative probability exceeds u_draw under max(0, P_a - Q_a) / Z, Z its sum — from P_a if Z == 0; u_draw's edge cases as
+               in ``sample_reference``.
+      greedy   temperature == 0, top_k == 1 or no uniforms: x_j stands while it is the lowest index of p[j]'s maximum; the token is that
+               index of p[a].  q is not read and may be None.
+    Returns (a int64 (B,), token int64 (B,), the cumulative distribution float64 (B, V) the token was drawn from)."""
+    one = p.dim() == 2
+    if one:
+        p, draft = p.unsqueeze(0), torch.as_tensor(draft).unsqueeze(0)
+        q = None if q is None else q.unsqueeze(0)
+        u_accept = None if u_accept is None else torch.as_tensor(u_accept).unsqueeze(0)
+    if p.dim() != 3 or p.shape[1] < 2:
+        raise ValueError(f"verify_reference: p must be (B, k + 1, V) or (k + 1, V) with k >= 1, got {tuple(p.shape)}")
+    b, k, v = p.shape[0], p.shape[1] - 1, p.shape[2]
+    dev = p.device
+    x = torch.as_tensor(draft, device=dev).to(torch.int64)
+    if x.shape != (b, k):
+        raise ValueError(f"verify_reference: draft must be ({b}, {k}), got {tuple(x.shape)}")
+    inside = (x >= 0) & (x < v)
+    xc = x.clamp(0, v - 1).unsqueeze(2)
+    rows = torch.arange(b, device=dev)
+    greedy = u_accept is None or u_draw is None or temperature == 0 or top_k == 1
+    if greedy:
+        top = sample_reference(p.reshape(b * (k + 1), v), None)[0].view(b, k + 1)
+        ok = inside & (x == top[:, :k])
+        a = ok.long().cumprod(dim=1).sum(dim=1)
+        token = top[rows, a]
+        out = a, token, (torch.arange(v, device=dev).unsqueeze(0) >= token.unsqueeze(1)).double()
+        return tuple(t[0] for t in out) if one else out
+    if q is None or q.shape != (b, k, v):
+        raise ValueError(f"verify_reference: q must be ({b}, {k}, {v}) unless the call is greedy")
+    P, Q = verify_distributions(p, q, temperature, top_k, top_p, n_kept_p, n_kept_q)
+    px = torch.where(inside, P[:, :k].gather(2, xc).squeeze(2), torch.zeros((), dtype=torch.float64, device=dev))
+    qx = torch.where(inside, Q.gather(2, xc).squeeze(2), torch.zeros((), dtype=torch.float64, device=dev))
+    ua = torch.as_tensor(u_accept, dtype=torch.float64, device=dev).reshape(b, k)
+    ua = torch.where(ua > 0, ua, torch.zeros_like(ua))                                   # NaN or negative: 0
+    ok = (px > 0) & ((qx == 0) | (ua < px / torch.where(qx > 0, qx, torch.ones_like(qx))))
+    a = ok.long().cumprod(dim=1).sum(dim=1)
+    pa = P[rows, a]
+    res = (pa - Q[rows, a.clamp(max=k - 1)]).clamp(min=0)
+    res = torch.where((a < k).unsqueeze(1), res, torch.zeros_like(res))
+    w = torch.where(res.sum(dim=1, keepdim=True) > 0, res, pa)                           # a == k or Z == 0: P_a itself
+    token, cdf = _draw(w, u_draw)
+    token = torch.where(w.sum(dim=1) > 0, token, torch.zeros_like(token))
+    bonus = sample_reference(p[:, k], u_draw, temperature, top_k, top_p, None if n_kept_p is None else torch.as_tensor(n_kept_p).reshape(b, k + 1)[:, k])
+    token, cdf = torch.where(a == k, bonus[0], token), torch.where((a == k).unsqueeze(1), bonus[2], cdf)
+    out = a, token, cdf
     return tuple(t[0] for t in out) if one else out

@@ -64,15 +64,16 @@ def timed(fn, n):
     return e0.elapsed_time(e1) / n * 1e3
 
 
-def build(block_size, dev):
-    """the small config as an autoregressive model, muP base shapes set as the trainer sets them (train_encoder.build_model)"""
+def build(block_size, dev, n_layer=8):
+    """the small config as an autoregressive model, muP base shapes set as the trainer sets them (train_encoder.build_model); ``n_layer``
+    other than its 8: the same width with fewer layers (spec_bench.py's draft)"""
     import warnings
     from omnibiote_amd.model import OmniBioTA, OmniBioTAConfig
     from omnibiote_amd.mup_compat import set_base_shapes
 
     def make(n_embd, n_head):
         c = OmniBioTAConfig()
-        c.block_size, c.vocab_size, c.n_layer, c.n_head, c.n_embd, c.dropout, c.flash = block_size, 2 ** 16, 8, n_head, n_embd, 0.0, True
+        c.block_size, c.vocab_size, c.n_layer, c.n_head, c.n_embd, c.dropout, c.flash = block_size, 2 ** 16, n_layer, n_head, n_embd, 0.0, True
         c.autoregressive = True
         return OmniBioTA(c)
     torch.manual_seed(0)
