@@ -204,6 +204,18 @@ SYMBOLS_SPEC = {
                                         C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
 }
 
+# the key/value cache stored as OCP e4m3 (include/omnibiote_hip_kv8.h): a table of its own as well
+SYMBOLS_KV8 = {
+    "obte_kv8_cache_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "obte_kv8_cache_store": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, c_stream]),
+    "obte_kv8_cache_rope_store_rows": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_attn_decode_kv8": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                       C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_fwd_prefill_kv8": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_decode_kv8": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                        c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -232,7 +244,7 @@ def lib():
             except OSError as e:
                 raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
             for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
-                                            + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items())):
+                                            + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

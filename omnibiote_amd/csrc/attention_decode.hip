@@ -28,10 +28,7 @@
 
 namespace {
 
-constexpr int DEC_WAVES = 4;     // waves per workgroup
-constexpr int DEC_UNROLL = 4;    // keys per lane group whose loads are in flight together (K and V: 8 loads of 16 bytes per lane)
-constexpr int DEC_CHUNK = 64;    // split boundaries are multiples of this many keys (16 KiB of K at head size 128)
-constexpr int DEC_PAD = 4;       // a partial is hs + 4 floats (acc[hs], m, l, 2 unused): 16-byte aligned rows
+// (DEC_WAVES, DEC_UNROLL, DEC_CHUNK, DEC_PAD: common.h — attention_kv8.hip shares the partition and the partial layout)
 
 __device__ __forceinline__ void unpack8(u32x4 r, float* f) {
 #pragma unroll
@@ -323,13 +320,19 @@ extern "C" int obte_attn_decode_splits(int64_t B, int32_t n_head, int32_t head_d
     return n < 1 ? 1 : (int)n;
 }
 
+// the combine launch behind a split launch of this file's kernel or of attention_kv8.hip's (the same partials)
+void obte_attn_decode_combine(int head_dim, int BH, int splits, const float* ws, bf16* o, float* lse, hipStream_t st) {
+    if (head_dim == 128) hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(BH), dim3(128), 0, st, ws, o, lse, splits);
+    else hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(BH), dim3(64), 0, st, ws, o, lse, splits);
+}
+
 // obte_attn_decode (rows_n null: every row over the keys [0, n_keys)) and obte_attn_decode_rows_off (ROWS: row b over rows_n[b] + key_off keys,
 // n_keys the host's bound on that, the kernel forming `per` from the row's own count): the same checks, the same launch
 template <int HS, bool ROWS>
 static void launch_decode(const dim3& grid, hipStream_t st, const bf16* q, int64_t q_ld, const bf16* cache, bf16* o, float* lse, float* ws, int H, int64_t T_max,
                           int64_t v_off, int n_keys, int per, float qscale, const int32_t* rows_n, int key_off) {
     hipLaunchKernelGGL((attn_decode_kernel<HS, ROWS>), grid, dim3(DEC_WAVES * 64), 0, st, q, q_ld, cache, o, lse, ws, H, T_max, v_off, n_keys, per, qscale, rows_n, key_off);
-    if (grid.x > 1) hipLaunchKernelGGL(attn_decode_combine_kernel<HS>, dim3(grid.y), dim3(HS), 0, st, (const float*)ws, o, lse, (int)grid.x);
+    if (grid.x > 1) obte_attn_decode_combine(HS, (int)grid.y, (int)grid.x, ws, o, lse, st);
 }
 
 template <bool ROWS>

@@ -491,6 +491,8 @@ struct InferAttention {
                                           // joins the cache store (rope_cos / rope_sin: the FULL tables)
     int64_t n_new = 0;                    // > 0: against the cache, n_new new positions per row; 0: the attention of the call's own T positions
     bool decode = false;                  // n_new == 1 on the one-query launchers (obte_block_decode, obte_block_decode_rows)
+    bool kv8 = false;                     // the cache is the e4m3 one (include/omnibiote_hip_kv8.h): prefill and decode only, its launchers in the same places
+    const char* who = "";                 // kv8: the entry point its launchers name in an error
 };
 int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const InferLayout& w, int64_t M, const float* rope_cos,
                    const float* rope_sin, int64_t rope_T, const InferAttention& at, obte_stream s) {
@@ -507,10 +509,15 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
     const float scale = 8.0f / (float)C;  // model.py:119
     if (at.n_new > 0) {   // n_new positions per row join the cache (the rows form rotates them as it stores), then each attends over those up to its own
         const int64_t q_ld = 3 * (int64_t)C;
-        if (!at.pos_rows) TRY(obte_kv_cache_store(w.qkv, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, at.pos, s));
+        if (at.kv8 && !at.pos_rows) TRY(obte_kv8_cache_store(w.qkv, d->B, 1, H, hs, at.kv_cache, at.T_max, at.pos, s));   // (kv8: decode only)
+        else if (at.kv8) TRY(obte_kv8_rope_store_rows_as(at.who, w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.T_max, s));
+        else if (!at.pos_rows) TRY(obte_kv_cache_store(w.qkv, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, at.pos, s));
         else if (at.decode) TRY(obte_kv_cache_rope_store_rows(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.T_max, s));
         else TRY(obte_kv_cache_rope_store_chunk(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, s));
-        if (!at.decode)
+        if (at.kv8)             // uniform (pos_rows null: every row over pos + 1 keys) or row b over its own pos_rows[b] + 1
+            TRY(obte_attn_decode_kv8_off(at.who, w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos + 1, at.pos_rows, 1, H, hs, scale, 0, at.dec_ws,
+                                         at.dec_ws_bytes, s));
+        else if (!at.decode)
             TRY(obte_attn_extend(w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.n_new, at.pos, at.pos_rows, H, hs, scale, 0, at.dec_ws, at.dec_ws_bytes, s));
         else if (at.pos_rows)   // row b over its own pos_rows[b] + 1 keys
             TRY(obte_attn_decode_rows_off("obte_block_decode_rows", w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos_rows, 1, at.pos + 1, H, hs, scale, 0,
@@ -523,7 +530,8 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
         af.B = d->B; af.T = d->T; af.n_head = H; af.head_dim = hs; af.scale = scale;
         af.dropout_p = d->dropout_p; af.dropout_seed = d->dropout_seed;
         TRY(obte_attn_fwd(&af, s));
-        if (at.kv_cache) TRY(obte_kv_cache_store(w.qkv, d->B, d->T, H, hs, at.kv_cache, at.T_max, 0, s));   // (c_fc's activation overwrites qkv below)
+        if (at.kv_cache && at.kv8) TRY(obte_kv8_cache_store(w.qkv, d->B, d->T, H, hs, at.kv_cache, at.T_max, 0, s));
+        else if (at.kv_cache) TRY(obte_kv_cache_store(w.qkv, d->B, d->T, H, hs, at.kv_cache, at.T_max, 0, s));   // (c_fc's activation overwrites qkv below)
     }
     TRY(run(plus_residual(xWt(w.att, d->proj_w, w.x1, M, C, C), x, d->dropout_p, d->dropout_seed, SITE_RESID), s));
     TRY(obte_layernorm_fwd(w.x1, d->ln2_w, w.h2, w.mean, w.rstd, M, C, 1e-5f, s));
@@ -535,7 +543,7 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
 
 // obte_block_fwd_infer and obte_block_fwd_prefill: the same checks, the same workspace
 int infer_or_prefill(const char* who, const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* ws, int64_t ws_bytes, obte_bf16* kv_cache,
-                     int64_t T_max, bool prefill, obte_stream s) {
+                     int64_t T_max, bool prefill, obte_stream s, bool kv8 = false) {
     TRY(check_desc(who, d));
     if (d->out_rows) {
         obte_set_error("%s: the rows form (out_rows) stays with obte_block_fwd", who);
@@ -543,9 +551,11 @@ int infer_or_prefill(const char* who, const obte_block_desc* d, const obte_bf16*
     }
     OBTE_REQUIRE(x && y_out && ws && (!prefill || kv_cache), "%s: null pointer", who);
     OBTE_REQUIRE(!prefill || d->T <= T_max, "%s: %lld positions do not fit T_max = %lld", who, (long long)d->T, (long long)T_max);
+    OBTE_REQUIRE(!kv8 || ((uintptr_t)kv_cache & 15) == 0, "%s: cache8 must be 16-byte aligned", who);
     const InferLayout w(d->B, d->T, d->n_embd, d->n_head, ws);
     OBTE_REQUIRE(ws_bytes >= w.total, "%s: workspace of %lld bytes, obte_block_infer_ws_bytes() asks for %lld", who, (long long)ws_bytes, (long long)w.total);
-    const InferAttention at = {prefill ? kv_cache : nullptr, T_max, -1, nullptr, 0};
+    InferAttention at = {prefill ? kv_cache : nullptr, T_max, -1, nullptr, 0};
+    at.kv8 = kv8; at.who = who;
     return infer_sequence(d, x, y_out, w, d->B * d->T, d->rope_cos, d->rope_sin, d->T, at, s);
 }
 
@@ -560,6 +570,11 @@ extern "C" int obte_block_fwd_prefill(const obte_block_desc* d, const obte_bf16*
     return infer_or_prefill("obte_block_fwd_prefill", d, x, y_out, ws, ws_bytes, kv_cache, T_max, true, s);
 }
 
+extern "C" int obte_block_fwd_prefill_kv8(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* ws, int64_t ws_bytes, void* cache8, int64_t T_max,
+                                          obte_stream s) {
+    return infer_or_prefill("obte_block_fwd_prefill_kv8", d, x, y_out, ws, ws_bytes, (obte_bf16*)cache8, T_max, true, s, true);
+}
+
 // ---- new positions per row against the cache --------------------------------------------------------------------------------------------
 namespace {
 
@@ -567,7 +582,7 @@ namespace {
 // pos_rows[b] on, read on the device, with `pos` the host's bound on it.  decode: the one-position launchers (obte_kv_cache_rope_store_rows,
 // obte_attn_decode / _rows and their workspace behind InferLayout) instead of obte_attn_extend's.
 int cached_step(const char* who, const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, int64_t pos,
-                const int32_t* pos_rows, bool rows, bool decode, void* ws, int64_t ws_bytes, obte_stream s) {
+                const int32_t* pos_rows, bool rows, bool decode, void* ws, int64_t ws_bytes, obte_stream s, bool kv8 = false) {
     TRY(check_desc(who, d));
     OBTE_REQUIRE(!decode || d->T == 1, "%s: one new position per row (T = 1), got T = %lld", who, (long long)d->T);
     if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
@@ -586,13 +601,16 @@ int cached_step(const char* who, const obte_block_desc* d, const obte_bf16* x, o
         return OBTE_EINVAL;
     }
     const int C = d->n_embd, H = d->n_head, hs = C / H;
+    if (kv8)   // what its two launchers would refuse, before the first launch of the sequence
+        OBTE_REQUIRE(((uintptr_t)kv_cache & 15) == 0 && ((uintptr_t)pos_rows & 3) == 0 && d->B * H <= 65535,
+                     "%s: cache8 must be 16-byte aligned, pos_rows 4-byte aligned, B * n_head <= 65535", who);
     const int64_t att_bytes = decode ? obte_attn_decode_ws_bytes(d->B, H, hs) : obte_attn_extend_ws_bytes(d->B, H, hs, n, 0);
     OBTE_REQUIRE(decode || att_bytes > 0, "%s: bad shape (B * n_head <= 65535)", who);
     const InferLayout w(d->B, n, C, H, ws);
     const int64_t need = w.total + align256(att_bytes);
     OBTE_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes, obte_block_%s_ws_bytes() asks for %lld", who, (long long)ws_bytes, decode ? "decode" : "extend",
                  (long long)need);
-    const InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, att_bytes, rows ? pos_rows : nullptr, n, decode};
+    const InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, att_bytes, rows ? pos_rows : nullptr, n, decode, kv8, who};
     // uniform: c_attn rotates row b n + j by the tables' row pos + j (rope_T = n on the tables advanced by pos rows); rows form: the FULL tables
     const int64_t row = at.pos_rows ? 0 : pos * (hs / 2);
     return infer_sequence(d, x, y_out, w, d->B * n, d->rope_cos + row, d->rope_sin + row, n, at, s);
@@ -614,6 +632,12 @@ extern "C" int obte_block_decode(const obte_block_desc* d, const obte_bf16* x, o
 extern "C" int obte_block_decode_rows(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, const int32_t* pos,
                                       int64_t max_pos, void* ws, int64_t ws_bytes, obte_stream s) {
     return cached_step("obte_block_decode_rows", d, x, y_out, kv_cache, T_max, max_pos, pos, true, true, ws, ws_bytes, s);
+}
+
+// the two on the e4m3 cache (include/omnibiote_hip_kv8.h): pos_rows null or not
+extern "C" int obte_block_decode_kv8(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* cache8, int64_t T_max, int64_t pos, const int32_t* pos_rows,
+                                     void* ws, int64_t ws_bytes, obte_stream s) {
+    return cached_step("obte_block_decode_kv8", d, x, y_out, (obte_bf16*)cache8, T_max, pos, pos_rows, pos_rows != nullptr, true, ws, ws_bytes, s, true);
 }
 
 // InferLayout at T = n_new (M = B n_new rows) with obte_attn_extend's partials behind it (include/omnibiote_hip_extend.h)

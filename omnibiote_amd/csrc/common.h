@@ -10,6 +10,7 @@
 #include "../../include/omnibiote_hip_sample.h"
 #include "../../include/omnibiote_hip_extend.h"
 #include "../../include/omnibiote_hip_spec.h"
+#include "../../include/omnibiote_hip_kv8.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -90,6 +91,21 @@ int obte_rows_add_bf16(const obte_bf16* src, const int64_t* rows, obte_bf16* dst
 int obte_attn_decode_rows_off(const char* who, const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max,
                               const int32_t* n_keys, int32_t key_off, int64_t max_keys, int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws,
                               int64_t ws_bytes, obte_stream s);
+
+// ---- one query per (batch, head) against a key/value cache: what attention_decode.hip (bf16 cache) and attention_kv8.hip (e4m3 cache) share
+constexpr int DEC_WAVES = 4;     // waves per workgroup
+constexpr int DEC_UNROLL = 4;    // keys per lane group whose loads are in flight together (bf16 cache: K and V, 8 loads of 16 bytes per lane)
+constexpr int DEC_CHUNK = 64;    // split boundaries are multiples of this many keys (16 KiB of K at head size 128 in bf16)
+constexpr int DEC_PAD = 4;       // a partial is hs + 4 floats (acc[hs], m, l, 2 unused): 16-byte aligned rows
+// attn_decode_combine_kernel<head_dim> on BH rows of `splits` partials in ws (attention_decode.hip)
+void obte_attn_decode_combine(int head_dim, int BH, int splits, const float* ws, __bf16* o, float* lse, hipStream_t st);
+// the e4m3 cache's launchers with the entry point named in an error and row b's count read as n_keys_rows[b] + key_off (attention_kv8.hip;
+// csrc/block.cpp hands a step's positions and 1)
+int obte_kv8_rope_store_rows_as(const char* who, obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos, int64_t max_pos, int64_t B,
+                                int32_t n_head, int32_t head_dim, void* cache8, int64_t T_max, obte_stream s);
+int obte_attn_decode_kv8_off(const char* who, const obte_bf16* q, int64_t q_ld, const void* cache8, obte_bf16* o, float* lse, int64_t B, int64_t T_max,
+                             int64_t n_keys, const int32_t* n_keys_rows, int32_t key_off, int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws,
+                             int64_t ws_bytes, obte_stream s);
 
 // device status word (lib.cpp): pinned host memory kernels OR failure bits into; null if it could not be allocated
 int32_t* obte_status_word();

@@ -877,6 +877,8 @@ class CachePositions:
     bound on it — the longest row — and ``min_pos`` a host-side lower bound on the shortest row that is not parked (0: unknown; only
     ``rewind`` reads it).  ``reset``, ``advance``, ``park``, ``rewind`` and ``rewind_rows`` are the only writers of the three."""
 
+    dtype = "bf16"   # what the buffers behind the positions hold (KVCache sets it): no operation here touches a cache byte
+
     def __init__(self, batch, max_len):
         self.batch, self.max_len = int(batch), int(max_len)
         self.reset(0)
@@ -974,9 +976,16 @@ class KVCache(CachePositions):
     (default and at most ``config.block_size``): one buffer per layer (include/omnibiote_hip.h, obte_kv_cache_bytes), the workspaces of
     a decode step and of ``extend``, and where the rows stand (``CachePositions``).  ``OmniBioTA.prefill`` starts it over (nothing is
     cleared: positions beyond ``pos`` are never read), ``decode_step`` advances it by one token per row, ``extend`` by several,
-    ``rewind`` steps back."""
+    ``rewind`` steps back.
 
-    def __init__(self, model, batch, max_len=None):
+    ``dtype``: "bf16" (the default) or "fp8" — keys and values stored as OCP e4m3 with one power-of-two scale per (row, head, position)
+    vector (include/omnibiote_hip_kv8.h, kvquant.py): 2 (hs + 4) bytes per cached vector instead of 4 hs.  ``prefill`` (unchunked),
+    ``decode_step`` and ``generate`` run on either; several new positions per row in one call (``extend``, ``prefill(chunk=)``,
+    ``generate_speculative``) need a bf16 cache and raise NotImplementedError on an fp8 one."""
+
+    def __init__(self, model, batch, max_len=None, dtype="bf16"):
+        if dtype not in ("bf16", "fp8"):
+            raise ValueError(f"KVCache: dtype must be 'bf16' or 'fp8', got {dtype!r}")
         cfg = model.config
         if not cfg.autoregressive:
             raise ValueError("KVCache: the model is not autoregressive (config.autoregressive): an encoder has no next token")
@@ -989,7 +998,9 @@ class KVCache(CachePositions):
         _require_hip(wte, "KVCache")
         super().__init__(batch, max_len)
         hs = cfg.n_embd // cfg.n_head
-        self.layers = [ops.kv_cache_buffer(self.batch, max_len, cfg.n_head, hs, wte.device) for _ in model.transformer.h]
+        self.dtype = dtype
+        new = ops.kv8_cache_buffer if dtype == "fp8" else ops.kv_cache_buffer
+        self.layers = [new(self.batch, max_len, cfg.n_head, hs, wte.device) for _ in model.transformer.h]
         self.decode_ws = ops.block_decode_workspace(self.batch, cfg.n_embd, cfg.n_head, wte.device)
         self.extend_ws = None   # OmniBioTA.extend's workspace: allocated by the first call, replaced when a call needs more bytes
 
@@ -1095,6 +1106,13 @@ class OmniBioTA(nn.Module):
         if cache is not None and cache.batch != batch:
             raise ValueError(f"OmniBioTA.{what}: the cache was built for batch size {cache.batch}, got {batch}")
 
+    @staticmethod
+    def _refuse_fp8(what, cache):
+        """NotImplementedError in ``OmniBioTA.what``'s name on an fp8 cache: before anything is launched or any state changes"""
+        if cache.dtype == "fp8":
+            raise NotImplementedError(f"OmniBioTA.{what}: the cache is an fp8 cache (KVCache(dtype='fp8')), over which only one new position per "
+                                      "row attends (prefill, decode_step, generate); several new positions in one call need a bf16 cache")
+
     def _readout_rows(self, x):
         """The readout of a generation step's (B, C) rows: at most ops' small_m_max of them, bf16 on the GPU, through the
         weight-streaming product with MuReadout.forward's alpha; anything else through the module."""
@@ -1118,6 +1136,8 @@ class OmniBioTA(nn.Module):
         every further ``chunk`` of them through ``extend``'s block path at uniform positions (right padding stays harmless under the
         causal rule), each embedded on its own — the activation workspace is sized by the chunk, no (B, T0, C) tensor exists — and
         row b's last hidden state is picked up in the chunk that holds it.  The cache ends in the same state."""
+        if chunk is not None:
+            self._refuse_fp8("prefill(chunk=)", cache)
         if idx.dim() != 2:
             raise ValueError(f"OmniBioTA.prefill: idx must be (B, T0), got {tuple(idx.shape)}")
         if chunk is not None and int(chunk) < 1:
@@ -1138,8 +1158,9 @@ class OmniBioTA(nn.Module):
         mask = ops.MaskSpec.from_user(_autoregressive_mask(True, None, b, t, idx.device), b, t, self.config.n_head, idx.device)
         x = ops.embedding_fwd(idx.contiguous(), wte)
         ws = ops.block_infer_workspace(b, t, self.config.n_embd, self.config.n_head, idx.device)
+        block_prefill = ops.block_prefill_kv8 if cache.dtype == "fp8" else ops.block_prefill
         for block, kv in zip(self.transformer.h, cache.layers):
-            ops.block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, kv, cache.max_len, ws=ws, out=x)
+            block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, kv, cache.max_len, ws=ws, out=x)
         self._prefilled(cache, t, lens, idx.device)
         if lens is None:
             return self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()))
@@ -1204,6 +1225,7 @@ class OmniBioTA(nn.Module):
         logits predict token j + 1.  Returns (B, vocab), the logits behind the last token, for ``logits="last"`` or (B, n, vocab) for
         ``"all"`` — what verifying a block of drafted tokens or scoring a continuation needs.  ``pos`` / ``positions`` advance
         by n; parked rows stay parked.  n == 1 is ``decode_step``.  ``KVCache.rewind`` steps back over tokens that are not kept."""
+        self._refuse_fp8("extend", cache)
         if tokens.dim() != 2:
             raise ValueError(f"OmniBioTA.extend: tokens must be (B, n), got {tuple(tokens.shape)}")
         b, n = tokens.shape
@@ -1244,7 +1266,10 @@ class OmniBioTA(nn.Module):
             raise RuntimeError("OmniBioTA.decode_step: tokens must be on the GPU")
         x = ops.embedding_fwd(tokens.contiguous(), wte)
         # rows mode: every row at its own position, read on the device, with pos the host's bound on it
-        step, at = (ops.block_decode, (cache.pos,)) if cache.positions is None else (ops.block_decode_rows, (cache.positions, cache.pos))
+        if cache.dtype == "fp8":   # one entry point for both forms: (pos, pos_rows)
+            step, at = ops.block_decode_kv8, (cache.pos, cache.positions)
+        else:
+            step, at = (ops.block_decode, (cache.pos,)) if cache.positions is None else (ops.block_decode_rows, (cache.positions, cache.pos))
         for block, kv in zip(self.transformer.h, cache.layers):
             step(x, self._block_params(block), block.attn.rope(), self.config.n_head, kv, cache.max_len, *at, ws=cache.decode_ws, out=x)
         cache.advance(1)
@@ -1252,7 +1277,7 @@ class OmniBioTA(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None, lengths=None, pad_token=None, top_p=None,
-                 sampler="torch"):
+                 sampler="torch", kv_dtype="bf16"):
         """nanoGPT's generate(): ``idx`` (B, T0) int64 continued by up to ``max_new_tokens`` sampled tokens (``sample_next``); returns
         (B, T0 + n) int64.  The prompt runs once (``prefill``), every new token costs one ``decode_step``.  Where nanoGPT crops the
         context to block_size, this raises: T0 + max_new_tokens must fit.  ``eos_token``: a row that has produced it keeps producing
@@ -1267,9 +1292,13 @@ class OmniBioTA(nn.Module):
 
         ``top_p``: nucleus sampling (``sample_next``).  ``sampler``: "torch" (``sample_next`` under ``generator``, as ever) or "device":
         the uniforms of the whole call are drawn once, ``torch.rand((max_new_tokens, B), generator=generator)``, and every step's
-        tokens come from one launch on the step's bf16 logits (``ops.sample_logits``: the same rule, another random stream)."""
+        tokens come from one launch on the step's bf16 logits (``ops.sample_logits``: the same rule, another random stream).
+
+        ``kv_dtype``: "bf16" or "fp8", the ``KVCache`` the call builds (``KVCache``: the e4m3 cache, about half the bytes)."""
         if sampler not in ("torch", "device"):
             raise ValueError(f"OmniBioTA.generate: sampler must be 'torch' or 'device', got {sampler!r}")
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"OmniBioTA.generate: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         _check_top_p("OmniBioTA.generate", top_p)
         self._check_generation("generate", idx.shape[0] if idx.dim() == 2 else 0)
         if idx.dim() != 2:
@@ -1279,12 +1308,12 @@ class OmniBioTA(nn.Module):
             raise ValueError("OmniBioTA.generate: the prompt is empty")
         if lengths is not None:
             return self._generate_ragged(idx, _check_lengths("generate", lengths, b, t0), max_new_tokens, temperature, top_k, generator, eos_token,
-                                         pad_token, top_p, sampler)
+                                         pad_token, top_p, sampler, kv_dtype)
         if max_new_tokens < 0 or t0 + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {t0} prompt tokens + {max_new_tokens} new ones exceed block_size = {self.config.block_size}")
         if max_new_tokens == 0:
             return idx.clone()
-        cache = KVCache(self, b, t0 + max_new_tokens)
+        cache = KVCache(self, b, t0 + max_new_tokens, dtype=kv_dtype)
         out = [idx]
         logits = self.prefill(idx, cache)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
@@ -1301,7 +1330,7 @@ class OmniBioTA(nn.Module):
             logits = self.decode_step(nxt, cache)
         return torch.cat(out, dim=1)
 
-    def _generate_ragged(self, idx, lens, max_new_tokens, temperature, top_k, generator, eos_token, pad_token, top_p=None, sampler="torch"):
+    def _generate_ragged(self, idx, lens, max_new_tokens, temperature, top_k, generator, eos_token, pad_token, top_p=None, sampler="torch", kv_dtype="bf16"):
         longest = max(lens)
         if max_new_tokens < 0 or longest + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {longest} prompt tokens (the longest row) + {max_new_tokens} new ones exceed "
@@ -1312,7 +1341,7 @@ class OmniBioTA(nn.Module):
         if max_new_tokens == 0:
             none = torch.zeros((b, 0), dtype=torch.int64, device=idx.device)
             return ragged_output(idx, lens, none, none.bool(), pad)
-        cache = KVCache(self, b, longest + max_new_tokens)
+        cache = KVCache(self, b, longest + max_new_tokens, dtype=kv_dtype)
         logits = self.prefill(idx, cache, lengths=lens)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
         tokens, valid = [], []
@@ -1340,6 +1369,7 @@ class OmniBioTA(nn.Module):
         round's ``(draws (k, B), u_accept (B, k), u_draw (B,))`` float32 on the device.  Returns ``(x (B, k) int64, n_accept (B,) int32,
         token (B,) int64)`` on the device; nothing waits for them.  The caller reads n_accept and steps both caches back by
         ``k - n_accept[b]`` (``rewind_rows``): row b has emitted x_0 .. x_{a-1} and ``token``, its new pending token."""
+        self._refuse_fp8("draft_and_verify", cache)         # (the draft only takes decode steps: its cache may be either)
         b = pending.shape[0]
         greedy = uniforms is None or temperature == 0 or top_k == 1
         draws, u_accept, u_draw = (None, None, None) if greedy else uniforms
@@ -1359,7 +1389,7 @@ class OmniBioTA(nn.Module):
 
     @torch.no_grad()
     def generate_speculative(self, idx, max_new_tokens, draft, k=4, temperature=1.0, top_k=None, top_p=None, generator=None, eos_token=None,
-                             lengths=None, pad_token=None, return_stats=False):
+                             lengths=None, pad_token=None, return_stats=False, kv_dtype="bf16"):
         """``generate`` by draft and verify: ``draft`` — any autoregressive OmniBioTA on the same device with the same vocabulary, a smaller
         model in practice, this model itself for a self-check — proposes ``k`` tokens per round (1 <= k <= 31), this model scores them in
         one ``extend`` and ``ops.spec_verify`` keeps a prefix of them and adds one token of its own, so that every emitted token is
@@ -1378,6 +1408,11 @@ class OmniBioTA(nn.Module):
         ``(out, out_lengths)`` as ``generate`` does (``ragged_output``).  ``return_stats`` appends a dict of host ints: ``rounds``, and
         over all rows and rounds ``drafted`` (k per running row) and ``accepted`` (the drafted tokens that stood)."""
         what = "generate_speculative"
+        if kv_dtype == "fp8":
+            raise NotImplementedError(f"OmniBioTA.{what}: kv_dtype 'fp8': verifying a drafted block attends from several new positions per row, "
+                                      "which is not built over an fp8 cache; use the bf16 cache")
+        if kv_dtype != "bf16":
+            raise ValueError(f"OmniBioTA.{what}: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         _check_top_p(f"OmniBioTA.{what}", top_p)
         self._check_generation(what, idx.shape[0] if idx.dim() == 2 else 0)
         if not isinstance(draft, OmniBioTA) or not draft.config.autoregressive:

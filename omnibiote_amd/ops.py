@@ -799,14 +799,14 @@ def block_infer(x, params, rope, H, mask: MaskSpec, dropout_p=0.0, dropout_seed=
         L.lib().obte_block_fwd_infer(d, _ptr(x), _ptr(y), _ptr(w), w.numel(), _stream()), "obte_block_fwd_infer"), mask, dropout_p, dropout_seed)
 
 
-def _block_call(x, params, rope, H, ws, out, new_ws, call, mask=None, dropout_p=0.0, dropout_seed=0, cache=None, T_max=0, rows=None, at=0, one=False):
+def _block_call(x, params, rope, H, ws, out, new_ws, call, mask=None, dropout_p=0.0, dropout_seed=0, cache=None, T_max=0, rows=None, at=0, one=False, kv8=False):
     """What block_infer, block_prefill, block_decode, block_decode_rows and block_extend share: the checks of x (B, T, C — or, ``one``, (B, C)
     at T = 1), the cache, ``rows`` (a per-row int32 tensor and its name), the parameters and the tables (``at`` + T rows of them), the
     workspace (``new_ws(B, T, C, H, device)`` when ws is None) and the output (x's like when out is None), then ``call(d, y, ws)`` with the
-    descriptor by reference.  Returns y."""
+    descriptor by reference.  ``kv8``: the cache is the e4m3 one (kv8_cache_buffer).  Returns y."""
     _need(x, "x")
     if cache is not None:
-        _need(cache, "cache")
+        _need(cache, "cache", torch.uint8 if kv8 else bf16)
     if one:
         (B, Cc), T = x.shape, 1
     else:
@@ -816,7 +816,8 @@ def _block_call(x, params, rope, H, ws, out, new_ws, call, mask=None, dropout_p=
     for i, w in enumerate(params):
         _need(w, f"param{i}")
     _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
-    assert rope[0].shape[0] >= at + T and (cache is None or cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_max, H, Cc // H))
+    assert rope[0].shape[0] >= at + T
+    assert cache is None or cache.numel() * cache.element_size() == (L.lib().obte_kv8_cache_bytes if kv8 else L.lib().obte_kv_cache_bytes)(B, T_max, H, Cc // H)
     if ws is None:
         ws = new_ws(B, T, Cc, H, x.device)
     else:
@@ -932,6 +933,77 @@ def block_decode_rows(x, params, rope, H, cache, T_max, pos, max_pos, ws=None, o
     return _block_call(x, params, rope, H, ws, out, _decode_ws, lambda d, y, w: L.check(
         L.lib().obte_block_decode_rows(d, _ptr(x), _ptr(y), _ptr(cache), T_max, _ptr(pos), int(max_pos), _ptr(w), w.numel(), _stream()),
         "obte_block_decode_rows"), cache=cache, T_max=T_max, rows=(pos, "pos"), at=max_pos, one=True)
+
+
+# ---- the key/value cache stored as OCP e4m3 (include/omnibiote_hip_kv8.h; the format in plain torch: kvquant.py) ----
+def kv8_cache_buffer(B, T_max, H, hs, device) -> torch.Tensor:
+    """One layer's e4m3 key/value cache (K codes [B, H, T_max, hs], V codes, K scales fp32 [B, H, T_max], V scales) as the flat uint8
+    tensor the kv8 entry points take: 2 (hs + 4) bytes per cached head vector against the bf16 cache's 4 hs."""
+    nbytes = int(L.lib().obte_kv8_cache_bytes(B, T_max, H, hs))
+    if nbytes <= 0:
+        raise RuntimeError(f"kv8_cache_buffer: unsupported shape (B {B}, T_max {T_max}, n_head {H}, head size {hs}): head size 64 or 128")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _need_kv8(cache, B, T_max, H, hs):
+    _need(cache, "cache", torch.uint8)
+    assert cache.numel() == L.lib().obte_kv8_cache_bytes(B, T_max, H, hs)
+
+
+def kv8_cache_store(qkv, B, t, H, hs, cache, T_max, pos0):
+    """kv_cache_store into an e4m3 cache (obte_kv8_cache_store): the k and v thirds of the packed, rotated qkv [B*t, 3C], quantised per
+    head vector, into positions [pos0, pos0 + t)."""
+    _need(qkv, "qkv"); _need_kv8(cache, B, T_max, H, hs)
+    assert qkv.numel() == B * t * 3 * H * hs
+    L.check(L.lib().obte_kv8_cache_store(_ptr(qkv), B, t, H, hs, _ptr(cache), T_max, pos0, _stream()), "obte_kv8_cache_store")
+    return cache
+
+
+def kv8_cache_rope_store_rows(qkv, rope, pos, max_pos, B, H, hs, cache, T_max):
+    """kv_cache_rope_store_rows into an e4m3 cache (obte_kv8_cache_rope_store_rows): qkv is left with the same bits, the rotated k and
+    the v of row b are quantised into cache position pos[b]; a row whose value lies outside [0, max_pos] is left alone."""
+    _need(qkv, "qkv"); _need_kv8(cache, B, T_max, H, hs); _need_rows(pos, "pos", B)
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert qkv.numel() == B * 3 * H * hs
+    assert rope[0].shape[0] > max_pos and rope[1].shape[0] > max_pos
+    L.check(L.lib().obte_kv8_cache_rope_store_rows(_ptr(qkv), _ptr(rope[0]), _ptr(rope[1]), _ptr(pos), int(max_pos), B, H, hs, _ptr(cache), T_max,
+                                                   _stream()), "obte_kv8_cache_rope_store_rows")
+    return qkv
+
+
+def attn_decode_kv8(q, cache, B, T_max, n_keys, H, hs, scale, splits=0, q_ld=None, ws=None, n_keys_rows=None, out=None, lse=None):
+    """attn_decode over an e4m3 cache (obte_attn_decode_kv8): (o (B, C) bf16, lse (B, H) fp32).  n_keys_rows: None, every row over
+    cache positions [0, n_keys); or int32 (B,) on the device, row b over [0, n_keys_rows[b]) with n_keys the host's bound (a row whose
+    count lies outside [1, n_keys] gives zeros and lse = -inf).  splits, q_ld and ws as in attn_decode; out / lse: where the results go
+    (allocated here when None)."""
+    _need(q, "q", contiguous=False); _need_kv8(cache, B, T_max, H, hs)
+    if n_keys_rows is not None:
+        _need_rows(n_keys_rows, "n_keys_rows", B)
+    q_ld = q.shape[-1] if q_ld is None else q_ld
+    assert not q.is_contiguous() or q.numel() >= (B - 1) * q_ld + H * hs     # (a strided q: rows of q_ld elements, the caller's account)
+    o = torch.empty((B, H * hs), dtype=bf16, device=q.device) if out is None else out
+    lse = torch.empty((B, H), dtype=torch.float32, device=q.device) if lse is None else lse
+    if ws is None:
+        ws = torch.empty(int(L.lib().obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=q.device)
+    L.check(L.lib().obte_attn_decode_kv8(_ptr(q), q_ld, _ptr(cache), _ptr(o), _ptr(lse), B, T_max, int(n_keys), _ptr(n_keys_rows), H, hs, float(scale),
+                                         int(splits), _ptr(ws), ws.numel(), _stream()), "obte_attn_decode_kv8")
+    return o, lse
+
+
+def block_prefill_kv8(x, params, rope, H, mask: MaskSpec, cache, T_max, ws=None, out=None):
+    """block_prefill into an e4m3 cache (obte_block_fwd_prefill_kv8): y bit for bit block_infer's, the prompt's own attention on the
+    unquantised qkv, the rotated keys and the values quantised into positions [0, T)."""
+    return _block_call(x, params, rope, H, ws, out, block_infer_workspace, lambda d, y, w: L.check(
+        L.lib().obte_block_fwd_prefill_kv8(d, _ptr(x), _ptr(y), _ptr(w), w.numel(), _ptr(cache), T_max, _stream()), "obte_block_fwd_prefill_kv8"),
+        mask, cache=cache, T_max=T_max, kv8=True)
+
+
+def block_decode_kv8(x, params, rope, H, cache, T_max, pos, pos_rows=None, ws=None, out=None):
+    """block_decode (pos_rows None: every row at position `pos`) or block_decode_rows (pos_rows int32 (B,) on the device, `pos` the
+    host's bound on it) against an e4m3 cache (obte_block_decode_kv8): x (B, C) -> y (B, C).  rope: the FULL tables.  out may be x."""
+    return _block_call(x, params, rope, H, ws, out, _decode_ws, lambda d, y, w: L.check(
+        L.lib().obte_block_decode_kv8(d, _ptr(x), _ptr(y), _ptr(cache), T_max, int(pos), _ptr(pos_rows), _ptr(w), w.numel(), _stream()),
+        "obte_block_decode_kv8"), cache=cache, T_max=T_max, rows=None if pos_rows is None else (pos_rows, "pos_rows"), at=pos, one=True, kv8=True)
 
 
 # ---- n new positions per row against a filled cache (include/omnibiote_hip_extend.h) ----

@@ -30,6 +30,16 @@ library's default against 0 at B x ctx in {1 x 2048, 8 x 2048, 64 x 1024, 64 x 2
 the same way, and the launch profiler's split of a step on the new path.  One JSON line per (B, ctx).
 
     python tools/decode_bench.py --small-m [--rounds 5] [--steps 300]
+
+--kv8: the e4m3 key/value cache (KVCache(dtype="fp8"), include/omnibiote_hip_kv8.h) against the bf16 cache at B x ctx in {8 x 2048,
+64 x 1024, 64 x 2048} unless --batches / --contexts say otherwise, both alternating in one process over the same windows and rounds:
+(a) the attention alone, obte_attn_decode_kv8 and obte_attn_decode on preallocated outputs, each walking its own set of per-layer caches,
+at the library's split count (at 8 x 2048 also under every forced count of --sweep: does the bf16 split rule still pick well with half the
+bytes?); the bytes a call reads — 2 B H ctx (hs + 4) against 4 B H ctx hs — over its time as a share of 6.3 TB/s, the bytes of both cache
+sets, and `served_from` for each: a set that fits the 256 MB Infinity Cache is not an HBM measurement.  (b) decode_step on both caches.
+One JSON line per (B, ctx), then one line with the deviation of the fp8 attention output from the bf16 one on unit-variance inputs.
+
+    python tools/decode_bench.py --kv8 [--rounds 5] [--steps 300]
 """
 import argparse
 import contextlib
@@ -291,12 +301,93 @@ def small_m_tokens(m, B, ctx, rounds, steps, dev, ragged=False):
     return out
 
 
+def kv8_compare(m, B, ctx, rounds, steps, sweep, dev):
+    """the e4m3 cache against the bf16 cache: the attention alone over each set of per-layer caches, and decode_step"""
+    from omnibiote_amd import _lib
+    from omnibiote_amd.model import KVCache
+    lib = _lib.lib()
+    H, C = m.config.n_head, m.config.n_embd
+    hs = C // H
+    g = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    idx = torch.randint(4, m.config.vocab_size, (B, ctx), device=dev, generator=g)
+    caches = {"bf16": KVCache(m, B, ctx), "fp8": KVCache(m, B, ctx, dtype="fp8")}
+    for cache in caches.values():
+        m.prefill(idx[:, :ctx - 1], cache)
+    last = idx[:, -1].contiguous()
+    q = torch.randn(B, 3 * C, device=dev, generator=torch.Generator(device=dev).manual_seed(1)).to(torch.bfloat16)
+    ws = torch.empty(int(lib.obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=dev)
+    o = torch.empty(B, C, device=dev, dtype=torch.bfloat16)
+    lse = torch.empty(B, H, device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream().cuda_stream
+    ptrs = {k: [kv.data_ptr() for kv in cache.layers] for k, cache in caches.items()}
+    state = {"i": 0}
+
+    def attn(kind, splits):    # the C entry points themselves on preallocated outputs, each call on the next layer's cache
+        state["i"] += 1
+        kv = ptrs[kind][state["i"] % len(ptrs[kind])]
+        if kind == "fp8":
+            rc = lib.obte_attn_decode_kv8(q.data_ptr(), 3 * C, kv, o.data_ptr(), lse.data_ptr(), B, ctx, ctx, None, H, hs, 8.0 / C, splits, ws.data_ptr(),
+                                          ws.numel(), stream)
+        else:
+            rc = lib.obte_attn_decode(q.data_ptr(), 3 * C, kv, o.data_ptr(), lse.data_ptr(), B, ctx, ctx, H, hs, 8.0 / C, splits, ws.data_ptr(), ws.numel(),
+                                      stream)
+        if rc != 0:
+            _lib.check(rc, "obte_attn_decode" + ("_kv8" if kind == "fp8" else ""))
+
+    def step(kind):
+        def fn():                    # the same position every time: the context stays ctx long
+            caches[kind].reset(ctx - 1)
+            m.decode_step(last, caches[kind])
+        return fn
+    counts = [0] + [s for s in sweep if s == 1 or s * 64 <= max(ctx, 64)]
+    legs = {(kind, s): (lambda kind=kind, s=s: attn(kind, s)) for s in counts for kind in ("bf16", "fp8")}
+    legs.update({(kind, "step"): step(kind) for kind in ("bf16", "fp8")})
+    for key, fn in legs.items():
+        for _ in range(3 if key[1] == "step" else 8):
+            fn()
+    us = {key: [] for key in legs}
+    for r in range(rounds):
+        for key in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            us[key].append(timed(legs[key], steps))
+    med = {key: statistics.median(v) for key, v in us.items()}
+    nbytes = {"bf16": 4 * B * H * ctx * hs, "fp8": 2 * B * H * ctx * (hs + 4)}
+    sets = {k: sum(kv.numel() * kv.element_size() for kv in caches[k].layers) for k in caches}
+    name = lambda s: "default" if s == 0 else str(s)   # noqa: E731
+    out = {"B": B, "context": ctx, "windows": {"calls": steps, "rounds": rounds}, "default_splits": int(lib.obte_attn_decode_splits(B, H, hs, ctx)),
+           "cache_set_bytes": sets, "fp8_over_bf16_bytes": round(sets["fp8"] / sets["bf16"], 3),
+           "served_from": {k: "HBM" if v > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)" for k, v in sets.items()},
+           "attention_bytes_per_call": nbytes,
+           "attention_us": {k: {name(s): summary(us[(k, s)]) for s in counts} for k in caches},
+           "attention_share_of_6.3TBps": {k: {name(s): round(nbytes[k] / (med[(k, s)] * 1e-6) / HBM_RATE, 3) for s in counts} for k in caches},
+           "attention_fp8_over_bf16": {name(s): round(med[("fp8", s)] / med[("bf16", s)], 3) for s in counts},
+           "decode_step_us": {k: summary(us[(k, "step")], 1) for k in caches},
+           "decode_step_fp8_over_bf16": round(med[("fp8", "step")] / med[("bf16", "step")], 3)}
+    return out
+
+
+def kv8_unit_variance_deviation(dev, B=8, H=8, hs=128, T=2048):
+    """what e4m3 does to one attention output on unit-variance q, k, v: |o_fp8 - o_bf16| against the bf16 cache's output"""
+    from omnibiote_amd import ops
+    C = H * hs
+    qkv = torch.randn(B, T, 3 * C, device=dev, generator=torch.Generator(device=dev).manual_seed(2)).to(torch.bfloat16)
+    bf, f8 = ops.kv_cache_buffer(B, T, H, hs, dev), ops.kv8_cache_buffer(B, T, H, hs, dev)
+    ops.kv_cache_store(qkv, B, T, H, hs, bf, T, 0)
+    ops.kv8_cache_store(qkv, B, T, H, hs, f8, T, 0)
+    q = qkv[:, -1].contiguous()
+    a, _ = ops.attn_decode(q, bf, B, T, T, H, hs, 8.0 / C)
+    b, _ = ops.attn_decode_kv8(q, f8, B, T, T, H, hs, 8.0 / C)
+    d = (a.float() - b.float()).abs()
+    return {"unit_variance_attention": {"B": B, "H": H, "hs": hs, "keys": T, "max_abs_deviation": round(d.max().item(), 5),
+                                        "mean_abs_deviation": round(d.mean().item(), 6), "rms_of_bf16_output": round(a.float().square().mean().sqrt().item(), 5)}}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batches", default=None, help="default 1,8,64 (--ragged: 8,64)")
     p.add_argument("--contexts", default=None, help="default 128,1024,2048 (--ragged: 2048)")
     p.add_argument("--ragged", action="store_true", help="the one-position-per-row step against the uniform step")
     p.add_argument("--small-m", action="store_true", help="the weight-streaming product against the tile structures: alone, and in a decode step")
+    p.add_argument("--kv8", action="store_true", help="the e4m3 key/value cache against the bf16 cache: the attention alone, and decode_step")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300, help="decode steps (and attention calls) per timed window")
     p.add_argument("--baseline_ms", type=float, default=400.0, help="the full forward's window: as many calls as fit, at least 3")
@@ -310,6 +401,17 @@ def main():
         for B, ctx, ragged in ((1, 2048, False), (8, 2048, False), (8, 2048, True), (64, 1024, False), (64, 2048, False)):
             print(json.dumps(small_m_tokens(m, B, ctx, a.rounds, a.steps, dev, ragged)), flush=True)
             torch.cuda.empty_cache()
+        return
+    if a.kv8:
+        shapes = ((8, 2048), (64, 1024), (64, 2048))
+        if a.batches or a.contexts:
+            shapes = tuple((int(b), int(c)) for b in (a.batches or "8,64").split(",") for c in (a.contexts or "2048").split(","))
+        m = build(max(c for _, c in shapes), dev)
+        sweep = [int(s) for s in a.sweep.split(",")]
+        for B, ctx in shapes:
+            print(json.dumps(kv8_compare(m, B, ctx, a.rounds, a.steps, sweep if (B, ctx) == (8, 2048) else [], dev)), flush=True)
+            torch.cuda.empty_cache()
+        print(json.dumps(kv8_unit_variance_deviation(dev)), flush=True)
         return
     contexts = [int(c) for c in (a.contexts or ("2048" if a.ragged else "128,1024,2048")).split(",")]
     batches = [int(b) for b in (a.batches or ("8,64" if a.ragged else "1,8,64")).split(",")]
