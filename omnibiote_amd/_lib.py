@@ -216,6 +216,18 @@ SYMBOLS_KV8 = {
                                         c_stream]),
 }
 
+# a prefix cache shared by groups of rows, many samples per prompt (include/omnibiote_hip_shared.h): a table of its own as well
+ATTN_SHARED_MAX_SPLITS = 32   # OBTE_ATTN_SHARED_MAX_SPLITS
+SYMBOLS_SHARED = {
+    "obte_attn_shared_prefix_splits": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
+    "obte_attn_decode_shared_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "obte_attn_decode_shared": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_decode_shared_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "obte_block_decode_shared": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.c_int64, C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -244,7 +256,8 @@ def lib():
             except OSError as e:
                 raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
             for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
-                                            + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())):
+                                            + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
+                                            + list(SYMBOLS_SHARED.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -108,7 +108,9 @@ __device__ __forceinline__ void decode_keys(Part& st, const float* qf, const bf1
 // splits == 1: o and lse are final.  Else part[(bh * splits + split) * (HS + DEC_PAD)] = (acc[HS], m, l).
 // ROWS: row b has rows_n[b] + rows_off keys if that lies in [1, n_keys] (n_keys: the host's bound), else none (an inactive row: no
 // key is loaded, the state stays (m = -inf, l = 0, acc = 0)); per is formed here from the row's own count.
-template <int HS, bool ROWS>
+// PARTIAL (the suffix part of obte_attn_decode_shared, attention_shared.hip): the state leaves as a partial at one split too, o and lse
+// are not touched.
+template <int HS, bool ROWS, bool PARTIAL = false>
 __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16* __restrict__ q, int64_t q_ld, const bf16* __restrict__ cache,
                                                                       bf16* __restrict__ o, float* __restrict__ lse, float* __restrict__ part,
                                                                       int H, int64_t T_max, int64_t v_off, int n_keys, int per, float qscale,
@@ -177,7 +179,7 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16*
         for (int j = 0; j < 8; ++j) p.acc[j] = lds[w][lane][2 + j];
         merge(tot, p);
     }
-    if (splits == 1) {   // n_keys >= 1: l > 0; an inactive row (ROWS): l = 0, o = 0 and lse = -inf
+    if (!PARTIAL && splits == 1) {   // n_keys >= 1: l > 0; an inactive row (ROWS): l = 0, o = 0 and lse = -inf
         const float inv = (ROWS && tot.l == 0.f) ? 0.f : 1.0f / tot.l;
         bf16x8 out;
 #pragma unroll
@@ -324,6 +326,19 @@ extern "C" int obte_attn_decode_splits(int64_t B, int32_t n_head, int32_t head_d
 void obte_attn_decode_combine(int head_dim, int BH, int splits, const float* ws, bf16* o, float* lse, hipStream_t st) {
     if (head_dim == 128) hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3(BH), dim3(128), 0, st, ws, o, lse, splits);
     else hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3(BH), dim3(64), 0, st, ws, o, lse, splits);
+}
+
+// The kernel alone with PARTIAL (attention_shared.hip has checked every argument): BH rows of a cache of T_max positions, every row over
+// the keys [0, n_keys), `splits` partials per row to part in this file's layout, the keys divided as obte_attn_decode divides them.
+void obte_attn_decode_partials(int head_dim, int BH, int H, int splits, const bf16* q, int64_t q_ld, const bf16* cache, int64_t T_max, int n_keys, float qscale,
+                               float* part, hipStream_t st) {
+    const int per = (int)(cdiv64(cdiv64(n_keys, splits), DEC_CHUNK) * DEC_CHUNK);
+    const dim3 grid((unsigned)splits, (unsigned)BH);
+    const int64_t v_off = (int64_t)BH * T_max * head_dim;
+    if (head_dim == 128)
+        hipLaunchKernelGGL((attn_decode_kernel<128, false, true>), grid, dim3(DEC_WAVES * 64), 0, st, q, q_ld, cache, nullptr, nullptr, part, H, T_max, v_off, n_keys, per, qscale, nullptr, 0);
+    else
+        hipLaunchKernelGGL((attn_decode_kernel<64, false, true>), grid, dim3(DEC_WAVES * 64), 0, st, q, q_ld, cache, nullptr, nullptr, part, H, T_max, v_off, n_keys, per, qscale, nullptr, 0);
 }
 
 // obte_attn_decode (rows_n null: every row over the keys [0, n_keys)) and obte_attn_decode_rows_off (ROWS: row b over rows_n[b] + key_off keys,

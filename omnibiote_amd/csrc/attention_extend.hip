@@ -90,7 +90,10 @@ __device__ __forceinline__ void ext_inactive(bf16* o, float* lse, int64_t b, int
 
 // grid (splits, ceil(n / 32), B H), 256 threads.  pos: every row's first new position, or (ROWS) the bound of pos_rows[b].
 // splits == 1: o and lse are final.  Else part[((bh * tiles + tile) * splits + split) * PART] = the workgroup's state.
-template <int D, bool ROWS>
+// GROUP (the shared-prefix form behind obte_attn_decode_shared, attention_shared.hip; ROWS false): the "chunk" is a group of n rows that
+// share cache row b — the n queries of group b stand at rows b n + j of q as a chunk's do — every tile sees the keys [0, pos) and no
+// other, nothing is masked by position, and the state always leaves as a partial (o and lse are not touched).
+template <int D, bool ROWS, bool GROUP = false>
 __global__ __launch_bounds__(EXT_WAVES * 64, 2) void attn_extend_kernel(const bf16* __restrict__ q, int64_t q_ld, const bf16* __restrict__ cache, bf16* __restrict__ o,
                                                                       float* __restrict__ lse, float* __restrict__ part, int H, int64_t T_max, int64_t v_off, int n,
                                                                       int pos, const int32_t* __restrict__ pos_rows, float qscale) {
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(EXT_WAVES * 64, 2) void attn_extend_kernel(const bf
             return;
         }
     }
-    const int nk = p + j0 + nq;                                  // the keys a query of this tile may see: [0, nk), nk >= 1
+    const int nk = GROUP ? p : p + j0 + nq;                      // the keys a query of this tile may see: [0, nk), nk >= 1
     const int per = ((nk + splits - 1) / splits + EXT_KT - 1) / EXT_KT * EXT_KT;
     const int k0 = min(split * per, nk), k1 = min(k0 + per, nk);
     const int qpos = p + j0 + r;                                 // this lane's query sees keys 0 .. qpos
@@ -166,7 +169,7 @@ __global__ __launch_bounds__(EXT_WAVES * 64, 2) void attn_extend_kernel(const bf
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
             const int key = key0 + acc_row(g, h);
-            sc[g] = (key > qpos || key >= k1) ? -INFINITY : sc[g] * qscale;
+            sc[g] = ((!GROUP && key > qpos) || key >= k1) ? -INFINITY : sc[g] * qscale;
             mx = fmaxf(mx, sc[g]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -215,7 +218,7 @@ __global__ __launch_bounds__(EXT_WAVES * 64, 2) void attn_extend_kernel(const bf
         const float* w = mg + (wv - 1) * Sh::PART + lane;
         st.merge(w[Sh::NR * 64], w[(Sh::NR + 1) * 64], [&](int g) { return w[g * 64]; });
     }
-    if (splits == 1) {
+    if (!GROUP && splits == 1) {
         ext_finish<D>(st, smem + Sh::LDS - Sh::VREG, o, lse, b, bh, hd, C, n, j0, nq, lane);
         return;
     }
@@ -300,6 +303,19 @@ static void launch_extend(const dim3& grid, hipStream_t st, const bf16* q, int64
     else hipLaunchKernelGGL((attn_extend_kernel<D, false>), grid, dim3(EXT_WAVES * 64), 0, st, q, q_ld, cache, o, lse, ws, H, T_max, v_off, n, pos, pos_rows, qscale);
     if (grid.x > 1)
         hipLaunchKernelGGL(attn_extend_combine_kernel<D>, dim3(grid.y, grid.z), dim3(64), 0, st, (const float*)ws, o, lse, H, n, pos, pos_rows, (int)grid.x);
+}
+
+// The group form's launch (attention_shared.hip has checked every argument): P cache rows of n_prefix keys, G queries each at rows
+// p G + j of q, `splits` partials per (p, h, 32-query tile) to part in this file's layout.  One launch, nothing else.
+void obte_attn_extend_group_partials(int head_dim, int64_t P, int G, int H, int splits, const bf16* q, int64_t q_ld, const bf16* cache, int64_t T_pre, int n_prefix,
+                                     float qscale, float* part, hipStream_t st) {
+    static_assert(ExtShape<64>::PART == (64 / 2 + 2) * 64 && ExtShape<128>::PART == (128 / 2 + 2) * 64, "obte_ext_part_floats (common.h) states this layout");
+    const dim3 grid((unsigned)splits, (unsigned)tiles_of(G), (unsigned)(P * H));
+    const int64_t v_off = P * H * T_pre * head_dim;
+    if (head_dim == 128)
+        hipLaunchKernelGGL((attn_extend_kernel<128, false, true>), grid, dim3(EXT_WAVES * 64), 0, st, q, q_ld, cache, nullptr, nullptr, part, H, T_pre, v_off, G, n_prefix, nullptr, qscale);
+    else
+        hipLaunchKernelGGL((attn_extend_kernel<64, false, true>), grid, dim3(EXT_WAVES * 64), 0, st, q, q_ld, cache, nullptr, nullptr, part, H, T_pre, v_off, G, n_prefix, nullptr, qscale);
 }
 
 extern "C" int obte_attn_extend(const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max, int64_t n_new,

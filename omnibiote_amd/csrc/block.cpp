@@ -28,8 +28,9 @@
 // obte_block_fwd_infer is the full form's forward for a caller who will never run the backward: the same products, nothing kept
 // (InferLayout: seven [M, C] units instead of fifteen), c_fc's activation without its derivative.  obte_block_fwd_prefill is that call with
 // the rotated keys and the values also copied into a layer's key/value cache, obte_block_decode the same sequence on ONE new position per
-// row whose attention reads that cache (csrc/attention_decode.hip), obte_block_extend on n new positions per row (csrc/attention_extend.hip):
-// the four share infer_sequence() below.
+// row whose attention reads that cache (csrc/attention_decode.hip), obte_block_extend on n new positions per row (csrc/attention_extend.hip),
+// obte_block_decode_shared the decode step of P groups of rows over a prefix cache per group and a suffix cache per row
+// (csrc/attention_shared.hip): the five share infer_sequence() below.
 #include "common.h"
 
 namespace {
@@ -482,7 +483,8 @@ namespace {
 
 // The one sequence of a forward nobody will differentiate, on M rows laid out in `w`: obte_block_fwd_infer (the attention over the call's
 // own positions), obte_block_fwd_prefill (the same, and the rotated keys and the values kept), obte_block_decode (one new position per
-// row against the cache) and obte_block_extend (n new positions per row against it).  rope_cos / rope_sin / rope_T: what c_attn's epilogue rotates by (position = row % rope_T).
+// row against the cache), obte_block_extend (n new positions per row against it) and obte_block_decode_shared (one new position per row against
+// a prefix cache shared by the row's group and the row's own suffix cache).  rope_cos / rope_sin / rope_T: what c_attn's epilogue rotates by (position = row % rope_T).
 struct InferAttention {
     obte_bf16* kv_cache; int64_t T_max;   // the layer's cache (null: obte_block_fwd_infer)
     int64_t pos;                          // against the cache: every row's first new position
@@ -493,6 +495,9 @@ struct InferAttention {
     bool decode = false;                  // n_new == 1 on the one-query launchers (obte_block_decode, obte_block_decode_rows)
     bool kv8 = false;                     // the cache is the e4m3 one (include/omnibiote_hip_kv8.h): prefill and decode only, its launchers in the same places
     const char* who = "";                 // kv8: the entry point its launchers name in an error
+    // a prefix shared by groups of rows (obte_block_decode_shared, include/omnibiote_hip_shared.h): the prefix cache of P rows holding n_prefix
+    // positions; kv_cache / T_max / pos are then the SUFFIX cache of B rows, its slots and the step's slot (decode, uniform)
+    const obte_bf16* prefix_cache = nullptr; int64_t P = 0, T_pre = 0, n_prefix = 0;
 };
 int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const InferLayout& w, int64_t M, const float* rope_cos,
                    const float* rope_sin, int64_t rope_T, const InferAttention& at, obte_stream s) {
@@ -517,6 +522,9 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
         if (at.kv8)             // uniform (pos_rows null: every row over pos + 1 keys) or row b over its own pos_rows[b] + 1
             TRY(obte_attn_decode_kv8_off(at.who, w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos + 1, at.pos_rows, 1, H, hs, scale, 0, at.dec_ws,
                                          at.dec_ws_bytes, s));
+        else if (at.prefix_cache)   // the group's prefix once per 32 rows, then the row's own slots 0 .. pos
+            TRY(obte_attn_decode_shared(w.qkv, q_ld, at.prefix_cache, at.P, at.T_pre, at.n_prefix, at.kv_cache, d->B / at.P, at.T_max, at.pos + 1, w.att, nullptr, H, hs,
+                                        scale, 0, 0, at.dec_ws, at.dec_ws_bytes, s));
         else if (!at.decode)
             TRY(obte_attn_extend(w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.n_new, at.pos, at.pos_rows, H, hs, scale, 0, at.dec_ws, at.dec_ws_bytes, s));
         else if (at.pos_rows)   // row b over its own pos_rows[b] + 1 keys
@@ -650,6 +658,43 @@ extern "C" int64_t obte_block_extend_ws_bytes(int64_t B, int64_t n_new, int32_t 
 extern "C" int obte_block_extend(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, int64_t pos,
                                  const int32_t* pos_rows, void* ws, int64_t ws_bytes, obte_stream s) {
     return cached_step("obte_block_extend", d, x, y_out, kv_cache, T_max, pos, pos_rows, pos_rows != nullptr, false, ws, ws_bytes, s);
+}
+
+// InferLayout at T = 1 (M = P G rows) with obte_attn_decode_shared's partials behind it (include/omnibiote_hip_shared.h)
+extern "C" int64_t obte_block_decode_shared_ws_bytes(int64_t P, int64_t G, int32_t n_embd, int32_t n_head) {
+    if (P <= 0 || G <= 0 || P > 65535 || G >= (1ll << 20)) return 0;
+    const int64_t base = obte_block_infer_ws_bytes(P * G, 1, n_embd, n_head);
+    const int64_t part = base > 0 ? obte_attn_decode_shared_ws_bytes(P, G, n_head, n_embd / n_head, 0, 0) : 0;
+    return part > 0 ? base + align256(part) : 0;
+}
+
+// obte_block_decode's sequence with the cache in two parts: the new position joins the row's suffix cache at slot suf_pos, and is rotated
+// as absolute position n_prefix + suf_pos
+extern "C" int obte_block_decode_shared(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const obte_bf16* prefix_cache, int64_t P, int64_t T_pre,
+                                        int64_t n_prefix, obte_bf16* suffix_cache, int64_t T_suf, int64_t suf_pos, void* ws, int64_t ws_bytes, obte_stream s) {
+    const char* who = "obte_block_decode_shared";
+    TRY(check_desc(who, d));
+    OBTE_REQUIRE(d->T == 1, "%s: one new position per row (T = 1), got T = %lld", who, (long long)d->T);
+    if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
+        obte_set_error("%s: key_ranges, mask, query_bounds, out_rows and dropout_p must be NULL / 0 (a new position sees every cached one up to itself)", who);
+        return OBTE_EUNSUPPORTED;
+    }
+    OBTE_REQUIRE(x && y_out && prefix_cache && suffix_cache && ws, "%s: null pointer", who);
+    OBTE_REQUIRE(P >= 1 && d->B % P == 0, "%s: the %lld rows are not P = %lld groups of equal size", who, (long long)d->B, (long long)P);
+    OBTE_REQUIRE(T_pre >= 1 && n_prefix >= 1 && n_prefix <= T_pre, "%s: n_prefix = %lld outside [1, T_pre = %lld]", who, (long long)n_prefix, (long long)T_pre);
+    OBTE_REQUIRE(suf_pos >= 0 && suf_pos < T_suf, "%s: suffix slot %lld outside the suffix cache's [0, %lld)", who, (long long)suf_pos, (long long)T_suf);
+    OBTE_REQUIRE((((uintptr_t)prefix_cache | (uintptr_t)suffix_cache) & 15) == 0, "%s: both caches must be 16-byte aligned", who);
+    const int C = d->n_embd, H = d->n_head, hs = C / H;
+    const int64_t G = d->B / P;
+    const int64_t att_bytes = obte_attn_decode_shared_ws_bytes(P, G, H, hs, 0, 0);
+    OBTE_REQUIRE(att_bytes > 0 && T_pre < (1ll << 24) && T_suf < (1ll << 24), "%s: bad shape (P * n_head and B * n_head <= 65535)", who);
+    const InferLayout w(d->B, 1, C, H, ws);
+    const int64_t need = w.total + align256(att_bytes);
+    OBTE_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes, obte_block_decode_shared_ws_bytes() asks for %lld", who, (long long)ws_bytes, (long long)need);
+    InferAttention at = {suffix_cache, T_suf, suf_pos, (char*)ws + w.total, att_bytes, nullptr, 1, true, false, who};
+    at.prefix_cache = prefix_cache; at.P = P; at.T_pre = T_pre; at.n_prefix = n_prefix;
+    const int64_t row = (n_prefix + suf_pos) * (hs / 2);   // c_attn rotates every row by the tables' row n_prefix + suf_pos (rope_T = 1)
+    return infer_sequence(d, x, y_out, w, d->B, d->rope_cos + row, d->rope_sin + row, 1, at, s);
 }
 
 extern "C" int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,

@@ -11,6 +11,7 @@
 #include "../../include/omnibiote_hip_extend.h"
 #include "../../include/omnibiote_hip_spec.h"
 #include "../../include/omnibiote_hip_kv8.h"
+#include "../../include/omnibiote_hip_shared.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -99,6 +100,15 @@ constexpr int DEC_CHUNK = 64;    // split boundaries are multiples of this many 
 constexpr int DEC_PAD = 4;       // a partial is hs + 4 floats (acc[hs], m, l, 2 unused): 16-byte aligned rows
 // attn_decode_combine_kernel<head_dim> on BH rows of `splits` partials in ws (attention_decode.hip)
 void obte_attn_decode_combine(int head_dim, int BH, int splits, const float* ws, __bf16* o, float* lse, hipStream_t st);
+// ---- a prefix cache shared by groups of rows (attention_shared.hip, include/omnibiote_hip_shared.h): the two partial-only launches
+// attn_decode_kernel<.., PARTIAL> (attention_decode.hip): BH rows over the keys [0, n_keys) of their own cache row, `splits` partials each
+void obte_attn_decode_partials(int head_dim, int BH, int H, int splits, const __bf16* q, int64_t q_ld, const __bf16* cache, int64_t T_max, int n_keys, float qscale,
+                               float* part, hipStream_t st);
+// attn_extend_kernel<.., GROUP> (attention_extend.hip): the G queries at rows p G + j of q over the keys [0, n_prefix) of cache row p, `splits`
+// partials per (p, h, 32-query tile); a partial is obte_ext_part_floats() floats, [hs / 2 + 2][64 lanes] = O^T, m, l
+void obte_attn_extend_group_partials(int head_dim, int64_t P, int G, int H, int splits, const __bf16* q, int64_t q_ld, const __bf16* cache, int64_t T_pre, int n_prefix,
+                                     float qscale, float* part, hipStream_t st);
+static inline int64_t obte_ext_part_floats(int head_dim) { return (int64_t)(head_dim / 2 + 2) * 64; }
 // the e4m3 cache's launchers with the entry point named in an error and row b's count read as n_keys_rows[b] + key_off (attention_kv8.hip;
 // csrc/block.cpp hands a step's positions and 1)
 int obte_kv8_rope_store_rows_as(const char* who, obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos, int64_t max_pos, int64_t B,

@@ -1005,6 +1005,65 @@ class KVCache(CachePositions):
         self.extend_ws = None   # OmniBioTA.extend's workspace: allocated by the first call, replaced when a call needs more bytes
 
 
+class SharedPrefixCache(CachePositions):
+    """The cache of ``prompts`` prompts with ``samples`` samples drawn from each (include/omnibiote_hip_shared.h): ``batch = prompts *
+    samples`` rows, row p * samples + g the g-th sample of prompt p.  Per layer a PREFIX buffer of ``prompts`` rows and ``prefix_len``
+    positions, which ``OmniBioTA.prefill`` fills once per prompt and every row of the group reads, and a SUFFIX buffer of ``batch`` rows
+    and ``max_new`` slots for the rows' own tokens, both ``ops.kv_cache_buffer``'s; ``layers[i]`` is the pair.  ``pos`` counts absolute
+    positions as on a ``KVCache`` (a token's RoPE row is ``pos``); ``n_prefix`` is the prompt length the last prefill left, and slot
+    ``pos - n_prefix`` of the suffix takes the next token.  ``group = samples``.
+
+    Uniform mode only (every prompt of a call has the same length): ``park`` and ``rewind_rows`` raise, and ``rewind`` does not step
+    into the prefix.  bf16 only.  ``prefill`` (without ``lengths`` / ``chunk``), ``decode_step`` and ``generate(num_samples=)`` run on
+    it; ``extend`` and the speculative loop raise NotImplementedError."""
+
+    def __init__(self, model, prompts, samples, prefix_len, max_new):
+        cfg = model.config
+        if not cfg.autoregressive:
+            raise ValueError("SharedPrefixCache: the model is not autoregressive (config.autoregressive): an encoder has no next token")
+        prompts, samples, prefix_len, max_new = int(prompts), int(samples), int(prefix_len), int(max_new)
+        if prompts < 1 or samples < 1:
+            raise ValueError(f"SharedPrefixCache: prompts and samples must be at least 1, got {prompts} and {samples}")
+        if prefix_len < 1 or max_new < 1 or prefix_len + max_new > cfg.block_size:
+            raise ValueError(f"SharedPrefixCache: prefix_len {prefix_len} and max_new {max_new} must be at least 1 and together at most "
+                             f"block_size = {cfg.block_size}")
+        wte = model.transformer.wte.weight
+        _require_hip(wte, "SharedPrefixCache")
+        super().__init__(prompts * samples, prefix_len + max_new)
+        self._shape(prompts, samples, prefix_len, max_new)
+        hs = cfg.n_embd // cfg.n_head
+        self.layers = [(ops.kv_cache_buffer(prompts, prefix_len, cfg.n_head, hs, wte.device),
+                        ops.kv_cache_buffer(self.batch, max_new, cfg.n_head, hs, wte.device)) for _ in model.transformer.h]
+        self.decode_ws = ops.block_decode_shared_workspace(prompts, samples, cfg.n_embd, cfg.n_head, wte.device)
+        self.extend_ws = None
+
+    def _shape(self, prompts, samples, prefix_len, max_new):
+        """host integers only (the position logic below reads nothing else)"""
+        self.prompts, self.group, self.prefix_len, self.max_new = prompts, samples, prefix_len, max_new
+        self.n_prefix = 0   # set by prefill
+
+    def require_room(self, what, n, detail=False):
+        """ValueError in ``OmniBioTA.what``'s name unless ``n`` more suffix slots are free"""
+        if self.pos - self.n_prefix + n > self.max_new:
+            tail = f": {n} more from slot {self.pos - self.n_prefix} do not fit" if detail else ""
+            raise ValueError(f"OmniBioTA.{what}: the shared-prefix cache's {self.max_new} suffix slots are full{tail}")
+
+    def park(self, done):
+        raise ValueError("SharedPrefixCache.park: a shared-prefix cache is in uniform mode (rows are not parked)")
+
+    def rewind_rows(self, back, now=None):
+        raise ValueError("SharedPrefixCache.rewind_rows: a shared-prefix cache is in uniform mode: use rewind")
+
+    def rewind(self, n):
+        """``CachePositions.rewind`` within the rows' own tokens: at least one of them stays (the prefix is the prompt, not a sample)"""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"SharedPrefixCache.rewind: n must not be negative, got {n}")
+        if self.pos - n < self.n_prefix + 1:
+            raise ValueError(f"SharedPrefixCache.rewind: {n} positions back from {self.pos} steps into the shared prefix of {self.n_prefix}")
+        self.pos -= n
+
+
 class OmniBioTA(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -1113,6 +1172,14 @@ class OmniBioTA(nn.Module):
             raise NotImplementedError(f"OmniBioTA.{what}: the cache is an fp8 cache (KVCache(dtype='fp8')), over which only one new position per "
                                       "row attends (prefill, decode_step, generate); several new positions in one call need a bf16 cache")
 
+    @staticmethod
+    def _refuse_shared(what, cache):
+        """NotImplementedError in ``OmniBioTA.what``'s name on a shared-prefix cache: before anything is launched or any state changes"""
+        if isinstance(cache, SharedPrefixCache):
+            raise NotImplementedError(f"OmniBioTA.{what}: the cache is a shared-prefix cache (SharedPrefixCache), on which every row takes one new "
+                                      "position at a time (prefill, decode_step, generate(num_samples=)); several new positions per row in one "
+                                      "call need a KVCache")
+
     def _readout_rows(self, x):
         """The readout of a generation step's (B, C) rows: at most ops' small_m_max of them, bf16 on the GPU, through the
         weight-streaming product with MuReadout.forward's alpha; anything else through the module."""
@@ -1136,6 +1203,8 @@ class OmniBioTA(nn.Module):
         every further ``chunk`` of them through ``extend``'s block path at uniform positions (right padding stays harmless under the
         causal rule), each embedded on its own — the activation workspace is sized by the chunk, no (B, T0, C) tensor exists — and
         row b's last hidden state is picked up in the chunk that holds it.  The cache ends in the same state."""
+        if isinstance(cache, SharedPrefixCache):
+            return self._prefill_shared(idx, cache, lengths, chunk)
         if chunk is not None:
             self._refuse_fp8("prefill(chunk=)", cache)
         if idx.dim() != 2:
@@ -1166,6 +1235,35 @@ class OmniBioTA(nn.Module):
             return self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()))
         last = x[torch.arange(b, device=idx.device), (cache.positions - 1).long()]          # (B, C): row b at its own last position
         return self._readout_rows(self.transformer.ln_f(last.contiguous()))
+
+    def _prefill_shared(self, idx, cache, lengths, chunk):
+        """``prefill`` on a ``SharedPrefixCache``: ``idx`` (P, T0), one row per prompt, through the same kernels into the prefix buffers;
+        the logits of the last position come back once per sample, (P * G, vocab), row p repeated G times"""
+        if lengths is not None or chunk is not None:
+            raise ValueError("OmniBioTA.prefill: a shared-prefix cache takes prompts of one length in one piece (no lengths=, no chunk=)")
+        if idx.dim() != 2:
+            raise ValueError(f"OmniBioTA.prefill: idx must be (P, T0), got {tuple(idx.shape)}")
+        p, t = idx.shape
+        self._check_generation("prefill", p)
+        if p != cache.prompts:
+            raise ValueError(f"OmniBioTA.prefill: the shared-prefix cache was built for {cache.prompts} prompts, got {p}")
+        if t == 0:
+            raise ValueError("OmniBioTA.prefill: the prompt is empty")
+        if t > cache.prefix_len:
+            raise ValueError(f"OmniBioTA.prefill: a prompt of {t} tokens does not fit the cache's prefix of {cache.prefix_len} positions")
+        wte = self.transformer.wte.weight
+        _require_hip(wte, "OmniBioTA")
+        if not idx.is_cuda:
+            raise RuntimeError("OmniBioTA.prefill: idx must be on the GPU")
+        mask = ops.MaskSpec.from_user(_autoregressive_mask(True, None, p, t, idx.device), p, t, self.config.n_head, idx.device)
+        x = ops.embedding_fwd(idx.contiguous(), wte)
+        ws = ops.block_infer_workspace(p, t, self.config.n_embd, self.config.n_head, idx.device)
+        for block, (prefix, _) in zip(self.transformer.h, cache.layers):
+            ops.block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, prefix, cache.prefix_len, ws=ws, out=x)
+        cache.reset(t)
+        cache.n_prefix = t
+        logits = self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()))
+        return logits.repeat_interleave(cache.group, dim=0)
 
     @staticmethod
     def _prefilled(cache, t, lens, device):
@@ -1226,6 +1324,7 @@ class OmniBioTA(nn.Module):
         ``"all"`` — what verifying a block of drafted tokens or scoring a continuation needs.  ``pos`` / ``positions`` advance
         by n; parked rows stay parked.  n == 1 is ``decode_step``.  ``KVCache.rewind`` steps back over tokens that are not kept."""
         self._refuse_fp8("extend", cache)
+        self._refuse_shared("extend", cache)
         if tokens.dim() != 2:
             raise ValueError(f"OmniBioTA.extend: tokens must be (B, n), got {tuple(tokens.shape)}")
         b, n = tokens.shape
@@ -1265,6 +1364,12 @@ class OmniBioTA(nn.Module):
         if not tokens.is_cuda:
             raise RuntimeError("OmniBioTA.decode_step: tokens must be on the GPU")
         x = ops.embedding_fwd(tokens.contiguous(), wte)
+        if isinstance(cache, SharedPrefixCache):   # the group's prefix and the row's own slots: two buffers per layer
+            for block, (prefix, suffix) in zip(self.transformer.h, cache.layers):
+                ops.block_decode_shared(x, self._block_params(block), block.attn.rope(), self.config.n_head, prefix, cache.prompts, cache.prefix_len,
+                                        cache.n_prefix, suffix, cache.max_new, cache.pos - cache.n_prefix, ws=cache.decode_ws, out=x)
+            cache.advance(1)
+            return self._readout_rows(self.transformer.ln_f(x))
         # rows mode: every row at its own position, read on the device, with pos the host's bound on it
         if cache.dtype == "fp8":   # one entry point for both forms: (pos, pos_rows)
             step, at = ops.block_decode_kv8, (cache.pos, cache.positions)
@@ -1277,7 +1382,7 @@ class OmniBioTA(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None, lengths=None, pad_token=None, top_p=None,
-                 sampler="torch", kv_dtype="bf16"):
+                 sampler="torch", kv_dtype="bf16", num_samples=None):
         """nanoGPT's generate(): ``idx`` (B, T0) int64 continued by up to ``max_new_tokens`` sampled tokens (``sample_next``); returns
         (B, T0 + n) int64.  The prompt runs once (``prefill``), every new token costs one ``decode_step``.  Where nanoGPT crops the
         context to block_size, this raises: T0 + max_new_tokens must fit.  ``eos_token``: a row that has produced it keeps producing
@@ -1294,11 +1399,22 @@ class OmniBioTA(nn.Module):
         the uniforms of the whole call are drawn once, ``torch.rand((max_new_tokens, B), generator=generator)``, and every step's
         tokens come from one launch on the step's bf16 logits (``ops.sample_logits``: the same rule, another random stream).
 
-        ``kv_dtype``: "bf16" or "fp8", the ``KVCache`` the call builds (``KVCache``: the e4m3 cache, about half the bytes)."""
+        ``kv_dtype``: "bf16" or "fp8", the ``KVCache`` the call builds (``KVCache``: the e4m3 cache, about half the bytes).
+
+        ``num_samples`` (an int G >= 1; None: everything above): G samples of every prompt.  ``idx`` is (P, T0), the result
+        (P * G, T0 + n) int64 with row p * G + g prompt p followed by its g-th sample — what ``generate(idx.repeat_interleave(G, 0), ...)``
+        returns, drawn the same way (the device sampler's uniforms are ``torch.rand((max_new_tokens, P * G), generator=generator)``), but
+        on a ``SharedPrefixCache``: the prompt is prefilled and stored once per prompt and read once per 32 samples.  Prompts of one
+        length and a bf16 cache only: with ``lengths`` or ``kv_dtype="fp8"`` it raises ValueError."""
         if sampler not in ("torch", "device"):
             raise ValueError(f"OmniBioTA.generate: sampler must be 'torch' or 'device', got {sampler!r}")
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"OmniBioTA.generate: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
+        if num_samples is not None:
+            if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
+                raise ValueError(f"OmniBioTA.generate: num_samples must be an integer of at least 1, got {num_samples!r}")
+            if lengths is not None or kv_dtype != "bf16":
+                raise ValueError("OmniBioTA.generate: num_samples needs prompts of one length (no lengths=) and the bf16 cache (no kv_dtype='fp8')")
         _check_top_p("OmniBioTA.generate", top_p)
         self._check_generation("generate", idx.shape[0] if idx.dim() == 2 else 0)
         if idx.dim() != 2:
@@ -1311,10 +1427,15 @@ class OmniBioTA(nn.Module):
                                          pad_token, top_p, sampler, kv_dtype)
         if max_new_tokens < 0 or t0 + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {t0} prompt tokens + {max_new_tokens} new ones exceed block_size = {self.config.block_size}")
+        if num_samples is None:
+            rows = idx
+        else:                                                               # row p G + g: prompt p, sample g
+            rows, b = idx.repeat_interleave(num_samples, dim=0), b * num_samples
         if max_new_tokens == 0:
-            return idx.clone()
-        cache = KVCache(self, b, t0 + max_new_tokens, dtype=kv_dtype)
-        out = [idx]
+            return rows.clone()
+        cache = KVCache(self, b, t0 + max_new_tokens, dtype=kv_dtype) if num_samples is None else SharedPrefixCache(self, idx.shape[0], num_samples, t0,
+                                                                                                                  max_new_tokens)
+        out = [rows]
         logits = self.prefill(idx, cache)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
         done = None
@@ -1370,6 +1491,7 @@ class OmniBioTA(nn.Module):
         token (B,) int64)`` on the device; nothing waits for them.  The caller reads n_accept and steps both caches back by
         ``k - n_accept[b]`` (``rewind_rows``): row b has emitted x_0 .. x_{a-1} and ``token``, its new pending token."""
         self._refuse_fp8("draft_and_verify", cache)         # (the draft only takes decode steps: its cache may be either)
+        self._refuse_shared("draft_and_verify", cache)
         b = pending.shape[0]
         greedy = uniforms is None or temperature == 0 or top_k == 1
         draws, u_accept, u_draw = (None, None, None) if greedy else uniforms
@@ -1389,7 +1511,7 @@ class OmniBioTA(nn.Module):
 
     @torch.no_grad()
     def generate_speculative(self, idx, max_new_tokens, draft, k=4, temperature=1.0, top_k=None, top_p=None, generator=None, eos_token=None,
-                             lengths=None, pad_token=None, return_stats=False, kv_dtype="bf16"):
+                             lengths=None, pad_token=None, return_stats=False, kv_dtype="bf16", num_samples=None):
         """``generate`` by draft and verify: ``draft`` — any autoregressive OmniBioTA on the same device with the same vocabulary, a smaller
         model in practice, this model itself for a self-check — proposes ``k`` tokens per round (1 <= k <= 31), this model scores them in
         one ``extend`` and ``ops.spec_verify`` keeps a prefix of them and adds one token of its own, so that every emitted token is
@@ -1408,6 +1530,9 @@ class OmniBioTA(nn.Module):
         ``(out, out_lengths)`` as ``generate`` does (``ragged_output``).  ``return_stats`` appends a dict of host ints: ``rounds``, and
         over all rows and rounds ``drafted`` (k per running row) and ``accepted`` (the drafted tokens that stood)."""
         what = "generate_speculative"
+        if num_samples is not None:
+            raise NotImplementedError(f"OmniBioTA.{what}: num_samples: verifying a drafted block attends from several new positions per row, which "
+                                      "is not built over a shared-prefix cache (SharedPrefixCache); repeat the prompts instead")
         if kv_dtype == "fp8":
             raise NotImplementedError(f"OmniBioTA.{what}: kv_dtype 'fp8': verifying a drafted block attends from several new positions per row, "
                                       "which is not built over an fp8 cache; use the bf16 cache")

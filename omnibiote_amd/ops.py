@@ -1063,6 +1063,56 @@ def block_extend(x, params, rope, H, cache, T_max, pos, pos_rows=None, ws=None, 
         cache=cache, T_max=T_max, rows=None if pos_rows is None else (pos_rows, "pos_rows"), at=pos)
 
 
+# ---- a prefix cache shared by groups of rows: many samples per prompt (include/omnibiote_hip_shared.h) ----
+def attn_decode_shared(q, prefix_cache, P, T_pre, n_prefix, suffix_cache, G, T_suf, n_suffix, H, hs, scale, prefix_splits=0, suffix_splits=0, q_ld=None,
+                       ws=None, out=None, lse=None):
+    """One query per (b, h) of B = P * G rows, row b = p * G + g, over positions [0, n_prefix) of row p of the prefix cache followed by
+    slots [0, n_suffix) of row b of the suffix cache (obte_attn_decode_shared): (o (B, C) bf16, lse (B, H) fp32).  Both caches are
+    kv_cache_buffer's, of P and of B rows.  q: any bf16 tensor whose row b holds the query of head h at b * q_ld + h * hs (q_ld
+    defaults to its last dimension).  n_suffix = 0: the prefix alone (suffix_cache may then be None).  The split counts: 0 = the
+    library's choice, else a forced count.  out / lse: where the results go (allocated here when None)."""
+    _need(q, "q", contiguous=False); _need(prefix_cache, "prefix_cache")
+    B = P * G
+    q_ld = q.shape[-1] if q_ld is None else q_ld
+    assert prefix_cache.numel() * 2 == L.lib().obte_kv_cache_bytes(P, T_pre, H, hs)
+    if suffix_cache is not None:
+        _need(suffix_cache, "suffix_cache")
+        assert suffix_cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_suf, H, hs)
+    o = torch.empty((B, H * hs), dtype=bf16, device=q.device) if out is None else out
+    lse = torch.empty((B, H), dtype=torch.float32, device=q.device) if lse is None else lse
+    if ws is None:
+        ws = torch.empty(max(int(L.lib().obte_attn_decode_shared_ws_bytes(P, G, H, hs, int(prefix_splits), int(suffix_splits))), 16), dtype=torch.uint8,
+                         device=q.device)
+    L.check(L.lib().obte_attn_decode_shared(_ptr(q), q_ld, _ptr(prefix_cache), P, T_pre, int(n_prefix), _ptr(suffix_cache), G, T_suf, int(n_suffix), _ptr(o),
+                                            _ptr(lse), H, hs, float(scale), int(prefix_splits), int(suffix_splits), _ptr(ws), ws.numel(), _stream()),
+            "obte_attn_decode_shared")
+    return o, lse
+
+
+def block_decode_shared_workspace(P, G, Cc, H, device) -> torch.Tensor:
+    nbytes = int(L.lib().obte_block_decode_shared_ws_bytes(P, G, Cc, H))
+    if nbytes <= 0:
+        raise RuntimeError(f"block_decode_shared: unsupported shape (P {P}, G {G}, n_embd {Cc}, n_head {H}): head size 64 or 128, "
+                           "n_embd a multiple of 64 and <= 4096, P * G * n_head <= 65535")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def block_decode_shared(x, params, rope, H, prefix_cache, P, T_pre, n_prefix, suffix_cache, T_suf, suf_pos, ws=None, out=None):
+    """block_decode for P groups of G = B / P rows over a shared prefix (obte_block_decode_shared): x (B, C) -> y (B, C).  Every row's new
+    token stands at absolute position n_prefix + suf_pos and joins slot suf_pos of its row of the suffix cache; it attends over
+    positions [0, n_prefix) of its group's row of the prefix cache and its own slots [0, suf_pos].  rope: the FULL tables (at least
+    n_prefix + suf_pos + 1 rows).  out may be x itself."""
+    _need(prefix_cache, "prefix_cache")
+    B, Cc = x.shape
+    if P < 1 or B % P:
+        raise ValueError(f"block_decode_shared: {B} rows are not P = {P} groups of equal size")
+    assert prefix_cache.numel() * 2 == L.lib().obte_kv_cache_bytes(P, T_pre, H, Cc // H)
+    return _block_call(x, params, rope, H, ws, out, lambda B_, T_, C_, H_, dev: block_decode_shared_workspace(P, B_ // P, C_, H_, dev), lambda d, y, w: L.check(
+        L.lib().obte_block_decode_shared(d, _ptr(x), _ptr(y), _ptr(prefix_cache), P, T_pre, int(n_prefix), _ptr(suffix_cache), T_suf, int(suf_pos), _ptr(w),
+                                         w.numel(), _stream()), "obte_block_decode_shared"),
+        cache=suffix_cache, T_max=T_suf, at=n_prefix + suf_pos, one=True)
+
+
 def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None, dropout_p=0.0, dropout_seed=0, ln_partials=None,
               ln_partial_mode=0, out_rows=None, dy_masked=None, dx_mask_seed=None, acc32=None, acc32_mode=0):
     """accumulate_into: optional list of 6 tensors-or-None (same order as params).  When the four matrix entries are all

@@ -40,6 +40,15 @@ sets, and `served_from` for each: a set that fits the 256 MB Infinity Cache is n
 One JSON line per (B, ctx), then one line with the deviation of the fp8 attention output from the bf16 one on unit-variance inputs.
 
     python tools/decode_bench.py --kv8 [--rounds 5] [--steps 300]
+
+--shared: G samples of one prompt on a shared-prefix cache (SharedPrefixCache, include/omnibiote_hip_shared.h) against the same rows on a
+replicated KVCache, at P = 1, G in {8, 64}, n_prefix = 2048, n_suffix in {1, 256}, both alternating in one process over the same windows
+and rounds: (a) the attention alone, obte_attn_decode_shared and obte_attn_decode on preallocated outputs at the library's split counts,
+each walking its own set of per-layer caches, with the bytes each must read by the model 4 hs B H n against
+4 hs H (P ceil(G / 32) n_prefix + B n_suffix); (b) decode_step on both caches; (c) the prefill of generate (G rows against one), one call
+per window; and the bytes of both cache sets.  One JSON line per (G, n_suffix).
+
+    python tools/decode_bench.py --shared [--rounds 5] [--steps 300]
 """
 import argparse
 import contextlib
@@ -381,6 +390,80 @@ def kv8_unit_variance_deviation(dev, B=8, H=8, hs=128, T=2048):
                                         "mean_abs_deviation": round(d.mean().item(), 6), "rms_of_bf16_output": round(a.float().square().mean().sqrt().item(), 5)}}
 
 
+def shared_compare(m, G, n_prefix, n_suffix, rounds, steps, dev):
+    """G samples of one prompt: the shared-prefix cache against the replicated cache — the attention alone, decode_step, the prefill"""
+    from omnibiote_amd import _lib
+    from omnibiote_amd.model import KVCache, SharedPrefixCache
+    lib = _lib.lib()
+    H, C = m.config.n_head, m.config.n_embd
+    hs, ctx = C // H, n_prefix + n_suffix
+    g = torch.Generator(device=dev).manual_seed(G * 10007 + ctx)
+    prompt = torch.randint(4, m.config.vocab_size, (1, n_prefix), device=dev, generator=g)
+    rows = prompt.repeat_interleave(G, 0).contiguous()
+    last = torch.randint(4, m.config.vocab_size, (G,), device=dev, generator=g)
+    caches = {"replicated": KVCache(m, G, ctx), "shared": SharedPrefixCache(m, 1, G, n_prefix, n_suffix)}
+    for kv in caches["replicated"].layers:                     # the rows' own positions hold finite values of the keys' size (only the time is read)
+        kv.normal_()
+    for _, suffix in caches["shared"].layers:
+        suffix.normal_()
+    prefill = {"replicated": lambda: m.prefill(rows, caches["replicated"]), "shared": lambda: m.prefill(prompt, caches["shared"])}
+    q = torch.randn(G, 3 * C, device=dev, generator=torch.Generator(device=dev).manual_seed(1)).to(torch.bfloat16)
+    ws = torch.empty(max(int(lib.obte_attn_decode_ws_bytes(G, H, hs)), int(lib.obte_attn_decode_shared_ws_bytes(1, G, H, hs, 0, 0))), dtype=torch.uint8, device=dev)
+    o = torch.empty(G, C, device=dev, dtype=torch.bfloat16)
+    lse = torch.empty(G, H, device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream().cuda_stream
+    rep_ptrs = [kv.data_ptr() for kv in caches["replicated"].layers]
+    sh_ptrs = [(a.data_ptr(), b.data_ptr()) for a, b in caches["shared"].layers]
+    state = {"i": 0}
+
+    def attn(kind):            # the C entry points themselves on preallocated outputs, each call on the next layer's cache
+        state["i"] += 1
+        if kind == "shared":
+            pre, suf = sh_ptrs[state["i"] % len(sh_ptrs)]
+            rc = lib.obte_attn_decode_shared(q.data_ptr(), 3 * C, pre, 1, n_prefix, n_prefix, suf, G, n_suffix, n_suffix, o.data_ptr(), lse.data_ptr(), H, hs,
+                                             8.0 / C, 0, 0, ws.data_ptr(), ws.numel(), stream)
+        else:
+            rc = lib.obte_attn_decode(q.data_ptr(), 3 * C, rep_ptrs[state["i"] % len(rep_ptrs)], o.data_ptr(), lse.data_ptr(), G, ctx, ctx, H, hs, 8.0 / C, 0,
+                                      ws.data_ptr(), ws.numel(), stream)
+        if rc != 0:
+            _lib.check(rc, "obte_attn_decode" + ("_shared" if kind == "shared" else ""))
+
+    def step(kind):
+        def fn():                    # the same position every time: the last suffix slot, the context stays ctx long
+            caches[kind].reset(ctx - 1)
+            m.decode_step(last, caches[kind])
+        return fn
+    for kind in caches:
+        prefill[kind]()
+    legs = {(kind, what): (step(kind) if what == "step" else (lambda kind=kind: attn(kind))) for what in ("attention", "step") for kind in caches}
+    for key, fn in legs.items():
+        for _ in range(3 if key[1] == "step" else 8):
+            fn()
+    us = {key: [] for key in legs}
+    us.update({(kind, "prefill"): [] for kind in caches})
+    for r in range(rounds):
+        for key in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            us[key].append(timed(legs[key], steps))
+        for kind in (list(caches) if r % 2 == 0 else list(caches)[::-1]):
+            us[(kind, "prefill")].append(timed(prefill[kind], 1))
+    med = {key: statistics.median(v) for key, v in us.items()}
+    sets = {"replicated": sum(kv.numel() * 2 for kv in caches["replicated"].layers), "shared": sum(a.numel() * 2 + b.numel() * 2 for a, b in caches["shared"].layers)}
+    nbytes = {"replicated": 4 * hs * G * H * ctx, "shared": 4 * hs * H * (-(-G // 32) * n_prefix + G * n_suffix)}
+    out = {"P": 1, "G": G, "n_prefix": n_prefix, "n_suffix": n_suffix, "windows": {"calls": steps, "rounds": rounds, "prefills_per_window": 1},
+           "splits": {"replicated": int(lib.obte_attn_decode_splits(G, H, hs, ctx)), "shared_prefix": int(lib.obte_attn_shared_prefix_splits(1, G, H, hs, n_prefix)),
+                      "shared_suffix": int(lib.obte_attn_decode_splits(G, H, hs, n_suffix))},
+           "cache_set_bytes": sets, "replicated_over_shared_set_bytes": round(sets["replicated"] / sets["shared"], 2),
+           "served_from": {k: "HBM" if v > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)" for k, v in sets.items()},
+           "attention_bytes_per_call": nbytes, "replicated_over_shared_attention_bytes": round(nbytes["replicated"] / nbytes["shared"], 2)}
+    for what, nd in (("attention", 2), ("step", 1), ("prefill", 1)):
+        out[what + "_us"] = {k: summary(us[(k, what)], nd) for k in caches}
+        out[what + "_replicated_over_shared"] = round(med[("replicated", what)] / med[("shared", what)], 2)
+        gap = med[("replicated", what)] - med[("shared", what)]
+        spreads = [max(us[(k, what)]) - min(us[(k, what)]) for k in caches]
+        out[what + "_gap_us_and_spreads"] = [round(gap, 2)] + [round(v, 2) for v in spreads]
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batches", default=None, help="default 1,8,64 (--ragged: 8,64)")
@@ -388,6 +471,7 @@ def main():
     p.add_argument("--ragged", action="store_true", help="the one-position-per-row step against the uniform step")
     p.add_argument("--small-m", action="store_true", help="the weight-streaming product against the tile structures: alone, and in a decode step")
     p.add_argument("--kv8", action="store_true", help="the e4m3 key/value cache against the bf16 cache: the attention alone, and decode_step")
+    p.add_argument("--shared", action="store_true", help="G samples of one prompt: the shared-prefix cache against the replicated cache")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300, help="decode steps (and attention calls) per timed window")
     p.add_argument("--baseline_ms", type=float, default=400.0, help="the full forward's window: as many calls as fit, at least 3")
@@ -401,6 +485,13 @@ def main():
         for B, ctx, ragged in ((1, 2048, False), (8, 2048, False), (8, 2048, True), (64, 1024, False), (64, 2048, False)):
             print(json.dumps(small_m_tokens(m, B, ctx, a.rounds, a.steps, dev, ragged)), flush=True)
             torch.cuda.empty_cache()
+        return
+    if a.shared:
+        m = build(2048 + 256, dev)
+        for G in (8, 64):
+            for n_suffix in (1, 256):
+                print(json.dumps(shared_compare(m, G, 2048, n_suffix, a.rounds, a.steps, dev)), flush=True)
+                torch.cuda.empty_cache()
         return
     if a.kv8:
         shapes = ((8, 2048), (64, 1024), (64, 2048))
