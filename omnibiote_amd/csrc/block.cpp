@@ -493,8 +493,8 @@ struct InferAttention {
                                           // joins the cache store (rope_cos / rope_sin: the FULL tables)
     int64_t n_new = 0;                    // > 0: against the cache, n_new new positions per row; 0: the attention of the call's own T positions
     bool decode = false;                  // n_new == 1 on the one-query launchers (obte_block_decode, obte_block_decode_rows)
-    bool kv8 = false;                     // the cache is the e4m3 one (include/omnibiote_hip_kv8.h): prefill and decode only, its launchers in the same places
-    const char* who = "";                 // kv8: the entry point its launchers name in an error
+    bool kv8 = false;                     // the cache is the e4m3 one (include/omnibiote_hip_kv8.h): prefill and decode only
+    const char* who = "";                 // the entry point that the cache's launchers name in an error where they take a name
     // a prefix shared by groups of rows (obte_block_decode_shared, include/omnibiote_hip_shared.h): the prefix cache of P rows holding n_prefix
     // positions; kv_cache / T_max / pos are then the SUFFIX cache of B rows, its slots and the step's slot (decode, uniform)
     const obte_bf16* prefix_cache = nullptr; int64_t P = 0, T_pre = 0, n_prefix = 0;
@@ -514,23 +514,16 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
     const float scale = 8.0f / (float)C;  // model.py:119
     if (at.n_new > 0) {   // n_new positions per row join the cache (the rows form rotates them as it stores), then each attends over those up to its own
         const int64_t q_ld = 3 * (int64_t)C;
-        if (at.kv8 && !at.pos_rows) TRY(obte_kv8_cache_store(w.qkv, d->B, 1, H, hs, at.kv_cache, at.T_max, at.pos, s));   // (kv8: decode only)
-        else if (at.kv8) TRY(obte_kv8_rope_store_rows_as(at.who, w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.T_max, s));
-        else if (!at.pos_rows) TRY(obte_kv_cache_store(w.qkv, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, at.pos, s));
-        else if (at.decode) TRY(obte_kv_cache_rope_store_rows(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.T_max, s));
-        else TRY(obte_kv_cache_rope_store_chunk(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, s));
-        if (at.kv8)             // uniform (pos_rows null: every row over pos + 1 keys) or row b over its own pos_rows[b] + 1
-            TRY(obte_attn_decode_kv8_off(at.who, w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos + 1, at.pos_rows, 1, H, hs, scale, 0, at.dec_ws,
-                                         at.dec_ws_bytes, s));
-        else if (at.prefix_cache)   // the group's prefix once per 32 rows, then the row's own slots 0 .. pos
+        const char* who = at.kv8 || at.pos_rows ? at.who : "obte_attn_decode";   // (the uniform bf16 step's attention refuses under its own name)
+        TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, s));
+        if (at.prefix_cache)    // the group's prefix once per 32 rows, then the row's own slots 0 .. pos
             TRY(obte_attn_decode_shared(w.qkv, q_ld, at.prefix_cache, at.P, at.T_pre, at.n_prefix, at.kv_cache, d->B / at.P, at.T_max, at.pos + 1, w.att, nullptr, H, hs,
                                         scale, 0, 0, at.dec_ws, at.dec_ws_bytes, s));
         else if (!at.decode)
             TRY(obte_attn_extend(w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.n_new, at.pos, at.pos_rows, H, hs, scale, 0, at.dec_ws, at.dec_ws_bytes, s));
-        else if (at.pos_rows)   // row b over its own pos_rows[b] + 1 keys
-            TRY(obte_attn_decode_rows_off("obte_block_decode_rows", w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos_rows, 1, at.pos + 1, H, hs, scale, 0,
-                                          at.dec_ws, at.dec_ws_bytes, s));
-        else TRY(obte_attn_decode(w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos + 1, H, hs, scale, 0, at.dec_ws, at.dec_ws_bytes, s));
+        else                    // uniform (pos_rows null: every row over pos + 1 keys) or row b over its own pos_rows[b] + 1
+            TRY(obte_attn_decode_on(at.kv8, who, w.qkv, q_ld, at.kv_cache, w.att, nullptr, d->B, at.T_max, at.pos + 1, at.pos_rows, 1, H, hs, scale, 0, at.dec_ws,
+                                    at.dec_ws_bytes, s));
     } else {
         obte_attn_fwd_args af = {};
         af.qkv = w.qkv; af.o = w.att; af.lse = w.lse; af.key_ranges = d->key_ranges; af.mask = d->mask;
@@ -538,8 +531,7 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
         af.B = d->B; af.T = d->T; af.n_head = H; af.head_dim = hs; af.scale = scale;
         af.dropout_p = d->dropout_p; af.dropout_seed = d->dropout_seed;
         TRY(obte_attn_fwd(&af, s));
-        if (at.kv_cache && at.kv8) TRY(obte_kv8_cache_store(w.qkv, d->B, d->T, H, hs, at.kv_cache, at.T_max, 0, s));
-        else if (at.kv_cache) TRY(obte_kv_cache_store(w.qkv, d->B, d->T, H, hs, at.kv_cache, at.T_max, 0, s));   // (c_fc's activation overwrites qkv below)
+        if (at.kv_cache) TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, nullptr, nullptr, nullptr, 0, d->B, d->T, H, hs, at.kv_cache, at.T_max, s));   // (c_fc's activation overwrites qkv below)
     }
     TRY(run(plus_residual(xWt(w.att, d->proj_w, w.x1, M, C, C), x, d->dropout_p, d->dropout_seed, SITE_RESID), s));
     TRY(obte_layernorm_fwd(w.x1, d->ln2_w, w.h2, w.mean, w.rstd, M, C, 1e-5f, s));

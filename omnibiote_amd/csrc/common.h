@@ -87,19 +87,19 @@ int obte_dropout_rows_bf16(const obte_bf16* in, const obte_bf16* aux, obte_bf16*
 int obte_rope_cols_bf16(obte_bf16* x, int64_t ld, int32_t ncols, const float* cos_t, const float* sin_t, int64_t rows, int64_t T, const int32_t* pos,
                         int32_t head_dim, obte_stream s);
 int obte_rows_add_bf16(const obte_bf16* src, const int64_t* rows, obte_bf16* dst, int64_t n_rows, int32_t cols, obte_stream s);
-// obte_attn_decode_rows with row b's key count read as n_keys[b] + key_off (csrc/block.cpp hands a step's positions and 1); who: the
-// entry point named in an error
-int obte_attn_decode_rows_off(const char* who, const obte_bf16* q, int64_t q_ld, const obte_bf16* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max,
-                              const int32_t* n_keys, int32_t key_off, int64_t max_keys, int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws,
-                              int64_t ws_bytes, obte_stream s);
 
-// ---- one query per (batch, head) against a key/value cache: what attention_decode.hip (bf16 cache) and attention_kv8.hip (e4m3 cache) share
-constexpr int DEC_WAVES = 4;     // waves per workgroup
-constexpr int DEC_UNROLL = 4;    // keys per lane group whose loads are in flight together (bf16 cache: K and V, 8 loads of 16 bytes per lane)
-constexpr int DEC_CHUNK = 64;    // split boundaries are multiples of this many keys (16 KiB of K at head size 128 in bf16)
-constexpr int DEC_PAD = 4;       // a partial is hs + 4 floats (acc[hs], m, l, 2 unused): 16-byte aligned rows
-// attn_decode_combine_kernel<head_dim> on BH rows of `splits` partials in ws (attention_decode.hip)
-void obte_attn_decode_combine(int head_dim, int BH, int splits, const float* ws, __bf16* o, float* lse, hipStream_t st);
+// ---- one query per (batch, head) against a key/value cache in bf16 or (e4m3) in OCP e4m3 (attention_decode.hip): what csrc/block.cpp's cached step calls
+// obte_attn_decode (rows_n null), obte_attn_decode_rows or obte_attn_decode_kv8 with row b's key count read as rows_n[b] + key_off (the
+// block hands a step's positions and 1: no launch to form pos + 1); who: the entry point named in an error
+int obte_attn_decode_on(bool e4m3, const char* who, const obte_bf16* q, int64_t q_ld, const void* cache, obte_bf16* o, float* lse, int64_t B, int64_t T_max,
+                        int64_t n_keys, const int32_t* rows_n, int32_t key_off, int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws,
+                        int64_t ws_bytes, obte_stream s);
+// the store entry point for n positions per row from `pos` on (pos_rows null; the rows rotated already) or from pos_rows[b] on (rotated
+// here; pos: their bound; e4m3: n = 1); who: named in an error where the entry point's own name is not (the e4m3 rows form)
+int obte_kv_store_on(bool e4m3, const char* who, obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos_rows, int64_t pos, int64_t B, int64_t n,
+                     int32_t n_head, int32_t head_dim, void* cache, int64_t T_max, obte_stream s);
+constexpr int DEC_PAD = 4;       // a partial of the attention is hs + 4 floats (acc[hs], m, l, 2 unused): 16-byte aligned rows
+
 // ---- a prefix cache shared by groups of rows (attention_shared.hip, include/omnibiote_hip_shared.h): the two partial-only launches
 // attn_decode_kernel<.., PARTIAL> (attention_decode.hip): BH rows over the keys [0, n_keys) of their own cache row, `splits` partials each
 void obte_attn_decode_partials(int head_dim, int BH, int H, int splits, const __bf16* q, int64_t q_ld, const __bf16* cache, int64_t T_max, int n_keys, float qscale,
@@ -109,13 +109,6 @@ void obte_attn_decode_partials(int head_dim, int BH, int H, int splits, const __
 void obte_attn_extend_group_partials(int head_dim, int64_t P, int G, int H, int splits, const __bf16* q, int64_t q_ld, const __bf16* cache, int64_t T_pre, int n_prefix,
                                      float qscale, float* part, hipStream_t st);
 static inline int64_t obte_ext_part_floats(int head_dim) { return (int64_t)(head_dim / 2 + 2) * 64; }
-// the e4m3 cache's launchers with the entry point named in an error and row b's count read as n_keys_rows[b] + key_off (attention_kv8.hip;
-// csrc/block.cpp hands a step's positions and 1)
-int obte_kv8_rope_store_rows_as(const char* who, obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos, int64_t max_pos, int64_t B,
-                                int32_t n_head, int32_t head_dim, void* cache8, int64_t T_max, obte_stream s);
-int obte_attn_decode_kv8_off(const char* who, const obte_bf16* q, int64_t q_ld, const void* cache8, obte_bf16* o, float* lse, int64_t B, int64_t T_max,
-                             int64_t n_keys, const int32_t* n_keys_rows, int32_t key_off, int32_t n_head, int32_t head_dim, float scale, int32_t splits, void* ws,
-                             int64_t ws_bytes, obte_stream s);
 
 // device status word (lib.cpp): pinned host memory kernels OR failure bits into; null if it could not be allocated
 int32_t* obte_status_word();

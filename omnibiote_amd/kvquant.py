@@ -1,4 +1,4 @@
-"""The e4m3 key/value cache's format in plain torch (include/omnibiote_hip_kv8.h): the tests' yardstick for csrc/attention_kv8.hip, as
+"""The e4m3 key/value cache's format in plain torch (include/omnibiote_hip_kv8.h): the tests' yardstick for csrc/attention_decode.hip's e4m3 format, as
 sampling.py is for the sampler.  Nothing here runs on a generation path.
 
 A head vector x of hs bf16 values is stored as hs codes and one fp32 scale:
