@@ -228,6 +228,12 @@ SYMBOLS_SHARED = {
                                            C.c_int64, C.c_void_p, C.c_int64, c_stream]),
 }
 
+# the generation loop's state on the device (include/omnibiote_hip_loop.h): a table of its own as well
+SYMBOLS_LOOP = {
+    "obte_gen_advance": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_void_p, C.c_int64, C.c_int32, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -257,7 +263,7 @@ def lib():
                 raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
             for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
                                             + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
-                                            + list(SYMBOLS_SHARED.items())):
+                                            + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

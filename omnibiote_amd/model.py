@@ -875,7 +875,9 @@ class CachePositions:
     ``lengths`` the rows stand at different positions: ``positions`` is then an int32 (B,) device tensor, row b's next position (the
     kernels read it there; a negative value parks a finished row: it stores nothing and attends to nothing), ``pos`` the host's upper
     bound on it — the longest row — and ``min_pos`` a host-side lower bound on the shortest row that is not parked (0: unknown; only
-    ``rewind`` reads it).  ``reset``, ``advance``, ``park``, ``rewind`` and ``rewind_rows`` are the only writers of the three."""
+    ``rewind`` reads it).  ``reset``, ``advance``, ``park``, ``rewind`` and ``rewind_rows`` are the only writers of the three — and, for a
+    ``DecodeLoop``, ``advanced_on_device``: there the loop's kernel (obte_gen_advance) is the writer of the device tensor, in place, and
+    this class moves the host bounds alone."""
 
     dtype = "bf16"   # what the buffers behind the positions hold (KVCache sets it): no operation here touches a cache byte
 
@@ -906,6 +908,15 @@ class CachePositions:
         if self.positions is not None:
             self.positions = torch.add(self.positions, self.positions >= 0, alpha=n)   # int32 + n * bool: int32; parked rows (< 0) stay
             self.min_pos += n
+
+    def advanced_on_device(self, n):
+        """``n`` more positions were filled, and ``positions`` has been moved (and finished rows parked) in place by a kernel on the
+        stream: only the host bounds follow here.  ``positions`` stays the same tensor — launches recorded against its address, a
+        captured graph's among them, keep reading the live state.  Rows mode only."""
+        if self.positions is None:
+            raise ValueError("KVCache.advanced_on_device: the cache is in uniform mode (no positions tensor for a kernel to move)")
+        self.pos += n
+        self.min_pos += n
 
     def park(self, done):
         """Park the rows where ``done`` (bool (B,)) holds: they store nothing and read nothing from here on.  Rows mode only."""
@@ -1064,6 +1075,182 @@ class SharedPrefixCache(CachePositions):
         self.pos -= n
 
 
+class DecodeLoop:
+    """The token loop of ``generate`` with its state on the device: ``model`` stepping a prefilled ``KVCache`` (bf16 or fp8) for up to
+    ``max_steps`` tokens per row with no value passing through the host, so that one step is the same sequence of launches with the
+    same arguments every time — and, with ``capture=True``, one replay of a captured graph.
+
+    The loop owns buffers whose addresses never change: ``logits`` (B, V) bf16, ``sampled`` and ``token`` (B,) int64, ``u`` (B,) fp32,
+    ``x`` (B, C) bf16, ``count`` and ``n_new`` (B,) int32, ``out`` (B, max_steps) int64; the rows' positions are ``cache.positions``,
+    moved in place (a cache in uniform mode is put into rows mode here, every row at ``cache.pos``).  One step — the body — is: every
+    block's rows-form cached step on ``x`` at ``positions`` under the FIXED bound ``cache.max_len - 1``, ``ln_f``, the readout into
+    ``logits``, ``ops.sample_logits`` into ``sampled``, and ``ops.gen_advance``, which records the tokens, parks the rows that drew
+    ``eos_token``, fetches the next uniforms and embeds the next tokens (include/omnibiote_hip_loop.h): one launch fewer than a
+    ``decode_step`` plus the sampler, the embedding's, and none of the host's small tensor operations.
+
+    ``uniforms``: (steps, B) float32 on the device, row i the draws of the i-th token (as ``generate(sampler="device")`` draws them; steps
+    beyond the last row reuse it); None, ``temperature == 0`` or ``top_k == 1``: greedy.
+
+    ``start(prefill_logits)`` draws the first token from the prefill's logits (no cache position is consumed), ``run(k)`` takes k steps,
+    ``result()`` returns the tokens.  The loop can be run again on its cache behind another prompt: ``loop.prefill(idx, lengths)`` is
+    ``model.prefill`` that keeps the rows' positions in the loop's own tensor.  ``start`` raises when ``cache.positions`` is no longer that
+    tensor — an eager ``decode_step``, ``extend``, ``rewind`` or a plain ``model.prefill`` replaces it.
+
+    The fixed bound: a row's attention launch has the split count of ``max_len`` keys whatever the row's position, where ``decode_step``
+    uses the count of ``cache.pos + 1`` keys.  Row b's attention is, bit for bit, the uniform call's at the same split count
+    (include/omnibiote_hip_rows.h), so the loop's logits equal ``decode_step``'s to the accuracy of another summation order — within the
+    generation tests' bounds — not bit for bit.  ``capture=True`` and ``capture=False`` run the same launches and agree bit for bit.
+
+    ``capture=True``: the body runs once eagerly with every row parked — it touches no cache byte by the rows convention, and takes the
+    kernels' one-time set-up out of the capture; the loop's state is restored — and is then recorded into a ``torch.cuda.CUDAGraph``,
+    one linear stream.  It needs B <= the weight-streaming product's row limit (``obte_small_m_max``): above it the products take
+    paths that have not been vetted for capture, and the constructor raises ValueError (the eager body takes any B).  Weights, cache
+    buffers and tables are captured BY ADDRESS: in-place updates of the parameters are seen by the next replay, but ``model.to(...)``,
+    a reloaded parameter or a new cache leave the graph reading freed memory — build a new loop."""
+
+    def __init__(self, model, cache, *, max_steps, temperature=1.0, top_k=None, top_p=None, uniforms=None, eos_token=None, capture=False):
+        if isinstance(cache, SharedPrefixCache):
+            raise ValueError("DecodeLoop: a SharedPrefixCache steps at a host suffix position, which changes every step: the device loop needs a KVCache")
+        model._check_generation("DecodeLoop", cache.batch, cache)
+        if int(max_steps) < 1:
+            raise ValueError(f"DecodeLoop: max_steps must be at least 1, got {max_steps}")
+        if temperature < 0:
+            raise ValueError(f"DecodeLoop: temperature must not be negative, got {temperature}")
+        if top_k is not None and top_k < 1:
+            raise ValueError(f"DecodeLoop: top_k must be at least 1, got {top_k}")
+        _check_top_p("DecodeLoop", top_p)
+        if cache.pos == 0:
+            raise ValueError("DecodeLoop: the cache is empty: prefill a prompt first")
+        cfg = model.config
+        b = cache.batch
+        wte = model.transformer.wte.weight
+        _require_hip(wte, "DecodeLoop")
+        dev = wte.device
+        greedy = uniforms is None or temperature == 0 or top_k == 1
+        if not greedy and (uniforms.dim() != 2 or uniforms.shape[0] < 1 or uniforms.shape[1] != b or uniforms.dtype != torch.float32):
+            raise ValueError(f"DecodeLoop: uniforms must be (steps >= 1, {b}) float32, got {tuple(uniforms.shape)} {uniforms.dtype}")
+        if capture and b > L.lib().obte_small_m_max():
+            raise ValueError(f"DecodeLoop: capture needs a batch of at most {L.lib().obte_small_m_max()} rows (the weight-streaming product's "
+                             f"limit), got {b}; capture=False takes any batch")
+        self.model, self.cache, self.max_steps, self.eos_token = model, cache, int(max_steps), eos_token
+        self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
+        self.uniforms = None if greedy else uniforms.contiguous()
+        if cache.positions is None:
+            cache.reset(cache.pos, positions=torch.full((b,), cache.pos, dtype=torch.int32, device=dev), min_pos=cache.pos)
+        self.positions = cache.positions
+        self.logits = torch.zeros((b, cfg.vocab_size), dtype=torch.bfloat16, device=dev)
+        self.sampled = torch.zeros(b, dtype=torch.int64, device=dev)
+        self.token = torch.zeros(b, dtype=torch.int64, device=dev)
+        self.u = torch.zeros(b, dtype=torch.float32, device=dev)
+        self.x = torch.zeros((b, cfg.n_embd), dtype=torch.bfloat16, device=dev)
+        self.count = torch.zeros(b, dtype=torch.int32, device=dev)
+        self.n_new = torch.zeros(b, dtype=torch.int32, device=dev)
+        self.out = torch.zeros((b, self.max_steps), dtype=torch.int64, device=dev)
+        self.steps = 0          # body runs since start
+        self.started = False
+        self.graph = None
+        if capture:
+            self._capture()
+
+    def _sample_and_advance(self, commit):
+        ops.sample_logits(self.logits, self.u if self.uniforms is not None else None, self.temperature, self.top_k, self.top_p, out=self.sampled)
+        ops.gen_advance(self.sampled, self.positions, self.count, self.out, self.n_new, self.token, self.model.transformer.wte.weight, self.x,
+                        us=self.uniforms, u=self.u if self.uniforms is not None else None, eos=self.eos_token, commit=commit)
+
+    @torch.no_grad()
+    def _body(self):
+        """one step; no host-dependent value in it: every argument is an address or a constant of the loop"""
+        m, cache, x = self.model, self.cache, self.x
+        bound = cache.max_len - 1
+        for block, kv in zip(m.transformer.h, cache.layers):
+            if cache.dtype == "fp8":
+                ops.block_decode_kv8(x, m._block_params(block), block.attn.rope(), m.config.n_head, kv, cache.max_len, bound, self.positions,
+                                     ws=cache.decode_ws, out=x)
+            else:
+                ops.block_decode_rows(x, m._block_params(block), block.attn.rope(), m.config.n_head, kv, cache.max_len, self.positions, bound,
+                                      ws=cache.decode_ws, out=x)
+        m._readout_rows(m.transformer.ln_f(x), out=self.logits)
+        self._sample_and_advance(1)
+
+    def _capture(self):
+        state = [self.positions, self.count, self.n_new, self.token, self.u]
+        saved = [t.clone() for t in state]
+        self.positions.fill_(-1)                                        # every row parked: the warm-up step stores and reads no cache byte
+        self._body()
+        for t, was in zip(state, saved):
+            t.copy_(was)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._body()
+
+    @torch.no_grad()
+    def prefill(self, idx, lengths=None):
+        """``model.prefill(idx, cache, lengths)`` for a loop that is to run again on its cache: a prefill leaves new positions behind (a new
+        tensor, or uniform mode), and this writes them into the loop's own tensor and hands that back to the cache.  Returns the logits
+        for ``start``."""
+        logits = self.model.prefill(idx, self.cache, lengths=lengths)
+        c = self.cache
+        if c.positions is None:
+            self.positions.fill_(c.pos)
+            c.reset(c.pos, self.positions, c.pos)
+        else:
+            self.positions.copy_(c.positions)
+            c.reset(c.pos, self.positions, c.min_pos)
+        self.started = False
+        return logits
+
+    @torch.no_grad()
+    def start(self, prefill_logits):
+        """The first token of every row, drawn from the prefill's logits (B, V): recorded, and embedded for the first step; no cache
+        position is consumed.  Resets the loop's counters, so a loop may be started again behind another prefill."""
+        if self.cache.positions is not self.positions:
+            raise ValueError("DecodeLoop.start: cache.positions is no longer the tensor this loop was built on (an eager decode_step, extend, "
+                             "rewind or model.prefill replaced it): prefill through loop.prefill, or build a new loop")
+        if prefill_logits.shape != self.logits.shape:
+            raise ValueError(f"DecodeLoop.start: logits must be {tuple(self.logits.shape)}, got {tuple(prefill_logits.shape)}")
+        self.logits.copy_(prefill_logits)
+        for t in (self.count, self.n_new, self.token, self.out):
+            t.zero_()
+        if self.uniforms is not None:
+            self.u.copy_(self.uniforms[0])
+        self._sample_and_advance(0)
+        self.steps, self.started = 0, True
+
+    @torch.no_grad()
+    def run(self, k, poll=16):
+        """``k`` steps (fewer with ``eos_token`` once every row is parked: the positions are read on the host once every ``poll`` steps — the
+        loop's only synchronisation, none without ``eos_token``).  Returns the steps taken."""
+        if not self.started:
+            raise ValueError("DecodeLoop.run: start the loop first")
+        if self.cache.positions is not self.positions:
+            raise ValueError("DecodeLoop.run: cache.positions is no longer the tensor this loop was built on: build a new loop")
+        k, poll = int(k), int(poll)
+        if k < 0 or poll < 1:
+            raise ValueError(f"DecodeLoop.run: k must not be negative and poll at least 1, got {k} and {poll}")
+        if 1 + self.steps + k > self.max_steps:
+            raise ValueError(f"DecodeLoop.run: {k} more steps behind {self.steps} exceed max_steps = {self.max_steps} (the first token included)")
+        self.cache.require_room("DecodeLoop.run", k, detail=True)
+        for i in range(k):
+            if self.graph is not None:
+                self.graph.replay()
+            else:
+                self._body()
+            self.cache.advanced_on_device(1)
+            self.steps += 1
+            if self.eos_token is not None and (i + 1) % poll == 0 and i + 1 < k and not bool((self.positions >= 0).any()):
+                return i + 1
+        return k
+
+    def result(self):
+        """(tokens (B, S) int64, n_new (B,) int32): row b's first n_new[b] columns are its tokens, the rest means nothing.  S is the
+        number of tokens drawn, 1 + the steps run — or, once every row has finished, the longest row's count (with ``eos_token`` this
+        reads the positions on the host)."""
+        width = 1 + self.steps
+        if self.eos_token is not None and not bool((self.positions >= 0).any()):
+            width = int(self.n_new.max())
+        return self.out[:, :width].clone(), self.n_new.clone()
+
+
 class OmniBioTA(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -1180,13 +1367,14 @@ class OmniBioTA(nn.Module):
                                       "position at a time (prefill, decode_step, generate(num_samples=)); several new positions per row in one "
                                       "call need a KVCache")
 
-    def _readout_rows(self, x):
+    def _readout_rows(self, x, out=None):
         """The readout of a generation step's (B, C) rows: at most ops' small_m_max of them, bf16 on the GPU, through the
-        weight-streaming product with MuReadout.forward's alpha; anything else through the module."""
+        weight-streaming product with MuReadout.forward's alpha; anything else through the module.  ``out``: a (B, vocab) buffer of the
+        caller's that takes the logits (a ``DecodeLoop``'s, whose address must not change)."""
         w = self.lm_head.weight
         if x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.shape[0] <= L.lib().obte_small_m_max():
-            return ops.linear_small_m(x, w, alpha=float(self.lm_head.output_mult) / float(self.lm_head.width_mult()))
-        return self.lm_head(x)
+            return ops.linear_small_m(x, w, alpha=float(self.lm_head.output_mult) / float(self.lm_head.width_mult()), out=out)
+        return self.lm_head(x) if out is None else out.copy_(self.lm_head(x))
 
     @torch.no_grad()
     def prefill(self, idx, cache, lengths=None, chunk=None):
@@ -1382,7 +1570,7 @@ class OmniBioTA(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None, lengths=None, pad_token=None, top_p=None,
-                 sampler="torch", kv_dtype="bf16", num_samples=None):
+                 sampler="torch", kv_dtype="bf16", num_samples=None, loop=None):
         """nanoGPT's generate(): ``idx`` (B, T0) int64 continued by up to ``max_new_tokens`` sampled tokens (``sample_next``); returns
         (B, T0 + n) int64.  The prompt runs once (``prefill``), every new token costs one ``decode_step``.  Where nanoGPT crops the
         context to block_size, this raises: T0 + max_new_tokens must fit.  ``eos_token``: a row that has produced it keeps producing
@@ -1405,9 +1593,21 @@ class OmniBioTA(nn.Module):
         (P * G, T0 + n) int64 with row p * G + g prompt p followed by its g-th sample — what ``generate(idx.repeat_interleave(G, 0), ...)``
         returns, drawn the same way (the device sampler's uniforms are ``torch.rand((max_new_tokens, P * G), generator=generator)``), but
         on a ``SharedPrefixCache``: the prompt is prefilled and stored once per prompt and read once per 32 samples.  Prompts of one
-        length and a bf16 cache only: with ``lengths`` or ``kv_dtype="fp8"`` it raises ValueError."""
+        length and a bf16 cache only: with ``lengths`` or ``kv_dtype="fp8"`` it raises ValueError.
+
+        ``loop``: None (everything above), "device" or "graph": the token loop runs as a ``DecodeLoop`` — its state lives on the device,
+        finished rows are parked there, and the host looks at the rows once every 16 tokens (never without ``eos_token``); "graph" also
+        replays every step as one captured graph (B <= 64).  Same arguments, same shape of result, the device sampler's rule and uniforms;
+        the tokens are those of ``loop=None, sampler="device"`` except where two logits lie closer than the attention's summation order
+        resolves (``DecodeLoop``: the fixed bound).  Needs ``sampler="device"``; not with ``num_samples``: both raise ValueError."""
         if sampler not in ("torch", "device"):
             raise ValueError(f"OmniBioTA.generate: sampler must be 'torch' or 'device', got {sampler!r}")
+        if loop not in (None, "device", "graph"):
+            raise ValueError(f"OmniBioTA.generate: loop must be None, 'device' or 'graph', got {loop!r}")
+        if loop is not None and sampler != "device":
+            raise ValueError("OmniBioTA.generate: loop= draws with the device sampler (sampler='device'); torch.multinomial's stream is not part of it")
+        if loop is not None and num_samples is not None:
+            raise ValueError("OmniBioTA.generate: loop= does not run on the shared-prefix cache of num_samples")
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"OmniBioTA.generate: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         if num_samples is not None:
@@ -1424,7 +1624,7 @@ class OmniBioTA(nn.Module):
             raise ValueError("OmniBioTA.generate: the prompt is empty")
         if lengths is not None:
             return self._generate_ragged(idx, _check_lengths("generate", lengths, b, t0), max_new_tokens, temperature, top_k, generator, eos_token,
-                                         pad_token, top_p, sampler, kv_dtype)
+                                         pad_token, top_p, sampler, kv_dtype, loop)
         if max_new_tokens < 0 or t0 + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {t0} prompt tokens + {max_new_tokens} new ones exceed block_size = {self.config.block_size}")
         if num_samples is None:
@@ -1438,6 +1638,12 @@ class OmniBioTA(nn.Module):
         out = [rows]
         logits = self.prefill(idx, cache)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
+        if loop is not None:
+            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop)
+            if eos_token is not None:                                   # a finished row keeps producing EOS
+                live = torch.arange(tokens.shape[1], device=idx.device).view(1, -1) < n_new.view(-1, 1)
+                tokens = torch.where(live, tokens, torch.full_like(tokens, eos_token))
+            return torch.cat([rows, tokens], dim=1)
         done = None
         for i in range(max_new_tokens):
             nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i])
@@ -1451,7 +1657,16 @@ class OmniBioTA(nn.Module):
             logits = self.decode_step(nxt, cache)
         return torch.cat(out, dim=1)
 
-    def _generate_ragged(self, idx, lens, max_new_tokens, temperature, top_k, generator, eos_token, pad_token, top_p=None, sampler="torch", kv_dtype="bf16"):
+    def _device_loop(self, cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop):
+        """``generate``'s token loop as a ``DecodeLoop`` behind the prefill that gave ``logits``: (tokens (B, S), n_new (B,))"""
+        run = DecodeLoop(self, cache, max_steps=max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
+                         uniforms=us if isinstance(us, torch.Tensor) else None, eos_token=eos_token, capture=loop == "graph")
+        run.start(logits)
+        run.run(max_new_tokens - 1)
+        return run.result()
+
+    def _generate_ragged(self, idx, lens, max_new_tokens, temperature, top_k, generator, eos_token, pad_token, top_p=None, sampler="torch", kv_dtype="bf16",
+                         loop=None):
         longest = max(lens)
         if max_new_tokens < 0 or longest + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {longest} prompt tokens (the longest row) + {max_new_tokens} new ones exceed "
@@ -1465,6 +1680,9 @@ class OmniBioTA(nn.Module):
         cache = KVCache(self, b, longest + max_new_tokens, dtype=kv_dtype)
         logits = self.prefill(idx, cache, lengths=lens)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
+        if loop is not None:
+            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop)
+            return ragged_output(idx, lens, tokens, torch.arange(tokens.shape[1], device=idx.device).view(1, -1) < n_new.view(-1, 1), pad)
         tokens, valid = [], []
         done = torch.zeros(b, dtype=torch.bool, device=idx.device)
         for i in range(max_new_tokens):

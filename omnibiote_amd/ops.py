@@ -262,12 +262,12 @@ def small_m_max(m: int):
         L.lib().obte_small_m_max_set(prev)
 
 
-def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, return_kept=False):
+def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, return_kept=False, out=None):
     """The next token of every row of ``logits`` (B, V) bf16, V <= 65536, in one launch (obte_sample_logits_bf16; the rule:
     include/omnibiote_hip_sample.h, restated in plain torch by sampling.sample_reference): temperature, top-k, top-p, softmax and the
     draw against ``u`` (B,) float32 uniforms.  ``u is None``, ``temperature == 0`` or ``top_k == 1``: the lowest index of the row maximum.
-    logits may be a row-strided view: last-dimension stride 1, row stride a multiple of 8.  Returns (B,) int64, with
-    ``return_kept`` also the size of every row's kept set, (B,) int32."""
+    logits may be a row-strided view: last-dimension stride 1, row stride a multiple of 8.  Returns (B,) int64 (``out`` when given: a
+    caller's buffer that keeps its address from step to step), with ``return_kept`` also the size of every row's kept set, (B,) int32."""
     _need(logits, "logits", contiguous=False)
     if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
         raise ValueError(f"sample_logits: logits must be (B, V) with B, V >= 1, got {tuple(logits.shape)}")
@@ -281,11 +281,44 @@ def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, retur
             raise ValueError(f"sample_logits: u must be ({B},), got {tuple(u.shape)}")
     if top_k is not None and top_k < 1:
         raise ValueError(f"sample_logits: top_k must be at least 1, got {top_k}")
-    token = torch.empty(B, dtype=torch.int64, device=logits.device)
+    token = torch.empty(B, dtype=torch.int64, device=logits.device) if out is None else out
+    if out is not None:
+        _need(out, "out", torch.int64)
+        if out.shape != (B,):
+            raise ValueError(f"sample_logits: out must be ({B},), got {tuple(out.shape)}")
     kept = torch.empty(B, dtype=torch.int32, device=logits.device) if return_kept else None
     L.check(L.lib().obte_sample_logits_bf16(_ptr(logits), ld, B, V, _ptr(u), float(temperature), 0 if top_k is None else min(int(top_k), 2 ** 31 - 1),
                                             1.0 if top_p is None else float(top_p), _ptr(token), _ptr(kept), _stream()), "obte_sample_logits_bf16")
     return (token, kept) if return_kept else token
+
+
+def gen_advance(sampled, pos, count, out, n_new, token, wte, x, us=None, u=None, eos=None, commit=1):
+    """A step's sampled tokens into the next step's inputs, in one launch and in place (obte_gen_advance; the rule:
+    include/omnibiote_hip_loop.h, restated in plain torch by sampling.advance_reference).  ``sampled`` (B,) int64 is read; ``pos``, ``count``,
+    ``n_new`` (B,) int32, ``out`` (B, S) int64, ``token`` (B,) int64, ``x`` (B, C) bf16 and, with the call's uniforms ``us`` (steps, B)
+    float32, ``u`` (B,) float32 are updated: a running row (pos >= 0) moves on by ``commit`` (0 or 1), records its token in column
+    count[b] of out while that column exists, parks itself on ``eos`` (None: no such token); every row's x becomes the embedding of
+    its token and its u the next step's row of us.  Every argument keeps its address: the call is the same for every step."""
+    _need(sampled, "sampled", torch.int64); _need(token, "token", torch.int64); _need(out, "out", torch.int64)
+    _need(wte, "wte"); _need(x, "x")
+    if sampled.dim() != 1 or sampled.shape[0] < 1:
+        raise ValueError(f"gen_advance: sampled must be (B,) with B >= 1, got {tuple(sampled.shape)}")
+    B = sampled.shape[0]
+    for t, name in ((pos, "pos"), (count, "count"), (n_new, "n_new")):
+        _need_rows(t, name, B)
+    if token.shape != (B,) or out.dim() != 2 or out.shape[0] != B or out.shape[1] < 1:
+        raise ValueError(f"gen_advance: token must be ({B},) and out ({B}, S >= 1), got {tuple(token.shape)} and {tuple(out.shape)}")
+    if wte.dim() != 2 or x.shape != (B, wte.shape[1]):
+        raise ValueError(f"gen_advance: wte must be (vocab, C) and x ({B}, C), got {tuple(wte.shape)} and {tuple(x.shape)}")
+    if commit not in (0, 1):
+        raise ValueError(f"gen_advance: commit must be 0 or 1, got {commit!r}")
+    if us is not None:
+        _need(us, "us", torch.float32); _need(u, "u", torch.float32)
+        if us.dim() != 2 or us.shape[0] < 1 or us.shape[1] != B or u.shape != (B,):
+            raise ValueError(f"gen_advance: us must be (steps >= 1, {B}) and u ({B},), got {tuple(us.shape)} and {tuple(u.shape)}")
+    L.check(L.lib().obte_gen_advance(_ptr(sampled), _ptr(pos), _ptr(count), _ptr(out), out.shape[1], _ptr(n_new), _ptr(token), _ptr(wte), wte.shape[0],
+                                     wte.shape[1], _ptr(x), _ptr(us), 0 if us is None else us.shape[0], _ptr(u) if us is not None else None,
+                                     -1 if eos is None else int(eos), int(commit), B, _stream()), "obte_gen_advance")
 
 
 def spec_verify(p, q, draft, u_accept=None, u_draw=None, temperature=1.0, top_k=None, top_p=None):

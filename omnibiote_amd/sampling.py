@@ -173,3 +173,35 @@ def verify_reference(p, q, draft, u_accept=None, u_draw=None, temperature=1.0, t
     token, cdf = torch.where(a == k, bonus[0], token), torch.where((a == k).unsqueeze(1), bonus[2], cdf)
     out = a, token, cdf
     return tuple(t[0] for t in out) if one else out
+
+
+def advance_reference(sampled, pos, count, out, n_new, token, wte, us=None, eos=None, commit=1):
+    """The generation loop's per-row bookkeeping in plain torch on any device: what obte_gen_advance (include/omnibiote_hip_loop.h)
+    implements.  Nothing is changed in place; returns the new ``(pos, count, out, n_new, token, x, u)``.  ``sampled`` (B,) int64 are the
+    tokens drawn from the step's logits, ``pos`` (B,) int32 every row's next cache position (negative: parked), ``count`` (B,) int32 the
+    steps the row has seen, ``out`` (B, S) int64 and ``n_new`` (B,) int32 what it has emitted, ``token`` (B,) int64 its last emitted token,
+    ``wte`` (vocab, C), ``us`` (steps, B) the uniforms of a whole call or None.  For row b:
+
+      running   pos[b] >= 0.  With ``commit`` (0 or 1) a running row moves on: p = pos[b] + commit — the step that just ran stored at pos[b].
+      record    a running row with 0 <= s = count[b] < S:  out[b, s] = sampled[b], n_new[b] += 1, token[b] = sampled[b], and if that is
+                ``eos`` (None or negative: no such token) the row is parked, p = -1.  Otherwise out, n_new and token stay as they are.
+      always    pos[b] = p, count[b] = s + 1, x[b] = wte[clamp(token[b], 0, vocab - 1)] from the token this call leaves, and with ``us``
+                u[b] = us[clamp(s + 1, 0, steps - 1), b], the next step's uniforms (u is None without ``us``).
+    int32 arithmetic wraps as the kernel's does."""
+    if commit not in (0, 1):
+        raise ValueError(f"advance_reference: commit must be 0 or 1, got {commit!r}")
+    b, width = out.shape
+    rows = torch.arange(b, device=out.device)
+    running = pos >= 0
+    p = torch.where(running, pos + commit, pos) if commit else pos.clone()
+    record = running & (count >= 0) & (count.long() < width)
+    col = count.long().clamp(0, width - 1)
+    new_out = out.clone()
+    new_out[rows, col] = torch.where(record, sampled, out[rows, col])
+    new_n = n_new + record.to(n_new.dtype)
+    new_token = torch.where(record, sampled, token)
+    if eos is not None and eos >= 0:
+        p = torch.where(record & (sampled == eos), torch.full_like(p, -1), p)
+    x = wte[new_token.clamp(0, wte.shape[0] - 1)]
+    u = None if us is None else us[(count.long() + 1).clamp(0, us.shape[0] - 1), rows]
+    return p, count + 1, new_out, new_n, new_token, x, u

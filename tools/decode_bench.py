@@ -49,6 +49,15 @@ each walking its own set of per-layer caches, with the bytes each must read by t
 per window; and the bytes of both cache sets.  One JSON line per (G, n_suffix).
 
     python tools/decode_bench.py --shared [--rounds 5] [--steps 300]
+
+--graph: the device-resident token loop (model.DecodeLoop, include/omnibiote_hip_loop.h) at B x ctx in {1, 8, 64} x 2048 unless --batches /
+--contexts say otherwise, with sampling (T = 0.8, top_k = 200, top_p = 0.9) and an eos_token that no row draws.  Contenders alternate in one
+process over the same windows and rounds, every window walking the same cache positions up to ctx - 2: today's loop (decode_step on the rows
+path + ops.sample_logits + the host's bookkeeping, without its per-token host read), DecodeLoop eager, DecodeLoop captured, and the captured
+loop without an eos_token (no host read at all).  Also the one-time cost of building each loop (warm-up + capture) and the kernel nodes of
+one step before and after, counted in captured graphs of their own.  One JSON line per (B, ctx).
+
+    python tools/decode_bench.py --graph [--rounds 5] [--steps 300]
 """
 import argparse
 import contextlib
@@ -464,6 +473,105 @@ def shared_compare(m, G, n_prefix, n_suffix, rounds, steps, dev):
     return out
 
 
+def _graph_nodes(record):
+    """the kernel nodes of what ``record()`` launches, counted in a captured graph of its own that is never replayed (None if the runtime
+    does not hand the graph out)"""
+    import ctypes as C
+    try:
+        g = torch.cuda.CUDAGraph(keep_graph=True)
+        with torch.cuda.graph(g):
+            record()
+        hip = C.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))
+        n = C.c_size_t(0)
+        rc = hip.hipGraphGetNodes(C.c_void_p(g.raw_cuda_graph()), None, C.byref(n))
+        return int(n.value) if rc == 0 else None
+    except Exception as e:   # a count is a report, not a measurement the table depends on
+        print(f"# graph node count unavailable: {type(e).__name__}: {e}", file=sys.stderr)
+        return None
+
+
+def graph_compare(m, B, ctx, rounds, steps, dev):
+    """A generated token with sampling (T = 0.8, top_k = 200, top_p = 0.9) and an eos_token nobody draws, three ways, alternating in one
+    process: today's loop (decode_step on the rows path + ops.sample_logits + _generate_ragged's bookkeeping, without its per-token host
+    read), DecodeLoop eager and DecodeLoop captured (both read the positions once per 16 steps), and the captured loop with no eos_token
+    (no host read at all).  Every window walks the same positions, ctx - 1 - steps .. ctx - 2, so every contender attends over the same
+    keys; only run() / the steps are between the events."""
+    import time
+    from omnibiote_amd import ops
+    from omnibiote_amd.model import DecodeLoop, KVCache
+    V = m.config.vocab_size
+    first = ctx - 1 - steps
+    g = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    idx = torch.randint(4, V, (B, first), device=dev, generator=g)
+    us = torch.rand((steps + 1, B), device=dev, generator=g)
+    setting = dict(temperature=0.8, top_k=200, top_p=0.9)
+    eos = V                                                        # a valid "no row ever finishes": the bookkeeping runs, nothing parks
+    caches = {k: KVCache(m, B, ctx) for k in ("eager", "device", "graph", "graph_no_eos")}
+    logits0 = {k: m.prefill(idx, c, lengths=[first] * B) for k, c in caches.items()}
+    loops, build_ms = {}, {}
+    for k in ("device", "graph", "graph_no_eos"):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        loops[k] = DecodeLoop(m, caches[k], max_steps=steps + 1, uniforms=us, eos_token=None if k == "graph_no_eos" else eos, capture=k != "device", **setting)
+        torch.cuda.synchronize()
+        build_ms[k] = round((time.perf_counter() - t0) * 1e3, 1)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    none_done = torch.zeros(B, dtype=torch.bool, device=dev)
+
+    def eager_steps(cache, logits, n):
+        done = none_done
+        for i in range(n):
+            nxt = ops.sample_logits(logits, us[i], **setting)
+            valid = ~done                                          # noqa: F841 (the loop appends it)
+            done = done | (nxt == eos)
+            cache.park(done)
+            logits = m.decode_step(nxt, cache)
+
+    def window(k):
+        cache = caches[k]
+        if k == "eager":
+            cache.reset(first, torch.full((B,), first, dtype=torch.int32, device=dev), first)
+            torch.cuda.synchronize()
+            e0.record()
+            eager_steps(cache, logits0[k], steps)
+        else:
+            loops[k].positions.fill_(first)
+            cache.reset(first, loops[k].positions, first)
+            loops[k].start(logits0[k])
+            torch.cuda.synchronize()
+            e0.record()
+            loops[k].run(steps)
+        e1.record()
+        e1.synchronize()
+        assert cache.pos == ctx - 1
+        return e0.elapsed_time(e1) / steps * 1e3
+    legs = list(caches)
+    for k in legs:
+        window(k)
+    usec = {k: [] for k in legs}
+    for r in range(rounds):
+        for k in (legs if r % 2 == 0 else legs[::-1]):
+            usec[k].append(window(k))
+    med = {k: statistics.median(v) for k, v in usec.items()}
+    spread = {k: max(v) - min(v) for k, v in usec.items()}
+
+    caches["eager"].reset(first, torch.full((B,), first, dtype=torch.int32, device=dev), first)
+
+    def eager_once():                                              # (the window's set-up stays outside: one step's kernels alone)
+        eager_steps(caches["eager"], logits0["eager"], 1)
+    loops["device"].positions.fill_(first)
+    caches["device"].reset(first, loops["device"].positions, first)
+    nodes = {"eager_step": _graph_nodes(eager_once), "loop_body": _graph_nodes(loops["device"]._body)}
+    out = {"B": B, "context": ctx, "setting": setting, "windows": {"steps": steps, "rounds": rounds, "positions": [first, ctx - 2]},
+           "us_per_token": {k: summary(v, 1) for k, v in usec.items()},
+           "eager_over": {k: round(med["eager"] / med[k], 2) for k in legs if k != "eager"},
+           "gap_us_and_spreads": {k: [round(med["eager"] - med[k], 1), round(spread["eager"], 1), round(spread[k], 1)] for k in legs if k != "eager"},
+           "tokens_per_s": {k: round(B / med[k] * 1e6) for k in legs},
+           "loop_build_ms": build_ms, "kernel_nodes_per_step": nodes}
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batches", default=None, help="default 1,8,64 (--ragged: 8,64)")
@@ -472,6 +580,7 @@ def main():
     p.add_argument("--small-m", action="store_true", help="the weight-streaming product against the tile structures: alone, and in a decode step")
     p.add_argument("--kv8", action="store_true", help="the e4m3 key/value cache against the bf16 cache: the attention alone, and decode_step")
     p.add_argument("--shared", action="store_true", help="G samples of one prompt: the shared-prefix cache against the replicated cache")
+    p.add_argument("--graph", action="store_true", help="the device-resident token loop, eager and captured, against today's host-driven loop")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300, help="decode steps (and attention calls) per timed window")
     p.add_argument("--baseline_ms", type=float, default=400.0, help="the full forward's window: as many calls as fit, at least 3")
@@ -479,6 +588,13 @@ def main():
     a = p.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
+    if a.graph:
+        shapes = tuple((int(b), int(c)) for b in (a.batches or "1,8,64").split(",") for c in (a.contexts or "2048").split(","))
+        m = build(max(c for _, c in shapes), dev)
+        for B, ctx in shapes:
+            print(json.dumps(graph_compare(m, B, ctx, a.rounds, a.steps, dev)), flush=True)
+            torch.cuda.empty_cache()
+        return
     if a.small_m:
         small_m_products(a.rounds, a.steps, dev)
         m = build(2048, dev)
