@@ -234,6 +234,15 @@ SYMBOLS_LOOP = {
                                    C.c_void_p, C.c_int64, C.c_int32, C.c_int64, c_stream]),
 }
 
+# the sampler and the draft verification over a restricted vocabulary (include/omnibiote_hip_constrain.h): a table of its own as well
+SYMBOLS_CONSTRAIN = {
+    "obte_sample_logits_constrained_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_int32, C.c_float,
+                                                      C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, c_stream]),
+    "obte_spec_verify_constrained_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                    C.c_void_p, C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -263,7 +272,7 @@ def lib():
                 raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
             for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
                                             + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
-                                            + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items())):
+                                            + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -10,6 +10,7 @@
 #include "../../include/omnibiote_hip_sample.h"
 #include "../../include/omnibiote_hip_extend.h"
 #include "../../include/omnibiote_hip_spec.h"
+#include "../../include/omnibiote_hip_constrain.h"
 #include "../../include/omnibiote_hip_kv8.h"
 #include "../../include/omnibiote_hip_shared.h"
 

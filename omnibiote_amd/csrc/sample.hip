@@ -3,6 +3,7 @@
 // the load, the maximum, the select and the weights).
 //   draw     per-wave integer totals -> the wave that holds floor(u total); there one wave scan per register group finds the lane,
 //            and the lane walks its 8 columns.
+// CON: the restricted form (include/omnibiote_hip_constrain.h) — the load clears the excluded keys, everything after it is the same code.
 #include "sample_common.h"
 
 namespace {
@@ -16,9 +17,10 @@ struct SampleParams {
     float scale;      // log2(e) / temperature
     float top_p;
     int32_t V, top_k, greedy;
+    SpConstraint con;   // read by the CON kernels only
 };
 
-template <int NT, int R>
+template <int NT, int R, bool CON>
 __global__ __launch_bounds__(NT) void sample_kernel(SampleParams p) {
     __shared__ u64 hist[SP_BINS];
     __shared__ u64 hist2[16];
@@ -32,7 +34,8 @@ __global__ __launch_bounds__(NT) void sample_kernel(SampleParams p) {
     const int chunk0 = wave * R * 64 + lane;
 
     uint32_t k[R][4];
-    sp_load_row<R>(x, chunk0, V, k);
+    if (CON) sp_load_row_masked<R>(x, chunk0, V, sp_row_mask(p.con, row, 0), k);
+    else sp_load_row<R>(x, chunk0, V, k);
     const uint32_t best = sp_row_max<NT, R>(k, chunk0, red);
     const uint32_t maxkey = best >> 16;
     const int argmax = 65535 - (int)(best & 0xFFFFu);
@@ -89,11 +92,9 @@ __global__ __launch_bounds__(NT) void sample_kernel(SampleParams p) {
     }
 }
 
-}  // namespace
-
-extern "C" int obte_sample_logits_bf16(const obte_bf16* logits, int64_t ld, int64_t B, int64_t V, const float* u, float temperature, int32_t top_k, float top_p,
-                                       int64_t* token, int32_t* n_kept, obte_stream s) {
-    static const char* who = "obte_sample_logits_bf16";
+// both entry points: `con` NULL is obte_sample_logits_bf16 itself
+int sample_launch(const char* who, const obte_bf16* logits, int64_t ld, int64_t B, int64_t V, const float* u, float temperature, int32_t top_k, float top_p,
+                  const SpConstraint* con, int64_t hold_token, int64_t* token, int32_t* n_kept, obte_stream s) {
     OBTE_REQUIRE(logits && token, "%s: null pointer (logits, token)", who);
     OBTE_REQUIRE(B >= 1 && B < (1ll << 31) && V >= 1, "%s: B and V must be at least 1 (B=%lld V=%lld)", who, (long long)B, (long long)V);
     if (V > SP_MAX_V) {
@@ -113,13 +114,38 @@ extern "C" int obte_sample_logits_bf16(const obte_bf16* logits, int64_t ld, int6
     p.V = (int32_t)V; p.top_k = top_k; p.top_p = top_p;
     p.greedy = (!u || temperature == 0.f || top_k == 1) ? 1 : 0;
     p.scale = p.greedy ? 1.f : (float)(1.4426950408889634 / (double)temperature);
+    p.con = SpConstraint{nullptr, 0, nullptr, -1, 0};
+    if (con) {
+        const int rc = sp_check_constraint(who, *con, hold_token, V, &p.con);
+        if (rc != OBTE_OK) return rc;
+    }
     hipStream_t st = (hipStream_t)s;
     const int prof = obte_prof_begin(st, 114, B, V, p.greedy);
     const dim3 grid((unsigned)B);
-    if (V <= 256 * 8) hipLaunchKernelGGL((sample_kernel<256, 1>), grid, dim3(256), 0, st, p);
-    else if (V <= 1024 * 8 * 2) hipLaunchKernelGGL((sample_kernel<1024, 2>), grid, dim3(1024), 0, st, p);
-    else hipLaunchKernelGGL((sample_kernel<1024, 8>), grid, dim3(1024), 0, st, p);
+    if (con) {
+        if (V <= 256 * 8) hipLaunchKernelGGL((sample_kernel<256, 1, true>), grid, dim3(256), 0, st, p);
+        else if (V <= 1024 * 8 * 2) hipLaunchKernelGGL((sample_kernel<1024, 2, true>), grid, dim3(1024), 0, st, p);
+        else hipLaunchKernelGGL((sample_kernel<1024, 8, true>), grid, dim3(1024), 0, st, p);
+    } else {
+        if (V <= 256 * 8) hipLaunchKernelGGL((sample_kernel<256, 1, false>), grid, dim3(256), 0, st, p);
+        else if (V <= 1024 * 8 * 2) hipLaunchKernelGGL((sample_kernel<1024, 2, false>), grid, dim3(1024), 0, st, p);
+        else hipLaunchKernelGGL((sample_kernel<1024, 8, false>), grid, dim3(1024), 0, st, p);
+    }
     obte_prof_end(prof, st);
     OBTE_CHECK_LAUNCH(who);
     return OBTE_OK;
+}
+
+}  // namespace
+
+extern "C" int obte_sample_logits_bf16(const obte_bf16* logits, int64_t ld, int64_t B, int64_t V, const float* u, float temperature, int32_t top_k, float top_p,
+                                       int64_t* token, int32_t* n_kept, obte_stream s) {
+    return sample_launch("obte_sample_logits_bf16", logits, ld, B, V, u, temperature, top_k, top_p, nullptr, -1, token, n_kept, s);
+}
+
+extern "C" int obte_sample_logits_constrained_bf16(const obte_bf16* logits, int64_t ld, int64_t B, int64_t V, const float* u, float temperature, int32_t top_k,
+                                                   float top_p, const uint8_t* allowed, int64_t allowed_ld, int64_t hold_token, const int32_t* emitted,
+                                                   int32_t min_emitted, int64_t* token, int32_t* n_kept, obte_stream s) {
+    const SpConstraint con{allowed, allowed_ld, emitted, 0, min_emitted};
+    return sample_launch("obte_sample_logits_constrained_bf16", logits, ld, B, V, u, temperature, top_k, top_p, &con, hold_token, token, n_kept, s);
 }

@@ -3,7 +3,8 @@
 // fixed-point weights.  Every sum is an integer sum, so what one kernel computes of a row — threshold, kept count, total, an entry's
 // weight — is bit for bit what the other computes, whatever the workgroup shape.
 //   load     16 bytes per lane, wave w owning the contiguous chunks [w R 64, (w + 1) R 64) of 8 columns (chunk (w R + j) 64 + lane in
-//            register group j: coalesced per wave and in index order wave by wave).  Columns >= V, NaN and -inf become key 0 = "never kept".
+//            register group j: coalesced per wave and in index order wave by wave).  Columns >= V, NaN and -inf become key 0 = "never kept",
+//            and so do the columns a restriction excludes (sp_load_row_masked: one mask byte per chunk, an AND before the fence).
 //   maximum  one u32 max over key << 16 | (65535 - column): the row maximum and, among its ties, the lowest column.
 //   select   "the first value, walking the distinct values downwards, at which the running sum reaches a target": top-k with weight 1
 //            and target k, top-p with the fixed-point weights and target ceil(top_p total).  Two levels: 4096 bins of the key's upper 12
@@ -61,6 +62,91 @@ __device__ __forceinline__ void sp_load_row(const bf16* x, int chunk0, int V, ui
         sp_load_chunk(x, chunk0 + j * 64, nch, V, k[j]);
 #pragma unroll
         for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(k[j][q]));   // opaque: 32 packed registers stay 32, the passes unpack as they go
+    }
+}
+
+// ---- a restricted row (include/omnibiote_hip_constrain.h): excluded columns become key 0 at load time, nothing after the load changes ----
+struct SpConstraint {          // a call's restriction, as the host hands it over (allowed NULL: no mask; hold_token -1: nothing held)
+    const uint8_t* allowed;
+    int64_t allowed_ld;        // bytes between the rows' masks, 0: one mask for every row
+    const int32_t* emitted;
+    int32_t hold_token;        // already inside [0, V), or -1
+    int32_t min_emitted;
+};
+struct SpRowMask {             // one logits row's share of it
+    const uint8_t* bits;       // ceil(V / 8) bytes, or NULL
+    int hold;                  // the column held in this row, or -1
+};
+// batch row b at drafted position j (0 in the sampler): the hold applies while emitted[b] + j < min_emitted, summed in 64 bits
+__device__ __forceinline__ SpRowMask sp_row_mask(const SpConstraint& c, int64_t b, int j) {
+    SpRowMask m;
+    m.bits = c.allowed ? c.allowed + b * c.allowed_ld : nullptr;
+    m.hold = -1;
+    if (c.hold_token >= 0) {
+        const int64_t e = c.emitted ? (int64_t)c.emitted[b] : 0;
+        if (e + j < (int64_t)c.min_emitted) m.hold = c.hold_token;
+    }
+    return m;
+}
+// the 8 bits of chunk c's columns, a clear bit = excluded (bits of columns >= V mean nothing: sp_load_chunk has made those keys 0)
+__device__ __forceinline__ uint32_t sp_mask_byte(const SpRowMask& m, int c, int nch) {
+    uint32_t bits = 0xFFu;
+    if (m.bits && c < nch) bits = m.bits[c];
+    if ((m.hold >> 3) == c) bits &= ~(1u << (m.hold & 7));   // (hold = -1: chunk -1, never)
+    return bits;
+}
+// sp_load_chunk under such a byte: the bits take the place of the test "column < V" (a bit field extract and an AND per key where the
+// plain load has a compare and a select), so a restricted row costs the plain load's instructions plus a few per chunk
+__device__ __forceinline__ void sp_load_chunk_masked(const bf16* x, int c, int nch, int V, uint32_t bits, uint32_t (&k)[4]) {
+    u32x4 raw = {0u, 0u, 0u, 0u};
+    if (c < nch) raw = *reinterpret_cast<const u32x4*>(x + (int64_t)c * 8);
+    const int nv = V - c * 8;   // columns of this group inside the row (<= 0: none)
+    const uint32_t in = bits & (nv >= 8 ? 0xFFu : nv <= 0 ? 0u : (1u << nv) - 1u);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t lo = sp_key(raw[q] & 0xFFFFu) & (uint32_t)(-(int32_t)((in >> (2 * q)) & 1u));
+        const uint32_t hi = sp_key(raw[q] >> 16) & (uint32_t)(-(int32_t)((in >> (2 * q + 1)) & 1u));
+        k[q] = lo | (hi << 16);
+    }
+}
+// is column t (inside [0, V)) of the row excluded?
+__device__ __forceinline__ bool sp_excluded(const SpRowMask& m, int t) {
+    return t == m.hold || (m.bits && !((m.bits[t >> 3] >> (t & 7)) & 1u));
+}
+
+// the host's checks of a restriction (OBTE_EINVAL before any launch); `out` is what the kernels get: hold_token inside [0, V) or -1
+inline int sp_check_constraint(const char* who, const SpConstraint& c, int64_t hold_token, int64_t V, SpConstraint* out) {
+    OBTE_REQUIRE(c.allowed_ld >= 0, "%s: allowed_ld must not be negative, got %lld", who, (long long)c.allowed_ld);
+    OBTE_REQUIRE(c.allowed_ld == 0 || c.allowed_ld >= (V + 7) / 8, "%s: allowed_ld %lld is smaller than the ceil(V / 8) = %lld bytes of a mask row", who,
+                 (long long)c.allowed_ld, (long long)((V + 7) / 8));
+    OBTE_REQUIRE_ALIGNED(who, c.emitted, "emitted", 4);
+    OBTE_REQUIRE(c.min_emitted >= 0, "%s: min_emitted must not be negative, got %d", who, (int)c.min_emitted);
+    *out = c;
+    out->hold_token = hold_token >= 0 && hold_token < V ? (int32_t)hold_token : -1;
+    return OBTE_OK;
+}
+
+// sp_load_row of a restricted row: the lane that loads chunk c loads byte c of the row's mask — 64 consecutive bytes per wave and
+// register group — and clears the excluded keys before the fence.  The R mask bytes are fetched first, all in flight at once and
+// without a branch (the index is clamped: a chunk >= nch holds key 0 whatever its byte says), so that the row's own loads, which
+// follow one another, wait for one more memory latency and not for R more.
+template <int R>
+__device__ __forceinline__ void sp_load_row_masked(const bf16* x, int chunk0, int V, const SpRowMask& m, uint32_t (&k)[R][4]) {
+    const int nch = (V + 7) >> 3;
+    uint32_t bits[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) bits[j] = 0xFFu;
+    if (m.bits) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) bits[j] = m.bits[min(chunk0 + j * 64, nch - 1)];
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const int c = chunk0 + j * 64;
+        if ((m.hold >> 3) == c) bits[j] &= ~(1u << (m.hold & 7));   // (hold = -1: chunk -1, never)
+        sp_load_chunk_masked(x, c, nch, V, bits[j], k[j]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(k[j][q]));
     }
 }
 

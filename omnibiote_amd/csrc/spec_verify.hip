@@ -5,6 +5,7 @@
 //            workgroup reads p[a] — and q[a] for the residual — once more, 8 columns per lane and in the sampler's index order, and
 //            draws in integer prefix sums as the sampler does: per-wave totals -> the wave that holds the target -> one wave scan per
 //            group of chunks -> the lane walks its 8 columns.
+// CON: the restricted form (include/omnibiote_hip_constrain.h) — both launches clear the excluded keys of p[b, j] and q[b, j] as they load them.
 #include "sample_common.h"
 
 namespace {
@@ -33,6 +34,7 @@ struct SpecParams {
     float scale;      // log2(e) / temperature
     float top_p;
     int32_t k, V, top_k, greedy;
+    SpConstraint con;   // read by the CON kernels only
 };
 
 // Logits row r of batch row b's 2 k + 1 (k + 1 when greedy): r <= k is p[b, r], beyond it q[b, r - k - 1]; `j` the position whose drafted
@@ -46,7 +48,7 @@ __device__ __forceinline__ const bf16* sv_row(const SpecParams& a, int64_t b, in
     return a.q + (b * a.k + j) * a.ld_q;
 }
 
-template <int NT, int R>
+template <int NT, int R, bool CON>
 __global__ __launch_bounds__(NT) void spec_rows_kernel(SpecParams a) {
     __shared__ u64 hist[SP_BINS];
     __shared__ u64 hist2[16];
@@ -64,7 +66,13 @@ __global__ __launch_bounds__(NT) void spec_rows_kernel(SpecParams a) {
     SpecRow* out = a.rows + blockIdx.x;
 
     uint32_t k[R][4];
-    sp_load_row<R>(x, chunk0, V, k);
+    SpRowMask rm{nullptr, -1};
+    if (CON) {
+        rm = sp_row_mask(a.con, b, r <= a.k ? r : r - a.k - 1);   // the drafted position of the row: p[b, r] or q[b, r - k - 1]
+        sp_load_row_masked<R>(x, chunk0, V, rm, k);
+    } else {
+        sp_load_row<R>(x, chunk0, V, k);
+    }
     const uint32_t best = sp_row_max<NT, R>(k, chunk0, red);
     const uint32_t maxkey = best >> 16;
     if (maxkey == 0 || a.greedy) {
@@ -80,7 +88,8 @@ __global__ __launch_bounds__(NT) void spec_rows_kernel(SpecParams a) {
         if (j >= 0) {
             const int64_t t = a.draft[b * a.k + j];
             if (t >= 0 && t < V) {   // (any other value is never an index)
-                const uint32_t key = sp_key(reinterpret_cast<const uint16_t*>(x)[t]);
+                uint32_t key = sp_key(reinterpret_cast<const uint16_t*>(x)[t]);
+                if (CON && sp_excluded(rm, (int)t)) key = 0;
                 if (key >= thr) wx = sp_weight(key, maxkey, maxv, scale);   // thr >= 1: key 0 is never kept
             }
         }
@@ -136,16 +145,23 @@ __device__ __forceinline__ u64 sv_residual(u64 wp, u64 tq, u64 wq, u64 tp, int S
 
 struct SvSide {        // one logits row as the draw reads it
     const bf16* x;
+    SpRowMask rm;      // (CON only)
     uint32_t maxkey, thr;
     float maxv;
 };
 
 // the weights of chunk c's 8 columns: the kept entries' fixed-point weights of `P`, or with RES the residual against `Q`
-template <bool RES>
+template <bool RES, bool CON>
 __device__ __forceinline__ void sv_chunk(const SvSide& P, const SvSide& Q, int c, int nch, int V, float scale, u64 tp, u64 tq, int S, u64 (&w)[8]) {
     uint32_t kp[4], kq[4] = {0u, 0u, 0u, 0u};
-    sp_load_chunk(P.x, c, nch, V, kp);
-    if (RES) sp_load_chunk(Q.x, c, nch, V, kq);
+    if (CON) {   // P and Q are rows of one drafted position: one restriction
+        const uint32_t bits = sp_mask_byte(P.rm, c, nch);
+        sp_load_chunk_masked(P.x, c, nch, V, bits, kp);
+        if (RES) sp_load_chunk_masked(Q.x, c, nch, V, bits, kq);
+    } else {
+        sp_load_chunk(P.x, c, nch, V, kp);
+        if (RES) sp_load_chunk(Q.x, c, nch, V, kq);
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const uint32_t a = (i & 1) ? kp[i >> 1] >> 16 : kp[i >> 1] & 0xFFFFu;
@@ -162,7 +178,7 @@ __device__ __forceinline__ void sv_chunk(const SvSide& P, const SvSide& Q, int c
 
 // The draw over the row's V entries in index order, weights by sv_chunk<RES>: wave w owns chunks [w R 64, (w + 1) R 64), group g of them
 // holds chunk (w R + g) 64 + lane.  Returns the row's total; with `find` (total > 0) the lane that holds the target writes the token.
-template <int NT, bool RES>
+template <int NT, bool RES, bool CON>
 __device__ __forceinline__ u64 sv_draw(const SvSide& P, const SvSide& Q, int V, float scale, u64 tp, u64 tq, int S, float u, bool find, int fallback,
                                        int64_t* token, u64* red) {
     constexpr int NW = NT / 64;
@@ -173,7 +189,7 @@ __device__ __forceinline__ u64 sv_draw(const SvSide& P, const SvSide& Q, int V, 
     u64 w[8];
     u64 mass = 0;
     for (int g = 0; g < R; ++g) {
-        sv_chunk<RES>(P, Q, chunk0 + g * 64, nch, V, scale, tp, tq, S, w);
+        sv_chunk<RES, CON>(P, Q, chunk0 + g * 64, nch, V, scale, tp, tq, S, w);
 #pragma unroll
         for (int i = 0; i < 8; ++i) mass += w[i];
     }
@@ -195,7 +211,7 @@ __device__ __forceinline__ u64 sv_draw(const SvSide& P, const SvSide& Q, int V, 
     u64 run = base;
     for (int g = 0; g < R; ++g) {
         const int c = chunk0 + g * 64;
-        sv_chunk<RES>(P, Q, c, nch, V, scale, tp, tq, S, w);
+        sv_chunk<RES, CON>(P, Q, c, nch, V, scale, tp, tq, S, w);
         u64 sj = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) sj += w[i];
@@ -220,7 +236,7 @@ __device__ __forceinline__ u64 sv_draw(const SvSide& P, const SvSide& Q, int V, 
     return total;
 }
 
-template <int NT>
+template <int NT, bool CON>
 __global__ __launch_bounds__(NT) void spec_decide_kernel(SpecParams a) {
     __shared__ u64 red[NT / 64];
     __shared__ int sh_a;
@@ -257,6 +273,7 @@ __global__ __launch_bounds__(NT) void spec_decide_kernel(SpecParams a) {
     int unused;
     SvSide P, Q;
     P.x = sv_row(a, b, n, unused); P.maxkey = maxkey; P.thr = rp.thr; P.maxv = sp_val(maxkey);
+    P.rm = CON ? sp_row_mask(a.con, b, n) : SpRowMask{nullptr, -1};
     Q = P;
     const float u = a.u_draw[b];
     const u64 tp = rp.total;
@@ -265,25 +282,36 @@ __global__ __launch_bounds__(NT) void spec_decide_kernel(SpecParams a) {
         if (rq.total > 0) {          // (0: the draft row holds nothing to sample: Q = 0 everywhere, the residual is P)
             Q.x = sv_row(a, b, k + 1 + n, unused); Q.maxkey = rq.best >> 16; Q.thr = rq.thr; Q.maxv = sp_val(Q.maxkey);
             const int S = sv_bits(tp) + sv_bits(rq.total) - 62;
-            if (sv_draw<NT, true>(P, Q, a.V, a.scale, tp, rq.total, S, u, true, argmax, a.token + b, red) > 0) return;
+            if (sv_draw<NT, true, CON>(P, Q, a.V, a.scale, tp, rq.total, S, u, true, argmax, a.token + b, red) > 0) return;
         }
     }
-    sv_draw<NT, false>(P, P, a.V, a.scale, tp, 0, 0, u, true, argmax, a.token + b, red);
+    sv_draw<NT, false, CON>(P, P, a.V, a.scale, tp, 0, 0, u, true, argmax, a.token + b, red);
 }
 
 int64_t rows_of(int64_t B, int64_t k, bool greedy) { return B * (greedy ? k + 1 : 2 * k + 1); }
 
-}  // namespace
+template <bool CON>
+void spec_launch(const SpecParams& a, int64_t B, int64_t k, int64_t V, bool greedy, hipStream_t st) {
+    const dim3 grid((unsigned)rows_of(B, k, greedy)), gridb((unsigned)B);
+    if (V <= 256 * 8) {
+        hipLaunchKernelGGL((spec_rows_kernel<256, 1, CON>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((spec_decide_kernel<256, CON>), gridb, dim3(256), 0, st, a);
+    } else {
+        if (V <= 1024 * 8 * 2) hipLaunchKernelGGL((spec_rows_kernel<1024, 2, CON>), grid, dim3(1024), 0, st, a);
+        else hipLaunchKernelGGL((spec_rows_kernel<1024, 8, CON>), grid, dim3(1024), 0, st, a);
+        hipLaunchKernelGGL((spec_decide_kernel<1024, CON>), gridb, dim3(1024), 0, st, a);
+    }
+}
 
-extern "C" int64_t obte_spec_verify_ws_bytes(int64_t B, int64_t k) {
+int64_t ws_bytes_of(int64_t B, int64_t k) {
     if (B < 1 || k < 1 || k > SV_MAX_K || B >= (1ll << 24)) return 0;
     return rows_of(B, k, false) * (int64_t)sizeof(SpecRow);
 }
 
-extern "C" int obte_spec_verify_bf16(const obte_bf16* p, int64_t ld_p, const obte_bf16* q, int64_t ld_q, const int64_t* draft, int64_t B, int64_t k, int64_t V,
-                                     const float* u_accept, const float* u_draw, float temperature, int32_t top_k, float top_p, int32_t* n_accept,
-                                     int64_t* token, void* ws, int64_t ws_bytes, obte_stream s) {
-    static const char* who = "obte_spec_verify_bf16";
+// both entry points: `con` NULL is obte_spec_verify_bf16 itself
+int spec_verify(const char* who, const obte_bf16* p, int64_t ld_p, const obte_bf16* q, int64_t ld_q, const int64_t* draft, int64_t B, int64_t k, int64_t V,
+                const float* u_accept, const float* u_draw, float temperature, int32_t top_k, float top_p, const SpConstraint* con, int64_t hold_token,
+                int32_t* n_accept, int64_t* token, void* ws, int64_t ws_bytes, obte_stream s) {
     static_assert(sizeof(SpecRow) == 32, "the workspace holds 32 bytes per logits row");
     OBTE_REQUIRE(p && draft && n_accept && token && ws, "%s: null pointer (p, draft, n_accept, token, ws)", who);
     OBTE_REQUIRE(B >= 1 && B < (1ll << 24) && k >= 1 && V >= 1, "%s: B, k and V must be at least 1 (B=%lld k=%lld V=%lld)", who, (long long)B, (long long)k,
@@ -314,7 +342,7 @@ extern "C" int obte_spec_verify_bf16(const obte_bf16* p, int64_t ld_p, const obt
     OBTE_REQUIRE_ALIGNED(who, n_accept, "n_accept", 4);
     OBTE_REQUIRE_ALIGNED(who, token, "token", 8);
     OBTE_REQUIRE_ALIGNED(who, ws, "ws", 8);
-    const int64_t need = obte_spec_verify_ws_bytes(B, k);
+    const int64_t need = ws_bytes_of(B, k);
     OBTE_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes, %lld needed (obte_spec_verify_ws_bytes)", who, (long long)ws_bytes, (long long)need);
     SpecParams a;
     a.p = (const bf16*)p; a.q = (const bf16*)q; a.ld_p = ld_p; a.ld_q = ld_q; a.draft = draft; a.u_accept = u_accept; a.u_draw = u_draw;
@@ -322,18 +350,37 @@ extern "C" int obte_spec_verify_bf16(const obte_bf16* p, int64_t ld_p, const obt
     a.k = (int32_t)k; a.V = (int32_t)V; a.top_k = top_k; a.top_p = top_p;
     a.greedy = greedy ? 1 : 0;
     a.scale = greedy ? 1.f : (float)(1.4426950408889634 / (double)temperature);
+    a.con = SpConstraint{nullptr, 0, nullptr, -1, 0};
+    if (con) {
+        const int rc = sp_check_constraint(who, *con, hold_token, V, &a.con);
+        if (rc != OBTE_OK) return rc;
+    }
     hipStream_t st = (hipStream_t)s;
     const int prof = obte_prof_begin(st, 115, B, k, V);
-    const dim3 grid((unsigned)rows_of(B, k, greedy)), gridb((unsigned)B);
-    if (V <= 256 * 8) {
-        hipLaunchKernelGGL((spec_rows_kernel<256, 1>), grid, dim3(256), 0, st, a);
-        hipLaunchKernelGGL((spec_decide_kernel<256>), gridb, dim3(256), 0, st, a);
-    } else {
-        if (V <= 1024 * 8 * 2) hipLaunchKernelGGL((spec_rows_kernel<1024, 2>), grid, dim3(1024), 0, st, a);
-        else hipLaunchKernelGGL((spec_rows_kernel<1024, 8>), grid, dim3(1024), 0, st, a);
-        hipLaunchKernelGGL((spec_decide_kernel<1024>), gridb, dim3(1024), 0, st, a);
-    }
+    if (con) spec_launch<true>(a, B, k, V, greedy, st);
+    else spec_launch<false>(a, B, k, V, greedy, st);
     obte_prof_end(prof, st);
     OBTE_CHECK_LAUNCH(who);
     return OBTE_OK;
 }
+
+}  // namespace
+
+extern "C" int64_t obte_spec_verify_ws_bytes(int64_t B, int64_t k) { return ws_bytes_of(B, k); }
+
+extern "C" int obte_spec_verify_bf16(const obte_bf16* p, int64_t ld_p, const obte_bf16* q, int64_t ld_q, const int64_t* draft, int64_t B, int64_t k, int64_t V,
+                                     const float* u_accept, const float* u_draw, float temperature, int32_t top_k, float top_p, int32_t* n_accept,
+                                     int64_t* token, void* ws, int64_t ws_bytes, obte_stream s) {
+    return spec_verify("obte_spec_verify_bf16", p, ld_p, q, ld_q, draft, B, k, V, u_accept, u_draw, temperature, top_k, top_p, nullptr, -1, n_accept, token, ws,
+                       ws_bytes, s);
+}
+
+extern "C" int obte_spec_verify_constrained_bf16(const obte_bf16* p, int64_t ld_p, const obte_bf16* q, int64_t ld_q, const int64_t* draft, int64_t B, int64_t k,
+                                                 int64_t V, const float* u_accept, const float* u_draw, float temperature, int32_t top_k, float top_p,
+                                                 const uint8_t* allowed, int64_t allowed_ld, int64_t hold_token, const int32_t* emitted, int32_t min_emitted,
+                                                 int32_t* n_accept, int64_t* token, void* ws, int64_t ws_bytes, obte_stream s) {
+    const SpConstraint con{allowed, allowed_ld, emitted, 0, min_emitted};
+    return spec_verify("obte_spec_verify_constrained_bf16", p, ld_p, q, ld_q, draft, B, k, V, u_accept, u_draw, temperature, top_k, top_p, &con, hold_token,
+                       n_accept, token, ws, ws_bytes, s);
+}
+

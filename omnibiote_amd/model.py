@@ -815,13 +815,71 @@ def sample_next(logits, temperature=1.0, top_k=None, generator=None, top_p=None)
     return torch.multinomial(probs, num_samples=1, generator=generator).squeeze(1)
 
 
-def _next_tokens(what, logits, temperature, top_k, top_p, generator, u):
+class TokenConstraint:
+    """``allowed_tokens`` and ``min_new_tokens`` of one generation call, checked and packed once before the prefill (the rule:
+    include/omnibiote_hip_constrain.h; in plain torch ``sampling.constrain_reference``).  ``allowed``: bool (V,) or (rows, V) on the
+    call's device, or None; ``packed``: the same as ``sampling.pack_token_mask`` makes it; ``hold``: ``eos_token`` while a minimum length is
+    asked for, else None; ``min_new``: that length.  ``TokenConstraint.of`` returns None for a call that restricts nothing."""
+
+    @classmethod
+    def of(cls, what, allowed_tokens, min_new_tokens, max_new_tokens, eos_token, rows, vocab, device):
+        if isinstance(min_new_tokens, bool) or not isinstance(min_new_tokens, int) or not 0 <= min_new_tokens <= max(int(max_new_tokens), 0):
+            raise ValueError(f"OmniBioTA.{what}: min_new_tokens must be an integer in [0, max_new_tokens = {max_new_tokens}], got {min_new_tokens!r}")
+        if min_new_tokens > 0 and eos_token is None:
+            raise ValueError(f"OmniBioTA.{what}: min_new_tokens = {min_new_tokens} holds eos_token back, and there is no eos_token")
+        if allowed_tokens is None and min_new_tokens == 0:
+            return None
+        mask = None
+        if allowed_tokens is not None:
+            t = allowed_tokens if isinstance(allowed_tokens, torch.Tensor) else torch.as_tensor(allowed_tokens)
+            if t.dtype == torch.bool:
+                if t.shape not in ((vocab,), (rows, vocab)):
+                    raise ValueError(f"OmniBioTA.{what}: a bool allowed_tokens must be ({vocab},) or ({rows}, {vocab}): one row per output row, got "
+                                     f"{tuple(t.shape)}")
+                mask = t.to(device)
+            else:
+                if t.dim() == 1 and t.numel() == 0:                     # (an empty list comes as float32)
+                    t = t.to(torch.int64)
+                if t.dim() != 1 or t.is_floating_point() or t.is_complex():
+                    raise ValueError(f"OmniBioTA.{what}: allowed_tokens must be a 1-D sequence of token ids or a bool mask, got {t.dtype} {tuple(t.shape)}")
+                if t.numel() > 0 and (int(t.min()) < 0 or int(t.max()) >= vocab):
+                    raise ValueError(f"OmniBioTA.{what}: allowed_tokens holds an id outside [0, vocab_size = {vocab})")
+                mask = torch.zeros(vocab, dtype=torch.bool, device=device)
+                mask[t.to(device=device, dtype=torch.int64)] = True
+            if not bool(mask.any(dim=-1).all()):
+                raise ValueError(f"OmniBioTA.{what}: allowed_tokens allows nothing" + (" in some row" if mask.dim() == 2 else ""))
+            if min_new_tokens > 0 and 0 <= int(eos_token) < vocab:
+                other = mask.clone()
+                other[..., int(eos_token)] = False
+                if not bool(other.any(dim=-1).all()):
+                    raise ValueError(f"OmniBioTA.{what}: min_new_tokens = {min_new_tokens} holds eos_token back, and allowed_tokens allows nothing else"
+                                     + (" in some row" if mask.dim() == 2 else ""))
+        from .sampling import pack_token_mask
+        con = cls()
+        con.allowed, con.packed = mask, None if mask is None else pack_token_mask(mask)
+        con.min_new, con.hold = min_new_tokens, eos_token if min_new_tokens > 0 else None
+        return con
+
+    def device_args(self, emitted_by_all=0):
+        """the keywords of ``ops.sample_logits`` in a host-driven loop: every running row has emitted ``emitted_by_all`` tokens"""
+        return dict(allowed_packed=self.packed, hold_token=self.hold, emitted=None, min_emitted=max(0, self.min_new - emitted_by_all))
+
+    def restrict(self, logits, emitted_by_all=0):
+        """``logits`` with the excluded columns at -inf, for the torch sampler"""
+        from .sampling import constrain_reference
+        return constrain_reference(logits, self.allowed, self.hold, None, max(0, self.min_new - emitted_by_all))
+
+
+def _next_tokens(what, logits, temperature, top_k, top_p, generator, u, con=None, step=0):
     """one step's tokens: ``sample_next`` (u is None: the torch sampler), or one launch of the device sampler against this step's
-    uniforms ``u`` (B,) — False: greedy, nothing was drawn"""
+    uniforms ``u`` (B,) — False: greedy, nothing was drawn.  ``con``: the call's ``TokenConstraint`` or None; ``step``: the tokens every
+    running row has emitted so far"""
     if u is None:
-        return sample_next(logits, temperature, top_k, generator, top_p)
+        return sample_next(logits if con is None else con.restrict(logits, step), temperature, top_k, generator, top_p)
     if not (logits.is_cuda and logits.dtype == torch.bfloat16):
         raise ValueError(f"OmniBioTA.{what}: sampler='device' needs bf16 logits on the GPU, got {logits.dtype} on {logits.device}")
+    if con is not None:
+        return ops.sample_logits(logits, None if u is False else u, temperature, top_k, top_p, **con.device_args(step))
     return ops.sample_logits(logits, None if u is False else u, temperature, top_k, top_p)
 
 
@@ -1104,11 +1162,16 @@ class DecodeLoop:
     ``capture=True``: the body runs once eagerly with every row parked — it touches no cache byte by the rows convention, and takes the
     kernels' one-time set-up out of the capture; the loop's state is restored — and is then recorded into a ``torch.cuda.CUDAGraph``,
     one linear stream.  It needs B <= the weight-streaming product's row limit (``obte_small_m_max``): above it the products take
-    paths that have not been vetted for capture, and the constructor raises ValueError (the eager body takes any B).  Weights, cache
+    paths that have not been vetted for capture, and the constructor raises ValueError (the eager body takes any B).
+
+    ``allowed`` (a packed mask, uint8 (n,) or (B, n) on the device as ``ops.pack_token_mask`` makes it) and ``hold_min`` restrict every draw,
+    the first token's included (include/omnibiote_hip_constrain.h): the sampler gets the mask, ``eos_token`` as the held token and the
+    loop's own ``n_new`` as the rows' emitted counts — addresses and constants, so a captured graph replays it.  Weights, cache
     buffers and tables are captured BY ADDRESS: in-place updates of the parameters are seen by the next replay, but ``model.to(...)``,
     a reloaded parameter or a new cache leave the graph reading freed memory — build a new loop."""
 
-    def __init__(self, model, cache, *, max_steps, temperature=1.0, top_k=None, top_p=None, uniforms=None, eos_token=None, capture=False):
+    def __init__(self, model, cache, *, max_steps, temperature=1.0, top_k=None, top_p=None, uniforms=None, eos_token=None, capture=False, allowed=None,
+                 hold_min=0):
         if isinstance(cache, SharedPrefixCache):
             raise ValueError("DecodeLoop: a SharedPrefixCache steps at a host suffix position, which changes every step: the device loop needs a KVCache")
         model._check_generation("DecodeLoop", cache.batch, cache)
@@ -1119,6 +1182,10 @@ class DecodeLoop:
         if top_k is not None and top_k < 1:
             raise ValueError(f"DecodeLoop: top_k must be at least 1, got {top_k}")
         _check_top_p("DecodeLoop", top_p)
+        if isinstance(hold_min, bool) or not isinstance(hold_min, int) or hold_min < 0:
+            raise ValueError(f"DecodeLoop: hold_min must be an integer of at least 0, got {hold_min!r}")
+        if hold_min > 0 and eos_token is None:
+            raise ValueError(f"DecodeLoop: hold_min = {hold_min} holds eos_token back, and there is no eos_token")
         if cache.pos == 0:
             raise ValueError("DecodeLoop: the cache is empty: prefill a prompt first")
         cfg = model.config
@@ -1135,6 +1202,7 @@ class DecodeLoop:
         self.model, self.cache, self.max_steps, self.eos_token = model, cache, int(max_steps), eos_token
         self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
         self.uniforms = None if greedy else uniforms.contiguous()
+        self.allowed, self.hold_min = allowed, hold_min
         if cache.positions is None:
             cache.reset(cache.pos, positions=torch.full((b,), cache.pos, dtype=torch.int32, device=dev), min_pos=cache.pos)
         self.positions = cache.positions
@@ -1153,7 +1221,12 @@ class DecodeLoop:
             self._capture()
 
     def _sample_and_advance(self, commit):
-        ops.sample_logits(self.logits, self.u if self.uniforms is not None else None, self.temperature, self.top_k, self.top_p, out=self.sampled)
+        if self.allowed is not None or self.hold_min > 0:
+            ops.sample_logits(self.logits, self.u if self.uniforms is not None else None, self.temperature, self.top_k, self.top_p, out=self.sampled,
+                              allowed_packed=self.allowed, hold_token=self.eos_token if self.hold_min > 0 else None, emitted=self.n_new,
+                              min_emitted=self.hold_min)
+        else:
+            ops.sample_logits(self.logits, self.u if self.uniforms is not None else None, self.temperature, self.top_k, self.top_p, out=self.sampled)
         ops.gen_advance(self.sampled, self.positions, self.count, self.out, self.n_new, self.token, self.model.transformer.wte.weight, self.x,
                         us=self.uniforms, u=self.u if self.uniforms is not None else None, eos=self.eos_token, commit=commit)
 
@@ -1570,7 +1643,7 @@ class OmniBioTA(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None, lengths=None, pad_token=None, top_p=None,
-                 sampler="torch", kv_dtype="bf16", num_samples=None, loop=None):
+                 sampler="torch", kv_dtype="bf16", num_samples=None, loop=None, allowed_tokens=None, min_new_tokens=0):
         """nanoGPT's generate(): ``idx`` (B, T0) int64 continued by up to ``max_new_tokens`` sampled tokens (``sample_next``); returns
         (B, T0 + n) int64.  The prompt runs once (``prefill``), every new token costs one ``decode_step``.  Where nanoGPT crops the
         context to block_size, this raises: T0 + max_new_tokens must fit.  ``eos_token``: a row that has produced it keeps producing
@@ -1599,7 +1672,15 @@ class OmniBioTA(nn.Module):
         finished rows are parked there, and the host looks at the rows once every 16 tokens (never without ``eos_token``); "graph" also
         replays every step as one captured graph (B <= 64).  Same arguments, same shape of result, the device sampler's rule and uniforms;
         the tokens are those of ``loop=None, sampler="device"`` except where two logits lie closer than the attention's summation order
-        resolves (``DecodeLoop``: the fixed bound).  Needs ``sampler="device"``; not with ``num_samples``: both raise ValueError."""
+        resolves (``DecodeLoop``: the fixed bound).  Needs ``sampler="device"``; not with ``num_samples``: both raise ValueError.
+
+        ``allowed_tokens``: what may be generated — a 1-D sequence or tensor of token ids, a bool (V,) mask, or a bool (rows, V) mask with
+        one row per output row (P * G rows with ``num_samples=G``).  Everything else is treated as a logit of -inf at every step
+        (``sampling.constrain_reference``; on the device the sampler reads the packed mask itself).  ``eos_token`` is not added: list it
+        if rows are to end.  The prompt and ``pad_token`` are not restricted.  ``min_new_tokens``: ``eos_token`` is excluded as well until a
+        row has that many new tokens.  Both work with every sampler, cache and loop above; with neither given nothing changes.
+        ValueError before anything is launched: an id outside [0, V), a row that allows nothing, ``min_new_tokens`` outside
+        [0, max_new_tokens] or without an ``eos_token``, a row that allows nothing but the held ``eos_token``."""
         if sampler not in ("torch", "device"):
             raise ValueError(f"OmniBioTA.generate: sampler must be 'torch' or 'device', got {sampler!r}")
         if loop not in (None, "device", "graph"):
@@ -1622,9 +1703,11 @@ class OmniBioTA(nn.Module):
         b, t0 = idx.shape
         if t0 == 0:
             raise ValueError("OmniBioTA.generate: the prompt is empty")
+        con = TokenConstraint.of("generate", allowed_tokens, min_new_tokens, max_new_tokens, eos_token, b * (num_samples or 1), self.config.vocab_size,
+                                 idx.device)
         if lengths is not None:
             return self._generate_ragged(idx, _check_lengths("generate", lengths, b, t0), max_new_tokens, temperature, top_k, generator, eos_token,
-                                         pad_token, top_p, sampler, kv_dtype, loop)
+                                         pad_token, top_p, sampler, kv_dtype, loop, con)
         if max_new_tokens < 0 or t0 + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {t0} prompt tokens + {max_new_tokens} new ones exceed block_size = {self.config.block_size}")
         if num_samples is None:
@@ -1639,14 +1722,14 @@ class OmniBioTA(nn.Module):
         logits = self.prefill(idx, cache)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
         if loop is not None:
-            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop)
+            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con)
             if eos_token is not None:                                   # a finished row keeps producing EOS
                 live = torch.arange(tokens.shape[1], device=idx.device).view(1, -1) < n_new.view(-1, 1)
                 tokens = torch.where(live, tokens, torch.full_like(tokens, eos_token))
             return torch.cat([rows, tokens], dim=1)
         done = None
         for i in range(max_new_tokens):
-            nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i])
+            nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i], con, i)
             if eos_token is not None:
                 if done is not None:
                     nxt = torch.where(done, torch.full_like(nxt, eos_token), nxt)
@@ -1657,16 +1740,17 @@ class OmniBioTA(nn.Module):
             logits = self.decode_step(nxt, cache)
         return torch.cat(out, dim=1)
 
-    def _device_loop(self, cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop):
+    def _device_loop(self, cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con=None):
         """``generate``'s token loop as a ``DecodeLoop`` behind the prefill that gave ``logits``: (tokens (B, S), n_new (B,))"""
         run = DecodeLoop(self, cache, max_steps=max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
-                         uniforms=us if isinstance(us, torch.Tensor) else None, eos_token=eos_token, capture=loop == "graph")
+                         uniforms=us if isinstance(us, torch.Tensor) else None, eos_token=eos_token, capture=loop == "graph",
+                         allowed=None if con is None else con.packed, hold_min=0 if con is None else con.min_new)
         run.start(logits)
         run.run(max_new_tokens - 1)
         return run.result()
 
     def _generate_ragged(self, idx, lens, max_new_tokens, temperature, top_k, generator, eos_token, pad_token, top_p=None, sampler="torch", kv_dtype="bf16",
-                         loop=None):
+                         loop=None, con=None):
         longest = max(lens)
         if max_new_tokens < 0 or longest + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {longest} prompt tokens (the longest row) + {max_new_tokens} new ones exceed "
@@ -1681,12 +1765,12 @@ class OmniBioTA(nn.Module):
         logits = self.prefill(idx, cache, lengths=lens)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
         if loop is not None:
-            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop)
+            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con)
             return ragged_output(idx, lens, tokens, torch.arange(tokens.shape[1], device=idx.device).view(1, -1) < n_new.view(-1, 1), pad)
         tokens, valid = [], []
         done = torch.zeros(b, dtype=torch.bool, device=idx.device)
         for i in range(max_new_tokens):
-            nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i])
+            nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i], con, i)
             tokens.append(nxt)
             valid.append(~done)                                         # a row's token counts if the row was running when it was drawn
             if eos_token is not None:
@@ -1699,7 +1783,8 @@ class OmniBioTA(nn.Module):
         return ragged_output(idx, lens, torch.stack(tokens, dim=1), torch.stack(valid, dim=1), pad)
 
     @torch.no_grad()
-    def draft_and_verify(self, draft, pending, cache, draft_cache, k, uniforms=None, temperature=1.0, top_k=None, top_p=None):
+    def draft_and_verify(self, draft, pending, cache, draft_cache, k, uniforms=None, temperature=1.0, top_k=None, top_p=None, allowed=None, hold_token=None,
+                         emitted=None, min_emitted=0):
         """One round of speculative decoding, everything but the step back.  ``pending`` (B,) int64 is every row's last emitted token,
         in neither cache yet; ``cache`` (this model's) and ``draft_cache`` (``draft``'s) stand at the same per-row positions.  The draft
         runs k ``decode_step``s, drawing x_0 .. x_{k-1} with ``ops.sample_logits`` from its logits q_0 .. q_{k-1}, and one more that
@@ -1707,29 +1792,43 @@ class OmniBioTA(nn.Module):
         caches then hold k + 1 new positions per row.  ``uniforms``: None (greedy: the draft proposes its argmax, q is not kept) or the
         round's ``(draws (k, B), u_accept (B, k), u_draw (B,))`` float32 on the device.  Returns ``(x (B, k) int64, n_accept (B,) int32,
         token (B,) int64)`` on the device; nothing waits for them.  The caller reads n_accept and steps both caches back by
-        ``k - n_accept[b]`` (``rewind_rows``): row b has emitted x_0 .. x_{a-1} and ``token``, its new pending token."""
+        ``k - n_accept[b]`` (``rewind_rows``): row b has emitted x_0 .. x_{a-1} and ``token``, its new pending token.
+
+        ``allowed`` (a packed mask, uint8 (n,) or (B, n) on the device), ``hold_token``, ``emitted`` (B,) int32 — what every row has emitted,
+        the pending token included — and ``min_emitted`` restrict the draft's draws and the verification alike
+        (include/omnibiote_hip_constrain.h): the draft's j-th draw and the verification's position j hold ``hold_token`` while
+        ``emitted[b] + j < min_emitted``.  With none given the round runs the unrestricted entry points."""
         self._refuse_fp8("draft_and_verify", cache)         # (the draft only takes decode steps: its cache may be either)
         self._refuse_shared("draft_and_verify", cache)
         b = pending.shape[0]
         greedy = uniforms is None or temperature == 0 or top_k == 1
         draws, u_accept, u_draw = (None, None, None) if greedy else uniforms
         q = None if greedy else torch.empty((b, k, self.config.vocab_size), dtype=torch.bfloat16, device=pending.device)
+        restricted = allowed is not None or hold_token is not None or emitted is not None or min_emitted != 0
         xs, tok = [], pending
         for j in range(k):
             ql = draft.decode_step(tok, draft_cache)
             if q is not None:
                 q[:, j] = ql
-            tok = ops.sample_logits(ql, None if greedy else draws[j], temperature, top_k, top_p)
+            if restricted:
+                tok = ops.sample_logits(ql, None if greedy else draws[j], temperature, top_k, top_p, allowed_packed=allowed, hold_token=hold_token,
+                                        emitted=emitted, min_emitted=max(0, min_emitted - j))
+            else:
+                tok = ops.sample_logits(ql, None if greedy else draws[j], temperature, top_k, top_p)
             xs.append(tok)
         draft.decode_step(tok, draft_cache)                             # x_{k-1} joins the draft's cache as it joins the target's below
         x = torch.stack(xs, dim=1)
         p = self.extend(torch.cat([pending.unsqueeze(1), x], dim=1), cache, logits="all")
-        n_accept, token = ops.spec_verify(p, q, x, u_accept, u_draw, temperature, top_k, top_p)
+        if restricted:
+            n_accept, token = ops.spec_verify(p, q, x, u_accept, u_draw, temperature, top_k, top_p, allowed_packed=allowed, hold_token=hold_token,
+                                              emitted=emitted, min_emitted=min_emitted)
+        else:
+            n_accept, token = ops.spec_verify(p, q, x, u_accept, u_draw, temperature, top_k, top_p)
         return x, n_accept, token
 
     @torch.no_grad()
     def generate_speculative(self, idx, max_new_tokens, draft, k=4, temperature=1.0, top_k=None, top_p=None, generator=None, eos_token=None,
-                             lengths=None, pad_token=None, return_stats=False, kv_dtype="bf16", num_samples=None):
+                             lengths=None, pad_token=None, return_stats=False, kv_dtype="bf16", num_samples=None, allowed_tokens=None, min_new_tokens=0):
         """``generate`` by draft and verify: ``draft`` — any autoregressive OmniBioTA on the same device with the same vocabulary, a smaller
         model in practice, this model itself for a self-check — proposes ``k`` tokens per round (1 <= k <= 31), this model scores them in
         one ``extend`` and ``ops.spec_verify`` keeps a prefix of them and adds one token of its own, so that every emitted token is
@@ -1746,7 +1845,11 @@ class OmniBioTA(nn.Module):
 
         Returns (B, T0 + max_new_tokens) int64, a row that emitted ``eos_token`` filled with it to the end; with ``lengths``
         ``(out, out_lengths)`` as ``generate`` does (``ragged_output``).  ``return_stats`` appends a dict of host ints: ``rounds``, and
-        over all rows and rounds ``drafted`` (k per running row) and ``accepted`` (the drafted tokens that stood)."""
+        over all rows and rounds ``drafted`` (k per running row) and ``accepted`` (the drafted tokens that stood).
+
+        ``allowed_tokens`` and ``min_new_tokens`` as in ``generate``: the draft's draws and the verification take the same mask and the same
+        held ``eos_token``, so the emitted tokens are distributed as this model's own restricted sampling; the rows' emitted counts reach
+        the device once per round, behind the round's host synchronisation."""
         what = "generate_speculative"
         if num_samples is not None:
             raise NotImplementedError(f"OmniBioTA.{what}: num_samples: verifying a drafted block attends from several new positions per row, which "
@@ -1782,6 +1885,7 @@ class OmniBioTA(nn.Module):
         if max_new_tokens < 0 or longest + max_new_tokens + k > block:
             raise ValueError(f"OmniBioTA.{what}: {longest} prompt tokens (the longest row) + {max_new_tokens} new ones + k = {k} drafted exceed "
                              f"block_size = {block} (the smaller of the two models')")
+        con = TokenConstraint.of(what, allowed_tokens, min_new_tokens, max_new_tokens, eos_token, b, self.config.vocab_size, idx.device)
         pad = pad_token if pad_token is not None else (eos_token if eos_token is not None else 0)
         idx = idx[:, :longest]
         dev = idx.device
@@ -1802,7 +1906,11 @@ class OmniBioTA(nn.Module):
         cache, draft_cache = KVCache(self, b, longest + max_new_tokens + k), KVCache(draft, b, longest + max_new_tokens + k)
         logits = self.prefill(idx, cache, lengths=lens)
         draft.prefill(idx, draft_cache, lengths=lens)
-        pending = ops.sample_logits(logits, None if greedy else torch.rand(b, device=dev, generator=generator), temperature, top_k, top_p)
+        if con is None:
+            pending = ops.sample_logits(logits, None if greedy else torch.rand(b, device=dev, generator=generator), temperature, top_k, top_p)
+        else:
+            pending = ops.sample_logits(logits, None if greedy else torch.rand(b, device=dev, generator=generator), temperature, top_k, top_p,
+                                        **con.device_args())
         # the host's account: where the rows stand in both caches (-1: parked), what each has emitted and where in `cols` it lies
         at = list(lens)
         cols, width = [pending.unsqueeze(1)], 1
@@ -1821,7 +1929,12 @@ class OmniBioTA(nn.Module):
             if not greedy:
                 r = torch.rand(b * (2 * k + 1), device=dev, generator=generator)
                 us = r[:k * b].view(k, b), r[k * b:2 * k * b].view(b, k), r[2 * k * b:]
-            x, n_accept, token = self.draft_and_verify(draft, pending, cache, draft_cache, k, us, temperature, top_k, top_p)
+            if con is None:
+                x, n_accept, token = self.draft_and_verify(draft, pending, cache, draft_cache, k, us, temperature, top_k, top_p)
+            else:                                                       # what the rows have emitted: the host's account, as of the last round's read
+                emitted = torch.tensor([len(w) for w in where], dtype=torch.int32, device=dev) if con.min_new > 0 else None
+                x, n_accept, token = self.draft_and_verify(draft, pending, cache, draft_cache, k, us, temperature, top_k, top_p, allowed=con.packed,
+                                                           hold_token=con.hold, emitted=emitted, min_emitted=con.min_new)
             a_dev = n_accept.long().unsqueeze(1)
             emitted = torch.cat([x, token.unsqueeze(1)], dim=1).scatter(1, a_dev, token.unsqueeze(1))   # x_0 .. x_{a-1}, token, (stale)
             if eos_token is None:

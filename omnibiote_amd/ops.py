@@ -262,12 +262,63 @@ def small_m_max(m: int):
         L.lib().obte_small_m_max_set(prev)
 
 
-def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, return_kept=False, out=None):
+def pack_token_mask(mask):
+    """bool (..., V) on the device -> uint8 (..., ceil(V / 8)) on the device: column i is bit i & 7 of byte i >> 3 (sampling.pack_token_mask:
+    the ``allowed_packed`` of ``sample_logits`` and ``spec_verify``).  A few torch launches, once per mask — not part of a step."""
+    _need(mask, "mask", torch.bool, contiguous=False)
+    from .sampling import pack_token_mask as pack
+    return pack(mask)
+
+
+def _constraint(what, B, V, device, allowed, allowed_packed, hold_token, emitted, min_emitted):
+    """The restriction of include/omnibiote_hip_constrain.h as the C call's five arguments ``(mask tensor or None, allowed_ld, hold_token,
+    emitted or None, min_emitted)`` — None when no keyword was given: the caller takes the unrestricted symbol."""
+    if allowed is None and allowed_packed is None and hold_token is None and emitted is None and min_emitted == 0:
+        return None
+    if allowed is not None and allowed_packed is not None:
+        raise ValueError(f"{what}: allowed and allowed_packed are the same mask in two forms: give one")
+    nb = (V + 7) // 8
+    if allowed is not None:
+        _need(allowed, "allowed", torch.bool, contiguous=False)
+        if allowed.shape not in ((V,), (B, V)):
+            raise ValueError(f"{what}: allowed must be bool ({V},) or ({B}, {V}), got {tuple(allowed.shape)}")
+        allowed_packed = pack_token_mask(allowed)
+    ld = 0
+    if allowed_packed is not None:
+        _need(allowed_packed, "allowed_packed", torch.uint8, contiguous=False)
+        if allowed_packed.dim() not in (1, 2) or allowed_packed.shape[-1] < nb or (allowed_packed.dim() == 2 and allowed_packed.shape[0] != B):
+            raise ValueError(f"{what}: allowed_packed must be uint8 (n,) or ({B}, n) with n >= ceil(V / 8) = {nb}, got {tuple(allowed_packed.shape)}")
+        if allowed_packed.stride(-1) != 1 and allowed_packed.shape[-1] > 1:
+            raise ValueError(f"{what}: allowed_packed must have stride 1 along the bytes of a mask")
+        if allowed_packed.dim() == 2 and B > 1:
+            ld = allowed_packed.stride(0)
+            if ld < nb:
+                raise ValueError(f"{what}: the rows of allowed_packed must lie at least ceil(V / 8) = {nb} bytes apart, got a stride of {ld}")
+    if emitted is not None:
+        _need(emitted, "emitted", torch.int32)
+        if emitted.shape != (B,):
+            raise ValueError(f"{what}: emitted must be int32 ({B},), got {tuple(emitted.shape)}")
+    if isinstance(min_emitted, bool) or not isinstance(min_emitted, int) or not 0 <= min_emitted < 2 ** 31:
+        raise ValueError(f"{what}: min_emitted must be an integer in [0, 2^31), got {min_emitted!r}")
+    hold = -1 if hold_token is None else int(hold_token)
+    if not -2 ** 63 <= hold < 2 ** 63:
+        raise ValueError(f"{what}: hold_token must fit 64 bits, got {hold_token!r}")
+    return allowed_packed, ld, hold, emitted, min_emitted
+
+
+def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, return_kept=False, out=None, allowed=None, allowed_packed=None,
+                  hold_token=None, emitted=None, min_emitted=0):
     """The next token of every row of ``logits`` (B, V) bf16, V <= 65536, in one launch (obte_sample_logits_bf16; the rule:
     include/omnibiote_hip_sample.h, restated in plain torch by sampling.sample_reference): temperature, top-k, top-p, softmax and the
     draw against ``u`` (B,) float32 uniforms.  ``u is None``, ``temperature == 0`` or ``top_k == 1``: the lowest index of the row maximum.
     logits may be a row-strided view: last-dimension stride 1, row stride a multiple of 8.  Returns (B,) int64 (``out`` when given: a
-    caller's buffer that keeps its address from step to step), with ``return_kept`` also the size of every row's kept set, (B,) int32."""
+    caller's buffer that keeps its address from step to step), with ``return_kept`` also the size of every row's kept set, (B,) int32.
+
+    The restriction (obte_sample_logits_constrained_bf16; the rule: include/omnibiote_hip_constrain.h, in plain torch
+    sampling.constrain_reference): ``allowed`` bool (V,) or (B, V) — packed here, a few torch launches — or ``allowed_packed`` uint8
+    (n,) or (B, n), n >= ceil(V / 8), as ``pack_token_mask`` makes it (any byte address; rows may be strided): a column whose bit is clear is
+    treated as -inf.  ``hold_token`` is excluded too in every row with ``emitted[b] < min_emitted`` (``emitted`` (B,) int32 on the device,
+    None: 0).  With none of the five given the call is the unrestricted one."""
     _need(logits, "logits", contiguous=False)
     if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
         raise ValueError(f"sample_logits: logits must be (B, V) with B, V >= 1, got {tuple(logits.shape)}")
@@ -287,6 +338,13 @@ def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, retur
         if out.shape != (B,):
             raise ValueError(f"sample_logits: out must be ({B},), got {tuple(out.shape)}")
     kept = torch.empty(B, dtype=torch.int32, device=logits.device) if return_kept else None
+    con = _constraint("sample_logits", B, V, logits.device, allowed, allowed_packed, hold_token, emitted, min_emitted)
+    if con is not None:
+        L.check(L.lib().obte_sample_logits_constrained_bf16(_ptr(logits), ld, B, V, _ptr(u), float(temperature),
+                                                            0 if top_k is None else min(int(top_k), 2 ** 31 - 1), 1.0 if top_p is None else float(top_p),
+                                                            _ptr(con[0]), con[1], con[2], _ptr(con[3]), con[4], _ptr(token), _ptr(kept), _stream()),
+                "obte_sample_logits_constrained_bf16")
+        return (token, kept) if return_kept else token
     L.check(L.lib().obte_sample_logits_bf16(_ptr(logits), ld, B, V, _ptr(u), float(temperature), 0 if top_k is None else min(int(top_k), 2 ** 31 - 1),
                                             1.0 if top_p is None else float(top_p), _ptr(token), _ptr(kept), _stream()), "obte_sample_logits_bf16")
     return (token, kept) if return_kept else token
@@ -321,14 +379,19 @@ def gen_advance(sampled, pos, count, out, n_new, token, wte, x, us=None, u=None,
                                      -1 if eos is None else int(eos), int(commit), B, _stream()), "obte_gen_advance")
 
 
-def spec_verify(p, q, draft, u_accept=None, u_draw=None, temperature=1.0, top_k=None, top_p=None):
+def spec_verify(p, q, draft, u_accept=None, u_draw=None, temperature=1.0, top_k=None, top_p=None, allowed=None, allowed_packed=None, hold_token=None,
+                emitted=None, min_emitted=0):
     """Speculative decoding's verification in two launches (obte_spec_verify_bf16; the rule: include/omnibiote_hip_spec.h, restated in
     plain torch by sampling.verify_reference).  ``p`` (B, k + 1, V) bf16: the target's logits behind the pending token and behind each of
     the k drafted tokens ``draft`` (B, k) int64; ``q`` (B, k, V) bf16: the logits the draft drew them from; ``u_accept`` (B, k) and
     ``u_draw`` (B,) float32 uniforms.  1 <= k <= 31, V <= 65536.  Without uniforms, with ``temperature == 0`` or ``top_k == 1`` the call is
     greedy — a drafted token stands while it is the lowest index of the target row's maximum — and ``q`` may be None.  p and q may be
     row-strided views: last-dimension stride 1, row stride a multiple of 8, rows evenly spaced.  Returns ``(n_accept (B,) int32, token
-    (B,) int64)``: how many drafted tokens stand and the token behind them."""
+    (B,) int64)``: how many drafted tokens stand and the token behind them.
+
+    ``allowed`` / ``allowed_packed`` / ``hold_token`` / ``emitted`` / ``min_emitted`` as in ``sample_logits``, one mask row per batch row
+    (obte_spec_verify_constrained_bf16): the restriction applies to p[b, j] and q[b, j] alike, the hold while ``emitted[b] + j <
+    min_emitted`` at drafted position j, and a drafted token that is excluded never stands.  With none given: the unrestricted call."""
     _need(p, "p", contiguous=False)
     if p.dim() != 3 or p.shape[0] < 1 or p.shape[1] < 2 or p.shape[2] < 1:
         raise ValueError(f"spec_verify: p must be (B, k + 1, V) with B, k, V >= 1, got {tuple(p.shape)}")
@@ -366,6 +429,13 @@ def spec_verify(p, q, draft, u_accept=None, u_draw=None, temperature=1.0, top_k=
     token = torch.empty(B, dtype=torch.int64, device=p.device)
     ws_bytes = max(int(L.lib().obte_spec_verify_ws_bytes(B, min(k, L.SPEC_VERIFY_MAX_K))), 8)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
+    con = _constraint("spec_verify", B, V, p.device, allowed, allowed_packed, hold_token, emitted, min_emitted)
+    if con is not None:
+        L.check(L.lib().obte_spec_verify_constrained_bf16(_ptr(p), ld_p, _ptr(q), ld_q, _ptr(draft), B, k, V, _ptr(u_accept), _ptr(u_draw), float(temperature),
+                                                          0 if top_k is None else min(int(top_k), 2 ** 31 - 1), 1.0 if top_p is None else float(top_p),
+                                                          _ptr(con[0]), con[1], con[2], _ptr(con[3]), con[4], _ptr(n_accept), _ptr(token), _ptr(ws), ws_bytes,
+                                                          _stream()), "obte_spec_verify_constrained_bf16")
+        return n_accept, token
     L.check(L.lib().obte_spec_verify_bf16(_ptr(p), ld_p, _ptr(q), ld_q, _ptr(draft), B, k, V, _ptr(u_accept), _ptr(u_draw), float(temperature),
                                           0 if top_k is None else min(int(top_k), 2 ** 31 - 1), 1.0 if top_p is None else float(top_p),
                                           _ptr(n_accept), _ptr(token), _ptr(ws), ws_bytes, _stream()), "obte_spec_verify_bf16")

@@ -175,6 +175,53 @@ def verify_reference(p, q, draft, u_accept=None, u_draw=None, temperature=1.0, t
     return tuple(t[0] for t in out) if one else out
 
 
+def pack_token_mask(mask):
+    """bool (..., V) -> uint8 (..., ceil(V / 8)): column i is bit i & 7 of byte i >> 3, the padding bits of the last byte clear (the
+    ``allowed`` argument of include/omnibiote_hip_constrain.h).  Plain torch on any device."""
+    if mask.dtype != torch.bool or mask.dim() < 1 or mask.shape[-1] < 1:
+        raise ValueError(f"pack_token_mask: mask must be bool (..., V) with V >= 1, got {mask.dtype} {tuple(mask.shape)}")
+    v = mask.shape[-1]
+    nb = (v + 7) // 8
+    bits = torch.zeros(mask.shape[:-1] + (nb * 8,), dtype=torch.int32, device=mask.device)
+    bits[..., :v] = mask
+    weight = (1 << torch.arange(8, device=mask.device, dtype=torch.int32))
+    return (bits.view(mask.shape[:-1] + (nb, 8)) * weight).sum(dim=-1).to(torch.uint8)
+
+
+def unpack_token_mask(packed, v):
+    """uint8 (..., n >= ceil(V / 8)) -> bool (..., V): the inverse of ``pack_token_mask``; bits of columns >= V are ignored."""
+    if packed.dtype != torch.uint8 or packed.dim() < 1 or v < 1 or packed.shape[-1] * 8 < v:
+        raise ValueError(f"unpack_token_mask: packed must be uint8 (..., >= ceil(V / 8)) with V = {v} >= 1, got {packed.dtype} {tuple(packed.shape)}")
+    col = torch.arange(v, device=packed.device)
+    return ((packed[..., col >> 3].to(torch.int32) >> (col & 7).to(torch.int32)) & 1).bool()
+
+
+def constrain_reference(logits, allowed=None, hold_token=None, emitted=None, min_emitted=0, offset=0):
+    """``logits`` (B, V) or (V,) with the excluded columns set to -inf: the restriction of include/omnibiote_hip_constrain.h in plain
+    torch on any device.  ``allowed``: bool (V,) — one mask for every row — or (B, V); a False column is excluded.  ``hold_token`` (None,
+    negative or >= V: nothing) is excluded too in every row b with ``emitted[b] + offset < min_emitted``; ``emitted``: None (0), a number
+    or (B,) integers; ``offset``: the drafted position j of the row (0 in the sampler).  ``sample_reference`` / ``verify_reference`` on
+    the result are what the constrained kernels implement."""
+    one = logits.dim() == 1
+    x = logits.unsqueeze(0) if one else logits
+    if x.dim() != 2:
+        raise ValueError(f"constrain_reference: logits must be (B, V) or (V,), got {tuple(logits.shape)}")
+    if min_emitted < 0:
+        raise ValueError(f"constrain_reference: min_emitted must not be negative, got {min_emitted}")
+    b, v = x.shape
+    out = torch.zeros((b, v), dtype=torch.bool, device=x.device)         # excluded
+    if allowed is not None:
+        a = torch.as_tensor(allowed, device=x.device)
+        if a.dtype != torch.bool or a.shape not in ((v,), (b, v)):
+            raise ValueError(f"constrain_reference: allowed must be bool ({v},) or ({b}, {v}), got {a.dtype} {tuple(a.shape)}")
+        out = out | ~a.expand(b, v)
+    if hold_token is not None and 0 <= int(hold_token) < v:
+        e = torch.zeros(b, dtype=torch.int64, device=x.device) if emitted is None else _per_row(emitted, b, x.device, torch.int64)
+        out[:, int(hold_token)] |= e + int(offset) < int(min_emitted)
+    res = x.masked_fill(out, float("-inf"))
+    return res[0] if one else res
+
+
 def advance_reference(sampled, pos, count, out, n_new, token, wte, us=None, eos=None, commit=1):
     """The generation loop's per-row bookkeeping in plain torch on any device: what obte_gen_advance (include/omnibiote_hip_loop.h)
     implements.  Nothing is changed in place; returns the new ``(pos, count, out, n_new, token, x, u)``.  ``sampled`` (B,) int64 are the

@@ -57,7 +57,7 @@ path + ops.sample_logits + the host's bookkeeping, without its per-token host re
 loop without an eos_token (no host read at all).  Also the one-time cost of building each loop (warm-up + capture) and the kernel nodes of
 one step before and after, counted in captured graphs of their own.  One JSON line per (B, ctx).
 
-    python tools/decode_bench.py --graph [--rounds 5] [--steps 300]
+    python tools/decode_bench.py --graph [--constrained] [--rounds 5] [--steps 300]
 """
 import argparse
 import contextlib
@@ -490,12 +490,13 @@ def _graph_nodes(record):
         return None
 
 
-def graph_compare(m, B, ctx, rounds, steps, dev):
+def graph_compare(m, B, ctx, rounds, steps, dev, constrained=False):
     """A generated token with sampling (T = 0.8, top_k = 200, top_p = 0.9) and an eos_token nobody draws, three ways, alternating in one
     process: today's loop (decode_step on the rows path + ops.sample_logits + _generate_ragged's bookkeeping, without its per-token host
     read), DecodeLoop eager and DecodeLoop captured (both read the positions once per 16 steps), and the captured loop with no eos_token
     (no host read at all).  Every window walks the same positions, ctx - 1 - steps .. ctx - 2, so every contender attends over the same
-    keys; only run() / the steps are between the events."""
+    keys; only run() / the steps are between the events.  ``constrained`` adds the captured loop under a restriction
+    (include/omnibiote_hip_constrain.h): per-row masks that allow a random half of the vocabulary and a minimum length nobody reaches."""
     import time
     from omnibiote_amd import ops
     from omnibiote_amd.model import DecodeLoop, KVCache
@@ -506,13 +507,15 @@ def graph_compare(m, B, ctx, rounds, steps, dev):
     us = torch.rand((steps + 1, B), device=dev, generator=g)
     setting = dict(temperature=0.8, top_k=200, top_p=0.9)
     eos = V                                                        # a valid "no row ever finishes": the bookkeeping runs, nothing parks
-    caches = {k: KVCache(m, B, ctx) for k in ("eager", "device", "graph", "graph_no_eos")}
+    caches = {k: KVCache(m, B, ctx) for k in ("eager", "device", "graph", "graph_no_eos") + (("graph_constrained",) if constrained else ())}
     logits0 = {k: m.prefill(idx, c, lengths=[first] * B) for k, c in caches.items()}
     loops, build_ms = {}, {}
-    for k in ("device", "graph", "graph_no_eos"):
+    for k in list(caches)[1:]:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        loops[k] = DecodeLoop(m, caches[k], max_steps=steps + 1, uniforms=us, eos_token=None if k == "graph_no_eos" else eos, capture=k != "device", **setting)
+        extra = dict(allowed=ops.pack_token_mask(torch.rand((B, V), device=dev, generator=g) < 0.5), hold_min=steps + 1) if k == "graph_constrained" else {}
+        loops[k] = DecodeLoop(m, caches[k], max_steps=steps + 1, uniforms=us, eos_token=None if k == "graph_no_eos" else eos, capture=k != "device", **setting,
+                              **extra)
         torch.cuda.synchronize()
         build_ms[k] = round((time.perf_counter() - t0) * 1e3, 1)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -581,6 +584,7 @@ def main():
     p.add_argument("--kv8", action="store_true", help="the e4m3 key/value cache against the bf16 cache: the attention alone, and decode_step")
     p.add_argument("--shared", action="store_true", help="G samples of one prompt: the shared-prefix cache against the replicated cache")
     p.add_argument("--graph", action="store_true", help="the device-resident token loop, eager and captured, against today's host-driven loop")
+    p.add_argument("--constrained", action="store_true", help="with --graph: also the captured loop under per-row token masks and a minimum length")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300, help="decode steps (and attention calls) per timed window")
     p.add_argument("--baseline_ms", type=float, default=400.0, help="the full forward's window: as many calls as fit, at least 3")
@@ -592,7 +596,7 @@ def main():
         shapes = tuple((int(b), int(c)) for b in (a.batches or "1,8,64").split(",") for c in (a.contexts or "2048").split(","))
         m = build(max(c for _, c in shapes), dev)
         for B, ctx in shapes:
-            print(json.dumps(graph_compare(m, B, ctx, a.rounds, a.steps, dev)), flush=True)
+            print(json.dumps(graph_compare(m, B, ctx, a.rounds, a.steps, dev, a.constrained)), flush=True)
             torch.cuda.empty_cache()
         return
     if a.small_m:

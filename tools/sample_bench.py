@@ -11,6 +11,14 @@ Device events around windows of --steps calls, --rounds rounds after warm-up; me
 (part, B).
 
     python tools/sample_bench.py [--batches 1,8,64] [--rounds 5] [--steps 300] [--part a|b|ab]
+
+--constrained: what a restricted vocabulary costs (include/omnibiote_hip_constrain.h), the sampler alone as in (a), B in {1, 64} unless
+--batches says otherwise, greedy and top_k = 200 with top_p = 0.9, half the vocabulary allowed.  Four contenders alternate: the
+unconstrained call; the constrained call with one shared mask and with per-row masks; and what a caller had to do before — masked_fill
+in torch into a second tensor, then the unconstrained call.  The expectation: constrained <= unconstrained (1 + 1/16) + the unconstrained
+call's own spread — it reads V / 8 mask bytes on top of 2 V logits bytes — and below the masked_fill route.
+
+    python tools/sample_bench.py --constrained [--batches 1,64] [--rounds 5] [--steps 300]
 """
 import argparse
 import json
@@ -73,6 +81,41 @@ def sampler_alone(B, rounds, steps, dev):
     return out
 
 
+def constrained_compare(B, rounds, steps, dev):
+    from decode_bench import timed
+    from omnibiote_amd import ops
+    gen = torch.Generator(device=dev).manual_seed(B + 1)
+    logits = (torch.randn(B, VOCAB, device=dev, generator=gen) * 2).to(torch.bfloat16)
+    u = torch.rand(B, device=dev, generator=gen)
+    rows = torch.rand(B, VOCAB, device=dev, generator=gen) < 0.5
+    shared, per_row = ops.pack_token_mask(rows[0].contiguous()), ops.pack_token_mask(rows)
+    excluded = ~rows
+    out = {"part": "constrained sampler alone", "B": B, "V": VOCAB, "allowed": "a random half", "windows": {"calls": steps, "rounds": rounds}, "us": {}}
+    for name, kw in (SETTINGS[0], SETTINGS[4]):
+        uu = None if kw.get("top_k") == 1 else u
+        args = (kw["temperature"], kw.get("top_k"), kw.get("top_p"))
+        legs = {"unconstrained": lambda: ops.sample_logits(logits, uu, *args),
+                "constrained_shared": lambda: ops.sample_logits(logits, uu, *args, allowed_packed=shared),
+                "constrained_per_row": lambda: ops.sample_logits(logits, uu, *args, allowed_packed=per_row),
+                "masked_fill_then_unconstrained": lambda: ops.sample_logits(logits.masked_fill(excluded, float("-inf")), uu, *args)}
+        for fn in legs.values():
+            for _ in range(5):
+                fn()
+        us = {k: [] for k in legs}
+        for r in range(rounds):
+            for leg in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+                us[leg].append(timed(legs[leg], steps))
+        med = {k: statistics.median(v) for k, v in us.items()}
+        res = {k: summary(v) for k, v in us.items()}
+        bound = med["unconstrained"] * (1 + 1 / 16) + (max(us["unconstrained"]) - min(us["unconstrained"]))
+        res["bound_unconstrained_plus_a_sixteenth_plus_its_spread"] = round(bound, 1)
+        for k in ("constrained_shared", "constrained_per_row"):
+            res[k + "_within_bound"] = med[k] <= bound
+            res[k + "_beats_masked_fill"] = med[k] < med["masked_fill_then_unconstrained"]
+        out["us"][name] = res
+    return out
+
+
 def generated_token(m, B, ctx, rounds, steps, dev):
     from omnibiote_amd.model import KVCache
     gen = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
@@ -96,7 +139,8 @@ def generated_token(m, B, ctx, rounds, steps, dev):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--batches", default="1,8,64")
+    p.add_argument("--batches", default=None, help="default 1,8,64 (--constrained: 1,64)")
+    p.add_argument("--constrained", action="store_true", help="the constrained sampler against the unconstrained one and the masked_fill route")
     p.add_argument("--context", type=int, default=2048)
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300)
@@ -104,7 +148,11 @@ def main():
     a = p.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
-    batches = [int(b) for b in a.batches.split(",")]
+    batches = [int(b) for b in (a.batches or ("1,64" if a.constrained else "1,8,64")).split(",")]
+    if a.constrained:
+        for B in batches:
+            print(json.dumps(constrained_compare(B, a.rounds, a.steps, dev)), flush=True)
+        return
     if "a" in a.part:
         for B in batches:
             print(json.dumps(sampler_alone(B, a.rounds, a.steps, dev)), flush=True)
