@@ -243,6 +243,13 @@ SYMBOLS_CONSTRAIN = {
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
 }
 
+# the decode step's weights stored as OCP e4m3 (include/omnibiote_hip_w8.h): a table of its own as well
+SYMBOLS_W8 = {
+    "obte_linear_small_m_w8": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p, C.c_int64, C.c_void_p, c_stream]),
+    "obte_block_step_w8": (C.c_int, [C.POINTER(BlockDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -272,7 +279,8 @@ def lib():
                 raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
             for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
                                             + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
-                                            + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())):
+                                            + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
+                                            + list(SYMBOLS_W8.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -498,19 +498,25 @@ struct InferAttention {
     // a prefix shared by groups of rows (obte_block_decode_shared, include/omnibiote_hip_shared.h): the prefix cache of P rows holding n_prefix
     // positions; kv_cache / T_max / pos are then the SUFFIX cache of B rows, its slots and the step's slot (decode, uniform)
     const obte_bf16* prefix_cache = nullptr; int64_t P = 0, T_pre = 0, n_prefix = 0;
+    // the four weights as e4m3 codes and row scales (obte_block_step_w8, include/omnibiote_hip_w8.h), in the order of the products below; null:
+    // bf16 from the descriptor, which holds the dequantised weights either way
+    const void* const* w8_codes = nullptr; const float* const* w8_scales = nullptr;
 };
 int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const InferLayout& w, int64_t M, const float* rope_cos,
                    const float* rope_sin, int64_t rope_T, const InferAttention& at, obte_stream s) {
     const int C = d->n_embd, H = d->n_head, hs = C / H;
     // a call against the cache — decode (M = B rows) or extend (M = B * n_new rows) — of at most obte_small_m_max() rows: its four
     // products on the weight-streaming kernel (gemm_small_m.hip), the same epilogues; every other call (prefill, the forward-only block,
-    // a larger extend) on the tile structures at every M
+    // a larger extend) on the tile structures at every M.  `which`: the product's place among the four, for the e4m3 form of the streamed weight
     const bool stream_w = at.n_new > 0 && M <= obte_small_m_max();
-    auto run = [stream_w](const obte_gemm_args& g, obte_stream st) { return stream_w ? obte_linear_small_m_bf16(&g, st) : obte_gemm_bf16_ws(&g, nullptr, 0, st); };
+    auto run = [stream_w, &at](const obte_gemm_args& g, int which, obte_stream st) {
+        if (!stream_w) return obte_gemm_bf16_ws(&g, nullptr, 0, st);
+        return at.w8_codes ? obte_linear_small_m_w8(&g, at.w8_codes[which], g.K, at.w8_scales[which], st) : obte_linear_small_m_bf16(&g, st);
+    };
     TRY(obte_layernorm_fwd(x, d->ln1_w, w.h1, w.mean, w.rstd, M, C, 1e-5f, s));
     obte_gemm_args qkv = xWt(w.h1, d->attn_w, w.qkv, M, 3 * C, C);
     if (!at.pos_rows) { qkv.epilogue = OBTE_EPI_ROPE_QK; qkv.rope_cos = rope_cos; qkv.rope_sin = rope_sin; qkv.rope_T = rope_T; qkv.rope_head_dim = hs; }
-    TRY(run(qkv, s));
+    TRY(run(qkv, 0, s));
     const float scale = 8.0f / (float)C;  // model.py:119
     if (at.n_new > 0) {   // n_new positions per row join the cache (the rows form rotates them as it stores), then each attends over those up to its own
         const int64_t q_ld = 3 * (int64_t)C;
@@ -533,12 +539,12 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
         TRY(obte_attn_fwd(&af, s));
         if (at.kv_cache) TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, nullptr, nullptr, nullptr, 0, d->B, d->T, H, hs, at.kv_cache, at.T_max, s));   // (c_fc's activation overwrites qkv below)
     }
-    TRY(run(plus_residual(xWt(w.att, d->proj_w, w.x1, M, C, C), x, d->dropout_p, d->dropout_seed, SITE_RESID), s));
+    TRY(run(plus_residual(xWt(w.att, d->proj_w, w.x1, M, C, C), x, d->dropout_p, d->dropout_seed, SITE_RESID), 1, s));
     TRY(obte_layernorm_fwd(w.x1, d->ln2_w, w.h2, w.mean, w.rstd, M, C, 1e-5f, s));
     obte_gemm_args fc = xWt(w.h2, d->fc_w, w.hact, M, 4 * C, C);
     fc.epilogue = OBTE_EPI_GELU_ACT;
-    TRY(run(fc, s));
-    return run(plus_residual(xWt(w.hact, d->mlp_w, y_out, M, C, 4 * C), w.x1, d->dropout_p, d->dropout_seed, SITE_MLP), s);
+    TRY(run(fc, 2, s));
+    return run(plus_residual(xWt(w.hact, d->mlp_w, y_out, M, C, 4 * C), w.x1, d->dropout_p, d->dropout_seed, SITE_MLP), 3, s);
 }
 
 // obte_block_fwd_infer and obte_block_fwd_prefill: the same checks, the same workspace
@@ -582,7 +588,8 @@ namespace {
 // pos_rows[b] on, read on the device, with `pos` the host's bound on it.  decode: the one-position launchers (obte_kv_cache_rope_store_rows,
 // obte_attn_decode / _rows and their workspace behind InferLayout) instead of obte_attn_extend's.
 int cached_step(const char* who, const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, int64_t pos,
-                const int32_t* pos_rows, bool rows, bool decode, void* ws, int64_t ws_bytes, obte_stream s, bool kv8 = false) {
+                const int32_t* pos_rows, bool rows, bool decode, void* ws, int64_t ws_bytes, obte_stream s, bool kv8 = false,
+                const void* const* w8_codes = nullptr, const float* const* w8_scales = nullptr) {
     TRY(check_desc(who, d));
     OBTE_REQUIRE(!decode || d->T == 1, "%s: one new position per row (T = 1), got T = %lld", who, (long long)d->T);
     if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
@@ -610,7 +617,8 @@ int cached_step(const char* who, const obte_block_desc* d, const obte_bf16* x, o
     const int64_t need = w.total + align256(att_bytes);
     OBTE_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes, obte_block_%s_ws_bytes() asks for %lld", who, (long long)ws_bytes, decode ? "decode" : "extend",
                  (long long)need);
-    const InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, att_bytes, rows ? pos_rows : nullptr, n, decode, kv8, who};
+    InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, att_bytes, rows ? pos_rows : nullptr, n, decode, kv8, who};
+    at.w8_codes = w8_codes; at.w8_scales = w8_scales;
     // uniform: c_attn rotates row b n + j by the tables' row pos + j (rope_T = n on the tables advanced by pos rows); rows form: the FULL tables
     const int64_t row = at.pos_rows ? 0 : pos * (hs / 2);
     return infer_sequence(d, x, y_out, w, d->B * n, d->rope_cos + row, d->rope_sin + row, n, at, s);
@@ -638,6 +646,18 @@ extern "C" int obte_block_decode_rows(const obte_block_desc* d, const obte_bf16*
 extern "C" int obte_block_decode_kv8(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* cache8, int64_t T_max, int64_t pos, const int32_t* pos_rows,
                                      void* ws, int64_t ws_bytes, obte_stream s) {
     return cached_step("obte_block_decode_kv8", d, x, y_out, (obte_bf16*)cache8, T_max, pos, pos_rows, pos_rows != nullptr, true, ws, ws_bytes, s, true);
+}
+
+// the decode step with its four products' weights in e4m3 (include/omnibiote_hip_w8.h): any of the three above by (cache_e4m3, pos_rows)
+extern "C" int obte_block_step_w8(const obte_block_desc* d, const void* const* codes, const float* const* scales, const obte_bf16* x, obte_bf16* y_out, void* cache,
+                                  int32_t cache_e4m3, int64_t T_max, int64_t pos, const int32_t* pos_rows, void* ws, int64_t ws_bytes, obte_stream s) {
+    const char* who = "obte_block_step_w8";
+    OBTE_REQUIRE(codes && scales, "%s: null pointer", who);
+    for (int i = 0; i < 4; ++i) {
+        OBTE_REQUIRE(codes[i] && scales[i], "%s: null pointer (codes[%d] / scales[%d])", who, i, i);
+        OBTE_REQUIRE(((uintptr_t)codes[i] & 15) == 0 && ((uintptr_t)scales[i] & 3) == 0, "%s: codes[%d] must be 16-byte aligned, scales[%d] 4-byte aligned", who, i, i);
+    }
+    return cached_step(who, d, x, y_out, (obte_bf16*)cache, T_max, pos, pos_rows, pos_rows != nullptr, true, ws, ws_bytes, s, cache_e4m3 != 0, codes, scales);
 }
 
 // InferLayout at T = n_new (M = B n_new rows) with obte_attn_extend's partials behind it (include/omnibiote_hip_extend.h)

@@ -13,6 +13,7 @@
 #include "../../include/omnibiote_hip_constrain.h"
 #include "../../include/omnibiote_hip_kv8.h"
 #include "../../include/omnibiote_hip_shared.h"
+#include "../../include/omnibiote_hip_w8.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

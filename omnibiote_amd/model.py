@@ -26,6 +26,7 @@ Contract notes (each mirrors a reference behaviour):
 """
 from __future__ import annotations
 
+import copy
 import warnings
 import weakref
 from dataclasses import dataclass
@@ -37,6 +38,7 @@ from torch.utils.checkpoint import checkpoint
 
 from . import _lib as L
 from . import ops
+from . import w8quant
 
 try:  # the real package, if the environment has it (README.md:16 pins mup==1.0.0)
     from mup import MuReadout as _MuReadoutBase  # type: ignore
@@ -1133,6 +1135,81 @@ class SharedPrefixCache(CachePositions):
         self.pos -= n
 
 
+class QuantizedWeights:
+    """``model``'s decode-step weights as OCP e4m3 with one power-of-two scale per output row (include/omnibiote_hip_w8.h, w8quant.py):
+    what ``prefill``, ``decode_step``, ``generate`` and ``DecodeLoop`` take as ``weights=``.  Per block, in the order c_attn, attention
+    c_proj, c_fc, MLP c_proj: ``codes[i]`` (four uint8 (N, K) tensors in w8quant's stored order), ``scales[i]`` (four fp32 (N,)) and
+    ``dequantized[i]`` (the four bf16 weights those codes stand for); ``head_codes``, ``head_scales`` and ``head_dequantized`` the same
+    three things for ``lm_head.weight``.  The embedding ``wte`` and the LayerNorm weights are read from the model as ever.
+
+    A cached step of at most ``ops.small_m_max`` rows reads the codes — half the bytes — and computes, bit for bit, the bf16 step on the
+    dequantised weights; everything else (the prompt, a larger batch) runs the existing kernels on the dequantised weights, so prompt and
+    continuation see ONE model: ``dequantized_model()``.
+
+    A snapshot: it remembers every source parameter's ``data_ptr()`` and ``_version``, and every use raises ValueError ("quantize_weights
+    again") once a parameter was updated or moved.  It holds 3 bytes per parameter (codes and the bf16 copy) beside the model's 2;
+    serving from the codes alone, without the bf16 copies, is not built."""
+
+    def __init__(self, model):
+        self.model = model
+        self._sources = []
+        self.codes, self.scales, self.dequantized, self._params = [], [], [], []
+        for block in model.transformer.h:
+            p = model._block_params(block)
+            c, s, d = zip(*(self._take(w) for w in (p[1], p[2], p[4], p[5])))
+            self.codes.append(c); self.scales.append(s); self.dequantized.append(d)
+            self._params.append((p[0], d[0], d[1], p[3], d[2], d[3]))
+        self.head_codes, self.head_scales, self.head_dequantized = self._take(model.lm_head.weight)
+
+    def _take(self, param):
+        if param.dtype != torch.bfloat16:
+            raise ValueError(f"quantize_weights: the weights must be torch.bfloat16, got {param.dtype}: call model.to(torch.bfloat16)")
+        self._sources.append((param, param.data_ptr(), param._version))
+        with torch.no_grad():
+            codes, scales = w8quant.quantize_weight(param.detach())
+            return codes, scales, w8quant.dequantize_weight(codes, scales)
+
+    def check(self, model, what):
+        """ValueError in ``what``'s name unless this is ``model``'s snapshot and every source parameter is where and what it was"""
+        if model is not self.model:
+            raise ValueError(f"{what}: weights= is the snapshot of another model: call quantize_weights again on this one")
+        for p, ptr, version in self._sources:
+            if p.data_ptr() != ptr or p._version != version:
+                raise ValueError(f"{what}: a parameter was updated or moved since model.quantize_weights(): call quantize_weights again")
+
+    def block_params(self, index):
+        """block ``index``'s six parameters with the four matrices dequantised (the LayerNorm weights are the model's own)"""
+        return self._params[index]
+
+    def dequantized_model(self):
+        """A deep copy of the model whose four matrices per block and readout are the dequantised ones: the bf16 model that ``weights=``
+        computes, and the tests' yardstick.  Everything else (``wte``, the LayerNorm weights) is copied as it is."""
+        m = copy.deepcopy(self.model)
+        for p, src in zip(m.parameters(), self.model.parameters()):    # (a deep copy of a Parameter drops the muP tag set_base_shapes gave it)
+            if hasattr(src, "infshape") and not hasattr(p, "infshape"):
+                p.infshape = copy.deepcopy(src.infshape)
+        with torch.no_grad():
+            for block, d in zip(m.transformer.h, self.dequantized):
+                for w, dq in zip((block.attn.c_attn.weight, block.attn.c_proj.weight, block.mlp.c_fc.weight, block.mlp.c_proj.weight), d):
+                    w.copy_(dq)
+            m.lm_head.weight.copy_(self.head_dequantized)
+        return m
+
+
+def _checked_weights(model, what, weights):
+    """``weights=`` of a generation call: a QuantizedWeights of this model, still current (ValueError otherwise)"""
+    if not isinstance(weights, QuantizedWeights):
+        raise ValueError(f"{what}: weights must be what model.quantize_weights() returns, got {type(weights).__name__}")
+    weights.check(model, what)
+
+
+def _refuse_weights(what, weights, why):
+    """NotImplementedError in ``OmniBioTA.what``'s name when e4m3 weights are given: before anything is launched or any state changes"""
+    if weights is not None:
+        raise NotImplementedError(f"OmniBioTA.{what}: weights= (e4m3 weights, QuantizedWeights) {why}; they serve prefill, decode_step, generate and "
+                                  "DecodeLoop on a KVCache")
+
+
 class DecodeLoop:
     """The token loop of ``generate`` with its state on the device: ``model`` stepping a prefilled ``KVCache`` (bf16 or fp8) for up to
     ``max_steps`` tokens per row with no value passing through the host, so that one step is the same sequence of launches with the
@@ -1168,13 +1245,19 @@ class DecodeLoop:
     the first token's included (include/omnibiote_hip_constrain.h): the sampler gets the mask, ``eos_token`` as the held token and the
     loop's own ``n_new`` as the rows' emitted counts — addresses and constants, so a captured graph replays it.  Weights, cache
     buffers and tables are captured BY ADDRESS: in-place updates of the parameters are seen by the next replay, but ``model.to(...)``,
-    a reloaded parameter or a new cache leave the graph reading freed memory — build a new loop."""
+    a reloaded parameter or a new cache leave the graph reading freed memory — build a new loop.
 
-    def __init__(self, model, cache, *, max_steps, temperature=1.0, top_k=None, top_p=None, uniforms=None, eos_token=None, capture=False, allowed=None,
-                 hold_min=0):
+    ``weights`` (``model.quantize_weights()``): every block's step and the readout read the e4m3 codes (``QuantizedWeights``); a captured
+    graph holds the codes' and scales' addresses like every other.  The snapshot is checked here, in ``prefill``, ``start`` and ``run``."""
+
+    def __init__(self, model, cache, *, max_steps, temperature=1.0, top_k=None, top_p=None, uniforms=None, eos_token=None, capture=False, weights=None,
+                 allowed=None, hold_min=0):
         if isinstance(cache, SharedPrefixCache):
+            _refuse_weights("DecodeLoop", weights, "do not run on a shared-prefix cache (SharedPrefixCache)")
             raise ValueError("DecodeLoop: a SharedPrefixCache steps at a host suffix position, which changes every step: the device loop needs a KVCache")
         model._check_generation("DecodeLoop", cache.batch, cache)
+        if weights is not None:
+            _checked_weights(model, "DecodeLoop", weights)
         if int(max_steps) < 1:
             raise ValueError(f"DecodeLoop: max_steps must be at least 1, got {max_steps}")
         if temperature < 0:
@@ -1202,7 +1285,7 @@ class DecodeLoop:
         self.model, self.cache, self.max_steps, self.eos_token = model, cache, int(max_steps), eos_token
         self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
         self.uniforms = None if greedy else uniforms.contiguous()
-        self.allowed, self.hold_min = allowed, hold_min
+        self.allowed, self.hold_min, self.weights = allowed, hold_min, weights
         if cache.positions is None:
             cache.reset(cache.pos, positions=torch.full((b,), cache.pos, dtype=torch.int32, device=dev), min_pos=cache.pos)
         self.positions = cache.positions
@@ -1235,14 +1318,21 @@ class DecodeLoop:
         """one step; no host-dependent value in it: every argument is an address or a constant of the loop"""
         m, cache, x = self.model, self.cache, self.x
         bound = cache.max_len - 1
-        for block, kv in zip(m.transformer.h, cache.layers):
-            if cache.dtype == "fp8":
+        for i, (block, kv) in enumerate(zip(m.transformer.h, cache.layers)):
+            if self.weights is not None:
+                w = self.weights
+                ops.block_step_w8(x, w.block_params(i), (w.codes[i], w.scales[i]), block.attn.rope(), m.config.n_head, kv, cache.max_len, bound,
+                                  self.positions, kv8=cache.dtype == "fp8", ws=cache.decode_ws, out=x)
+            elif cache.dtype == "fp8":
                 ops.block_decode_kv8(x, m._block_params(block), block.attn.rope(), m.config.n_head, kv, cache.max_len, bound, self.positions,
                                      ws=cache.decode_ws, out=x)
             else:
                 ops.block_decode_rows(x, m._block_params(block), block.attn.rope(), m.config.n_head, kv, cache.max_len, self.positions, bound,
                                       ws=cache.decode_ws, out=x)
-        m._readout_rows(m.transformer.ln_f(x), out=self.logits)
+        if self.weights is not None:
+            m._readout_rows(m.transformer.ln_f(x), out=self.logits, weights=self.weights)
+        else:
+            m._readout_rows(m.transformer.ln_f(x), out=self.logits)
         self._sample_and_advance(1)
 
     def _capture(self):
@@ -1261,7 +1351,8 @@ class DecodeLoop:
         """``model.prefill(idx, cache, lengths)`` for a loop that is to run again on its cache: a prefill leaves new positions behind (a new
         tensor, or uniform mode), and this writes them into the loop's own tensor and hands that back to the cache.  Returns the logits
         for ``start``."""
-        logits = self.model.prefill(idx, self.cache, lengths=lengths)
+        logits = self.model.prefill(idx, self.cache, lengths=lengths) if self.weights is None else self.model.prefill(
+            idx, self.cache, lengths=lengths, weights=self.weights)
         c = self.cache
         if c.positions is None:
             self.positions.fill_(c.pos)
@@ -1279,6 +1370,8 @@ class DecodeLoop:
         if self.cache.positions is not self.positions:
             raise ValueError("DecodeLoop.start: cache.positions is no longer the tensor this loop was built on (an eager decode_step, extend, "
                              "rewind or model.prefill replaced it): prefill through loop.prefill, or build a new loop")
+        if self.weights is not None:
+            self.weights.check(self.model, "DecodeLoop.start")
         if prefill_logits.shape != self.logits.shape:
             raise ValueError(f"DecodeLoop.start: logits must be {tuple(self.logits.shape)}, got {tuple(prefill_logits.shape)}")
         self.logits.copy_(prefill_logits)
@@ -1297,6 +1390,8 @@ class DecodeLoop:
             raise ValueError("DecodeLoop.run: start the loop first")
         if self.cache.positions is not self.positions:
             raise ValueError("DecodeLoop.run: cache.positions is no longer the tensor this loop was built on: build a new loop")
+        if self.weights is not None:
+            self.weights.check(self.model, "DecodeLoop.run")
         k, poll = int(k), int(poll)
         if k < 0 or poll < 1:
             raise ValueError(f"DecodeLoop.run: k must not be negative and poll at least 1, got {k} and {poll}")
@@ -1440,17 +1535,33 @@ class OmniBioTA(nn.Module):
                                       "position at a time (prefill, decode_step, generate(num_samples=)); several new positions per row in one "
                                       "call need a KVCache")
 
-    def _readout_rows(self, x, out=None):
+    def quantize_weights(self):
+        """This model's four matrices per block and its readout as e4m3 codes with a power-of-two scale per output row, together with
+        their dequantised bf16 form: a ``QuantizedWeights`` for ``weights=`` of ``prefill``, ``decode_step``, ``generate`` and
+        ``DecodeLoop``.  Runs in plain torch on the parameters' device, once; a snapshot — after an optimizer step, a ``load_state_dict``
+        or a ``.to(...)`` call it again.  It holds 3 bytes per parameter beside the model's 2 (the bf16 copies serve the prompt and
+        batches above the weight-streaming product's row limit; dropping them is not built)."""
+        return QuantizedWeights(self)
+
+    def _readout_rows(self, x, out=None, weights=None):
         """The readout of a generation step's (B, C) rows: at most ops' small_m_max of them, bf16 on the GPU, through the
         weight-streaming product with MuReadout.forward's alpha; anything else through the module.  ``out``: a (B, vocab) buffer of the
-        caller's that takes the logits (a ``DecodeLoop``'s, whose address must not change)."""
+        caller's that takes the logits (a ``DecodeLoop``'s, whose address must not change).  ``weights``: the readout's e4m3 codes on
+        that product, the tile product on the dequantised readout above its row limit."""
+        if weights is not None:
+            _require_hip(x, "OmniBioTA")
+            alpha = float(self.lm_head.output_mult) / float(self.lm_head.width_mult())
+            if x.shape[0] <= L.lib().obte_small_m_max():
+                return ops.linear_small_m_w8(x, weights.head_codes, weights.head_scales, alpha=alpha, out=out)
+            y = ops.linear_fwd(x, weights.head_dequantized, alpha=alpha)
+            return y if out is None else out.copy_(y)
         w = self.lm_head.weight
         if x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.shape[0] <= L.lib().obte_small_m_max():
             return ops.linear_small_m(x, w, alpha=float(self.lm_head.output_mult) / float(self.lm_head.width_mult()), out=out)
         return self.lm_head(x) if out is None else out.copy_(self.lm_head(x))
 
     @torch.no_grad()
-    def prefill(self, idx, cache, lengths=None, chunk=None):
+    def prefill(self, idx, cache, lengths=None, chunk=None, weights=None):
         """The prompt ``idx`` (B, T0) through every block under the causal mask, its keys and values left in ``cache`` (started
         over: ``cache.pos = T0``); returns the logits of the last position, (B, vocab).  ln_f and the readout run on that row alone.
 
@@ -1463,9 +1574,15 @@ class OmniBioTA(nn.Module):
         ``chunk`` (an int >= 1; None or >= T0: the call above, bit for bit): the first ``chunk`` columns go through the prefill kernels,
         every further ``chunk`` of them through ``extend``'s block path at uniform positions (right padding stays harmless under the
         causal rule), each embedded on its own — the activation workspace is sized by the chunk, no (B, T0, C) tensor exists — and
-        row b's last hidden state is picked up in the chunk that holds it.  The cache ends in the same state."""
+        row b's last hidden state is picked up in the chunk that holds it.  The cache ends in the same state.
+
+        ``weights`` (``quantize_weights()``): the prompt runs through the same kernels on the DEQUANTISED weights, so that it and a
+        continuation by ``decode_step(weights=)`` see one model; the readout of the last position reads the e4m3 codes."""
         if isinstance(cache, SharedPrefixCache):
+            _refuse_weights("prefill", weights, "do not run on a shared-prefix cache (SharedPrefixCache)")
             return self._prefill_shared(idx, cache, lengths, chunk)
+        if weights is not None:
+            _checked_weights(self, "OmniBioTA.prefill", weights)
         if chunk is not None:
             self._refuse_fp8("prefill(chunk=)", cache)
         if idx.dim() != 2:
@@ -1484,18 +1601,23 @@ class OmniBioTA(nn.Module):
         if not idx.is_cuda:
             raise RuntimeError("OmniBioTA.prefill: idx must be on the GPU")
         if chunk is not None and int(chunk) < t:
-            return self._prefill_chunked(idx, cache, lens, int(chunk))
+            return self._prefill_chunked(idx, cache, lens, int(chunk), weights)
+        params = self._params_for(weights)
         mask = ops.MaskSpec.from_user(_autoregressive_mask(True, None, b, t, idx.device), b, t, self.config.n_head, idx.device)
         x = ops.embedding_fwd(idx.contiguous(), wte)
         ws = ops.block_infer_workspace(b, t, self.config.n_embd, self.config.n_head, idx.device)
         block_prefill = ops.block_prefill_kv8 if cache.dtype == "fp8" else ops.block_prefill
-        for block, kv in zip(self.transformer.h, cache.layers):
-            block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, kv, cache.max_len, ws=ws, out=x)
+        for i, (block, kv) in enumerate(zip(self.transformer.h, cache.layers)):
+            block_prefill(x, params(i, block), block.attn.rope(), self.config.n_head, mask, kv, cache.max_len, ws=ws, out=x)
         self._prefilled(cache, t, lens, idx.device)
         if lens is None:
-            return self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()))
+            return self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()), weights=weights)
         last = x[torch.arange(b, device=idx.device), (cache.positions - 1).long()]          # (B, C): row b at its own last position
-        return self._readout_rows(self.transformer.ln_f(last.contiguous()))
+        return self._readout_rows(self.transformer.ln_f(last.contiguous()), weights=weights)
+
+    def _params_for(self, weights):
+        """(index, block) -> the block's six parameters: the model's own, or with the four matrices dequantised from ``weights``"""
+        return (lambda i, block: self._block_params(block)) if weights is None else (lambda i, block: weights.block_params(i))
 
     def _prefill_shared(self, idx, cache, lengths, chunk):
         """``prefill`` on a ``SharedPrefixCache``: ``idx`` (P, T0), one row per prompt, through the same kernels into the prefix buffers;
@@ -1544,16 +1666,19 @@ class OmniBioTA(nn.Module):
             cache.extend_ws = torch.empty(need, dtype=torch.uint8, device=device)
         return cache.extend_ws
 
-    def _extend_hidden(self, tokens, cache, pos, pos_rows):
-        """``tokens`` (B, n) through every block against the cache at positions ``pos`` (or ``pos_rows``) on: the hidden states (B, n, C)"""
+    def _extend_hidden(self, tokens, cache, pos, pos_rows, weights=None):
+        """``tokens`` (B, n) through every block against the cache at positions ``pos`` (or ``pos_rows``) on: the hidden states (B, n, C).
+        ``weights``: on their dequantised matrices (a chunked prefill's later chunks)"""
         ws = self._extend_ws(cache, tokens.device, tokens.shape[1])
         x = ops.embedding_fwd(tokens.contiguous(), self.transformer.wte.weight)
-        for block, kv in zip(self.transformer.h, cache.layers):
-            ops.block_extend(x, self._block_params(block), block.attn.rope(), self.config.n_head, kv, cache.max_len, pos, pos_rows=pos_rows, ws=ws, out=x)
+        params = self._params_for(weights)
+        for i, (block, kv) in enumerate(zip(self.transformer.h, cache.layers)):
+            ops.block_extend(x, params(i, block), block.attn.rope(), self.config.n_head, kv, cache.max_len, pos, pos_rows=pos_rows, ws=ws, out=x)
         return x
 
-    def _prefill_chunked(self, idx, cache, lens, chunk):
+    def _prefill_chunked(self, idx, cache, lens, chunk, weights=None):
         b, t = idx.shape
+        params = self._params_for(weights)
         dev = idx.device
         # one buffer for every chunk size to come (the last chunk may be shorter and still ask for more bytes); it is at least the
         # prefill kernels' workspace for the first chunk's rows, so it serves them too
@@ -1566,24 +1691,26 @@ class OmniBioTA(nn.Module):
             if start == 0:
                 mask = ops.MaskSpec.from_user(_autoregressive_mask(True, None, b, n, dev), b, n, self.config.n_head, dev)
                 x = ops.embedding_fwd(part.contiguous(), self.transformer.wte.weight)
-                for block, kv in zip(self.transformer.h, cache.layers):
-                    ops.block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, kv, cache.max_len, ws=ws, out=x)
+                for i, (block, kv) in enumerate(zip(self.transformer.h, cache.layers)):
+                    ops.block_prefill(x, params(i, block), block.attn.rope(), self.config.n_head, mask, kv, cache.max_len, ws=ws, out=x)
             else:
-                x = self._extend_hidden(part, cache, start, None)
+                x = self._extend_hidden(part, cache, start, None, weights)
             rows = [r for r in range(b) if start <= last_at[r] < start + n]
             if rows:
                 rt = torch.tensor(rows, device=dev)
                 last[rt] = x[rt, torch.tensor([last_at[r] - start for r in rows], device=dev)]
         self._prefilled(cache, t, lens, dev)
-        return self._readout_rows(self.transformer.ln_f(last))
+        return self._readout_rows(self.transformer.ln_f(last), weights=weights)
 
     @torch.no_grad()
-    def extend(self, tokens, cache, logits="last"):
+    def extend(self, tokens, cache, logits="last", weights=None):
         """``tokens`` (B, n) int64: n new tokens per row in one call, row b's at positions ``cache.pos .. cache.pos + n - 1`` (after a
         prefill with ``lengths``: ``cache.positions[b] + j``, read on the device).  Their keys and values join the cache; position j's
         logits predict token j + 1.  Returns (B, vocab), the logits behind the last token, for ``logits="last"`` or (B, n, vocab) for
         ``"all"`` — what verifying a block of drafted tokens or scoring a continuation needs.  ``pos`` / ``positions`` advance
-        by n; parked rows stay parked.  n == 1 is ``decode_step``.  ``KVCache.rewind`` steps back over tokens that are not kept."""
+        by n; parked rows stay parked.  n == 1 is ``decode_step``.  ``KVCache.rewind`` steps back over tokens that are not kept.
+        ``weights`` must be None: there is no e4m3-weight form of several new positions per row (NotImplementedError)."""
+        _refuse_weights("extend", weights, "have no form for several new positions per row")
         self._refuse_fp8("extend", cache)
         self._refuse_shared("extend", cache)
         if tokens.dim() != 2:
@@ -1609,11 +1736,18 @@ class OmniBioTA(nn.Module):
         return self._readout_rows(self.transformer.ln_f(x.view(b * n, -1))).view(b, n, -1)
 
     @torch.no_grad()
-    def decode_step(self, tokens, cache):
+    def decode_step(self, tokens, cache, weights=None):
         """One new token per row, ``tokens`` (B,) int64, at position ``cache.pos`` of every row: its keys and values join the cache
         and the logits of the token after it come back, (B, vocab).  O(1) in projections, one read of the cache per layer.
         After a prefill with ``lengths`` row b's token goes to position ``cache.positions[b]``, read on the device; the positions of
-        the rows not parked (>= 0) then advance by one there, ``cache.pos`` on the host.  A parked row's logits mean nothing."""
+        the rows not parked (>= 0) then advance by one there, ``cache.pos`` on the host.  A parked row's logits mean nothing.
+
+        ``weights`` (``quantize_weights()``): every block's four products and the readout read e4m3 codes (``ops.block_step_w8``,
+        ``ops.linear_small_m_w8``) — half the weight bytes — and give, bit for bit, this step of ``weights.dequantized_model()``.  On a
+        ``KVCache`` of either dtype, uniform or per-row positions; not on a ``SharedPrefixCache`` (NotImplementedError)."""
+        if weights is not None:
+            _refuse_weights("decode_step", weights if isinstance(cache, SharedPrefixCache) else None, "do not run on a shared-prefix cache (SharedPrefixCache)")
+            _checked_weights(self, "OmniBioTA.decode_step", weights)
         if tokens.dim() != 1:
             raise ValueError(f"OmniBioTA.decode_step: tokens must be (B,), got {tuple(tokens.shape)}")
         b = tokens.shape[0]
@@ -1631,6 +1765,12 @@ class OmniBioTA(nn.Module):
                                         cache.n_prefix, suffix, cache.max_new, cache.pos - cache.n_prefix, ws=cache.decode_ws, out=x)
             cache.advance(1)
             return self._readout_rows(self.transformer.ln_f(x))
+        if weights is not None:    # one entry point for every form: (pos, pos_rows, the cache's dtype)
+            for i, (block, kv) in enumerate(zip(self.transformer.h, cache.layers)):
+                ops.block_step_w8(x, weights.block_params(i), (weights.codes[i], weights.scales[i]), block.attn.rope(), self.config.n_head, kv, cache.max_len,
+                                  cache.pos, cache.positions, kv8=cache.dtype == "fp8", ws=cache.decode_ws, out=x)
+            cache.advance(1)
+            return self._readout_rows(self.transformer.ln_f(x), weights=weights)
         # rows mode: every row at its own position, read on the device, with pos the host's bound on it
         if cache.dtype == "fp8":   # one entry point for both forms: (pos, pos_rows)
             step, at = ops.block_decode_kv8, (cache.pos, cache.positions)
@@ -1643,7 +1783,7 @@ class OmniBioTA(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None, lengths=None, pad_token=None, top_p=None,
-                 sampler="torch", kv_dtype="bf16", num_samples=None, loop=None, allowed_tokens=None, min_new_tokens=0):
+                 sampler="torch", kv_dtype="bf16", num_samples=None, loop=None, allowed_tokens=None, min_new_tokens=0, weights=None):
         """nanoGPT's generate(): ``idx`` (B, T0) int64 continued by up to ``max_new_tokens`` sampled tokens (``sample_next``); returns
         (B, T0 + n) int64.  The prompt runs once (``prefill``), every new token costs one ``decode_step``.  Where nanoGPT crops the
         context to block_size, this raises: T0 + max_new_tokens must fit.  ``eos_token``: a row that has produced it keeps producing
@@ -1680,7 +1820,14 @@ class OmniBioTA(nn.Module):
         if rows are to end.  The prompt and ``pad_token`` are not restricted.  ``min_new_tokens``: ``eos_token`` is excluded as well until a
         row has that many new tokens.  Both work with every sampler, cache and loop above; with neither given nothing changes.
         ValueError before anything is launched: an id outside [0, V), a row that allows nothing, ``min_new_tokens`` outside
-        [0, max_new_tokens] or without an ``eos_token``, a row that allows nothing but the held ``eos_token``."""
+        [0, max_new_tokens] or without an ``eos_token``, a row that allows nothing but the held ``eos_token``.
+
+        ``weights`` (``quantize_weights()``): the prompt runs on the dequantised weights and every new token's step reads the e4m3 codes:
+        the tokens are those of ``weights.dequantized_model().generate(...)`` with the same arguments.  With every sampler, ``lengths``,
+        ``kv_dtype``, ``eos_token``, ``allowed_tokens`` / ``min_new_tokens`` and ``loop``; not with ``num_samples`` (NotImplementedError)."""
+        if weights is not None:
+            _refuse_weights("generate", weights if num_samples is not None else None, "do not run on the shared-prefix cache of num_samples")
+            _checked_weights(self, "OmniBioTA.generate", weights)
         if sampler not in ("torch", "device"):
             raise ValueError(f"OmniBioTA.generate: sampler must be 'torch' or 'device', got {sampler!r}")
         if loop not in (None, "device", "graph"):
@@ -1707,7 +1854,7 @@ class OmniBioTA(nn.Module):
                                  idx.device)
         if lengths is not None:
             return self._generate_ragged(idx, _check_lengths("generate", lengths, b, t0), max_new_tokens, temperature, top_k, generator, eos_token,
-                                         pad_token, top_p, sampler, kv_dtype, loop, con)
+                                         pad_token, top_p, sampler, kv_dtype, loop, con, weights)
         if max_new_tokens < 0 or t0 + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {t0} prompt tokens + {max_new_tokens} new ones exceed block_size = {self.config.block_size}")
         if num_samples is None:
@@ -1719,10 +1866,11 @@ class OmniBioTA(nn.Module):
         cache = KVCache(self, b, t0 + max_new_tokens, dtype=kv_dtype) if num_samples is None else SharedPrefixCache(self, idx.shape[0], num_samples, t0,
                                                                                                                   max_new_tokens)
         out = [rows]
-        logits = self.prefill(idx, cache)
+        step = {} if weights is None else {"weights": weights}              # (weights=None: every call below is the call it was)
+        logits = self.prefill(idx, cache, **step)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
         if loop is not None:
-            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con)
+            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con, weights)
             if eos_token is not None:                                   # a finished row keeps producing EOS
                 live = torch.arange(tokens.shape[1], device=idx.device).view(1, -1) < n_new.view(-1, 1)
                 tokens = torch.where(live, tokens, torch.full_like(tokens, eos_token))
@@ -1737,20 +1885,20 @@ class OmniBioTA(nn.Module):
             out.append(nxt.unsqueeze(1))
             if i + 1 == max_new_tokens or (eos_token is not None and bool(done.all())):
                 break
-            logits = self.decode_step(nxt, cache)
+            logits = self.decode_step(nxt, cache, **step)
         return torch.cat(out, dim=1)
 
-    def _device_loop(self, cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con=None):
+    def _device_loop(self, cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con=None, weights=None):
         """``generate``'s token loop as a ``DecodeLoop`` behind the prefill that gave ``logits``: (tokens (B, S), n_new (B,))"""
         run = DecodeLoop(self, cache, max_steps=max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
-                         uniforms=us if isinstance(us, torch.Tensor) else None, eos_token=eos_token, capture=loop == "graph",
+                         uniforms=us if isinstance(us, torch.Tensor) else None, eos_token=eos_token, capture=loop == "graph", weights=weights,
                          allowed=None if con is None else con.packed, hold_min=0 if con is None else con.min_new)
         run.start(logits)
         run.run(max_new_tokens - 1)
         return run.result()
 
     def _generate_ragged(self, idx, lens, max_new_tokens, temperature, top_k, generator, eos_token, pad_token, top_p=None, sampler="torch", kv_dtype="bf16",
-                         loop=None, con=None):
+                         loop=None, con=None, weights=None):
         longest = max(lens)
         if max_new_tokens < 0 or longest + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {longest} prompt tokens (the longest row) + {max_new_tokens} new ones exceed "
@@ -1762,10 +1910,11 @@ class OmniBioTA(nn.Module):
             none = torch.zeros((b, 0), dtype=torch.int64, device=idx.device)
             return ragged_output(idx, lens, none, none.bool(), pad)
         cache = KVCache(self, b, longest + max_new_tokens, dtype=kv_dtype)
-        logits = self.prefill(idx, cache, lengths=lens)
+        step = {} if weights is None else {"weights": weights}
+        logits = self.prefill(idx, cache, lengths=lens, **step)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
         if loop is not None:
-            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con)
+            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con, weights)
             return ragged_output(idx, lens, tokens, torch.arange(tokens.shape[1], device=idx.device).view(1, -1) < n_new.view(-1, 1), pad)
         tokens, valid = [], []
         done = torch.zeros(b, dtype=torch.bool, device=idx.device)
@@ -1779,12 +1928,12 @@ class OmniBioTA(nn.Module):
                 break
             if eos_token is not None:                                   # park the finished rows: they store nothing and read nothing
                 cache.park(done)
-            logits = self.decode_step(nxt, cache)
+            logits = self.decode_step(nxt, cache, **step)
         return ragged_output(idx, lens, torch.stack(tokens, dim=1), torch.stack(valid, dim=1), pad)
 
     @torch.no_grad()
     def draft_and_verify(self, draft, pending, cache, draft_cache, k, uniforms=None, temperature=1.0, top_k=None, top_p=None, allowed=None, hold_token=None,
-                         emitted=None, min_emitted=0):
+                         emitted=None, min_emitted=0, weights=None, draft_weights=None):
         """One round of speculative decoding, everything but the step back.  ``pending`` (B,) int64 is every row's last emitted token,
         in neither cache yet; ``cache`` (this model's) and ``draft_cache`` (``draft``'s) stand at the same per-row positions.  The draft
         runs k ``decode_step``s, drawing x_0 .. x_{k-1} with ``ops.sample_logits`` from its logits q_0 .. q_{k-1}, and one more that
@@ -1797,7 +1946,10 @@ class OmniBioTA(nn.Module):
         ``allowed`` (a packed mask, uint8 (n,) or (B, n) on the device), ``hold_token``, ``emitted`` (B,) int32 — what every row has emitted,
         the pending token included — and ``min_emitted`` restrict the draft's draws and the verification alike
         (include/omnibiote_hip_constrain.h): the draft's j-th draw and the verification's position j hold ``hold_token`` while
-        ``emitted[b] + j < min_emitted``.  With none given the round runs the unrestricted entry points."""
+        ``emitted[b] + j < min_emitted``.  With none given the round runs the unrestricted entry points.  ``weights`` / ``draft_weights``
+        must be None: e4m3 weights are not built for either model of a round (NotImplementedError)."""
+        _refuse_weights("draft_and_verify", weights if weights is not None else draft_weights,
+                        "are not built for speculative decoding, for the target (several new positions per row) or the draft")
         self._refuse_fp8("draft_and_verify", cache)         # (the draft only takes decode steps: its cache may be either)
         self._refuse_shared("draft_and_verify", cache)
         b = pending.shape[0]
@@ -1828,7 +1980,8 @@ class OmniBioTA(nn.Module):
 
     @torch.no_grad()
     def generate_speculative(self, idx, max_new_tokens, draft, k=4, temperature=1.0, top_k=None, top_p=None, generator=None, eos_token=None,
-                             lengths=None, pad_token=None, return_stats=False, kv_dtype="bf16", num_samples=None, allowed_tokens=None, min_new_tokens=0):
+                             lengths=None, pad_token=None, return_stats=False, kv_dtype="bf16", num_samples=None, allowed_tokens=None, min_new_tokens=0,
+                             weights=None, draft_weights=None):
         """``generate`` by draft and verify: ``draft`` — any autoregressive OmniBioTA on the same device with the same vocabulary, a smaller
         model in practice, this model itself for a self-check — proposes ``k`` tokens per round (1 <= k <= 31), this model scores them in
         one ``extend`` and ``ops.spec_verify`` keeps a prefix of them and adds one token of its own, so that every emitted token is
@@ -1849,8 +2002,11 @@ class OmniBioTA(nn.Module):
 
         ``allowed_tokens`` and ``min_new_tokens`` as in ``generate``: the draft's draws and the verification take the same mask and the same
         held ``eos_token``, so the emitted tokens are distributed as this model's own restricted sampling; the rows' emitted counts reach
-        the device once per round, behind the round's host synchronisation."""
+        the device once per round, behind the round's host synchronisation.  ``weights`` / ``draft_weights`` must be None: e4m3 weights
+        are not built for either model (NotImplementedError)."""
         what = "generate_speculative"
+        _refuse_weights(what, weights if weights is not None else draft_weights,
+                        "are not built for speculative decoding, for the target (several new positions per row) or the draft")
         if num_samples is not None:
             raise NotImplementedError(f"OmniBioTA.{what}: num_samples: verifying a drafted block attends from several new positions per row, which "
                                       "is not built over a shared-prefix cache (SharedPrefixCache); repeat the prompts instead")

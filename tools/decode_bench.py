@@ -58,6 +58,17 @@ loop without an eos_token (no host read at all).  Also the one-time cost of buil
 one step before and after, counted in captured graphs of their own.  One JSON line per (B, ctx).
 
     python tools/decode_bench.py --graph [--constrained] [--rounds 5] [--steps 300]
+
+--w8: the decode step's weights as e4m3 (model.quantize_weights(), include/omnibiote_hip_w8.h) against bf16, both alternating in one process over
+the same windows and rounds.  (a) the product alone, obte_linear_small_m_w8 against obte_linear_small_m_bf16 on preallocated buffers: the four
+block shapes and the readout at widths C = 1024 and 2048, M = 1, 8, 64, each call on the next of enough distinct copies of the weight that
+BOTH sets exceed the 256 MB Infinity Cache (`served_from` says so); each format's weight bytes over its time as a share of 6.3 TB/s, and the
+byte ratio (K + 4) / (2 K).  `kernel` says which of the two kernels a shape takes.  One JSON line per (C, shape).  (b) decode_step with and
+without weights= on the small (8 layers, 1024 wide) and the large (24 layers, 2048 wide) config at B x ctx in {1, 8, 64} x 2048 (cache contents:
+random values, only the time is read), and the captured DecodeLoop at B = 1.  One JSON line per (config, B).  --w8-part products|small|large
+runs one part.
+
+    python tools/decode_bench.py --w8 [--w8-part products] [--rounds 5] [--steps 300]
 """
 import argparse
 import contextlib
@@ -92,9 +103,9 @@ def timed(fn, n):
     return e0.elapsed_time(e1) / n * 1e3
 
 
-def build(block_size, dev, n_layer=8):
+def build(block_size, dev, n_layer=8, n_embd=1024, n_head=8, on_device=False):
     """the small config as an autoregressive model, muP base shapes set as the trainer sets them (train_encoder.build_model); ``n_layer``
-    other than its 8: the same width with fewer layers (spec_bench.py's draft)"""
+    other than its 8: the same width with fewer layers (spec_bench.py's draft); ``n_embd`` / ``n_head``: another width (--w8's large config)"""
     import warnings
     from omnibiote_amd.model import OmniBioTA, OmniBioTAConfig
     from omnibiote_amd.mup_compat import set_base_shapes
@@ -107,7 +118,8 @@ def build(block_size, dev, n_layer=8):
     torch.manual_seed(0)
     with contextlib.redirect_stdout(io.StringIO()), warnings.catch_warnings():
         warnings.simplefilter("ignore")          # "Casting complex values to real": the reference's cos-only RoPE regime
-        m = make(1024, 8)
+        with torch.device(dev if on_device else "cpu"):   # (on_device: a billion parameters are initialised where they will live)
+            m = make(n_embd, n_head)
         set_base_shapes(m, make(24, 3), delta=make(48, 12))
         m.to(torch.bfloat16)
     return m.to(dev).eval()
@@ -575,6 +587,140 @@ def graph_compare(m, B, ctx, rounds, steps, dev, constrained=False):
     return out
 
 
+W8_ROWS = (1, 8, 64)
+
+
+def w8_products(C_, rounds, steps, dev):
+    """obte_linear_small_m_w8 against obte_linear_small_m_bf16 alone at width C_, every call on the next distinct copy of the weight"""
+    import ctypes as C
+    from omnibiote_amd import _lib, w8quant
+    lib, stream = _lib.lib(), torch.cuda.current_stream().cuda_stream
+    gen = torch.Generator(device=dev).manual_seed(5)
+    for name, N, K in (("c_attn", 3 * C_, C_), ("proj", C_, C_), ("fc", 4 * C_, C_), ("mlp", C_, 4 * C_), ("readout", 65536, C_)):
+        copies = -(-(INFINITY_CACHE * 5 // 4) // (N * K))               # the e4m3 set, the smaller one, is 1.25 Infinity Caches
+        w = torch.randn(N, K, device=dev, generator=gen).mul_(0.02).to(torch.bfloat16)
+        codes, scales = w8quant.quantize_weight(w)
+        ws = [w] + [w.clone() for _ in range(copies - 1)]
+        cs = [codes] + [codes.clone() for _ in range(copies - 1)]
+        ss = [scales] + [scales.clone() for _ in range(copies - 1)]
+        strips, ch = -(-N // 16), K // 256 if K % 256 == 0 else 0
+        out = {"width": C_, "product": name, "N": N, "K": K, "weight_copies": copies,
+               "kernel": "x-stationary" if strips > 512 and ch in (1, 2, 4) else "one strip per workgroup",
+               "set_bytes": {"bf16": copies * N * K * 2, "e4m3": copies * N * (K + 4)},
+               "served_from": "HBM" if copies * N * K > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)",
+               "byte_ratio": round((K + 4) / (2 * K), 4), "M": {}}
+        for M in W8_ROWS:
+            x = torch.randn(M, K, device=dev, generator=gen).to(torch.bfloat16)
+            d = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+            args = [_lib.GemmArgs(x.data_ptr(), wi.data_ptr(), d.data_ptr(), None, None, M, N, K, K, K, N, 1, 1, _lib.EPI_NONE, 1.0, 0.0, 0, 0) for wi in ws]
+            state = {"i": 0}
+
+            def bf16():
+                state["i"] += 1
+                rc = lib.obte_linear_small_m_bf16(C.byref(args[state["i"] % copies]), stream)
+                if rc != 0:
+                    _lib.check(rc, "obte_linear_small_m_bf16")
+
+            def e4m3():
+                state["i"] += 1
+                i = state["i"] % copies
+                rc = lib.obte_linear_small_m_w8(C.byref(args[i]), cs[i].data_ptr(), K, ss[i].data_ptr(), stream)
+                if rc != 0:
+                    _lib.check(rc, "obte_linear_small_m_w8")
+            legs = {"bf16": bf16, "e4m3": e4m3}
+            for fn in legs.values():
+                for _ in range(8):
+                    fn()
+            us = {k: [] for k in legs}
+            for r in range(rounds):
+                for leg in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+                    us[leg].append(timed(legs[leg], steps))
+            med = {k: statistics.median(v) for k, v in us.items()}
+            out["M"][str(M)] = {"us": {k: summary(v) for k, v in us.items()}, "e4m3_over_bf16": round(med["e4m3"] / med["bf16"], 3),
+                                "gap_us_and_spreads": [round(med["bf16"] - med["e4m3"], 2)] + [round(max(v) - min(v), 2) for v in us.values()],
+                                "share_of_6.3TBps": {"bf16": round(N * K * 2 / (med["bf16"] * 1e-6) / HBM_RATE, 3),
+                                                     "e4m3": round(N * (K + 4) / (med["e4m3"] * 1e-6) / HBM_RATE, 3)}}
+        print(json.dumps(out), flush=True)
+        del ws, cs, ss, w, codes, scales
+        torch.cuda.empty_cache()
+
+
+def w8_tokens(m, wq, config, B, ctx, rounds, steps, dev, graph=False):
+    """decode_step with and without weights=, alternating; ``graph``: also the captured DecodeLoop both ways"""
+    from omnibiote_amd.model import DecodeLoop, KVCache
+    g = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    last = torch.randint(4, m.config.vocab_size, (B,), device=dev, generator=g)
+    cache = KVCache(m, B, ctx)
+    for kv in cache.layers:                                           # finite values of the keys' size: only the time is read
+        kv.normal_()
+
+    def step(weights):
+        def fn():                    # the same position every time: the context stays ctx long
+            cache.reset(ctx - 1)
+            if weights is None:
+                m.decode_step(last, cache)
+            else:
+                m.decode_step(last, cache, weights=weights)
+        return fn
+    legs = {"bf16": step(None), "e4m3": step(wq)}
+    for fn in legs.values():
+        for _ in range(3):
+            fn()
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for leg in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            us[leg].append(timed(legs[leg], steps))
+    med = {k: statistics.median(v) for k, v in us.items()}
+    out = {"config": config, "B": B, "context": ctx, "windows": {"decode_steps": steps, "rounds": rounds},
+           "decode_step_us": {k: summary(v, 1) for k, v in us.items()}, "e4m3_over_bf16": round(med["e4m3"] / med["bf16"], 3),
+           "gap_us_and_spreads": [round(med["bf16"] - med["e4m3"], 1)] + [round(max(v) - min(v), 1) for v in us.values()]}
+    if graph:
+        first = ctx - 1 - steps
+        idx = torch.randint(4, m.config.vocab_size, (B, first), device=dev, generator=g)
+        runs = {}
+        for k, w in (("bf16", None), ("e4m3", wq)):
+            c = KVCache(m, B, ctx)
+            extra = {} if w is None else {"weights": w}
+            logits = m.prefill(idx, c, lengths=[first] * B, **extra)
+            runs[k] = (c, logits, DecodeLoop(m, c, max_steps=steps + 1, capture=True, **extra))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+        def window(k):
+            c, logits, loop = runs[k]
+            loop.positions.fill_(first)
+            c.reset(first, loop.positions, first)
+            loop.start(logits)
+            torch.cuda.synchronize()
+            e0.record()
+            loop.run(steps)
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) / steps * 1e3
+        for k in runs:
+            window(k)
+        gus = {k: [] for k in runs}
+        for r in range(rounds):
+            for k in (list(runs) if r % 2 == 0 else list(runs)[::-1]):
+                gus[k].append(window(k))
+        out["graph_loop_us_per_token"] = {k: summary(v, 1) for k, v in gus.items()}
+        out["graph_loop_e4m3_over_bf16"] = round(statistics.median(gus["e4m3"]) / statistics.median(gus["bf16"]), 3)
+    return out
+
+
+def w8_deviation(m, wq, dev, B=2, T0=20, steps=6):
+    """what e4m3 weights do to the logits of this (randomly initialised) model: max |logit(weights=) - logit(bf16)| over a few steps"""
+    from omnibiote_amd.model import KVCache
+    idx = torch.randint(4, m.config.vocab_size, (B, T0), device=dev, generator=torch.Generator(device=dev).manual_seed(9))
+    ca, cb = KVCache(m, B, T0 + steps), KVCache(m, B, T0 + steps)
+    la, lb = m.prefill(idx, ca, weights=wq), m.prefill(idx, cb)
+    worst, size = 0.0, 0.0
+    for _ in range(steps):
+        worst, size = max(worst, (la.float() - lb.float()).abs().max().item()), max(size, lb.float().abs().max().item())
+        tok = lb.float().argmax(-1)
+        la, lb = m.decode_step(tok, ca, weights=wq), m.decode_step(tok, cb)
+    return {"max_abs_logit_deviation": round(worst, 4), "max_abs_logit": round(size, 4)}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batches", default=None, help="default 1,8,64 (--ragged: 8,64)")
@@ -585,6 +731,8 @@ def main():
     p.add_argument("--shared", action="store_true", help="G samples of one prompt: the shared-prefix cache against the replicated cache")
     p.add_argument("--graph", action="store_true", help="the device-resident token loop, eager and captured, against today's host-driven loop")
     p.add_argument("--constrained", action="store_true", help="with --graph: also the captured loop under per-row token masks and a minimum length")
+    p.add_argument("--w8", action="store_true", help="e4m3 weights against bf16: the product alone, decode_step on the small and the large config")
+    p.add_argument("--w8-part", default="products,small,large", help="with --w8: which parts run")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300, help="decode steps (and attention calls) per timed window")
     p.add_argument("--baseline_ms", type=float, default=400.0, help="the full forward's window: as many calls as fit, at least 3")
@@ -592,6 +740,23 @@ def main():
     a = p.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
+    if a.w8:
+        parts = a.w8_part.split(",")
+        if "products" in parts:
+            for C_ in (1024, 2048):
+                w8_products(C_, a.rounds, a.steps, dev)
+        for config, kw in (("small", dict(n_layer=8, n_embd=1024, n_head=8)), ("large", dict(n_layer=24, n_embd=2048, n_head=16, on_device=True))):
+            if config not in parts:
+                continue
+            m = build(2048, dev, **kw)
+            wq = m.quantize_weights()
+            print(json.dumps({"config": config, **w8_deviation(m, wq, dev)}), flush=True)
+            for B in (1, 8, 64):
+                print(json.dumps(w8_tokens(m, wq, config, B, 2048, a.rounds, a.steps, dev, graph=B == 1)), flush=True)
+                torch.cuda.empty_cache()
+            del m, wq
+            torch.cuda.empty_cache()
+        return
     if a.graph:
         shapes = tuple((int(b), int(c)) for b in (a.batches or "1,8,64").split(",") for c in (a.contexts or "2048").split(","))
         m = build(max(c for _, c in shapes), dev)
