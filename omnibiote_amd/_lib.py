@@ -250,6 +250,15 @@ SYMBOLS_W8 = {
                                      C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
 }
 
+# sequence scoring, the readout fused with its log-softmax (include/omnibiote_hip_score.h): a table of its own as well
+READOUT_SCORE_MAX_SLICES, READOUT_SCORE_MAX_K = 64, 64
+SYMBOLS_SCORE = {
+    "obte_readout_score_slices": (C.c_int32, [C.c_int64, C.c_int64]),
+    "obte_readout_score_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "obte_readout_score_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -280,7 +289,7 @@ def lib():
             for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
                                             + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
                                             + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
-                                            + list(SYMBOLS_W8.items())):
+                                            + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -30,7 +30,7 @@ import copy
 import warnings
 import weakref
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -1419,6 +1419,14 @@ class DecodeLoop:
         return self.out[:, :width].clone(), self.n_new.clone()
 
 
+class SequenceScore(NamedTuple):
+    """What ``OmniBioTA.score`` returns: log p of every next token (B, T - 1) fp32 (0 behind a row's length), the row sums (B,) fp32 and
+    the number of scored tokens per row (B,) int64."""
+    token_logprobs: torch.Tensor
+    total: torch.Tensor
+    count: torch.Tensor
+
+
 class OmniBioTA(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -1507,6 +1515,71 @@ class OmniBioTA(nn.Module):
         elif method == "max":
             return emb.max(dim=1)[0]
         return emb
+
+    # ---- scoring (beyond the reference): log-probabilities without a logits tensor -------------------------------------------------------
+    @torch.no_grad()
+    def token_logprobs(self, idx, rows, candidates, attn_mask=None):
+        """log p(candidate) under the model at listed positions, fp32: ``rows`` int64 (n,), ascending flat positions of the (b*t) batch
+        as in ``forward(rows=)``; ``candidates`` int64 or int32 (n, K) — K token ids per position, 1 <= K <= 64, or -1 for "none", which
+        gives 0 — or (n,), which returns (n,).  Any model: for an encoder the caller places the MASK id in ``idx`` itself (a variant-effect
+        score is then the difference of two entries of one row); for an autoregressive one position t scores token t + 1.
+        ``forward(idx, attn_mask, return_embeddings=True, rows=rows)`` and then ``ops.readout_score`` with the readout's alpha: the last
+        block's MLP half and ln_f run on the listed rows alone, and no (n, vocab) logits exist.  The values are those of
+        ``log_softmax(model(idx, rows=rows).float())`` at the candidates, up to the fp32 summation order.  No gradient, and no dropout
+        whatever ``self.training`` says."""
+        if not torch.is_tensor(candidates) or candidates.dtype not in (torch.int64, torch.int32) or candidates.dim() not in (1, 2):
+            raise ValueError("OmniBioTA.token_logprobs: candidates must be an int64 or int32 tensor of shape (n,) or (n, K)")
+        if not torch.is_tensor(rows) or rows.dim() != 1 or candidates.shape[0] != rows.numel():
+            raise ValueError("OmniBioTA.token_logprobs: rows must be 1-D with one entry per row of candidates")
+        if candidates.dim() == 2 and not 1 <= candidates.shape[1] <= L.READOUT_SCORE_MAX_K:
+            raise ValueError(f"OmniBioTA.token_logprobs: 1 <= K <= {L.READOUT_SCORE_MAX_K} candidates per position, got {candidates.shape[1]}")
+        modes = [(m, m.training) for m in self.modules()]
+        try:
+            self.eval()
+            emb = self.forward(idx, attn_mask, return_embeddings=True, rows=rows)
+        finally:
+            for m, was in modes:
+                m.training = was
+        alpha = float(self.lm_head.output_mult) / float(self.lm_head.width_mult())
+        return ops.readout_score(emb, self.lm_head.weight, candidates, alpha=alpha)[0]
+
+    @torch.no_grad()
+    def score(self, idx, lengths=None):
+        """The model's log-likelihood of the sequences ``idx`` (B, T) int64, T >= 2, autoregressive models only.  Returns a
+        ``SequenceScore``: ``token_logprobs`` fp32 (B, T - 1) with entry [b, t] = log p(idx[b, t + 1] | idx[b, :t + 1]), ``total`` fp32
+        (B,) its row sums, ``count`` int64 (B,) the number of scored tokens, so that ``-total.sum() / count.sum()`` is the mean
+        next-token loss.  ``lengths`` (a host sequence of B ints, 2 <= len_b <= T; None: all T): rows of different lengths, right-padded;
+        entries at t + 1 >= lengths[b] are 0 and count is lengths - 1.  Under the causal mask padding cannot reach a real position.
+        Only the sum(lengths - 1) real positions go through the last block's MLP half, ln_f and the readout (``token_logprobs``), and no
+        logits tensor exists.  ``score(model.generate(...))`` is the model's own log-likelihood of its samples at temperature 1 and
+        without truncation (no top_k, top_p or allowed_tokens), whatever they were drawn with; a ragged ``generate`` returns the
+        ``lengths`` to pass.  No gradient and no dropout."""
+        if not torch.is_tensor(idx) or idx.dim() != 2:
+            raise ValueError("OmniBioTA.score: idx must be a (B, T) tensor")
+        b, t = idx.shape
+        self._check_generation("score", b)
+        if t < 2:
+            raise ValueError(f"OmniBioTA.score: nothing to score in sequences of length {t}: T >= 2")
+        lens = [t] * b if lengths is None else _check_lengths("score", lengths, b, t)
+        if min(lens) < 2:
+            raise ValueError(f"OmniBioTA.score: every length must lie in [2, T = {t}], got {lens}")
+        dev = idx.device
+        if min(lens) == t:                                                              # every (b, t): nothing to work out on the host
+            at = torch.arange(b * (t - 1), device=dev)
+            count = torch.full((b,), t - 1, dtype=torch.int64, device=dev)
+        else:
+            def up(h):   # from pinned memory, so that the copy does not make the host wait for the stream
+                return h.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else h.to(dev)
+            count = torch.tensor(lens, dtype=torch.int64) - 1
+            real = torch.arange(t - 1).view(1, -1) < count.view(-1, 1)                   # host: which (b, t) have a real token t + 1
+            at = up(real.flatten().nonzero().flatten())                                 # into (B, T - 1), ascending
+            count = up(count)
+        rows = at // (t - 1) * t + at % (t - 1)                                          # the same positions in (B, T)
+        lp = self.token_logprobs(idx, rows, idx[:, 1:].reshape(-1).index_select(0, at))
+        out = torch.zeros(b * (t - 1), dtype=torch.float32, device=dev)
+        out.index_copy_(0, at, lp)
+        out = out.view(b, t - 1)
+        return SequenceScore(out, out.sum(dim=1), count)
 
     # ---- generation (beyond the reference, whose model.py strikes nanoGPT's generate() out) -----------------------------------------
     # Dropout is never applied on these paths, whatever ``training`` says: a sample is drawn from the model, not from a thinned one.

@@ -856,6 +856,62 @@ def next_token_loss(logits, idx):
     return _NextTokenLossFn.apply(logits.contiguous(), targets, rows)
 
 
+def readout_score_workspace(R: int, V: int, slices: int = 0, device=None) -> torch.Tensor:
+    """The workspace of ``readout_score`` for R rows over V columns: one (max, sum) pair per row and slice, 8 R slices bytes."""
+    n = L.lib().obte_readout_score_ws_bytes(R, V, slices)
+    if n < 0:
+        raise ValueError(f"readout_score_workspace: R >= 1, 1 <= V < 2^31 and 0 <= slices <= {L.READOUT_SCORE_MAX_SLICES}, got R={R} V={V} slices={slices}")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def readout_score(x, w, targets, alpha=1.0, slices=0, ws=None):
+    """Log-probabilities under the readout without its logits (obte_readout_score_bf16): x bf16 (R, C), w bf16 (V, C) — both may be
+    row-strided views with stride 1 along C — and targets int64 or int32 (R, K) or (R,), 1 <= K <= 64.  With
+    z = bf16(alpha x w^T), the logits ``linear_fwd(x, w, alpha=alpha)`` would write, returns fp32 ``(logprobs, lse, logits_at)``:
+    lse (R,) = logsumexp(z) over the V columns, logits_at = z at the targets, logprobs = logits_at - lse, the latter two shaped like
+    ``targets``.  A target of -1 gives 0 in both; any other value outside [0, V) gives NaN in both.  Nothing of R V elements is
+    allocated: ``ws`` (``readout_score_workspace``; None: allocated here) is 8 R slices bytes, ``slices`` = 0 lets the library pick the
+    split over V.  Bitwise repeatable; at a fixed ``slices`` a row's results do not depend on the other rows."""
+    _need(x, "x", contiguous=False); _need(w, "w", contiguous=False)
+    if not isinstance(targets, torch.Tensor):
+        raise TypeError("targets: expected a tensor")
+    if not targets.is_cuda:
+        raise RuntimeError(f"targets: the OmniBioTE HIP path runs on MI355X only; got a {targets.device} tensor (there is no CPU fallback)")
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1] or x.shape[0] < 1 or w.shape[0] < 1:
+        raise ValueError(f"readout_score: x (R, C) and w (V, C), got {tuple(x.shape)} and {tuple(w.shape)}")
+    R, Cc = x.shape
+    V = w.shape[0]
+    if x.stride(1) != 1 or w.stride(1) != 1:
+        raise ValueError("readout_score: x and w must have stride 1 along C")
+    if targets.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"readout_score: targets must be int64 or int32, got {targets.dtype}")
+    if targets.dim() not in (1, 2) or targets.shape[0] != R or (targets.dim() == 2 and not 1 <= targets.shape[1] <= L.READOUT_SCORE_MAX_K):
+        raise ValueError(f"readout_score: targets must be ({R},) or ({R}, K) with 1 <= K <= {L.READOUT_SCORE_MAX_K}, got {tuple(targets.shape)}")
+    if Cc % 64 != 0 or Cc < 64:
+        raise ValueError(f"readout_score: C must be a multiple of 64, got {Cc}")
+    if isinstance(slices, bool) or not isinstance(slices, int) or not 0 <= slices <= L.READOUT_SCORE_MAX_SLICES:
+        raise ValueError(f"readout_score: slices must be an integer in [0, {L.READOUT_SCORE_MAX_SLICES}], got {slices!r}")
+    K = 1 if targets.dim() == 1 else targets.shape[1]
+    ldx = x.stride(0) if R > 1 else Cc
+    ldw = w.stride(0) if V > 1 else Cc
+    need = L.lib().obte_readout_score_ws_bytes(R, V, slices)
+    if ws is None:
+        ws = torch.empty(max(need, 0), dtype=torch.uint8, device=x.device)
+    else:
+        _need(ws, "ws", dtype=None)
+        if ws.numel() * ws.element_size() < need:
+            raise ValueError(f"readout_score: ws holds {ws.numel() * ws.element_size()} bytes, {need} are needed")
+    tg = targets.to(torch.int32).contiguous()      # (token ids fit: V < 2^31; an id beyond int32 is out of range either way)
+    if targets.dtype == torch.int64:
+        tg = torch.where((targets < -1) | (targets >= V), torch.full_like(tg, -2), tg).contiguous()
+    logprobs = torch.empty(targets.shape, dtype=torch.float32, device=x.device)
+    logits_at = torch.empty(targets.shape, dtype=torch.float32, device=x.device)
+    lse = torch.empty(R, dtype=torch.float32, device=x.device)
+    L.check(L.lib().obte_readout_score_bf16(_ptr(x), ldx, _ptr(w), ldw, R, V, Cc, float(alpha), _ptr(tg), K, _ptr(logprobs), _ptr(lse), _ptr(logits_at),
+                                            slices, _ptr(ws), ws.numel() * ws.element_size(), _stream()), "obte_readout_score_bf16")
+    return logprobs, lse, logits_at
+
+
 def adamw_step_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, clip_coef=None):
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _need(t, n)
