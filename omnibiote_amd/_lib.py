@@ -259,6 +259,20 @@ SYMBOLS_SCORE = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
 }
 
+# encoder infilling, the draw fused into the readout and the unmasking loop's bookkeeping (include/omnibiote_hip_fill.h): a table of its
+# own as well
+SITE_FILL = 8                                      # OBTE_SITE_FILL: the noise rule's site constant
+FILL_CONFIDENCE, FILL_RANDOM, FILL_LEFT = 0, 1, 2  # OBTE_FILL_*
+FILL_MAX_SEG = 8192                                # the most entries per sequence obte_fill_commit takes
+SYMBOLS_FILL = {
+    "obte_readout_sample_slices": (C.c_int32, [C.c_int64, C.c_int64]),
+    "obte_readout_sample_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "obte_readout_sample_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_uint64,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_fill_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64,
+                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -289,7 +303,7 @@ def lib():
             for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
                                             + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
                                             + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
-                                            + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items())):
+                                            + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -285,6 +285,6 @@ static inline DropCfg make_drop(float p, uint64_t seed, uint32_t site) {
     c.scale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
     return c;
 }
-enum { OBTE_SITE_EMBED = 0, OBTE_SITE_ATTN = 1, OBTE_SITE_RESID = 2, OBTE_SITE_MLP = 3, OBTE_SITE_USER = 7 };
+enum { OBTE_SITE_EMBED = 0, OBTE_SITE_ATTN = 1, OBTE_SITE_RESID = 2, OBTE_SITE_MLP = 3, OBTE_SITE_USER = 7, OBTE_SITE_FILL = 8 };
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -1581,6 +1581,136 @@ class OmniBioTA(nn.Module):
         out = out.view(b, t - 1)
         return SequenceScore(out, out.sum(dim=1), count)
 
+    # ---- infilling (beyond the reference): tokens drawn at listed positions without a logits tensor ------------------------------------
+    def _check_draw(self, what, idx, temperature, seed, allowed_tokens):
+        """The arguments ``sample_tokens`` and ``infill`` share, checked on the host before any device work: returns
+        ``(seed, allowed)`` with a drawn seed for None and ``allowed`` None or a bool (V,) tensor on the CPU."""
+        from .sampling import inv_temperature
+        who = f"OmniBioTA.{what}"
+        if not torch.is_tensor(idx) or idx.dim() != 2 or idx.dtype != torch.int64 or idx.numel() == 0:
+            raise ValueError(f"{who}: idx must be a non-empty (B, T) int64 tensor")
+        if idx.shape[1] > self.config.block_size:
+            raise ValueError(f"{who}: sequences of length {idx.shape[1]}, the block size is {self.config.block_size}")
+        try:
+            inv_temperature(temperature)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{who}: {e}") from None
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64):
+            raise ValueError(f"{who}: seed must be None or an integer in [0, 2^64), got {seed!r}")
+        V = self.config.vocab_size
+        allowed = None
+        if allowed_tokens is not None:
+            a = torch.as_tensor(allowed_tokens).detach().cpu()
+            if a.numel() == 0:
+                raise ValueError(f"{who}: allowed_tokens is empty: there is nothing to draw")
+            if a.dtype == torch.bool:
+                if a.shape != (V,):
+                    raise ValueError(f"{who}: a bool allowed_tokens must be ({V},), one set for all rows, got {tuple(a.shape)}")
+                allowed = a.clone()
+            else:
+                if a.dim() != 1 or a.dtype not in (torch.int64, torch.int32) or (a.numel() and (int(a.min()) < 0 or int(a.max()) >= V)):
+                    raise ValueError(f"{who}: allowed_tokens must be a bool ({V},) mask or a 1-D list of token ids in [0, {V})")
+                allowed = torch.zeros(V, dtype=torch.bool)
+                allowed[a.long()] = True
+            if not bool(allowed.any()):
+                raise ValueError(f"{who}: allowed_tokens is empty: there is nothing to draw")
+        return (_new_seed() if seed is None else seed), allowed
+
+    def _draw_rows(self, idx, rows, temperature, seed, allowed_packed, attn_mask):
+        """(tokens, logprob, lse) at ``rows``: the forward on those rows alone, then the fused readout + draw with keys = rows"""
+        emb = self.forward(idx, attn_mask, return_embeddings=True, rows=rows)
+        alpha = float(self.lm_head.output_mult) / float(self.lm_head.width_mult())
+        return ops.readout_sample(emb, self.lm_head.weight, temperature, seed, keys=rows, allowed_packed=allowed_packed, alpha=alpha)
+
+    @torch.no_grad()
+    def sample_tokens(self, idx, rows, temperature=1.0, seed=None, allowed_tokens=None, attn_mask=None):
+        """One token drawn from the model's distribution at each listed position: ``rows`` int64 (n,), ascending flat positions of the
+        (b*t) batch as in ``forward(rows=)``.  Returns ``(tokens (n,) int64, logprobs (n,) fp32)``: the log-probability each token was
+        drawn with, at ``temperature`` and over ``allowed_tokens`` (None, token ids, or a bool (V,) mask: one non-empty set for all rows;
+        the distribution is renormalised over it).  ``temperature`` 0: the most likely allowed token, its log-probability at temperature 1.
+        Any model; ``token_logprobs``' conventions: for an encoder the caller places the MASK id in ``idx`` itself, no gradient, no dropout
+        whatever ``self.training`` says.  ``forward(idx, attn_mask, return_embeddings=True, rows=rows)`` and then ``ops.readout_sample`` with
+        the readout's alpha and keys = rows: no (n, vocab) logits exist, and a position's draw depends on the seed, its flat position and
+        its logits alone.  ``seed`` None draws one from torch's generator."""
+        seed, allowed = self._check_draw("sample_tokens", idx, temperature, seed, allowed_tokens)
+        if not torch.is_tensor(rows) or rows.dim() != 1 or rows.dtype != torch.int64 or rows.numel() == 0 or rows.numel() > idx.numel():
+            raise ValueError("OmniBioTA.sample_tokens: rows must be a non-empty 1-D int64 tensor of positions of the batch")
+        packed = None if allowed is None else ops.pack_token_mask(allowed.to(idx.device))
+        modes = [(m, m.training) for m in self.modules()]
+        try:
+            self.eval()
+            tokens, logprob, _ = self._draw_rows(idx, rows, temperature, seed, packed, attn_mask)
+        finally:
+            for m, was in modes:
+                m.training = was
+        return tokens, logprob
+
+    @torch.no_grad()
+    def infill(self, idx, masked, steps=1, temperature=1.0, order="confidence", seed=None, allowed_tokens=None, mask_token=2, attn_mask=None):
+        """Fill the positions ``masked`` (bool (B, T)) of ``idx`` (B, T) int64 with tokens drawn from the model, unmasking over ``steps``
+        iterations (mask-predict).  Returns ``(out (B, T) int64, logprobs (B, T) fp32)``: ``idx`` with every masked position filled, and
+        the log-probability — at ``temperature``, over ``allowed_tokens`` — each token was drawn with in the context of its iteration; 0 at
+        positions that were not masked.  ``idx`` is copied and ``mask_token`` written at the masked positions.  Iteration s runs the
+        forward on the still-masked rows, draws a token at each (``ops.readout_sample``, keys = the flat positions, the seed of
+        ``sampling.fill_iteration_seed(seed, s)``) and commits ``sampling.fill_schedule(m_b, steps)[s]`` of sequence b's — by ``order``:
+        "confidence" (largest log-probability first), "random", or "left" (lowest position first); the rest stay masked and are drawn
+        again.  ``steps`` 1 draws all positions independently at once; ``steps`` >= the largest masked count unmasks one position per
+        sequence and iteration.  ``masked`` is read on the host once, up front (the schedule and every iteration's offsets); the loop
+        itself reads nothing back.  At most 8192 masked positions per sequence.  ``allowed_tokens``, ``seed``, ``attn_mask``, modes and
+        gradients as ``sample_tokens``."""
+        from .sampling import fill_iteration_seed, fill_schedule
+        seed, allowed = self._check_draw("infill", idx, temperature, seed, allowed_tokens)
+        who = "OmniBioTA.infill"
+        if not torch.is_tensor(masked) or masked.dtype != torch.bool or masked.shape != idx.shape:
+            raise ValueError(f"{who}: masked must be a bool tensor of idx's shape {tuple(idx.shape)}")
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"{who}: steps must be an integer >= 1, got {steps!r}")
+        if order not in ops.FILL_ORDERS:
+            raise ValueError(f"{who}: order must be one of {tuple(ops.FILL_ORDERS)}, got {order!r}")
+        if isinstance(mask_token, bool) or not isinstance(mask_token, int) or not 0 <= mask_token < self.config.vocab_size:
+            raise ValueError(f"{who}: mask_token must be a token id in [0, {self.config.vocab_size}), got {mask_token!r}")
+        B, T = idx.shape
+        held = masked.detach().cpu()                                                      # the one host read
+        counts = held.sum(dim=1).tolist()
+        if sum(counts) == 0:
+            raise ValueError(f"{who}: nothing is masked")
+        if max(counts) > L.FILL_MAX_SEG:
+            raise ValueError(f"{who}: at most {L.FILL_MAX_SEG} masked positions per sequence, got {max(counts)}")
+        # every iteration's takes and offsets, from the counts alone
+        per_seq = [fill_schedule(m, steps) for m in counts]
+        takes, offs, rem = [], [], list(counts)
+        for s in range(steps):
+            if sum(rem) == 0:
+                break
+            offs.append([sum(rem[:b]) for b in range(B + 1)])
+            takes.append([per_seq[b][s] for b in range(B)])
+            rem = [rem[b] - takes[-1][b] for b in range(B)]
+        offs.append([0] * (B + 1))
+        dev = idx.device
+        _require_hip(self.transformer.wte.weight, "OmniBioTA")
+        if not idx.is_cuda:
+            raise RuntimeError("OmniBioTA.infill: idx must be on the GPU")
+
+        def up(h):
+            return h.pin_memory().to(dev, non_blocking=True)
+        take_d, off_d = up(torch.tensor(takes, dtype=torch.int32)), up(torch.tensor(offs, dtype=torch.int32))
+        rows = up(held.flatten().nonzero().flatten())
+        out = idx.clone().masked_fill_(up(held), mask_token)
+        logprobs = torch.zeros(B, T, dtype=torch.float32, device=dev)
+        packed = None if allowed is None else ops.pack_token_mask(up(allowed))
+        modes = [(m, m.training) for m in self.modules()]
+        try:
+            self.eval()
+            for s in range(len(takes)):
+                tokens, logprob, _ = self._draw_rows(out, rows, temperature, fill_iteration_seed(seed, s), packed, attn_mask)
+                rows_next = torch.empty(offs[s + 1][B], dtype=torch.int64, device=dev)
+                ops.fill_commit(rows, off_d[s], tokens, logprob, take_d[s], order, seed, out, logprobs, rows_next, off_d[s + 1], max(counts))
+                rows = rows_next
+        finally:
+            for m, was in modes:
+                m.training = was
+        return out, logprobs
+
     # ---- generation (beyond the reference, whose model.py strikes nanoGPT's generate() out) -----------------------------------------
     # Dropout is never applied on these paths, whatever ``training`` says: a sample is drawn from the model, not from a thinned one.
     def _block_params(self, block):

@@ -912,6 +912,112 @@ def readout_score(x, w, targets, alpha=1.0, slices=0, ws=None):
     return logprobs, lse, logits_at
 
 
+def readout_sample_workspace(R: int, V: int, slices: int = 0, device=None) -> torch.Tensor:
+    """The workspace of ``readout_sample`` for R rows over V columns: a (max, sum) pair and a best triple per row and slice, 20 R slices bytes."""
+    n = L.lib().obte_readout_sample_ws_bytes(R, V, slices)
+    if n < 0:
+        raise ValueError(f"readout_sample_workspace: R >= 1, 1 <= V < 2^31 and 0 <= slices <= {L.READOUT_SCORE_MAX_SLICES}, got R={R} V={V} slices={slices}")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _seed64(what, seed):
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{what}: seed must be an integer in [0, 2^64), got {seed!r}")
+    return seed
+
+
+def readout_sample(x, w, temperature, seed, keys=None, allowed=None, allowed_packed=None, alpha=1.0, slices=0, ws=None):
+    """One token per row drawn from the readout's distribution without its logits (obte_readout_sample_bf16; the rule:
+    include/omnibiote_hip_fill.h, in float64 sampling.readout_sample_reference): x bf16 (R, C), w bf16 (V, C), both possibly row-strided.
+    With z = bf16(alpha x w^T) and y = z fp32(1 / temperature), returns ``(tokens int64 (R,), logprob fp32 (R,), lse fp32 (R,))``:
+    the token is argmax_v y[v] + g[v] with the counter-based Gumbel noise g of (``seed``, the row's key, v) — a draw from softmax(y) —
+    logprob its log-probability and lse = logsumexp(y).  ``keys`` int64 (R,) on the device (None: the row numbers): a row's draw depends
+    on its key, its logits and the seed alone, not on R, ``slices`` or its place in the batch.  ``temperature`` 0: the lowest index of
+    the maximum, lse and logprob as at temperature 1.  ``allowed`` bool (V,) or (R, V), or ``allowed_packed`` uint8 (n,) or (R, n) as
+    ``pack_token_mask`` makes it: an excluded column enters neither the sum nor the draw; a row that allows nothing gets -1, -inf, -inf.
+    Nothing of R V elements is allocated: ``ws`` (``readout_sample_workspace``; None: allocated here) is 20 R slices bytes."""
+    from .sampling import inv_temperature
+    _need(x, "x", contiguous=False); _need(w, "w", contiguous=False)
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1] or x.shape[0] < 1 or w.shape[0] < 1:
+        raise ValueError(f"readout_sample: x (R, C) and w (V, C), got {tuple(x.shape)} and {tuple(w.shape)}")
+    R, Cc = x.shape
+    V = w.shape[0]
+    if x.stride(1) != 1 or w.stride(1) != 1:
+        raise ValueError("readout_sample: x and w must have stride 1 along C")
+    if Cc % 64 != 0 or Cc < 64:
+        raise ValueError(f"readout_sample: C must be a multiple of 64, got {Cc}")
+    if isinstance(slices, bool) or not isinstance(slices, int) or not 0 <= slices <= L.READOUT_SCORE_MAX_SLICES:
+        raise ValueError(f"readout_sample: slices must be an integer in [0, {L.READOUT_SCORE_MAX_SLICES}], got {slices!r}")
+    try:
+        inv_temp = inv_temperature(temperature)
+    except ValueError as e:
+        raise ValueError(f"readout_sample: {e}") from None
+    seed = _seed64("readout_sample", seed)
+    if keys is not None:
+        _need(keys, "keys", torch.int64)
+        if keys.shape != (R,):
+            raise ValueError(f"readout_sample: keys must be int64 ({R},), got {tuple(keys.shape)}")
+    con = _constraint("readout_sample", R, V, x.device, allowed, allowed_packed, None, None, 0)
+    mask, mask_ld = (None, 0) if con is None else (con[0], con[1])
+    ldx = x.stride(0) if R > 1 else Cc
+    ldw = w.stride(0) if V > 1 else Cc
+    need = L.lib().obte_readout_sample_ws_bytes(R, V, slices)
+    if ws is None:
+        ws = torch.empty(max(need, 0), dtype=torch.uint8, device=x.device)
+    else:
+        _need(ws, "ws", dtype=None)
+        if ws.numel() * ws.element_size() < need:
+            raise ValueError(f"readout_sample: ws holds {ws.numel() * ws.element_size()} bytes, {need} are needed")
+    tokens = torch.empty(R, dtype=torch.int32, device=x.device)
+    logprob = torch.empty(R, dtype=torch.float32, device=x.device)
+    lse = torch.empty(R, dtype=torch.float32, device=x.device)
+    L.check(L.lib().obte_readout_sample_bf16(_ptr(x), ldx, _ptr(w), ldw, R, V, Cc, float(alpha), inv_temp, seed, _ptr(keys), _ptr(mask), mask_ld,
+                                             _ptr(tokens), _ptr(logprob), _ptr(lse), slices, _ptr(ws), ws.numel() * ws.element_size(), _stream()),
+            "obte_readout_sample_bf16")
+    return tokens.long(), logprob, lse
+
+
+FILL_ORDERS = {"confidence": L.FILL_CONFIDENCE, "random": L.FILL_RANDOM, "left": L.FILL_LEFT}
+
+
+def fill_commit(rows, seg_off, tokens, logprob, take, order, seed, idx, out_logprob, rows_next, seg_off_next, max_seg):
+    """An unmasking iteration's bookkeeping in one launch and in place (obte_fill_commit; the rule: include/omnibiote_hip_fill.h, in plain
+    torch sampling.fill_commit_reference).  ``rows`` int64 (n,) ascending flat positions, sequence b's entries the run
+    [seg_off[b], seg_off[b + 1]) (``seg_off`` int32 (B + 1,) on the device; ``max_seg`` <= 8192: the host's bound on a run);
+    ``tokens`` int64 or int32 (n,) and ``logprob`` fp32 (n,) belong to the entries.  ``take`` int32 (B,) of each sequence's entries are
+    selected by ``order`` ("confidence", "random" under ``seed``, "left"): their tokens go to ``idx`` (int64, any shape, contiguous) and
+    their logprobs to ``out_logprob`` (fp32, as many elements) at the entries' positions; the other positions go, ascending, to
+    ``rows_next`` (int64) at ``seg_off_next[b]`` (int32 (B + 1,)).  Returns nothing."""
+    if order not in FILL_ORDERS:
+        raise ValueError(f"fill_commit: order must be one of {tuple(FILL_ORDERS)}, got {order!r}")
+    seed = _seed64("fill_commit", seed)
+    for t, name, dt in ((rows, "rows", torch.int64), (seg_off, "seg_off", torch.int32), (logprob, "logprob", torch.float32), (take, "take", torch.int32),
+                        (idx, "idx", torch.int64), (out_logprob, "out_logprob", torch.float32), (rows_next, "rows_next", torch.int64),
+                        (seg_off_next, "seg_off_next", torch.int32)):
+        _need(t, name, dt)
+    _need(tokens, "tokens", None)
+    if tokens.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"fill_commit: tokens must be int64 or int32, got {tokens.dtype}")
+    n, B = rows.numel(), take.numel()
+    if rows.dim() != 1 or tokens.shape != (n,) or logprob.shape != (n,):
+        raise ValueError(f"fill_commit: rows, tokens and logprob must be (n,), got {tuple(rows.shape)}, {tuple(tokens.shape)} and {tuple(logprob.shape)}")
+    if B < 1 or take.dim() != 1 or seg_off.shape != (B + 1,) or seg_off_next.shape != (B + 1,):
+        raise ValueError(f"fill_commit: take (B,), seg_off and seg_off_next (B + 1,), got {tuple(take.shape)}, {tuple(seg_off.shape)} and "
+                         f"{tuple(seg_off_next.shape)}")
+    if idx.numel() < 1 or out_logprob.numel() != idx.numel():
+        raise ValueError(f"fill_commit: idx and out_logprob must hold the same number (>= 1) of elements, got {idx.numel()} and {out_logprob.numel()}")
+    if isinstance(max_seg, bool) or not isinstance(max_seg, int) or not 0 <= max_seg <= L.FILL_MAX_SEG:
+        raise ValueError(f"fill_commit: max_seg must be an integer in [0, {L.FILL_MAX_SEG}] (entries per sequence), got {max_seg!r}")
+    if rows_next.dim() != 1 or (n > 0 and rows_next.data_ptr() == rows.data_ptr()):
+        raise ValueError("fill_commit: rows_next must be a 1-D buffer of its own")
+    tk = tokens if tokens.dtype == torch.int32 else tokens.to(torch.int32)
+    pad = torch.empty(2, dtype=torch.int64, device=idx.device)    # an empty tensor has no address: the C call wants non-null, distinct pointers
+    one, two = pad[:1], pad[1:]
+    L.check(L.lib().obte_fill_commit(_ptr(rows if n else one), _ptr(seg_off), n, B, max_seg, _ptr(tk if n else one), _ptr(logprob if n else one), _ptr(take),
+                                     FILL_ORDERS[order], seed, _ptr(idx), _ptr(out_logprob), idx.numel(), _ptr(rows_next if rows_next.numel() else two),
+                                     _ptr(seg_off_next), rows_next.numel(), _stream()), "obte_fill_commit")
+
+
 def adamw_step_(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, clip_coef=None):
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _need(t, n)

@@ -252,3 +252,149 @@ def advance_reference(sampled, pos, count, out, n_new, token, wte, us=None, eos=
     x = wte[new_token.clamp(0, wte.shape[0] - 1)]
     u = None if us is None else us[(count.long() + 1).clamp(0, us.shape[0] - 1), rows]
     return p, count + 1, new_out, new_n, new_token, x, u
+
+
+# ---------------------------------------------------------------------------------------------------------------- encoder infilling
+# The rules of include/omnibiote_hip_fill.h in plain torch, in float64: the counter-based Gumbel noise, the draw fused into the readout
+# (obte_readout_sample_bf16), the unmasking schedule and the loop's bookkeeping (obte_fill_commit).
+SITE_FILL = 8            # OBTE_SITE_FILL
+GUMBEL_EPS = 2.0 ** -15  # how far the kernel's fp32 perturbed value y + g may lie from the float64 rule's, for |y| <= 128
+_M32 = 0xFFFFFFFF
+
+
+def _hash32(x):
+    """csrc/common.h's obte_hash32 on an int64 tensor of 32-bit values (int64 products wrap mod 2^64: the low 32 bits are right)"""
+    x = x & _M32
+    x = x ^ (x >> 16)
+    x = (x * 0x7FEB352D) & _M32
+    x = x ^ (x >> 15)
+    x = (x * 0x846CA68B) & _M32
+    return x ^ (x >> 16)
+
+
+def _rowkey(keys, seed, site=SITE_FILL):
+    """drop_rowkey(key, make_drop(0, seed, site)): int64 keys of any shape -> 32-bit values as int64"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    s0 = (seed & _M32) ^ ((site * 0x632BE5AB) & _M32)
+    s1 = ((seed >> 32) + site * 0x9E3779B9) & _M32
+    k = torch.as_tensor(keys, dtype=torch.int64)
+    lo, hi = k & _M32, (k >> 32) & _M32
+    return _hash32((_hash32(lo ^ s0) + ((hi * 0x9E3779B1) & _M32) + s1) & _M32)
+
+
+def gumbel_of_hash(h):
+    """g = -ln(-ln(1 - w)), w = (h + 0.5) 2^-32, float64, for 32-bit values h (an int64 tensor).  1 - w = (2^32 - h - 0.5) 2^-32 is exact
+    in float64, so this is the rule to the last bits of two float64 logarithms; finite for every h: |g| < 23."""
+    h = torch.as_tensor(h, dtype=torch.int64)
+    u = ((1 << 32) - h).double() - 0.5                         # exact: below 2^53
+    return -torch.log(-torch.log(u * 2.0 ** -32))
+
+
+def gumbel_noise(seed, keys, V):
+    """(n, V) float64: the noise of columns 0 .. V - 1 for the rows with the int64 ``keys`` (n,) under ``seed``:
+    g[i, v] = gumbel_of_hash(obte_hash32(rowkey(keys[i]) ^ v))."""
+    k = torch.as_tensor(keys, dtype=torch.int64)
+    if k.dim() != 1 or V < 1:
+        raise ValueError(f"gumbel_noise: keys must be (n,) and V >= 1, got {tuple(k.shape)} and {V}")
+    col = torch.arange(V, dtype=torch.int64, device=k.device)
+    return gumbel_of_hash(_hash32(_rowkey(k, seed).unsqueeze(1) ^ col.unsqueeze(0)))
+
+
+def inv_temperature(temperature):
+    """The fp32 number the kernel multiplies the logits by, as a Python float: fp32(1 / temperature); 0 for temperature 0 (greedy)"""
+    t = float(temperature)
+    if not t >= 0 or t == float("inf"):
+        raise ValueError(f"temperature must be finite and not negative, got {temperature}")
+    if t == 0:
+        return 0.0
+    it = float(torch.tensor(1.0 / t, dtype=torch.float64).to(torch.float32))
+    if it == float("inf"):
+        raise ValueError(f"temperature {temperature} is too small: 1 / temperature overflows fp32")
+    return it
+
+
+def readout_sample_reference(x, w, temperature, seed, keys=None, allowed=None, alpha=1.0):
+    """(tokens int64 (R,), logprob (R,), lse (R,), perturbed (R, V), y (R, V)), the last four float64: the rule of
+    obte_readout_sample_bf16.  z = bf16(alpha x w^T) from the float64 product (the kernel's z when its fp32 sum is exact),
+    y = z inv_temperature(temperature), -inf where ``allowed`` (bool (V,) or (R, V)) is False; perturbed = y + gumbel_noise(seed, keys);
+    token = the first index of the maximum of perturbed, lse = logsumexp(y), logprob = y[token] - lse.  temperature 0: no noise, the
+    first index of the maximum of z over the allowed columns, lse and logprob at temperature 1.  A row with no finite allowed y:
+    token -1, logprob -inf.  ``keys`` None: the row numbers."""
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"readout_sample_reference: x (R, C) and w (V, C), got {tuple(x.shape)} and {tuple(w.shape)}")
+    r, v = x.shape[0], w.shape[0]
+    it = inv_temperature(temperature)
+    z = (float(alpha) * (x.double() @ w.double().t())).to(torch.bfloat16).double()
+    y = constrain_reference(z * (it if it > 0 else 1.0), allowed)
+    if it > 0:
+        k = torch.arange(r, dtype=torch.int64) if keys is None else torch.as_tensor(keys, dtype=torch.int64)
+        if k.shape != (r,):
+            raise ValueError(f"readout_sample_reference: keys must be ({r},), got {tuple(k.shape)}")
+        pert = y + gumbel_noise(seed, k.to(y.device), v)
+    else:
+        pert = y.clone()
+    best = pert.max(dim=1, keepdim=True).values
+    col = torch.arange(v, device=y.device).unsqueeze(0)
+    some = torch.isfinite(best.squeeze(1))
+    token = torch.where(pert == best, col, v).min(dim=1).values
+    token = torch.where(some, token, torch.full_like(token, -1))
+    lse = torch.logsumexp(y, dim=1)
+    ninf = torch.full_like(lse, float("-inf"))
+    logprob = torch.where(some, y.gather(1, token.clamp(min=0).unsqueeze(1)).squeeze(1) - torch.where(some, lse, torch.zeros_like(lse)), ninf)
+    return token, logprob, torch.where(some, lse, ninf), pert, y
+
+
+def fill_schedule(m, steps):
+    """How many of ``m`` masked positions each of ``steps`` iterations commits: with rem left and steps - s iterations to go, iteration s
+    takes ceil(rem / (steps - s)).  The list sums to m and never increases; steps > m: one per iteration, then nothing."""
+    if isinstance(m, bool) or isinstance(steps, bool) or not isinstance(m, int) or not isinstance(steps, int) or m < 0 or steps < 1:
+        raise ValueError(f"fill_schedule: m >= 0 and steps >= 1 integers, got {m!r} and {steps!r}")
+    out, rem = [], m
+    for s in range(steps):
+        k = -(-rem // (steps - s))
+        out.append(k)
+        rem -= k
+    return out
+
+
+def fill_iteration_seed(seed, s):
+    """The seed of iteration ``s`` of an unmasking loop run under ``seed``: (seed + s 0x9E3779B97F4A7C15) mod 2^64"""
+    return (int(seed) + int(s) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+
+FILL_ORDERS = ("confidence", "random", "left")
+
+
+def fill_commit_reference(rows, seg_off, tokens, logprob, take, order, seed, idx, out_logprob, seg_off_next, rows_next=None):
+    """obte_fill_commit in plain torch on any device; nothing is changed in place.  ``rows`` int64 (n,) ascending flat positions, sequence
+    b's entries the run [seg_off[b], seg_off[b + 1]); ``tokens`` and ``logprob`` (n,) belong to them; ``take`` (B,) of each sequence's
+    entries are selected — ``order`` "confidence": larger logprob first, NaN as -inf; "random": smaller drop_rowkey(position) under
+    ``seed`` first; "left": lowest position first; equal ranks to the lower position — and written through to copies of ``idx`` (flat
+    int64) and ``out_logprob`` (flat fp32); the other positions go, ascending, to ``rows_next`` at seg_off_next[b].  take[b] outside
+    [0, n_b]: nothing selected.  Returns (idx, out_logprob, rows_next); rows_next starts as the argument's copy, or -1 everywhere in
+    seg_off_next[-1] entries."""
+    if order not in FILL_ORDERS:
+        raise ValueError(f"fill_commit_reference: order must be one of {FILL_ORDERS}, got {order!r}")
+    so, sn, tk = [int(v) for v in seg_off], [int(v) for v in seg_off_next], [int(v) for v in take]
+    idx, out_logprob = idx.clone(), out_logprob.clone()
+    nxt = torch.full((sn[-1],), -1, dtype=torch.int64, device=rows.device) if rows_next is None else rows_next.clone()
+    for b in range(len(tk)):
+        lo, hi = so[b], so[b + 1]
+        nb = hi - lo
+        k = tk[b] if 0 <= tk[b] <= nb else 0
+        pos = rows[lo:hi]
+        if order == "confidence":
+            lp = logprob[lo:hi].double()
+            key = -torch.where(torch.isnan(lp), torch.full_like(lp, float("-inf")), lp)
+        elif order == "random":
+            key = _rowkey(pos.cpu(), seed).to(rows.device)
+        else:
+            key = torch.zeros(nb, dtype=torch.int64, device=rows.device)
+        first = torch.sort(key, stable=True).indices[:k]                      # stable: equal ranks to the lower position
+        sel = torch.zeros(nb, dtype=torch.bool, device=rows.device)
+        sel[first] = True
+        idx[pos[sel]] = tokens[lo:hi][sel].to(idx.dtype)
+        out_logprob[pos[sel]] = logprob[lo:hi][sel].to(out_logprob.dtype)
+        rest = pos[~sel]
+        nxt[sn[b]:sn[b] + rest.numel()] = rest
+    return idx, out_logprob, nxt
