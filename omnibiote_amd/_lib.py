@@ -273,6 +273,15 @@ SYMBOLS_FILL = {
                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
 }
 
+# the sampler with repetition, presence and frequency penalties (include/omnibiote_hip_penalty.h): a table of its own as well
+PENALTY_MAX_GEN, PENALTY_MAX_PROMPT = 32767, 2 ** 24 - 1   # the largest gen_max and prompt_max the call takes
+SYMBOLS_PENALTY = {
+    "obte_sample_logits_penalized_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_int32, C.c_float,
+                                                    C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -303,7 +312,7 @@ def lib():
             for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
                                             + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
                                             + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
-                                            + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items())):
+                                            + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items()) + list(SYMBOLS_PENALTY.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -11,6 +11,7 @@
 #include "../../include/omnibiote_hip_extend.h"
 #include "../../include/omnibiote_hip_spec.h"
 #include "../../include/omnibiote_hip_constrain.h"
+#include "../../include/omnibiote_hip_penalty.h"
 #include "../../include/omnibiote_hip_kv8.h"
 #include "../../include/omnibiote_hip_shared.h"
 #include "../../include/omnibiote_hip_w8.h"

@@ -96,10 +96,9 @@ __device__ __forceinline__ uint32_t sp_mask_byte(const SpRowMask& m, int c, int 
     return bits;
 }
 // sp_load_chunk under such a byte: the bits take the place of the test "column < V" (a bit field extract and an AND per key where the
-// plain load has a compare and a select), so a restricted row costs the plain load's instructions plus a few per chunk
-__device__ __forceinline__ void sp_load_chunk_masked(const bf16* x, int c, int nch, int V, uint32_t bits, uint32_t (&k)[4]) {
-    u32x4 raw = {0u, 0u, 0u, 0u};
-    if (c < nch) raw = *reinterpret_cast<const u32x4*>(x + (int64_t)c * 8);
+// plain load has a compare and a select), so a restricted row costs the plain load's instructions plus a few per chunk.  The packing
+// is a function of its own: the penalised load rewrites the 16 bytes between the load and it.
+__device__ __forceinline__ void sp_pack_chunk_masked(const u32x4& raw, int c, int V, uint32_t bits, uint32_t (&k)[4]) {
     const int nv = V - c * 8;   // columns of this group inside the row (<= 0: none)
     const uint32_t in = bits & (nv >= 8 ? 0xFFu : nv <= 0 ? 0u : (1u << nv) - 1u);
 #pragma unroll
@@ -108,6 +107,11 @@ __device__ __forceinline__ void sp_load_chunk_masked(const bf16* x, int c, int n
         const uint32_t hi = sp_key(raw[q] >> 16) & (uint32_t)(-(int32_t)((in >> (2 * q + 1)) & 1u));
         k[q] = lo | (hi << 16);
     }
+}
+__device__ __forceinline__ void sp_load_chunk_masked(const bf16* x, int c, int nch, int V, uint32_t bits, uint32_t (&k)[4]) {
+    u32x4 raw = {0u, 0u, 0u, 0u};
+    if (c < nch) raw = *reinterpret_cast<const u32x4*>(x + (int64_t)c * 8);
+    sp_pack_chunk_masked(raw, c, V, bits, k);
 }
 // is column t (inside [0, V)) of the row excluded?
 __device__ __forceinline__ bool sp_excluded(const SpRowMask& m, int t) {
@@ -145,6 +149,103 @@ __device__ __forceinline__ void sp_load_row_masked(const bf16* x, int chunk0, in
         const int c = chunk0 + j * 64;
         if ((m.hold >> 3) == c) bits[j] &= ~(1u << (m.hold & 7));   // (hold = -1: chunk -1, never)
         sp_load_chunk_masked(x, c, nch, V, bits[j], k[j]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(k[j][q]));
+    }
+}
+
+// ---- a penalised row (include/omnibiote_hip_penalty.h): the columns of the row's history are rewritten at load time, nothing after the
+// load changes.  The workgroup first counts the history into a table in LDS, one 16-bit entry per column (two per 32-bit word): bit 15
+// = "in the prompt", bits 0..14 = how often the column was generated (<= gen_max <= 32767: a count never reaches bit 15).  The sums
+// are integers, so the table does not depend on the order the LDS atomics arrive in.
+struct SpPenalty {             // a call's penalties, as the host hands them over (a NULL list has the bound 0)
+    const int64_t* prompt;
+    int64_t prompt_ld;
+    const int32_t* prompt_len; // or NULL: every row holds prompt_max
+    const int64_t* gen;
+    int64_t gen_ld;
+    const int32_t* n_gen;      // or NULL: 0
+    int64_t n_gen_all;
+    int32_t prompt_max, gen_max;
+    float repetition, inv_repetition, presence, frequency;
+};
+// clamp(n + add, 0, hi), the sum in 64 bits: it cannot overflow, whatever the count holds
+__device__ __forceinline__ int sp_count(const int32_t* n, int64_t b, int64_t add, int32_t hi) {
+    const int64_t v = (n ? (int64_t)n[b] : 0) + add;
+    return (int)(v < 0 ? 0 : v > (int64_t)hi ? (int64_t)hi : v);
+}
+// Row b's history into `table` (16 nch bytes, 16-byte aligned): cleared, a barrier, the two lists walked NT entries at a time (ids outside
+// [0, V) are skipped: no index is formed from them), a barrier.  Exactly the row's prompt_len_b and n_gen_b entries are read.
+template <int NT>
+__device__ __forceinline__ void sp_history_table(const SpPenalty& pen, int64_t b, int V, uint32_t* table) {
+    const int tid = threadIdx.x, nch = (V + 7) >> 3;
+    const int np = pen.prompt_max > 0 ? sp_count(pen.prompt_len, b, pen.prompt_len ? 0 : pen.prompt_max, pen.prompt_max) : 0;
+    const int ng = pen.gen_max > 0 ? sp_count(pen.n_gen, b, pen.n_gen_all, pen.gen_max) : 0;
+    const int64_t* prompt = pen.prompt + b * pen.prompt_ld;
+    const int64_t* gen = pen.gen + b * pen.gen_ld;
+    // the first NT ids of both lists are fetched ahead of the clear: one memory round trip under it instead of two behind it
+    int64_t tp = tid < np ? prompt[tid] : -1, tg = tid < ng ? gen[tid] : -1;
+    const u32x4 zero = {0u, 0u, 0u, 0u};
+    for (int c = tid; c < nch; c += NT) reinterpret_cast<u32x4*>(table)[c] = zero;
+    __syncthreads();
+    for (int i = tid; i < np; i += NT) {
+        if (i != tid) tp = prompt[i];
+        if ((u64)tp < (u64)V) atomicOr(&table[tp >> 1], 0x8000u << (16 * ((int)tp & 1)));
+    }
+    for (int i = tid; i < ng; i += NT) {
+        if (i != tid) tg = gen[i];
+        if ((u64)tg < (u64)V) atomicAdd(&table[tg >> 1], 1u << (16 * ((int)tg & 1)));
+    }
+    __syncthreads();
+}
+// the bf16 bits b of a column whose table entry e is not 0, penalised: every operation rounded to fp32 on its own, then to bf16 (nearest even)
+__device__ __forceinline__ uint32_t sp_penalize(uint32_t b, uint32_t e, const SpPenalty& pen) {
+#pragma clang fp contract(off)
+    float x = __builtin_bit_cast(float, b << 16);
+    if (pen.repetition != 1.0f) x = x < 0.0f ? x * pen.repetition : x * pen.inv_repetition;
+    const uint32_t c = e & 0x7FFFu;
+    if (c) {
+        const float prod = pen.frequency * (float)c;
+        const float sum = pen.presence + prod;
+        x = x - sum;
+    }
+    const uint32_t u = __builtin_bit_cast(uint32_t, x);
+    return x != x ? 0x7FC0u : (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+// sp_load_row_masked of a penalised row: the lane that loads chunk c reads the chunk's eight entries as one 16-byte LDS read and rewrites
+// the bits of the columns whose entry is not 0 before it packs the keys.  The row's own loads and the mask bytes are issued ahead of
+// the table's two barriers, so their latency passes under the history's.
+template <int NT, int R>
+__device__ __forceinline__ void sp_load_row_penalized(const bf16* x, int chunk0, int V, const SpRowMask& m, const SpPenalty& pen, int64_t b, uint32_t* table,
+                                                      uint32_t (&k)[R][4]) {
+    const int nch = (V + 7) >> 3;
+    uint32_t bits[R];
+    u32x4 raw[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const int c = chunk0 + j * 64;
+        bits[j] = m.bits ? (uint32_t)m.bits[min(c, nch - 1)] : 0xFFu;
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+        raw[j] = c < nch ? *reinterpret_cast<const u32x4*>(x + (int64_t)c * 8) : zero;
+    }
+    sp_history_table<NT>(pen, b, V, table);
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const int c = chunk0 + j * 64;
+        if (c < nch) {
+            const u32x4 e = reinterpret_cast<const u32x4*>(table)[c];
+            if (e[0] | e[1] | e[2] | e[3]) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    uint32_t lo = raw[j][q] & 0xFFFFu, hi = raw[j][q] >> 16;
+                    if (e[q] & 0xFFFFu) lo = sp_penalize(lo, e[q] & 0xFFFFu, pen);
+                    if (e[q] >> 16) hi = sp_penalize(hi, e[q] >> 16, pen);
+                    raw[j][q] = lo | (hi << 16);
+                }
+            }
+        }
+        if ((m.hold >> 3) == c) bits[j] &= ~(1u << (m.hold & 7));   // (hold = -1: chunk -1, never)
+        sp_pack_chunk_masked(raw[j], c, V, bits[j], k[j]);
 #pragma unroll
         for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(k[j][q]));
     }

@@ -872,14 +872,87 @@ class TokenConstraint:
         return constrain_reference(logits, self.allowed, self.hold, None, max(0, self.min_new - emitted_by_all))
 
 
-def _next_tokens(what, logits, temperature, top_k, top_p, generator, u, con=None, step=0):
+class TokenPenalty:
+    """``repetition_penalty``, ``presence_penalty`` and ``frequency_penalty`` of one generation call (the rule:
+    include/omnibiote_hip_penalty.h; in plain torch ``sampling.penalize_reference``): repetition divides the positive and multiplies the
+    negative logits of every token of the row's prompt or output, once per distinct token; presence + frequency * count is subtracted
+    from the logits of the tokens the row has generated.  ``TokenPenalty.of`` checks the numbers — ValueError before anything is
+    launched — and returns None for a call that penalises nothing; ``bind`` attaches the rows' prompts, (rows, T0) int64 with their
+    lengths as (rows,) int32 on the device, and for a host-driven loop the (rows, max_new_tokens) int64 buffer of generated tokens:
+    ``record`` writes a step's tokens into it with one device copy and no host read, ``device_args(i)`` is the ``penalty`` of
+    ``ops.sample_logits`` at step i and ``apply(logits, i)`` the torch sampler's penalised copy.  ``loop_args`` reads a ``DecodeLoop``'s
+    own ``out`` / ``n_new`` instead."""
+
+    @classmethod
+    def of(cls, what, repetition_penalty, presence_penalty, frequency_penalty, max_new_tokens):
+        from .sampling import penalty_numbers
+        for name, v in (("repetition_penalty", repetition_penalty), ("presence_penalty", presence_penalty), ("frequency_penalty", frequency_penalty)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"{what}: {name} must be a number, got {v!r}")
+        try:
+            r, _, pp, fp = penalty_numbers(repetition_penalty, presence_penalty, frequency_penalty)
+        except ValueError as e:
+            raise ValueError(f"{what}: repetition_penalty must be positive and all three penalties finite in fp32 ({e})") from None
+        if r == 1.0 and pp == 0.0 and fp == 0.0:
+            return None
+        if int(max_new_tokens) > L.PENALTY_MAX_GEN:
+            raise ValueError(f"{what}: penalties count a row's generated tokens up to {L.PENALTY_MAX_GEN}, got max_new_tokens = {max_new_tokens}")
+        pen = cls()
+        pen.repetition, pen.presence, pen.frequency, pen.max_new = r, pp, fp, int(max_new_tokens)
+        pen.prompt = pen.prompt_len = pen.gen = None
+        return pen
+
+    def bind(self, prompt, lengths=None, own_buffer=True):
+        """the rows' prompts ``prompt`` (rows, T0) int64 and their lengths (a host sequence; None: T0 each) — copied, so a loop that is
+        prefilled again can rewrite them in place (``rebind``)"""
+        rows, t0 = prompt.shape
+        self.prompt = prompt.to(torch.int64).contiguous().clone()
+        self.prompt_len = torch.tensor([t0] * rows if lengths is None else [int(n) for n in lengths], dtype=torch.int32).to(prompt.device)
+        self.gen = torch.zeros((rows, self.max_new), dtype=torch.int64, device=prompt.device) if own_buffer else None
+        return self
+
+    def rebind(self, prompt, lengths=None):
+        """another prompt into the buffers ``bind`` made: the addresses a captured graph holds stay valid"""
+        rows, width = self.prompt.shape
+        if prompt.dim() != 2 or prompt.shape[0] != rows or prompt.shape[1] > width:
+            raise ValueError(f"TokenPenalty.rebind: the prompt must be ({rows}, at most {width}), got {tuple(prompt.shape)}")
+        t0 = prompt.shape[1]
+        self.prompt[:, :t0].copy_(prompt)
+        self.prompt_len.copy_(torch.tensor([t0] * rows if lengths is None else [int(n) for n in lengths], dtype=torch.int32))
+
+    def record(self, step, tokens):
+        self.gen[:, step].copy_(tokens)
+
+    def _numbers(self):
+        return dict(repetition=self.repetition, presence=self.presence, frequency=self.frequency)
+
+    def device_args(self, step):
+        """the ``penalty`` of ``ops.sample_logits`` in a host-driven loop: every row has ``step`` recorded tokens"""
+        return ops.Penalty(self.prompt, self.prompt_len, self.gen, step, **self._numbers())
+
+    def loop_args(self, out, n_new):
+        """the same for a ``DecodeLoop``: its ``out`` and ``n_new`` are the generated lists and their counts — addresses only"""
+        return ops.Penalty(self.prompt, self.prompt_len, out, n_new, **self._numbers())
+
+    def apply(self, logits, step):
+        """``logits`` with the history's columns rewritten (bf16), for the torch sampler"""
+        from .sampling import penalize_reference
+        return penalize_reference(logits, self.prompt, self.prompt_len, self.gen, step, **self._numbers())
+
+
+def _next_tokens(what, logits, temperature, top_k, top_p, generator, u, con=None, step=0, pen=None):
     """one step's tokens: ``sample_next`` (u is None: the torch sampler), or one launch of the device sampler against this step's
     uniforms ``u`` (B,) — False: greedy, nothing was drawn.  ``con``: the call's ``TokenConstraint`` or None; ``step``: the tokens every
-    running row has emitted so far"""
+    running row has emitted so far; ``pen``: the call's ``TokenPenalty`` or None (the caller records the tokens it keeps)"""
     if u is None:
+        if pen is not None:
+            logits = pen.apply(logits, step)
         return sample_next(logits if con is None else con.restrict(logits, step), temperature, top_k, generator, top_p)
     if not (logits.is_cuda and logits.dtype == torch.bfloat16):
         raise ValueError(f"OmniBioTA.{what}: sampler='device' needs bf16 logits on the GPU, got {logits.dtype} on {logits.device}")
+    if pen is not None:
+        return ops.sample_logits(logits, None if u is False else u, temperature, top_k, top_p, penalty=pen.device_args(step),
+                                 **({} if con is None else con.device_args(step)))
     if con is not None:
         return ops.sample_logits(logits, None if u is False else u, temperature, top_k, top_p, **con.device_args(step))
     return ops.sample_logits(logits, None if u is False else u, temperature, top_k, top_p)
@@ -1248,10 +1321,15 @@ class DecodeLoop:
     a reloaded parameter or a new cache leave the graph reading freed memory — build a new loop.
 
     ``weights`` (``model.quantize_weights()``): every block's step and the readout read the e4m3 codes (``QuantizedWeights``); a captured
-    graph holds the codes' and scales' addresses like every other.  The snapshot is checked here, in ``prefill``, ``start`` and ``run``."""
+    graph holds the codes' and scales' addresses like every other.  The snapshot is checked here, in ``prefill``, ``start`` and ``run``.
 
-    def __init__(self, model, cache, *, max_steps, temperature=1.0, top_k=None, top_p=None, uniforms=None, eos_token=None, capture=False, weights=None,
-                 allowed=None, hold_min=0):
+    ``penalty`` (a ``TokenPenalty`` bound to the prompts the cache was prefilled with, ``TokenPenalty.of(...).bind(idx, lengths,
+    own_buffer=False)``): every draw is penalised (include/omnibiote_hip_penalty.h).  The sampler reads the loop's own ``out`` and ``n_new``
+    as the rows' generated tokens and the penalty's prompt buffer — addresses and constants again, so a captured graph replays it;
+    ``loop.prefill`` rewrites that buffer in place (a prompt no wider than the first).  ``max_steps`` is at most 32767 then."""
+
+    def __init__(self, model, cache, *, max_steps, temperature=1.0, top_k=None, top_p=None, uniforms=None, eos_token=None, capture=False, penalty=None,
+                 weights=None, allowed=None, hold_min=0):
         if isinstance(cache, SharedPrefixCache):
             _refuse_weights("DecodeLoop", weights, "do not run on a shared-prefix cache (SharedPrefixCache)")
             raise ValueError("DecodeLoop: a SharedPrefixCache steps at a host suffix position, which changes every step: the device loop needs a KVCache")
@@ -1271,6 +1349,11 @@ class DecodeLoop:
             raise ValueError(f"DecodeLoop: hold_min = {hold_min} holds eos_token back, and there is no eos_token")
         if cache.pos == 0:
             raise ValueError("DecodeLoop: the cache is empty: prefill a prompt first")
+        if penalty is not None:
+            if not isinstance(penalty, TokenPenalty) or penalty.prompt is None or penalty.prompt.shape[0] != cache.batch:
+                raise ValueError(f"DecodeLoop: penalty must be a TokenPenalty bound to the prompts of the cache's {cache.batch} rows")
+            if int(max_steps) > L.PENALTY_MAX_GEN:
+                raise ValueError(f"DecodeLoop: penalties count a row's generated tokens up to {L.PENALTY_MAX_GEN}, got max_steps = {max_steps}")
         cfg = model.config
         b = cache.batch
         wte = model.transformer.wte.weight
@@ -1297,6 +1380,8 @@ class DecodeLoop:
         self.count = torch.zeros(b, dtype=torch.int32, device=dev)
         self.n_new = torch.zeros(b, dtype=torch.int32, device=dev)
         self.out = torch.zeros((b, self.max_steps), dtype=torch.int64, device=dev)
+        self.penalty = penalty
+        self._pen = {} if penalty is None else {"penalty": penalty.loop_args(self.out, self.n_new)}   # (no penalty: the calls are the calls they were)
         self.steps = 0          # body runs since start
         self.started = False
         self.graph = None
@@ -1307,9 +1392,10 @@ class DecodeLoop:
         if self.allowed is not None or self.hold_min > 0:
             ops.sample_logits(self.logits, self.u if self.uniforms is not None else None, self.temperature, self.top_k, self.top_p, out=self.sampled,
                               allowed_packed=self.allowed, hold_token=self.eos_token if self.hold_min > 0 else None, emitted=self.n_new,
-                              min_emitted=self.hold_min)
+                              min_emitted=self.hold_min, **self._pen)
         else:
-            ops.sample_logits(self.logits, self.u if self.uniforms is not None else None, self.temperature, self.top_k, self.top_p, out=self.sampled)
+            ops.sample_logits(self.logits, self.u if self.uniforms is not None else None, self.temperature, self.top_k, self.top_p, out=self.sampled,
+                              **self._pen)
         ops.gen_advance(self.sampled, self.positions, self.count, self.out, self.n_new, self.token, self.model.transformer.wte.weight, self.x,
                         us=self.uniforms, u=self.u if self.uniforms is not None else None, eos=self.eos_token, commit=commit)
 
@@ -1360,6 +1446,8 @@ class DecodeLoop:
         else:
             self.positions.copy_(c.positions)
             c.reset(c.pos, self.positions, c.min_pos)
+        if self.penalty is not None:
+            self.penalty.rebind(idx, lengths)
         self.started = False
         return logits
 
@@ -1986,7 +2074,8 @@ class OmniBioTA(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, generator=None, eos_token=None, lengths=None, pad_token=None, top_p=None,
-                 sampler="torch", kv_dtype="bf16", num_samples=None, loop=None, allowed_tokens=None, min_new_tokens=0, weights=None):
+                 sampler="torch", kv_dtype="bf16", num_samples=None, loop=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+                 allowed_tokens=None, min_new_tokens=0, weights=None):
         """nanoGPT's generate(): ``idx`` (B, T0) int64 continued by up to ``max_new_tokens`` sampled tokens (``sample_next``); returns
         (B, T0 + n) int64.  The prompt runs once (``prefill``), every new token costs one ``decode_step``.  Where nanoGPT crops the
         context to block_size, this raises: T0 + max_new_tokens must fit.  ``eos_token``: a row that has produced it keeps producing
@@ -2025,6 +2114,17 @@ class OmniBioTA(nn.Module):
         ValueError before anything is launched: an id outside [0, V), a row that allows nothing, ``min_new_tokens`` outside
         [0, max_new_tokens] or without an ``eos_token``, a row that allows nothing but the held ``eos_token``.
 
+        ``repetition_penalty`` (> 0), ``presence_penalty``, ``frequency_penalty``: damp repeats (``TokenPenalty``; the rule:
+        include/omnibiote_hip_penalty.h, ``sampling.penalize_reference``).  At every step the logit x of a token of the row's prompt or of
+        its output so far becomes x / repetition_penalty (x * repetition_penalty if x < 0), once per distinct token, and a token the row
+        has generated c > 0 times loses presence_penalty + frequency_penalty * c; the restriction above applies to the result.  The
+        device sampler reads the row's history itself, in its one launch (``ops.sample_logits(penalty=...)``: with ``loop=`` the loop's own
+        token buffer, so a captured graph carries the penalties); the torch sampler draws from the rewritten copy.  With every
+        sampler, cache, loop, ``lengths``, ``num_samples`` and ``weights``; with 1, 0, 0 nothing changes.  ValueError before anything is
+        launched: a penalty that is not a finite number, ``repetition_penalty <= 0``, ``max_new_tokens > 32767`` with a penalty set.  Not
+        part of ``generate_speculative`` / ``draft_and_verify`` (the verification would need the history to grow inside a drafted block),
+        and there are no no-repeat n-grams or stop sequences.
+
         ``weights`` (``quantize_weights()``): the prompt runs on the dequantised weights and every new token's step reads the e4m3 codes:
         the tokens are those of ``weights.dequantized_model().generate(...)`` with the same arguments.  With every sampler, ``lengths``,
         ``kv_dtype``, ``eos_token``, ``allowed_tokens`` / ``min_new_tokens`` and ``loop``; not with ``num_samples`` (NotImplementedError)."""
@@ -2055,9 +2155,10 @@ class OmniBioTA(nn.Module):
             raise ValueError("OmniBioTA.generate: the prompt is empty")
         con = TokenConstraint.of("generate", allowed_tokens, min_new_tokens, max_new_tokens, eos_token, b * (num_samples or 1), self.config.vocab_size,
                                  idx.device)
+        pen = TokenPenalty.of("OmniBioTA.generate", repetition_penalty, presence_penalty, frequency_penalty, max_new_tokens)
         if lengths is not None:
             return self._generate_ragged(idx, _check_lengths("generate", lengths, b, t0), max_new_tokens, temperature, top_k, generator, eos_token,
-                                         pad_token, top_p, sampler, kv_dtype, loop, con, weights)
+                                         pad_token, top_p, sampler, kv_dtype, loop, con, weights, pen)
         if max_new_tokens < 0 or t0 + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {t0} prompt tokens + {max_new_tokens} new ones exceed block_size = {self.config.block_size}")
         if num_samples is None:
@@ -2072,36 +2173,40 @@ class OmniBioTA(nn.Module):
         step = {} if weights is None else {"weights": weights}              # (weights=None: every call below is the call it was)
         logits = self.prefill(idx, cache, **step)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
+        if pen is not None:
+            pen.bind(rows, None, own_buffer=loop is None)
         if loop is not None:
-            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con, weights)
+            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con, weights, pen)
             if eos_token is not None:                                   # a finished row keeps producing EOS
                 live = torch.arange(tokens.shape[1], device=idx.device).view(1, -1) < n_new.view(-1, 1)
                 tokens = torch.where(live, tokens, torch.full_like(tokens, eos_token))
             return torch.cat([rows, tokens], dim=1)
         done = None
         for i in range(max_new_tokens):
-            nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i], con, i)
+            nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i], con, i, pen)
             if eos_token is not None:
                 if done is not None:
                     nxt = torch.where(done, torch.full_like(nxt, eos_token), nxt)
                 done = (nxt == eos_token) if done is None else (done | (nxt == eos_token))
+            if pen is not None:
+                pen.record(i, nxt)
             out.append(nxt.unsqueeze(1))
             if i + 1 == max_new_tokens or (eos_token is not None and bool(done.all())):
                 break
             logits = self.decode_step(nxt, cache, **step)
         return torch.cat(out, dim=1)
 
-    def _device_loop(self, cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con=None, weights=None):
+    def _device_loop(self, cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con=None, weights=None, pen=None):
         """``generate``'s token loop as a ``DecodeLoop`` behind the prefill that gave ``logits``: (tokens (B, S), n_new (B,))"""
         run = DecodeLoop(self, cache, max_steps=max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p,
-                         uniforms=us if isinstance(us, torch.Tensor) else None, eos_token=eos_token, capture=loop == "graph", weights=weights,
-                         allowed=None if con is None else con.packed, hold_min=0 if con is None else con.min_new)
+                         uniforms=us if isinstance(us, torch.Tensor) else None, eos_token=eos_token, capture=loop == "graph", penalty=pen,
+                         weights=weights, allowed=None if con is None else con.packed, hold_min=0 if con is None else con.min_new)
         run.start(logits)
         run.run(max_new_tokens - 1)
         return run.result()
 
     def _generate_ragged(self, idx, lens, max_new_tokens, temperature, top_k, generator, eos_token, pad_token, top_p=None, sampler="torch", kv_dtype="bf16",
-                         loop=None, con=None, weights=None):
+                         loop=None, con=None, weights=None, pen=None):
         longest = max(lens)
         if max_new_tokens < 0 or longest + max_new_tokens > self.config.block_size:
             raise ValueError(f"OmniBioTA.generate: {longest} prompt tokens (the longest row) + {max_new_tokens} new ones exceed "
@@ -2116,13 +2221,17 @@ class OmniBioTA(nn.Module):
         step = {} if weights is None else {"weights": weights}
         logits = self.prefill(idx, cache, lengths=lens, **step)
         us = _device_uniforms(sampler, max_new_tokens, b, temperature, top_k, idx.device, generator)
+        if pen is not None:
+            pen.bind(idx, lens, own_buffer=loop is None)
         if loop is not None:
-            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con, weights)
+            tokens, n_new = self._device_loop(cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con, weights, pen)
             return ragged_output(idx, lens, tokens, torch.arange(tokens.shape[1], device=idx.device).view(1, -1) < n_new.view(-1, 1), pad)
         tokens, valid = [], []
         done = torch.zeros(b, dtype=torch.bool, device=idx.device)
         for i in range(max_new_tokens):
-            nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i], con, i)
+            nxt = _next_tokens("generate", logits, temperature, top_k, top_p, generator, None if us is None else us[i], con, i, pen)
+            if pen is not None:
+                pen.record(i, nxt)
             tokens.append(nxt)
             valid.append(~done)                                         # a row's token counts if the row was running when it was drawn
             if eos_token is not None:

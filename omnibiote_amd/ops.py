@@ -9,7 +9,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple, Union
 
 import torch
 
@@ -329,8 +329,71 @@ def _constraint(what, B, V, device, allowed, allowed_packed, hold_token, emitted
     return allowed_packed, ld, hold, emitted, min_emitted
 
 
+class Penalty(NamedTuple):
+    """The ``penalty`` of ``sample_logits``: every row's history and the three numbers of include/omnibiote_hip_penalty.h.  ``prompt`` (B, Tp)
+    and ``gen`` (B, S) int64 on the device (rows may be strided) or None; ``prompt_len`` / ``n_gen``: how many of a row's ids count — None
+    (the whole width), a host integer in [0, width] (every row: the call's NULL forms) or (B,) int32 on the device, clamped to the width
+    by the kernel.  S, or a host ``n_gen``, is at most 32767."""
+    prompt: Optional[torch.Tensor] = None
+    prompt_len: Union[None, int, torch.Tensor] = None
+    gen: Optional[torch.Tensor] = None
+    n_gen: Union[None, int, torch.Tensor] = None
+    repetition: float = 1.0
+    presence: float = 0.0
+    frequency: float = 0.0
+
+
+def _history(what, name, ids, n, B, most):
+    """one list of a ``Penalty`` as the C call's ``(ids tensor or None, ld, counts tensor or None, n_all, bound)``"""
+    if ids is None:
+        if n is not None:
+            raise ValueError(f"{what}: penalty.{name} is None, and its count is not")
+        return None, 0, None, 0, 0
+    _need(ids, f"penalty.{name}", torch.int64, contiguous=False)
+    if ids.dim() != 2 or ids.shape[0] != B:
+        raise ValueError(f"{what}: penalty.{name} must be int64 ({B}, n), got {tuple(ids.shape)}")
+    width = ids.shape[1]
+    if ids.stride(1) != 1 and width > 1:
+        raise ValueError(f"{what}: penalty.{name} must have stride 1 along a row's ids")
+    ld = ids.stride(0) if B > 1 else width
+    if ld < width:
+        raise ValueError(f"{what}: the rows of penalty.{name} must lie at least their width {width} apart, got a stride of {ld}")
+    if isinstance(n, torch.Tensor):
+        _need(n, f"the count of penalty.{name}", torch.int32)
+        if n.shape != (B,):
+            raise ValueError(f"{what}: the count of penalty.{name} must be int32 ({B},), got {tuple(n.shape)}")
+        counts, n_all, bound = n, 0, width
+    else:
+        if n is not None and (isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= width):
+            raise ValueError(f"{what}: the count of penalty.{name} must be None, an integer in [0, {width}] or an int32 ({B},) tensor, got {n!r}")
+        counts, bound = None, width if n is None else n
+        n_all = bound
+    if bound > most:
+        raise ValueError(f"{what}: penalty.{name} counts up to {bound} ids per row, more than the {most} the kernel takes")
+    return (ids if bound > 0 else None), ld, counts, n_all, bound
+
+
+def _penalty(what, B, penalty):
+    """``penalty`` as the C call's arguments behind min_emitted — None for a penalty that changes nothing: the caller takes the symbol it
+    took without one."""
+    if penalty is None:
+        return None
+    if not isinstance(penalty, Penalty):
+        raise TypeError(f"{what}: penalty must be an ops.Penalty, got {type(penalty).__name__}")
+    from .sampling import penalty_numbers
+    try:
+        r, inv, pp, fp = penalty_numbers(penalty.repetition, penalty.presence, penalty.frequency)
+    except ValueError as e:
+        raise ValueError(f"{what}: penalty: {e}") from None
+    prompt, prompt_ld, prompt_len, _, prompt_max = _history(what, "prompt", penalty.prompt, penalty.prompt_len, B, L.PENALTY_MAX_PROMPT)
+    gen, gen_ld, n_gen, n_gen_all, gen_max = _history(what, "gen", penalty.gen, penalty.n_gen, B, L.PENALTY_MAX_GEN)
+    if (r == 1.0 and pp == 0.0 and fp == 0.0) or (prompt_max == 0 and gen_max == 0):
+        return None
+    return (_ptr(prompt), prompt_ld, _ptr(prompt_len), prompt_max, _ptr(gen), gen_ld, _ptr(n_gen), n_gen_all, gen_max, r, inv, pp, fp)
+
+
 def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, return_kept=False, out=None, allowed=None, allowed_packed=None,
-                  hold_token=None, emitted=None, min_emitted=0):
+                  hold_token=None, emitted=None, min_emitted=0, penalty=None):
     """The next token of every row of ``logits`` (B, V) bf16, V <= 65536, in one launch (obte_sample_logits_bf16; the rule:
     include/omnibiote_hip_sample.h, restated in plain torch by sampling.sample_reference): temperature, top-k, top-p, softmax and the
     draw against ``u`` (B,) float32 uniforms.  ``u is None``, ``temperature == 0`` or ``top_k == 1``: the lowest index of the row maximum.
@@ -341,7 +404,12 @@ def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, retur
     sampling.constrain_reference): ``allowed`` bool (V,) or (B, V) — packed here, a few torch launches — or ``allowed_packed`` uint8
     (n,) or (B, n), n >= ceil(V / 8), as ``pack_token_mask`` makes it (any byte address; rows may be strided): a column whose bit is clear is
     treated as -inf.  ``hold_token`` is excluded too in every row with ``emitted[b] < min_emitted`` (``emitted`` (B,) int32 on the device,
-    None: 0).  With none of the five given the call is the unrestricted one."""
+    None: 0).  With none of the five given the call is the unrestricted one.
+
+    ``penalty`` (an ``ops.Penalty``; obte_sample_logits_penalized_bf16; the rule: include/omnibiote_hip_penalty.h, in plain torch
+    sampling.penalize_reference): the columns of every row's prompt and generated tokens are rewritten under the repetition, presence and
+    frequency penalties as the row is loaded — bit for bit this call on ``penalize_reference(logits, ...)``, in the same single launch, the
+    restriction applied to the rewritten row.  None, neutral numbers (1, 0, 0) or two empty lists: the call is the one above."""
     _need(logits, "logits", contiguous=False)
     if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
         raise ValueError(f"sample_logits: logits must be (B, V) with B, V >= 1, got {tuple(logits.shape)}")
@@ -362,6 +430,14 @@ def sample_logits(logits, u=None, temperature=1.0, top_k=None, top_p=None, retur
             raise ValueError(f"sample_logits: out must be ({B},), got {tuple(out.shape)}")
     kept = torch.empty(B, dtype=torch.int32, device=logits.device) if return_kept else None
     con = _constraint("sample_logits", B, V, logits.device, allowed, allowed_packed, hold_token, emitted, min_emitted)
+    pen = _penalty("sample_logits", B, penalty)
+    if pen is not None:
+        con = con if con is not None else (None, 0, -1, None, 0)
+        L.check(L.lib().obte_sample_logits_penalized_bf16(_ptr(logits), ld, B, V, _ptr(u), float(temperature),
+                                                          0 if top_k is None else min(int(top_k), 2 ** 31 - 1), 1.0 if top_p is None else float(top_p),
+                                                          _ptr(con[0]), con[1], con[2], _ptr(con[3]), con[4], *pen, _ptr(token), _ptr(kept), _stream()),
+                "obte_sample_logits_penalized_bf16")
+        return (token, kept) if return_kept else token
     if con is not None:
         L.check(L.lib().obte_sample_logits_constrained_bf16(_ptr(logits), ld, B, V, _ptr(u), float(temperature),
                                                             0 if top_k is None else min(int(top_k), 2 ** 31 - 1), 1.0 if top_p is None else float(top_p),

@@ -222,6 +222,71 @@ def constrain_reference(logits, allowed=None, hold_token=None, emitted=None, min
     return res[0] if one else res
 
 
+def _history_counts(what, ids, n, b, v, device):
+    """how often every column occurs among the first n[b] ids of row b — ``ids`` (B, W) integers or None, ``n`` None (W), a number or (B,),
+    clamped to [0, W]; ids outside [0, V) are ignored — as (B, V) int64"""
+    if ids is None:
+        return torch.zeros((b, v), dtype=torch.int64, device=device)
+    t = torch.as_tensor(ids, device=device)
+    t = t.unsqueeze(0) if t.dim() == 1 and b == 1 else t
+    if t.dim() != 2 or t.shape[0] != b or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError(f"penalize_reference: {what} must be ({b}, n) integers, got {t.dtype} {tuple(t.shape)}")
+    t = t.to(torch.int64)
+    w = t.shape[1]
+    n = torch.full((b,), w, dtype=torch.int64, device=device) if n is None else _per_row(n, b, device, torch.int64).clamp(0, w)
+    live = (torch.arange(w, device=device).unsqueeze(0) < n.unsqueeze(1)) & (t >= 0) & (t < v)
+    cnt = torch.zeros((b, v + 1), dtype=torch.int64, device=device)
+    cnt.scatter_add_(1, torch.where(live, t, torch.full_like(t, v)), live.to(torch.int64))
+    return cnt[:, :v]
+
+
+def penalty_numbers(repetition=1.0, presence=0.0, frequency=0.0):
+    """The four fp32 numbers of include/omnibiote_hip_penalty.h as Python floats: ``(r, inv_r, pp, fp)``, each the fp32 rounding of the
+    argument, ``inv_r = float32(1 / float64(r))``.  ValueError unless all are finite fp32 and r > 0."""
+    import ctypes
+    import math
+    r, pp, fp = (ctypes.c_float(float(v)).value for v in (repetition, presence, frequency))
+    if not (math.isfinite(r) and math.isfinite(pp) and math.isfinite(fp)) or not r > 0:
+        raise ValueError(f"repetition must be positive and repetition, presence and frequency finite in fp32, got {repetition!r}, {presence!r}, "
+                         f"{frequency!r}")
+    inv = ctypes.c_float(1.0 / r).value
+    if not math.isfinite(inv):
+        raise ValueError(f"repetition {repetition!r} is too small: 1 / repetition overflows fp32")
+    return r, inv, pp, fp
+
+
+def penalize_reference(logits, prompt=None, prompt_len=None, gen=None, n_gen=None, repetition=1.0, presence=0.0, frequency=0.0):
+    """A bf16 copy of ``logits`` (B, V) or (V,) with the columns of every row's history rewritten: the rule of
+    include/omnibiote_hip_penalty.h in plain torch on any device, in fp32 operations each rounded on its own.  ``prompt`` (B, Tp) and
+    ``gen`` (B, S) integers or None; row b's lists are their first ``prompt_len[b]`` / ``n_gen[b]`` ids (None: the whole width, else a number
+    or (B,), clamped to the width); ids outside [0, V) are ignored.  For a column i in either list, x the fp32 value of its bf16 logit
+    (``logits`` of another dtype are rounded to bf16 first) and c(i) its count in the generated list:
+
+      1. repetition r != 1:  x = x * r if x < 0 else x * float32(1 / float64(r))
+      2. c(i) > 0:           x = x - (presence + frequency * float32(c(i)))
+      3. the column becomes x rounded to bf16 (nearest even); every other column keeps its bits.
+
+    ``ops.sample_logits(logits, penalty=...)`` returns bit for bit what ``ops.sample_logits`` returns on this copy."""
+    one = logits.dim() == 1
+    x = (logits.unsqueeze(0) if one else logits).to(torch.bfloat16)
+    if x.dim() != 2:
+        raise ValueError(f"penalize_reference: logits must be (B, V) or (V,), got {tuple(logits.shape)}")
+    r, inv, pp, fp = penalty_numbers(repetition, presence, frequency)
+    b, v = x.shape
+    dev = x.device
+    c = _history_counts("gen", gen, n_gen, b, v, dev)
+    ctx = (_history_counts("prompt", prompt, prompt_len, b, v, dev) > 0) | (c > 0)
+    f32 = lambda value: torch.tensor(value, dtype=torch.float32, device=dev)
+    y = x.float()
+    if r != 1.0:
+        y = torch.where(y < 0, y * f32(r), y * f32(inv))
+    prod = f32(fp) * c.to(torch.float32)                                  # the product, then the sum, then the difference
+    total = f32(pp) + prod
+    y = torch.where(c > 0, y - total, y)
+    res = torch.where(ctx, y.to(torch.bfloat16), x)
+    return res[0] if one else res
+
+
 def advance_reference(sampled, pos, count, out, n_new, token, wte, us=None, eos=None, commit=1):
     """The generation loop's per-row bookkeeping in plain torch on any device: what obte_gen_advance (include/omnibiote_hip_loop.h)
     implements.  Nothing is changed in place; returns the new ``(pos, count, out, n_new, token, x, u)``.  ``sampled`` (B,) int64 are the

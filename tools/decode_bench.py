@@ -57,7 +57,10 @@ path + ops.sample_logits + the host's bookkeeping, without its per-token host re
 loop without an eos_token (no host read at all).  Also the one-time cost of building each loop (warm-up + capture) and the kernel nodes of
 one step before and after, counted in captured graphs of their own.  One JSON line per (B, ctx).
 
-    python tools/decode_bench.py --graph [--constrained] [--rounds 5] [--steps 300]
+    python tools/decode_bench.py --graph [--constrained] [--penalized] [--rounds 5] [--steps 300]
+
+--penalized (with --graph): also the captured loop with repetition, presence and frequency penalties (include/omnibiote_hip_penalty.h) — the
+sampler reads the prompt of ctx - 1 - steps tokens and the loop's own tokens so far, in its one launch.
 
 --w8: the decode step's weights as e4m3 (model.quantize_weights(), include/omnibiote_hip_w8.h) against bf16, both alternating in one process over
 the same windows and rounds.  (a) the product alone, obte_linear_small_m_w8 against obte_linear_small_m_bf16 on preallocated buffers: the four
@@ -502,16 +505,17 @@ def _graph_nodes(record):
         return None
 
 
-def graph_compare(m, B, ctx, rounds, steps, dev, constrained=False):
+def graph_compare(m, B, ctx, rounds, steps, dev, constrained=False, penalized=False):
     """A generated token with sampling (T = 0.8, top_k = 200, top_p = 0.9) and an eos_token nobody draws, three ways, alternating in one
     process: today's loop (decode_step on the rows path + ops.sample_logits + _generate_ragged's bookkeeping, without its per-token host
     read), DecodeLoop eager and DecodeLoop captured (both read the positions once per 16 steps), and the captured loop with no eos_token
     (no host read at all).  Every window walks the same positions, ctx - 1 - steps .. ctx - 2, so every contender attends over the same
     keys; only run() / the steps are between the events.  ``constrained`` adds the captured loop under a restriction
-    (include/omnibiote_hip_constrain.h): per-row masks that allow a random half of the vocabulary and a minimum length nobody reaches."""
+    (include/omnibiote_hip_constrain.h): per-row masks that allow a random half of the vocabulary and a minimum length nobody reaches;
+    ``penalized`` the captured loop under penalties 1.3 / 0.1 / 0.2 (include/omnibiote_hip_penalty.h) over the prompt and its own tokens."""
     import time
     from omnibiote_amd import ops
-    from omnibiote_amd.model import DecodeLoop, KVCache
+    from omnibiote_amd.model import DecodeLoop, KVCache, TokenPenalty
     V = m.config.vocab_size
     first = ctx - 1 - steps
     g = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
@@ -519,13 +523,16 @@ def graph_compare(m, B, ctx, rounds, steps, dev, constrained=False):
     us = torch.rand((steps + 1, B), device=dev, generator=g)
     setting = dict(temperature=0.8, top_k=200, top_p=0.9)
     eos = V                                                        # a valid "no row ever finishes": the bookkeeping runs, nothing parks
-    caches = {k: KVCache(m, B, ctx) for k in ("eager", "device", "graph", "graph_no_eos") + (("graph_constrained",) if constrained else ())}
+    caches = {k: KVCache(m, B, ctx) for k in ("eager", "device", "graph", "graph_no_eos") + (("graph_constrained",) if constrained else ())
+              + (("graph_penalized",) if penalized else ())}
     logits0 = {k: m.prefill(idx, c, lengths=[first] * B) for k, c in caches.items()}
     loops, build_ms = {}, {}
     for k in list(caches)[1:]:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         extra = dict(allowed=ops.pack_token_mask(torch.rand((B, V), device=dev, generator=g) < 0.5), hold_min=steps + 1) if k == "graph_constrained" else {}
+        if k == "graph_penalized":
+            extra = dict(penalty=TokenPenalty.of("decode_bench", 1.3, 0.1, 0.2, steps + 1).bind(idx, None, own_buffer=False))
         loops[k] = DecodeLoop(m, caches[k], max_steps=steps + 1, uniforms=us, eos_token=None if k == "graph_no_eos" else eos, capture=k != "device", **setting,
                               **extra)
         torch.cuda.synchronize()
@@ -733,6 +740,7 @@ def main():
     p.add_argument("--constrained", action="store_true", help="with --graph: also the captured loop under per-row token masks and a minimum length")
     p.add_argument("--w8", action="store_true", help="e4m3 weights against bf16: the product alone, decode_step on the small and the large config")
     p.add_argument("--w8-part", default="products,small,large", help="with --w8: which parts run")
+    p.add_argument("--penalized", action="store_true", help="with --graph: also the captured loop under repetition, presence and frequency penalties")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300, help="decode steps (and attention calls) per timed window")
     p.add_argument("--baseline_ms", type=float, default=400.0, help="the full forward's window: as many calls as fit, at least 3")
@@ -761,7 +769,7 @@ def main():
         shapes = tuple((int(b), int(c)) for b in (a.batches or "1,8,64").split(",") for c in (a.contexts or "2048").split(","))
         m = build(max(c for _, c in shapes), dev)
         for B, ctx in shapes:
-            print(json.dumps(graph_compare(m, B, ctx, a.rounds, a.steps, dev, a.constrained)), flush=True)
+            print(json.dumps(graph_compare(m, B, ctx, a.rounds, a.steps, dev, a.constrained, a.penalized)), flush=True)
             torch.cuda.empty_cache()
         return
     if a.small_m:

@@ -19,6 +19,13 @@ in torch into a second tensor, then the unconstrained call.  The expectation: co
 call's own spread — it reads V / 8 mask bytes on top of 2 V logits bytes — and below the masked_fill route.
 
     python tools/sample_bench.py --constrained [--batches 1,64] [--rounds 5] [--steps 300]
+
+--penalized: what repetition, presence and frequency penalties cost (include/omnibiote_hip_penalty.h), the sampler alone as in (a), B in
+{1, 64} unless --batches says otherwise, histories of 256 and 2048 tokens per row (half prompt, half generated, random ids), greedy and
+top_k = 200 with top_p = 0.9, penalties 1.3 / 0.1 / 0.2.  Three contenders alternate: the unpenalised call; the penalised call; and what
+a caller had to do before — gather / scatter on a copy of the logits in torch, then the unpenalised call.
+
+    python tools/sample_bench.py --penalized [--batches 1,64] [--rounds 5] [--steps 300]
 """
 import argparse
 import json
@@ -116,6 +123,47 @@ def constrained_compare(B, rounds, steps, dev):
     return out
 
 
+def penalized_compare(B, hist, rounds, steps, dev):
+    from decode_bench import timed
+    from omnibiote_amd import ops
+    from omnibiote_amd.sampling import penalty_numbers
+    gen = torch.Generator(device=dev).manual_seed(B + hist)
+    logits = (torch.randn(B, VOCAB, device=dev, generator=gen) * 2).to(torch.bfloat16)
+    u = torch.rand(B, device=dev, generator=gen)
+    prompt, made = (torch.randint(0, VOCAB, (B, hist // 2), device=dev, generator=gen) for _ in range(2))
+    both, ones = torch.cat([prompt, made], dim=1), torch.ones((B, hist // 2), device=dev)
+    r, inv, pp, fp = penalty_numbers(1.3, 0.1, 0.2)
+    pen = ops.Penalty(prompt, None, made, None, r, pp, fp)
+
+    def torch_route(uu, args):                                     # the rule's effect in the fewest torch launches: not bit for bit the rule
+        v = logits.gather(1, both).float()
+        y = logits.scatter(1, both, torch.where(v < 0, v * r, v * inv).to(torch.bfloat16))
+        cnt = torch.zeros((B, VOCAB), device=dev).scatter_add_(1, made, ones)
+        y = torch.where(cnt > 0, (y.float() - (pp + fp * cnt)).to(torch.bfloat16), y)
+        return ops.sample_logits(y, uu, *args)
+    out = {"part": "penalized sampler alone", "B": B, "V": VOCAB, "history": {"prompt": hist // 2, "generated": hist // 2},
+           "penalties": {"repetition": 1.3, "presence": 0.1, "frequency": 0.2}, "windows": {"calls": steps, "rounds": rounds}, "us": {}}
+    for name, kw in (SETTINGS[0], SETTINGS[4]):
+        uu = None if kw.get("top_k") == 1 else u
+        args = (kw["temperature"], kw.get("top_k"), kw.get("top_p"))
+        legs = {"unpenalized": lambda: ops.sample_logits(logits, uu, *args),
+                "penalized": lambda: ops.sample_logits(logits, uu, *args, penalty=pen),
+                "torch_route_then_unpenalized": lambda: torch_route(uu, args)}
+        for fn in legs.values():
+            for _ in range(5):
+                fn()
+        us = {k: [] for k in legs}
+        for r_ in range(rounds):
+            for leg in (list(legs) if r_ % 2 == 0 else list(legs)[::-1]):
+                us[leg].append(timed(legs[leg], steps))
+        med = {k: statistics.median(v) for k, v in us.items()}
+        res = {k: summary(v) for k, v in us.items()}
+        res["penalized_over_unpenalized"] = round(med["penalized"] / med["unpenalized"], 3)
+        res["penalized_beats_torch_route"] = med["penalized"] < med["torch_route_then_unpenalized"]
+        out["us"][name] = res
+    return out
+
+
 def generated_token(m, B, ctx, rounds, steps, dev):
     from omnibiote_amd.model import KVCache
     gen = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
@@ -139,8 +187,9 @@ def generated_token(m, B, ctx, rounds, steps, dev):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--batches", default=None, help="default 1,8,64 (--constrained: 1,64)")
+    p.add_argument("--batches", default=None, help="default 1,8,64 (--constrained, --penalized: 1,64)")
     p.add_argument("--constrained", action="store_true", help="the constrained sampler against the unconstrained one and the masked_fill route")
+    p.add_argument("--penalized", action="store_true", help="the penalised sampler against the unpenalised one and the gather / scatter route")
     p.add_argument("--context", type=int, default=2048)
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300)
@@ -148,7 +197,12 @@ def main():
     a = p.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
-    batches = [int(b) for b in (a.batches or ("1,64" if a.constrained else "1,8,64")).split(",")]
+    batches = [int(b) for b in (a.batches or ("1,64" if a.constrained or a.penalized else "1,8,64")).split(",")]
+    if a.penalized:
+        for B in batches:
+            for hist in (256, 2048):
+                print(json.dumps(penalized_compare(B, hist, a.rounds, a.steps, dev)), flush=True)
+        return
     if a.constrained:
         for B in batches:
             print(json.dumps(constrained_compare(B, a.rounds, a.steps, dev)), flush=True)
