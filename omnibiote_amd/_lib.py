@@ -282,6 +282,13 @@ SYMBOLS_PENALTY = {
                                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, c_stream]),
 }
 
+# the distillation loss of a causal-LM training step (include/omnibiote_hip_distill.h): a table of its own as well
+DISTILL_MAX_VOCAB = 131072                                 # the widest row obte_distill_ce_rows takes
+SYMBOLS_DISTILL = {
+    "obte_distill_ce_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -312,7 +319,8 @@ def lib():
             for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_ROWS.items()) + list(SYMBOLS_SMALL_M.items()) + list(SYMBOLS_SAMPLE.items())
                                             + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
                                             + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
-                                            + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items()) + list(SYMBOLS_PENALTY.items())):
+                                            + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items()) + list(SYMBOLS_PENALTY.items())
+                                            + list(SYMBOLS_DISTILL.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

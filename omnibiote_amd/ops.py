@@ -902,6 +902,41 @@ def masked_ce_rows(logits, targets, rows, n_accum: int, row_weights: Optional[to
     return row_loss.sum(), dl
 
 
+def distill_ce_rows_per_row(logits, teacher_logits, targets, n_accum: int, row_weights: Optional[torch.Tensor] = None, alpha: float = 0.5,
+                            temperature: float = 1.0):
+    """obte_distill_ce_rows (include/omnibiote_hip_distill.h; the rule in float64: distill.distill_reference) on the compact form —
+    logits and teacher_logits bf16 [n, V] hold the listed rows alone, targets int64 (n,).  Per row: the cross entropy against the
+    label and KL(softmax(teacher / temperature) || softmax(student / temperature)); the loss mixes them as alpha CE + (1 - alpha)
+    temperature^2 KL under masked_ce_rows' normalisation (1 / (n n_accum), or row_weights[r] / n_accum).
+    Returns (row_loss fp32 (n,) weighted, dlogits bf16 [n, V], row_ce fp32 (n,), row_kl fp32 (n,); the last two unweighted)."""
+    from .distill import distill_weights
+    _need(logits, "logits"); _need(teacher_logits, "teacher_logits"); _need(targets, "targets", torch.int64)
+    if logits.dim() != 2 or teacher_logits.shape != logits.shape or teacher_logits.device != logits.device:
+        raise RuntimeError(f"distill_ce_rows: logits and teacher_logits must be [n, V] on one device, got {tuple(logits.shape)} and {tuple(teacher_logits.shape)}")
+    n, V = logits.shape
+    if targets.numel() != n or n == 0:
+        raise RuntimeError(f"distill_ce_rows: {n} rows of logits, {targets.numel()} targets (at least one row is needed)")
+    if row_weights is not None:
+        _need(row_weights, "row_weights", torch.float32)
+        if row_weights.numel() != n:
+            raise RuntimeError(f"distill_ce_rows: {n} rows, {row_weights.numel()} row_weights")
+    ce_weight, kl_weight, inv_t = distill_weights(alpha, temperature)
+    row_scale = (1.0 if row_weights is not None else 1.0 / n) / n_accum
+    out = torch.empty((3, n), dtype=torch.float32, device=logits.device)   # row_loss, row_ce, row_kl
+    dl = torch.empty((n, V), dtype=bf16, device=logits.device)
+    L.check(L.lib().obte_distill_ce_rows(_ptr(logits), _ptr(teacher_logits), _ptr(targets), row_scale, _ptr(row_weights), ce_weight, kl_weight, inv_t,
+                                         _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(dl), n, V, _stream()), "obte_distill_ce_rows")
+    return out[0], dl, out[1], out[2]
+
+
+def distill_ce_rows(logits, teacher_logits, targets, n_accum: int, row_weights: Optional[torch.Tensor] = None, alpha: float = 0.5,
+                    temperature: float = 1.0):
+    """The distillation loss of a causal-LM step in the place of masked_ce_rows (compact form): (loss, dlogits bf16 [n, V], row_ce, row_kl)
+    — loss the sum of the weighted row losses; see distill_ce_rows_per_row."""
+    row_loss, dl, row_ce, row_kl = distill_ce_rows_per_row(logits, teacher_logits, targets, n_accum, row_weights, alpha, temperature)
+    return row_loss.sum(), dl, row_ce, row_kl
+
+
 class _NextTokenLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets, rows):

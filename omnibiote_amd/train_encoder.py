@@ -25,6 +25,10 @@ Added beyond the reference, off by default: ``--master_weights`` — fp32 master
 (FusedAdamW(master_weights=True)); the masters travel inside the optimizer checkpoint and ``--resume_from`` restores them;
 ``--fp32_grad_accum`` — every weight gradient summed over the micro-batches of a step in fp32 and rounded to bf16 once
 (TrainStep(grad_accum="fp32")) instead of after every micro-batch, as autograd's ``grad += new`` does (:284-311).
+``--objective clm`` — the next-token objective for autoregressive models (TrainStep(objective="clm"): the batch itself under the
+document-causal mask, the row-compact readout over next_token_rows' positions, the reference's per-micro-batch normalisation carried
+over) and ``--distill_from`` — the same step against a teacher's logits (ops.distill_ce_rows: one kernel for alpha * CE +
+(1 - alpha) * T^2 * KL and its gradient), the loss a speculative-decoding draft is trained with.
 Data: with ``--base_dir`` pointing at the reference's directory layout (``genbank/train``, ``uniref100/train`` ... of
 ``.npy`` token shards, train_encoder.py:70-99) batches come from ``omnibiote_amd.loader`` (same packing and mixing as the
 reference loader, loader thread + bounded queue, pinned-memory copies on their own stream); otherwise from synthetic rows
@@ -90,6 +94,40 @@ def mlm_corrupt(input_ids: torch.Tensor, mask_prob: float = 0.15):
     mask = torch.as_tensor(draw, dtype=torch.bool, device=input_ids.device)
     mask = mask & (input_ids != PAD_TOKEN) & (input_ids != EOS_TOKEN)
     return input_ids.masked_fill(mask, MASK_TOKEN), mask
+
+
+def _next_token_scored(ids):
+    """The positions a next-token objective scores, as a bool (rows, T) of ``ids``'s kind (a numpy array or a tensor): (b, t) with
+    t + 1 < T, ids[b, t] neither EOS (the pair "end of one document -> first token of the next" is no label pair) nor PAD, and
+    ids[b, t + 1] not PAD."""
+    scored = torch.zeros(ids.shape, dtype=torch.bool, device=ids.device) if torch.is_tensor(ids) else np.zeros(ids.shape, dtype=bool)
+    scored[:, :-1] = (ids[:, :-1] != EOS_TOKEN) & (ids[:, :-1] != PAD_TOKEN) & (ids[:, 1:] != PAD_TOKEN)
+    return scored
+
+
+def next_token_rows(ids_host, mini: int, n_accum: int):
+    """Which positions the causal-LM objective scores, from the host copy of the batch (numpy only, no device round trip):
+    ``(rows, labels)``, each a list of n_accum int64 arrays — per micro-batch of ``mini`` rows the ascending flat positions b T + t
+    (b counted within the micro-batch) that are scored (_next_token_scored) and, in the same order, their labels ids[b, t + 1].  EOS IS a
+    label, at a document's last real token, so that stopping at ``eos_token`` is learnt."""
+    ids = np.asarray(ids_host)[:mini * n_accum]
+    if ids.ndim != 2 or ids.shape[0] != mini * n_accum:
+        raise ValueError(f"next_token_rows: a (rows, T) batch of at least mini * n_accum = {mini * n_accum} rows is needed, got shape {np.shape(ids_host)}")
+    per = _next_token_scored(ids).reshape(n_accum, -1)
+    nxt = np.roll(ids, -1, axis=1).reshape(n_accum, -1)     # (the wrapped last column is never scored)
+    rows = [np.flatnonzero(per[j]).astype(np.int64) for j in range(n_accum)]
+    return rows, [nxt[j][rows[j]].astype(np.int64) for j in range(n_accum)]
+
+
+def next_token_rows_device(input_ids: torch.Tensor, mini: int, n_accum: int):
+    """next_token_rows without a host copy of the batch: the same integers from tensor ops and ONE blocking device-to-host copy (of the
+    bool table); lists of int64 tensors on ``input_ids``'s device."""
+    ids = input_ids[:mini * n_accum]
+    scored = _next_token_scored(ids).reshape(n_accum, -1)
+    nxt = torch.roll(ids, shifts=-1, dims=1).reshape(n_accum, -1)
+    sh = scored.cpu()
+    rows = [torch.nonzero(sh[j], as_tuple=False).reshape(-1).to(ids.device) for j in range(n_accum)]
+    return rows, [nxt[j].index_select(0, rows[j]) for j in range(n_accum)]
 
 
 # ---------------------------------------------------------------------------------------------------- optimizer
@@ -326,7 +364,8 @@ StepPlan = namedtuple("StepPlan", "rows n_accum sparse_rows readout rows_forward
 # policy entered (autograd's own `grad += new`).
 PassRecord = namedtuple("PassRecord", "j last isolate_last side slot no_sync ordered join_side delivery")
 # The corrupted batch of one step; rows / targets: per micro-batch, the masked positions and (host prelude only) their labels, or None
-_Batch = namedtuple("_Batch", "masked_ids mask rows targets")
+# labels (objective="clm" only): the batch shifted left by one, what the dense readout's CE indexes by position; None: the batch itself
+_Batch = namedtuple("_Batch", "masked_ids mask rows targets labels", defaults=(None,))
 
 
 def resolve_step_plan(s, rows: int, on_gpu: bool, has_reducer: bool, has_transformer: bool, env=os.environ) -> StepPlan:
@@ -340,6 +379,11 @@ def resolve_step_plan(s, rows: int, on_gpu: bool, has_reducer: bool, has_transfo
     rows = rows // s.mini * s.mini
     n_accum = rows // s.mini
     sparse_rows = s.lm_head_impl in ("dense", "masked") and fused and not stub
+    # objective="clm" (read with a default: callers hand any object with the older attributes) runs on the row-compact readout alone, so
+    # its plan is the MLM plan of the same settings; the attributes may have been reassigned on a live object since the constructor checked
+    if getattr(s, "objective", "mlm") == "clm" and not sparse_rows:
+        raise ValueError('TrainStep(objective="clm") needs lm_head_impl "masked" or "dense", loss_impl="fused" and no fused_loss_fn; got '
+                         f"lm_head_impl={s.lm_head_impl!r}, loss_impl={s.loss_impl!r}, fused_loss_fn {'set' if stub else 'None'}")
     k = s.per_pass if (sparse_rows and n_accum % s.per_pass == 0) else 1
     n_pass = n_accum // k
     pipelined = s.pipeline_streams >= 2 and on_gpu and fused and n_pass > 2 and not s.sync_every
@@ -401,8 +445,15 @@ class TrainStep:
                  loss_impl: str = "fused", mask_impl: str = "ranges", sync_every_micro_step: bool = False,
                  max_grad_norm: float = 1.0, lm_head_impl: str = "masked", pipeline_streams: int = 1,
                  fused_loss_fn: Optional[Callable] = None, micro_batches_per_pass: int = 1, backward_order: str = "layer",
-                 rows_forward: bool = True, grad_accum: str = "bf16"):
-        """grad_accum: "bf16" (default) — the reference's arithmetic: every micro-batch's weight gradient is rounded to bf16 and
+                 rows_forward: bool = True, grad_accum: str = "bf16", objective: str = "mlm", teacher=None, distill_alpha: float = 0.5,
+                 distill_temperature: float = 1.0):
+        """objective: "mlm" (default) — the reference's masked-LM step; "clm" — the next-token objective of an autoregressive model
+        (config.autoregressive): no corruption, the document-causal mask, and the row-compact readout over the positions
+        next_token_rows lists, every one weighted 1 / (n_accum * scored positions of its own micro-batch).  teacher (clm only): an
+        autoregressive OmniBioTA with the student's vocabulary, any depth and width; put in eval(), run under no_grad on the listed
+        rows, and the loss becomes distill_alpha * CE + (1 - distill_alpha) * distill_temperature^2 * KL(teacher || student) at that
+        temperature (ops.distill_ce_rows); the result dict then also carries "ce" and "kl", normalised like "loss".
+        grad_accum: "bf16" (default) — the reference's arithmetic: every micro-batch's weight gradient is rounded to bf16 and
         added to a bf16 running sum (autograd's ``grad += new``; here the wgrad epilogues do it in place).  "fp32" (beyond the
         reference, --fp32_grad_accum): over the passes of a step every weight gradient is summed in a persistent fp32 buffer of
         the weight's shape (model.Fp32GradStore, owned by this object: +4 bytes per parameter) from the contributions BEFORE
@@ -414,6 +465,10 @@ class TrainStep:
         the HIP kernel (ops.masked_ce) — lets the CPU multi-process tests drive the product scheduling (in-place
         accumulation, no_sync, hand-delivered d(logits)) with a stub model and a torch loss."""
         self.fused_loss_fn = fused_loss_fn
+        if objective not in ("mlm", "clm"):
+            raise ValueError(f'objective must be "mlm" or "clm", got {objective!r}')
+        self.objective = objective
+        self.teacher, self.distill_alpha, self.distill_temperature = teacher, float(distill_alpha), float(distill_temperature)
         # micro_batches_per_pass = k > 1 (the two row-compact readout paths): k consecutive micro-batches go through the model in ONE
         # forward/backward of k * mini_batch_size rows.  Rows never interact across a batch (attention is per row, the mask
         # builder's per-micro-batch quirk is kept), and the loss keeps the reference's normalisation — every masked row is
@@ -462,6 +517,8 @@ class TrainStep:
         self._ln_store = None
         self._acc32_store = None
         self._mask_rows_host = None   # the last call's per-micro-batch masked-row lists (read by tests)
+        self._clm_bufs = {}
+        self._check_objective()
         if grad_accum not in ("bf16", "fp32"):
             raise ValueError(f'grad_accum must be "bf16" or "fp32", got {grad_accum!r}')
         self.grad_accum = grad_accum
@@ -481,6 +538,32 @@ class TrainStep:
     def _core(self):
         """The model itself, out of a DDP wrapper."""
         return self.model.module if hasattr(self.model, "module") else self.model
+
+    def _check_objective(self) -> None:
+        """The refusals of objective="clm" and of a teacher: in the constructor and again at the top of every call (the public
+        attributes may be reassigned on a live object), before anything is launched."""
+        if self.objective != "clm":
+            if self.teacher is not None:
+                raise ValueError('TrainStep: a teacher needs objective="clm" (distillation is a next-token loss)')
+            return
+        if self.lm_head_impl == "dense_full":
+            raise ValueError('TrainStep(objective="clm"): lm_head_impl="dense_full" is not available (the next-token loss runs on the row-compact '
+                             'readout: "masked" or "dense")')
+        if self.fused_loss_fn is not None or self.loss_impl != "fused":
+            raise ValueError('TrainStep(objective="clm") needs the HIP loss (loss_impl="fused", no fused_loss_fn)')
+        if not bool(getattr(getattr(self._core, "config", None), "autoregressive", False)):
+            raise ValueError('TrainStep(objective="clm"): the model is not autoregressive (config.autoregressive): a bidirectional model sees the '
+                             "token it is asked to predict")
+        if self.teacher is not None:
+            from .distill import distill_weights
+            from .model import OmniBioTA
+            t = self.teacher
+            if not isinstance(t, OmniBioTA) or not t.config.autoregressive:
+                raise ValueError("TrainStep: teacher must be an autoregressive OmniBioTA")
+            if t.config.vocab_size != self._core.config.vocab_size:
+                raise ValueError(f"TrainStep: the teacher's vocabulary ({t.config.vocab_size}) differs from the student's ({self._core.config.vocab_size})")
+            distill_weights(self.distill_alpha, self.distill_temperature)
+            t.eval()
 
     @staticmethod
     def _refuse_env_switches() -> None:
@@ -530,10 +613,15 @@ class TrainStep:
         return ops.token_order(seg, vocab, ws=self._token_order_ws(plan.n_pass, seg.shape[1], vocab, seg.device))
 
     def _mask(self, plan: StepPlan, ranges, j: int, dtype):
-        """The attention mask of pass j out of the key ranges built once per optimizer step for every micro-batch."""
+        """The attention mask of pass j out of the range tables (a masks.RangeMask) built once per optimizer step for every micro-batch."""
         from . import masks
-        rm = masks.RangeMask(ranges[j * plan.span:(j + 1) * plan.span])
+        sl = slice(j * plan.span, (j + 1) * plan.span)
+        rm = masks.RangeMask(ranges.key_ranges[sl], None if ranges.query_bounds is None else ranges.query_bounds[sl])
         if plan.mask_impl == "ranges":
+            if rm.query_bounds is not None:   # objective="clm": resolved here, so that the model does not take it for a mask without causality
+                from . import ops
+                B, T, _ = rm.key_ranges.shape
+                return ops.MaskSpec.from_user(rm, B, T, self.n_head, rm.key_ranges.device)
             return rm
         return rm.dense(dtype).unsqueeze(1).expand(-1, self.n_head, -1, -1)   # train_encoder.py:292
 
@@ -590,6 +678,8 @@ class TrainStep:
             head = _Acc32FlushFn.apply(core.lm_head.weight) if plan.fp32_sum else core.lm_head.weight.sum() * 0
             (emb.sum() * 0 + head).backward()
             return torch.zeros((), dtype=torch.float32, device=x.device)
+        if self.teacher is not None:
+            return self._distill_loss_backward(plan, rec, chain, x, y, attn_mask, rows, weights, tg)
         dense = plan.readout == "dense"
         if not dense and plan.rows_forward:
             # the model is told which positions are wanted: the last block's MLP half and ln_f run on them alone (model.forward(rows=))
@@ -612,6 +702,82 @@ class TrainStep:
         wm = float(core.lm_head.output_mult) / float(core.lm_head.width_mult())
         _ReadoutRowsGradFn.apply(emb_rows, core.lm_head.weight, wm, dl).backward()
         return loss.detach()
+
+    def _distill_loss_backward(self, plan: StepPlan, rec: PassRecord, chain, x, y, attn_mask, rows, weights, tg):
+        """_rows_loss_backward with a teacher: the teacher's logits at the listed positions (no_grad: its blocks take the forward that
+        keeps nothing), ops.distill_ce_rows in the place of ops.masked_ce_rows, the same two backward products.  Returns
+        [loss, ce, kl], each under the step's normalisation."""
+        from . import ops
+        from .model import _ReadoutRowsGradFn
+        core = self._core
+        dense = plan.readout == "dense"
+        if not dense and plan.rows_forward:
+            emb_rows = self.model(x, attn_mask=attn_mask, return_embeddings=True, rows=rows)
+        else:
+            emb = self.model(x, attn_mask=attn_mask, return_embeddings=True)
+            emb_rows = None if dense else emb.reshape(-1, emb.shape[-1]).index_select(0, rows)
+        with torch.no_grad():
+            t_mask = attn_mask
+            if torch.is_tensor(attn_mask) and attn_mask.shape[1] != self.teacher.config.n_head:   # mask_impl="dense": one (T, T) table for every head
+                t_mask = attn_mask[:, :1].expand(-1, self.teacher.config.n_head, -1, -1)
+            t_logits = self.teacher.lm_head(self.teacher(x, attn_mask=t_mask, return_embeddings=True, rows=rows))
+            if dense:   # logits of every position, as the dense readout computes them; the loss kernel takes the listed ones
+                logits = core.lm_head(emb)
+                logits = logits.reshape(-1, logits.shape[-1]).index_select(0, rows)
+            else:
+                logits = core.lm_head(emb_rows)
+            labels = tg if tg is not None else y.reshape(-1).index_select(0, rows)
+            loss, dl, row_ce, row_kl = ops.distill_ce_rows(logits, t_logits, labels, plan.n_accum, row_weights=weights,
+                                                           alpha=self.distill_alpha, temperature=self.distill_temperature)
+            if weights is None:
+                parts = torch.stack([row_ce.sum(), row_kl.sum()]) / (rows.numel() * plan.n_accum)
+            else:
+                parts = torch.stack([(row_ce * weights).sum(), (row_kl * weights).sum()]) / plan.n_accum
+        del logits, t_logits
+        self._order_backward(rec, chain)
+        if dense:
+            emb_rows = emb.reshape(-1, emb.shape[-1]).index_select(0, rows)
+        wm = float(core.lm_head.output_mult) / float(core.lm_head.width_mult())
+        _ReadoutRowsGradFn.apply(emb_rows, core.lm_head.weight, wm, dl).backward()
+        return torch.cat([loss.detach().reshape(1), parts])
+
+    def _clm_batch(self, plan: StepPlan, input_ids, ids_host) -> _Batch:
+        """objective="clm": no corruption — the batch itself, the scored positions per micro-batch and their labels (next_token_rows).
+        With the host copy of the batch the lists are formed on the host and travel through reused pinned buffers as asynchronous
+        copies, as in _host_prelude; without it they come from tensor ops and one blocking copy (the same one-time warning)."""
+        labels = torch.roll(input_ids, shifts=-1, dims=1)
+        if ids_host is None or not input_ids.is_cuda:
+            if input_ids.is_cuda and not TrainStep._warned_no_host_copy:
+                TrainStep._warned_no_host_copy = True
+                import warnings
+                warnings.warn("TrainStep: no input_ids_host given — the scored-row lists of the readout path need a "
+                              "blocking device-to-host copy per optimizer step (pass the loader's host copy of the batch to avoid it)")
+            lists, targets = next_token_rows_device(input_ids, self.mini, plan.n_accum)
+            return _Batch(input_ids, None, lists, targets, labels)
+        dev = input_ids.device
+        rows, T = plan.rows, input_ids.shape[1]
+        idx, lab = next_token_rows(np.asarray(ids_host)[:rows], self.mini, plan.n_accum)
+        st = self._clm_bufs.get((rows, T, dev))
+        if st is None:
+            st = dict(rows_pin=torch.empty(rows * T, dtype=torch.int64).pin_memory(), rows_dev=torch.empty(rows * T, dtype=torch.int64, device=dev),
+                      tgt_pin=torch.empty(rows * T, dtype=torch.int64).pin_memory(), tgt_dev=torch.empty(rows * T, dtype=torch.int64, device=dev), done=None)
+            if len(self._clm_bufs) >= 4:           # --batch_ramp walks through many row counts: keep a few
+                self._clm_bufs.pop(next(iter(self._clm_bufs)))
+            self._clm_bufs[(rows, T, dev)] = st
+        if st["done"] is not None:
+            st["done"].synchronize()        # the previous step's copies out of these pinned buffers (long finished)
+        sizes = [len(v) for v in idx]
+        total = int(sum(sizes))
+        if total:
+            st["rows_pin"].numpy()[:total] = np.concatenate(idx)
+            st["rows_dev"][:total].copy_(st["rows_pin"][:total], non_blocking=True)
+            st["tgt_pin"].numpy()[:total] = np.concatenate(lab)
+            st["tgt_dev"][:total].copy_(st["tgt_pin"][:total], non_blocking=True)
+        off = np.concatenate([[0], np.cumsum(sizes)])
+        lists = [st["rows_dev"][int(off[j]):int(off[j + 1])] for j in range(plan.n_accum)]
+        targets = [st["tgt_dev"][int(off[j]):int(off[j + 1])] for j in range(plan.n_accum)]
+        st["done"] = torch.cuda.current_stream().record_event()
+        return _Batch(input_ids, None, lists, targets, labels)
 
     def _host_prelude(self, plan: StepPlan, input_ids, ids_host) -> _Batch:
         """The MLM corruption with every host-side input at hand (train_encoder.py:273-279): the Bernoulli draw AND the
@@ -659,7 +825,11 @@ class TrainStep:
 
     def _prepare_batch(self, plan: StepPlan, input_ids, mlm_mask, input_ids_host) -> _Batch:
         """The corrupted ids, the mask and — for the row-compact readouts — the masked positions per micro-batch, from the host
-        prelude, the host Bernoulli draw (mlm_corrupt) or the caller's mlm_mask."""
+        prelude, the host Bernoulli draw (mlm_corrupt) or the caller's mlm_mask.  objective="clm": _clm_batch."""
+        if self.objective == "clm":
+            if mlm_mask is not None:
+                raise ValueError('TrainStep(objective="clm"): there is no corruption, mlm_mask has no meaning')
+            return self._clm_batch(plan, input_ids, input_ids_host)
         if mlm_mask is None and input_ids_host is not None and input_ids.is_cuda:
             return self._host_prelude(plan, input_ids, input_ids_host)
         if mlm_mask is None:
@@ -699,7 +869,7 @@ class TrainStep:
         """Forward, loss and backward of one pass on the current stream; its share of the step's loss."""
         from .model import BackwardOrder, embedding_order
         sl = slice(rec.j * plan.span, (rec.j + 1) * plan.span)
-        x, y = batch.masked_ids[sl], input_ids[sl]
+        x, y = batch.masked_ids[sl], (input_ids if batch.labels is None else batch.labels)[sl]
         attn_mask = self._mask(plan, ranges, rec.j, dtype)
         ctx = self.model.no_sync() if rec.no_sync else contextlib.nullcontext()
         # this pass's slice of the step-wide id sort, for its embedding backward
@@ -726,6 +896,7 @@ class TrainStep:
         micro-batch): without it the final mask comes back from the device once per optimizer step — a blocking D2H copy that
         waits for the previous step to drain (a one-time warning says so)."""
         from . import masks
+        self._check_objective()   # (the public attributes may have been reassigned since the constructor)
         plan = self._resolve(input_ids.shape[0], input_ids.is_cuda)
         input_ids = input_ids[:plan.rows]
         self.optimizer.zero_grad(set_to_none=True)
@@ -735,8 +906,9 @@ class TrainStep:
             self._refuse_env_switches()
         dtype = next(self.model.parameters()).dtype
         emb_orders = self._embedding_orders(plan, batch.masked_ids)
-        ranges = masks.RangeMask.from_tokens(input_ids, padding=self.use_padding, group=self.mini).key_ranges
-        partial = [torch.zeros((), dtype=torch.float32, device=input_ids.device) for _ in range(plan.ns)]   # the loss, summed per stream
+        ranges = masks.RangeMask.from_tokens(input_ids, padding=self.use_padding, group=self.mini, causal=self.objective == "clm")
+        # the loss, summed per stream (with a teacher: [loss, ce, kl])
+        partial = [torch.zeros((3,) if self.teacher is not None else (), dtype=torch.float32, device=input_ids.device) for _ in range(plan.ns)]
         main = self._fork_streams(plan)
         # what links the backward passes of this call's side passes: the event after the previous one, that pass's per-group events,
         # and the BackwardOrder of the pass being built
@@ -763,6 +935,8 @@ class TrainStep:
         if self.scheduler is not None:
             self.scheduler.step()
         tokens = (input_ids != PAD_TOKEN).sum()
+        if self.teacher is not None:
+            return {"loss": cum_loss[0], "tokens": tokens, "ce": cum_loss[1], "kl": cum_loss[2]}
         return {"loss": cum_loss, "tokens": tokens}
 
 
@@ -796,6 +970,7 @@ def build_model(args, device, dtype=torch.bfloat16, vocab_size: int = 2 ** 16):
     config.n_head = args.n_head
     config.flash = not args.disable_flash
     config.checkpoint_freq = args.checkpoint_freq
+    config.autoregressive = getattr(args, "objective", "mlm") == "clm"   # --objective clm: a causal model (generate / score / sample serve it)
     m = OmniBioTA(config)
     config.n_embd, config.n_head = 24, 3
     base_model = OmniBioTA(config)
@@ -933,6 +1108,17 @@ def parse_args(argv=None):
                    help="sum every weight gradient over the micro-batches of a step in fp32 and round it to bf16 once, instead of after "
                         "every micro-batch (+4 bytes per parameter of scratch; beyond the reference's arithmetic, like --master_weights, whose "
                         "fp32 masters it feeds with a gradient rounded once); not with --checkpoint_freq > 0")
+    p.add_argument("--objective", default="mlm", choices=["mlm", "clm"],
+                   help="mlm: the reference's masked-LM objective; clm: next-token prediction — the model is built autoregressive "
+                        "(config.autoregressive), no corruption, document-causal attention, every position with a successor in its own document scored")
+    p.add_argument("--distill_from", type=str, default="",
+                   help="--objective clm only: a checkpoint written by checkpoint.save_checkpoint of an autoregressive teacher with the same vocabulary; "
+                        "the loss becomes distill_alpha * CE + (1 - distill_alpha) * T^2 * KL(teacher || student) at temperature T")
+    p.add_argument("--teacher_n_layer", type=int, default=0, help="the teacher's depth (0: --n_layer)")
+    p.add_argument("--teacher_n_embd", type=int, default=0, help="the teacher's width (0: --n_embd)")
+    p.add_argument("--teacher_n_head", type=int, default=0, help="the teacher's heads (0: --n_head)")
+    p.add_argument("--distill_alpha", type=float, default=0.5, help="weight of the hard-label cross entropy in the distillation loss")
+    p.add_argument("--distill_temperature", type=float, default=1.0, help="temperature both distributions are softened by in the KL term")
     p.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                    help="cpu only exercises the harness plumbing: the model itself has no CPU path and says so at the first forward")
     return p.parse_args(argv)
@@ -1044,14 +1230,31 @@ def make_test_sources(args, device, rng):
 @torch.no_grad()
 def evaluate(model, test_sources, args, world: int, device) -> Dict[str, float]:
     """The held-out pass of train_encoder.py:371-410: model.eval(), one mini-batch per test set, the same MLM corruption
-    and attention mask as training, loss = sum_masked(CE) / n_masked / world on every rank, summed over ranks."""
+    and attention mask as training, loss = sum_masked(CE) / n_masked / world on every rank, summed over ranks.
+    --objective clm: the mean next-token loss over the scored positions of the mini-batch (next_token_rows) under the document-causal
+    mask, through the row-compact readout; no MLM draw."""
     from . import masks, ops
     core = model.module if hasattr(model, "module") else model
     was_training = core.training
     model.eval()
     out = {}
+    clm = getattr(args, "objective", "mlm") == "clm"
     for name, next_rows in test_sources:
         test_batch = next_rows(args.mini_batch_size)
+        if clm:
+            rows, labels = next_token_rows_device(test_batch, test_batch.shape[0], 1)
+            if rows[0].numel() == 0:
+                loss = torch.full((), float("nan"), dtype=torch.float32, device=test_batch.device)   # nothing to score: 0 / 0, as the MLM mean gives
+            else:
+                attn = masks.RangeMask.from_tokens(test_batch, padding=args.use_padding, causal=True)
+                attn = ops.MaskSpec.from_user(attn, test_batch.shape[0], test_batch.shape[1], core.config.n_head, test_batch.device)
+                emb_rows = model(test_batch, attn_mask=attn, return_embeddings=True, rows=rows[0])
+                loss, _ = ops.masked_ce_rows(core.lm_head(emb_rows), labels[0], None, 1)
+            loss = loss.float() / world
+            if world > 1:
+                dist.all_reduce(loss)
+            out[name] = float(loss.item())
+            continue
         masked_ids, mask = mlm_corrupt(test_batch)
         attn = masks.RangeMask.from_tokens(test_batch, padding=args.use_padding)
         logits = model(masked_ids, attn_mask=attn)
@@ -1066,6 +1269,27 @@ def evaluate(model, test_sources, args, world: int, device) -> Dict[str, float]:
         out[name] = float(loss.item())
     model.train(was_training)
     return out
+
+
+def load_teacher(args, student, device):
+    """--distill_from: the teacher out of a checkpoint.save_checkpoint file, in bf16 on ``device``.  Its shape is the one the
+    --teacher_n_layer / --teacher_n_embd / --teacher_n_head flags declare (each defaults to the student's value): a checkpoint of
+    another shape is refused, so that a mistaken path does not train against the wrong model unnoticed."""
+    from .checkpoint import load_checkpoint
+    if getattr(args, "objective", "mlm") != "clm":
+        raise ValueError("--distill_from needs --objective clm")
+    t = load_checkpoint(args.distill_from, map_location=device)
+    want = {"n_layer": getattr(args, "teacher_n_layer", 0) or args.n_layer, "n_embd": getattr(args, "teacher_n_embd", 0) or args.n_embd,
+            "n_head": getattr(args, "teacher_n_head", 0) or args.n_head}
+    have = {k: getattr(t.config, k) for k in want}
+    if have != want:
+        raise ValueError(f"--distill_from {args.distill_from}: the checkpoint's model has {have}, expected {want} (--teacher_n_layer / --teacher_n_embd / "
+                         "--teacher_n_head; each defaults to the student's value)")
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")   # "Casting complex values to real", as in build_model
+        t.to(torch.bfloat16)
+    return t.to(device).eval()
 
 
 def run(args):
@@ -1115,9 +1339,12 @@ def run(args):
     model = wrap_ddp(m, local if on_gpu else None, grad_exchange=getattr(args, "grad_exchange", "allreduce")) if world > 1 else m
     total_iters = int(args.token_budget / (world * batch_size * args.ctx_len))
     opt, sched = build_optimizer(m, args, total_iters, fused=on_gpu)
+    objective = getattr(args, "objective", "mlm")
+    teacher = load_teacher(args, m, device) if getattr(args, "distill_from", "") else None
     step = TrainStep(model, opt, sched, mini_batch_size=args.mini_batch_size, n_head=args.n_head, use_padding=args.use_padding,
                      pipeline_streams=getattr(args, "pipeline_streams", 1), micro_batches_per_pass=getattr(args, "micro_batches_per_pass", 1),
-                     grad_accum="fp32" if getattr(args, "fp32_grad_accum", False) else "bf16")
+                     grad_accum="fp32" if getattr(args, "fp32_grad_accum", False) else "bf16", objective=objective, teacher=teacher,
+                     distill_alpha=getattr(args, "distill_alpha", 0.5), distill_temperature=getattr(args, "distill_temperature", 1.0))
     rng = np.random.default_rng(1234 + rank)
     next_batch, source, close_source = make_batch_source(args, batch_size, device, rng)
     test_sources = make_test_sources(args, device, rng)
@@ -1132,7 +1359,8 @@ def run(args):
     fpt = flops_per_token(n_params, args.n_layer, args.n_embd, args.ctx_len)   # the reference's MFU formula (:360)
     # what this step executes: its default readout runs on the ~15 % MLM-masked positions only (fewer FLOP, same gradients)
     fpt_exec = flops_per_token_executed(n_params, args.n_layer, args.n_embd, args.ctx_len, step.lm_head_impl, step.rows_forward,
-                                        rows_attention=step.rows_forward and step.mask_impl == "ranges")
+                                        rows_attention=step.rows_forward and step.mask_impl == "ranges",
+                                        masked_fraction=1.0 if objective == "clm" else 0.15)   # (clm scores nearly every position; a teacher's forward is not counted)
     n_steps = total_iters if args.max_steps <= 0 else min(total_iters, start + args.max_steps)
 
     def save(tag):
@@ -1147,7 +1375,7 @@ def run(args):
             rows = effective_batch(i, total_iters, args, batch_size)
             ids = next_batch(rows)
             out = step(ids, input_ids_host=getattr(ids, "_obte_host_copy", None))
-            stats = torch.stack([out["loss"], out["tokens"].float()])
+            stats = torch.stack([out["loss"], out["tokens"].float()] + ([out["ce"], out["kl"]] if teacher is not None else []))
             if world > 1:
                 dist.all_reduce(stats)
             if on_gpu:
@@ -1160,7 +1388,8 @@ def run(args):
             history.append(loss)
             if rank == 0:
                 lrs = [g["lr"] for g in opt.param_groups]
-                print(f"step {i} loss {loss:.4f} lr {lrs[0]:.5f}|{lrs[-1]:.5f} tokens/s {toks / dt:,.0f} "
+                parts = f" ce {stats[2].item() / world:.4f} kl {stats[3].item() / world:.4f}" if teacher is not None else ""
+                print(f"step {i} loss {loss:.4f}{parts} lr {lrs[0]:.5f}|{lrs[-1]:.5f} tokens/s {toks / dt:,.0f} "
                       f"MFMA-frac(executed FLOP) {toks / dt * fpt_exec / (2.5e15 * world) * 100:.1f}% "
                       f"[reference formula 6N+12LCT: {toks / dt * fpt / (2.5e15 * world) * 100:.1f}%] trained {trained / 1e6:.2f}M", flush=True)
             if trained - last_test > args.test_freq:            # train_encoder.py:371-410
