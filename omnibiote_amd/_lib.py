@@ -289,6 +289,21 @@ SYMBOLS_DISTILL = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_stream]),
 }
 
+# beam search, the selection and the attention / block step through an ancestry table (include/omnibiote_hip_beam.h): a table of its own
+# as well
+BEAM_MAX_WIDTH = 32                                        # OBTE_BEAM_MAX_WIDTH
+SYMBOLS_BEAM = {
+    "obte_beam_select_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "obte_beam_select_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int64, c_stream]),
+    "obte_attn_decode_beam": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_decode_beam_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "obte_block_decode_beam": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -320,7 +335,7 @@ def lib():
                                             + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
                                             + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
                                             + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items()) + list(SYMBOLS_PENALTY.items())
-                                            + list(SYMBOLS_DISTILL.items())):
+                                            + list(SYMBOLS_DISTILL.items()) + list(SYMBOLS_BEAM.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -69,6 +69,7 @@ __device__ __forceinline__ float group_reduce(float v) {
 // by all hs / 8 consecutive lanes of a head vector at once.
 
 struct CacheBf16 {
+    static constexpr bool ANC = false;
     static constexpr int DPL = 8;
     static constexpr bool SCALED = false;
     typedef u32x4 Piece;
@@ -86,7 +87,14 @@ struct CacheBf16 {
     __device__ __forceinline__ void put(int which, int64_t vec, int hs, int e, bf16x8 x) const { *(bf16x8*)((which ? v : k) + vec * hs + e) = x; }
 };
 
+// the bf16 cache read through an ancestry table (include/omnibiote_hip_beam.h): the same bytes, another row per key
+struct CacheBf16Anc : CacheBf16 {
+    static constexpr bool ANC = true;
+    using CacheBf16::CacheBf16;
+};
+
 struct CacheE4m3 {
+    static constexpr bool ANC = false;
     static constexpr int DPL = KV8_DPL;
     static constexpr bool SCALED = true;
     typedef __attribute__((ext_vector_type(DPL / 4))) uint32_t Piece;   // DPL code bytes
@@ -146,18 +154,35 @@ __device__ __forceinline__ void merge(Part<DPL>& a, const Part<DPL>& b) {
 }
 
 // DEC_UNROLL keys of one lane group.  TAIL: some of them may lie at or beyond k1.
-template <class Fmt, int HS, bool TAIL>
-__device__ __forceinline__ void decode_keys(Part<Fmt::DPL>& st, const float* qf, const Fmt& c, int key0, int kstride, int k1, int chunk) {
+// ANC (the ancestry form, include/omnibiote_hip_beam.h): c is the cache of the row's GROUP (its first row, the workgroup's head), key j is
+// read from the group's row anc[j], row_stride elements per row; an entry outside [0, group) is a key that is not there — as one at or
+// beyond k1, with its loads sent to the group's first row.  The UNROLL entries are loaded before the first K / V load is issued.
+template <class Fmt, int HS, bool TAIL, bool ANC = false>
+__device__ __forceinline__ void decode_keys(Part<Fmt::DPL>& st, const float* qf, const Fmt& c, int key0, int kstride, int k1, int chunk,
+                                            const int32_t* anc = nullptr, int group = 0, int64_t row_stride = 0) {
     constexpr int DPL = Fmt::DPL, LPR = HS / DPL;
     typename Fmt::Piece kr[DEC_UNROLL], vr[DEC_UNROLL];
     float ksc[DEC_UNROLL], vsc[DEC_UNROLL];   // (SCALED only)
     bool ok[DEC_UNROLL];
+    int from[DEC_UNROLL];                     // (ANC only)
+    if constexpr (ANC) {
+#pragma unroll
+        for (int u = 0; u < DEC_UNROLL; ++u) {
+            const int key = key0 + u * kstride;
+            from[u] = anc[(!TAIL || key < k1) ? key : k1 - 1];
+        }
+    }
 #pragma unroll
     for (int u = 0; u < DEC_UNROLL; ++u) {
         const int key = key0 + u * kstride;
         ok[u] = !TAIL || key < k1;
         const int64_t kk = ok[u] ? key : k1 - 1;   // (k1 - 1 >= k0: a workgroup with no key never gets here)
-        const int64_t off = kk * HS + chunk * DPL;   // in elements, of either format; one offset for both loads: K and V addresses are formed alike
+        int64_t off = kk * HS + chunk * DPL;   // in elements, of either format; one offset for both loads: K and V addresses are formed alike
+        if constexpr (ANC) {
+            const bool there = (uint32_t)from[u] < (uint32_t)group;
+            ok[u] = ok[u] && there;
+            off += (there ? (int64_t)from[u] : 0) * row_stride;
+        }
         kr[u] = Fmt::load(c.k + off);
         vr[u] = Fmt::load(c.v + off);
         if constexpr (Fmt::SCALED) {
@@ -179,7 +204,7 @@ __device__ __forceinline__ void decode_keys(Part<Fmt::DPL>& st, const float* qf,
         sc[u] = ok[u] ? d : -INFINITY;
         mx = fmaxf(mx, sc[u]);
     }
-    const float ms = (TAIL && mx == -INFINITY) ? 0.f : mx;
+    const float ms = ((TAIL || ANC) && mx == -INFINITY) ? 0.f : mx;
     const float alpha = __builtin_amdgcn_exp2f(st.m - ms);
     st.m = mx;
     st.l *= alpha;
@@ -204,11 +229,15 @@ __device__ __forceinline__ void decode_keys(Part<Fmt::DPL>& st, const float* qf,
 // key is loaded, the state stays (m = -inf, l = 0, acc = 0)); per is formed here from the row's own count.
 // PARTIAL (the suffix part of obte_attn_decode_shared, attention_shared.hip): the state leaves as a partial at one split too, o and lse
 // are not touched.
+// Fmt::ANC (CacheBf16Anc, with PARTIAL and not ROWS: the suffix part of obte_attn_decode_beam): rows_n is the ancestry table [B, T_max] and
+// rows_off the group size — the two arguments the uniform PARTIAL form leaves unused, so every instantiation keeps one signature and the
+// instantiations behind the other entry points keep their names and their code.
 template <class Fmt, int HS, bool ROWS, bool PARTIAL>
 __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16* __restrict__ q, int64_t q_ld, const void* __restrict__ cache,
                                                                       bf16* __restrict__ o, float* __restrict__ lse, float* __restrict__ part,
                                                                       int H, int64_t T_max, int64_t n_vec, int n_keys, int per, float qscale,
                                                                       const int32_t* __restrict__ rows_n, int rows_off) {
+    constexpr bool ANC = Fmt::ANC;
     constexpr int DPL = Fmt::DPL;
     constexpr int LPR = HS / DPL;      // lanes per key
     constexpr int G = 64 / LPR;        // keys per wave and load
@@ -229,7 +258,9 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16*
 #pragma unroll
     for (int j = 0; j < DPL; ++j) qf[j] *= qscale;
 
-    const Fmt c(const_cast<void*>(cache), n_vec, HS, bh, T_max);   // (read only here)
+    const Fmt c(const_cast<void*>(cache), n_vec, HS, ANC ? (int64_t)(b - b % rows_off) * H + h : (int64_t)bh, T_max);   // (read only here)
+    const int32_t* anc = ANC ? rows_n + (int64_t)b * T_max : nullptr;
+    const int64_t row_stride = (int64_t)H * T_max * HS;   // (ANC only)
     Part<DPL> st;
     st.m = -INFINITY; st.l = 0.f;
 #pragma unroll
@@ -239,8 +270,13 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16*
     constexpr int ROUND = KSTRIDE * DEC_UNROLL;         // keys of one workgroup round
     const int full_end = k0 + (k1 - k0) / ROUND * ROUND;
     int base = k0;
-    for (; base < full_end; base += ROUND) decode_keys<Fmt, HS, false>(st, qf, c, base + wave * G + grp, KSTRIDE, k1, chunk);
-    if (base < k1) decode_keys<Fmt, HS, true>(st, qf, c, base + wave * G + grp, KSTRIDE, k1, chunk);   // (workgroup-uniform)
+    if constexpr (ANC) {
+        for (; base < full_end; base += ROUND) decode_keys<Fmt, HS, false, true>(st, qf, c, base + wave * G + grp, KSTRIDE, k1, chunk, anc, rows_off, row_stride);
+        if (base < k1) decode_keys<Fmt, HS, true, true>(st, qf, c, base + wave * G + grp, KSTRIDE, k1, chunk, anc, rows_off, row_stride);
+    } else {
+        for (; base < full_end; base += ROUND) decode_keys<Fmt, HS, false>(st, qf, c, base + wave * G + grp, KSTRIDE, k1, chunk);
+        if (base < k1) decode_keys<Fmt, HS, true>(st, qf, c, base + wave * G + grp, KSTRIDE, k1, chunk);   // (workgroup-uniform)
+    }
 
     // the lane groups of a wave: exchange with the lane LPR, 2 LPR, .. 32 away (the same dims of another key's state)
 #pragma unroll
@@ -470,8 +506,15 @@ extern "C" int obte_attn_decode_splits(int64_t B, int32_t n_head, int32_t head_d
 
 // The kernel alone with PARTIAL (attention_shared.hip has checked every argument): BH rows of a bf16 cache of T_max positions, every row
 // over the keys [0, n_keys), `splits` partials per row to part in this file's layout, the keys divided as obte_attn_decode divides them.
+// ancestry (with its group size): the ancestry form, key j of row b read from row b - b % group + ancestry[b * T_max + j].
 void obte_attn_decode_partials(int head_dim, int BH, int H, int splits, const bf16* q, int64_t q_ld, const bf16* cache, int64_t T_max, int n_keys, float qscale,
-                               float* part, hipStream_t st) {
+                               float* part, hipStream_t st, const int32_t* ancestry, int group) {
+    if (ancestry) {
+        const decode_kernel_t kernel = decode_kernel_for<CacheBf16Anc, false, true>(head_dim);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)splits, (unsigned)BH), dim3(DEC_WAVES * 64), 0, st, q, q_ld, (const void*)cache, (bf16*)nullptr, (float*)nullptr, part, H,
+                           T_max, (int64_t)BH * T_max, n_keys, keys_per_split(n_keys, splits), qscale, ancestry, group);
+        return;
+    }
     launch_decode(false, true, head_dim, dim3((unsigned)splits, (unsigned)BH), st, q, q_ld, cache, nullptr, nullptr, part, H, T_max, n_keys,
                   keys_per_split(n_keys, splits), qscale, nullptr, 0);
 }

@@ -86,27 +86,31 @@ extern "C" int64_t obte_attn_decode_shared_ws_bytes(int64_t P, int64_t G, int32_
     return pre_bytes(P, G, n_head, head_dim, ps) + suf_bytes(P * G, n_head, head_dim, ss);
 }
 
-extern "C" int obte_attn_decode_shared(const obte_bf16* q, int64_t q_ld, const obte_bf16* prefix_cache, int64_t P, int64_t T_pre, int64_t n_prefix,
-                                       const obte_bf16* suffix_cache, int64_t G, int64_t T_suf, int64_t n_suffix, obte_bf16* o, float* lse, int32_t n_head,
-                                       int32_t head_dim, float scale, int32_t prefix_splits, int32_t suffix_splits, void* ws, int64_t ws_bytes, obte_stream s) {
-    OBTE_REQUIRE(q && prefix_cache && o && (suffix_cache || n_suffix == 0), "obte_attn_decode_shared: null pointer");
+namespace {
+
+// obte_attn_decode_shared (ancestry null) and obte_attn_decode_beam (include/omnibiote_hip_beam.h: the suffix launch reads slot j of row b
+// from the group's row ancestry[b][j]); who: the entry point named in an error
+int decode_shared_on(const char* who, bool beam, const obte_bf16* q, int64_t q_ld, const obte_bf16* prefix_cache, int64_t P, int64_t T_pre, int64_t n_prefix,
+                     const obte_bf16* suffix_cache, int64_t G, int64_t T_suf, int64_t n_suffix, const int32_t* ancestry, obte_bf16* o, float* lse, int32_t n_head,
+                     int32_t head_dim, float scale, int32_t prefix_splits, int32_t suffix_splits, void* ws, int64_t ws_bytes, obte_stream s) {
+    OBTE_REQUIRE(q && prefix_cache && o && (suffix_cache || n_suffix == 0) && (!beam || ancestry || n_suffix == 0), "%s: null pointer", who);
     OBTE_REQUIRE(shape_ok(P, G, n_head, head_dim) && T_pre > 0 && T_pre < (1ll << 24) && T_suf >= 0 && T_suf < (1ll << 24),
-                 "obte_attn_decode_shared: bad shape (head_dim 64 or 128, P * n_head and P * G * n_head <= 65535)");
-    OBTE_REQUIRE(n_prefix >= 1 && n_prefix <= T_pre, "obte_attn_decode_shared: n_prefix = %lld outside [1, T_pre = %lld]", (long long)n_prefix, (long long)T_pre);
-    OBTE_REQUIRE(n_suffix >= 0 && n_suffix <= T_suf, "obte_attn_decode_shared: n_suffix = %lld outside [0, T_suf = %lld]", (long long)n_suffix, (long long)T_suf);
-    OBTE_REQUIRE(q_ld >= (int64_t)n_head * head_dim && q_ld % 8 == 0, "obte_attn_decode_shared: q_ld must be a multiple of 8 and at least n_head * head_dim");
-    OBTE_REQUIRE((((uintptr_t)q | (uintptr_t)prefix_cache | (uintptr_t)suffix_cache | (uintptr_t)o) & 15) == 0 && ((uintptr_t)lse & 3) == 0,
-                 "obte_attn_decode_shared: q, both caches and o must be 16-byte aligned, lse 4-byte aligned");
-    OBTE_REQUIRE(prefix_splits >= 0 && prefix_splits <= OBTE_ATTN_SHARED_MAX_SPLITS, "obte_attn_decode_shared: prefix_splits = %d outside [0, %d]", prefix_splits,
+                 "%s: bad shape (head_dim 64 or 128, P * n_head and P * G * n_head <= 65535)", who);
+    OBTE_REQUIRE(n_prefix >= 1 && n_prefix <= T_pre, "%s: n_prefix = %lld outside [1, T_pre = %lld]", who, (long long)n_prefix, (long long)T_pre);
+    OBTE_REQUIRE(n_suffix >= 0 && n_suffix <= T_suf, "%s: n_suffix = %lld outside [0, T_suf = %lld]", who, (long long)n_suffix, (long long)T_suf);
+    OBTE_REQUIRE(q_ld >= (int64_t)n_head * head_dim && q_ld % 8 == 0, "%s: q_ld must be a multiple of 8 and at least n_head * head_dim", who);
+    OBTE_REQUIRE((((uintptr_t)q | (uintptr_t)prefix_cache | (uintptr_t)suffix_cache | (uintptr_t)o) & 15) == 0 && (((uintptr_t)lse | (uintptr_t)ancestry) & 3) == 0,
+                 "%s: q, both caches and o must be 16-byte aligned, lse%s 4-byte aligned", who, beam ? " and ancestry" : "");
+    OBTE_REQUIRE(prefix_splits >= 0 && prefix_splits <= OBTE_ATTN_SHARED_MAX_SPLITS, "%s: prefix_splits = %d outside [0, %d]", who, prefix_splits,
                  OBTE_ATTN_SHARED_MAX_SPLITS);
-    OBTE_REQUIRE(suffix_splits >= 0 && suffix_splits <= OBTE_ATTN_DECODE_MAX_SPLITS, "obte_attn_decode_shared: suffix_splits = %d outside [0, %d]", suffix_splits,
+    OBTE_REQUIRE(suffix_splits >= 0 && suffix_splits <= OBTE_ATTN_DECODE_MAX_SPLITS, "%s: suffix_splits = %d outside [0, %d]", who, suffix_splits,
                  OBTE_ATTN_DECODE_MAX_SPLITS);
     const int64_t B = P * G;
     const int ps = prefix_splits > 0 ? prefix_splits : obte_attn_shared_prefix_splits(P, G, n_head, head_dim, n_prefix);
     const int ss = n_suffix == 0 ? 0 : suffix_splits > 0 ? suffix_splits : obte_attn_decode_splits(B, n_head, head_dim, n_suffix);
     const int64_t pre = pre_bytes(P, G, n_head, head_dim, ps), need = pre + suf_bytes(B, n_head, head_dim, ss);
     OBTE_REQUIRE(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0,
-                 "obte_attn_decode_shared: %d prefix and %d suffix splits need a 16-byte aligned workspace of %lld bytes, got %lld", ps, ss, (long long)need,
+                 "%s: %d prefix and %d suffix splits need a 16-byte aligned workspace of %lld bytes, got %lld", who, ps, ss, (long long)need,
                  (long long)(ws ? ws_bytes : 0));
     const hipStream_t st = (hipStream_t)s;
     const float qscale = scale * 1.4426950408889634f;
@@ -117,8 +121,9 @@ extern "C" int obte_attn_decode_shared(const obte_bf16* q, int64_t q_ld, const o
     obte_attn_extend_group_partials(head_dim, P, (int)G, n_head, ps, (const bf16*)q, q_ld, (const bf16*)prefix_cache, T_pre, (int)n_prefix, qscale, pre_part, st);
     obte_prof_end(prof, st);
     if (ss > 0) {
-        prof = obte_prof_begin(st, 102, BH, n_suffix, head_dim);                   // cache bytes read = 4 * BH * n_suffix * head_dim
-        obte_attn_decode_partials(head_dim, BH, n_head, ss, (const bf16*)q, q_ld, (const bf16*)suffix_cache, T_suf, (int)n_suffix, qscale, suf_part, st);
+        prof = obte_prof_begin(st, beam ? 118 : 102, BH, n_suffix, head_dim);      // cache bytes read = 4 * BH * n_suffix * head_dim
+        obte_attn_decode_partials(head_dim, BH, n_head, ss, (const bf16*)q, q_ld, (const bf16*)suffix_cache, T_suf, (int)n_suffix, qscale, suf_part, st,
+                                  beam ? ancestry : nullptr, (int)G);
         obte_prof_end(prof, st);
     }
     prof = obte_prof_begin(st, 107, BH, ps + ss, head_dim);
@@ -129,6 +134,23 @@ extern "C" int obte_attn_decode_shared(const obte_bf16* q, int64_t q_ld, const o
         hipLaunchKernelGGL(attn_shared_combine_kernel<64>, dim3(BH), dim3(64), 0, st, (const float*)pre_part, (const float*)suf_part, (bf16*)o, lse, n_head, (int)G,
                            tiles, ps, ss);
     obte_prof_end(prof, st);
-    OBTE_CHECK_LAUNCH("obte_attn_decode_shared");
+    OBTE_CHECK_LAUNCH(who);
     return OBTE_OK;
+}
+
+}  // namespace
+
+extern "C" int obte_attn_decode_shared(const obte_bf16* q, int64_t q_ld, const obte_bf16* prefix_cache, int64_t P, int64_t T_pre, int64_t n_prefix,
+                                       const obte_bf16* suffix_cache, int64_t G, int64_t T_suf, int64_t n_suffix, obte_bf16* o, float* lse, int32_t n_head,
+                                       int32_t head_dim, float scale, int32_t prefix_splits, int32_t suffix_splits, void* ws, int64_t ws_bytes, obte_stream s) {
+    return decode_shared_on("obte_attn_decode_shared", false, q, q_ld, prefix_cache, P, T_pre, n_prefix, suffix_cache, G, T_suf, n_suffix, nullptr, o, lse, n_head,
+                            head_dim, scale, prefix_splits, suffix_splits, ws, ws_bytes, s);
+}
+
+extern "C" int obte_attn_decode_beam(const obte_bf16* q, int64_t q_ld, const obte_bf16* prefix_cache, int64_t P, int64_t T_pre, int64_t n_prefix,
+                                     const obte_bf16* suffix_cache, int64_t G, int64_t T_suf, int64_t n_suffix, const int32_t* ancestry, obte_bf16* o, float* lse,
+                                     int32_t n_head, int32_t head_dim, float scale, int32_t prefix_splits, int32_t suffix_splits, void* ws, int64_t ws_bytes,
+                                     obte_stream s) {
+    return decode_shared_on("obte_attn_decode_beam", true, q, q_ld, prefix_cache, P, T_pre, n_prefix, suffix_cache, G, T_suf, n_suffix, ancestry, o, lse, n_head,
+                            head_dim, scale, prefix_splits, suffix_splits, ws, ws_bytes, s);
 }

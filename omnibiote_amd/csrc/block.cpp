@@ -501,6 +501,8 @@ struct InferAttention {
     // the four weights as e4m3 codes and row scales (obte_block_step_w8, include/omnibiote_hip_w8.h), in the order of the products below; null:
     // bf16 from the descriptor, which holds the dequantised weights either way
     const void* const* w8_codes = nullptr; const float* const* w8_scales = nullptr;
+    // with prefix_cache: suffix slot j of row b is read from the group's row ancestry[b][j] (obte_block_decode_beam, include/omnibiote_hip_beam.h)
+    const int32_t* ancestry = nullptr;
 };
 int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const InferLayout& w, int64_t M, const float* rope_cos,
                    const float* rope_sin, int64_t rope_T, const InferAttention& at, obte_stream s) {
@@ -522,7 +524,10 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
         const int64_t q_ld = 3 * (int64_t)C;
         const char* who = at.kv8 || at.pos_rows ? at.who : "obte_attn_decode";   // (the uniform bf16 step's attention refuses under its own name)
         TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, s));
-        if (at.prefix_cache)    // the group's prefix once per 32 rows, then the row's own slots 0 .. pos
+        if (at.prefix_cache && at.ancestry)   // the same, the slots 0 .. pos read through the ancestry table
+            TRY(obte_attn_decode_beam(w.qkv, q_ld, at.prefix_cache, at.P, at.T_pre, at.n_prefix, at.kv_cache, d->B / at.P, at.T_max, at.pos + 1, at.ancestry, w.att, nullptr, H,
+                                      hs, scale, 0, 0, at.dec_ws, at.dec_ws_bytes, s));
+        else if (at.prefix_cache)    // the group's prefix once per 32 rows, then the row's own slots 0 .. pos
             TRY(obte_attn_decode_shared(w.qkv, q_ld, at.prefix_cache, at.P, at.T_pre, at.n_prefix, at.kv_cache, d->B / at.P, at.T_max, at.pos + 1, w.att, nullptr, H, hs,
                                         scale, 0, 0, at.dec_ws, at.dec_ws_bytes, s));
         else if (!at.decode)
@@ -680,33 +685,51 @@ extern "C" int64_t obte_block_decode_shared_ws_bytes(int64_t P, int64_t G, int32
     return part > 0 ? base + align256(part) : 0;
 }
 
+namespace {
+
 // obte_block_decode's sequence with the cache in two parts: the new position joins the row's suffix cache at slot suf_pos, and is rotated
-// as absolute position n_prefix + suf_pos
-extern "C" int obte_block_decode_shared(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const obte_bf16* prefix_cache, int64_t P, int64_t T_pre,
-                                        int64_t n_prefix, obte_bf16* suffix_cache, int64_t T_suf, int64_t suf_pos, void* ws, int64_t ws_bytes, obte_stream s) {
-    const char* who = "obte_block_decode_shared";
+// as absolute position n_prefix + suf_pos.  beam (obte_block_decode_beam): the suffix slots are read through `ancestry`
+int decode_shared_step(const char* who, bool beam, const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const obte_bf16* prefix_cache, int64_t P, int64_t T_pre,
+                       int64_t n_prefix, obte_bf16* suffix_cache, int64_t T_suf, int64_t suf_pos, const int32_t* ancestry, void* ws, int64_t ws_bytes, obte_stream s) {
     TRY(check_desc(who, d));
     OBTE_REQUIRE(d->T == 1, "%s: one new position per row (T = 1), got T = %lld", who, (long long)d->T);
     if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
         obte_set_error("%s: key_ranges, mask, query_bounds, out_rows and dropout_p must be NULL / 0 (a new position sees every cached one up to itself)", who);
         return OBTE_EUNSUPPORTED;
     }
-    OBTE_REQUIRE(x && y_out && prefix_cache && suffix_cache && ws, "%s: null pointer", who);
+    OBTE_REQUIRE(x && y_out && prefix_cache && suffix_cache && ws && (!beam || ancestry), "%s: null pointer", who);
     OBTE_REQUIRE(P >= 1 && d->B % P == 0, "%s: the %lld rows are not P = %lld groups of equal size", who, (long long)d->B, (long long)P);
     OBTE_REQUIRE(T_pre >= 1 && n_prefix >= 1 && n_prefix <= T_pre, "%s: n_prefix = %lld outside [1, T_pre = %lld]", who, (long long)n_prefix, (long long)T_pre);
     OBTE_REQUIRE(suf_pos >= 0 && suf_pos < T_suf, "%s: suffix slot %lld outside the suffix cache's [0, %lld)", who, (long long)suf_pos, (long long)T_suf);
     OBTE_REQUIRE((((uintptr_t)prefix_cache | (uintptr_t)suffix_cache) & 15) == 0, "%s: both caches must be 16-byte aligned", who);
+    OBTE_REQUIRE(((uintptr_t)ancestry & 3) == 0, "%s: ancestry must be 4-byte aligned", who);
     const int C = d->n_embd, H = d->n_head, hs = C / H;
     const int64_t G = d->B / P;
     const int64_t att_bytes = obte_attn_decode_shared_ws_bytes(P, G, H, hs, 0, 0);
     OBTE_REQUIRE(att_bytes > 0 && T_pre < (1ll << 24) && T_suf < (1ll << 24), "%s: bad shape (P * n_head and B * n_head <= 65535)", who);
     const InferLayout w(d->B, 1, C, H, ws);
     const int64_t need = w.total + align256(att_bytes);
-    OBTE_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes, obte_block_decode_shared_ws_bytes() asks for %lld", who, (long long)ws_bytes, (long long)need);
+    OBTE_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes, %s_ws_bytes() asks for %lld", who, (long long)ws_bytes, who, (long long)need);
     InferAttention at = {suffix_cache, T_suf, suf_pos, (char*)ws + w.total, att_bytes, nullptr, 1, true, false, who};
-    at.prefix_cache = prefix_cache; at.P = P; at.T_pre = T_pre; at.n_prefix = n_prefix;
+    at.prefix_cache = prefix_cache; at.P = P; at.T_pre = T_pre; at.n_prefix = n_prefix; at.ancestry = beam ? ancestry : nullptr;
     const int64_t row = (n_prefix + suf_pos) * (hs / 2);   // c_attn rotates every row by the tables' row n_prefix + suf_pos (rope_T = 1)
     return infer_sequence(d, x, y_out, w, d->B, d->rope_cos + row, d->rope_sin + row, 1, at, s);
+}
+
+}  // namespace
+
+extern "C" int obte_block_decode_shared(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const obte_bf16* prefix_cache, int64_t P, int64_t T_pre,
+                                        int64_t n_prefix, obte_bf16* suffix_cache, int64_t T_suf, int64_t suf_pos, void* ws, int64_t ws_bytes, obte_stream s) {
+    return decode_shared_step("obte_block_decode_shared", false, d, x, y_out, prefix_cache, P, T_pre, n_prefix, suffix_cache, T_suf, suf_pos, nullptr, ws, ws_bytes, s);
+}
+
+// the same step with the suffix slots read through an ancestry table (include/omnibiote_hip_beam.h): the same workspace
+extern "C" int64_t obte_block_decode_beam_ws_bytes(int64_t P, int64_t G, int32_t n_embd, int32_t n_head) { return obte_block_decode_shared_ws_bytes(P, G, n_embd, n_head); }
+
+extern "C" int obte_block_decode_beam(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const obte_bf16* prefix_cache, int64_t P, int64_t T_pre,
+                                      int64_t n_prefix, obte_bf16* suffix_cache, int64_t T_suf, int64_t suf_pos, const int32_t* ancestry, void* ws, int64_t ws_bytes,
+                                      obte_stream s) {
+    return decode_shared_step("obte_block_decode_beam", true, d, x, y_out, prefix_cache, P, T_pre, n_prefix, suffix_cache, T_suf, suf_pos, ancestry, ws, ws_bytes, s);
 }
 
 extern "C" int obte_block_bwd_acc(const obte_block_desc* d, const obte_bf16* x, const obte_bf16* dy, const void* act, void* ws,

@@ -15,6 +15,7 @@
 #include "../../include/omnibiote_hip_kv8.h"
 #include "../../include/omnibiote_hip_shared.h"
 #include "../../include/omnibiote_hip_w8.h"
+#include "../../include/omnibiote_hip_beam.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -106,7 +107,7 @@ constexpr int DEC_PAD = 4;       // a partial of the attention is hs + 4 floats 
 // ---- a prefix cache shared by groups of rows (attention_shared.hip, include/omnibiote_hip_shared.h): the two partial-only launches
 // attn_decode_kernel<.., PARTIAL> (attention_decode.hip): BH rows over the keys [0, n_keys) of their own cache row, `splits` partials each
 void obte_attn_decode_partials(int head_dim, int BH, int H, int splits, const __bf16* q, int64_t q_ld, const __bf16* cache, int64_t T_max, int n_keys, float qscale,
-                               float* part, hipStream_t st);
+                               float* part, hipStream_t st, const int32_t* ancestry = nullptr, int group = 0);   // (ancestry: include/omnibiote_hip_beam.h)
 // attn_extend_kernel<.., GROUP> (attention_extend.hip): the G queries at rows p G + j of q over the keys [0, n_prefix) of cache row p, `splits`
 // partials per (p, h, 32-query tile); a partial is obte_ext_part_floats() floats, [hs / 2 + 2][64 lanes] = O^T, m, l
 void obte_attn_extend_group_partials(int head_dim, int64_t P, int G, int H, int splits, const __bf16* q, int64_t q_ld, const __bf16* cache, int64_t T_pre, int n_prefix,

@@ -27,6 +27,7 @@ Contract notes (each mirrors a reference behaviour):
 from __future__ import annotations
 
 import copy
+import math
 import warnings
 import weakref
 from dataclasses import dataclass
@@ -1515,6 +1516,15 @@ class SequenceScore(NamedTuple):
     count: torch.Tensor
 
 
+class BeamResult(NamedTuple):
+    """What ``OmniBioTA.generate_beam`` returns: per prompt its beams, best first — ``sequences`` (P, W, T0 + n) int64 (the prompt, the new
+    tokens, ``pad_token`` behind a beam's first EOS), ``scores`` (P, W) fp32, the raw sums of the new tokens' log-probabilities (-inf: a
+    dead beam), and ``lengths`` (P, W) int64, the new tokens up to and including the first EOS."""
+    sequences: torch.Tensor
+    scores: torch.Tensor
+    lengths: torch.Tensor
+
+
 class OmniBioTA(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -2195,6 +2205,90 @@ class OmniBioTA(nn.Module):
                 break
             logits = self.decode_step(nxt, cache, **step)
         return torch.cat(out, dim=1)
+
+    @torch.no_grad()
+    def generate_beam(self, idx, max_new_tokens, num_beams=4, eos_token=None, pad_token=None, length_penalty=0.0, allowed_tokens=None):
+        """Beam search: the ``num_beams`` = W most probable continuations of every prompt of ``idx`` (P, T0) int64 that a beam of that width
+        finds, deterministic.  Returns a ``BeamResult`` (sequences (P, W, T0 + n), scores (P, W), lengths (P, W)), n the steps taken.
+
+        The W beams of a prompt are the rows of one group of a ``SharedPrefixCache(self, P, W, T0, max_new_tokens)``: the prompt is
+        prefilled and stored once and read once per step.  After the prefill the beams are identical, so beam 0 starts at score 0 and
+        the others at -inf.  Every step is one ``ops.beam_select`` (include/omnibiote_hip_beam.h: per prompt the W best of the W * V
+        candidates ``score + log_softmax``, equal scores to the lower beam, then the lower token), the embedding of the chosen tokens,
+        ``ops.block_decode_beam`` per layer and the readout.  No key or value is moved when a beam continues another: the selection
+        keeps an ancestry table — which row wrote suffix slot j of the history beam b now continues — in two (P * W, max_new_tokens)
+        int32 buffers used in turn, and the attention reads through it.  The result is one gather through the last table.
+
+        The rule: the selection inside the loop compares RAW sums of log-probabilities; a beam that has produced ``eos_token`` is finished,
+        keeps its slot and its frozen score and competes with it against the running beams (it proposes itself as its only
+        continuation).  With an ``eos_token`` the loop reads ``done.all()`` once per step — the only host synchronisation — and stops
+        once every beam of every prompt is finished; without one nothing is read.  ``lengths`` counts a beam's new tokens up to and
+        including its first EOS, the positions behind it hold ``pad_token`` (default: ``eos_token`` if given, else 0).  The beams of a
+        prompt come back ordered by ``scores / lengths ** length_penalty``, descending, by a stable sort of the finished result
+        (``length_penalty = 0``: by raw score, the order the last selection left); a dead beam — fewer than W candidates existed, as
+        under a small ``allowed_tokens`` — has score -inf and comes last.
+
+        ``allowed_tokens``: token ids, a bool (V,) mask or a bool (P, V) mask, one row per prompt; everything else never enters a beam.
+        ``eos_token`` is not added.  ValueError before anything is launched: a model that is not autoregressive, ``num_beams`` outside
+        [1, 32], T0 + max_new_tokens > block_size, an ``eos_token`` outside the vocabulary, an allowed set that is empty.  Not built:
+        ``lengths=``, the fp8 cache, ``weights=``, penalties, ``min_new_tokens``, a temperature, ``loop=``, diverse or length-pruned beams,
+        more than 32 beams, a vocabulary above 65 536."""
+        self._check_generation("generate_beam", 0)
+        W = num_beams
+        if isinstance(W, bool) or not isinstance(W, int) or not 1 <= W <= ops.BEAM_MAX_WIDTH:
+            raise ValueError(f"OmniBioTA.generate_beam: num_beams must be an integer in [1, {ops.BEAM_MAX_WIDTH}], got {W!r}")
+        if idx.dim() != 2 or idx.shape[0] < 1:
+            raise ValueError(f"OmniBioTA.generate_beam: idx must be (P, T0), got {tuple(idx.shape)}")
+        P, t0 = idx.shape
+        if t0 == 0:
+            raise ValueError("OmniBioTA.generate_beam: the prompt is empty")
+        n = int(max_new_tokens)
+        if n < 0 or t0 + n > self.config.block_size:
+            raise ValueError(f"OmniBioTA.generate_beam: {t0} prompt tokens + {max_new_tokens} new ones exceed block_size = {self.config.block_size}")
+        V = self.config.vocab_size
+        if eos_token is not None and not 0 <= int(eos_token) < V:
+            raise ValueError(f"OmniBioTA.generate_beam: eos_token {eos_token} outside [0, vocab_size = {V})")
+        if not math.isfinite(float(length_penalty)):
+            raise ValueError(f"OmniBioTA.generate_beam: length_penalty must be a finite number, got {length_penalty!r}")
+        con = TokenConstraint.of("generate_beam", allowed_tokens, 0, n, eos_token, P, V, idx.device)
+        dev, B = idx.device, P * W
+        score = torch.zeros((P, W), dtype=torch.float32, device=dev)
+        score[:, 1:] = float("-inf")
+        score = score.view(B)
+        if n == 0:
+            return BeamResult(idx.unsqueeze(1).repeat(1, W, 1), score.view(P, W), torch.zeros((P, W), dtype=torch.int64, device=dev))
+        cache = SharedPrefixCache(self, P, W, t0, n)
+        logits = self.prefill(idx, cache)
+        packed = None if con is None else (con.packed if con.packed.dim() == 1 else con.packed.repeat_interleave(W, dim=0))
+        done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        ancestry = [torch.zeros((B, n), dtype=torch.int32, device=dev) for _ in range(2)]
+        hist = torch.zeros((n, B), dtype=torch.int64, device=dev)
+        parent = torch.empty(B, dtype=torch.int32, device=dev)
+        token = torch.empty(B, dtype=torch.int64, device=dev)
+        ws = ops.beam_select_workspace(P, W, dev)
+        wte = self.transformer.wte.weight
+        steps = 0
+        for i in range(n):
+            table = ancestry[(i + 1) & 1]
+            ops.beam_select(logits, score, done, ancestry[i & 1], table, hist, i, W, eos_token=eos_token, allowed_packed=packed, parent=parent, token=token,
+                            score_out=score, done_out=done, ws=ws)
+            steps = i + 1
+            if steps == n or (eos_token is not None and bool(done.all())):
+                break
+            x = ops.embedding_fwd(token, wte)
+            for block, (prefix, suffix) in zip(self.transformer.h, cache.layers):
+                ops.block_decode_beam(x, self._block_params(block), block.attn.rope(), self.config.n_head, prefix, P, cache.prefix_len, cache.n_prefix, suffix,
+                                      cache.max_new, i, table, ws=cache.decode_ws, out=x)
+            cache.advance(1)
+            logits = self._readout_rows(self.transformer.ln_f(x))
+        from .sampling import beam_sequences_reference
+        pad = pad_token if pad_token is not None else (eos_token if eos_token is not None else 0)
+        new, lengths = beam_sequences_reference(hist, ancestry[steps & 1], steps, W, eos_token, pad)
+        score, lengths, new = score.view(P, W), lengths.view(P, W), new.view(P, W, steps)
+        key = score / lengths.clamp(min=1).to(torch.float32) ** float(length_penalty)
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices
+        seq = torch.cat([idx.unsqueeze(1).expand(P, W, t0), new.gather(1, order.unsqueeze(2).expand(P, W, steps))], dim=2)
+        return BeamResult(seq, score.gather(1, order), lengths.gather(1, order))
 
     def _device_loop(self, cache, logits, max_new_tokens, temperature, top_k, top_p, us, eos_token, loop, con=None, weights=None, pen=None):
         """``generate``'s token loop as a ``DecodeLoop`` behind the prefill that gave ``logits``: (tokens (B, S), n_new (B,))"""

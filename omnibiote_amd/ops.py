@@ -1534,6 +1534,107 @@ def block_decode_shared(x, params, rope, H, prefix_cache, P, T_pre, n_prefix, su
         cache=suffix_cache, T_max=T_suf, at=n_prefix + suf_pos, one=True)
 
 
+# ---- beam search: the selection, and the shared-prefix step through an ancestry table (include/omnibiote_hip_beam.h) ----
+BEAM_MAX_WIDTH = L.BEAM_MAX_WIDTH
+
+
+def beam_select_workspace(P, W, device) -> torch.Tensor:
+    nbytes = int(L.lib().obte_beam_select_ws_bytes(P, W))
+    if nbytes <= 0:
+        raise RuntimeError(f"beam_select: unsupported shape (P {P}, W {W}): P >= 1, 1 <= W <= {BEAM_MAX_WIDTH}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def beam_select(logits, score, done, ancestry_in, ancestry_out, token_hist, slot, W, eos_token=None, allowed_packed=None, parent=None, token=None,
+                score_out=None, done_out=None, ws=None):
+    """One beam step for the P = B / W groups of ``logits`` (B, V) bf16, row b = p * W + g (obte_beam_select_bf16; the rule:
+    include/omnibiote_hip_beam.h, restated in float64 by sampling.beam_step_reference): per group the W best of the W * V candidates
+    ``score[b] + log_softmax(logits[b])[v]``, equal scores to the lower beam and then the lower token, in two launches and one read of the
+    logits.  ``score`` (B,) fp32, ``done`` (B,) uint8, ``ancestry_in`` / ``ancestry_out`` (B, T_suf) int32 (two buffers), ``token_hist``
+    (T_suf, B) int64, ``slot`` the suffix slot the chosen tokens will occupy.  ``allowed_packed``: uint8 (n,) or (B, n), n >= ceil(V / 8),
+    as ``pack_token_mask`` makes it.  ``score_out`` / ``done_out`` may be ``score`` / ``done`` themselves.  Returns (parent (B,) int32,
+    token (B,) int64, score_out, done_out); ancestry_out[:, :slot + 1] and token_hist[slot] are written."""
+    _need(logits, "logits", contiguous=False)
+    if logits.dim() != 2 or logits.stride(1) != 1 and logits.shape[1] > 1:
+        raise ValueError(f"beam_select: logits must be (B, V) with last-dimension stride 1, got {tuple(logits.shape)} strides {logits.stride()}")
+    B, V = logits.shape
+    if W < 1 or B % W:
+        raise ValueError(f"beam_select: {B} rows are not groups of W = {W}")
+    dev = logits.device
+    _need(score, "score", torch.float32); _need(done, "done", torch.uint8)
+    _need(ancestry_in, "ancestry_in", torch.int32); _need(ancestry_out, "ancestry_out", torch.int32); _need(token_hist, "token_hist", torch.int64)
+    T_suf = ancestry_in.shape[1]
+    if ancestry_in.shape != (B, T_suf) or ancestry_out.shape != (B, T_suf) or token_hist.shape != (T_suf, B) or score.shape != (B,) or done.shape != (B,):
+        raise ValueError(f"beam_select: score, done ({B},), ancestry_in, ancestry_out ({B}, T_suf) and token_hist (T_suf, {B}) do not fit")
+    ld_mask = 0
+    if allowed_packed is not None:
+        _need(allowed_packed, "allowed_packed", torch.uint8, contiguous=False)
+        nb = (V + 7) // 8
+        if allowed_packed.dim() == 2 and allowed_packed.shape[0] == B and allowed_packed.shape[1] >= nb and allowed_packed.stride(1) == 1:
+            ld_mask = allowed_packed.stride(0)
+        elif not (allowed_packed.dim() == 1 and allowed_packed.shape[0] >= nb and allowed_packed.stride(0) == 1):
+            raise ValueError(f"beam_select: allowed_packed must be uint8 (n,) or ({B}, n) with n >= {nb}, got {tuple(allowed_packed.shape)}")
+    parent = torch.empty(B, dtype=torch.int32, device=dev) if parent is None else parent
+    token = torch.empty(B, dtype=torch.int64, device=dev) if token is None else token
+    score_out = torch.empty(B, dtype=torch.float32, device=dev) if score_out is None else score_out
+    done_out = torch.empty(B, dtype=torch.uint8, device=dev) if done_out is None else done_out
+    if ws is None:
+        ws = beam_select_workspace(B // W, W, dev)
+    L.check(L.lib().obte_beam_select_bf16(_ptr(logits), logits.stride(0), B // W, W, V, _ptr(score), _ptr(done),
+                                          -1 if eos_token is None else int(eos_token), _ptr(allowed_packed), ld_mask, _ptr(ancestry_in), T_suf, int(slot),
+                                          _ptr(parent), _ptr(token), _ptr(score_out), _ptr(done_out), _ptr(ancestry_out), _ptr(token_hist), _ptr(ws), ws.numel(),
+                                          _stream()), "obte_beam_select_bf16")
+    return parent, token, score_out, done_out
+
+
+def attn_decode_beam(q, prefix_cache, P, T_pre, n_prefix, suffix_cache, G, T_suf, n_suffix, ancestry, H, hs, scale, prefix_splits=0, suffix_splits=0, q_ld=None,
+                     ws=None, out=None, lse=None):
+    """``attn_decode_shared`` with the suffix slots read through ``ancestry`` (B, T_suf) int32 (obte_attn_decode_beam): slot j of row
+    b = p * G + g comes from suffix-cache row p * G + ancestry[b, j]; an entry outside [0, G) is a key that is not there.  The identity
+    table gives attn_decode_shared's bits; a valid table those of attn_decode_shared on the suffix cache gathered by it."""
+    _need(q, "q", contiguous=False); _need(prefix_cache, "prefix_cache")
+    B = P * G
+    q_ld = q.shape[-1] if q_ld is None else q_ld
+    assert prefix_cache.numel() * 2 == L.lib().obte_kv_cache_bytes(P, T_pre, H, hs)
+    if suffix_cache is not None:
+        _need(suffix_cache, "suffix_cache")
+        assert suffix_cache.numel() * 2 == L.lib().obte_kv_cache_bytes(B, T_suf, H, hs)
+    if ancestry is not None:
+        _need(ancestry, "ancestry", torch.int32)
+        assert ancestry.shape == (B, T_suf)
+    o = torch.empty((B, H * hs), dtype=bf16, device=q.device) if out is None else out
+    lse = torch.empty((B, H), dtype=torch.float32, device=q.device) if lse is None else lse
+    if ws is None:
+        ws = torch.empty(max(int(L.lib().obte_attn_decode_shared_ws_bytes(P, G, H, hs, int(prefix_splits), int(suffix_splits))), 16), dtype=torch.uint8,
+                         device=q.device)
+    L.check(L.lib().obte_attn_decode_beam(_ptr(q), q_ld, _ptr(prefix_cache), P, T_pre, int(n_prefix), _ptr(suffix_cache), G, T_suf, int(n_suffix), _ptr(ancestry),
+                                          _ptr(o), _ptr(lse), H, hs, float(scale), int(prefix_splits), int(suffix_splits), _ptr(ws), ws.numel(), _stream()),
+            "obte_attn_decode_beam")
+    return o, lse
+
+
+def block_decode_beam_workspace(P, G, Cc, H, device) -> torch.Tensor:
+    nbytes = int(L.lib().obte_block_decode_beam_ws_bytes(P, G, Cc, H))
+    if nbytes <= 0:
+        raise RuntimeError(f"block_decode_beam: unsupported shape (P {P}, G {G}, n_embd {Cc}, n_head {H}): head size 64 or 128, "
+                           "n_embd a multiple of 64 and <= 4096, P * G * n_head <= 65535")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def block_decode_beam(x, params, rope, H, prefix_cache, P, T_pre, n_prefix, suffix_cache, T_suf, suf_pos, ancestry, ws=None, out=None):
+    """``block_decode_shared`` with the suffix slots [0, suf_pos] read through ``ancestry`` (B, T_suf) int32 (obte_block_decode_beam).  Row b
+    stores its new key and value at (row b, slot suf_pos); ancestry[b, suf_pos] must already be b % G (``beam_select`` at that slot wrote it)."""
+    _need(prefix_cache, "prefix_cache"); _need(ancestry, "ancestry", torch.int32)
+    B, Cc = x.shape
+    if P < 1 or B % P:
+        raise ValueError(f"block_decode_beam: {B} rows are not P = {P} groups of equal size")
+    assert prefix_cache.numel() * 2 == L.lib().obte_kv_cache_bytes(P, T_pre, H, Cc // H) and ancestry.shape == (B, T_suf)
+    return _block_call(x, params, rope, H, ws, out, lambda B_, T_, C_, H_, dev: block_decode_beam_workspace(P, B_ // P, C_, H_, dev), lambda d, y, w: L.check(
+        L.lib().obte_block_decode_beam(d, _ptr(x), _ptr(y), _ptr(prefix_cache), P, T_pre, int(n_prefix), _ptr(suffix_cache), T_suf, int(suf_pos), _ptr(ancestry),
+                                       _ptr(w), w.numel(), _stream()), "obte_block_decode_beam"),
+        cache=suffix_cache, T_max=T_suf, at=n_prefix + suf_pos, one=True)
+
+
 def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None, dropout_p=0.0, dropout_seed=0, ln_partials=None,
               ln_partial_mode=0, out_rows=None, dy_masked=None, dx_mask_seed=None, acc32=None, acc32_mode=0):
     """accumulate_into: optional list of 6 tensors-or-None (same order as params).  When the four matrix entries are all

@@ -463,3 +463,93 @@ def fill_commit_reference(rows, seg_off, tokens, logprob, take, order, seed, idx
         rest = pos[~sel]
         nxt[sn[b]:sn[b] + rest.numel()] = rest
     return idx, out_logprob, nxt
+
+
+# ---- beam search (include/omnibiote_hip_beam.h) ------------------------------------------------------------------------------------
+def beam_step_reference(logits, score, done, ancestry, slot, W, eos_token=None, allowed=None):
+    """One beam step, obte_beam_select_bf16's rule in float64 on the CPU.  ``logits`` (B, V), B = P * W rows, row b = p * W + g; ``score``
+    (B,), ``done`` (B,), ``ancestry`` (B, T_suf) integers, ``slot`` the suffix slot of the chosen tokens; ``allowed``: None, bool (V,) or (B, V).
+
+      - a live row (score finite, not done) proposes (b, v) for every column v that is not NaN, not -inf and not excluded, with
+        S = score[b] + (x_v - max_b) - ln Z_b, Z_b the sum of exp(x - max_b) over the row's candidate columns; a column whose S is -inf
+        as an fp32 number is no candidate;
+      - a done row with a finite score proposes (b, eos_token) alone (token 0 without an eos_token) with S = score[b];
+      - a dead row (score not finite) and a row without a candidate column propose nothing;
+      - per group the W best by S descending take the group's rows in rank order, equal S to the lower beam, then the lower token;
+      - done_out = done[parent] or token == eos_token; a rank without a candidate is dead: parent the row itself, token eos_token (0
+        if none), score -inf, done;
+      - ancestry_out[b, j] = ancestry[parent[b], j] for j < slot and ancestry_out[b, slot] = b % W.
+
+    Returns (parent (B,) int64 global rows, token (B,) int64, score_out (B,) float64, done_out (B,) bool, ancestry_out (B, slot + 1)
+    int64, sorted): ``sorted`` is, per group, the float64 scores of its best candidates in that order — the W that placed and the next
+    one where there is one, for a test's margins."""
+    x = torch.as_tensor(logits).detach().cpu().double()
+    b, v = x.shape
+    if W < 1 or b % W:
+        raise ValueError(f"beam_step_reference: {b} rows are not groups of W = {W}")
+    score = torch.as_tensor(score).detach().cpu().double().reshape(b)
+    done = torch.as_tensor(done).detach().cpu().reshape(b) != 0
+    anc = torch.as_tensor(ancestry).detach().cpu().to(torch.int64)
+    eos = -1 if eos_token is None else int(eos_token)
+    fill = 0 if eos < 0 else eos
+    ok = ~(torch.isnan(x) | (x == float("-inf")))
+    if allowed is not None:
+        ok = ok & torch.as_tensor(allowed).detach().cpu().bool().expand(b, v)
+    xm = torch.where(ok, x, torch.full_like(x, float("-inf")))
+    cands = []                                                   # per row: [(S, beam, token)]
+    for r in range(b):
+        g, out = r % W, []
+        if not torch.isfinite(score[r]):
+            pass
+        elif done[r]:
+            out.append((float(score[r]), g, fill))
+        elif bool(ok[r].any()):
+            mx = xm[r].max()
+            d = torch.where(xm[r] == mx, torch.zeros_like(xm[r]), xm[r] - mx)          # (the maximum's own x - max is 0: inf - inf is never formed)
+            d = torch.where(ok[r], d, torch.full_like(d, float("-inf")))
+            s = score[r] + d - torch.log(torch.exp(d).sum())
+            top = torch.sort(s, descending=True, stable=True)                          # stable: equal S to the lower token
+            for sv, tv in zip(top.values[:W + 1].tolist(), top.indices[:W + 1].tolist()):
+                if ok[r, tv] and torch.tensor(sv, dtype=torch.float32).item() != float("-inf"):
+                    out.append((sv, g, tv))
+        cands.append(out)
+    parent = torch.empty(b, dtype=torch.int64)
+    token = torch.empty(b, dtype=torch.int64)
+    s_out = torch.empty(b, dtype=torch.float64)
+    d_out = torch.empty(b, dtype=torch.bool)
+    a_out = torch.empty((b, slot + 1), dtype=torch.int64)
+    ranked = []
+    for p in range(b // W):
+        row0 = p * W
+        group = sorted((c for r in range(row0, row0 + W) for c in cands[r]), key=lambda c: (-c[0], c[1], c[2]))
+        ranked.append(torch.tensor([c[0] for c in group[:W + 1]], dtype=torch.float64))
+        for r in range(W):
+            i = row0 + r
+            if r < len(group):
+                sv, g, tv = group[r]
+                parent[i], token[i], s_out[i], d_out[i] = row0 + g, tv, sv, bool(done[row0 + g]) or tv == eos
+            else:
+                parent[i], token[i], s_out[i], d_out[i] = i, fill, float("-inf"), True
+            a_out[i, :slot] = anc[parent[i], :slot]
+            a_out[i, slot] = r
+    return parent, token, s_out, d_out, a_out, ranked
+
+
+def beam_sequences_reference(token_hist, ancestry, n, W, eos_token=None, pad_token=None):
+    """The new tokens of every beam from a beam search's two tables: ``token_hist`` (T_suf, B) — row j the tokens chosen at step j, by
+    the row they went to — and the final ``ancestry`` (B, T_suf) — the local beam that held row b's token of step j: sequences[b, j] =
+    token_hist[j, b - b % W + ancestry[b, j]] for j < n.  ``lengths`` counts the tokens up to and including the first ``eos_token`` (n
+    without one); the positions behind it hold ``pad_token`` (default: eos_token, or 0).  Returns (sequences (B, n) int64, lengths (B,) int64)."""
+    th = torch.as_tensor(token_hist).to(torch.int64)
+    anc = torch.as_tensor(ancestry).to(torch.int64)
+    b = anc.shape[0]
+    rows = (torch.arange(b, device=anc.device) // W * W).unsqueeze(1) + anc[:, :n]                     # (B, n): the row that held the token
+    seq = th[:n].t().gather(0, rows) if n > 0 else torch.empty((b, 0), dtype=torch.int64, device=anc.device)
+    lengths = torch.full((b,), n, dtype=torch.int64, device=anc.device)
+    if eos_token is not None and n > 0:
+        hit = seq == int(eos_token)
+        first = torch.where(hit.any(dim=1), hit.int().argmax(dim=1) + 1, lengths)
+        lengths = first
+        pad = int(eos_token) if pad_token is None else int(pad_token)
+        seq = torch.where(torch.arange(n, device=anc.device).unsqueeze(0) >= lengths.unsqueeze(1), torch.full_like(seq, pad), seq)
+    return seq, lengths
