@@ -103,7 +103,7 @@ def test_reference_reproduces_the_ragged_loop(eos, n_steps):
     stream = _stream(3)
     if n_steps == STEPS and eos is not None:
         stream[6, 2], stream[7, 4] = EOS, EOS                                       # every row finishes: the loop stops at step 8
-    # _generate_ragged's bookkeeping, restated: tokens, valid, park, and decode_step's advance
+    # the bookkeeping of generate's host loop behind ragged prompts, restated: tokens, valid, park, and decode_step's advance
     cache = CachePositions(B, 64)
     cache.reset(max(LENS), torch.tensor(LENS, dtype=I32), min(LENS))
     tokens, valid, done, seen = [], [], torch.zeros(B, dtype=torch.bool), {}

@@ -334,6 +334,22 @@ def test_neutral_penalties_take_the_entry_point_the_call_took_before(stub):
     assert b[8:13] == (None, 0, -1, None, 0) and b[13:22] == (None, 0, None, 0, ids.data_ptr(), 5, n.data_ptr(), 0, 5) and b[22:26] == (2.0, 0.5, 0.0, 0.0)
 
 
+def test_spec_verify_takes_the_constrained_entry_point_only_when_a_restriction_is_given(stub):
+    """what lets the speculative loop pass an empty keyword dict for a call that restricts nothing"""
+    from omnibiote_amd import ops
+    p, x = torch.zeros((3, 3, 64), dtype=BF), torch.zeros((3, 2), dtype=I64)
+
+    def verified(**kw):                                                                      # (the workspace query is a call of the table too)
+        stub.calls.clear()
+        ops.spec_verify(p, None, x, **kw)
+        return [(name, len(args)) for name, args in stub.calls if name != "obte_spec_verify_ws_bytes"]
+    assert verified() == [("obte_spec_verify_bf16", 18)]
+    assert verified(allowed=None, allowed_packed=None, hold_token=None, emitted=None, min_emitted=0) == [("obte_spec_verify_bf16", 18)]
+    for kw in (dict(allowed=torch.ones(64, dtype=torch.bool)), dict(allowed_packed=torch.ones(8, dtype=torch.uint8)), dict(hold_token=7),
+               dict(emitted=torch.zeros(3, dtype=I32)), dict(min_emitted=2)):
+        assert verified(**kw) == [("obte_spec_verify_constrained_bf16", 23)], kw
+
+
 def test_sample_logits_validates_the_penalty(stub):
     from omnibiote_amd import ops
     x = torch.zeros(3, 64, dtype=BF)

@@ -314,5 +314,5 @@ def test_signatures():
     assert [p.name for p in sig[-3:]] == ["weights", "allowed", "hold_min"] and all(p.kind is p.KEYWORD_ONLY and p.default in (None, 0) for p in sig[-3:])
     gen = list(inspect.signature(OmniBioTA.generate).parameters)
     assert gen[-1] == "weights" and gen[1:4] == ["idx", "max_new_tokens", "temperature"] and gen[-3:-1] == ["allowed_tokens", "min_new_tokens"]
-    for f in (OmniBioTA.prefill, OmniBioTA.decode_step, OmniBioTA.generate, OmniBioTA._generate_ragged):
+    for f in (OmniBioTA.prefill, OmniBioTA.decode_step, OmniBioTA.generate, OmniBioTA._step_blocks):   # (generate carries it for ragged prompts too)
         assert inspect.signature(f).parameters["weights"].default is None

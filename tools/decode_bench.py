@@ -507,7 +507,7 @@ def _graph_nodes(record):
 
 def graph_compare(m, B, ctx, rounds, steps, dev, constrained=False, penalized=False):
     """A generated token with sampling (T = 0.8, top_k = 200, top_p = 0.9) and an eos_token nobody draws, three ways, alternating in one
-    process: today's loop (decode_step on the rows path + ops.sample_logits + _generate_ragged's bookkeeping, without its per-token host
+    process: today's loop (decode_step on the rows path + ops.sample_logits + the ragged host loop's bookkeeping, without its per-token host
     read), DecodeLoop eager and DecodeLoop captured (both read the positions once per 16 steps), and the captured loop with no eos_token
     (no host read at all).  Every window walks the same positions, ctx - 1 - steps .. ctx - 2, so every contender attends over the same
     keys; only run() / the steps are between the events.  ``constrained`` adds the captured loop under a restriction
