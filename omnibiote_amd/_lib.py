@@ -304,6 +304,20 @@ SYMBOLS_BEAM = {
                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
 }
 
+# the key/value cache in pages of 64 positions, one pool for rows of any lengths (include/omnibiote_hip_paged.h): a table of its own as well
+KV_PAGE = 64                                               # OBTE_KV_PAGE
+SYMBOLS_PAGED = {
+    "obte_kv_paged_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "obte_kv_paged_store": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
+    "obte_kv_paged_rope_store_rows": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
+    "obte_attn_decode_paged": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_fwd_prefill_paged": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                               c_stream]),
+    "obte_block_decode_paged": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                          C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -335,7 +349,7 @@ def lib():
                                             + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
                                             + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
                                             + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items()) + list(SYMBOLS_PENALTY.items())
-                                            + list(SYMBOLS_DISTILL.items()) + list(SYMBOLS_BEAM.items())):
+                                            + list(SYMBOLS_DISTILL.items()) + list(SYMBOLS_BEAM.items()) + list(SYMBOLS_PAGED.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -1,7 +1,7 @@
 // Autoregressive generation: the key/value cache and attention for ONE query per (batch, head) (include/omnibiote_hip.h,
 // "autoregressive generation"; extends training/model.py:115-130, whose generate() the reference struck out).
 //
-// One layer's cache comes in two formats, and every kernel of this file is written once over a format struct (CacheBf16, CacheE4m3):
+// One layer's cache comes in three formats, and every kernel of this file is written once over a format struct (CacheBf16, CacheE4m3, CachePaged):
 //   - bf16 (include/omnibiote_hip.h): K [B, H, T_max, hs] followed by V in the same shape: a (b, h)'s keys are hs * 2 bytes apart, so a
 //     step streams them as one contiguous run.
 //   - OCP e4m3 (include/omnibiote_hip_kv8.h; the format in words and in plain torch: omnibiote_amd/kvquant.py): K codes uint8
@@ -9,6 +9,8 @@
 //     4 hs.  A head vector x of hs bf16 values is stored as code_i = RNE_e4m3(x_i 2^-e) and scale = 2^e, e the smallest integer >= -126
 //     with max|x_i| 2^-e <= 448: a power of two, so the product is exact, the only rounding is the conversion's, nothing saturates, and
 //     the cache is a pure function of the bf16 inputs.
+//   - bf16 in pages (include/omnibiote_hip_paged.h; in plain torch: omnibiote_amd/paged.py): K [n_pages, H, 64, hs] followed by V, and an
+//     int32 table [rows, table_ld] that says which page holds positions [64 j, 64 j + 64) of row b: the same vectors at other addresses.
 // A format states what differs: the dims a lane holds (DPL), where V and the scales lie behind K, how a lane's piece of a key is loaded
 // and turned into floats, whether a per-key scale exists, and how 8 values of a head vector are written to the cache.
 //
@@ -70,6 +72,7 @@ __device__ __forceinline__ float group_reduce(float v) {
 
 struct CacheBf16 {
     static constexpr bool ANC = false;
+    static constexpr bool PAGED = false;
     static constexpr int DPL = 8;
     static constexpr bool SCALED = false;
     typedef u32x4 Piece;
@@ -93,8 +96,16 @@ struct CacheBf16Anc : CacheBf16 {
     using CacheBf16::CacheBf16;
 };
 
+// the bf16 vectors in a pool of pages (include/omnibiote_hip_paged.h): K [n_pages, H, 64, hs], V behind it; n_vec = n_pages H 64.  The
+// attention's view: k and v are head h's block of page 0, a page is H 64 hs elements further; the store's view: vec = (page H + h) 64 + slot
+struct CachePaged : CacheBf16 {
+    static constexpr bool PAGED = true;
+    using CacheBf16::CacheBf16;
+};
+
 struct CacheE4m3 {
     static constexpr bool ANC = false;
+    static constexpr bool PAGED = false;
     static constexpr int DPL = KV8_DPL;
     static constexpr bool SCALED = true;
     typedef __attribute__((ext_vector_type(DPL / 4))) uint32_t Piece;   // DPL code bytes
@@ -161,10 +172,19 @@ template <class Fmt, int HS, bool TAIL, bool ANC = false>
 __device__ __forceinline__ void decode_keys(Part<Fmt::DPL>& st, const float* qf, const Fmt& c, int key0, int kstride, int k1, int chunk,
                                             const int32_t* anc = nullptr, int group = 0, int64_t row_stride = 0) {
     constexpr int DPL = Fmt::DPL, LPR = HS / DPL;
+    constexpr bool PAGED = Fmt::PAGED;
     typename Fmt::Piece kr[DEC_UNROLL], vr[DEC_UNROLL];
     float ksc[DEC_UNROLL], vsc[DEC_UNROLL];   // (SCALED only)
     bool ok[DEC_UNROLL];
-    int from[DEC_UNROLL];                     // (ANC only)
+    int from[DEC_UNROLL];                     // (ANC only; PAGED: the table entry)
+    // PAGED (include/omnibiote_hip_paged.h): the round's first key is a multiple of 64, so key0 + u kstride lies in the round's page
+    // u kstride / 64 for every lane; anc holds the table entries of the round's pages (the kernel fetched them a round ahead, with
+    // workgroup-uniform indices; a page beyond the one of k1 - 1 is that page again: its keys are not there either way), group is the pool's
+    // page count and row_stride a page's elements.  An entry outside [0, group): as in the ancestry form.
+    if constexpr (PAGED) {
+#pragma unroll
+        for (int u = 0; u < DEC_UNROLL; ++u) from[u] = anc[u * kstride / DEC_CHUNK];
+    }
     if constexpr (ANC) {
 #pragma unroll
         for (int u = 0; u < DEC_UNROLL; ++u) {
@@ -177,8 +197,8 @@ __device__ __forceinline__ void decode_keys(Part<Fmt::DPL>& st, const float* qf,
         const int key = key0 + u * kstride;
         ok[u] = !TAIL || key < k1;
         const int64_t kk = ok[u] ? key : k1 - 1;   // (k1 - 1 >= k0: a workgroup with no key never gets here)
-        int64_t off = kk * HS + chunk * DPL;   // in elements, of either format; one offset for both loads: K and V addresses are formed alike
-        if constexpr (ANC) {
+        int64_t off = (PAGED ? kk & (DEC_CHUNK - 1) : kk) * HS + chunk * DPL;   // in elements, of either format; one offset for both loads: K and V addresses are formed alike
+        if constexpr (ANC || PAGED) {
             const bool there = (uint32_t)from[u] < (uint32_t)group;
             ok[u] = ok[u] && there;
             off += (there ? (int64_t)from[u] : 0) * row_stride;
@@ -204,7 +224,7 @@ __device__ __forceinline__ void decode_keys(Part<Fmt::DPL>& st, const float* qf,
         sc[u] = ok[u] ? d : -INFINITY;
         mx = fmaxf(mx, sc[u]);
     }
-    const float ms = ((TAIL || ANC) && mx == -INFINITY) ? 0.f : mx;
+    const float ms = ((TAIL || ANC || PAGED) && mx == -INFINITY) ? 0.f : mx;
     const float alpha = __builtin_amdgcn_exp2f(st.m - ms);
     st.m = mx;
     st.l *= alpha;
@@ -329,6 +349,117 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16*
     if (lane == 0) { pr[HS] = tot.m; pr[HS + 1] = tot.l; }
 }
 
+// The rows form over the pages of a pool (obte_attn_decode_paged, include/omnibiote_hip_paged.h): attn_decode_kernel<CacheBf16, HS, true, false>
+// line for line — the same partition of a row's keys, the same rounds, merges and writes, so the same bits — with a kernel of its own only
+// because it takes two more arguments, and the kernels above are to keep their argument layout and their code.  pool: K [n_pages, H, 64, hs]
+// and V behind it; table [B, table_ld]: entry j of row b the page of its positions [64 j, 64 j + 64), outside [0, n_pages): no page.  Row b
+// has rows_n[b] + rows_off keys if that lies in [1, max_keys] (max_keys <= 64 table_ld), else none.  k0 and ROUND are multiples of a page,
+// so every round's first key is: a round's keys lie in ROUND / 64 pages known from the loop counter, and their table entries are read
+// with workgroup-uniform indices (scalar loads), one round ahead: a round's K / V addresses need its entries, and a load issued at the top
+// of the round would stand between every two rounds' vector loads.
+template <int HS>
+__global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_paged_kernel(const bf16* __restrict__ q, int64_t q_ld, const void* __restrict__ pool,
+                                                                            bf16* __restrict__ o, float* __restrict__ lse, float* __restrict__ part, int H,
+                                                                            int64_t table_ld, int n_pages, int max_keys, float qscale,
+                                                                            const int32_t* __restrict__ rows_n, int rows_off,
+                                                                            const int32_t* __restrict__ table) {
+    typedef CachePaged Fmt;
+    constexpr int DPL = Fmt::DPL;
+    constexpr int LPR = HS / DPL;      // lanes per key
+    constexpr int G = 64 / LPR;        // keys per wave and load
+    const int split = blockIdx.x, splits = gridDim.x, bh = blockIdx.y;
+    const int b = bh / H, h = bh % H;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int chunk = lane % LPR, grp = lane / LPR;
+    const int64_t n = (int64_t)rows_n[b] + rows_off;
+    const int n_keys = (n >= 1 && n <= max_keys) ? (int)n : 0;
+    const int per = ((n_keys + splits - 1) / splits + DEC_CHUNK - 1) / DEC_CHUNK * DEC_CHUNK;
+    const int k0 = min(split * per, n_keys), k1 = min(k0 + per, n_keys);
+
+    float qf[DPL];
+#pragma unroll
+    for (int j = 0; j < DPL / 8; ++j) CacheBf16::to_float(*(const u32x4*)(q + b * q_ld + h * HS + chunk * DPL + j * 8), qf + j * 8);
+#pragma unroll
+    for (int j = 0; j < DPL; ++j) qf[j] *= qscale;
+
+    const Fmt c(const_cast<void*>(pool), (int64_t)n_pages * H * DEC_CHUNK, HS, h, DEC_CHUNK);   // (read only here) head h's block of page 0
+    const int32_t* row_table = table + (int64_t)b * table_ld;
+    const int64_t page_stride = (int64_t)H * DEC_CHUNK * HS;
+    const int last_page = (k1 - 1) / DEC_CHUNK;         // (of this split; an index beyond it is clamped to it: < table_ld by max_keys <= 64 table_ld)
+    Part<DPL> st;
+    st.m = -INFINITY; st.l = 0.f;
+#pragma unroll
+    for (int j = 0; j < DPL; ++j) st.acc[j] = 0.f;
+
+    constexpr int KSTRIDE = DEC_WAVES * G;              // keys between two of a lane group's UNROLL keys
+    constexpr int ROUND = KSTRIDE * DEC_UNROLL;         // keys of one workgroup round
+    const int full_end = k0 + (k1 - k0) / ROUND * ROUND;
+    int base = k0;
+    static_assert(DEC_CHUNK % KSTRIDE == 0 && ROUND % DEC_CHUNK == 0, "a lane group's UNROLL keys lie in workgroup-uniform pages");
+    constexpr int PAGES = ROUND / DEC_CHUNK;            // pages of one round
+    int ent[PAGES], ahead[PAGES];                       // the table entries of this round's pages and of the next one's
+#pragma unroll
+    for (int e = 0; e < PAGES; ++e) ent[e] = k0 < k1 ? row_table[min(k0 / DEC_CHUNK + e, last_page)] : -1;
+    for (; base < full_end; base += ROUND) {
+#pragma unroll
+        for (int e = 0; e < PAGES; ++e) ahead[e] = row_table[min((base + ROUND) / DEC_CHUNK + e, last_page)];
+        decode_keys<Fmt, HS, false>(st, qf, c, base + wave * G + grp, KSTRIDE, k1, chunk, ent, n_pages, page_stride);
+#pragma unroll
+        for (int e = 0; e < PAGES; ++e) ent[e] = ahead[e];
+    }
+    if (base < k1) decode_keys<Fmt, HS, true>(st, qf, c, base + wave * G + grp, KSTRIDE, k1, chunk, ent, n_pages, page_stride);   // (workgroup-uniform)
+
+    // the lane groups of a wave: exchange with the lane LPR, 2 LPR, .. 32 away (the same dims of another key's state)
+#pragma unroll
+    for (int off = LPR; off < 64; off <<= 1) {
+        Part<DPL> other;
+        other.m = __shfl_xor(st.m, off, 64); other.l = __shfl_xor(st.l, off, 64);
+#pragma unroll
+        for (int j = 0; j < DPL; ++j) other.acc[j] = __shfl_xor(st.acc[j], off, 64);
+        // both partners must add in one order for the result to be the same on each: the lower lane's state first
+        if (lane & off) { Part<DPL> t = other; merge(t, st); st = t; }
+        else merge(st, other);
+    }
+    // the waves, through LDS, in wave order
+    __shared__ float lds[DEC_WAVES][LPR][DPL + 2];
+    if (lane < LPR) {
+        lds[wave][lane][0] = st.m; lds[wave][lane][1] = st.l;
+#pragma unroll
+        for (int j = 0; j < DPL; ++j) lds[wave][lane][2 + j] = st.acc[j];
+    }
+    __syncthreads();
+    if (threadIdx.x >= LPR) return;
+    Part<DPL> tot;
+    tot.m = lds[0][lane][0]; tot.l = lds[0][lane][1];
+#pragma unroll
+    for (int j = 0; j < DPL; ++j) tot.acc[j] = lds[0][lane][2 + j];
+#pragma unroll
+    for (int w = 1; w < DEC_WAVES; ++w) {
+        Part<DPL> p;
+        p.m = lds[w][lane][0]; p.l = lds[w][lane][1];
+#pragma unroll
+        for (int j = 0; j < DPL; ++j) p.acc[j] = lds[w][lane][2 + j];
+        merge(tot, p);
+    }
+    if (splits == 1) {   // n_keys >= 1: l > 0; an inactive row or one without a page: l = 0, o = 0 and lse = -inf
+        const float inv = tot.l == 0.f ? 0.f : 1.0f / tot.l;
+#pragma unroll
+        for (int j = 0; j < DPL / 8; ++j) {
+            bf16x8 out;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) out[i] = f2bf(tot.acc[j * 8 + i] * inv);
+            *(bf16x8*)(o + ((int64_t)bh * HS + lane * DPL + j * 8)) = out;
+        }
+        if (lse && lane == 0)
+            lse[bh] = tot.l == 0.f ? -INFINITY : (tot.m + __builtin_amdgcn_logf(tot.l)) * 0.6931471805599453f;   // v_log_f32 is log2
+        return;
+    }
+    float* pr = part + ((int64_t)bh * splits + split) * (HS + DEC_PAD);
+#pragma unroll
+    for (int j = 0; j < DPL / 4; ++j) *(f32x4*)(pr + lane * DPL + j * 4) = f32x4{tot.acc[4 * j], tot.acc[4 * j + 1], tot.acc[4 * j + 2], tot.acc[4 * j + 3]};
+    if (lane == 0) { pr[HS] = tot.m; pr[HS + 1] = tot.l; }
+}
+
 // grid B * H, HS threads: thread d sums dim d of the partials in split order against their common maximum.  With a key in at least one
 // split (n_keys >= 1) the maximum is finite and an empty split's weight is exp2(-inf) = 0.  An inactive row of the rows form has no key
 // in any split: the maximum is made finite first, every weight is 0, and l = 0 gives o = 0 and lse = -inf.
@@ -372,10 +503,14 @@ __device__ __forceinline__ bf16x8 rope8(bf16x8 x, f32x4 c, f32x4 sn) {
 // The arguments every form reads come first and fill 64 bytes: a decode step's store is a chain of argument loads, two divisions, one
 // load and one store, and with the plain form's arguments spread over a second cache line (behind the tables and pos) a bf16
 // decode step at 64 rows measured 0.2 - 0.3 us longer per layer.
+// Fmt::PAGED (include/omnibiote_hip_paged.h): cache is the pool, n_vec = n_pages H 64, T_max the table's row length; position p of row b goes to
+// slot p % 64 of page table[b][p / 64], and nowhere if that is no page of the pool (the rotation of qkv has happened by then).  table and
+// n_pages stand behind every other argument: no other form reads them.
 template <class Fmt, bool ROPE>
 __global__ __launch_bounds__(256) void kv_store_kernel(bf16* __restrict__ qkv, void* __restrict__ cache, int64_t items, int64_t T_max, int64_t pos0,
                                                        int64_t n_vec, int n, int H, int hs, int max_pos, const float* __restrict__ cos_t,
-                                                       const float* __restrict__ sin_t, const int32_t* __restrict__ pos) {
+                                                       const float* __restrict__ sin_t, const int32_t* __restrict__ pos, const int32_t* __restrict__ table,
+                                                       int n_pages) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= items) return;
     constexpr int THIRDS = ROPE ? 3 : 2;
@@ -402,7 +537,12 @@ __global__ __launch_bounds__(256) void kv_store_kernel(bf16* __restrict__ qkv, v
         *(bf16x8*)ptr = x;
     }
     if (third == 0) return;   // (uniform over a head's lanes)
-    Fmt(cache, n_vec, hs).put(third - 1, (b * H + h) * T_max + p, hs, e, x);
+    if constexpr (Fmt::PAGED) {
+        const int page = table[b * T_max + p / DEC_CHUNK];
+        if ((uint32_t)page >= (uint32_t)n_pages) return;   // (uniform over a head's lanes)
+        Fmt(cache, n_vec, hs).put(third - 1, ((int64_t)page * H + h) * DEC_CHUNK + p % DEC_CHUNK, hs, e, x);
+    } else
+        Fmt(cache, n_vec, hs).put(third - 1, (b * H + h) * T_max + p, hs, e, x);
 }
 
 bool shape_ok(int64_t B, int64_t T_max, int32_t n_head, int32_t head_dim) {
@@ -419,7 +559,7 @@ int kv_store_launch(const char* who, bool e4m3, const obte_bf16* qkv, const floa
     const auto kernel = pos_rows ? (e4m3 ? kv_store_kernel<CacheE4m3, true> : kv_store_kernel<CacheBf16, true>)
                                  : (e4m3 ? kv_store_kernel<CacheE4m3, false> : kv_store_kernel<CacheBf16, false>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)cdiv64(items, 256)), dim3(256), 0, (hipStream_t)s, (bf16*)qkv, cache, items, T_max, pos0, B * n_head * T_max,
-                       (int)n, n_head, head_dim, (int)max_pos, rope_cos, rope_sin, pos_rows);
+                       (int)n, n_head, head_dim, (int)max_pos, rope_cos, rope_sin, pos_rows, (const int32_t*)nullptr, 0);
     OBTE_CHECK_LAUNCH(who);
     return OBTE_OK;
 }
@@ -603,4 +743,92 @@ int obte_kv_store_on(bool e4m3, const char* who, obte_bf16* qkv, const float* ro
     if (e4m3) return rope_store_rows_checked(who, true, qkv, rope_cos, rope_sin, pos_rows, pos, B, n_head, head_dim, cache, T_max, s);   // (n = 1: decode only)
     if (n == 1) return obte_kv_cache_rope_store_rows(qkv, rope_cos, rope_sin, pos_rows, pos, B, n_head, head_dim, (obte_bf16*)cache, T_max, s);
     return obte_kv_cache_rope_store_chunk(qkv, rope_cos, rope_sin, pos_rows, pos, B, n, n_head, head_dim, (obte_bf16*)cache, T_max, s);
+}
+
+// ---- the cache in pages (include/omnibiote_hip_paged.h) -------------------------------------------------------------------------------------
+namespace {
+
+bool paged_shape_ok(int64_t B, int64_t n_pages, int64_t table_ld, int32_t n_head, int32_t head_dim) {
+    return shape_ok(B, 1, n_head, head_dim) && n_pages > 0 && n_pages < (1ll << 24) && table_ld > 0 && table_ld < (1ll << 18);   // (64 table_ld < 2^24, as T_max)
+}
+
+// the launch behind the two paged stores, each after its own argument checks: kv_store_launch's, with the table
+int kv_paged_store_launch(const char* who, const obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos_rows, int64_t max_pos, int64_t B,
+                          int64_t n, int32_t n_head, int32_t head_dim, void* pool, int64_t n_pages, const int32_t* table, int64_t table_ld, obte_stream s) {
+    const int64_t items = B * n * (pos_rows ? 3 : 2) * n_head * head_dim / 8;
+    OBTE_REQUIRE(cdiv64(items, 256) < (1ll << 31), "%s: too many rows for one launch", who);
+    const auto kernel = pos_rows ? kv_store_kernel<CachePaged, true> : kv_store_kernel<CachePaged, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)cdiv64(items, 256)), dim3(256), 0, (hipStream_t)s, (bf16*)qkv, pool, items, table_ld, (int64_t)0,
+                       n_pages * n_head * DEC_CHUNK, (int)n, n_head, head_dim, (int)max_pos, rope_cos, rope_sin, pos_rows, table, (int)n_pages);
+    OBTE_CHECK_LAUNCH(who);
+    return OBTE_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t obte_kv_paged_bytes(int64_t n_pages, int32_t n_head, int32_t head_dim) {
+    return paged_shape_ok(1, n_pages, 1, n_head, head_dim) ? 2 * n_pages * n_head * DEC_CHUNK * head_dim * 2 : 0;
+}
+
+extern "C" int obte_kv_paged_store(const obte_bf16* qkv, int64_t B, int64_t t, int32_t n_head, int32_t head_dim, obte_bf16* pool, int64_t n_pages,
+                                   const int32_t* table, int64_t table_ld, obte_stream s) {
+    const char* who = "obte_kv_paged_store";
+    OBTE_REQUIRE(qkv && pool && table, "%s: null pointer", who);
+    OBTE_REQUIRE(paged_shape_ok(B, n_pages, table_ld, n_head, head_dim), "%s: bad shape (head_dim 64 or 128)", who);
+    OBTE_REQUIRE(t > 0 && t <= DEC_CHUNK * table_ld, "%s: positions [0, %lld) do not fit the table's %lld pages per row", who, (long long)t, (long long)table_ld);
+    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)pool) & 15) == 0 && ((uintptr_t)table & 3) == 0, "%s: qkv and pool must be 16-byte aligned, table 4-byte aligned", who);
+    return kv_paged_store_launch(who, qkv, nullptr, nullptr, nullptr, 0, B, t, n_head, head_dim, pool, n_pages, table, table_ld, s);
+}
+
+extern "C" int obte_kv_paged_rope_store_rows(obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos, int64_t max_pos, int64_t B,
+                                             int32_t n_head, int32_t head_dim, obte_bf16* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,
+                                             obte_stream s) {
+    const char* who = "obte_kv_paged_rope_store_rows";
+    OBTE_REQUIRE(qkv && rope_cos && rope_sin && pos && pool && table, "%s: null pointer", who);
+    OBTE_REQUIRE(paged_shape_ok(B, n_pages, table_ld, n_head, head_dim), "%s: bad shape (head_dim 64 or 128)", who);
+    OBTE_REQUIRE(max_pos >= 0 && max_pos < DEC_CHUNK * table_ld, "%s: max_pos = %lld outside the table's [0, %lld)", who, (long long)max_pos,
+                 (long long)(DEC_CHUNK * table_ld));
+    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)pool | (uintptr_t)rope_cos | (uintptr_t)rope_sin) & 15) == 0 && (((uintptr_t)pos | (uintptr_t)table) & 3) == 0,
+                 "%s: qkv, pool and the rope tables must be 16-byte aligned, pos and table 4-byte aligned", who);
+    return kv_paged_store_launch(who, qkv, rope_cos, rope_sin, pos, max_pos, B, 1, n_head, head_dim, pool, n_pages, table, table_ld, s);
+}
+
+// obte_attn_decode_on's checks and its two launches, on the pool: row b over rows_n[b] + key_off keys, max_keys the host's bound on that
+int obte_attn_decode_paged_on(const char* who, const obte_bf16* q, int64_t q_ld, const obte_bf16* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,
+                              obte_bf16* o, float* lse, int64_t B, const int32_t* rows_n, int32_t key_off, int64_t max_keys, int32_t n_head, int32_t head_dim,
+                              float scale, int32_t splits, void* ws, int64_t ws_bytes, obte_stream s) {
+    OBTE_REQUIRE(q && pool && table && o && rows_n, "%s: null pointer", who);
+    OBTE_REQUIRE(paged_shape_ok(B, n_pages, table_ld, n_head, head_dim) && B * n_head <= 65535, "%s: bad shape (head_dim 64 or 128, B * n_head <= 65535)", who);
+    OBTE_REQUIRE(max_keys >= 1 && max_keys <= DEC_CHUNK * table_ld, "%s: max_keys = %lld outside [1, 64 * table_ld = %lld]", who, (long long)max_keys,
+                 (long long)(DEC_CHUNK * table_ld));
+    OBTE_REQUIRE(q_ld >= (int64_t)n_head * head_dim && q_ld % 8 == 0, "%s: q_ld must be a multiple of 8 and at least n_head * head_dim", who);
+    OBTE_REQUIRE((((uintptr_t)q | (uintptr_t)pool | (uintptr_t)o) & 15) == 0 && (((uintptr_t)rows_n | (uintptr_t)table) & 3) == 0,
+                 "%s: q, pool and o must be 16-byte aligned, n_keys and table 4-byte aligned", who);
+    OBTE_REQUIRE(splits >= 0 && splits <= OBTE_ATTN_DECODE_MAX_SPLITS, "%s: splits = %d outside [0, %d]", who, splits, OBTE_ATTN_DECODE_MAX_SPLITS);
+    if (splits == 0) splits = obte_attn_decode_splits(B, n_head, head_dim, max_keys);
+    if (splits > 1) {
+        const int64_t need = B * n_head * splits * (int64_t)(head_dim + DEC_PAD) * 4;
+        OBTE_REQUIRE(ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0, "%s: %d splits need a 16-byte aligned workspace of %lld bytes, got %lld", who, splits,
+                     (long long)need, (long long)(ws ? ws_bytes : 0));
+    }
+    const hipStream_t st = (hipStream_t)s;
+    const int BH = (int)(B * n_head);
+    const int prof = obte_prof_begin(st, 102, BH, max_keys, head_dim);
+    const auto kernel = head_dim == 128 ? attn_decode_paged_kernel<128> : attn_decode_paged_kernel<64>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)splits, (unsigned)BH), dim3(DEC_WAVES * 64), 0, st, (const bf16*)q, q_ld, (const void*)pool, (bf16*)o, lse, (float*)ws,
+                       n_head, table_ld, (int)n_pages, (int)max_keys, scale * 1.4426950408889634f, rows_n, key_off, table);
+    if (splits > 1) {
+        if (head_dim == 128) hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3((unsigned)BH), dim3(128), 0, st, (const float*)ws, (bf16*)o, lse, (int)splits);
+        else hipLaunchKernelGGL(attn_decode_combine_kernel<64>, dim3((unsigned)BH), dim3(64), 0, st, (const float*)ws, (bf16*)o, lse, (int)splits);
+    }
+    obte_prof_end(prof, st);
+    OBTE_CHECK_LAUNCH(who);
+    return OBTE_OK;
+}
+
+extern "C" int obte_attn_decode_paged(const obte_bf16* q, int64_t q_ld, const obte_bf16* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,
+                                      obte_bf16* o, float* lse, int64_t B, const int32_t* n_keys, int64_t max_keys, int32_t n_head, int32_t head_dim, float scale,
+                                      int32_t splits, void* ws, int64_t ws_bytes, obte_stream s) {
+    return obte_attn_decode_paged_on("obte_attn_decode_paged", q, q_ld, pool, n_pages, table, table_ld, o, lse, B, n_keys, 0, max_keys, n_head, head_dim, scale, splits,
+                                     ws, ws_bytes, s);
 }

@@ -503,6 +503,9 @@ struct InferAttention {
     const void* const* w8_codes = nullptr; const float* const* w8_scales = nullptr;
     // with prefix_cache: suffix slot j of row b is read from the group's row ancestry[b][j] (obte_block_decode_beam, include/omnibiote_hip_beam.h)
     const int32_t* ancestry = nullptr;
+    // the cache in pages (include/omnibiote_hip_paged.h): kv_cache is the layer's pool of n_pages pages and page_table [B, table_ld] says where
+    // each row's positions lie; prefill, and decode in the rows form (T_max is not read)
+    const int32_t* page_table = nullptr; int64_t n_pages = 0, table_ld = 0;
 };
 int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const InferLayout& w, int64_t M, const float* rope_cos,
                    const float* rope_sin, int64_t rope_T, const InferAttention& at, obte_stream s) {
@@ -523,8 +526,14 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
     if (at.n_new > 0) {   // n_new positions per row join the cache (the rows form rotates them as it stores), then each attends over those up to its own
         const int64_t q_ld = 3 * (int64_t)C;
         const char* who = at.kv8 || at.pos_rows ? at.who : "obte_attn_decode";   // (the uniform bf16 step's attention refuses under its own name)
-        TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, s));
-        if (at.prefix_cache && at.ancestry)   // the same, the slots 0 .. pos read through the ancestry table
+        if (at.page_table)   // (the rows-form decode step through the page table)
+            TRY(obte_kv_paged_rope_store_rows(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.n_pages, at.page_table, at.table_ld, s));
+        else
+            TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, s));
+        if (at.page_table)    // row b over its own pos_rows[b] + 1 keys, each read from its page
+            TRY(obte_attn_decode_paged_on(who, w.qkv, q_ld, at.kv_cache, at.n_pages, at.page_table, at.table_ld, w.att, nullptr, d->B, at.pos_rows, 1, at.pos + 1, H, hs,
+                                          scale, 0, at.dec_ws, at.dec_ws_bytes, s));
+        else if (at.prefix_cache && at.ancestry)   // the same, the slots 0 .. pos read through the ancestry table
             TRY(obte_attn_decode_beam(w.qkv, q_ld, at.prefix_cache, at.P, at.T_pre, at.n_prefix, at.kv_cache, d->B / at.P, at.T_max, at.pos + 1, at.ancestry, w.att, nullptr, H,
                                       hs, scale, 0, 0, at.dec_ws, at.dec_ws_bytes, s));
         else if (at.prefix_cache)    // the group's prefix once per 32 rows, then the row's own slots 0 .. pos
@@ -542,7 +551,8 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
         af.B = d->B; af.T = d->T; af.n_head = H; af.head_dim = hs; af.scale = scale;
         af.dropout_p = d->dropout_p; af.dropout_seed = d->dropout_seed;
         TRY(obte_attn_fwd(&af, s));
-        if (at.kv_cache) TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, nullptr, nullptr, nullptr, 0, d->B, d->T, H, hs, at.kv_cache, at.T_max, s));   // (c_fc's activation overwrites qkv below)
+        if (at.page_table) TRY(obte_kv_paged_store(w.qkv, d->B, d->T, H, hs, at.kv_cache, at.n_pages, at.page_table, at.table_ld, s));
+        else if (at.kv_cache) TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, nullptr, nullptr, nullptr, 0, d->B, d->T, H, hs, at.kv_cache, at.T_max, s));   // (c_fc's activation overwrites qkv below)
     }
     TRY(run(plus_residual(xWt(w.att, d->proj_w, w.x1, M, C, C), x, d->dropout_p, d->dropout_seed, SITE_RESID), 1, s));
     TRY(obte_layernorm_fwd(w.x1, d->ln2_w, w.h2, w.mean, w.rstd, M, C, 1e-5f, s));
@@ -554,19 +564,21 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
 
 // obte_block_fwd_infer and obte_block_fwd_prefill: the same checks, the same workspace
 int infer_or_prefill(const char* who, const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* ws, int64_t ws_bytes, obte_bf16* kv_cache,
-                     int64_t T_max, bool prefill, obte_stream s, bool kv8 = false) {
+                     int64_t T_max, bool prefill, obte_stream s, bool kv8 = false, const int32_t* page_table = nullptr, int64_t n_pages = 0) {   // (paged: T_max is 64 table_ld)
     TRY(check_desc(who, d));
     if (d->out_rows) {
         obte_set_error("%s: the rows form (out_rows) stays with obte_block_fwd", who);
         return OBTE_EUNSUPPORTED;
     }
     OBTE_REQUIRE(x && y_out && ws && (!prefill || kv_cache), "%s: null pointer", who);
-    OBTE_REQUIRE(!prefill || d->T <= T_max, "%s: %lld positions do not fit T_max = %lld", who, (long long)d->T, (long long)T_max);
+    OBTE_REQUIRE(!prefill || d->T <= T_max, page_table ? "%s: %lld positions do not fit the table's %lld" : "%s: %lld positions do not fit T_max = %lld", who,
+                 (long long)d->T, (long long)T_max);
     OBTE_REQUIRE(!kv8 || ((uintptr_t)kv_cache & 15) == 0, "%s: cache8 must be 16-byte aligned", who);
     const InferLayout w(d->B, d->T, d->n_embd, d->n_head, ws);
     OBTE_REQUIRE(ws_bytes >= w.total, "%s: workspace of %lld bytes, obte_block_infer_ws_bytes() asks for %lld", who, (long long)ws_bytes, (long long)w.total);
     InferAttention at = {prefill ? kv_cache : nullptr, T_max, -1, nullptr, 0};
     at.kv8 = kv8; at.who = who;
+    at.page_table = page_table; at.n_pages = n_pages; at.table_ld = T_max / OBTE_KV_PAGE;
     return infer_sequence(d, x, y_out, w, d->B * d->T, d->rope_cos, d->rope_sin, d->T, at, s);
 }
 
@@ -586,6 +598,15 @@ extern "C" int obte_block_fwd_prefill_kv8(const obte_block_desc* d, const obte_b
     return infer_or_prefill("obte_block_fwd_prefill_kv8", d, x, y_out, ws, ws_bytes, (obte_bf16*)cache8, T_max, true, s, true);
 }
 
+// into the pages of a pool (include/omnibiote_hip_paged.h)
+extern "C" int obte_block_fwd_prefill_paged(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* ws, int64_t ws_bytes, obte_bf16* pool, int64_t n_pages,
+                                            const int32_t* table, int64_t table_ld, obte_stream s) {
+    const char* who = "obte_block_fwd_prefill_paged";
+    OBTE_REQUIRE(pool && table, "%s: null pointer", who);
+    OBTE_REQUIRE(n_pages > 0 && table_ld > 0 && table_ld < (1ll << 18), "%s: bad shape (n_pages and table_ld at least 1)", who);
+    return infer_or_prefill(who, d, x, y_out, ws, ws_bytes, pool, OBTE_KV_PAGE * table_ld, true, s, false, table, n_pages);
+}
+
 // ---- new positions per row against the cache --------------------------------------------------------------------------------------------
 namespace {
 
@@ -594,7 +615,7 @@ namespace {
 // obte_attn_decode / _rows and their workspace behind InferLayout) instead of obte_attn_extend's.
 int cached_step(const char* who, const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, int64_t pos,
                 const int32_t* pos_rows, bool rows, bool decode, void* ws, int64_t ws_bytes, obte_stream s, bool kv8 = false,
-                const void* const* w8_codes = nullptr, const float* const* w8_scales = nullptr) {
+                const void* const* w8_codes = nullptr, const float* const* w8_scales = nullptr, const int32_t* page_table = nullptr, int64_t n_pages = 0) {   // (paged: T_max is 64 table_ld)
     TRY(check_desc(who, d));
     OBTE_REQUIRE(!decode || d->T == 1, "%s: one new position per row (T = 1), got T = %lld", who, (long long)d->T);
     if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
@@ -624,6 +645,7 @@ int cached_step(const char* who, const obte_block_desc* d, const obte_bf16* x, o
                  (long long)need);
     InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, att_bytes, rows ? pos_rows : nullptr, n, decode, kv8, who};
     at.w8_codes = w8_codes; at.w8_scales = w8_scales;
+    at.page_table = page_table; at.n_pages = n_pages; at.table_ld = T_max / OBTE_KV_PAGE;
     // uniform: c_attn rotates row b n + j by the tables' row pos + j (rope_T = n on the tables advanced by pos rows); rows form: the FULL tables
     const int64_t row = at.pos_rows ? 0 : pos * (hs / 2);
     return infer_sequence(d, x, y_out, w, d->B * n, d->rope_cos + row, d->rope_sin + row, n, at, s);
@@ -645,6 +667,15 @@ extern "C" int obte_block_decode(const obte_block_desc* d, const obte_bf16* x, o
 extern "C" int obte_block_decode_rows(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, const int32_t* pos,
                                       int64_t max_pos, void* ws, int64_t ws_bytes, obte_stream s) {
     return cached_step("obte_block_decode_rows", d, x, y_out, kv_cache, T_max, max_pos, pos, true, true, ws, ws_bytes, s);
+}
+
+// the rows form on the pages of a pool (include/omnibiote_hip_paged.h)
+extern "C" int obte_block_decode_paged(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* pool, int64_t n_pages, const int32_t* table,
+                                       int64_t table_ld, const int32_t* pos, int64_t max_pos, void* ws, int64_t ws_bytes, obte_stream s) {
+    const char* who = "obte_block_decode_paged";
+    OBTE_REQUIRE(pool && table, "%s: null pointer", who);
+    OBTE_REQUIRE(n_pages > 0 && table_ld > 0 && table_ld < (1ll << 18), "%s: bad shape (n_pages and table_ld at least 1)", who);
+    return cached_step(who, d, x, y_out, pool, OBTE_KV_PAGE * table_ld, max_pos, pos, true, true, ws, ws_bytes, s, false, nullptr, nullptr, table, n_pages);
 }
 
 // the two on the e4m3 cache (include/omnibiote_hip_kv8.h): pos_rows null or not

@@ -504,6 +504,161 @@ class SharedPrefixCache(CachePositions):
         self.pos -= n
 
 
+class PagedPositions(CachePositions):
+    """Where the rows of a paged cache stand and which pages they hold (include/omnibiote_hip_paged.h): a ``CachePositions`` that is always
+    in rows mode, built on a ``paged.PageBook`` — the free list, the table as a CPU tensor and an exact host mirror of every row's
+    position, -1 for a parked row.  No buffer: it can be built and driven without a GPU (``device=None``: ``table`` and ``positions`` are
+    then CPU tensors); ``PagedKVCache`` adds the pools.
+
+    This class is the only writer of the table and the mirror.  ``assign(row, n_positions)`` gives a row the pages that cover that many
+    positions (ValueError when the free list cannot), ``release(row)`` takes them back, clears the row's entries and parks it,
+    ``park_rows(rows)`` parks rows that keep their pages, ``pages_in_use`` counts.  ``table`` (int32 (batch, ceil(max_len / 64)), -1: no
+    page) and ``positions`` (int32 (batch,)) are what the kernels read; a change of the book reaches them as one small copy each, made
+    when they are next read — so any number of changes between two steps cost one copy.  Each copy is a new tensor: launches already
+    queued read the old one.  ``pos`` = ``max_pos`` is the largest mirrored position.
+
+    ``park(done_tensor)``, ``rewind``, ``rewind_rows``, ``reset`` and ``advanced_on_device`` raise: the host must know where every row
+    stands, and those move rows by device values or by several positions."""
+
+    def __init__(self, batch, n_pages, max_len, free_order=None, device=None):
+        from .paged import PageBook
+        self.book = PageBook(batch, n_pages, max_len, free_order)
+        self.batch, self.max_len, self.n_pages, self.device = self.book.batch, self.book.max_len, self.book.n_pages, device
+        self.pos = self.min_pos = 0
+        self._positions = self._table = None
+        self._stale_positions = self._stale_table = True
+
+    # ---- what the kernels read -----------------------------------------------------------------------------------------------------------
+    def _put(self, t):
+        return t.clone() if self.device is None else t.to(self.device)
+
+    @property
+    def positions(self):
+        if self._stale_positions:
+            self._positions, self._stale_positions = self._put(torch.tensor(self.book.row_pos, dtype=torch.int32)), False
+        return self._positions
+
+    @positions.setter
+    def positions(self, value):                                         # (CachePositions.advance: the device's own + 1, the mirror's twin)
+        self._positions, self._stale_positions = value, False
+
+    @property
+    def table(self):
+        if self._stale_table:
+            self._table, self._stale_table = self._put(self.book.table), False
+        return self._table
+
+    def _moved(self, table=False):
+        """the book has changed: the bounds follow now, the kernels' copies when they are next read"""
+        active = [p for p in self.book.row_pos if p >= 0]
+        self.pos, self.min_pos = max(active, default=0), min(active, default=0)
+        self._stale_positions = True
+        self._stale_table = self._stale_table or table
+
+    # ---- the writers -----------------------------------------------------------------------------------------------------------------------
+    @property
+    def pages_in_use(self):
+        return self.book.pages_in_use
+
+    def assign(self, row, n_positions):
+        """row ``row`` gets the pages that cover ``n_positions`` positions (it keeps those it has); ValueError when the free list cannot"""
+        if self.book.assign(row, n_positions):
+            self._moved(table=True)
+
+    def release(self, row):
+        """row ``row``'s pages go back to the free list, its table entries are cleared and it is parked"""
+        self.book.release(row)
+        self._moved(table=True)
+
+    def park_rows(self, rows):
+        """park the rows of the host list ``rows``: they store nothing and read nothing from here on, and keep their pages until released"""
+        self.book.park_rows(rows)
+        self._moved()
+
+    def start_rows(self, rows, lengths):
+        """``prefill``'s bookkeeping: row rows[i] starts over behind a prompt of lengths[i] tokens, with pages for them (those it holds
+        count).  ValueError, with nothing changed, when the free list cannot cover all of them."""
+        from .paged import pages_for
+        more = sum(max(0, pages_for(n) - len(self.book.row_pages[r])) for r, n in zip(rows, lengths))
+        if more > len(self.book.free):
+            raise ValueError(f"PagedKVCache: the prompts of rows {list(rows)} need {more} more pages and {len(self.book.free)} of {self.n_pages} are free")
+        for r, n in zip(rows, lengths):
+            self.book.assign(r, n)
+            self.book.place(r, n)
+        self._moved(table=True)
+
+    def prepare_step(self):
+        """before a decode step is launched: every active row whose position opens a new page gets one (ValueError when none is left)"""
+        if self.book.grow_for_step():
+            self._moved(table=True)
+
+    def advance(self, n):
+        """one more position in every row that is not parked: on the device as ``CachePositions.advance``, and in the mirror"""
+        if n != 1:
+            raise ValueError(f"PagedKVCache.advance: a paged cache takes one new position per row at a time, got {n}")
+        super().advance(1)
+        self.book.step()
+        active = [p for p in self.book.row_pos if p >= 0]
+        self.pos, self.min_pos = max(active, default=0), min(active, default=0)
+
+    def _host_only(self, what):
+        raise ValueError(f"PagedKVCache.{what}: the host must know where every row of a paged cache stands: use assign, release, park_rows and "
+                         "prefill(rows=)")
+
+    def reset(self, pos, positions=None, min_pos=0):
+        self._host_only("reset")
+
+    def advanced_on_device(self, n):
+        self._host_only("advanced_on_device")
+
+    def park(self, done):
+        self._host_only("park")
+
+    def rewind(self, n):
+        self._host_only("rewind")
+
+    def rewind_rows(self, back, now=None):
+        self._host_only("rewind_rows")
+
+
+class PagedKVCache(PagedPositions):
+    """The rotated keys and the values of every layer of ``model`` for ``batch`` rows in a pool of ``n_pages`` pages of 64 positions
+    (include/omnibiote_hip_paged.h): memory is sized by what the rows hold together, not by ``batch`` times the longest row, and the pages
+    and the slot of a finished row serve the next prompt while the others go on.  Per layer one pool (``ops.kv_paged_buffer``); the table,
+    the free list and the rows' positions are ``PagedPositions``'s; ``max_len`` (default and at most ``config.block_size``) bounds one row.
+
+    ``OmniBioTA.prefill(idx, cache, lengths=, rows=)`` starts the rows of the host list ``rows`` over (default: all) and leaves the others
+    alone; ``decode_step`` gives every active row whose position opens a new page one from the free list, then steps;
+    ``OmniBioTA.generate_many`` is the loop that admits, steps and releases.  ``free_order``: the order in which pages are first handed out.
+
+    Not built, each refused before anything is launched: an e4m3 pool; several new positions per row over pages (``extend``,
+    ``prefill(chunk=)``, ``draft_and_verify`` and the speculative loop); e4m3 weights (``weights=``); the device-resident loop and graph
+    capture (``DecodeLoop``); pages shared between rows (prefix sharing, copy-on-write); preemption or swapping of running rows."""
+
+    def __init__(self, model, batch, n_pages, max_len=None, free_order=None):
+        cfg = model.config
+        if not cfg.autoregressive:
+            raise ValueError("PagedKVCache: the model is not autoregressive (config.autoregressive): an encoder has no next token")
+        max_len = cfg.block_size if max_len is None else int(max_len)
+        if not 1 <= max_len <= cfg.block_size:
+            raise ValueError(f"PagedKVCache: max_len {max_len} outside [1, block_size = {cfg.block_size}]")
+        if batch < 1 or n_pages < 1:
+            raise ValueError(f"PagedKVCache: batch and n_pages must be at least 1, got {batch} and {n_pages}")
+        wte = model.transformer.wte.weight
+        _require_hip(wte, "PagedKVCache")
+        super().__init__(batch, n_pages, max_len, free_order, wte.device)
+        hs = cfg.n_embd // cfg.n_head
+        self.layers = [ops.kv_paged_buffer(self.n_pages, cfg.n_head, hs, wte.device) for _ in model.transformer.h]
+        self.decode_ws = ops.block_decode_workspace(self.batch, cfg.n_embd, cfg.n_head, wte.device)
+        self.extend_ws = None
+
+
+def _refuse_paged(what, cache, why="over which one new position per row attends at a time (prefill, decode_step, generate_many)"):
+    """NotImplementedError in ``OmniBioTA.what``'s name on a paged cache: before anything is launched or any state changes"""
+    if isinstance(cache, PagedPositions):
+        raise NotImplementedError(f"OmniBioTA.{what}: the cache is a paged cache (PagedKVCache), {why}; this call needs a KVCache")
+
+
 class QuantizedWeights:
     """``model``'s decode-step weights as OCP e4m3 with one power-of-two scale per output row (include/omnibiote_hip_w8.h, w8quant.py):
     what ``prefill``, ``decode_step``, ``generate`` and ``DecodeLoop`` take as ``weights=``.  Per block, in the order c_attn, attention
@@ -629,6 +784,7 @@ class DecodeLoop:
         if isinstance(cache, SharedPrefixCache):
             _refuse_weights("DecodeLoop", weights, "do not run on a shared-prefix cache (SharedPrefixCache)")
             raise ValueError("DecodeLoop: a SharedPrefixCache steps at a host suffix position, which changes every step: the device loop needs a KVCache")
+        _refuse_paged("DecodeLoop", cache, "whose table and free list the host moves between steps (the device-resident loop and graph capture over pages are not built)")
         model._check_generation("DecodeLoop", cache.batch, cache)
         if weights is not None:
             _checked_weights(model, "DecodeLoop", weights)

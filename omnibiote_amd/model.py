@@ -39,9 +39,9 @@ from torch.utils.checkpoint import checkpoint
 from . import _lib as L
 from . import ops
 from .generation import (  # noqa: F401  (the generation state lives there; every name stays importable from this module)
-    BeamResult, CachePositions, DecodeLoop, KVCache, QuantizedWeights, SequenceScore, SharedPrefixCache, TokenConstraint, TokenPenalty,
-    _check_lengths, _check_prompt, _check_room, _check_top_p, _checked_weights, _default_pad, _device_uniforms, _live, _next_tokens,
-    _refuse_weights, _require_hip, _restriction, _round_restriction, _step_restriction, ragged_output, sample_next)
+    BeamResult, CachePositions, DecodeLoop, KVCache, PagedKVCache, PagedPositions, QuantizedWeights, SequenceScore, SharedPrefixCache, TokenConstraint,
+    TokenPenalty, _check_lengths, _check_prompt, _check_room, _check_top_p, _checked_weights, _default_pad, _device_uniforms, _live, _next_tokens,
+    _refuse_paged, _refuse_weights, _require_hip, _restriction, _round_restriction, _step_restriction, ragged_output, sample_next)
 
 try:  # the real package, if the environment has it (README.md:16 pins mup==1.0.0)
     from mup import MuReadout as _MuReadoutBase  # type: ignore
@@ -1108,7 +1108,7 @@ class OmniBioTA(nn.Module):
         return self.lm_head(x) if out is None else out.copy_(self.lm_head(x))
 
     @torch.no_grad()
-    def prefill(self, idx, cache, lengths=None, chunk=None, weights=None):
+    def prefill(self, idx, cache, lengths=None, chunk=None, weights=None, rows=None):
         """The prompt ``idx`` (B, T0) through every block under the causal mask, its keys and values left in ``cache`` (started
         over: ``cache.pos = T0``); returns the logits of the last position, (B, vocab).  ln_f and the readout run on that row alone.
 
@@ -1124,7 +1124,17 @@ class OmniBioTA(nn.Module):
         row b's last hidden state is picked up in the chunk that holds it.  The cache ends in the same state.
 
         ``weights`` (``quantize_weights()``): the prompt runs through the same kernels on the DEQUANTISED weights, so that it and a
-        continuation by ``decode_step(weights=)`` see one model; the readout of the last position reads the e4m3 codes."""
+        continuation by ``decode_step(weights=)`` see one model; the readout of the last position reads the e4m3 codes.
+
+        On a ``PagedKVCache``: ``rows`` is a host list of the cache rows the prompts go to, ``idx`` (len(rows), T0); the default is every
+        row.  Only those rows are started over — each gets pages for its ``len_b`` positions unless it holds them — and the others keep
+        their state.  The same causal kernels run over the right-padded prompts (``ops.block_prefill_paged`` with the gathered table rows:
+        the padding beyond a row's own pages is not stored).  ``chunk=`` and ``weights=`` raise NotImplementedError there: several new
+        positions per row over pages and e4m3 weights on pages are not built."""
+        if isinstance(cache, PagedPositions):
+            return self._prefill_paged(idx, cache, lengths, chunk, weights, rows)
+        if rows is not None:
+            raise ValueError("OmniBioTA.prefill: rows= names the rows of a PagedKVCache; every other cache is prefilled as a whole")
         if isinstance(cache, SharedPrefixCache):
             _refuse_weights("prefill", weights, "do not run on a shared-prefix cache (SharedPrefixCache)")
             return self._prefill_shared(idx, cache, lengths, chunk)
@@ -1161,6 +1171,38 @@ class OmniBioTA(nn.Module):
             return self._readout_rows(self.transformer.ln_f(x[:, -1].contiguous()), weights=weights)
         last = x[torch.arange(b, device=idx.device), (cache.positions - 1).long()]          # (B, C): row b at its own last position
         return self._readout_rows(self.transformer.ln_f(last.contiguous()), weights=weights)
+
+    def _prefill_paged(self, idx, cache, lengths, chunk, weights, rows):
+        """``prefill`` on a ``PagedKVCache``: the prompts ``idx`` (len(rows), T0) into the cache rows ``rows``; (len(rows), vocab)"""
+        if chunk is not None:
+            _refuse_paged("prefill(chunk=)", cache)
+        _refuse_weights("prefill", weights, "do not run on a paged cache (PagedKVCache)")
+        if idx.dim() != 2:
+            raise ValueError(f"OmniBioTA.prefill: idx must be (B, T0), got {tuple(idx.shape)}")
+        b, t = idx.shape
+        self._check_generation("prefill", b)
+        whole = rows is None
+        rows = list(range(cache.batch)) if whole else [int(r) for r in rows]
+        if len(rows) != b or len(set(rows)) != b or (rows and not 0 <= min(rows) <= max(rows) < cache.batch):
+            raise ValueError(f"OmniBioTA.prefill: rows must be {b} distinct rows of the cache's {cache.batch} (one per prompt), got {rows}")
+        if t == 0:
+            raise ValueError("OmniBioTA.prefill: the prompt is empty")
+        if t > cache.max_len:
+            raise ValueError(f"OmniBioTA.prefill: a prompt of {t} tokens does not fit the cache's {cache.max_len} positions")
+        lens = [t] * b if lengths is None else _check_lengths("prefill", lengths, b, t)
+        wte = self.transformer.wte.weight
+        _require_hip(wte, "OmniBioTA")
+        if not idx.is_cuda:
+            raise RuntimeError("OmniBioTA.prefill: idx must be on the GPU")
+        cache.start_rows(rows, lens)                                    # (ValueError with nothing changed when the free list cannot)
+        table = cache.table if whole else cache.table[torch.tensor(rows, device=idx.device)]
+        mask = ops.MaskSpec.from_user(_autoregressive_mask(True, None, b, t, idx.device), b, t, self.config.n_head, idx.device)
+        x = ops.embedding_fwd(idx.contiguous(), wte)
+        ws = ops.block_infer_workspace(b, t, self.config.n_embd, self.config.n_head, idx.device)
+        for block, pool in zip(self.transformer.h, cache.layers):
+            ops.block_prefill_paged(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, pool, cache.n_pages, table, ws=ws, out=x)
+        last = x[torch.arange(b, device=idx.device), torch.tensor(lens, device=idx.device) - 1]   # (B, C): row b at its own last position
+        return self._readout_rows(self.transformer.ln_f(last.contiguous()))
 
     def _params_for(self, weights):
         """(index, block) -> the block's six parameters: the model's own, or with the four matrices dequantised from ``weights``"""
@@ -1260,6 +1302,7 @@ class OmniBioTA(nn.Module):
         _refuse_weights("extend", weights, "have no form for several new positions per row")
         self._refuse_fp8("extend", cache)
         self._refuse_shared("extend", cache)
+        _refuse_paged("extend", cache)
         if tokens.dim() != 2:
             raise ValueError(f"OmniBioTA.extend: tokens must be (B, n), got {tuple(tokens.shape)}")
         b, n = tokens.shape
@@ -1291,9 +1334,14 @@ class OmniBioTA(nn.Module):
 
         ``weights`` (``quantize_weights()``): every block's four products and the readout read e4m3 codes (``ops.block_step_w8``,
         ``ops.linear_small_m_w8``) — half the weight bytes — and give, bit for bit, this step of ``weights.dequantized_model()``.  On a
-        ``KVCache`` of either dtype, uniform or per-row positions; not on a ``SharedPrefixCache`` (NotImplementedError)."""
+        ``KVCache`` of either dtype, uniform or per-row positions; not on a ``SharedPrefixCache`` (NotImplementedError).
+
+        On a ``PagedKVCache`` every active row whose position opens a new page first gets one from the free list — ValueError, before
+        anything is launched, if none is left — and the step reads and writes through the table (``ops.block_decode_paged``); ``weights=``
+        raises NotImplementedError there."""
         if weights is not None:
             _refuse_weights("decode_step", weights if isinstance(cache, SharedPrefixCache) else None, "do not run on a shared-prefix cache (SharedPrefixCache)")
+            _refuse_weights("decode_step", weights if isinstance(cache, PagedPositions) else None, "do not run on a paged cache (PagedKVCache)")
             _checked_weights(self, "OmniBioTA.decode_step", weights)
         if tokens.dim() != 1:
             raise ValueError(f"OmniBioTA.decode_step: tokens must be (B,), got {tuple(tokens.shape)}")
@@ -1305,6 +1353,8 @@ class OmniBioTA(nn.Module):
         wte = self.transformer.wte.weight
         if not tokens.is_cuda:
             raise RuntimeError("OmniBioTA.decode_step: tokens must be on the GPU")
+        if isinstance(cache, PagedPositions):                          # every active row whose position opens a new page gets one: ValueError
+            cache.prepare_step()                                        # before anything is launched when none is left
         x = ops.embedding_fwd(tokens.contiguous(), wte)
         self._step_blocks(x, cache, cache.pos, cache.positions, weights)
         cache.advance(1)
@@ -1315,11 +1365,14 @@ class OmniBioTA(nn.Module):
         step's op.  ``pos``: the position of every row, or with ``pos_rows`` (int32 (B,) on the device: rows mode, every row at its own
         position, read there) the host's bound on it.  A ``SharedPrefixCache`` — the group's prefix and the row's own slots, two buffers
         per layer — steps at suffix slot ``pos - n_prefix``, read through ``ancestry`` (beam search's table) when one is given; a
-        ``KVCache`` on the e4m3 codes of ``weights``, else by its dtype, else by its mode.  The cache is not advanced."""
+        ``PagedKVCache`` through its page table; a ``KVCache`` on the e4m3 codes of ``weights``, else by its dtype, else by its mode.  The
+        cache is not advanced."""
         H = self.config.n_head
         for i, (block, kv) in enumerate(zip(self.transformer.h, cache.layers)):
             params, rope, to = self._block_params(block), block.attn.rope(), dict(ws=cache.decode_ws, out=x)
-            if isinstance(cache, SharedPrefixCache):
+            if isinstance(cache, PagedPositions):                      # rows mode always: every row at its own position, its keys in its own pages
+                ops.block_decode_paged(x, params, rope, H, kv, cache.n_pages, cache.table, pos_rows, pos, **to)
+            elif isinstance(cache, SharedPrefixCache):
                 at = (kv[0], cache.prompts, cache.prefix_len, cache.n_prefix, kv[1], cache.max_new, pos - cache.n_prefix)
                 if ancestry is None:
                     ops.block_decode_shared(x, params, rope, H, *at, **to)
@@ -1471,6 +1524,86 @@ class OmniBioTA(nn.Module):
         return torch.cat([rows, tokens], dim=1)
 
     @torch.no_grad()
+    def generate_many(self, prompts, max_new_tokens, batch, n_pages=None, temperature=1.0, top_k=None, top_p=None, eos_token=None, generator=None):
+        """Continuous batching: ``prompts``, a sequence of 1-D int64 tensors of any lengths, each continued by up to ``max_new_tokens``
+        tokens, ``batch`` of them at a time on a ``PagedKVCache`` of ``n_pages`` pages.  Returns a list in the same order, each entry the
+        prompt followed by its new tokens up to and including its first ``eos_token``, int64 on the model's device.  A row that ends —
+        with its ``eos_token`` or after ``max_new_tokens`` — is released at once, and its slot and its pages serve the next waiting
+        prompt while the other rows go on: no row waits for the longest, and memory follows what the rows hold.
+
+        The rule (``paged.PagedSchedule``, which is all of it, without tensors): requests wait in the given order; a request needs
+        ceil((len + max_new_tokens) / 64) pages and is admitted when a slot is free and the pages not yet promised to running requests
+        cover its need — strictly first-in first-out, nothing is skipped.  ``n_pages=None``: enough for ``batch`` requests of the largest
+        need.  ValueError before anything is launched for a request that can never fit: ``len + max_new_tokens > block_size``, or a need
+        above ``n_pages``.  The requests admitted in one round are prefilled together, right-padded (``prefill(rows=)``), and each draws
+        its first token from the prefill's logits.
+
+        The device sampler only (``ops.sample_logits``: ``temperature``, ``top_k``, ``top_p`` as in ``generate``).  The uniforms are
+        ``torch.rand((max_new_tokens, len(prompts)), generator=generator)`` on the model's device, drawn once: request r draws its k-th
+        token against [k, r], wherever and whenever it runs; a greedy setting draws nothing.  With an ``eos_token`` the host reads the
+        step's tokens once per step, as ``generate``'s loop does; without one it reads nothing until the end.
+
+        Not built: an e4m3 pool, speculative decoding, the device-resident loop and graph capture, pages shared between requests (a
+        common prefix is stored once per request), preemption or swapping of running requests, penalties and token restrictions, the
+        torch sampler."""
+        from .paged import PagedSchedule
+        self._check_generation("generate_many", 0)
+        _check_top_p("OmniBioTA.generate_many", top_p)
+        if temperature < 0:
+            raise ValueError(f"OmniBioTA.generate_many: temperature must not be negative, got {temperature}")
+        if top_k is not None and top_k < 1:
+            raise ValueError(f"OmniBioTA.generate_many: top_k must be at least 1, got {top_k}")
+        prompts = list(prompts)
+        for r, p in enumerate(prompts):
+            if not isinstance(p, torch.Tensor) or p.dim() != 1 or p.dtype != torch.int64:
+                raise ValueError(f"OmniBioTA.generate_many: prompts must be 1-D int64 tensors, prompts[{r}] is not")
+        sched = PagedSchedule([p.numel() for p in prompts], max_new_tokens, batch, n_pages, self.config.block_size)
+        if not prompts:
+            return []
+        wte = self.transformer.wte.weight
+        _require_hip(wte, "OmniBioTA")
+        dev, R, steps, B = wte.device, len(prompts), sched.max_new, sched.batch
+        prompts = [p.to(dev) for p in prompts]
+        cache = PagedKVCache(self, B, sched.n_pages, max(p.numel() for p in prompts) + steps)
+        greedy = top_k == 1 or temperature == 0
+        # one column more than there are requests: what an idle slot draws against and writes to
+        us = None if greedy else torch.cat([torch.rand((steps, R), device=dev, generator=generator), torch.zeros((steps, 1), device=dev)], dim=1)
+        out = torch.zeros((R + 1, steps), dtype=torch.int64, device=dev)
+        logits = torch.zeros((B, self.config.vocab_size), dtype=torch.bfloat16, device=dev)
+        slot_req, slot_k = [R] * B, [0] * B                            # the host's account: the slot's request (R: idle) and its tokens so far
+        n_new = [0] * R
+        at, changed = None, True                                        # the same on the device, int64 (2, B): uploaded when a slot changes hands
+        while not sched.done:
+            admitted = sched.admit()
+            if admitted:
+                rows = [slot for _, slot in admitted]
+                lens = [prompts[r].numel() for r, _ in admitted]
+                idx = torch.nn.utils.rnn.pad_sequence([prompts[r] for r, _ in admitted], batch_first=True)
+                logits[torch.tensor(rows, device=dev)] = self.prefill(idx, cache, lengths=lens, rows=rows)
+                for r, slot in admitted:
+                    slot_req[slot], slot_k[slot] = r, 0
+                changed = True
+            if changed:
+                at, changed = torch.tensor([slot_req, slot_k], dtype=torch.int64).to(dev), False
+            nxt = ops.sample_logits(logits, None if greedy else us[at[1], at[0]], temperature, top_k, top_p)
+            out[at[0], at[1]] = nxt
+            seen = nxt.tolist() if eos_token is not None else None      # (the step's one host read)
+            for slot, r in enumerate(slot_req):
+                if r == R:
+                    continue
+                slot_k[slot] += 1
+                if slot_k[slot] == steps or (seen is not None and seen[slot] == eos_token):
+                    n_new[r] = slot_k[slot]
+                    sched.finish(r)
+                    cache.release(slot)
+                    slot_req[slot], slot_k[slot], changed = R, 0, True
+            if any(r != R for r in slot_req):
+                logits = self.decode_step(nxt, cache)
+                if not changed:
+                    at[1] += at[0] < R                                  # (no slot changed hands: the running ones count on, on the device)
+        return [torch.cat([p, out[r, :n_new[r]]]) for r, p in enumerate(prompts)]
+
+    @torch.no_grad()
     def generate_beam(self, idx, max_new_tokens, num_beams=4, eos_token=None, pad_token=None, length_penalty=0.0, allowed_tokens=None):
         """Beam search: the ``num_beams`` = W most probable continuations of every prompt of ``idx`` (P, T0) int64 that a beam of that width
         finds, deterministic.  Returns a ``BeamResult`` (sequences (P, W, T0 + n), scores (P, W), lengths (P, W)), n the steps taken.
@@ -1567,6 +1700,8 @@ class OmniBioTA(nn.Module):
                         "are not built for speculative decoding, for the target (several new positions per row) or the draft")
         self._refuse_fp8("draft_and_verify", cache)         # (the draft only takes decode steps: its cache may be either)
         self._refuse_shared("draft_and_verify", cache)
+        _refuse_paged("draft_and_verify", cache)
+        _refuse_paged("draft_and_verify", draft_cache, "which cannot step back over rejected tokens")
         b = pending.shape[0]
         greedy = uniforms is None or temperature == 0 or top_k == 1
         draws, u_accept, u_draw = (None, None, None) if greedy else uniforms

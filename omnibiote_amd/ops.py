@@ -1635,6 +1635,88 @@ def block_decode_beam(x, params, rope, H, prefix_cache, P, T_pre, n_prefix, suff
         cache=suffix_cache, T_max=T_suf, at=n_prefix + suf_pos, one=True)
 
 
+# ---- the key/value cache in pages: one pool for rows of any lengths (include/omnibiote_hip_paged.h; the format in plain torch: paged.py) ----
+KV_PAGE = L.KV_PAGE
+
+
+def kv_paged_buffer(n_pages, H, hs, device) -> torch.Tensor:
+    """One layer's pool of ``n_pages`` pages (K [n_pages, H, 64, hs], then V, bf16) as the flat bf16 tensor the entry points take."""
+    nbytes = int(L.lib().obte_kv_paged_bytes(n_pages, H, hs))
+    if nbytes <= 0:
+        raise RuntimeError(f"kv_paged_buffer: unsupported shape (n_pages {n_pages}, n_head {H}, head size {hs}): head size 64 or 128")
+    return torch.empty(nbytes // 2, dtype=bf16, device=device)
+
+
+def _need_paged(pool, table, B, n_pages, H, hs):
+    """the pool and the (B, table_ld) int32 table of a paged call; returns table_ld"""
+    _need(pool, "pool"); _need(table, "table", torch.int32)
+    if table.dim() != 2 or table.shape[0] != B:
+        raise ValueError(f"table: expected shape ({B}, table_ld), got {tuple(table.shape)}")
+    assert pool.numel() * 2 == L.lib().obte_kv_paged_bytes(n_pages, H, hs)
+    return table.shape[1]
+
+
+def kv_paged_store(qkv, B, t, H, hs, pool, n_pages, table):
+    """Copy the k and v thirds of the packed, rotated qkv [B*t, 3C] into positions [0, t) of each row, through the page table
+    (obte_kv_paged_store); a position whose table entry is no page of the pool is skipped.  table: int32 (B, table_ld) on the device."""
+    _need(qkv, "qkv")
+    ld = _need_paged(pool, table, B, n_pages, H, hs)
+    assert qkv.numel() == B * t * 3 * H * hs and t <= KV_PAGE * ld
+    L.check(L.lib().obte_kv_paged_store(_ptr(qkv), B, t, H, hs, _ptr(pool), n_pages, _ptr(table), ld, _stream()), "obte_kv_paged_store")
+    return pool
+
+
+def kv_paged_rope_store_rows(qkv, rope, pos, max_pos, B, H, hs, pool, n_pages, table):
+    """kv_cache_rope_store_rows into pages (obte_kv_paged_rope_store_rows): the same rotation of qkv in place, the rotated k and the v to
+    slot pos[b] % 64 of page table[b, pos[b] // 64] — or nowhere, if that is no page of the pool."""
+    _need(qkv, "qkv"); _need_rows(pos, "pos", B)
+    ld = _need_paged(pool, table, B, n_pages, H, hs)
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert qkv.numel() == B * 3 * H * hs and max_pos < KV_PAGE * ld
+    assert rope[0].shape[0] > max_pos and rope[1].shape[0] > max_pos
+    L.check(L.lib().obte_kv_paged_rope_store_rows(_ptr(qkv), _ptr(rope[0]), _ptr(rope[1]), _ptr(pos), int(max_pos), B, H, hs, _ptr(pool), n_pages, _ptr(table),
+                                                  ld, _stream()), "obte_kv_paged_rope_store_rows")
+    return qkv
+
+
+def attn_decode_paged(q, pool, n_pages, table, B, n_keys, max_keys, H, hs, scale, splits=0, q_ld=None, ws=None):
+    """attn_decode_rows over pages (obte_attn_decode_paged): row b over its positions [0, n_keys[b]) that have a page, read through
+    table (B, table_ld) int32; bit for bit attn_decode_rows on a rectangular cache holding the same vectors.  Returns (o, lse)."""
+    _need(q, "q"); _need_rows(n_keys, "n_keys", B)
+    ld = _need_paged(pool, table, B, n_pages, H, hs)
+    q_ld = q.shape[-1] if q_ld is None else q_ld
+    assert q.numel() >= (B - 1) * q_ld + H * hs and max_keys <= KV_PAGE * ld
+    o = torch.empty((B, H * hs), dtype=bf16, device=q.device)
+    lse = torch.empty((B, H), dtype=torch.float32, device=q.device)
+    if ws is None:
+        ws = torch.empty(int(L.lib().obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=q.device)
+    L.check(L.lib().obte_attn_decode_paged(_ptr(q), q_ld, _ptr(pool), n_pages, _ptr(table), ld, _ptr(o), _ptr(lse), B, _ptr(n_keys), int(max_keys), H, hs,
+                                           float(scale), int(splits), _ptr(ws), ws.numel(), _stream()), "obte_attn_decode_paged")
+    return o, lse
+
+
+def block_prefill_paged(x, params, rope, H, mask: MaskSpec, pool, n_pages, table, ws=None, out=None):
+    """block_prefill into pages (obte_block_fwd_prefill_paged): y bit for bit block_infer's, the same workspace; the rotated keys and the
+    values of positions [0, T) of row b go to the pages of table row b, int32 (B, table_ld) — any rows of a larger table, gathered."""
+    B, T, Cc = x.shape
+    ld = _need_paged(pool, table, B, n_pages, H, Cc // H)
+    assert T <= KV_PAGE * ld
+    return _block_call(x, params, rope, H, ws, out, block_infer_workspace, lambda d, y, w: L.check(
+        L.lib().obte_block_fwd_prefill_paged(d, _ptr(x), _ptr(y), _ptr(w), w.numel(), _ptr(pool), n_pages, _ptr(table), ld, _stream()),
+        "obte_block_fwd_prefill_paged"), mask)
+
+
+def block_decode_paged(x, params, rope, H, pool, n_pages, table, pos, max_pos, ws=None, out=None):
+    """block_decode_rows on pages (obte_block_decode_paged): row b at position pos[b], stored to and read from the pages of table row b.
+    The workspace is block_decode's.  rope: the FULL tables.  out may be x itself."""
+    B, Cc = x.shape
+    ld = _need_paged(pool, table, B, n_pages, H, Cc // H)
+    assert max_pos < KV_PAGE * ld
+    return _block_call(x, params, rope, H, ws, out, _decode_ws, lambda d, y, w: L.check(
+        L.lib().obte_block_decode_paged(d, _ptr(x), _ptr(y), _ptr(pool), n_pages, _ptr(table), ld, _ptr(pos), int(max_pos), _ptr(w), w.numel(), _stream()),
+        "obte_block_decode_paged"), rows=(pos, "pos"), at=max_pos, one=True)
+
+
 def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None, dropout_p=0.0, dropout_seed=0, ln_partials=None,
               ln_partial_mode=0, out_rows=None, dy_masked=None, dx_mask_seed=None, acc32=None, acc32_mode=0):
     """accumulate_into: optional list of 6 tensors-or-None (same order as params).  When the four matrix entries are all

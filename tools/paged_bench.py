@@ -1,0 +1,241 @@
+"""The paged key/value cache and continuous batching on the small config (8 layers, 1024 wide, 8 heads of 128; bf16): what the page
+table costs a step, and what releasing finished rows buys a workload.  Contenders alternate in one process over --rounds rounds after
+warm-up; median and [min - max] over the rounds.  One JSON line per measurement.
+
+  attention   obte_attn_decode_paged against obte_attn_decode_rows on the same keys, the pool's pages in random order (and, as a probe of what
+              the random order itself costs, in row order), every row over ctx keys, each call on the next layer's cache, at B x ctx in
+              {64 x 2048, 8 x 2048}.  The paged call reads the same bytes plus one table entry per 64 keys and head.  `served_from` says
+              whether a set of caches exceeds the 256 MB Infinity Cache: one that does not is not an HBM measurement.
+  step        OmniBioTA.decode_step on a KVCache in rows mode and on a PagedKVCache at the same shapes, every window walking the same
+              positions up to ctx - 2 (the paged step includes its host side: the page bookkeeping of every row).
+  workload    --prompts prompts (default 256), lengths spread evenly over [64, 1024], in a seeded random order, up to 256 new tokens each,
+              through generate_many(batch=64) and through generate(lengths=, sampler="device") over the same prompts in input-order
+              batches of 64: tokens per second of wall time (a device synchronise at the end), the cache bytes each holds at its peak, and
+              the share of row-steps spent on rows that had already finished.  A randomly initialised model with the 65536-token readout
+              practically never draws one given token, so rows would never end: the workload's model has --vocab tokens (default 256),
+              where every draw meets the eos_token with a probability near 1 / vocab and the rows end at spread-out times.  Also with a
+              pool of --pool-share (default 0.65) of the default page count.
+
+    python tools/paged_bench.py [--parts attention,step,workload] [--rounds 5] [--steps 200]
+"""
+import argparse
+import contextlib
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from decode_bench import HBM_RATE, INFINITY_CACHE, build, summary, timed  # noqa: E402
+
+
+def _gap(us, a, b, nd=2):
+    """median(a) - median(b) and both spreads"""
+    return [round(statistics.median(us[a]) - statistics.median(us[b]), nd)] + [round(max(us[k]) - min(us[k]), nd) for k in (a, b)]
+
+
+def attention(m, B, ctx, rounds, steps, dev):
+    from omnibiote_amd import _lib, ops
+    from omnibiote_amd.paged import paged_scatter_reference
+    lib = _lib.lib()
+    H, C = m.config.n_head, m.config.n_embd
+    hs, n_layer, n_pages = C // H, m.config.n_layer, B * ctx // 64
+    gen = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    table = torch.randperm(n_pages, device=dev, generator=gen).view(B, ctx // 64).to(torch.int32)
+    ordered = torch.arange(n_pages, device=dev, dtype=torch.int32).view(B, ctx // 64)   # the probe: the same pool layout, row b's pages side by side
+    rects, pools, pools_ordered = [], [], []
+    for _ in range(n_layer):
+        rect = ops.kv_cache_buffer(B, ctx, H, hs, dev).normal_(generator=gen)
+        K, V = rect.view(2, B, H, ctx, hs)
+        rects.append(rect)
+        pools.append(paged_scatter_reference(K, V, table, n_pages))
+        pools_ordered.append(paged_scatter_reference(K, V, ordered, n_pages))
+    q = torch.randn(B, 3 * C, device=dev, generator=gen).to(torch.bfloat16)
+    counts = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=dev)
+    o = torch.empty(B, C, device=dev, dtype=torch.bfloat16)
+    lse = torch.empty(B, H, device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream().cuda_stream
+    state = {"i": 0}
+
+    def rows():                # the C entry points themselves on preallocated outputs, each call on the next layer's cache
+        state["i"] += 1
+        rc = lib.obte_attn_decode_rows(q.data_ptr(), 3 * C, rects[state["i"] % n_layer].data_ptr(), o.data_ptr(), lse.data_ptr(), B, ctx, counts.data_ptr(), ctx,
+                                       H, hs, 8.0 / C, 0, ws.data_ptr(), ws.numel(), stream)
+        if rc != 0:
+            _lib.check(rc, "obte_attn_decode_rows")
+
+    def paged(pools=pools, table=table):
+        state["i"] += 1
+        rc = lib.obte_attn_decode_paged(q.data_ptr(), 3 * C, pools[state["i"] % n_layer].data_ptr(), n_pages, table.data_ptr(), ctx // 64, o.data_ptr(),
+                                        lse.data_ptr(), B, counts.data_ptr(), ctx, H, hs, 8.0 / C, 0, ws.data_ptr(), ws.numel(), stream)
+        if rc != 0:
+            _lib.check(rc, "obte_attn_decode_paged")
+    a, _ = ops.attn_decode_rows(q, rects[0], B, ctx, counts, ctx, H, hs, 8.0 / C)
+    b, _ = ops.attn_decode_paged(q, pools[0], n_pages, table, B, counts, ctx, H, hs, 8.0 / C)
+    legs = {"rows": rows, "paged": paged, "paged_pages_in_order": lambda: paged(pools_ordered, ordered)}
+    for fn in legs.values():
+        for _ in range(8):
+            fn()
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for k in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            us[k].append(timed(legs[k], steps))
+    nbytes, set_bytes = 4 * B * H * ctx * hs, sum(t.numel() * 2 for t in rects)
+    med = {k: statistics.median(v) for k, v in us.items()}
+    return {"part": "attention", "B": B, "context": ctx, "windows": {"calls": steps, "rounds": rounds}, "same_bits": bool(torch.equal(a, b)),
+            "splits": int(lib.obte_attn_decode_splits(B, H, hs, ctx)), "bytes_per_call": nbytes, "table_bytes_per_call": 4 * B * ctx // 64, "set_bytes": set_bytes,
+            "served_from": "HBM" if set_bytes > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)",
+            "us": {k: summary(v) for k, v in us.items()}, "share_of_6.3TBps": {k: round(nbytes / (med[k] * 1e-6) / HBM_RATE, 3) for k in legs},
+            "paged_over_rows": round(med["paged"] / med["rows"], 3), "paged_minus_rows_us_and_spreads": _gap(us, "paged", "rows"),
+            "in_order_minus_rows_us_and_spreads": _gap(us, "paged_pages_in_order", "rows")}
+
+
+def step(m, B, ctx, rounds, steps, dev):
+    from omnibiote_amd.model import KVCache, PagedKVCache
+    first = ctx - 1 - steps
+    gen = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    last = torch.randint(4, m.config.vocab_size, (B,), device=dev, generator=gen)
+    rect, paged = KVCache(m, B, ctx), PagedKVCache(m, B, B * ctx // 64, ctx, free_order=torch.randperm(B * ctx // 64, generator=torch.Generator().manual_seed(1)).tolist())
+    for kv in rect.layers + paged.layers:                              # finite values of the keys' size: only the time is read
+        kv.normal_(generator=gen)
+    for b in range(B):
+        paged.assign(b, ctx)
+
+    def window(kind):
+        if kind == "rows":
+            rect.reset(first, torch.full((B,), first, dtype=torch.int32, device=dev), first)
+            cache = rect
+        else:
+            paged.start_rows(range(B), [first] * B)                     # (the rows hold their pages: only the positions move)
+            cache = paged
+        return timed(lambda: m.decode_step(last, cache), steps)
+    legs = ("rows", "paged")
+    for k in legs:
+        window(k)
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for k in (legs if r % 2 == 0 else legs[::-1]):
+            us[k].append(window(k))
+    med = {k: statistics.median(v) for k, v in us.items()}
+    return {"part": "step", "B": B, "context": ctx, "windows": {"decode_steps": steps, "rounds": rounds, "positions": [first, ctx - 2]},
+            "us_per_token": {k: summary(v, 1) for k, v in us.items()}, "paged_over_rows": round(med["paged"] / med["rows"], 3),
+            "paged_minus_rows_us_and_spreads": _gap(us, "paged", "rows", 1), "tokens_per_s": {k: round(B / med[k] * 1e6) for k in legs}}
+
+
+def build_small_vocab(block_size, vocab, dev):
+    """decode_bench.build's model with another vocabulary (the workload: see the head of this file)"""
+    import warnings
+    from omnibiote_amd.model import OmniBioTA, OmniBioTAConfig
+    from omnibiote_amd.mup_compat import set_base_shapes
+
+    def make(n_embd, n_head):
+        c = OmniBioTAConfig()
+        c.block_size, c.vocab_size, c.n_layer, c.n_head, c.n_embd, c.dropout, c.flash = block_size, vocab, 8, n_head, n_embd, 0.0, True
+        c.autoregressive = True
+        return OmniBioTA(c)
+    torch.manual_seed(0)
+    with contextlib.redirect_stdout(io.StringIO()), warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        m = make(1024, 8)
+        set_base_shapes(m, make(24, 3), delta=make(48, 12))
+        m.to(torch.bfloat16)
+    return m.to(dev).eval()
+
+
+def workload(n_prompts, vocab, pool_share, rounds, dev):
+    from omnibiote_amd import _lib
+    from omnibiote_amd.paged import PagedSchedule, pool_bytes
+    new, batch, eos = 256, 64, 7
+    m = build_small_vocab(1024 + new, vocab, dev)
+    cfg = m.config
+    H, hs = cfg.n_head, cfg.n_embd // cfg.n_head
+    g = torch.Generator().manual_seed(11)
+    lens = torch.linspace(64, 1024, n_prompts).long()[torch.randperm(n_prompts, generator=g)].tolist()
+    prompts = [torch.randint(8, vocab, (n,), generator=g).to(dev) for n in lens]
+    default_pages = PagedSchedule(lens, new, batch).n_pages
+    pools = {"generate_many": default_pages, f"generate_many_{pool_share}_pool": max(int(default_pages * pool_share), max(PagedSchedule(lens, new, batch).need))}
+    calls = {"n": 0}
+    plain_step = m.decode_step
+
+    def counted(*a, **k):
+        calls["n"] += 1
+        return plain_step(*a, **k)
+    m.decode_step = counted
+
+    def many(n_pages):
+        def run():
+            out = m.generate_many(prompts, new, batch, n_pages=n_pages, eos_token=eos, generator=torch.Generator(device=dev).manual_seed(3))
+            return [o.numel() - n for o, n in zip(out, lens)], None
+        return run
+
+    def batched():
+        made, peak = [], 0
+        for i in range(0, n_prompts, batch):
+            part, ln = prompts[i:i + batch], lens[i:i + batch]
+            idx = torch.nn.utils.rnn.pad_sequence(part, batch_first=True)
+            _, n_out = m.generate(idx, new, lengths=ln, sampler="device", eos_token=eos, generator=torch.Generator(device=dev).manual_seed(3))
+            made += [int(a) - b for a, b in zip(n_out.tolist(), ln)]
+            peak = max(peak, cfg.n_layer * int(_lib.lib().obte_kv_cache_bytes(len(part), max(ln) + new, H, hs)))
+        return made, peak
+    legs = {"generate_batches": batched, **{k: many(v) for k, v in pools.items()}}
+    res = {k: {"tokens_per_s": [], "wall_s": []} for k in legs}
+    for r in range(rounds + 1):                                         # (round 0 warms up)
+        for k in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            calls["n"] = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            made, peak = legs[k]()
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            if r == 0:
+                res[k].update(new_tokens=sum(made), rows_ended_by_eos=sum(1 for n in made if n < new), decode_steps=calls["n"],
+                              share_of_row_steps_on_finished_rows=round(1 - sum(n - 1 for n in made) / max(calls["n"] * batch, 1), 3),
+                              peak_cache_bytes=peak if peak is not None else cfg.n_layer * pool_bytes(pools[k], H, hs))
+                continue
+            res[k]["tokens_per_s"].append(sum(made) / wall)
+            res[k]["wall_s"].append(wall)
+    base = statistics.median(res["generate_batches"]["tokens_per_s"])
+    for k, v in res.items():
+        v["over_generate_batches"] = round(statistics.median(v["tokens_per_s"]) / base, 3)
+        v["tokens_per_s"], v["wall_s"] = summary(v["tokens_per_s"], 0), summary(v["wall_s"], 3)
+    return {"part": "workload", "prompts": n_prompts, "lengths": [min(lens), max(lens)], "max_new_tokens": new, "batch": batch, "vocab": vocab, "eos_token": eos,
+            "pages": pools, "rounds": rounds, **res}
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--parts", default="attention,step,workload")
+    p.add_argument("--rounds", type=int, default=5)
+    p.add_argument("--steps", type=int, default=200, help="attention calls and decode steps per timed window")
+    p.add_argument("--prompts", type=int, default=256)
+    p.add_argument("--vocab", type=int, default=256)
+    p.add_argument("--pool-share", type=float, default=0.65)
+    a = p.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    parts = a.parts.split(",")
+    if "attention" in parts or "step" in parts:
+        m = build(2048, dev)
+        for B, ctx in ((64, 2048), (8, 2048)):
+            if "attention" in parts:
+                print(json.dumps(attention(m, B, ctx, a.rounds, a.steps, dev)), flush=True)
+                torch.cuda.empty_cache()
+            if "step" in parts:
+                print(json.dumps(step(m, B, ctx, a.rounds, a.steps, dev)), flush=True)
+                torch.cuda.empty_cache()
+        del m
+        torch.cuda.empty_cache()
+    if "workload" in parts:
+        print(json.dumps(workload(a.prompts, a.vocab, a.pool_share, a.rounds, dev)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
