@@ -318,6 +318,19 @@ SYMBOLS_PAGED = {
                                           C.c_void_p, C.c_int64, c_stream]),
 }
 
+# the pages as OCP e4m3 codes with one scale per head vector (include/omnibiote_hip_paged8.h): SYMBOLS_PAGED's argument lists over the e4m3 pool
+SYMBOLS_PAGED8 = {
+    "obte_kv8_paged_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "obte_kv8_paged_store": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
+    "obte_kv8_paged_rope_store_rows": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
+    "obte_attn_decode_paged8": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_fwd_prefill_paged8": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                c_stream]),
+    "obte_block_decode_paged8": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -349,7 +362,8 @@ def lib():
                                             + list(SYMBOLS_EXTEND.items()) + list(SYMBOLS_SPEC.items()) + list(SYMBOLS_KV8.items())
                                             + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
                                             + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items()) + list(SYMBOLS_PENALTY.items())
-                                            + list(SYMBOLS_DISTILL.items()) + list(SYMBOLS_BEAM.items()) + list(SYMBOLS_PAGED.items())):
+                                            + list(SYMBOLS_DISTILL.items()) + list(SYMBOLS_BEAM.items()) + list(SYMBOLS_PAGED.items())
+                                            + list(SYMBOLS_PAGED8.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

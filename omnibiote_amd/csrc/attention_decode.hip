@@ -1,7 +1,8 @@
 // Autoregressive generation: the key/value cache and attention for ONE query per (batch, head) (include/omnibiote_hip.h,
 // "autoregressive generation"; extends training/model.py:115-130, whose generate() the reference struck out).
 //
-// One layer's cache comes in three formats, and every kernel of this file is written once over a format struct (CacheBf16, CacheE4m3, CachePaged):
+// One layer's cache comes in four formats, and every kernel of this file is written once over a format struct (CacheBf16, CacheE4m3, CachePaged,
+// CachePaged8):
 //   - bf16 (include/omnibiote_hip.h): K [B, H, T_max, hs] followed by V in the same shape: a (b, h)'s keys are hs * 2 bytes apart, so a
 //     step streams them as one contiguous run.
 //   - OCP e4m3 (include/omnibiote_hip_kv8.h; the format in words and in plain torch: omnibiote_amd/kvquant.py): K codes uint8
@@ -11,6 +12,8 @@
 //     the cache is a pure function of the bf16 inputs.
 //   - bf16 in pages (include/omnibiote_hip_paged.h; in plain torch: omnibiote_amd/paged.py): K [n_pages, H, 64, hs] followed by V, and an
 //     int32 table [rows, table_ld] that says which page holds positions [64 j, 64 j + 64) of row b: the same vectors at other addresses.
+//   - e4m3 in pages (include/omnibiote_hip_paged8.h): K codes [n_pages, H, 64, hs], V codes, K scales fp32 [n_pages, H, 64], V scales, under
+//     the same table: the e4m3 cache's codes and scales at other addresses.
 // A format states what differs: the dims a lane holds (DPL), where V and the scales lie behind K, how a lane's piece of a key is loaded
 // and turned into floats, whether a per-key scale exists, and how 8 values of a head vector are written to the cache.
 //
@@ -148,6 +151,14 @@ struct CacheE4m3 {
     }
 };
 
+// the e4m3 vectors in a pool of pages (include/omnibiote_hip_paged8.h): K codes [n_pages, H, 64, hs], V codes, K scales [n_pages, H, 64], V scales;
+// n_vec = n_pages H 64.  The attention's view: k, v, ks and vs are head h's blocks of page 0, a page is H 64 hs codes and H 64 scales further;
+// the store's view: vec = (page H + h) 64 + slot, which is where put() writes the scale as well
+struct CachePaged8 : CacheE4m3 {
+    static constexpr bool PAGED = true;
+    using CacheE4m3::CacheE4m3;
+};
+
 // ---- the attention --------------------------------------------------------------------------------------------------------------------------
 template <int DPL>
 struct Part { float m, l, acc[DPL]; };   // one online-softmax state, exp2 domain: sum_k exp2(s_k - m) (1, v_k) for the DPL dims of a lane
@@ -197,17 +208,32 @@ __device__ __forceinline__ void decode_keys(Part<Fmt::DPL>& st, const float* qf,
         const int key = key0 + u * kstride;
         ok[u] = !TAIL || key < k1;
         const int64_t kk = ok[u] ? key : k1 - 1;   // (k1 - 1 >= k0: a workgroup with no key never gets here)
-        int64_t off = (PAGED ? kk & (DEC_CHUNK - 1) : kk) * HS + chunk * DPL;   // in elements, of either format; one offset for both loads: K and V addresses are formed alike
-        if constexpr (ANC || PAGED) {
+        if constexpr (Fmt::SCALED && PAGED) {
+            // Four loads per key, each a workgroup-uniform page base (a missing page: page 0, for the scales too; a page is row_stride codes
+            // and row_stride / HS = H 64 scales) plus the key's slot as a 32-bit lane offset.  Written as one 64-bit offset per load the
+            // address arithmetic took the registers of two of the round's sixteen loads, which then issued behind the first uses.
+            // Page 0 may be a page nobody holds: what the four loads of a key that is not ok bring is dropped where it is used, below.
             const bool there = (uint32_t)from[u] < (uint32_t)group;
             ok[u] = ok[u] && there;
-            off += (there ? (int64_t)from[u] : 0) * row_stride;
-        }
-        kr[u] = Fmt::load(c.k + off);
-        vr[u] = Fmt::load(c.v + off);
-        if constexpr (Fmt::SCALED) {
-            ksc[u] = c.ks[kk];
-            vsc[u] = c.vs[kk];
+            const int64_t page = there ? (int64_t)from[u] : 0;
+            const int slot = (int)kk & (DEC_CHUNK - 1), lo = slot * HS + chunk * DPL;
+            kr[u] = Fmt::load(c.k + page * row_stride + lo);
+            vr[u] = Fmt::load(c.v + page * row_stride + lo);
+            ksc[u] = (c.ks + page * (row_stride / HS))[slot];
+            vsc[u] = (c.vs + page * (row_stride / HS))[slot];
+        } else {
+            int64_t off = (PAGED ? kk & (DEC_CHUNK - 1) : kk) * HS + chunk * DPL;   // in elements, of either format; one offset for both loads: K and V addresses are formed alike
+            if constexpr (ANC || PAGED) {
+                const bool there = (uint32_t)from[u] < (uint32_t)group;
+                ok[u] = ok[u] && there;
+                off += (there ? (int64_t)from[u] : 0) * row_stride;
+            }
+            kr[u] = Fmt::load(c.k + off);
+            vr[u] = Fmt::load(c.v + off);
+            if constexpr (Fmt::SCALED) {
+                ksc[u] = c.ks[kk];
+                vsc[u] = c.vs[kk];
+            }
         }
     }
     float sc[DEC_UNROLL];
@@ -235,6 +261,9 @@ __device__ __forceinline__ void decode_keys(Part<Fmt::DPL>& st, const float* qf,
         const float p = ok[u] ? __builtin_amdgcn_exp2f(sc[u] - ms) : 0.f;
         float pv = p;
         if constexpr (Fmt::SCALED) pv = p * vsc[u];
+        // a key without a page has page 0's V scale, which may be anything (a page nobody holds: NaN, Inf): 0 * NaN would reach acc.  The
+        // rectangular form's key that is not ok reloads key k1 - 1, whose scale is a finite power of two: p * vsc is an exact 0 there
+        if constexpr (Fmt::SCALED && PAGED) pv = ok[u] ? pv : 0.f;
         float vf[DPL];
         Fmt::to_float(ok[u] ? vr[u] : typename Fmt::Piece{}, vf);   // (a zero piece)
         st.l += p;
@@ -357,13 +386,14 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16*
 // so every round's first key is: a round's keys lie in ROUND / 64 pages known from the loop counter, and their table entries are read
 // with workgroup-uniform indices (scalar loads), one round ahead: a round's K / V addresses need its entries, and a load issued at the top
 // of the round would stand between every two rounds' vector loads.
-template <int HS>
+// Fmt: CachePaged, or CachePaged8 (obte_attn_decode_paged8, include/omnibiote_hip_paged8.h): attn_decode_kernel<CacheE4m3, HS, true, false> in the
+// same way; a round is 2 (head size 128) or 4 (64) pages, and a key's two scales come from its page's scale block.
+template <class Fmt, int HS>
 __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_paged_kernel(const bf16* __restrict__ q, int64_t q_ld, const void* __restrict__ pool,
                                                                             bf16* __restrict__ o, float* __restrict__ lse, float* __restrict__ part, int H,
                                                                             int64_t table_ld, int n_pages, int max_keys, float qscale,
                                                                             const int32_t* __restrict__ rows_n, int rows_off,
                                                                             const int32_t* __restrict__ table) {
-    typedef CachePaged Fmt;
     constexpr int DPL = Fmt::DPL;
     constexpr int LPR = HS / DPL;      // lanes per key
     constexpr int G = 64 / LPR;        // keys per wave and load
@@ -752,16 +782,39 @@ bool paged_shape_ok(int64_t B, int64_t n_pages, int64_t table_ld, int32_t n_head
     return shape_ok(B, 1, n_head, head_dim) && n_pages > 0 && n_pages < (1ll << 24) && table_ld > 0 && table_ld < (1ll << 18);   // (64 table_ld < 2^24, as T_max)
 }
 
-// the launch behind the two paged stores, each after its own argument checks: kv_store_launch's, with the table
-int kv_paged_store_launch(const char* who, const obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos_rows, int64_t max_pos, int64_t B,
-                          int64_t n, int32_t n_head, int32_t head_dim, void* pool, int64_t n_pages, const int32_t* table, int64_t table_ld, obte_stream s) {
+// the launch behind the four paged stores, each after its own argument checks: kv_store_launch's, with the table
+int kv_paged_store_launch(const char* who, bool e4m3, const obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos_rows, int64_t max_pos,
+                          int64_t B, int64_t n, int32_t n_head, int32_t head_dim, void* pool, int64_t n_pages, const int32_t* table, int64_t table_ld, obte_stream s) {
     const int64_t items = B * n * (pos_rows ? 3 : 2) * n_head * head_dim / 8;
     OBTE_REQUIRE(cdiv64(items, 256) < (1ll << 31), "%s: too many rows for one launch", who);
-    const auto kernel = pos_rows ? kv_store_kernel<CachePaged, true> : kv_store_kernel<CachePaged, false>;
+    const auto kernel = pos_rows ? (e4m3 ? kv_store_kernel<CachePaged8, true> : kv_store_kernel<CachePaged, true>)
+                                 : (e4m3 ? kv_store_kernel<CachePaged8, false> : kv_store_kernel<CachePaged, false>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)cdiv64(items, 256)), dim3(256), 0, (hipStream_t)s, (bf16*)qkv, pool, items, table_ld, (int64_t)0,
                        n_pages * n_head * DEC_CHUNK, (int)n, n_head, head_dim, (int)max_pos, rope_cos, rope_sin, pos_rows, table, (int)n_pages);
     OBTE_CHECK_LAUNCH(who);
     return OBTE_OK;
+}
+
+// obte_kv_paged_store and obte_kv8_paged_store: the same checks
+int kv_paged_store_checked(const char* who, bool e4m3, const obte_bf16* qkv, int64_t B, int64_t t, int32_t n_head, int32_t head_dim, void* pool, int64_t n_pages,
+                           const int32_t* table, int64_t table_ld, obte_stream s) {
+    OBTE_REQUIRE(qkv && pool && table, "%s: null pointer", who);
+    OBTE_REQUIRE(paged_shape_ok(B, n_pages, table_ld, n_head, head_dim), "%s: bad shape (head_dim 64 or 128)", who);
+    OBTE_REQUIRE(t > 0 && t <= DEC_CHUNK * table_ld, "%s: positions [0, %lld) do not fit the table's %lld pages per row", who, (long long)t, (long long)table_ld);
+    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)pool) & 15) == 0 && ((uintptr_t)table & 3) == 0, "%s: qkv and pool must be 16-byte aligned, table 4-byte aligned", who);
+    return kv_paged_store_launch(who, e4m3, qkv, nullptr, nullptr, nullptr, 0, B, t, n_head, head_dim, pool, n_pages, table, table_ld, s);
+}
+
+// obte_kv_paged_rope_store_rows and obte_kv8_paged_rope_store_rows: the same checks
+int paged_rope_store_rows_checked(const char* who, bool e4m3, obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos, int64_t max_pos, int64_t B,
+                                  int32_t n_head, int32_t head_dim, void* pool, int64_t n_pages, const int32_t* table, int64_t table_ld, obte_stream s) {
+    OBTE_REQUIRE(qkv && rope_cos && rope_sin && pos && pool && table, "%s: null pointer", who);
+    OBTE_REQUIRE(paged_shape_ok(B, n_pages, table_ld, n_head, head_dim), "%s: bad shape (head_dim 64 or 128)", who);
+    OBTE_REQUIRE(max_pos >= 0 && max_pos < DEC_CHUNK * table_ld, "%s: max_pos = %lld outside the table's [0, %lld)", who, (long long)max_pos,
+                 (long long)(DEC_CHUNK * table_ld));
+    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)pool | (uintptr_t)rope_cos | (uintptr_t)rope_sin) & 15) == 0 && (((uintptr_t)pos | (uintptr_t)table) & 3) == 0,
+                 "%s: qkv, pool and the rope tables must be 16-byte aligned, pos and table 4-byte aligned", who);
+    return kv_paged_store_launch(who, e4m3, qkv, rope_cos, rope_sin, pos, max_pos, B, 1, n_head, head_dim, pool, n_pages, table, table_ld, s);
 }
 
 }  // namespace
@@ -770,31 +823,37 @@ extern "C" int64_t obte_kv_paged_bytes(int64_t n_pages, int32_t n_head, int32_t 
     return paged_shape_ok(1, n_pages, 1, n_head, head_dim) ? 2 * n_pages * n_head * DEC_CHUNK * head_dim * 2 : 0;
 }
 
+extern "C" int64_t obte_kv8_paged_bytes(int64_t n_pages, int32_t n_head, int32_t head_dim) {
+    return paged_shape_ok(1, n_pages, 1, n_head, head_dim) ? 2 * n_pages * n_head * DEC_CHUNK * (int64_t)(head_dim + 4) : 0;
+}
+
 extern "C" int obte_kv_paged_store(const obte_bf16* qkv, int64_t B, int64_t t, int32_t n_head, int32_t head_dim, obte_bf16* pool, int64_t n_pages,
                                    const int32_t* table, int64_t table_ld, obte_stream s) {
-    const char* who = "obte_kv_paged_store";
-    OBTE_REQUIRE(qkv && pool && table, "%s: null pointer", who);
-    OBTE_REQUIRE(paged_shape_ok(B, n_pages, table_ld, n_head, head_dim), "%s: bad shape (head_dim 64 or 128)", who);
-    OBTE_REQUIRE(t > 0 && t <= DEC_CHUNK * table_ld, "%s: positions [0, %lld) do not fit the table's %lld pages per row", who, (long long)t, (long long)table_ld);
-    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)pool) & 15) == 0 && ((uintptr_t)table & 3) == 0, "%s: qkv and pool must be 16-byte aligned, table 4-byte aligned", who);
-    return kv_paged_store_launch(who, qkv, nullptr, nullptr, nullptr, 0, B, t, n_head, head_dim, pool, n_pages, table, table_ld, s);
+    return kv_paged_store_checked("obte_kv_paged_store", false, qkv, B, t, n_head, head_dim, pool, n_pages, table, table_ld, s);
+}
+
+extern "C" int obte_kv8_paged_store(const obte_bf16* qkv, int64_t B, int64_t t, int32_t n_head, int32_t head_dim, void* pool8, int64_t n_pages, const int32_t* table,
+                                    int64_t table_ld, obte_stream s) {
+    return kv_paged_store_checked("obte_kv8_paged_store", true, qkv, B, t, n_head, head_dim, pool8, n_pages, table, table_ld, s);
 }
 
 extern "C" int obte_kv_paged_rope_store_rows(obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos, int64_t max_pos, int64_t B,
                                              int32_t n_head, int32_t head_dim, obte_bf16* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,
                                              obte_stream s) {
-    const char* who = "obte_kv_paged_rope_store_rows";
-    OBTE_REQUIRE(qkv && rope_cos && rope_sin && pos && pool && table, "%s: null pointer", who);
-    OBTE_REQUIRE(paged_shape_ok(B, n_pages, table_ld, n_head, head_dim), "%s: bad shape (head_dim 64 or 128)", who);
-    OBTE_REQUIRE(max_pos >= 0 && max_pos < DEC_CHUNK * table_ld, "%s: max_pos = %lld outside the table's [0, %lld)", who, (long long)max_pos,
-                 (long long)(DEC_CHUNK * table_ld));
-    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)pool | (uintptr_t)rope_cos | (uintptr_t)rope_sin) & 15) == 0 && (((uintptr_t)pos | (uintptr_t)table) & 3) == 0,
-                 "%s: qkv, pool and the rope tables must be 16-byte aligned, pos and table 4-byte aligned", who);
-    return kv_paged_store_launch(who, qkv, rope_cos, rope_sin, pos, max_pos, B, 1, n_head, head_dim, pool, n_pages, table, table_ld, s);
+    return paged_rope_store_rows_checked("obte_kv_paged_rope_store_rows", false, qkv, rope_cos, rope_sin, pos, max_pos, B, n_head, head_dim, pool, n_pages, table,
+                                         table_ld, s);
 }
 
-// obte_attn_decode_on's checks and its two launches, on the pool: row b over rows_n[b] + key_off keys, max_keys the host's bound on that
-int obte_attn_decode_paged_on(const char* who, const obte_bf16* q, int64_t q_ld, const obte_bf16* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,
+extern "C" int obte_kv8_paged_rope_store_rows(obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos, int64_t max_pos, int64_t B,
+                                              int32_t n_head, int32_t head_dim, void* pool8, int64_t n_pages, const int32_t* table, int64_t table_ld,
+                                              obte_stream s) {
+    return paged_rope_store_rows_checked("obte_kv8_paged_rope_store_rows", true, qkv, rope_cos, rope_sin, pos, max_pos, B, n_head, head_dim, pool8, n_pages, table,
+                                         table_ld, s);
+}
+
+// obte_attn_decode_on's checks and its two launches, on the pool (e4m3: the pool of include/omnibiote_hip_paged8.h): row b over rows_n[b] + key_off keys,
+// max_keys the host's bound on that
+int obte_attn_decode_paged_on(bool e4m3, const char* who, const obte_bf16* q, int64_t q_ld, const void* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,
                               obte_bf16* o, float* lse, int64_t B, const int32_t* rows_n, int32_t key_off, int64_t max_keys, int32_t n_head, int32_t head_dim,
                               float scale, int32_t splits, void* ws, int64_t ws_bytes, obte_stream s) {
     OBTE_REQUIRE(q && pool && table && o && rows_n, "%s: null pointer", who);
@@ -813,9 +872,10 @@ int obte_attn_decode_paged_on(const char* who, const obte_bf16* q, int64_t q_ld,
     }
     const hipStream_t st = (hipStream_t)s;
     const int BH = (int)(B * n_head);
-    const int prof = obte_prof_begin(st, 102, BH, max_keys, head_dim);
-    const auto kernel = head_dim == 128 ? attn_decode_paged_kernel<128> : attn_decode_paged_kernel<64>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)splits, (unsigned)BH), dim3(DEC_WAVES * 64), 0, st, (const bf16*)q, q_ld, (const void*)pool, (bf16*)o, lse, (float*)ws,
+    const int prof = obte_prof_begin(st, e4m3 ? 119 : 102, BH, max_keys, head_dim);
+    const auto kernel = e4m3 ? (head_dim == 128 ? attn_decode_paged_kernel<CachePaged8, 128> : attn_decode_paged_kernel<CachePaged8, 64>)
+                             : (head_dim == 128 ? attn_decode_paged_kernel<CachePaged, 128> : attn_decode_paged_kernel<CachePaged, 64>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)splits, (unsigned)BH), dim3(DEC_WAVES * 64), 0, st, (const bf16*)q, q_ld, pool, (bf16*)o, lse, (float*)ws,
                        n_head, table_ld, (int)n_pages, (int)max_keys, scale * 1.4426950408889634f, rows_n, key_off, table);
     if (splits > 1) {
         if (head_dim == 128) hipLaunchKernelGGL(attn_decode_combine_kernel<128>, dim3((unsigned)BH), dim3(128), 0, st, (const float*)ws, (bf16*)o, lse, (int)splits);
@@ -829,6 +889,13 @@ int obte_attn_decode_paged_on(const char* who, const obte_bf16* q, int64_t q_ld,
 extern "C" int obte_attn_decode_paged(const obte_bf16* q, int64_t q_ld, const obte_bf16* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,
                                       obte_bf16* o, float* lse, int64_t B, const int32_t* n_keys, int64_t max_keys, int32_t n_head, int32_t head_dim, float scale,
                                       int32_t splits, void* ws, int64_t ws_bytes, obte_stream s) {
-    return obte_attn_decode_paged_on("obte_attn_decode_paged", q, q_ld, pool, n_pages, table, table_ld, o, lse, B, n_keys, 0, max_keys, n_head, head_dim, scale, splits,
-                                     ws, ws_bytes, s);
+    return obte_attn_decode_paged_on(false, "obte_attn_decode_paged", q, q_ld, pool, n_pages, table, table_ld, o, lse, B, n_keys, 0, max_keys, n_head, head_dim, scale,
+                                     splits, ws, ws_bytes, s);
+}
+
+extern "C" int obte_attn_decode_paged8(const obte_bf16* q, int64_t q_ld, const void* pool8, int64_t n_pages, const int32_t* table, int64_t table_ld, obte_bf16* o,
+                                       float* lse, int64_t B, const int32_t* n_keys, int64_t max_keys, int32_t n_head, int32_t head_dim, float scale, int32_t splits,
+                                       void* ws, int64_t ws_bytes, obte_stream s) {
+    return obte_attn_decode_paged_on(true, "obte_attn_decode_paged8", q, q_ld, pool8, n_pages, table, table_ld, o, lse, B, n_keys, 0, max_keys, n_head, head_dim, scale,
+                                     splits, ws, ws_bytes, s);
 }

@@ -526,12 +526,14 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
     if (at.n_new > 0) {   // n_new positions per row join the cache (the rows form rotates them as it stores), then each attends over those up to its own
         const int64_t q_ld = 3 * (int64_t)C;
         const char* who = at.kv8 || at.pos_rows ? at.who : "obte_attn_decode";   // (the uniform bf16 step's attention refuses under its own name)
-        if (at.page_table)   // (the rows-form decode step through the page table)
+        if (at.page_table && at.kv8)   // (the rows-form decode step through the page table; the e4m3 pool: include/omnibiote_hip_paged8.h)
+            TRY(obte_kv8_paged_rope_store_rows(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.n_pages, at.page_table, at.table_ld, s));
+        else if (at.page_table)
             TRY(obte_kv_paged_rope_store_rows(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.n_pages, at.page_table, at.table_ld, s));
         else
             TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, s));
         if (at.page_table)    // row b over its own pos_rows[b] + 1 keys, each read from its page
-            TRY(obte_attn_decode_paged_on(who, w.qkv, q_ld, at.kv_cache, at.n_pages, at.page_table, at.table_ld, w.att, nullptr, d->B, at.pos_rows, 1, at.pos + 1, H, hs,
+            TRY(obte_attn_decode_paged_on(at.kv8, who, w.qkv, q_ld, at.kv_cache, at.n_pages, at.page_table, at.table_ld, w.att, nullptr, d->B, at.pos_rows, 1, at.pos + 1, H, hs,
                                           scale, 0, at.dec_ws, at.dec_ws_bytes, s));
         else if (at.prefix_cache && at.ancestry)   // the same, the slots 0 .. pos read through the ancestry table
             TRY(obte_attn_decode_beam(w.qkv, q_ld, at.prefix_cache, at.P, at.T_pre, at.n_prefix, at.kv_cache, d->B / at.P, at.T_max, at.pos + 1, at.ancestry, w.att, nullptr, H,
@@ -551,7 +553,8 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
         af.B = d->B; af.T = d->T; af.n_head = H; af.head_dim = hs; af.scale = scale;
         af.dropout_p = d->dropout_p; af.dropout_seed = d->dropout_seed;
         TRY(obte_attn_fwd(&af, s));
-        if (at.page_table) TRY(obte_kv_paged_store(w.qkv, d->B, d->T, H, hs, at.kv_cache, at.n_pages, at.page_table, at.table_ld, s));
+        if (at.page_table && at.kv8) TRY(obte_kv8_paged_store(w.qkv, d->B, d->T, H, hs, at.kv_cache, at.n_pages, at.page_table, at.table_ld, s));
+        else if (at.page_table) TRY(obte_kv_paged_store(w.qkv, d->B, d->T, H, hs, at.kv_cache, at.n_pages, at.page_table, at.table_ld, s));
         else if (at.kv_cache) TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, nullptr, nullptr, nullptr, 0, d->B, d->T, H, hs, at.kv_cache, at.T_max, s));   // (c_fc's activation overwrites qkv below)
     }
     TRY(run(plus_residual(xWt(w.att, d->proj_w, w.x1, M, C, C), x, d->dropout_p, d->dropout_seed, SITE_RESID), 1, s));
@@ -573,7 +576,7 @@ int infer_or_prefill(const char* who, const obte_block_desc* d, const obte_bf16*
     OBTE_REQUIRE(x && y_out && ws && (!prefill || kv_cache), "%s: null pointer", who);
     OBTE_REQUIRE(!prefill || d->T <= T_max, page_table ? "%s: %lld positions do not fit the table's %lld" : "%s: %lld positions do not fit T_max = %lld", who,
                  (long long)d->T, (long long)T_max);
-    OBTE_REQUIRE(!kv8 || ((uintptr_t)kv_cache & 15) == 0, "%s: cache8 must be 16-byte aligned", who);
+    OBTE_REQUIRE(!kv8 || (((uintptr_t)kv_cache & 15) == 0 && ((uintptr_t)page_table & 3) == 0), "%s: cache8 must be 16-byte aligned, a page table 4-byte aligned", who);
     const InferLayout w(d->B, d->T, d->n_embd, d->n_head, ws);
     OBTE_REQUIRE(ws_bytes >= w.total, "%s: workspace of %lld bytes, obte_block_infer_ws_bytes() asks for %lld", who, (long long)ws_bytes, (long long)w.total);
     InferAttention at = {prefill ? kv_cache : nullptr, T_max, -1, nullptr, 0};
@@ -607,6 +610,15 @@ extern "C" int obte_block_fwd_prefill_paged(const obte_block_desc* d, const obte
     return infer_or_prefill(who, d, x, y_out, ws, ws_bytes, pool, OBTE_KV_PAGE * table_ld, true, s, false, table, n_pages);
 }
 
+// into the pages of an e4m3 pool (include/omnibiote_hip_paged8.h): both flags of InferAttention
+extern "C" int obte_block_fwd_prefill_paged8(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* ws, int64_t ws_bytes, void* pool8, int64_t n_pages,
+                                             const int32_t* table, int64_t table_ld, obte_stream s) {
+    const char* who = "obte_block_fwd_prefill_paged8";
+    OBTE_REQUIRE(pool8 && table, "%s: null pointer", who);
+    OBTE_REQUIRE(n_pages > 0 && n_pages < (1ll << 24) && table_ld > 0 && table_ld < (1ll << 18), "%s: bad shape (n_pages in [1, 2^24), table_ld at least 1)", who);
+    return infer_or_prefill(who, d, x, y_out, ws, ws_bytes, (obte_bf16*)pool8, OBTE_KV_PAGE * table_ld, true, s, true, table, n_pages);
+}
+
 // ---- new positions per row against the cache --------------------------------------------------------------------------------------------
 namespace {
 
@@ -635,8 +647,8 @@ int cached_step(const char* who, const obte_block_desc* d, const obte_bf16* x, o
     }
     const int C = d->n_embd, H = d->n_head, hs = C / H;
     if (kv8)   // what its two launchers would refuse, before the first launch of the sequence
-        OBTE_REQUIRE(((uintptr_t)kv_cache & 15) == 0 && ((uintptr_t)pos_rows & 3) == 0 && d->B * H <= 65535,
-                     "%s: cache8 must be 16-byte aligned, pos_rows 4-byte aligned, B * n_head <= 65535", who);
+        OBTE_REQUIRE(((uintptr_t)kv_cache & 15) == 0 && (((uintptr_t)pos_rows | (uintptr_t)page_table) & 3) == 0 && d->B * H <= 65535,
+                     "%s: cache8 must be 16-byte aligned, pos_rows and a page table 4-byte aligned, B * n_head <= 65535", who);
     const int64_t att_bytes = decode ? obte_attn_decode_ws_bytes(d->B, H, hs) : obte_attn_extend_ws_bytes(d->B, H, hs, n, 0);
     OBTE_REQUIRE(decode || att_bytes > 0, "%s: bad shape (B * n_head <= 65535)", who);
     const InferLayout w(d->B, n, C, H, ws);
@@ -676,6 +688,15 @@ extern "C" int obte_block_decode_paged(const obte_block_desc* d, const obte_bf16
     OBTE_REQUIRE(pool && table, "%s: null pointer", who);
     OBTE_REQUIRE(n_pages > 0 && table_ld > 0 && table_ld < (1ll << 18), "%s: bad shape (n_pages and table_ld at least 1)", who);
     return cached_step(who, d, x, y_out, pool, OBTE_KV_PAGE * table_ld, max_pos, pos, true, true, ws, ws_bytes, s, false, nullptr, nullptr, table, n_pages);
+}
+
+// the same on the pages of an e4m3 pool (include/omnibiote_hip_paged8.h)
+extern "C" int obte_block_decode_paged8(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, void* pool8, int64_t n_pages, const int32_t* table,
+                                        int64_t table_ld, const int32_t* pos, int64_t max_pos, void* ws, int64_t ws_bytes, obte_stream s) {
+    const char* who = "obte_block_decode_paged8";
+    OBTE_REQUIRE(pool8 && table, "%s: null pointer", who);
+    OBTE_REQUIRE(n_pages > 0 && n_pages < (1ll << 24) && table_ld > 0 && table_ld < (1ll << 18), "%s: bad shape (n_pages in [1, 2^24), table_ld at least 1)", who);
+    return cached_step(who, d, x, y_out, (obte_bf16*)pool8, OBTE_KV_PAGE * table_ld, max_pos, pos, true, true, ws, ws_bytes, s, true, nullptr, nullptr, table, n_pages);
 }
 
 // the two on the e4m3 cache (include/omnibiote_hip_kv8.h): pos_rows null or not

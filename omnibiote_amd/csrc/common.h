@@ -17,6 +17,7 @@
 #include "../../include/omnibiote_hip_w8.h"
 #include "../../include/omnibiote_hip_beam.h"
 #include "../../include/omnibiote_hip_paged.h"
+#include "../../include/omnibiote_hip_paged8.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -103,8 +104,9 @@ int obte_attn_decode_on(bool e4m3, const char* who, const obte_bf16* q, int64_t 
 // here; pos: their bound; e4m3: n = 1); who: named in an error where the entry point's own name is not (the e4m3 rows form)
 int obte_kv_store_on(bool e4m3, const char* who, obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos_rows, int64_t pos, int64_t B, int64_t n,
                      int32_t n_head, int32_t head_dim, void* cache, int64_t T_max, obte_stream s);
-// obte_attn_decode_paged (include/omnibiote_hip_paged.h) with row b's key count read as rows_n[b] + key_off, under `who`'s name
-int obte_attn_decode_paged_on(const char* who, const obte_bf16* q, int64_t q_ld, const obte_bf16* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,
+// obte_attn_decode_paged (include/omnibiote_hip_paged.h; e4m3: obte_attn_decode_paged8, include/omnibiote_hip_paged8.h) with row b's key count read as
+// rows_n[b] + key_off, under `who`'s name
+int obte_attn_decode_paged_on(bool e4m3, const char* who, const obte_bf16* q, int64_t q_ld, const void* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,
                               obte_bf16* o, float* lse, int64_t B, const int32_t* rows_n, int32_t key_off, int64_t max_keys, int32_t n_head, int32_t head_dim,
                               float scale, int32_t splits, void* ws, int64_t ws_bytes, obte_stream s);
 constexpr int DEC_PAD = 4;       // a partial of the attention is hs + 4 floats (acc[hs], m, l, 2 unused): 16-byte aligned rows

@@ -631,11 +631,17 @@ class PagedKVCache(PagedPositions):
     alone; ``decode_step`` gives every active row whose position opens a new page one from the free list, then steps;
     ``OmniBioTA.generate_many`` is the loop that admits, steps and releases.  ``free_order``: the order in which pages are first handed out.
 
-    Not built, each refused before anything is launched: an e4m3 pool; several new positions per row over pages (``extend``,
+    ``dtype``: "bf16" (the default) or "fp8" — the pools hold OCP e4m3 codes with one power-of-two scale per head vector
+    (include/omnibiote_hip_paged8.h, ``ops.kv8_paged_buffer``): ``KVCache(dtype="fp8")``'s vectors in pages, 2 (hs + 4) bytes each instead
+    of 4 hs, so the same ``n_pages`` take about half the bytes.  The table, the free list and the positions do not depend on it.
+
+    Not built, each refused before anything is launched, for either dtype: several new positions per row over pages (``extend``,
     ``prefill(chunk=)``, ``draft_and_verify`` and the speculative loop); e4m3 weights (``weights=``); the device-resident loop and graph
     capture (``DecodeLoop``); pages shared between rows (prefix sharing, copy-on-write); preemption or swapping of running rows."""
 
-    def __init__(self, model, batch, n_pages, max_len=None, free_order=None):
+    def __init__(self, model, batch, n_pages, max_len=None, free_order=None, dtype="bf16"):
+        if dtype not in ("bf16", "fp8"):
+            raise ValueError(f"PagedKVCache: dtype must be 'bf16' or 'fp8', got {dtype!r}")
         cfg = model.config
         if not cfg.autoregressive:
             raise ValueError("PagedKVCache: the model is not autoregressive (config.autoregressive): an encoder has no next token")
@@ -648,7 +654,9 @@ class PagedKVCache(PagedPositions):
         _require_hip(wte, "PagedKVCache")
         super().__init__(batch, n_pages, max_len, free_order, wte.device)
         hs = cfg.n_embd // cfg.n_head
-        self.layers = [ops.kv_paged_buffer(self.n_pages, cfg.n_head, hs, wte.device) for _ in model.transformer.h]
+        self.dtype = dtype
+        new = ops.kv8_paged_buffer if dtype == "fp8" else ops.kv_paged_buffer
+        self.layers = [new(self.n_pages, cfg.n_head, hs, wte.device) for _ in model.transformer.h]
         self.decode_ws = ops.block_decode_workspace(self.batch, cfg.n_embd, cfg.n_head, wte.device)
         self.extend_ws = None
 

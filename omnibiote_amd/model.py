@@ -1128,8 +1128,8 @@ class OmniBioTA(nn.Module):
 
         On a ``PagedKVCache``: ``rows`` is a host list of the cache rows the prompts go to, ``idx`` (len(rows), T0); the default is every
         row.  Only those rows are started over — each gets pages for its ``len_b`` positions unless it holds them — and the others keep
-        their state.  The same causal kernels run over the right-padded prompts (``ops.block_prefill_paged`` with the gathered table rows:
-        the padding beyond a row's own pages is not stored).  ``chunk=`` and ``weights=`` raise NotImplementedError there: several new
+        their state.  The same causal kernels run over the right-padded prompts (``ops.block_prefill_paged``, on an fp8 pool
+        ``ops.block_prefill_paged8``, with the gathered table rows: the padding beyond a row's own pages is not stored).  ``chunk=`` and ``weights=`` raise NotImplementedError there: several new
         positions per row over pages and e4m3 weights on pages are not built."""
         if isinstance(cache, PagedPositions):
             return self._prefill_paged(idx, cache, lengths, chunk, weights, rows)
@@ -1199,8 +1199,9 @@ class OmniBioTA(nn.Module):
         mask = ops.MaskSpec.from_user(_autoregressive_mask(True, None, b, t, idx.device), b, t, self.config.n_head, idx.device)
         x = ops.embedding_fwd(idx.contiguous(), wte)
         ws = ops.block_infer_workspace(b, t, self.config.n_embd, self.config.n_head, idx.device)
+        block_prefill = ops.block_prefill_paged8 if cache.dtype == "fp8" else ops.block_prefill_paged
         for block, pool in zip(self.transformer.h, cache.layers):
-            ops.block_prefill_paged(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, pool, cache.n_pages, table, ws=ws, out=x)
+            block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, pool, cache.n_pages, table, ws=ws, out=x)
         last = x[torch.arange(b, device=idx.device), torch.tensor(lens, device=idx.device) - 1]   # (B, C): row b at its own last position
         return self._readout_rows(self.transformer.ln_f(last.contiguous()))
 
@@ -1337,7 +1338,8 @@ class OmniBioTA(nn.Module):
         ``KVCache`` of either dtype, uniform or per-row positions; not on a ``SharedPrefixCache`` (NotImplementedError).
 
         On a ``PagedKVCache`` every active row whose position opens a new page first gets one from the free list — ValueError, before
-        anything is launched, if none is left — and the step reads and writes through the table (``ops.block_decode_paged``); ``weights=``
+        anything is launched, if none is left — and the step reads and writes through the table (``ops.block_decode_paged``, on an fp8
+        pool ``ops.block_decode_paged8``); ``weights=``
         raises NotImplementedError there."""
         if weights is not None:
             _refuse_weights("decode_step", weights if isinstance(cache, SharedPrefixCache) else None, "do not run on a shared-prefix cache (SharedPrefixCache)")
@@ -1365,13 +1367,14 @@ class OmniBioTA(nn.Module):
         step's op.  ``pos``: the position of every row, or with ``pos_rows`` (int32 (B,) on the device: rows mode, every row at its own
         position, read there) the host's bound on it.  A ``SharedPrefixCache`` — the group's prefix and the row's own slots, two buffers
         per layer — steps at suffix slot ``pos - n_prefix``, read through ``ancestry`` (beam search's table) when one is given; a
-        ``PagedKVCache`` through its page table; a ``KVCache`` on the e4m3 codes of ``weights``, else by its dtype, else by its mode.  The
+        ``PagedKVCache`` through its page table, by its dtype; a ``KVCache`` on the e4m3 codes of ``weights``, else by its dtype, else by its mode.  The
         cache is not advanced."""
         H = self.config.n_head
         for i, (block, kv) in enumerate(zip(self.transformer.h, cache.layers)):
             params, rope, to = self._block_params(block), block.attn.rope(), dict(ws=cache.decode_ws, out=x)
             if isinstance(cache, PagedPositions):                      # rows mode always: every row at its own position, its keys in its own pages
-                ops.block_decode_paged(x, params, rope, H, kv, cache.n_pages, cache.table, pos_rows, pos, **to)
+                step = ops.block_decode_paged8 if cache.dtype == "fp8" else ops.block_decode_paged
+                step(x, params, rope, H, kv, cache.n_pages, cache.table, pos_rows, pos, **to)
             elif isinstance(cache, SharedPrefixCache):
                 at = (kv[0], cache.prompts, cache.prefix_len, cache.n_prefix, kv[1], cache.max_new, pos - cache.n_prefix)
                 if ancestry is None:
@@ -1524,7 +1527,8 @@ class OmniBioTA(nn.Module):
         return torch.cat([rows, tokens], dim=1)
 
     @torch.no_grad()
-    def generate_many(self, prompts, max_new_tokens, batch, n_pages=None, temperature=1.0, top_k=None, top_p=None, eos_token=None, generator=None):
+    def generate_many(self, prompts, max_new_tokens, batch, n_pages=None, temperature=1.0, top_k=None, top_p=None, eos_token=None, generator=None,
+                      kv_dtype="bf16"):
         """Continuous batching: ``prompts``, a sequence of 1-D int64 tensors of any lengths, each continued by up to ``max_new_tokens``
         tokens, ``batch`` of them at a time on a ``PagedKVCache`` of ``n_pages`` pages.  Returns a list in the same order, each entry the
         prompt followed by its new tokens up to and including its first ``eos_token``, int64 on the model's device.  A row that ends —
@@ -1543,11 +1547,16 @@ class OmniBioTA(nn.Module):
         token against [k, r], wherever and whenever it runs; a greedy setting draws nothing.  With an ``eos_token`` the host reads the
         step's tokens once per step, as ``generate``'s loop does; without one it reads nothing until the end.
 
-        Not built: an e4m3 pool, speculative decoding, the device-resident loop and graph capture, pages shared between requests (a
+        ``kv_dtype``: "bf16" or "fp8", the ``PagedKVCache`` the call builds (``PagedKVCache``: the e4m3 pool, the same pages at about half
+        the bytes).  The schedule, the promise rule, the uniforms and the default ``n_pages`` do not depend on it.
+
+        Not built: speculative decoding, the device-resident loop and graph capture, pages shared between requests (a
         common prefix is stored once per request), preemption or swapping of running requests, penalties and token restrictions, the
         torch sampler."""
         from .paged import PagedSchedule
         self._check_generation("generate_many", 0)
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"OmniBioTA.generate_many: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         _check_top_p("OmniBioTA.generate_many", top_p)
         if temperature < 0:
             raise ValueError(f"OmniBioTA.generate_many: temperature must not be negative, got {temperature}")
@@ -1564,7 +1573,7 @@ class OmniBioTA(nn.Module):
         _require_hip(wte, "OmniBioTA")
         dev, R, steps, B = wte.device, len(prompts), sched.max_new, sched.batch
         prompts = [p.to(dev) for p in prompts]
-        cache = PagedKVCache(self, B, sched.n_pages, max(p.numel() for p in prompts) + steps)
+        cache = PagedKVCache(self, B, sched.n_pages, max(p.numel() for p in prompts) + steps, dtype=kv_dtype)
         greedy = top_k == 1 or temperature == 0
         # one column more than there are requests: what an idle slot draws against and writes to
         us = None if greedy else torch.cat([torch.rand((steps, R), device=dev, generator=generator), torch.zeros((steps, 1), device=dev)], dim=1)

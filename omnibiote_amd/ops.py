@@ -1647,12 +1647,15 @@ def kv_paged_buffer(n_pages, H, hs, device) -> torch.Tensor:
     return torch.empty(nbytes // 2, dtype=bf16, device=device)
 
 
-def _need_paged(pool, table, B, n_pages, H, hs):
-    """the pool and the (B, table_ld) int32 table of a paged call; returns table_ld"""
-    _need(pool, "pool"); _need(table, "table", torch.int32)
+def _need_paged(pool, table, B, n_pages, H, hs, e4m3=False):
+    """the pool (bf16; e4m3: the uint8 pool of include/omnibiote_hip_paged8.h) and the (B, table_ld) int32 table of a paged call; returns table_ld"""
+    _need(pool, "pool", torch.uint8 if e4m3 else bf16); _need(table, "table", torch.int32)
     if table.dim() != 2 or table.shape[0] != B:
         raise ValueError(f"table: expected shape ({B}, table_ld), got {tuple(table.shape)}")
-    assert pool.numel() * 2 == L.lib().obte_kv_paged_bytes(n_pages, H, hs)
+    if e4m3:
+        assert pool.numel() == L.lib().obte_kv8_paged_bytes(n_pages, H, hs)
+    else:
+        assert pool.numel() * 2 == L.lib().obte_kv_paged_bytes(n_pages, H, hs)
     return table.shape[1]
 
 
@@ -1715,6 +1718,77 @@ def block_decode_paged(x, params, rope, H, pool, n_pages, table, pos, max_pos, w
     return _block_call(x, params, rope, H, ws, out, _decode_ws, lambda d, y, w: L.check(
         L.lib().obte_block_decode_paged(d, _ptr(x), _ptr(y), _ptr(pool), n_pages, _ptr(table), ld, _ptr(pos), int(max_pos), _ptr(w), w.numel(), _stream()),
         "obte_block_decode_paged"), rows=(pos, "pos"), at=max_pos, one=True)
+
+
+# ---- the pages as OCP e4m3 (include/omnibiote_hip_paged8.h; the format in plain torch: paged.py, the quantiser: kvquant.py) ----
+def kv8_paged_buffer(n_pages, H, hs, device) -> torch.Tensor:
+    """One layer's e4m3 pool of ``n_pages`` pages (K codes [n_pages, H, 64, hs], V codes, K scales fp32 [n_pages, H, 64], V scales) as the
+    flat uint8 tensor the entry points take: 2 (hs + 4) bytes per cached head vector against the bf16 pool's 4 hs."""
+    nbytes = int(L.lib().obte_kv8_paged_bytes(n_pages, H, hs))
+    if nbytes <= 0:
+        raise RuntimeError(f"kv8_paged_buffer: unsupported shape (n_pages {n_pages}, n_head {H}, head size {hs}): head size 64 or 128")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def kv8_paged_store(qkv, B, t, H, hs, pool, n_pages, table):
+    """kv_paged_store into an e4m3 pool (obte_kv8_paged_store): the k and v thirds of the packed, rotated qkv [B*t, 3C], quantised per head
+    vector as kv8_cache_store quantises them, into positions [0, t) of each row through the page table; a position without a page is skipped."""
+    _need(qkv, "qkv")
+    ld = _need_paged(pool, table, B, n_pages, H, hs, e4m3=True)
+    assert qkv.numel() == B * t * 3 * H * hs and t <= KV_PAGE * ld
+    L.check(L.lib().obte_kv8_paged_store(_ptr(qkv), B, t, H, hs, _ptr(pool), n_pages, _ptr(table), ld, _stream()), "obte_kv8_paged_store")
+    return pool
+
+
+def kv8_paged_rope_store_rows(qkv, rope, pos, max_pos, B, H, hs, pool, n_pages, table):
+    """kv_paged_rope_store_rows into an e4m3 pool (obte_kv8_paged_rope_store_rows): qkv is left with the same bits, kv8_cache_rope_store_rows's
+    codes and scales go to slot pos[b] % 64 of page table[b, pos[b] // 64] — or nowhere, if that is no page of the pool."""
+    _need(qkv, "qkv"); _need_rows(pos, "pos", B)
+    ld = _need_paged(pool, table, B, n_pages, H, hs, e4m3=True)
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert qkv.numel() == B * 3 * H * hs and max_pos < KV_PAGE * ld
+    assert rope[0].shape[0] > max_pos and rope[1].shape[0] > max_pos
+    L.check(L.lib().obte_kv8_paged_rope_store_rows(_ptr(qkv), _ptr(rope[0]), _ptr(rope[1]), _ptr(pos), int(max_pos), B, H, hs, _ptr(pool), n_pages, _ptr(table),
+                                                   ld, _stream()), "obte_kv8_paged_rope_store_rows")
+    return qkv
+
+
+def attn_decode_paged8(q, pool, n_pages, table, B, n_keys, max_keys, H, hs, scale, splits=0, q_ld=None, ws=None, out=None, lse=None):
+    """attn_decode_paged over an e4m3 pool (obte_attn_decode_paged8): bit for bit attn_decode_kv8(n_keys_rows=) on a rectangular e4m3 cache
+    holding the same codes and scales.  q_ld, ws, out and lse as in attn_decode_kv8.  Returns (o, lse)."""
+    _need(q, "q", contiguous=False); _need_rows(n_keys, "n_keys", B)
+    ld = _need_paged(pool, table, B, n_pages, H, hs, e4m3=True)
+    q_ld = q.shape[-1] if q_ld is None else q_ld
+    assert (not q.is_contiguous() or q.numel() >= (B - 1) * q_ld + H * hs) and max_keys <= KV_PAGE * ld
+    o = torch.empty((B, H * hs), dtype=bf16, device=q.device) if out is None else out
+    lse = torch.empty((B, H), dtype=torch.float32, device=q.device) if lse is None else lse
+    if ws is None:
+        ws = torch.empty(int(L.lib().obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=q.device)
+    L.check(L.lib().obte_attn_decode_paged8(_ptr(q), q_ld, _ptr(pool), n_pages, _ptr(table), ld, _ptr(o), _ptr(lse), B, _ptr(n_keys), int(max_keys), H, hs,
+                                            float(scale), int(splits), _ptr(ws), ws.numel(), _stream()), "obte_attn_decode_paged8")
+    return o, lse
+
+
+def block_prefill_paged8(x, params, rope, H, mask: MaskSpec, pool, n_pages, table, ws=None, out=None):
+    """block_prefill_paged into an e4m3 pool (obte_block_fwd_prefill_paged8): y bit for bit block_infer's, the rotated keys and the values
+    quantised into the pages of table row b."""
+    B, T, Cc = x.shape
+    ld = _need_paged(pool, table, B, n_pages, H, Cc // H, e4m3=True)
+    assert T <= KV_PAGE * ld
+    return _block_call(x, params, rope, H, ws, out, block_infer_workspace, lambda d, y, w: L.check(
+        L.lib().obte_block_fwd_prefill_paged8(d, _ptr(x), _ptr(y), _ptr(w), w.numel(), _ptr(pool), n_pages, _ptr(table), ld, _stream()),
+        "obte_block_fwd_prefill_paged8"), mask)
+
+
+def block_decode_paged8(x, params, rope, H, pool, n_pages, table, pos, max_pos, ws=None, out=None):
+    """block_decode_paged on an e4m3 pool (obte_block_decode_paged8): y bit for bit block_decode_kv8's rows form on a rectangular e4m3 cache
+    holding the same vectors.  The workspace is block_decode's.  rope: the FULL tables.  out may be x itself."""
+    B, Cc = x.shape
+    ld = _need_paged(pool, table, B, n_pages, H, Cc // H, e4m3=True)
+    assert max_pos < KV_PAGE * ld
+    return _block_call(x, params, rope, H, ws, out, _decode_ws, lambda d, y, w: L.check(
+        L.lib().obte_block_decode_paged8(d, _ptr(x), _ptr(y), _ptr(pool), n_pages, _ptr(table), ld, _ptr(pos), int(max_pos), _ptr(w), w.numel(), _stream()),
+        "obte_block_decode_paged8"), rows=(pos, "pos"), at=max_pos, one=True)
 
 
 def block_bwd(x, dy, act, params, rope, H, mask: MaskSpec, accumulate_into=None, dropout_p=0.0, dropout_seed=0, ln_partials=None,

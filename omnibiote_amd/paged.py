@@ -6,7 +6,11 @@ kernel is called here and nothing needs a GPU; ``generation.PagedKVCache`` adds 
 
 One layer's pool: K bf16 [n_pages, H, 64, hs], V behind it in the same shape.  The table: int32 [rows, table_ld], entry j of row b the
 page that holds positions [64 j, 64 j + 64) of that row; an entry outside [0, n_pages) means no page: nothing is stored there, and its
-keys are not there."""
+keys are not there.
+
+The e4m3 pool (include/omnibiote_hip_paged8.h): K codes uint8 [n_pages, H, 64, hs], V codes, K scales fp32 [n_pages, H, 64], V scales, under
+the same table; a head vector is quantised as ``kvquant.quantize_reference`` quantises it (``paged8_gather_reference``,
+``paged8_scatter_reference``)."""
 from __future__ import annotations
 
 import torch
@@ -57,6 +61,61 @@ def paged_scatter_reference(K, V, table, n_pages, fill=float("nan")):
     src = torch.stack([K, V]).view(2, B, H, T // KV_PAGE, KV_PAGE, hs).permute(0, 1, 3, 2, 4, 5)   # [2, B, ld, H, 64, hs]
     pool[:, t[there]] = src[:, there]
     return pool.view(-1)
+
+
+def pool8_bytes(n_pages, H, hs) -> int:
+    """obte_kv8_paged_bytes for a supported shape"""
+    return 2 * n_pages * H * KV_PAGE * (hs + 4)
+
+
+def _pool8_views(pool, n_pages, H, hs):
+    """the codes [2, n_pages, H, 64, hs] (uint8) and the scales [2, n_pages, H, 64] (fp32) of one layer's flat uint8 e4m3 pool, as views"""
+    n_codes = 2 * n_pages * H * KV_PAGE * hs
+    return pool[:n_codes].view(2, n_pages, H, KV_PAGE, hs), pool[n_codes:].view(torch.float32).view(2, n_pages, H, KV_PAGE)
+
+
+def paged8_gather_reference(pool, table, n_pages, H, hs, T=None, fill_code=0, fill_scale=0.0):
+    """The rectangular codes and scales an e4m3 pool and a table stand for: (codes, scales), uint8 [2, B, H, T, hs] and fp32 [2, B, H, T]
+    (index 0: K, 1: V; what the four regions of ``kvquant``'s rectangular cache hold), T = 64 * table_ld unless given (then the first T
+    positions).  ``pool``: one layer's flat uint8 buffer; ``table``: int32 [B, table_ld] on any device.  The positions of an entry outside
+    [0, n_pages) hold ``fill_code`` and ``fill_scale``.  Ordinary torch indexing, bit for bit a copy."""
+    if pool.dtype != torch.uint8 or pool.numel() != pool8_bytes(n_pages, H, hs):
+        raise ValueError(f"paged8_gather_reference: the pool must be {pool8_bytes(n_pages, H, hs)} uint8 values, got {pool.numel()} {pool.dtype}")
+    if table.dim() != 2:
+        raise ValueError(f"paged8_gather_reference: the table must be (rows, table_ld), got {tuple(table.shape)}")
+    B, ld = table.shape
+    codes, scales = _pool8_views(pool, n_pages, H, hs)
+    t = table.to(device=pool.device, dtype=torch.int64)
+    there = (t >= 0) & (t < n_pages)
+    at = torch.where(there, t, torch.zeros_like(t))
+    c = codes[:, at]                                                    # [2, B, ld, H, 64, hs]
+    c = torch.where(there.view(1, B, ld, 1, 1, 1), c, torch.full_like(c, fill_code))
+    s = scales[:, at]                                                   # [2, B, ld, H, 64]
+    s = torch.where(there.view(1, B, ld, 1, 1), s, torch.full_like(s, fill_scale))
+    c = c.permute(0, 1, 3, 2, 4, 5).reshape(2, B, H, ld * KV_PAGE, hs)
+    s = s.permute(0, 1, 3, 2, 4).reshape(2, B, H, ld * KV_PAGE)
+    if T is not None:
+        c, s = c[:, :, :, :T], s[:, :, :, :T]
+    return c.contiguous(), s.contiguous()
+
+
+def paged8_scatter_reference(codes, scales, table, n_pages, fill_code=0x7F, fill_scale=float("nan")):
+    """The inverse, for building a test's pool: codes uint8 [2, B, H, T, hs] and scales fp32 [2, B, H, T] with T a multiple of 64 -> the
+    flat uint8 pool in which page table[b][j] holds positions [64 j, 64 j + 64) of row b, and every page no entry names holds the NaN
+    code ``fill_code`` and ``fill_scale``."""
+    two, B, H, T, hs = codes.shape
+    if two != 2 or scales.shape != (2, B, H, T) or codes.dtype != torch.uint8 or scales.dtype != torch.float32:
+        raise ValueError(f"paged8_scatter_reference: codes uint8 [2, B, H, T, hs] and scales fp32 [2, B, H, T], got {tuple(codes.shape)} and {tuple(scales.shape)}")
+    if T % KV_PAGE != 0 or table.shape != (B, T // KV_PAGE):
+        raise ValueError(f"paged8_scatter_reference: T = {T} must be a multiple of 64 and the table ({B}, {T // KV_PAGE}), got {tuple(table.shape)}")
+    pool = torch.empty(pool8_bytes(n_pages, H, hs), dtype=torch.uint8, device=codes.device)
+    pc, ps = _pool8_views(pool, n_pages, H, hs)
+    pc.fill_(fill_code); ps.fill_(fill_scale)
+    t = table.to(device=codes.device, dtype=torch.int64)
+    there = (t >= 0) & (t < n_pages)
+    pc[:, t[there]] = codes.view(2, B, H, T // KV_PAGE, KV_PAGE, hs).permute(0, 1, 3, 2, 4, 5)[:, there]   # from [2, B, ld, H, 64, hs]
+    ps[:, t[there]] = scales.view(2, B, H, T // KV_PAGE, KV_PAGE).permute(0, 1, 3, 2, 4)[:, there]         # from [2, B, ld, H, 64]
+    return pool
 
 
 class PageBook:

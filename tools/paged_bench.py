@@ -16,7 +16,14 @@ warm-up; median and [min - max] over the rounds.  One JSON line per measurement.
               where every draw meets the eos_token with a probability near 1 / vocab and the rows end at spread-out times.  Also with a
               pool of --pool-share (default 0.65) of the default page count.
 
-    python tools/paged_bench.py [--parts attention,step,workload] [--rounds 5] [--steps 200]
+  --kv8       the e4m3 pool (include/omnibiote_hip_paged8.h) in the same three parts, under the same protocol:
+              attention   obte_attn_decode_paged8 (pages in random order, and in row order) against obte_attn_decode_kv8's rows form on a
+                          rectangle holding the same codes and scales, and in the same process the bf16 pair above and paged e4m3 against
+                          paged bf16 (the byte ratio is (hs + 4) / (2 hs) = 0.516);
+              step        decode_step on PagedKVCache(dtype="fp8") against KVCache(dtype="fp8") in rows mode and against the bf16 pool;
+              workload    the same prompts also through generate_many(kv_dtype="fp8") at the default page count.
+
+    python tools/paged_bench.py [--kv8] [--parts attention,step,workload] [--rounds 5] [--steps 200]
 """
 import argparse
 import contextlib
@@ -98,6 +105,124 @@ def attention(m, B, ctx, rounds, steps, dev):
             "in_order_minus_rows_us_and_spreads": _gap(us, "paged_pages_in_order", "rows")}
 
 
+def attention8(m, B, ctx, rounds, steps, dev):
+    """--kv8: the four one-query calls over the same keys' worth of positions, alternating in one process"""
+    from omnibiote_amd import _lib, ops
+    from omnibiote_amd.kvquant import split_cache
+    from omnibiote_amd.paged import paged8_scatter_reference, paged_scatter_reference
+    lib = _lib.lib()
+    H, C = m.config.n_head, m.config.n_embd
+    hs, n_layer, n_pages, ld = C // H, m.config.n_layer, B * ctx // 64, ctx // 64
+    gen = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    table = torch.randperm(n_pages, device=dev, generator=gen).view(B, ld).to(torch.int32)
+    ordered = torch.arange(n_pages, device=dev, dtype=torch.int32).view(B, ld)
+    rects, pools, rects8, pools8, pools8_ordered = [], [], [], [], []
+    for _ in range(n_layer):
+        rect = ops.kv_cache_buffer(B, ctx, H, hs, dev).normal_(generator=gen)
+        K, V = rect.view(2, B, H, ctx, hs)
+        rects.append(rect)
+        pools.append(paged_scatter_reference(K, V, table, n_pages))
+        rect8 = ops.kv8_cache_buffer(B, ctx, H, hs, dev)
+        kc, vc, ks, vs = split_cache(rect8, B, ctx, H, hs)
+        kc.random_(0, 0x7F, generator=gen); vc.random_(0, 0x7F, generator=gen)          # finite codes, scales of the keys' size: only the time is read
+        ks.fill_(2.0 ** -7); vs.fill_(2.0 ** -7)
+        codes, scales = torch.stack([kc, vc]), torch.stack([ks, vs])
+        rects8.append(rect8)
+        pools8.append(paged8_scatter_reference(codes, scales, table, n_pages))
+        pools8_ordered.append(paged8_scatter_reference(codes, scales, ordered, n_pages))
+        del codes, scales
+    q = torch.randn(B, 3 * C, device=dev, generator=gen).to(torch.bfloat16)
+    counts = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.obte_attn_decode_ws_bytes(B, H, hs)), dtype=torch.uint8, device=dev)
+    o = torch.empty(B, C, device=dev, dtype=torch.bfloat16)
+    lse = torch.empty(B, H, device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream().cuda_stream
+    state = {"i": 0}
+
+    def call(name, *args):
+        rc = getattr(lib, name)(*args)
+        if rc != 0:
+            _lib.check(rc, name)
+
+    def nxt(bufs):
+        state["i"] += 1
+        return bufs[state["i"] % n_layer].data_ptr()
+    tail = (H, hs, 8.0 / C, 0, ws.data_ptr(), ws.numel(), stream)
+    legs = {
+        "rows": lambda: call("obte_attn_decode_rows", q.data_ptr(), 3 * C, nxt(rects), o.data_ptr(), lse.data_ptr(), B, ctx, counts.data_ptr(), ctx, *tail),
+        "paged": lambda: call("obte_attn_decode_paged", q.data_ptr(), 3 * C, nxt(pools), n_pages, table.data_ptr(), ld, o.data_ptr(), lse.data_ptr(), B, counts.data_ptr(),
+                              ctx, *tail),
+        "kv8_rows": lambda: call("obte_attn_decode_kv8", q.data_ptr(), 3 * C, nxt(rects8), o.data_ptr(), lse.data_ptr(), B, ctx, ctx, counts.data_ptr(), *tail),
+        "paged8": lambda: call("obte_attn_decode_paged8", q.data_ptr(), 3 * C, nxt(pools8), n_pages, table.data_ptr(), ld, o.data_ptr(), lse.data_ptr(), B,
+                               counts.data_ptr(), ctx, *tail),
+        "paged8_pages_in_order": lambda: call("obte_attn_decode_paged8", q.data_ptr(), 3 * C, nxt(pools8_ordered), n_pages, ordered.data_ptr(), ld, o.data_ptr(),
+                                              lse.data_ptr(), B, counts.data_ptr(), ctx, *tail),
+    }
+    a, _ = ops.attn_decode_kv8(q, rects8[0], B, ctx, ctx, H, hs, 8.0 / C, n_keys_rows=counts)
+    b, _ = ops.attn_decode_paged8(q, pools8[0], n_pages, table, B, counts, ctx, H, hs, 8.0 / C)
+    for fn in legs.values():
+        for _ in range(8):
+            fn()
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for k in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            us[k].append(timed(legs[k], steps))
+    nbytes = {"rows": 4 * B * H * ctx * hs, "kv8_rows": 2 * B * H * ctx * (hs + 4)}
+    nbytes["paged"], nbytes["paged8"], nbytes["paged8_pages_in_order"] = nbytes["rows"], nbytes["kv8_rows"], nbytes["kv8_rows"]
+    set8 = sum(t.numel() for t in rects8)
+    med = {k: statistics.median(v) for k, v in us.items()}
+    return {"part": "attention", "kv8": True, "B": B, "context": ctx, "windows": {"calls": steps, "rounds": rounds}, "same_bits": bool(torch.equal(a, b)),
+            "splits": int(lib.obte_attn_decode_splits(B, H, hs, ctx)), "bytes_per_call": nbytes, "table_bytes_per_call": 4 * B * ld,
+            "set_bytes": {"bf16": sum(t.numel() * 2 for t in rects), "e4m3": set8},
+            "served_from": {"bf16": "HBM" if sum(t.numel() * 2 for t in rects) > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)",
+                            "e4m3": "HBM" if set8 > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)"},
+            "us": {k: summary(v) for k, v in us.items()}, "share_of_6.3TBps": {k: round(nbytes[k] / (med[k] * 1e-6) / HBM_RATE, 3) for k in legs},
+            "paged8_over_kv8_rows": round(med["paged8"] / med["kv8_rows"], 4), "paged8_minus_kv8_rows_us_and_spreads": _gap(us, "paged8", "kv8_rows"),
+            "in_order_minus_kv8_rows_us_and_spreads": _gap(us, "paged8_pages_in_order", "kv8_rows"),
+            "paged_over_rows": round(med["paged"] / med["rows"], 4), "paged_minus_rows_us_and_spreads": _gap(us, "paged", "rows"),
+            "paged8_over_paged": round(med["paged8"] / med["paged"], 3), "kv8_rows_over_rows": round(med["kv8_rows"] / med["rows"], 3),
+            "byte_ratio": round((hs + 4) / (2 * hs), 3)}
+
+
+def step8(m, B, ctx, rounds, steps, dev):
+    """--kv8: decode_step on the e4m3 pool, on the e4m3 rectangle in rows mode and on the bf16 pool, every window walking the same positions"""
+    from omnibiote_amd.model import KVCache, PagedKVCache
+    first = ctx - 1 - steps
+    gen = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
+    last = torch.randint(4, m.config.vocab_size, (B,), device=dev, generator=gen)
+    order = torch.randperm(B * ctx // 64, generator=torch.Generator().manual_seed(1)).tolist()
+    rect8 = KVCache(m, B, ctx, dtype="fp8")
+    caches = {"paged": PagedKVCache(m, B, B * ctx // 64, ctx, free_order=order), "paged8": PagedKVCache(m, B, B * ctx // 64, ctx, free_order=order, dtype="fp8")}
+    for kv in caches["paged"].layers:
+        kv.normal_(generator=gen)
+    for kv in rect8.layers + caches["paged8"].layers:                   # every code 1.0 and every scale the fp32 of the same bytes, 4.4e-5: finite
+        kv.fill_(0x38)
+    for c in caches.values():
+        for b in range(B):
+            c.assign(b, ctx)
+
+    def window(kind):
+        if kind == "kv8_rows":
+            rect8.reset(first, torch.full((B,), first, dtype=torch.int32, device=dev), first)
+            cache = rect8
+        else:
+            cache = caches[kind]
+            cache.start_rows(range(B), [first] * B)
+        return timed(lambda: m.decode_step(last, cache), steps)
+    legs = ("kv8_rows", "paged8", "paged")
+    for k in legs:
+        window(k)
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for k in (legs if r % 2 == 0 else legs[::-1]):
+            us[k].append(window(k))
+    med = {k: statistics.median(v) for k, v in us.items()}
+    return {"part": "step", "kv8": True, "B": B, "context": ctx, "windows": {"decode_steps": steps, "rounds": rounds, "positions": [first, ctx - 2]},
+            "us_per_token": {k: summary(v, 1) for k, v in us.items()}, "paged8_over_kv8_rows": round(med["paged8"] / med["kv8_rows"], 3),
+            "paged8_minus_kv8_rows_us_and_spreads": _gap(us, "paged8", "kv8_rows", 1), "paged8_over_paged": round(med["paged8"] / med["paged"], 3),
+            "tokens_per_s": {k: round(B / med[k] * 1e6) for k in legs}}
+
+
 def step(m, B, ctx, rounds, steps, dev):
     from omnibiote_amd.model import KVCache, PagedKVCache
     first = ctx - 1 - steps
@@ -150,9 +275,9 @@ def build_small_vocab(block_size, vocab, dev):
     return m.to(dev).eval()
 
 
-def workload(n_prompts, vocab, pool_share, rounds, dev):
+def workload(n_prompts, vocab, pool_share, rounds, dev, kv8=False):
     from omnibiote_amd import _lib
-    from omnibiote_amd.paged import PagedSchedule, pool_bytes
+    from omnibiote_amd.paged import PagedSchedule, pool8_bytes, pool_bytes
     new, batch, eos = 256, 64, 7
     m = build_small_vocab(1024 + new, vocab, dev)
     cfg = m.config
@@ -170,9 +295,9 @@ def workload(n_prompts, vocab, pool_share, rounds, dev):
         return plain_step(*a, **k)
     m.decode_step = counted
 
-    def many(n_pages):
+    def many(n_pages, kv_dtype="bf16"):
         def run():
-            out = m.generate_many(prompts, new, batch, n_pages=n_pages, eos_token=eos, generator=torch.Generator(device=dev).manual_seed(3))
+            out = m.generate_many(prompts, new, batch, n_pages=n_pages, eos_token=eos, generator=torch.Generator(device=dev).manual_seed(3), kv_dtype=kv_dtype)
             return [o.numel() - n for o, n in zip(out, lens)], None
         return run
 
@@ -186,6 +311,9 @@ def workload(n_prompts, vocab, pool_share, rounds, dev):
             peak = max(peak, cfg.n_layer * int(_lib.lib().obte_kv_cache_bytes(len(part), max(ln) + new, H, hs)))
         return made, peak
     legs = {"generate_batches": batched, **{k: many(v) for k, v in pools.items()}}
+    if kv8:                                                             # the same page count at about half the bytes
+        pools["generate_many_fp8"] = default_pages
+        legs["generate_many_fp8"] = many(default_pages, "fp8")
     res = {k: {"tokens_per_s": [], "wall_s": []} for k in legs}
     for r in range(rounds + 1):                                         # (round 0 warms up)
         for k in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
@@ -198,7 +326,7 @@ def workload(n_prompts, vocab, pool_share, rounds, dev):
             if r == 0:
                 res[k].update(new_tokens=sum(made), rows_ended_by_eos=sum(1 for n in made if n < new), decode_steps=calls["n"],
                               share_of_row_steps_on_finished_rows=round(1 - sum(n - 1 for n in made) / max(calls["n"] * batch, 1), 3),
-                              peak_cache_bytes=peak if peak is not None else cfg.n_layer * pool_bytes(pools[k], H, hs))
+                              peak_cache_bytes=peak if peak is not None else cfg.n_layer * (pool8_bytes if k.endswith("_fp8") else pool_bytes)(pools[k], H, hs))
                 continue
             res[k]["tokens_per_s"].append(sum(made) / wall)
             res[k]["wall_s"].append(wall)
@@ -218,6 +346,7 @@ def main():
     p.add_argument("--prompts", type=int, default=256)
     p.add_argument("--vocab", type=int, default=256)
     p.add_argument("--pool-share", type=float, default=0.65)
+    p.add_argument("--kv8", action="store_true", help="the e4m3 pool: see the head of this file")
     a = p.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -226,15 +355,15 @@ def main():
         m = build(2048, dev)
         for B, ctx in ((64, 2048), (8, 2048)):
             if "attention" in parts:
-                print(json.dumps(attention(m, B, ctx, a.rounds, a.steps, dev)), flush=True)
+                print(json.dumps((attention8 if a.kv8 else attention)(m, B, ctx, a.rounds, a.steps, dev)), flush=True)
                 torch.cuda.empty_cache()
             if "step" in parts:
-                print(json.dumps(step(m, B, ctx, a.rounds, a.steps, dev)), flush=True)
+                print(json.dumps((step8 if a.kv8 else step)(m, B, ctx, a.rounds, a.steps, dev)), flush=True)
                 torch.cuda.empty_cache()
         del m
         torch.cuda.empty_cache()
     if "workload" in parts:
-        print(json.dumps(workload(a.prompts, a.vocab, a.pool_share, a.rounds, dev)), flush=True)
+        print(json.dumps(workload(a.prompts, a.vocab, a.pool_share, a.rounds, dev, a.kv8)), flush=True)
 
 
 if __name__ == "__main__":
