@@ -250,6 +250,13 @@ SYMBOLS_W8 = {
                                      C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
 }
 
+# the decode step's weights stored as OCP MXFP4 (include/omnibiote_hip_w4.h): a table of its own as well
+SYMBOLS_W4 = {
+    "obte_linear_small_m_w4": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
+    "obte_block_step_w4": (C.c_int, [C.POINTER(BlockDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
+}
+
 # sequence scoring, the readout fused with its log-softmax (include/omnibiote_hip_score.h): a table of its own as well
 READOUT_SCORE_MAX_SLICES, READOUT_SCORE_MAX_K = 64, 64
 SYMBOLS_SCORE = {
@@ -363,7 +370,7 @@ def lib():
                                             + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
                                             + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items()) + list(SYMBOLS_PENALTY.items())
                                             + list(SYMBOLS_DISTILL.items()) + list(SYMBOLS_BEAM.items()) + list(SYMBOLS_PAGED.items())
-                                            + list(SYMBOLS_PAGED8.items())):
+                                            + list(SYMBOLS_PAGED8.items()) + list(SYMBOLS_W4.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

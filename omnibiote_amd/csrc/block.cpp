@@ -498,9 +498,11 @@ struct InferAttention {
     // a prefix shared by groups of rows (obte_block_decode_shared, include/omnibiote_hip_shared.h): the prefix cache of P rows holding n_prefix
     // positions; kv_cache / T_max / pos are then the SUFFIX cache of B rows, its slots and the step's slot (decode, uniform)
     const obte_bf16* prefix_cache = nullptr; int64_t P = 0, T_pre = 0, n_prefix = 0;
-    // the four weights as e4m3 codes and row scales (obte_block_step_w8, include/omnibiote_hip_w8.h), in the order of the products below; null:
-    // bf16 from the descriptor, which holds the dequantised weights either way
-    const void* const* w8_codes = nullptr; const float* const* w8_scales = nullptr;
+    // the four weights as codes and scales, in the order of the products below, in the format w_format names: W_E4M3 (obte_block_step_w8,
+    // include/omnibiote_hip_w8.h: fp32 row scales) or W_MXFP4 (obte_block_step_w4, include/omnibiote_hip_w4.h: e8m0 block scales); W_BF16: bf16
+    // from the descriptor, which holds the dequantised weights either way
+    enum WFormat { W_BF16, W_E4M3, W_MXFP4 };
+    WFormat w_format = W_BF16; const void* const* w_codes = nullptr; const void* const* w_scales = nullptr;
     // with prefix_cache: suffix slot j of row b is read from the group's row ancestry[b][j] (obte_block_decode_beam, include/omnibiote_hip_beam.h)
     const int32_t* ancestry = nullptr;
     // the cache in pages (include/omnibiote_hip_paged.h): kv_cache is the layer's pool of n_pages pages and page_table [B, table_ld] says where
@@ -516,7 +518,11 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
     const bool stream_w = at.n_new > 0 && M <= obte_small_m_max();
     auto run = [stream_w, &at](const obte_gemm_args& g, int which, obte_stream st) {
         if (!stream_w) return obte_gemm_bf16_ws(&g, nullptr, 0, st);
-        return at.w8_codes ? obte_linear_small_m_w8(&g, at.w8_codes[which], g.K, at.w8_scales[which], st) : obte_linear_small_m_bf16(&g, st);
+        switch (at.w_format) {
+            case InferAttention::W_E4M3: return obte_linear_small_m_w8(&g, at.w_codes[which], g.K, (const float*)at.w_scales[which], st);
+            case InferAttention::W_MXFP4: return obte_linear_small_m_w4(&g, at.w_codes[which], g.K / 2, at.w_scales[which], g.K / 32, st);
+            default: return obte_linear_small_m_bf16(&g, st);
+        }
     };
     TRY(obte_layernorm_fwd(x, d->ln1_w, w.h1, w.mean, w.rstd, M, C, 1e-5f, s));
     obte_gemm_args qkv = xWt(w.h1, d->attn_w, w.qkv, M, 3 * C, C);
@@ -627,7 +633,7 @@ namespace {
 // obte_attn_decode / _rows and their workspace behind InferLayout) instead of obte_attn_extend's.
 int cached_step(const char* who, const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, int64_t pos,
                 const int32_t* pos_rows, bool rows, bool decode, void* ws, int64_t ws_bytes, obte_stream s, bool kv8 = false,
-                const void* const* w8_codes = nullptr, const float* const* w8_scales = nullptr, const int32_t* page_table = nullptr, int64_t n_pages = 0) {   // (paged: T_max is 64 table_ld)
+                InferAttention::WFormat w_format = InferAttention::W_BF16, const void* const* w_codes = nullptr, const void* const* w_scales = nullptr, const int32_t* page_table = nullptr, int64_t n_pages = 0) {   // (paged: T_max is 64 table_ld)
     TRY(check_desc(who, d));
     OBTE_REQUIRE(!decode || d->T == 1, "%s: one new position per row (T = 1), got T = %lld", who, (long long)d->T);
     if (d->key_ranges || d->mask || d->query_bounds || d->out_rows || d->dropout_p > 0.f) {
@@ -656,7 +662,7 @@ int cached_step(const char* who, const obte_block_desc* d, const obte_bf16* x, o
     OBTE_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes, obte_block_%s_ws_bytes() asks for %lld", who, (long long)ws_bytes, decode ? "decode" : "extend",
                  (long long)need);
     InferAttention at = {kv_cache, T_max, pos, (char*)ws + w.total, att_bytes, rows ? pos_rows : nullptr, n, decode, kv8, who};
-    at.w8_codes = w8_codes; at.w8_scales = w8_scales;
+    at.w_format = w_format; at.w_codes = w_codes; at.w_scales = w_scales;
     at.page_table = page_table; at.n_pages = n_pages; at.table_ld = T_max / OBTE_KV_PAGE;
     // uniform: c_attn rotates row b n + j by the tables' row pos + j (rope_T = n on the tables advanced by pos rows); rows form: the FULL tables
     const int64_t row = at.pos_rows ? 0 : pos * (hs / 2);
@@ -687,7 +693,7 @@ extern "C" int obte_block_decode_paged(const obte_block_desc* d, const obte_bf16
     const char* who = "obte_block_decode_paged";
     OBTE_REQUIRE(pool && table, "%s: null pointer", who);
     OBTE_REQUIRE(n_pages > 0 && table_ld > 0 && table_ld < (1ll << 18), "%s: bad shape (n_pages and table_ld at least 1)", who);
-    return cached_step(who, d, x, y_out, pool, OBTE_KV_PAGE * table_ld, max_pos, pos, true, true, ws, ws_bytes, s, false, nullptr, nullptr, table, n_pages);
+    return cached_step(who, d, x, y_out, pool, OBTE_KV_PAGE * table_ld, max_pos, pos, true, true, ws, ws_bytes, s, false, InferAttention::W_BF16, nullptr, nullptr, table, n_pages);
 }
 
 // the same on the pages of an e4m3 pool (include/omnibiote_hip_paged8.h)
@@ -696,7 +702,7 @@ extern "C" int obte_block_decode_paged8(const obte_block_desc* d, const obte_bf1
     const char* who = "obte_block_decode_paged8";
     OBTE_REQUIRE(pool8 && table, "%s: null pointer", who);
     OBTE_REQUIRE(n_pages > 0 && n_pages < (1ll << 24) && table_ld > 0 && table_ld < (1ll << 18), "%s: bad shape (n_pages in [1, 2^24), table_ld at least 1)", who);
-    return cached_step(who, d, x, y_out, (obte_bf16*)pool8, OBTE_KV_PAGE * table_ld, max_pos, pos, true, true, ws, ws_bytes, s, true, nullptr, nullptr, table, n_pages);
+    return cached_step(who, d, x, y_out, (obte_bf16*)pool8, OBTE_KV_PAGE * table_ld, max_pos, pos, true, true, ws, ws_bytes, s, true, InferAttention::W_BF16, nullptr, nullptr, table, n_pages);
 }
 
 // the two on the e4m3 cache (include/omnibiote_hip_kv8.h): pos_rows null or not
@@ -714,7 +720,21 @@ extern "C" int obte_block_step_w8(const obte_block_desc* d, const void* const* c
         OBTE_REQUIRE(codes[i] && scales[i], "%s: null pointer (codes[%d] / scales[%d])", who, i, i);
         OBTE_REQUIRE(((uintptr_t)codes[i] & 15) == 0 && ((uintptr_t)scales[i] & 3) == 0, "%s: codes[%d] must be 16-byte aligned, scales[%d] 4-byte aligned", who, i, i);
     }
-    return cached_step(who, d, x, y_out, (obte_bf16*)cache, T_max, pos, pos_rows, pos_rows != nullptr, true, ws, ws_bytes, s, cache_e4m3 != 0, codes, scales);
+    return cached_step(who, d, x, y_out, (obte_bf16*)cache, T_max, pos, pos_rows, pos_rows != nullptr, true, ws, ws_bytes, s, cache_e4m3 != 0, InferAttention::W_E4M3, codes,
+                       (const void* const*)scales);
+}
+
+// the same with the weights in MXFP4 (include/omnibiote_hip_w4.h)
+extern "C" int obte_block_step_w4(const obte_block_desc* d, const void* const* codes, const void* const* scales, const obte_bf16* x, obte_bf16* y_out, void* cache,
+                                  int32_t cache_e4m3, int64_t T_max, int64_t pos, const int32_t* pos_rows, void* ws, int64_t ws_bytes, obte_stream s) {
+    const char* who = "obte_block_step_w4";
+    OBTE_REQUIRE(codes && scales, "%s: null pointer", who);
+    for (int i = 0; i < 4; ++i) {
+        OBTE_REQUIRE(codes[i] && scales[i], "%s: null pointer (codes[%d] / scales[%d])", who, i, i);
+        OBTE_REQUIRE(((uintptr_t)codes[i] & 7) == 0 && ((uintptr_t)scales[i] & 1) == 0, "%s: codes[%d] must be 8-byte aligned, scales[%d] 2-byte aligned", who, i, i);
+    }
+    return cached_step(who, d, x, y_out, (obte_bf16*)cache, T_max, pos, pos_rows, pos_rows != nullptr, true, ws, ws_bytes, s, cache_e4m3 != 0, InferAttention::W_MXFP4, codes,
+                       scales);
 }
 
 // InferLayout at T = n_new (M = B n_new rows) with obte_attn_extend's partials behind it (include/omnibiote_hip_extend.h)

@@ -15,6 +15,7 @@
 #include "../../include/omnibiote_hip_kv8.h"
 #include "../../include/omnibiote_hip_shared.h"
 #include "../../include/omnibiote_hip_w8.h"
+#include "../../include/omnibiote_hip_w4.h"
 #include "../../include/omnibiote_hip_beam.h"
 #include "../../include/omnibiote_hip_paged.h"
 #include "../../include/omnibiote_hip_paged8.h"

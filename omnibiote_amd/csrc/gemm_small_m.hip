@@ -22,6 +22,8 @@
 // The format of W is a policy of both kernels (WBf16 / WE4m3 below, as attention_decode.hip has CacheBf16 / CacheE4m3): W as OCP e4m3 codes
 // with one power-of-two fp32 scale per row (include/omnibiote_hip_w8.h, obte_linear_small_m_w8) is the same kernels with half the bytes per
 // lane, an exact code -> bf16 conversion in front of the same MFMA and the row's scale on the fp32 sum in the finish.  DESIGN.md 14.11.
+// WMxfp4: W as OCP MXFP4 (include/omnibiote_hip_w4.h, obte_linear_small_m_w4), a quarter of the bytes per lane and one scale byte per 32-deep
+// block, applied inside the exact conversion: nothing reaches the finish.  DESIGN.md 14.20.
 #include "common.h"
 #include <atomic>
 #include <stdlib.h>
@@ -41,6 +43,10 @@ struct SmallMParams {
 
 struct SmallMParamsW8 : SmallMParams {   // w is null, ldb the codes' row stride in bytes
     const uint8_t* codes; const float* scales;
+};
+
+struct SmallMParamsW4 : SmallMParams {   // w is null, ldb the codes' row stride in bytes, lds the scale bytes'
+    const uint8_t* codes; const uint8_t* scales; int64_t lds;
 };
 
 // ---- the format of W ---------------------------------------------------------------------------------------------------------------------
@@ -102,6 +108,33 @@ struct WE4m3 {
 #pragma unroll
         for (int j = 0; j < 4; ++j) { lo[j] *= sc.v[j]; hi[j] *= sc.v[4 + j]; }
     }
+};
+// MXFP4 (include/omnibiote_hip_w4.h): OCP e2m1 codes, two to a byte, 32 bytes to a chunk in the order pack_codes (omnibiote_amd/w4quant.py)
+// leaves them — byte 8 fq + 4 s + j / 2 of a 32-byte group holds k = 32 s + 8 fq + j, even j in the low nibble — so a lane's two fragments
+// are ONE 8-byte load, word s the eight codes of k-step s in k order; and one e8m0 byte per 32-deep block of a row, which is one k-step of
+// one row: the two of a chunk are one 2-byte load, every lane of a row the same two.  v_cvt_scalef32_pk_bf16_fp4 turns byte `sel` of a word
+// into two bf16 (the low nibble first) times 2^(exponent field of the scale operand - 127); the operand here is the fp32 with the e8m0 byte as its
+// exponent field and no mantissa, 2^(byte - 127) itself for the bytes 1 .. 254.  An e2m1 value has 2 significant bits and the quantiser's
+// scales keep every product a normal bf16, so the conversion is exact and the block's scale needs no place in the sum: Scale is empty.
+struct WMxfp4 {
+    using Params = SmallMParamsW4;
+    struct Row { const uint8_t* c; const uint8_t* e; };
+    struct Raw { u32x2 q; uint32_t e; };
+    struct Scale {};
+    static constexpr const char* NAME = "obte_linear_small_m_w4";
+    static __device__ __forceinline__ Row row(const Params& p, int64_t n, int fq) { return Row{p.codes + n * p.ldb + fq * 8, p.scales + n * p.lds}; }
+    static __device__ __forceinline__ Raw load(Row r, int64_t k) {   // k % 64 == 0
+        return Raw{*reinterpret_cast<const u32x2*>(r.c + (k >> 1)), *reinterpret_cast<const uint16_t*>(r.e + (k >> 5))};
+    }
+    static __device__ __forceinline__ bf16x8 frag(const Raw& w, int s) {
+        const float scale = __builtin_bit_cast(float, ((w.e >> (8 * s)) & 0xffu) << 23);
+        const uint32_t word = w.q[s];
+        const bf16x2 f0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, scale, 0), f1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, scale, 1);
+        const bf16x2 f2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, scale, 2), f3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, scale, 3);
+        return bf16x8{f0[0], f0[1], f1[0], f1[1], f2[0], f2[1], f3[0], f3[1]};
+    }
+    static __device__ __forceinline__ Scale scale(const Params&, int64_t, bool) { return {}; }
+    static __device__ __forceinline__ void apply(f32x4&, f32x4&, const Scale&) {}
 };
 // the thread of small_m_finish that owns columns n .. n + 7 of a strip at n0 loads their scales ahead of the sum
 template <class WF, int MT>
@@ -399,4 +432,21 @@ extern "C" int obte_linear_small_m_w8(const obte_gemm_args* g, const void* codes
     fill_params(p, g);
     p.w = nullptr; p.ldb = ld_codes; p.codes = (const uint8_t*)codes; p.scales = scales;
     return launch_any<WE4m3>(p, g, 9, (hipStream_t)s);
+}
+
+extern "C" int obte_linear_small_m_w4(const obte_gemm_args* g, const void* codes, int64_t ld_codes, const void* scales, int64_t ld_scales, obte_stream s) {
+    const char* who = "obte_linear_small_m_w4";
+    const int rc = check_args(who, g, true);
+    if (rc != OBTE_OK) return rc;
+    OBTE_REQUIRE(codes && scales, "%s: null pointer", who);
+    OBTE_REQUIRE(ld_codes % 8 == 0 && ld_codes >= g->K / 2, "%s: ld_codes must be a multiple of 8 and at least K / 2 (ld_codes=%lld K=%lld)", who, (long long)ld_codes,
+                 (long long)g->K);
+    OBTE_REQUIRE(ld_scales % 2 == 0 && ld_scales >= g->K / 32, "%s: ld_scales must be even and at least K / 32 (ld_scales=%lld K=%lld)", who, (long long)ld_scales,
+                 (long long)g->K);
+    OBTE_REQUIRE_ALIGNED(who, codes, "codes", 8);
+    OBTE_REQUIRE_ALIGNED(who, scales, "scales", 2);
+    SmallMParamsW4 p;
+    fill_params(p, g);
+    p.w = nullptr; p.ldb = ld_codes; p.codes = (const uint8_t*)codes; p.scales = (const uint8_t*)scales; p.lds = ld_scales;
+    return launch_any<WMxfp4>(p, g, 10, (hipStream_t)s);
 }

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import w4quant
 from . import w8quant
 
 
@@ -680,9 +681,19 @@ class QuantizedWeights:
 
     A snapshot: it remembers every source parameter's ``data_ptr()`` and ``_version``, and every use raises ValueError ("quantize_weights
     again") once a parameter was updated or moved.  It holds 3 bytes per parameter (codes and the bf16 copy) beside the model's 2;
-    serving from the codes alone, without the bf16 copies, is not built."""
+    serving from the codes alone, without the bf16 copies, is not built.
 
-    def __init__(self, model):
+    ``format="mxfp4"`` (``.format`` says which): OCP MXFP4 instead (include/omnibiote_hip_w4.h, w4quant.py) — ``codes[i]`` uint8 (N, K / 2), two
+    e2m1 codes per byte in w4quant's stored order, ``scales[i]`` uint8 (N, K / 32), one e8m0 power of two per 32 elements of a row; the
+    same attributes under the same names, the same contract, a quarter of the bytes and a sixteenth per cached step, and about 2.53 bytes
+    per parameter held beside the model's 2.  Any other format: ValueError."""
+
+    FORMATS = {"e4m3": w8quant, "mxfp4": w4quant}
+
+    def __init__(self, model, format="e4m3"):
+        if format not in self.FORMATS:
+            raise ValueError(f"quantize_weights: format must be one of {', '.join(map(repr, self.FORMATS))}, got {format!r}")
+        self.format, self._quant = format, self.FORMATS[format]
         self.model = model
         self._sources = []
         self.codes, self.scales, self.dequantized, self._params = [], [], [], []
@@ -698,8 +709,8 @@ class QuantizedWeights:
             raise ValueError(f"quantize_weights: the weights must be torch.bfloat16, got {param.dtype}: call model.to(torch.bfloat16)")
         self._sources.append((param, param.data_ptr(), param._version))
         with torch.no_grad():
-            codes, scales = w8quant.quantize_weight(param.detach())
-            return codes, scales, w8quant.dequantize_weight(codes, scales)
+            codes, scales = self._quant.quantize_weight(param.detach())
+            return codes, scales, self._quant.dequantize_weight(codes, scales)
 
     def check(self, model, what):
         """ValueError in ``what``'s name unless this is ``model``'s snapshot and every source parameter is where and what it was"""

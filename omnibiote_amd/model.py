@@ -1082,24 +1082,27 @@ class OmniBioTA(nn.Module):
                                       "position at a time (prefill, decode_step, generate(num_samples=)); several new positions per row in one "
                                       "call need a KVCache")
 
-    def quantize_weights(self):
+    def quantize_weights(self, format="e4m3"):
         """This model's four matrices per block and its readout as e4m3 codes with a power-of-two scale per output row, together with
         their dequantised bf16 form: a ``QuantizedWeights`` for ``weights=`` of ``prefill``, ``decode_step``, ``generate`` and
         ``DecodeLoop``.  Runs in plain torch on the parameters' device, once; a snapshot — after an optimizer step, a ``load_state_dict``
         or a ``.to(...)`` call it again.  It holds 3 bytes per parameter beside the model's 2 (the bf16 copies serve the prompt and
-        batches above the weight-streaming product's row limit; dropping them is not built)."""
-        return QuantizedWeights(self)
+        batches above the weight-streaming product's row limit; dropping them is not built).  ``format="mxfp4"``: OCP MXFP4 instead, e2m1
+        codes with a power-of-two scale per 32 elements of a row (w4quant.py): a quarter of the bf16 bytes and a sixteenth, about 2.53
+        bytes per parameter held."""
+        return QuantizedWeights(self, format)
 
     def _readout_rows(self, x, out=None, weights=None):
         """The readout of a generation step's (B, C) rows: at most ops' small_m_max of them, bf16 on the GPU, through the
         weight-streaming product with MuReadout.forward's alpha; anything else through the module.  ``out``: a (B, vocab) buffer of the
-        caller's that takes the logits (a ``DecodeLoop``'s, whose address must not change).  ``weights``: the readout's e4m3 codes on
-        that product, the tile product on the dequantised readout above its row limit."""
+        caller's that takes the logits (a ``DecodeLoop``'s, whose address must not change).  ``weights``: the readout's codes (e4m3 or
+        MXFP4, by ``weights.format``) on that product, the tile product on the dequantised readout above its row limit."""
         if weights is not None:
             _require_hip(x, "OmniBioTA")
             alpha = float(self.lm_head.output_mult) / float(self.lm_head.width_mult())
             if x.shape[0] <= L.lib().obte_small_m_max():
-                return ops.linear_small_m_w8(x, weights.head_codes, weights.head_scales, alpha=alpha, out=out)
+                product = ops.linear_small_m_w4 if weights.format == "mxfp4" else ops.linear_small_m_w8
+                return product(x, weights.head_codes, weights.head_scales, alpha=alpha, out=out)
             y = ops.linear_fwd(x, weights.head_dequantized, alpha=alpha)
             return y if out is None else out.copy_(y)
         w = self.lm_head.weight
@@ -1382,8 +1385,8 @@ class OmniBioTA(nn.Module):
                 else:
                     ops.block_decode_beam(x, params, rope, H, *at, ancestry, **to)
             elif weights is not None:
-                ops.block_step_w8(x, weights.block_params(i), (weights.codes[i], weights.scales[i]), rope, H, kv, cache.max_len, pos, pos_rows,
-                                  kv8=cache.dtype == "fp8", **to)
+                step = ops.block_step_w4 if weights.format == "mxfp4" else ops.block_step_w8
+                step(x, weights.block_params(i), (weights.codes[i], weights.scales[i]), rope, H, kv, cache.max_len, pos, pos_rows, kv8=cache.dtype == "fp8", **to)
             elif cache.dtype == "fp8":
                 ops.block_decode_kv8(x, params, rope, H, kv, cache.max_len, pos, pos_rows, **to)
             elif pos_rows is not None:

@@ -273,6 +273,32 @@ def linear_small_m_w8(x2d, codes, scales, epilogue=L.EPI_NONE, aux=None, alpha=1
     return d
 
 
+def linear_small_m_w4(x2d, codes, scales, epilogue=L.EPI_NONE, aux=None, alpha=1.0, rope=None, out=None):
+    """linear_small_m with W as MXFP4: codes uint8 [N, K / 2] (in w4quant's stored order) and block scales uint8 [N, K / 32]
+    (obte_linear_small_m_w4); either may be a row-strided view, the codes' stride a multiple of 8, the scales' even.  Bit for bit
+    linear_small_m on ``w4quant.dequantize_weight(codes, scales)``, reading a quarter of the bytes and a sixteenth.  The same epilogues,
+    aux, alpha, rope and out."""
+    _need(x2d, "x", contiguous=False); _need(codes, "codes", torch.uint8, contiguous=False); _need(scales, "scales", torch.uint8, contiguous=False)
+    M, K = x2d.shape
+    N = codes.shape[0]
+    assert K % 64 == 0 and codes.dim() == 2 and codes.shape[1] == K // 2 and codes.stride(1) == 1 and x2d.stride(1) == 1
+    assert scales.dim() == 2 and scales.shape == (N, K // 32) and scales.stride(1) == 1
+    d = out if out is not None else torch.empty((M, N), dtype=bf16, device=x2d.device)
+    _need(d, "out", contiguous=False); assert d.shape == (M, N) and d.stride(1) == 1
+    if epilogue == L.EPI_ADD:
+        _need(aux, "aux", contiguous=False); assert aux.shape == (M, N) and aux.stride(1) == 1 and (M == 1 or aux.stride(0) == d.stride(0))
+    g = L.GemmArgs(_ptr(x2d), None, _ptr(d), _ptr(aux), None, M, N, K, x2d.stride(0) if M > 1 else K, K, d.stride(0) if M > 1 else N,
+                   1, 1, epilogue, float(alpha), 0.0, 0, 0)
+    if epilogue == L.EPI_ROPE_QK:
+        cos, sin, rT, rhs = rope
+        _need(cos, "cos", torch.float32); _need(sin, "sin", torch.float32)
+        assert cos.shape[0] >= rT and cos.shape[-1] == rhs // 2
+        g.rope_cos, g.rope_sin, g.rope_T, g.rope_head_dim = _ptr(cos), _ptr(sin), rT, rhs
+    L.check(L.lib().obte_linear_small_m_w4(C.byref(g), _ptr(codes), codes.stride(0) if N > 1 else K // 2, _ptr(scales), scales.stride(0) if N > 1 else K // 32,
+                                           _stream()), "obte_linear_small_m_w4")
+    return d
+
+
 @contextlib.contextmanager
 def small_m_max(m: int):
     """Within the block, decode steps and last-position readouts of at most ``m`` rows (0..64, 0: none) take the weight-streaming
@@ -1424,6 +1450,27 @@ def block_step_w8(x, params, w8, rope, H, cache, T_max, pos, pos_rows=None, kv8=
     return _block_call(x, params, rope, H, ws, out, _decode_ws, lambda d, y, w: L.check(
         L.lib().obte_block_step_w8(d, cp, sp, _ptr(x), _ptr(y), _ptr(cache), 1 if kv8 else 0, T_max, int(pos), _ptr(pos_rows), _ptr(w), w.numel(),
                                    _stream()), "obte_block_step_w8"),
+        cache=cache, T_max=T_max, rows=None if pos_rows is None else (pos_rows, "pos_rows"), at=pos, one=True, kv8=kv8)
+
+
+# ---- the same with the weights stored as OCP MXFP4 (include/omnibiote_hip_w4.h; the format in plain torch: w4quant.py) ----
+def block_step_w4(x, params, w4, rope, H, cache, T_max, pos, pos_rows=None, kv8=False, ws=None, out=None):
+    """block_step_w8 with the four products on linear_small_m_w4 (obte_block_step_w4): x (B, C) -> y (B, C).  w4 = (codes, scales): four
+    uint8 (N, K / 2) tensors in w4quant's stored order and four uint8 (N, K / 32) ones, in the order c_attn, attention c_proj, c_fc, MLP
+    c_proj.  ``params`` holds the DEQUANTISED four weights (``w4quant.dequantize_weight``): the result has the bits of the bf16 step on
+    them, and above small_m_max rows the products run on the tile structures from them."""
+    codes, scales = w4
+    if len(codes) != 4 or len(scales) != 4:
+        raise ValueError("block_step_w4: w4 = (four code tensors, four scale tensors)")
+    for i, (c, sc, w) in enumerate(zip(codes, scales, (params[1], params[2], params[4], params[5]))):
+        _need(c, f"codes{i}", torch.uint8); _need(sc, f"scales{i}", torch.uint8)
+        if w.shape[1] % 64 != 0 or c.shape != (w.shape[0], w.shape[1] // 2) or sc.shape != (w.shape[0], w.shape[1] // 32):
+            raise ValueError(f"block_step_w4: codes{i} {tuple(c.shape)} / scales{i} {tuple(sc.shape)} do not match the weight {tuple(w.shape)}")
+    cp = (C.c_void_p * 4)(*[_ptr(c) for c in codes])
+    sp = (C.c_void_p * 4)(*[_ptr(sc) for sc in scales])
+    return _block_call(x, params, rope, H, ws, out, _decode_ws, lambda d, y, w: L.check(
+        L.lib().obte_block_step_w4(d, cp, sp, _ptr(x), _ptr(y), _ptr(cache), 1 if kv8 else 0, T_max, int(pos), _ptr(pos_rows), _ptr(w), w.numel(),
+                                   _stream()), "obte_block_step_w4"),
         cache=cache, T_max=T_max, rows=None if pos_rows is None else (pos_rows, "pos_rows"), at=pos, one=True, kv8=kv8)
 
 

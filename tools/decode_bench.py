@@ -72,6 +72,12 @@ random values, only the time is read), and the captured DecodeLoop at B = 1.  On
 runs one part.
 
     python tools/decode_bench.py --w8 [--w8-part products] [--rounds 5] [--steps 300]
+
+--w4: --w8 with MXFP4 weights (model.quantize_weights(format="mxfp4"), include/omnibiote_hip_w4.h) as a third leg of every comparison, the three
+alternating in one process.  The products at M = 1 and 64, on enough copies that the MXFP4 set, the smallest, exceeds the Infinity Cache; the byte
+ratio to e4m3 is (K / 2 + K / 32) / (K + 4).  Every line carries mxfp4_over_e4m3 and mxfp4_over_bf16 beside what --w8 prints.
+
+    python tools/decode_bench.py --w4 [--w8-part products] [--rounds 5] [--steps 300]
 """
 import argparse
 import contextlib
@@ -597,26 +603,34 @@ def graph_compare(m, B, ctx, rounds, steps, dev, constrained=False, penalized=Fa
 W8_ROWS = (1, 8, 64)
 
 
-def w8_products(C_, rounds, steps, dev):
-    """obte_linear_small_m_w8 against obte_linear_small_m_bf16 alone at width C_, every call on the next distinct copy of the weight"""
+def w8_products(C_, rounds, steps, dev, mxfp4=False, rows=W8_ROWS):
+    """obte_linear_small_m_w8 against obte_linear_small_m_bf16 alone at width C_, every call on the next distinct copy of the weight;
+    ``mxfp4``: obte_linear_small_m_w4 as a third leg, the copies counted so that ITS set, the smallest, is 1.25 Infinity Caches"""
     import ctypes as C
-    from omnibiote_amd import _lib, w8quant
+    from omnibiote_amd import _lib, w4quant, w8quant
     lib, stream = _lib.lib(), torch.cuda.current_stream().cuda_stream
     gen = torch.Generator(device=dev).manual_seed(5)
     for name, N, K in (("c_attn", 3 * C_, C_), ("proj", C_, C_), ("fc", 4 * C_, C_), ("mlp", C_, 4 * C_), ("readout", 65536, C_)):
-        copies = -(-(INFINITY_CACHE * 5 // 4) // (N * K))               # the e4m3 set, the smaller one, is 1.25 Infinity Caches
+        copies = -(-(INFINITY_CACHE * 5 // 4) // (N * K // 2 if mxfp4 else N * K))   # the smallest set is 1.25 Infinity Caches
         w = torch.randn(N, K, device=dev, generator=gen).mul_(0.02).to(torch.bfloat16)
         codes, scales = w8quant.quantize_weight(w)
         ws = [w] + [w.clone() for _ in range(copies - 1)]
         cs = [codes] + [codes.clone() for _ in range(copies - 1)]
         ss = [scales] + [scales.clone() for _ in range(copies - 1)]
+        if mxfp4:
+            c4, s4 = w4quant.quantize_weight(w)
+            cs4 = [c4] + [c4.clone() for _ in range(copies - 1)]
+            ss4 = [s4] + [s4.clone() for _ in range(copies - 1)]
         strips, ch = -(-N // 16), K // 256 if K % 256 == 0 else 0
         out = {"width": C_, "product": name, "N": N, "K": K, "weight_copies": copies,
                "kernel": "x-stationary" if strips > 512 and ch in (1, 2, 4) else "one strip per workgroup",
                "set_bytes": {"bf16": copies * N * K * 2, "e4m3": copies * N * (K + 4)},
-               "served_from": "HBM" if copies * N * K > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)",
+               "served_from": "HBM" if copies * N * K // (2 if mxfp4 else 1) > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)",
                "byte_ratio": round((K + 4) / (2 * K), 4), "M": {}}
-        for M in W8_ROWS:
+        if mxfp4:
+            out["set_bytes"]["mxfp4"] = copies * N * (K // 2 + K // 32)
+            out["mxfp4_byte_ratio_to_e4m3"] = round((K // 2 + K // 32) / (K + 4), 4)
+        for M in rows:
             x = torch.randn(M, K, device=dev, generator=gen).to(torch.bfloat16)
             d = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
             args = [_lib.GemmArgs(x.data_ptr(), wi.data_ptr(), d.data_ptr(), None, None, M, N, K, K, K, N, 1, 1, _lib.EPI_NONE, 1.0, 0.0, 0, 0) for wi in ws]
@@ -634,7 +648,14 @@ def w8_products(C_, rounds, steps, dev):
                 rc = lib.obte_linear_small_m_w8(C.byref(args[i]), cs[i].data_ptr(), K, ss[i].data_ptr(), stream)
                 if rc != 0:
                     _lib.check(rc, "obte_linear_small_m_w8")
-            legs = {"bf16": bf16, "e4m3": e4m3}
+
+            def fp4():
+                state["i"] += 1
+                i = state["i"] % copies
+                rc = lib.obte_linear_small_m_w4(C.byref(args[i]), cs4[i].data_ptr(), K // 2, ss4[i].data_ptr(), K // 32, stream)
+                if rc != 0:
+                    _lib.check(rc, "obte_linear_small_m_w4")
+            legs = {"bf16": bf16, "e4m3": e4m3, **({"mxfp4": fp4} if mxfp4 else {})}
             for fn in legs.values():
                 for _ in range(8):
                     fn()
@@ -647,13 +668,20 @@ def w8_products(C_, rounds, steps, dev):
                                 "gap_us_and_spreads": [round(med["bf16"] - med["e4m3"], 2)] + [round(max(v) - min(v), 2) for v in us.values()],
                                 "share_of_6.3TBps": {"bf16": round(N * K * 2 / (med["bf16"] * 1e-6) / HBM_RATE, 3),
                                                      "e4m3": round(N * (K + 4) / (med["e4m3"] * 1e-6) / HBM_RATE, 3)}}
+            if mxfp4:
+                out["M"][str(M)]["mxfp4_over_e4m3"] = round(med["mxfp4"] / med["e4m3"], 3)
+                out["M"][str(M)]["mxfp4_over_bf16"] = round(med["mxfp4"] / med["bf16"], 3)
+                out["M"][str(M)]["share_of_6.3TBps"]["mxfp4"] = round(N * (K // 2 + K // 32) / (med["mxfp4"] * 1e-6) / HBM_RATE, 3)
         print(json.dumps(out), flush=True)
+        if mxfp4:
+            del cs4, ss4, c4, s4
         del ws, cs, ss, w, codes, scales
         torch.cuda.empty_cache()
 
 
-def w8_tokens(m, wq, config, B, ctx, rounds, steps, dev, graph=False):
-    """decode_step with and without weights=, alternating; ``graph``: also the captured DecodeLoop both ways"""
+def w8_tokens(m, wq, config, B, ctx, rounds, steps, dev, graph=False, wq4=None):
+    """decode_step with and without weights=, alternating; ``graph``: also the captured DecodeLoop both ways; ``wq4``: the MXFP4 snapshot as
+    a third leg of both"""
     from omnibiote_amd.model import DecodeLoop, KVCache
     g = torch.Generator(device=dev).manual_seed(B * 10007 + ctx)
     last = torch.randint(4, m.config.vocab_size, (B,), device=dev, generator=g)
@@ -669,7 +697,7 @@ def w8_tokens(m, wq, config, B, ctx, rounds, steps, dev, graph=False):
             else:
                 m.decode_step(last, cache, weights=weights)
         return fn
-    legs = {"bf16": step(None), "e4m3": step(wq)}
+    legs = {"bf16": step(None), "e4m3": step(wq), **({"mxfp4": step(wq4)} if wq4 is not None else {})}
     for fn in legs.values():
         for _ in range(3):
             fn()
@@ -681,11 +709,13 @@ def w8_tokens(m, wq, config, B, ctx, rounds, steps, dev, graph=False):
     out = {"config": config, "B": B, "context": ctx, "windows": {"decode_steps": steps, "rounds": rounds},
            "decode_step_us": {k: summary(v, 1) for k, v in us.items()}, "e4m3_over_bf16": round(med["e4m3"] / med["bf16"], 3),
            "gap_us_and_spreads": [round(med["bf16"] - med["e4m3"], 1)] + [round(max(v) - min(v), 1) for v in us.values()]}
+    if wq4 is not None:
+        out["mxfp4_over_e4m3"], out["mxfp4_over_bf16"] = round(med["mxfp4"] / med["e4m3"], 3), round(med["mxfp4"] / med["bf16"], 3)
     if graph:
         first = ctx - 1 - steps
         idx = torch.randint(4, m.config.vocab_size, (B, first), device=dev, generator=g)
         runs = {}
-        for k, w in (("bf16", None), ("e4m3", wq)):
+        for k, w in (("bf16", None), ("e4m3", wq)) + ((("mxfp4", wq4),) if wq4 is not None else ()):
             c = KVCache(m, B, ctx)
             extra = {} if w is None else {"weights": w}
             logits = m.prefill(idx, c, lengths=[first] * B, **extra)
@@ -711,6 +741,8 @@ def w8_tokens(m, wq, config, B, ctx, rounds, steps, dev, graph=False):
                 gus[k].append(window(k))
         out["graph_loop_us_per_token"] = {k: summary(v, 1) for k, v in gus.items()}
         out["graph_loop_e4m3_over_bf16"] = round(statistics.median(gus["e4m3"]) / statistics.median(gus["bf16"]), 3)
+        if wq4 is not None:
+            out["graph_loop_mxfp4_over_e4m3"] = round(statistics.median(gus["mxfp4"]) / statistics.median(gus["e4m3"]), 3)
     return out
 
 
@@ -739,7 +771,8 @@ def main():
     p.add_argument("--graph", action="store_true", help="the device-resident token loop, eager and captured, against today's host-driven loop")
     p.add_argument("--constrained", action="store_true", help="with --graph: also the captured loop under per-row token masks and a minimum length")
     p.add_argument("--w8", action="store_true", help="e4m3 weights against bf16: the product alone, decode_step on the small and the large config")
-    p.add_argument("--w8-part", default="products,small,large", help="with --w8: which parts run")
+    p.add_argument("--w8-part", default="products,small,large", help="with --w8 / --w4: which parts run")
+    p.add_argument("--w4", action="store_true", help="--w8 with MXFP4 weights as a third leg of every comparison (products at M = 1 and 64)")
     p.add_argument("--penalized", action="store_true", help="with --graph: also the captured loop under repetition, presence and frequency penalties")
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--steps", type=int, default=300, help="decode steps (and attention calls) per timed window")
@@ -748,21 +781,24 @@ def main():
     a = p.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
-    if a.w8:
+    if a.w8 or a.w4:
         parts = a.w8_part.split(",")
         if "products" in parts:
             for C_ in (1024, 2048):
-                w8_products(C_, a.rounds, a.steps, dev)
+                w8_products(C_, a.rounds, a.steps, dev, mxfp4=a.w4, rows=(1, 64) if a.w4 else W8_ROWS)
         for config, kw in (("small", dict(n_layer=8, n_embd=1024, n_head=8)), ("large", dict(n_layer=24, n_embd=2048, n_head=16, on_device=True))):
             if config not in parts:
                 continue
             m = build(2048, dev, **kw)
             wq = m.quantize_weights()
+            wq4 = m.quantize_weights(format="mxfp4") if a.w4 else None
             print(json.dumps({"config": config, **w8_deviation(m, wq, dev)}), flush=True)
+            if a.w4:
+                print(json.dumps({"config": config, "format": "mxfp4", **w8_deviation(m, wq4, dev)}), flush=True)
             for B in (1, 8, 64):
-                print(json.dumps(w8_tokens(m, wq, config, B, 2048, a.rounds, a.steps, dev, graph=B == 1)), flush=True)
+                print(json.dumps(w8_tokens(m, wq, config, B, 2048, a.rounds, a.steps, dev, graph=B == 1, wq4=wq4)), flush=True)
                 torch.cuda.empty_cache()
-            del m, wq
+            del m, wq, wq4
             torch.cuda.empty_cache()
         return
     if a.graph:
