@@ -338,6 +338,17 @@ SYMBOLS_PAGED8 = {
                                            C.c_void_p, C.c_int64, c_stream]),
 }
 
+# several new positions per row against the pages of a bf16 pool (include/omnibiote_hip_paged_extend.h): SYMBOLS_EXTEND's argument lists with
+# (pool, n_pages, table, table_ld) in the place of (cache, T_max)
+SYMBOLS_PAGED_EXTEND = {
+    "obte_attn_extend_paged": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                         C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    "obte_kv_paged_rope_store_chunk": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                                    c_stream]),
+    "obte_block_extend_paged": (C.c_int, [C.POINTER(BlockDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -370,7 +381,7 @@ def lib():
                                             + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
                                             + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items()) + list(SYMBOLS_PENALTY.items())
                                             + list(SYMBOLS_DISTILL.items()) + list(SYMBOLS_BEAM.items()) + list(SYMBOLS_PAGED.items())
-                                            + list(SYMBOLS_PAGED8.items()) + list(SYMBOLS_W4.items())):
+                                            + list(SYMBOLS_PAGED8.items()) + list(SYMBOLS_W4.items()) + list(SYMBOLS_PAGED_EXTEND.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

@@ -851,6 +851,22 @@ extern "C" int obte_kv8_paged_rope_store_rows(obte_bf16* qkv, const float* rope_
                                          table_ld, s);
 }
 
+// n_new positions per row from pos_rows[b] on, through the table (include/omnibiote_hip_paged_extend.h): obte_kv_cache_rope_store_chunk's shape rule and
+// bound with 64 table_ld in T_max's place, the paged stores' launch at n = n_new
+extern "C" int obte_kv_paged_rope_store_chunk(obte_bf16* qkv, const float* rope_cos, const float* rope_sin, const int32_t* pos_rows, int64_t max_pos, int64_t B,
+                                              int64_t n_new, int32_t n_head, int32_t head_dim, obte_bf16* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,
+                                              obte_stream s) {
+    const char* who = "obte_kv_paged_rope_store_chunk";
+    OBTE_REQUIRE(qkv && rope_cos && rope_sin && pos_rows && pool && table, "%s: null pointer", who);
+    OBTE_REQUIRE(paged_shape_ok(B, n_pages, table_ld, n_head, head_dim) && B * n_head <= 65535 && n_new > 0 && n_new < (1ll << 20) && B * n_new < (1ll << 31),
+                 "%s: bad shape (head_dim 64 or 128, n_new >= 1)", who);
+    OBTE_REQUIRE(max_pos >= 0 && max_pos + n_new <= DEC_CHUNK * table_ld, "%s: positions up to %lld + %lld do not fit the table's [0, 64 * table_ld = %lld)", who,
+                 (long long)max_pos, (long long)n_new, (long long)(DEC_CHUNK * table_ld));
+    OBTE_REQUIRE((((uintptr_t)qkv | (uintptr_t)pool | (uintptr_t)rope_cos | (uintptr_t)rope_sin) & 15) == 0 && (((uintptr_t)pos_rows | (uintptr_t)table) & 3) == 0,
+                 "%s: qkv, pool and the rope tables must be 16-byte aligned, pos_rows and table 4-byte aligned", who);
+    return kv_paged_store_launch(who, false, qkv, rope_cos, rope_sin, pos_rows, max_pos, B, n_new, n_head, head_dim, pool, n_pages, table, table_ld, s);
+}
+
 // obte_attn_decode_on's checks and its two launches, on the pool (e4m3: the pool of include/omnibiote_hip_paged8.h): row b over rows_n[b] + key_off keys,
 // max_keys the host's bound on that
 int obte_attn_decode_paged_on(bool e4m3, const char* who, const obte_bf16* q, int64_t q_ld, const void* pool, int64_t n_pages, const int32_t* table, int64_t table_ld,

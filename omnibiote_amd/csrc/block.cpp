@@ -506,7 +506,7 @@ struct InferAttention {
     // with prefix_cache: suffix slot j of row b is read from the group's row ancestry[b][j] (obte_block_decode_beam, include/omnibiote_hip_beam.h)
     const int32_t* ancestry = nullptr;
     // the cache in pages (include/omnibiote_hip_paged.h): kv_cache is the layer's pool of n_pages pages and page_table [B, table_ld] says where
-    // each row's positions lie; prefill, and decode in the rows form (T_max is not read)
+    // each row's positions lie; prefill, and decode or (bf16) n_new positions per row in the rows form (T_max is not read)
     const int32_t* page_table = nullptr; int64_t n_pages = 0, table_ld = 0;
 };
 int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, const InferLayout& w, int64_t M, const float* rope_cos,
@@ -532,13 +532,18 @@ int infer_sequence(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_ou
     if (at.n_new > 0) {   // n_new positions per row join the cache (the rows form rotates them as it stores), then each attends over those up to its own
         const int64_t q_ld = 3 * (int64_t)C;
         const char* who = at.kv8 || at.pos_rows ? at.who : "obte_attn_decode";   // (the uniform bf16 step's attention refuses under its own name)
-        if (at.page_table && at.kv8)   // (the rows-form decode step through the page table; the e4m3 pool: include/omnibiote_hip_paged8.h)
+        if (at.page_table && !at.decode)   // (n_new positions per row through the page table: include/omnibiote_hip_paged_extend.h; bf16, rows form)
+            TRY(obte_kv_paged_rope_store_chunk(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.n_pages, at.page_table, at.table_ld, s));
+        else if (at.page_table && at.kv8)   // (the rows-form decode step through the page table; the e4m3 pool: include/omnibiote_hip_paged8.h)
             TRY(obte_kv8_paged_rope_store_rows(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.n_pages, at.page_table, at.table_ld, s));
         else if (at.page_table)
             TRY(obte_kv_paged_rope_store_rows(w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, H, hs, at.kv_cache, at.n_pages, at.page_table, at.table_ld, s));
         else
             TRY(obte_kv_store_on(at.kv8, at.who, w.qkv, rope_cos, rope_sin, at.pos_rows, at.pos, d->B, at.n_new, H, hs, at.kv_cache, at.T_max, s));
-        if (at.page_table)    // row b over its own pos_rows[b] + 1 keys, each read from its page
+        if (at.page_table && !at.decode)   // row b's n_new queries over its keys up to each one's own position, each key read from its page
+            TRY(obte_attn_extend_paged(w.qkv, q_ld, at.kv_cache, at.n_pages, at.page_table, at.table_ld, w.att, nullptr, d->B, at.n_new, at.pos, at.pos_rows, H, hs, scale, 0,
+                                       at.dec_ws, at.dec_ws_bytes, s));
+        else if (at.page_table)    // row b over its own pos_rows[b] + 1 keys, each read from its page
             TRY(obte_attn_decode_paged_on(at.kv8, who, w.qkv, q_ld, at.kv_cache, at.n_pages, at.page_table, at.table_ld, w.att, nullptr, d->B, at.pos_rows, 1, at.pos + 1, H, hs,
                                           scale, 0, at.dec_ws, at.dec_ws_bytes, s));
         else if (at.prefix_cache && at.ancestry)   // the same, the slots 0 .. pos read through the ancestry table
@@ -747,6 +752,18 @@ extern "C" int64_t obte_block_extend_ws_bytes(int64_t B, int64_t n_new, int32_t 
 extern "C" int obte_block_extend(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* kv_cache, int64_t T_max, int64_t pos,
                                  const int32_t* pos_rows, void* ws, int64_t ws_bytes, obte_stream s) {
     return cached_step("obte_block_extend", d, x, y_out, kv_cache, T_max, pos, pos_rows, pos_rows != nullptr, false, ws, ws_bytes, s);
+}
+
+// the rows form on the pages of a pool (include/omnibiote_hip_paged_extend.h)
+extern "C" int obte_block_extend_paged(const obte_block_desc* d, const obte_bf16* x, obte_bf16* y_out, obte_bf16* pool, int64_t n_pages, const int32_t* table,
+                                       int64_t table_ld, int64_t pos, const int32_t* pos_rows, void* ws, int64_t ws_bytes, obte_stream s) {
+    const char* who = "obte_block_extend_paged";
+    OBTE_REQUIRE(pool && table && pos_rows, "%s: null pointer", who);
+    OBTE_REQUIRE(n_pages > 0 && n_pages < (1ll << 24) && table_ld > 0 && table_ld < (1ll << 18), "%s: bad shape (n_pages in [1, 2^24), table_ld at least 1)", who);
+    OBTE_REQUIRE(((uintptr_t)pool & 15) == 0 && (((uintptr_t)pos_rows | (uintptr_t)table) & 3) == 0, "%s: pool must be 16-byte aligned, pos_rows and table 4-byte aligned",
+                 who);
+    return cached_step(who, d, x, y_out, pool, OBTE_KV_PAGE * table_ld, pos, pos_rows, true, false, ws, ws_bytes, s, false, InferAttention::W_BF16, nullptr, nullptr, table,
+                       n_pages);
 }
 
 // InferLayout at T = 1 (M = P G rows) with obte_attn_decode_shared's partials behind it (include/omnibiote_hip_shared.h)

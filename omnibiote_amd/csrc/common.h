@@ -19,6 +19,7 @@
 #include "../../include/omnibiote_hip_beam.h"
 #include "../../include/omnibiote_hip_paged.h"
 #include "../../include/omnibiote_hip_paged8.h"
+#include "../../include/omnibiote_hip_paged_extend.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

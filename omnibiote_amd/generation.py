@@ -576,17 +576,42 @@ class PagedPositions(CachePositions):
         self.book.park_rows(rows)
         self._moved()
 
-    def start_rows(self, rows, lengths):
+    def start_rows(self, rows, lengths, shared=None):
         """``prefill``'s bookkeeping: row rows[i] starts over behind a prompt of lengths[i] tokens, with pages for them (those it holds
-        count).  ValueError, with nothing changed, when the free list cannot cover all of them."""
+        count).  ``shared[i]`` (``prefill(shared_pages=)``): the pages that hold row rows[i]'s first 64 * len(shared[i]) positions
+        already — the row names them (``PageBook.assign_shared``: it must hold no page, and 64 * len(shared[i]) < lengths[i]) and gets
+        pages of its own for the rest.  ValueError, with nothing changed, for a bad ``shared`` or when the free list cannot cover every
+        row: only the pages that must come from the free list count, after the shared pages that lie on it (released, still valid) are
+        taken off it."""
         from .paged import pages_for
-        more = sum(max(0, pages_for(n) - len(self.book.row_pages[r])) for r, n in zip(rows, lengths))
-        if more > len(self.book.free):
-            raise ValueError(f"PagedKVCache: the prompts of rows {list(rows)} need {more} more pages and {len(self.book.free)} of {self.n_pages} are free")
+        rows, lengths = [int(r) for r in rows], [int(n) for n in lengths]
+        shared = self.check_shared(rows, lengths, shared)
+        revived = {p for pages in shared for p in pages if self.book.refs[p] == 0}
+        more = sum(max(0, pages_for(n) - len(self.book.row_pages[r]) - len(pages)) for r, n, pages in zip(rows, lengths, shared))
+        if more > len(self.book.free) - len(revived):
+            raise ValueError(f"PagedKVCache: the prompts of rows {list(rows)} need {more} more pages and {len(self.book.free) - len(revived)} of "
+                             f"{self.n_pages} are free")
+        for r, pages in zip(rows, shared):
+            if pages:
+                self.book.assign_shared(r, pages)
         for r, n in zip(rows, lengths):
             self.book.assign(r, n)
             self.book.place(r, n)
         self._moved(table=True)
+
+    def check_shared(self, rows, lengths, shared):
+        """``shared`` as ``start_rows`` takes it, one list of ints per row, or a ValueError that changes nothing: a row that still holds
+        pages, a page outside the pool, pages that cover a whole prompt (64 * len(shared[i]) >= lengths[i])"""
+        from .paged import KV_PAGE
+        shared = [[] for _ in rows] if shared is None else [list(p) for p in shared]
+        if len(shared) != len(rows):
+            raise ValueError(f"PagedKVCache: {len(shared)} lists of shared pages for {len(rows)} rows")
+        for i, (r, n) in enumerate(zip(rows, lengths)):
+            if shared[i]:
+                _, shared[i] = self.book.check_shared(r, shared[i])
+                if KV_PAGE * len(shared[i]) >= n:
+                    raise ValueError(f"PagedKVCache: row {r}: {len(shared[i])} shared pages cover the whole prompt of {n} tokens (at least one is computed)")
+        return shared
 
     def prepare_step(self):
         """before a decode step is launched: every active row whose position opens a new page gets one (ValueError when none is left)"""
@@ -638,7 +663,11 @@ class PagedKVCache(PagedPositions):
 
     Not built, each refused before anything is launched, for either dtype: several new positions per row over pages (``extend``,
     ``prefill(chunk=)``, ``draft_and_verify`` and the speculative loop); e4m3 weights (``weights=``); the device-resident loop and graph
-    capture (``DecodeLoop``); pages shared between rows (prefix sharing, copy-on-write); preemption or swapping of running rows."""
+    capture (``DecodeLoop``); copy-on-write and sharing of generated (non-prompt) pages; preemption or swapping of running rows.
+
+    Pages shared between rows (bf16 only): ``prefill(..., shared_pages=)`` lets a row name pages another row has filled with the same
+    prompt tokens and computes only the rest of its prompt against them (include/omnibiote_hip_paged_extend.h); ``PageBook`` counts the
+    rows that name a page and frees it with the last one; ``generate_many(share_prefix=True)`` finds the pages (``paged.PrefixIndex``)."""
 
     def __init__(self, model, batch, n_pages, max_len=None, free_order=None, dtype="bf16"):
         if dtype not in ("bf16", "fp8"):

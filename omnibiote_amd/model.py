@@ -1111,7 +1111,7 @@ class OmniBioTA(nn.Module):
         return self.lm_head(x) if out is None else out.copy_(self.lm_head(x))
 
     @torch.no_grad()
-    def prefill(self, idx, cache, lengths=None, chunk=None, weights=None, rows=None):
+    def prefill(self, idx, cache, lengths=None, chunk=None, weights=None, rows=None, shared_pages=None):
         """The prompt ``idx`` (B, T0) through every block under the causal mask, its keys and values left in ``cache`` (started
         over: ``cache.pos = T0``); returns the logits of the last position, (B, vocab).  ln_f and the readout run on that row alone.
 
@@ -1133,9 +1133,23 @@ class OmniBioTA(nn.Module):
         row.  Only those rows are started over — each gets pages for its ``len_b`` positions unless it holds them — and the others keep
         their state.  The same causal kernels run over the right-padded prompts (``ops.block_prefill_paged``, on an fp8 pool
         ``ops.block_prefill_paged8``, with the gathered table rows: the padding beyond a row's own pages is not stored).  ``chunk=`` and ``weights=`` raise NotImplementedError there: several new
-        positions per row over pages and e4m3 weights on pages are not built."""
+        positions per row over pages and e4m3 weights on pages are not built.
+
+        ``shared_pages`` (a bf16 ``PagedKVCache`` only): a host list with one list of page ids per prompt.  The caller vouches that the
+        m_i pages of ``shared_pages[i]`` hold positions [0, 64 m_i) of row i's prompt — another row computed them from the same tokens —
+        and 64 m_i < len_i.  Row i then NAMES those pages (``PageBook.assign_shared``) instead of computing and storing them again, gets
+        pages of its own for the rest, and only its remaining len_i - 64 m_i tokens run, right-padded to the longest tail, through
+        ``ops.block_extend_paged`` at positions 64 m_i on; its logits come from its last tail row.  Rows with an empty list go through the
+        path above — with every list empty, the same kernels and the same bits.  Where the rows' starts and tails do not fit one call
+        (max start + longest tail > ``cache.max_len``: a long start with a short tail beside a short start with a long tail) the host
+        makes several, sorted by start.  Shared pages are read-only by construction: a sharer's first store is at position 64 m_i, in a
+        page of its own, and the owner's later stores are at positions >= its prompt length >= 64 m_i; nothing copies on write.
+        NotImplementedError on an fp8 pool, on any other cache or with ``weights=``; ValueError for a page id outside the pool,
+        64 m_i >= len_i or a row that still holds pages — all before any state changes."""
         if isinstance(cache, PagedPositions):
-            return self._prefill_paged(idx, cache, lengths, chunk, weights, rows)
+            return self._prefill_paged(idx, cache, lengths, chunk, weights, rows, shared_pages)
+        if shared_pages is not None:
+            raise NotImplementedError("OmniBioTA.prefill: shared_pages= names pages of a PagedKVCache; no other cache shares positions between rows")
         if rows is not None:
             raise ValueError("OmniBioTA.prefill: rows= names the rows of a PagedKVCache; every other cache is prefilled as a whole")
         if isinstance(cache, SharedPrefixCache):
@@ -1175,11 +1189,13 @@ class OmniBioTA(nn.Module):
         last = x[torch.arange(b, device=idx.device), (cache.positions - 1).long()]          # (B, C): row b at its own last position
         return self._readout_rows(self.transformer.ln_f(last.contiguous()), weights=weights)
 
-    def _prefill_paged(self, idx, cache, lengths, chunk, weights, rows):
+    def _prefill_paged(self, idx, cache, lengths, chunk, weights, rows, shared_pages=None):
         """``prefill`` on a ``PagedKVCache``: the prompts ``idx`` (len(rows), T0) into the cache rows ``rows``; (len(rows), vocab)"""
         if chunk is not None:
             _refuse_paged("prefill(chunk=)", cache)
         _refuse_weights("prefill", weights, "do not run on a paged cache (PagedKVCache)")
+        if shared_pages is not None and cache.dtype == "fp8":
+            raise NotImplementedError("OmniBioTA.prefill: shared_pages= on an fp8 pool: several new positions per row over pages need a bf16 PagedKVCache")
         if idx.dim() != 2:
             raise ValueError(f"OmniBioTA.prefill: idx must be (B, T0), got {tuple(idx.shape)}")
         b, t = idx.shape
@@ -1193,20 +1209,73 @@ class OmniBioTA(nn.Module):
         if t > cache.max_len:
             raise ValueError(f"OmniBioTA.prefill: a prompt of {t} tokens does not fit the cache's {cache.max_len} positions")
         lens = [t] * b if lengths is None else _check_lengths("prefill", lengths, b, t)
+        if shared_pages is not None:
+            shared_pages = cache.check_shared(rows, lens, shared_pages)  # (ValueError with nothing changed)
+            if not any(shared_pages):
+                shared_pages = None                                     # nothing is shared: the call below, bit for bit
         wte = self.transformer.wte.weight
         _require_hip(wte, "OmniBioTA")
         if not idx.is_cuda:
             raise RuntimeError("OmniBioTA.prefill: idx must be on the GPU")
-        cache.start_rows(rows, lens)                                    # (ValueError with nothing changed when the free list cannot)
+        cache.start_rows(rows, lens, shared_pages)                      # (ValueError with nothing changed when the free list cannot, or for bad pages)
+        if shared_pages is not None:
+            return self._prefill_paged_tails(idx, cache, lens, rows, shared_pages)
         table = cache.table if whole else cache.table[torch.tensor(rows, device=idx.device)]
+        last = self._prefill_paged_rows(idx, cache, lens, table)
+        return self._readout_rows(self.transformer.ln_f(last.contiguous()))
+
+    def _prefill_paged_rows(self, idx, cache, lens, table):
+        """the prompts ``idx`` (b, t) under the causal mask into the pages of ``table`` (b, table_ld): (b, C), row i at its own last position"""
+        b, t = idx.shape
         mask = ops.MaskSpec.from_user(_autoregressive_mask(True, None, b, t, idx.device), b, t, self.config.n_head, idx.device)
-        x = ops.embedding_fwd(idx.contiguous(), wte)
+        x = ops.embedding_fwd(idx.contiguous(), self.transformer.wte.weight)
         ws = ops.block_infer_workspace(b, t, self.config.n_embd, self.config.n_head, idx.device)
         block_prefill = ops.block_prefill_paged8 if cache.dtype == "fp8" else ops.block_prefill_paged
         for block, pool in zip(self.transformer.h, cache.layers):
             block_prefill(x, self._block_params(block), block.attn.rope(), self.config.n_head, mask, pool, cache.n_pages, table, ws=ws, out=x)
-        last = x[torch.arange(b, device=idx.device), torch.tensor(lens, device=idx.device) - 1]   # (B, C): row b at its own last position
-        return self._readout_rows(self.transformer.ln_f(last.contiguous()))
+        return x[torch.arange(b, device=idx.device), torch.tensor(lens, device=idx.device) - 1]
+
+    @staticmethod
+    def _tail_calls(starts, tails, max_len):
+        """The rows (indices into ``starts``) of each ``block_extend_paged`` call: sorted by start, a call takes rows while its largest
+        start and its longest tail together stay within ``max_len`` (the RoPE tables' and the kernels' bound: pos + n).  A row alone
+        always fits: start + tail is its prompt length."""
+        calls = []
+        for i in sorted(range(len(starts)), key=lambda i: (starts[i], i)):
+            if calls and starts[i] + max(tails[i], max(tails[j] for j in calls[-1])) <= max_len:   # (sorted: starts[i] is the call's largest)
+                calls[-1].append(i)
+            else:
+                calls.append([i])
+        return calls
+
+    def _prefill_paged_tails(self, idx, cache, lens, rows, shared_pages):
+        """``prefill(shared_pages=)`` behind ``start_rows``: the rows without shared pages through the prefill kernels, the others'
+        tails through ``ops.block_extend_paged``; (len(rows), vocab)"""
+        from .paged import KV_PAGE
+        dev, H = idx.device, self.config.n_head
+        last = torch.empty((len(rows), self.config.n_embd), dtype=torch.bfloat16, device=dev)
+        plain = [i for i, p in enumerate(shared_pages) if not p]
+        if plain:
+            at = torch.tensor(plain, device=dev)
+            t = max(lens[i] for i in plain)
+            last[at] = self._prefill_paged_rows(idx[at, :t], cache, [lens[i] for i in plain], cache.table[torch.tensor([rows[i] for i in plain], device=dev)])
+        tailed = [i for i, p in enumerate(shared_pages) if p]
+        starts = [KV_PAGE * len(shared_pages[i]) for i in tailed]
+        tails = [lens[i] - s for i, s in zip(tailed, starts)]
+        for call in self._tail_calls(starts, tails, cache.max_len):
+            n, g = max(tails[k] for k in call), len(call)
+            tokens = torch.zeros((g, n), dtype=torch.int64, device=dev)          # right padding: any valid id; no real position sees it
+            for j, k in enumerate(call):
+                tokens[j, :tails[k]] = idx[tailed[k], starts[k]:starts[k] + tails[k]]
+            table = cache.table[torch.tensor([rows[tailed[k]] for k in call], device=dev)]
+            pos_rows = torch.tensor([starts[k] for k in call], dtype=torch.int32, device=dev)
+            bound = max(starts[k] for k in call)
+            ws = ops.block_extend_workspace(g, n, self.config.n_embd, H, dev)
+            x = ops.embedding_fwd(tokens, self.transformer.wte.weight)
+            for block, pool in zip(self.transformer.h, cache.layers):
+                ops.block_extend_paged(x, self._block_params(block), block.attn.rope(), H, pool, cache.n_pages, table, bound, pos_rows, ws=ws, out=x)
+            last[torch.tensor([tailed[k] for k in call], device=dev)] = x[torch.arange(g, device=dev), torch.tensor([tails[k] - 1 for k in call], device=dev)]
+        return self._readout_rows(self.transformer.ln_f(last))
 
     def _params_for(self, weights):
         """(index, block) -> the block's six parameters: the model's own, or with the four matrices dequantised from ``weights``"""
@@ -1531,7 +1600,7 @@ class OmniBioTA(nn.Module):
 
     @torch.no_grad()
     def generate_many(self, prompts, max_new_tokens, batch, n_pages=None, temperature=1.0, top_k=None, top_p=None, eos_token=None, generator=None,
-                      kv_dtype="bf16"):
+                      kv_dtype="bf16", share_prefix=False, stats=None):
         """Continuous batching: ``prompts``, a sequence of 1-D int64 tensors of any lengths, each continued by up to ``max_new_tokens``
         tokens, ``batch`` of them at a time on a ``PagedKVCache`` of ``n_pages`` pages.  Returns a list in the same order, each entry the
         prompt followed by its new tokens up to and including its first ``eos_token``, int64 on the model's device.  A row that ends —
@@ -1553,13 +1622,28 @@ class OmniBioTA(nn.Module):
         ``kv_dtype``: "bf16" or "fp8", the ``PagedKVCache`` the call builds (``PagedKVCache``: the e4m3 pool, the same pages at about half
         the bytes).  The schedule, the promise rule, the uniforms and the default ``n_pages`` do not depend on it.
 
-        Not built: speculative decoding, the device-resident loop and graph capture, pages shared between requests (a
-        common prefix is stored once per request), preemption or swapping of running requests, penalties and token restrictions, the
-        torch sampler."""
-        from .paged import PagedSchedule
+        ``share_prefix`` (bf16 only; False: nothing below happens): every admitted request is looked up in a ``paged.PrefixIndex`` kept
+        for the call — exact token content of whole 64-token pages, chained from position 0 — takes the longest chain of pages it finds,
+        names them instead of computing them (``prefill(shared_pages=)``) and computes the rest of its prompt, at least one token,
+        against them.  Its own full prompt pages are registered once its prefill is enqueued: later readers are ordered behind it on the
+        stream.  Requests admitted in the same round share too: one that has a page in common with an earlier request of the round
+        waits for that request's prefill call, so a round may make several.  A finished request's prompt pages stay findable while the
+        free list keeps them.  The promise rule is unchanged: sharing makes a request hold fewer pages than promised, never more.
+        ``share_prefix=True`` with ``kv_dtype="fp8"`` raises NotImplementedError before anything is launched.
+
+        ``stats`` (an optional dict, filled by the call): ``prefill_positions`` (prompt positions computed), ``shared_positions`` (prompt
+        positions taken from shared pages), ``peak_pages`` (the most pages in use at once) and ``decode_steps``.
+
+        Not built: speculative decoding, the device-resident loop and graph capture, sharing of generated (non-prompt) pages and
+        copy-on-write, admission that counts shared pages against the promise, preemption or swapping of running requests, penalties
+        and token restrictions, the torch sampler."""
+        from .paged import KV_PAGE, PagedSchedule, PrefixIndex
         self._check_generation("generate_many", 0)
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"OmniBioTA.generate_many: kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
+        if share_prefix and kv_dtype == "fp8":
+            raise NotImplementedError("OmniBioTA.generate_many: share_prefix=True needs kv_dtype='bf16': several new positions per row over the pages "
+                                      "of an e4m3 pool are not built")
         _check_top_p("OmniBioTA.generate_many", top_p)
         if temperature < 0:
             raise ValueError(f"OmniBioTA.generate_many: temperature must not be negative, got {temperature}")
@@ -1585,13 +1669,40 @@ class OmniBioTA(nn.Module):
         slot_req, slot_k = [R] * B, [0] * B                            # the host's account: the slot's request (R: idle) and its tokens so far
         n_new = [0] * R
         at, changed = None, True                                        # the same on the device, int64 (2, B): uploaded when a slot changes hands
+        count = dict(prefill_positions=0, shared_positions=0, peak_pages=0, decode_steps=0)
+        index = PrefixIndex(cache.book) if share_prefix else None
+        host = [p.tolist() for p in prompts] if share_prefix else None  # (the prompts' tokens on the host: what the index compares)
+
+        def prefill_round(admitted, shared=None):
+            rows = [slot for _, slot in admitted]
+            lens = [prompts[r].numel() for r, _ in admitted]
+            idx = torch.nn.utils.rnn.pad_sequence([prompts[r] for r, _ in admitted], batch_first=True)
+            more = {} if shared is None else dict(shared_pages=shared)
+            logits[torch.tensor(rows, device=dev)] = self.prefill(idx, cache, lengths=lens, rows=rows, **more)
+            taken = 0 if shared is None else KV_PAGE * sum(len(p) for p in shared)
+            count["prefill_positions"] += sum(lens) - taken
+            count["shared_positions"] += taken
+
         while not sched.done:
             admitted = sched.admit()
+            if admitted and not share_prefix:
+                prefill_round(admitted)
+            waiting = admitted if share_prefix else []
+            while waiting:                                              # one prefill call per pass: whoever shares with a request of this pass waits for the next
+                now, later, seen_now = [], [], PrefixIndex()
+                for r, slot in waiting:
+                    found = index.lookup(host[r])
+                    if len(seen_now.lookup(host[r])) > len(found):
+                        later.append((r, slot))
+                    else:
+                        now.append((r, slot, found))
+                        seen_now.register(host[r], range(len(seen_now), len(seen_now) + len(host[r]) // KV_PAGE))   # (stand-in page numbers, each once)
+                prefill_round([(r, slot) for r, slot, _ in now], [found for _, _, found in now])
+                for r, slot, _ in now:
+                    index.register(host[r], cache.book.row_pages[slot])
+                waiting = later
             if admitted:
-                rows = [slot for _, slot in admitted]
-                lens = [prompts[r].numel() for r, _ in admitted]
-                idx = torch.nn.utils.rnn.pad_sequence([prompts[r] for r, _ in admitted], batch_first=True)
-                logits[torch.tensor(rows, device=dev)] = self.prefill(idx, cache, lengths=lens, rows=rows)
+                count["peak_pages"] = max(count["peak_pages"], cache.pages_in_use)
                 for r, slot in admitted:
                     slot_req[slot], slot_k[slot] = r, 0
                 changed = True
@@ -1611,8 +1722,12 @@ class OmniBioTA(nn.Module):
                     slot_req[slot], slot_k[slot], changed = R, 0, True
             if any(r != R for r in slot_req):
                 logits = self.decode_step(nxt, cache)
+                count["decode_steps"] += 1
+                count["peak_pages"] = max(count["peak_pages"], cache.pages_in_use)
                 if not changed:
                     at[1] += at[0] < R                                  # (no slot changed hands: the running ones count on, on the device)
+        if stats is not None:
+            stats.update(count)
         return [torch.cat([p, out[r, :n_new[r]]]) for r, p in enumerate(prompts)]
 
     @torch.no_grad()

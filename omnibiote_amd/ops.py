@@ -1767,6 +1767,51 @@ def block_decode_paged(x, params, rope, H, pool, n_pages, table, pos, max_pos, w
         "obte_block_decode_paged"), rows=(pos, "pos"), at=max_pos, one=True)
 
 
+# ---- several new positions per row against the pages of a bf16 pool (include/omnibiote_hip_paged_extend.h) ----
+def kv_paged_rope_store_chunk(qkv, rope, pos, max_pos, B, n, H, hs, pool, n_pages, table):
+    """kv_cache_rope_store_chunk into pages (obte_kv_paged_rope_store_chunk): the same rotation of the packed qkv [B * n, 3C] in place, the
+    rotated k and the v of row b * n + j to slot (pos[b] + j) % 64 of page table[b, (pos[b] + j) // 64] — or nowhere, if that is no page
+    of the pool.  pos: int32 (B,) on the device; a row whose value lies outside [0, max_pos] is left alone."""
+    _need(qkv, "qkv"); _need_rows(pos, "pos", B)
+    ld = _need_paged(pool, table, B, n_pages, H, hs)
+    _need(rope[0], "rope_cos", torch.float32); _need(rope[1], "rope_sin", torch.float32)
+    assert qkv.numel() == B * n * 3 * H * hs and max_pos + n <= KV_PAGE * ld
+    assert rope[0].shape[0] >= max_pos + n and rope[1].shape[0] >= max_pos + n
+    L.check(L.lib().obte_kv_paged_rope_store_chunk(_ptr(qkv), _ptr(rope[0]), _ptr(rope[1]), _ptr(pos), int(max_pos), B, n, H, hs, _ptr(pool), n_pages,
+                                                   _ptr(table), ld, _stream()), "obte_kv_paged_rope_store_chunk")
+    return qkv
+
+
+def attn_extend_paged(q, pool, n_pages, table, B, n, pos, H, hs, scale, pos_rows, splits=0, q_ld=None, ws=None, out=None, lse=None):
+    """attn_extend's rows form over pages (obte_attn_extend_paged): n queries per (b, h) at positions pos_rows[b] .. pos_rows[b] + n - 1,
+    query j over the positions [0, pos_rows[b] + j + 1) of row b that have a page, read through table (B, table_ld) int32; bit for bit
+    attn_extend(pos_rows=) on a rectangular cache holding the same vectors.  pos: the host's bound on pos_rows (a row outside [0, pos]
+    gives zeros and lse = -inf), pos + n <= 64 * table_ld.  Returns (o (B * n, C) bf16, lse (B, H, n) fp32)."""
+    _need(q, "q", contiguous=False); _need_rows(pos_rows, "pos_rows", B)
+    ld = _need_paged(pool, table, B, n_pages, H, hs)
+    q_ld = q.shape[-1] if q_ld is None else q_ld
+    assert n >= 1 and pos + n <= KV_PAGE * ld
+    o = torch.empty((B * n, H * hs), dtype=bf16, device=q.device) if out is None else out
+    lse = torch.empty((B, H, n), dtype=torch.float32, device=q.device) if lse is None else lse
+    if ws is None:
+        ws = torch.empty(max(int(L.lib().obte_attn_extend_ws_bytes(B, H, hs, n, int(splits))), 16), dtype=torch.uint8, device=q.device)
+    L.check(L.lib().obte_attn_extend_paged(_ptr(q), q_ld, _ptr(pool), n_pages, _ptr(table), ld, _ptr(o), _ptr(lse), B, n, int(pos), _ptr(pos_rows), H, hs,
+                                           float(scale), int(splits), _ptr(ws), ws.numel(), _stream()), "obte_attn_extend_paged")
+    return o, lse
+
+
+def block_extend_paged(x, params, rope, H, pool, n_pages, table, pos, pos_rows, ws=None, out=None):
+    """block_extend's rows form on pages (obte_block_extend_paged): x (B, n, C) -> y (B, n, C), row b's positions from pos_rows[b] on
+    (int32 (B,) on the device; pos the host's bound on it, pos + n <= 64 * table_ld), stored to and read from the pages of table row b.
+    The workspace is block_extend's.  rope: the FULL tables (at least pos + n rows).  out may be x itself."""
+    B, n, Cc = x.shape
+    ld = _need_paged(pool, table, B, n_pages, H, Cc // H)
+    assert pos + n <= KV_PAGE * ld
+    return _block_call(x, params, rope, H, ws, out, block_extend_workspace, lambda d, y, w: L.check(
+        L.lib().obte_block_extend_paged(d, _ptr(x), _ptr(y), _ptr(pool), n_pages, _ptr(table), ld, int(pos), _ptr(pos_rows), _ptr(w), w.numel(), _stream()),
+        "obte_block_extend_paged"), rows=(pos_rows, "pos_rows"), at=pos)
+
+
 # ---- the pages as OCP e4m3 (include/omnibiote_hip_paged8.h; the format in plain torch: paged.py, the quantiser: kvquant.py) ----
 def kv8_paged_buffer(n_pages, H, hs, device) -> torch.Tensor:
     """One layer's e4m3 pool of ``n_pages`` pages (K codes [n_pages, H, 64, hs], V codes, K scales fp32 [n_pages, H, 64], V scales) as the

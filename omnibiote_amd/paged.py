@@ -1,6 +1,7 @@
 """The paged key/value cache's format in plain torch and its host bookkeeping (include/omnibiote_hip_paged.h): the tests' yardstick for the
 paged kernels of csrc/attention_decode.hip, as kvquant.py is for the e4m3 format, and the two host objects that decide where things go —
-``PageBook`` (which page holds which 64 positions of which row) and ``PagedSchedule`` (which request runs in which slot, and when).  No
+``PageBook`` (which page holds which 64 positions of which row, and how many rows name it), ``PrefixIndex`` (which page holds which prompt
+content) and ``PagedSchedule`` (which request runs in which slot, and when).  No
 kernel is called here and nothing needs a GPU; ``generation.PagedKVCache`` adds the buffers to a ``PageBook`` and
 ``OmniBioTA.generate_many`` drives a ``PagedSchedule``.
 
@@ -124,7 +125,13 @@ class PageBook:
     Host integers and one CPU tensor, no buffer and no device: ``PagedKVCache`` keeps the device copies in step with it.
 
     ``free_order`` (a sequence holding every page once): the order in which pages are handed out, first entry first; the default is
-    0, 1, 2, ...  A released row's pages go to the back of the list."""
+    0, 1, 2, ...  A released row's pages go to the back of the list.
+
+    Pages may be SHARED between rows (``assign_shared``): ``refs[p]`` counts the rows whose table names page p, ``release`` lowers the
+    counts and only a page that reaches zero goes back to the free list.  A page on the free list keeps its content until it is handed out
+    again — ``on_hand_out(page)``, when set, is called at that moment (``PrefixIndex`` forgets the page there) — and ``assign_shared`` may
+    name such a page: it is taken off the list again (revived).  With nothing shared every count is 0 or 1 and nothing here differs
+    from a book without counts."""
 
     def __init__(self, batch, n_pages, max_len, free_order=None):
         self.batch, self.n_pages, self.max_len = int(batch), int(n_pages), int(max_len)
@@ -138,6 +145,8 @@ class PageBook:
         self.table = torch.full((self.batch, self.table_ld), -1, dtype=torch.int32)
         self.row_pos = [-1] * self.batch          # the mirror: row b's next position, -1: parked
         self.row_pages = [[] for _ in range(self.batch)]
+        self.refs = [0] * self.n_pages            # the rows that name each page
+        self.on_hand_out = None                   # callable(page): the page leaves the free list for new content
 
     @property
     def pages_in_use(self):
@@ -166,18 +175,55 @@ class PageBook:
             raise ValueError(f"PageBook.assign: row {row} needs {more} more pages for {n_positions} positions and {len(self.free)} of {self.n_pages} are free")
         added = [self.free.pop(0) for _ in range(max(more, 0))]
         for p in added:
+            if self.on_hand_out is not None:
+                self.on_hand_out(p)
+            self.refs[p] = 1
             self.table[row, len(have)] = p
             have.append(p)
         return added
+
+    def check_shared(self, row, pages):
+        """what ``assign_shared`` refuses, as a ValueError with nothing changed; returns (row, pages) as ints"""
+        row = self._row(row)
+        pages = [int(p) for p in pages]
+        if self.row_pages[row]:
+            raise ValueError(f"PageBook.assign_shared: row {row} still holds {len(self.row_pages[row])} pages (release it first)")
+        if len(pages) > self.table_ld or len(set(pages)) != len(pages):
+            raise ValueError(f"PageBook.assign_shared: row {row}: at most {self.table_ld} distinct pages, got {pages}")
+        for p in pages:
+            if not 0 <= p < self.n_pages:
+                raise ValueError(f"PageBook.assign_shared: page {p} outside the pool's [0, {self.n_pages})")
+        return row, pages
+
+    def assign_shared(self, row, pages):
+        """Row ``row``, which must hold no page, names ``pages`` in its first ``len(pages)`` table entries; each page's count goes up by
+        one.  A named page that is on the free list is taken off it: a released page whose content is still valid is revived (nothing is
+        told to ``on_hand_out``: the content stays).  ValueError with nothing changed for a row that holds pages or a page outside the
+        pool.  Returns the pages revived."""
+        row, pages = self.check_shared(row, pages)
+        revived = [p for p in pages if self.refs[p] == 0]
+        for p in revived:
+            self.free.remove(p)
+        for j, p in enumerate(pages):
+            self.refs[p] += 1
+            self.table[row, j] = p
+        self.row_pages[row] = list(pages)
+        return revived
 
     def place(self, row, position):
         """the mirror's writer: row ``row`` stands at ``position`` (-1: parked)"""
         self.row_pos[self._row(row)] = int(position)
 
     def release(self, row):
-        """Row ``row`` gives its pages back, its table entries are cleared and it is parked.  Returns the pages."""
+        """Row ``row`` gives its pages back, its table entries are cleared and it is parked.  A page another row still names stays in
+        use; the others go to the back of the free list.  Returns the pages that did."""
         row = self._row(row)
-        pages, self.row_pages[row] = self.row_pages[row], []
+        held, self.row_pages[row] = self.row_pages[row], []
+        pages = []
+        for p in held:
+            self.refs[p] -= 1
+            if self.refs[p] == 0:
+                pages.append(p)
         self.free.extend(pages)
         self.table[row].fill_(-1)
         self.row_pos[row] = -1
@@ -205,6 +251,66 @@ class PageBook:
     def step(self):
         """after a decode step: every active row has one more position"""
         self.row_pos = [p + 1 if p >= 0 else p for p in self.row_pos]
+
+
+class PrefixIndex:
+    """Which page of a pool holds which 64 prompt tokens behind which earlier ones: what lets a request reuse the pages another request
+    has filled.  A node is one page; its key is (the node of the page before it — 0 at position 0 —, the page's 64 tokens as a tuple), so a
+    match compares the exact token content of whole pages, chained from position 0, and never a bare hash.  Pure host, no tensors.
+
+    ``register(tokens, pages)`` records the ``len(tokens) // 64`` pages that prompt tokens cover completely, ``pages[j]`` holding tokens
+    [64 j, 64 j + 64) (a chain that is recorded already keeps its page).  ``lookup(tokens)`` returns the longest recorded chain of pages
+    for ``tokens``, at most ``(len(tokens) - 1) // 64`` of them: at least one token is always left to compute, because the first new token
+    needs logits.  ``forget(page)`` drops a page; a chain through it ends before it (what lay behind becomes unreachable, and is dropped as
+    its own pages are forgotten).  With ``book`` given the index makes itself the book's ``on_hand_out``: a page leaves the index when the
+    ``PageBook`` hands it out again from the free list, so a released page stays findable for as long as the free list keeps it — first
+    in, first out keeps it longest."""
+
+    def __init__(self, book=None):
+        self.nodes = {}        # (parent node, 64 tokens) -> (node, page)
+        self.key_of = {}       # page -> its key
+        self.next_node = 1     # (0: the root)
+        if book is not None:
+            book.on_hand_out = self.forget
+
+    @staticmethod
+    def _tokens(tokens):
+        return [int(t) for t in (tokens.tolist() if isinstance(tokens, torch.Tensor) else tokens)]
+
+    def register(self, tokens, pages):
+        tokens = self._tokens(tokens)
+        full = len(tokens) // KV_PAGE
+        if len(pages) < full:
+            raise ValueError(f"PrefixIndex.register: {len(tokens)} tokens cover {full} pages and {len(pages)} are given")
+        parent = 0
+        for j in range(full):
+            key = (parent, tuple(tokens[KV_PAGE * j:KV_PAGE * j + KV_PAGE]))
+            if key not in self.nodes:
+                page = int(pages[j])
+                self.forget(page)                                      # (a page holds one content)
+                self.nodes[key] = (self.next_node, page)
+                self.key_of[page] = key
+                self.next_node += 1
+            parent = self.nodes[key][0]
+
+    def lookup(self, tokens):
+        tokens = self._tokens(tokens)
+        parent, pages = 0, []
+        for j in range((len(tokens) - 1) // KV_PAGE if tokens else 0):
+            hit = self.nodes.get((parent, tuple(tokens[KV_PAGE * j:KV_PAGE * j + KV_PAGE])))
+            if hit is None:
+                break
+            parent = hit[0]
+            pages.append(hit[1])
+        return pages
+
+    def forget(self, page):
+        key = self.key_of.pop(int(page), None)
+        if key is not None:
+            del self.nodes[key]
+
+    def __len__(self):
+        return len(self.nodes)
 
 
 class PagedSchedule:

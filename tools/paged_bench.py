@@ -23,7 +23,16 @@ warm-up; median and [min - max] over the rounds.  One JSON line per measurement.
               step        decode_step on PagedKVCache(dtype="fp8") against KVCache(dtype="fp8") in rows mode and against the bf16 pool;
               workload    the same prompts also through generate_many(kv_dtype="fp8") at the default page count.
 
-    python tools/paged_bench.py [--kv8] [--parts attention,step,workload] [--rounds 5] [--steps 200]
+  --share     prompt pages shared between requests (include/omnibiote_hip_paged_extend.h), instead of the parts above:
+              extend      obte_attn_extend_paged, the pool's pages in random order, against obte_attn_extend's rows form on a rectangle holding
+                          the same keys, every row's n new positions behind ctx - n cached ones, at B x ctx in {8 x 2048, 64 x 2048} and
+                          n in {32, 64}, each call on the next layer's cache;
+              sharing     a seeded workload of --prompts prompts, each one of 4 prefixes of 512 tokens followed by a tail of 16 .. 256
+                          tokens of its own, 128 new tokens, batch 64, no eos_token: generate_many(share_prefix=True) against
+                          share_prefix=False — tokens per second of wall time, and from `stats` the prompt positions computed, the
+                          pages in use at the peak and the decode steps.
+
+    python tools/paged_bench.py [--kv8 | --share] [--parts attention,step,workload] [--rounds 5] [--steps 200]
 """
 import argparse
 import contextlib
@@ -255,6 +264,95 @@ def step(m, B, ctx, rounds, steps, dev):
             "paged_minus_rows_us_and_spreads": _gap(us, "paged", "rows", 1), "tokens_per_s": {k: round(B / med[k] * 1e6) for k in legs}}
 
 
+def extend_attention(m, B, ctx, n, rounds, steps, dev):
+    """--share: n queries per row behind ctx - n cached positions, through the page table and on the rectangle, alternating in one process"""
+    from omnibiote_amd import _lib, ops
+    from omnibiote_amd.paged import paged_scatter_reference
+    lib = _lib.lib()
+    H, C = m.config.n_head, m.config.n_embd
+    hs, n_layer, n_pages, ld = C // H, m.config.n_layer, B * ctx // 64, ctx // 64
+    gen = torch.Generator(device=dev).manual_seed(B * 10007 + ctx + n)
+    table = torch.randperm(n_pages, device=dev, generator=gen).view(B, ld).to(torch.int32)
+    rects, pools = [], []
+    for _ in range(n_layer):
+        rect = ops.kv_cache_buffer(B, ctx, H, hs, dev).normal_(generator=gen)
+        K, V = rect.view(2, B, H, ctx, hs)
+        rects.append(rect)
+        pools.append(paged_scatter_reference(K, V, table, n_pages))
+    q = torch.randn(B * n, 3 * C, device=dev, generator=gen).to(torch.bfloat16)
+    pos = ctx - n
+    starts = torch.full((B,), pos, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(lib.obte_attn_extend_ws_bytes(B, H, hs, n, 0)), 16), dtype=torch.uint8, device=dev)
+    o = torch.empty(B * n, C, device=dev, dtype=torch.bfloat16)
+    lse = torch.empty(B, H, n, device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream().cuda_stream
+    state = {"i": 0}
+
+    def rows():
+        state["i"] += 1
+        rc = lib.obte_attn_extend(q.data_ptr(), 3 * C, rects[state["i"] % n_layer].data_ptr(), o.data_ptr(), lse.data_ptr(), B, ctx, n, pos, starts.data_ptr(), H, hs,
+                                  8.0 / C, 0, ws.data_ptr(), ws.numel(), stream)
+        if rc != 0:
+            _lib.check(rc, "obte_attn_extend")
+
+    def paged():
+        state["i"] += 1
+        rc = lib.obte_attn_extend_paged(q.data_ptr(), 3 * C, pools[state["i"] % n_layer].data_ptr(), n_pages, table.data_ptr(), ld, o.data_ptr(), lse.data_ptr(), B, n,
+                                        pos, starts.data_ptr(), H, hs, 8.0 / C, 0, ws.data_ptr(), ws.numel(), stream)
+        if rc != 0:
+            _lib.check(rc, "obte_attn_extend_paged")
+    a, _ = ops.attn_extend(q, rects[0], B, ctx, n, pos, H, hs, 8.0 / C, pos_rows=starts)
+    b, _ = ops.attn_extend_paged(q, pools[0], n_pages, table, B, n, pos, H, hs, 8.0 / C, starts)
+    legs = {"rows": rows, "paged": paged}
+    for fn in legs.values():
+        for _ in range(8):
+            fn()
+    us = {k: [] for k in legs}
+    for r in range(rounds):
+        for k in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            us[k].append(timed(legs[k], steps))
+    nbytes, set_bytes = 4 * B * H * ctx * hs * ((n + 31) // 32), sum(t.numel() * 2 for t in rects)
+    med = {k: statistics.median(v) for k, v in us.items()}
+    return {"part": "extend", "B": B, "context": ctx, "n_new": n, "windows": {"calls": steps, "rounds": rounds}, "same_bits": bool(torch.equal(a, b)),
+            "splits": int(lib.obte_attn_extend_splits(B, H, hs, n, ctx)), "bytes_read_per_call_at_most": nbytes, "set_bytes": set_bytes,
+            "served_from": "HBM" if set_bytes > INFINITY_CACHE else "Infinity Cache (not an HBM measurement)",
+            "us": {k: summary(v) for k, v in us.items()}, "paged_over_rows": round(med["paged"] / med["rows"], 4),
+            "paged_minus_rows_us_and_spreads": _gap(us, "paged", "rows")}
+
+
+def sharing(n_prompts, vocab, rounds, dev):
+    """--share: generate_many with and without share_prefix over prompts that carry one of 4 prefixes of 512 tokens"""
+    new, batch, n_prefix, prefix_len = 128, 64, 4, 512
+    m = build_small_vocab(prefix_len + 256 + new, vocab, dev)
+    g = torch.Generator().manual_seed(17)
+    prefixes = [torch.randint(8, vocab, (prefix_len,), generator=g) for _ in range(n_prefix)]
+    tails = torch.randint(16, 257, (n_prompts,), generator=g).tolist()
+    which = torch.randint(0, n_prefix, (n_prompts,), generator=g).tolist()
+    prompts = [torch.cat([prefixes[w], torch.randint(8, vocab, (t,), generator=g)]).to(dev) for w, t in zip(which, tails)]
+    legs = {"share_prefix_false": False, "share_prefix_true": True}
+    res = {k: {"tokens_per_s": [], "wall_s": []} for k in legs}
+    for r in range(rounds + 1):                                         # (round 0 warms up)
+        for k in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
+            stats = {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = m.generate_many(prompts, new, batch, generator=torch.Generator(device=dev).manual_seed(3), share_prefix=legs[k], stats=stats)
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            if r == 0:
+                res[k].update(new_tokens=sum(o.numel() - p.numel() for o, p in zip(out, prompts)), **stats)
+                continue
+            res[k]["tokens_per_s"].append(res[k]["new_tokens"] / wall)
+            res[k]["wall_s"].append(wall)
+    base = statistics.median(res["share_prefix_false"]["tokens_per_s"])
+    spreads = [round(max(res[k]["tokens_per_s"]) - min(res[k]["tokens_per_s"])) for k in legs]
+    for v in res.values():
+        v["over_share_prefix_false"] = round(statistics.median(v["tokens_per_s"]) / base, 3)
+        v["tokens_per_s"], v["wall_s"] = summary(v["tokens_per_s"], 0), summary(v["wall_s"], 3)
+    return {"part": "sharing", "prompts": n_prompts, "prefixes": n_prefix, "prefix_tokens": prefix_len, "tails": [min(tails), max(tails)], "max_new_tokens": new,
+            "batch": batch, "vocab": vocab, "rounds": rounds, "tokens_per_s_spreads": spreads, **res}
+
+
 def build_small_vocab(block_size, vocab, dev):
     """decode_bench.build's model with another vocabulary (the workload: see the head of this file)"""
     import warnings
@@ -347,10 +445,24 @@ def main():
     p.add_argument("--vocab", type=int, default=256)
     p.add_argument("--pool-share", type=float, default=0.65)
     p.add_argument("--kv8", action="store_true", help="the e4m3 pool: see the head of this file")
+    p.add_argument("--share", action="store_true", help="prompt pages shared between requests (parts extend,sharing): see the head of this file")
     a = p.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     parts = a.parts.split(",")
+    if a.share:
+        parts = ["extend", "sharing"] if a.parts == p.get_default("parts") else parts
+        if "extend" in parts:
+            m = build(2048, dev)
+            for B, ctx in ((8, 2048), (64, 2048)):
+                for n in (32, 64):
+                    print(json.dumps(extend_attention(m, B, ctx, n, a.rounds, a.steps, dev)), flush=True)
+                    torch.cuda.empty_cache()
+            del m
+            torch.cuda.empty_cache()
+        if "sharing" in parts:
+            print(json.dumps(sharing(a.prompts, a.vocab, a.rounds, dev)), flush=True)
+        return
     if "attention" in parts or "step" in parts:
         m = build(2048, dev)
         for B, ctx in ((64, 2048), (8, 2048)):
