@@ -349,6 +349,22 @@ SYMBOLS_PAGED_EXTEND = {
                                           C.c_int64, c_stream]),
 }
 
+# attention maps, the softmax weights of one layer as a tensor (include/omnibiote_hip_probs.h): a table of its own as well, and the one
+# aggregate type obte_struct_sizes does not list (lib() checks its size against obte_attn_probs_args_bytes)
+class AttnProbsArgs(C.Structure):
+    _fields_ = [("qkv", C.c_void_p), ("key_ranges", C.c_void_p), ("mask", C.c_void_p),
+                ("mask_sb", C.c_int64), ("mask_sh", C.c_int64), ("mask_sq", C.c_int64), ("ranges_exact", C.c_void_p),
+                ("B", C.c_int64), ("T", C.c_int64), ("n_head", C.c_int32), ("head_dim", C.c_int32), ("scale", C.c_float),
+                ("out", C.c_void_p), ("out_sb", C.c_int64), ("out_bf16", C.c_int32), ("head_mean", C.c_int32),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
+SYMBOLS_PROBS = {
+    "obte_attn_probs_args_bytes": (C.c_int64, []),
+    "obte_attn_probs_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "obte_attn_probs": (C.c_int, [C.POINTER(AttnProbsArgs), c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -381,7 +397,8 @@ def lib():
                                             + list(SYMBOLS_SHARED.items()) + list(SYMBOLS_LOOP.items()) + list(SYMBOLS_CONSTRAIN.items())
                                             + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items()) + list(SYMBOLS_PENALTY.items())
                                             + list(SYMBOLS_DISTILL.items()) + list(SYMBOLS_BEAM.items()) + list(SYMBOLS_PAGED.items())
-                                            + list(SYMBOLS_PAGED8.items()) + list(SYMBOLS_W4.items()) + list(SYMBOLS_PAGED_EXTEND.items())):
+                                            + list(SYMBOLS_PAGED8.items()) + list(SYMBOLS_W4.items()) + list(SYMBOLS_PAGED_EXTEND.items())
+                                            + list(SYMBOLS_PROBS.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:
@@ -393,6 +410,9 @@ def lib():
             mine = [C.sizeof(GemmArgs), C.sizeof(AttnFwdArgs), C.sizeof(AttnBwdArgs), C.sizeof(MtArgs), C.sizeof(BlockDesc), C.sizeof(MtMasterArgs)]
             if n != len(mine) or list(sizes[:n]) != mine:
                 raise HipLibraryError(f"struct layout mismatch between _lib.py {mine} and {LIB_PATH} {list(sizes[:n])}")
+            if l.obte_attn_probs_args_bytes() != C.sizeof(AttnProbsArgs):
+                raise HipLibraryError(f"struct layout mismatch between _lib.py AttnProbsArgs ({C.sizeof(AttnProbsArgs)}) and {LIB_PATH} "
+                                      f"({l.obte_attn_probs_args_bytes()})")
             _lib = l
     return _lib
 

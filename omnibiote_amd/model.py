@@ -27,6 +27,7 @@ Contract notes (each mirrors a reference behaviour):
 from __future__ import annotations
 
 import math
+import operator
 import warnings
 import weakref
 from dataclasses import dataclass
@@ -886,6 +887,74 @@ class OmniBioTA(nn.Module):
                 m.training = was
         alpha = float(self.lm_head.output_mult) / float(self.lm_head.width_mult())
         return ops.readout_score(emb, self.lm_head.weight, candidates, alpha=alpha)[0]
+
+    # ---- attention maps: what a forward hook on the reference's attn_dropout sees with flash=False ------------------------------------------
+    @torch.no_grad()
+    def attention_maps(self, idx, attn_mask=None, layers=None, heads="all", dtype=torch.float32):
+        """The softmax weights of the attention of chosen layers: (B, len(layers), n_head, T, T), or (B, len(layers), T, T) with
+        ``heads="mean"`` (the heads' mean, summed in fp32), as ``dtype`` (torch.float32, or torch.bfloat16: the rounded fp32 value).
+        ``layers``: ascending distinct block indices in [0, n_layer), None for all.  ``attn_mask`` as in ``forward`` (None, the
+        reference's additive tensor, a ``masks.RangeMask``; an autoregressive model is causal without one).  The hidden states are
+        those of ``model(idx, attn_mask)`` without a gradient: the blocks run as ``forward`` runs them, up to the last requested layer
+        and no further.  For a requested layer the packed, rotated qkv is formed from the block's input by ``ops.layernorm_fwd`` and
+        the c_attn product with its RoPE epilogue — before the block runs, which may write its output over its input — and
+        ``ops.attn_probs`` writes that layer's slice of the result, allocated once.  The rule: attnmaps.attention_probs_reference.
+        No gradient, and no dropout whatever ``self.training`` says.  Argument errors are ValueError, raised before anything is launched."""
+        n_layer = len(self.transformer.h)
+        if layers is None:
+            layers = list(range(n_layer))
+        else:
+            try:
+                layers = [operator.index(v) for v in layers]
+            except TypeError:
+                layers = []
+            if not layers:
+                raise ValueError("OmniBioTA.attention_maps: layers must be a non-empty sequence of ints, or None for every layer")
+            if any(not 0 <= v < n_layer for v in layers):
+                raise ValueError(f"OmniBioTA.attention_maps: layers must lie in [0, {n_layer}), got {layers}")
+            if any(b <= a for a, b in zip(layers, layers[1:])):
+                raise ValueError(f"OmniBioTA.attention_maps: layers must be ascending and distinct, got {layers}")
+        if not layers:
+            raise ValueError("OmniBioTA.attention_maps: the model has no block")
+        if not isinstance(heads, str) or heads not in ("all", "mean"):
+            raise ValueError(f"OmniBioTA.attention_maps: heads must be \"all\" or \"mean\", got {heads!r}")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"OmniBioTA.attention_maps: dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+        if not torch.is_tensor(idx) or idx.dim() != 2 or idx.dtype != torch.int64:
+            raise ValueError("OmniBioTA.attention_maps: idx must be a (b, t) int64 tensor")
+        b, t = idx.shape
+        if not 1 <= t <= self.config.block_size or b < 1:
+            raise ValueError(f"OmniBioTA.attention_maps: idx is {tuple(idx.shape)}, the block size is {self.config.block_size}")
+        wte = self.transformer.wte.weight
+        _require_hip(wte, "OmniBioTA.attention_maps")
+        if not idx.is_cuda:
+            raise RuntimeError("OmniBioTA.attention_maps: idx must be on the GPU")
+        H, C = self.config.n_head, self.config.n_embd
+        hs = C // H
+        modes = [(m, m.training) for m in self.modules()]
+        try:
+            self.eval()
+            attn_mask = _autoregressive_mask(self.config.autoregressive, attn_mask, b, t, idx.device)
+            mask = ops.MaskSpec.from_user(attn_mask, b, t, H, idx.device)
+            x = _EmbeddingFn.apply(idx, wte, 0.0, 0, None)
+            out = torch.empty((b, len(layers)) + ((t, t) if heads == "mean" else (H, t, t)), dtype=dtype, device=idx.device)
+            ws = ops.attn_probs_workspace(b, t, H, idx.device)
+            handoff = _GradHandOff()
+            infer = [None]
+            slot = {layer: j for j, layer in enumerate(layers)}
+            for i, block in enumerate(self.transformer.h):
+                if i in slot:
+                    h1 = ops.layernorm_fwd(x.contiguous(), block.ln_1.weight)[0]
+                    cos, sin = block.attn.rope()
+                    qkv = ops.gemm(h1.view(b * t, C), block.attn.c_attn.weight, b * t, 3 * C, C, epilogue=L.EPI_ROPE_QK, rope=(cos, sin, t, hs))
+                    ops.attn_probs(qkv, b, t, H, hs, 8.0 / C, mask, heads=heads, dtype=dtype, out=out[:, slot[i]], ws=ws)
+                if i == layers[-1]:
+                    break
+                x = block(x, attn_mask=mask, handoff=handoff, index=i, infer=infer)
+        finally:
+            for m, was in modes:
+                m.training = was
+        return out
 
     @torch.no_grad()
     def score(self, idx, lengths=None):

@@ -752,6 +752,41 @@ def attn_bwd(qkv, o, d_o, lse, B, T, H, hs, scale, mask: Optional[MaskSpec] = No
     return dqkv
 
 
+def attn_probs_workspace(B, T, H, device) -> torch.Tensor:
+    """The (m, l) pairs of ``attn_probs``: 8 * B * H * T bytes, contents irrelevant before and after; one buffer serves every layer."""
+    return torch.empty(int(L.lib().obte_attn_probs_ws_bytes(B, T, H)), dtype=torch.uint8, device=device)
+
+
+def attn_probs(qkv, B, T, H, hs, scale, mask: Optional[MaskSpec] = None, heads="all", dtype=torch.float32, out=None, ws=None):
+    """The softmax weights of the attention ``attn_fwd`` runs on the same operands (include/omnibiote_hip_probs.h; the rule:
+    attnmaps.attention_probs_reference in fp32): (B, H, T, T), or (B, T, T) with ``heads="mean"`` — the heads' mean, summed in fp32
+    in ascending order; fp32 or bf16 (the rounded fp32 value).  ``out``: a tensor of that shape and dtype whose dimensions after
+    the first are contiguous; its batch stride may be larger than the payload (one layer's slice of a larger tensor), nothing
+    between the batch rows is touched.  ``ws``: ``attn_probs_workspace(B, T, H, device)``."""
+    if not isinstance(heads, str) or heads not in ("all", "mean"):
+        raise ValueError(f"attn_probs: heads must be \"all\" or \"mean\", got {heads!r}")
+    if dtype not in (torch.float32, bf16):
+        raise ValueError(f"attn_probs: dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+    _need(qkv, "qkv"); assert qkv.numel() == B * T * 3 * H * hs
+    mask = mask or MaskSpec()
+    mean = heads == "mean"
+    shape = (B, T, T) if mean else (B, H, T, T)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=qkv.device)
+    _need(out, "out", dtype, contiguous=False)
+    if tuple(out.shape) != shape or (B > 0 and not out[0].is_contiguous()):
+        raise RuntimeError(f"attn_probs: out must be {shape} with every dimension after the first contiguous, got {tuple(out.shape)} "
+                           f"with strides {out.stride()}")
+    need = int(L.lib().obte_attn_probs_ws_bytes(B, T, H))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)
+    _need(ws, "ws", torch.uint8)
+    a = L.AttnProbsArgs(_ptr(qkv), _ptr(mask.ranges), _ptr(mask.dense), mask.sb, mask.sh, mask.sq, _ptr(mask.exact), B, T, H, hs, float(scale),
+                        _ptr(out), out.stride(0) if B > 1 else out[0].numel(), int(dtype == bf16), int(mean), _ptr(ws), ws.numel())
+    L.check(L.lib().obte_attn_probs(C.byref(a), _stream()), "obte_attn_probs")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- embedding
 def embedding_fwd(idx, wte, dropout_p=0.0, dropout_seed=0):
     _need(idx, "idx", torch.int64); _need(wte, "wte")
