@@ -365,6 +365,17 @@ SYMBOLS_PROBS = {
     "obte_attn_probs": (C.c_int, [C.POINTER(AttnProbsArgs), c_stream]),
 }
 
+# speculative decoding without a draft model, the n-gram lookup draft and the verification of a drafted token (include/omnibiote_hip_lookup.h):
+# a table of its own as well
+LOOKUP_MAX_HISTORY, LOOKUP_MAX_NGRAM = 8192, 16           # OBTE_LOOKUP_MAX_HISTORY, OBTE_LOOKUP_MAX_NGRAM
+SYMBOLS_LOOKUP = {
+    "obte_lookup_draft": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                    c_stream]),
+    "obte_spec_verify_point_ws_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "obte_spec_verify_point_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
+                                              C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -398,7 +409,7 @@ def lib():
                                             + list(SYMBOLS_W8.items()) + list(SYMBOLS_SCORE.items()) + list(SYMBOLS_FILL.items()) + list(SYMBOLS_PENALTY.items())
                                             + list(SYMBOLS_DISTILL.items()) + list(SYMBOLS_BEAM.items()) + list(SYMBOLS_PAGED.items())
                                             + list(SYMBOLS_PAGED8.items()) + list(SYMBOLS_W4.items()) + list(SYMBOLS_PAGED_EXTEND.items())
-                                            + list(SYMBOLS_PROBS.items())):
+                                            + list(SYMBOLS_PROBS.items()) + list(SYMBOLS_LOOKUP.items())):
                 try:
                     fn = getattr(l, name)
                 except AttributeError as e:

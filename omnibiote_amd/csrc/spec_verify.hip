@@ -6,7 +6,12 @@
 //            draws in integer prefix sums as the sampler does: per-wave totals -> the wave that holds the target -> one wave scan per
 //            group of chunks -> the lane walks its 8 columns.
 // CON: the restricted form (include/omnibiote_hip_constrain.h) — both launches clear the excluded keys of p[b, j] and q[b, j] as they load them.
+// PT: the point form (include/omnibiote_hip_lookup.h) — the draft of position j is the token draft[b, j] itself and no q exists.  What the
+// other form computes of the row that is 0 at x and -inf elsewhere is known without reading it — total 2^40, x's weight 2^40, every
+// other column's 0, and nothing at all for an x outside [0, V) — so `rows` runs over p's k + 1 rows only and `decide` puts those
+// integers where it would have loaded them.
 #include "sample_common.h"
+#include "../../include/omnibiote_hip_lookup.h"
 
 namespace {
 
@@ -48,7 +53,7 @@ __device__ __forceinline__ const bf16* sv_row(const SpecParams& a, int64_t b, in
     return a.q + (b * a.k + j) * a.ld_q;
 }
 
-template <int NT, int R, bool CON>
+template <int NT, int R, bool CON, bool PT>
 __global__ __launch_bounds__(NT) void spec_rows_kernel(SpecParams a) {
     __shared__ u64 hist[SP_BINS];
     __shared__ u64 hist2[16];
@@ -56,7 +61,7 @@ __global__ __launch_bounds__(NT) void spec_rows_kernel(SpecParams a) {
     __shared__ u64 red_n[NT / 64];
     __shared__ u64 sel[2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = a.greedy ? a.k + 1 : 2 * a.k + 1;
+    const int per = a.greedy || PT ? a.k + 1 : 2 * a.k + 1;
     const int64_t b = blockIdx.x / per;
     const int r = (int)(blockIdx.x % per);
     int j;
@@ -148,10 +153,11 @@ struct SvSide {        // one logits row as the draw reads it
     SpRowMask rm;      // (CON only)
     uint32_t maxkey, thr;
     float maxv;
+    int point;         // (PT only, the draft's side) the one column of weight 2^40
 };
 
 // the weights of chunk c's 8 columns: the kept entries' fixed-point weights of `P`, or with RES the residual against `Q`
-template <bool RES, bool CON>
+template <bool RES, bool CON, bool PT>
 __device__ __forceinline__ void sv_chunk(const SvSide& P, const SvSide& Q, int c, int nch, int V, float scale, u64 tp, u64 tq, int S, u64 (&w)[8]) {
     uint32_t kp[4], kq[4] = {0u, 0u, 0u, 0u};
     if (CON) {   // P and Q are rows of one drafted position: one restriction
@@ -160,7 +166,7 @@ __device__ __forceinline__ void sv_chunk(const SvSide& P, const SvSide& Q, int c
         if (RES) sp_load_chunk_masked(Q.x, c, nch, V, bits, kq);
     } else {
         sp_load_chunk(P.x, c, nch, V, kp);
-        if (RES) sp_load_chunk(Q.x, c, nch, V, kq);
+        if (RES && !PT) sp_load_chunk(Q.x, c, nch, V, kq);
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -168,7 +174,7 @@ __device__ __forceinline__ void sv_chunk(const SvSide& P, const SvSide& Q, int c
         const u64 wp = a >= P.thr ? sp_weight(a, P.maxkey, P.maxv, scale) : 0ull;
         if (RES) {
             const uint32_t bq = (i & 1) ? kq[i >> 1] >> 16 : kq[i >> 1] & 0xFFFFu;
-            const u64 wq = bq >= Q.thr ? sp_weight(bq, Q.maxkey, Q.maxv, scale) : 0ull;
+            const u64 wq = PT ? (c * 8 + i == Q.point ? SP_ONE : 0ull) : bq >= Q.thr ? sp_weight(bq, Q.maxkey, Q.maxv, scale) : 0ull;
             w[i] = sv_residual(wp, tq, wq, tp, S);
         } else {
             w[i] = wp;
@@ -178,7 +184,7 @@ __device__ __forceinline__ void sv_chunk(const SvSide& P, const SvSide& Q, int c
 
 // The draw over the row's V entries in index order, weights by sv_chunk<RES>: wave w owns chunks [w R 64, (w + 1) R 64), group g of them
 // holds chunk (w R + g) 64 + lane.  Returns the row's total; with `find` (total > 0) the lane that holds the target writes the token.
-template <int NT, bool RES, bool CON>
+template <int NT, bool RES, bool CON, bool PT>
 __device__ __forceinline__ u64 sv_draw(const SvSide& P, const SvSide& Q, int V, float scale, u64 tp, u64 tq, int S, float u, bool find, int fallback,
                                        int64_t* token, u64* red) {
     constexpr int NW = NT / 64;
@@ -189,7 +195,7 @@ __device__ __forceinline__ u64 sv_draw(const SvSide& P, const SvSide& Q, int V, 
     u64 w[8];
     u64 mass = 0;
     for (int g = 0; g < R; ++g) {
-        sv_chunk<RES, CON>(P, Q, chunk0 + g * 64, nch, V, scale, tp, tq, S, w);
+        sv_chunk<RES, CON, PT>(P, Q, chunk0 + g * 64, nch, V, scale, tp, tq, S, w);
 #pragma unroll
         for (int i = 0; i < 8; ++i) mass += w[i];
     }
@@ -211,7 +217,7 @@ __device__ __forceinline__ u64 sv_draw(const SvSide& P, const SvSide& Q, int V, 
     u64 run = base;
     for (int g = 0; g < R; ++g) {
         const int c = chunk0 + g * 64;
-        sv_chunk<RES, CON>(P, Q, c, nch, V, scale, tp, tq, S, w);
+        sv_chunk<RES, CON, PT>(P, Q, c, nch, V, scale, tp, tq, S, w);
         u64 sj = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) sj += w[i];
@@ -236,13 +242,13 @@ __device__ __forceinline__ u64 sv_draw(const SvSide& P, const SvSide& Q, int V, 
     return total;
 }
 
-template <int NT, bool CON>
+template <int NT, bool CON, bool PT>
 __global__ __launch_bounds__(NT) void spec_decide_kernel(SpecParams a) {
     __shared__ u64 red[NT / 64];
     __shared__ int sh_a;
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
-    const int k = a.k, per = a.greedy ? k + 1 : 2 * k + 1;
+    const int k = a.k, per = a.greedy || PT ? k + 1 : 2 * k + 1;
     const SpecRow* rows = a.rows + b * per;
     if (tid == 0) {
         int n = 0;
@@ -253,8 +259,12 @@ __global__ __launch_bounds__(NT) void spec_decide_kernel(SpecParams a) {
                 if (a.draft[b * k + n] != want) break;
                 continue;
             }
-            const SpecRow rq = rows[k + 1 + n];
             if (rp.wx == 0) break;                       // P(x) = 0 never stands
+            if (PT) {                                    // (x is inside [0, V): Q(x) = 2^40 / 2^40)
+                if (!sv_accept(a.u_accept[b * k + n], rp.wx, rp.total, SP_ONE, SP_ONE)) break;
+                continue;
+            }
+            const SpecRow rq = rows[k + 1 + n];
             if (rq.wx == 0) continue;                    // Q(x) = 0 < P(x) stands
             if (!sv_accept(a.u_accept[b * k + n], rp.wx, rp.total, rq.wx, rq.total)) break;
         }
@@ -274,42 +284,52 @@ __global__ __launch_bounds__(NT) void spec_decide_kernel(SpecParams a) {
     SvSide P, Q;
     P.x = sv_row(a, b, n, unused); P.maxkey = maxkey; P.thr = rp.thr; P.maxv = sp_val(maxkey);
     P.rm = CON ? sp_row_mask(a.con, b, n) : SpRowMask{nullptr, -1};
+    P.point = -1;
     Q = P;
     const float u = a.u_draw[b];
     const u64 tp = rp.total;
-    if (n < k) {
+    if (PT) {
+        if (n < k) {
+            const int64_t t = a.draft[b * k + n];
+            if (t >= 0 && t < a.V) {     // (any other value: the draft row holds nothing, the residual is P)
+                Q.point = (int)t;
+                const int S = sv_bits(tp) + sv_bits(SP_ONE) - 62;
+                if (sv_draw<NT, true, CON, true>(P, Q, a.V, a.scale, tp, SP_ONE, S, u, true, argmax, a.token + b, red) > 0) return;
+            }
+        }
+    } else if (n < k) {
         const SpecRow rq = rows[k + 1 + n];
         if (rq.total > 0) {          // (0: the draft row holds nothing to sample: Q = 0 everywhere, the residual is P)
             Q.x = sv_row(a, b, k + 1 + n, unused); Q.maxkey = rq.best >> 16; Q.thr = rq.thr; Q.maxv = sp_val(Q.maxkey);
             const int S = sv_bits(tp) + sv_bits(rq.total) - 62;
-            if (sv_draw<NT, true, CON>(P, Q, a.V, a.scale, tp, rq.total, S, u, true, argmax, a.token + b, red) > 0) return;
+            if (sv_draw<NT, true, CON, false>(P, Q, a.V, a.scale, tp, rq.total, S, u, true, argmax, a.token + b, red) > 0) return;
         }
     }
-    sv_draw<NT, false, CON>(P, P, a.V, a.scale, tp, 0, 0, u, true, argmax, a.token + b, red);
+    sv_draw<NT, false, CON, false>(P, P, a.V, a.scale, tp, 0, 0, u, true, argmax, a.token + b, red);
 }
 
 int64_t rows_of(int64_t B, int64_t k, bool greedy) { return B * (greedy ? k + 1 : 2 * k + 1); }
 
-template <bool CON>
+template <bool CON, bool PT>
 void spec_launch(const SpecParams& a, int64_t B, int64_t k, int64_t V, bool greedy, hipStream_t st) {
-    const dim3 grid((unsigned)rows_of(B, k, greedy)), gridb((unsigned)B);
+    const dim3 grid((unsigned)rows_of(B, k, greedy || PT)), gridb((unsigned)B);
     if (V <= 256 * 8) {
-        hipLaunchKernelGGL((spec_rows_kernel<256, 1, CON>), grid, dim3(256), 0, st, a);
-        hipLaunchKernelGGL((spec_decide_kernel<256, CON>), gridb, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((spec_rows_kernel<256, 1, CON, PT>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((spec_decide_kernel<256, CON, PT>), gridb, dim3(256), 0, st, a);
     } else {
-        if (V <= 1024 * 8 * 2) hipLaunchKernelGGL((spec_rows_kernel<1024, 2, CON>), grid, dim3(1024), 0, st, a);
-        else hipLaunchKernelGGL((spec_rows_kernel<1024, 8, CON>), grid, dim3(1024), 0, st, a);
-        hipLaunchKernelGGL((spec_decide_kernel<1024, CON>), gridb, dim3(1024), 0, st, a);
+        if (V <= 1024 * 8 * 2) hipLaunchKernelGGL((spec_rows_kernel<1024, 2, CON, PT>), grid, dim3(1024), 0, st, a);
+        else hipLaunchKernelGGL((spec_rows_kernel<1024, 8, CON, PT>), grid, dim3(1024), 0, st, a);
+        hipLaunchKernelGGL((spec_decide_kernel<1024, CON, PT>), gridb, dim3(1024), 0, st, a);
     }
 }
 
-int64_t ws_bytes_of(int64_t B, int64_t k) {
+int64_t ws_bytes_of(int64_t B, int64_t k, bool point = false) {
     if (B < 1 || k < 1 || k > SV_MAX_K || B >= (1ll << 24)) return 0;
-    return rows_of(B, k, false) * (int64_t)sizeof(SpecRow);
+    return rows_of(B, k, point) * (int64_t)sizeof(SpecRow);
 }
 
-// both entry points: `con` NULL is obte_spec_verify_bf16 itself
-int spec_verify(const char* who, const obte_bf16* p, int64_t ld_p, const obte_bf16* q, int64_t ld_q, const int64_t* draft, int64_t B, int64_t k, int64_t V,
+// the three entry points: `con` NULL and `point` false is obte_spec_verify_bf16 itself; `point`: no q, the draft is draft[b, j] itself
+int spec_verify(const char* who, bool point, const obte_bf16* p, int64_t ld_p, const obte_bf16* q, int64_t ld_q, const int64_t* draft, int64_t B, int64_t k, int64_t V,
                 const float* u_accept, const float* u_draw, float temperature, int32_t top_k, float top_p, const SpConstraint* con, int64_t hold_token,
                 int32_t* n_accept, int64_t* token, void* ws, int64_t ws_bytes, obte_stream s) {
     static_assert(sizeof(SpecRow) == 32, "the workspace holds 32 bytes per logits row");
@@ -327,7 +347,7 @@ int spec_verify(const char* who, const obte_bf16* p, int64_t ld_p, const obte_bf
     OBTE_REQUIRE(temperature >= 0.f && isfinite(temperature), "%s: temperature must be finite and not negative", who);
     OBTE_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p must lie in (0, 1]", who);
     const bool greedy = !u_accept || !u_draw || temperature == 0.f || top_k == 1;
-    OBTE_REQUIRE(q || greedy, "%s: null pointer (q): only a greedy call goes without the draft's logits", who);
+    OBTE_REQUIRE(q || greedy || point, "%s: null pointer (q): only a greedy call goes without the draft's logits", who);
     OBTE_REQUIRE(ld_p % 8 == 0, "%s: ld_p must be a multiple of 8 (16-byte rows), got %lld", who, (long long)ld_p);
     OBTE_REQUIRE(ld_p >= V, "%s: ld_p %lld is smaller than V %lld", who, (long long)ld_p, (long long)V);
     OBTE_REQUIRE_ALIGNED(who, p, "p", 16);
@@ -342,8 +362,9 @@ int spec_verify(const char* who, const obte_bf16* p, int64_t ld_p, const obte_bf
     OBTE_REQUIRE_ALIGNED(who, n_accept, "n_accept", 4);
     OBTE_REQUIRE_ALIGNED(who, token, "token", 8);
     OBTE_REQUIRE_ALIGNED(who, ws, "ws", 8);
-    const int64_t need = ws_bytes_of(B, k);
-    OBTE_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes, %lld needed (obte_spec_verify_ws_bytes)", who, (long long)ws_bytes, (long long)need);
+    const int64_t need = ws_bytes_of(B, k, point);
+    OBTE_REQUIRE(ws_bytes >= need, "%s: workspace of %lld bytes, %lld needed (%s)", who, (long long)ws_bytes, (long long)need,
+                 point ? "obte_spec_verify_point_ws_bytes" : "obte_spec_verify_ws_bytes");
     SpecParams a;
     a.p = (const bf16*)p; a.q = (const bf16*)q; a.ld_p = ld_p; a.ld_q = ld_q; a.draft = draft; a.u_accept = u_accept; a.u_draw = u_draw;
     a.rows = (SpecRow*)ws; a.n_accept = n_accept; a.token = token;
@@ -356,9 +377,10 @@ int spec_verify(const char* who, const obte_bf16* p, int64_t ld_p, const obte_bf
         if (rc != OBTE_OK) return rc;
     }
     hipStream_t st = (hipStream_t)s;
-    const int prof = obte_prof_begin(st, 115, B, k, V);
-    if (con) spec_launch<true>(a, B, k, V, greedy, st);
-    else spec_launch<false>(a, B, k, V, greedy, st);
+    const int prof = obte_prof_begin(st, point ? 123 : 115, B, k, V);
+    if (point) spec_launch<false, true>(a, B, k, V, greedy, st);
+    else if (con) spec_launch<true, false>(a, B, k, V, greedy, st);
+    else spec_launch<false, false>(a, B, k, V, greedy, st);
     obte_prof_end(prof, st);
     OBTE_CHECK_LAUNCH(who);
     return OBTE_OK;
@@ -371,7 +393,7 @@ extern "C" int64_t obte_spec_verify_ws_bytes(int64_t B, int64_t k) { return ws_b
 extern "C" int obte_spec_verify_bf16(const obte_bf16* p, int64_t ld_p, const obte_bf16* q, int64_t ld_q, const int64_t* draft, int64_t B, int64_t k, int64_t V,
                                      const float* u_accept, const float* u_draw, float temperature, int32_t top_k, float top_p, int32_t* n_accept,
                                      int64_t* token, void* ws, int64_t ws_bytes, obte_stream s) {
-    return spec_verify("obte_spec_verify_bf16", p, ld_p, q, ld_q, draft, B, k, V, u_accept, u_draw, temperature, top_k, top_p, nullptr, -1, n_accept, token, ws,
+    return spec_verify("obte_spec_verify_bf16", false, p, ld_p, q, ld_q, draft, B, k, V, u_accept, u_draw, temperature, top_k, top_p, nullptr, -1, n_accept, token, ws,
                        ws_bytes, s);
 }
 
@@ -380,7 +402,15 @@ extern "C" int obte_spec_verify_constrained_bf16(const obte_bf16* p, int64_t ld_
                                                  const uint8_t* allowed, int64_t allowed_ld, int64_t hold_token, const int32_t* emitted, int32_t min_emitted,
                                                  int32_t* n_accept, int64_t* token, void* ws, int64_t ws_bytes, obte_stream s) {
     const SpConstraint con{allowed, allowed_ld, emitted, 0, min_emitted};
-    return spec_verify("obte_spec_verify_constrained_bf16", p, ld_p, q, ld_q, draft, B, k, V, u_accept, u_draw, temperature, top_k, top_p, &con, hold_token,
+    return spec_verify("obte_spec_verify_constrained_bf16", false, p, ld_p, q, ld_q, draft, B, k, V, u_accept, u_draw, temperature, top_k, top_p, &con, hold_token,
                        n_accept, token, ws, ws_bytes, s);
 }
 
+extern "C" int64_t obte_spec_verify_point_ws_bytes(int64_t B, int64_t k) { return ws_bytes_of(B, k, true); }
+
+extern "C" int obte_spec_verify_point_bf16(const obte_bf16* p, int64_t ld_p, const int64_t* draft, int64_t B, int64_t k, int64_t V, const float* u_accept,
+                                           const float* u_draw, float temperature, int32_t top_k, float top_p, int32_t* n_accept, int64_t* token, void* ws,
+                                           int64_t ws_bytes, obte_stream s) {
+    return spec_verify("obte_spec_verify_point_bf16", true, p, ld_p, nullptr, 0, draft, B, k, V, u_accept, u_draw, temperature, top_k, top_p, nullptr, -1, n_accept,
+                       token, ws, ws_bytes, s);
+}

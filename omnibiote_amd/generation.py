@@ -39,13 +39,13 @@ def _check_prompt(what, idx, shape="(B, T0)", min_rows=0):
     return idx.shape
 
 
-def _check_room(what, prompt, max_new_tokens, block_size, longest=False, drafted=0):
+def _check_room(what, prompt, max_new_tokens, block_size, longest=False, drafted=0, draft_model=True):
     """ValueError naming ``OmniBioTA.what`` unless ``prompt`` tokens (``longest``: of the longest row), ``max_new_tokens`` new ones and the
-    ``drafted`` a speculative round may write beyond them fit ``block_size`` (with a draft: the smaller of the two models')"""
+    ``drafted`` a speculative round may write beyond them fit ``block_size`` (with a draft model: the smaller of the two models')"""
     if max_new_tokens < 0 or prompt + max_new_tokens + drafted > block_size:
         raise ValueError(f"OmniBioTA.{what}: {prompt} prompt tokens{' (the longest row)' if longest else ''} + {max_new_tokens} new ones"
                          + (f" + k = {drafted} drafted" if drafted else "") + f" exceed block_size = {block_size}"
-                         + (" (the smaller of the two models')" if drafted else ""))
+                         + (" (the smaller of the two models')" if drafted and draft_model else ""))
 
 
 def _default_pad(pad_token, eos_token):

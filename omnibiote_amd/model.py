@@ -2046,6 +2046,146 @@ class OmniBioTA(nn.Module):
         gather = torch.tensor([w[:steps] + [width] * (steps - len(w)) for w in where], device=dev)
         return result(every.gather(1, gather), counts)
 
+    @torch.no_grad()
+    def lookup_and_verify(self, pending, cache, history, lengths, k, uniforms=None, temperature=1.0, top_k=None, top_p=None, ngram=(1, 4)):
+        """One round of speculative decoding without a draft model, everything but the step back: ``draft_and_verify`` with an n-gram
+        lookup in every row's own tokens as the draft.  ``pending`` (B,) int64 is every row's last emitted token, not in ``cache`` yet;
+        ``history`` (B, W) int64 and ``lengths`` (B,) int32, both on the device, hold every row's tokens so far, the pending one last:
+        ``history[b, :lengths[b]]``.  ``ops.lookup_draft`` proposes x_0 .. x_{k-1} — what followed the most recent longest earlier
+        occurrence of the row's last ``ngram`` = (g_min, g_max) tokens, or the last token repeated — at the cost of no model
+        evaluation; this model runs ``extend([pending, x_0 .. x_{k-1}], logits="all")``; ``ops.spec_verify_point`` decides, the draft
+        distribution of a position being the point mass on its token.  The cache then holds k + 1 new positions per row.  ``uniforms``:
+        None (greedy) or the round's ``(u_accept (B, k), u_draw (B,))`` float32 on the device.  Returns ``(x (B, k) int64, n_accept (B,)
+        int32, token (B,) int64, match_len (B,) int32)`` on the device; nothing waits for them.  The caller reads n_accept and steps the
+        cache back by ``k - n_accept[b]`` (``rewind_rows``): row b has emitted x_0 .. x_{a-1} and ``token``, its new pending token."""
+        what = "lookup_and_verify"
+        self._refuse_fp8(what, cache)
+        self._refuse_shared(what, cache)
+        _refuse_paged(what, cache)
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= L.SPEC_VERIFY_MAX_K:
+            raise ValueError(f"OmniBioTA.{what}: k must lie in [1, {L.SPEC_VERIFY_MAX_K}], got {k!r}")
+        ngram = ops._ngram(f"OmniBioTA.{what}", ngram)
+        greedy = uniforms is None or temperature == 0 or top_k == 1
+        u_accept, u_draw = (None, None) if greedy else uniforms
+        x, match_len = ops.lookup_draft(history, lengths, k, ngram, self.config.vocab_size)
+        p = self.extend(torch.cat([pending.unsqueeze(1), x], dim=1), cache, logits="all")
+        n_accept, token = ops.spec_verify_point(p, x, u_accept, u_draw, temperature, top_k, top_p)
+        return x, n_accept, token, match_len
+
+    @torch.no_grad()
+    def generate_lookup(self, idx, max_new_tokens, k=8, ngram=(1, 4), temperature=1.0, top_k=None, top_p=None, generator=None, eos_token=None,
+                        lengths=None, pad_token=None, return_stats=False):
+        """``generate_speculative`` without a draft model: every round (``lookup_and_verify``) drafts ``k`` tokens per row (1 <= k <= 31)
+        by an n-gram lookup in the row's own prompt and output — the tokens that followed the most recent longest earlier occurrence
+        of its last ``ngram`` = (g_min, g_max) tokens, 1 <= g_min <= g_max <= 16 — scores them in one ``extend`` and keeps a prefix of
+        them plus one token of its own, so that every emitted token is distributed as this model's own sampling under ``temperature``
+        / ``top_k`` / ``top_p`` would have it (the rule: ``sampling.verify_point_reference``; with ``top_k == 1`` or ``temperature == 0``
+        the output is this model's greedy stream up to the two paths' rounding).  The draft costs no model evaluation: sequences with
+        tandem repeats, repeated motifs or continuations that copy the prompt gain up to k + 1 tokens per round, others pay the
+        wider ``extend`` for one.
+
+        ``lengths``, ``eos_token``, ``pad_token``, the return forms and ``return_stats`` as in ``generate_speculative``; the stats gain
+        ``matched``, the running row-rounds whose lookup found a match.  The last round may write k positions it does not keep: longest
+        prompt + max_new_tokens + k must fit block_size.  The call owns a history buffer (B, longest + max_new_tokens + k + 1) int64 —
+        at most 8192 columns — and a device int32 length vector: a round's k + 1 emitted columns are written behind each row's length
+        on the device before the round's one host synchronisation, the lengths then advance by the tokens that count, and the next
+        round overwrites the rest.  All uniforms come from ``generator`` on the device, one ``torch.rand(B * (k + 1))`` per round and one
+        draw for the first token, so a seeded call is repeatable.
+
+        Not built: ``allowed_tokens`` / ``min_new_tokens`` and the penalties, ``kv_dtype="fp8"``, ``num_samples``, ``weights=``, paged caches,
+        the device-resident loop and graph capture."""
+        what = "generate_lookup"
+        _check_top_p(f"OmniBioTA.{what}", top_p)
+        self._check_generation(what, idx.shape[0] if idx.dim() == 2 else 0)
+        b, t0 = _check_prompt(what, idx)
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= L.SPEC_VERIFY_MAX_K:
+            raise ValueError(f"OmniBioTA.{what}: k must lie in [1, {L.SPEC_VERIFY_MAX_K}], got {k!r}")
+        ngram = ops._ngram(f"OmniBioTA.{what}", ngram)
+        if temperature < 0:
+            raise ValueError(f"OmniBioTA.{what}: temperature must not be negative, got {temperature}")
+        if top_k is not None and top_k < 1:
+            raise ValueError(f"OmniBioTA.{what}: top_k must be at least 1, got {top_k}")
+        lens = [t0] * b if lengths is None else _check_lengths(what, lengths, b, t0)
+        longest = max(lens)
+        _check_room(what, longest, max_new_tokens, self.config.block_size, longest=True, drafted=k, draft_model=False)
+        width = longest + max_new_tokens + k + 1
+        if width > L.LOOKUP_MAX_HISTORY:
+            raise ValueError(f"OmniBioTA.{what}: a history of {width} tokens per row (the longest prompt + max_new_tokens + k + 1) exceeds the "
+                             f"{L.LOOKUP_MAX_HISTORY} the lookup takes")
+        pad = _default_pad(pad_token, eos_token)
+        idx = idx[:, :longest]
+        dev = idx.device
+        stats = dict(rounds=0, drafted=0, accepted=0, matched=0)
+
+        def result(tokens, counts):
+            if lengths is None:
+                out = (torch.cat([idx, tokens], dim=1),)
+            else:
+                out = ragged_output(idx, lens, tokens, _live(torch.tensor(counts, device=dev), tokens.shape[1], dev), pad)
+            out = out + (stats,) if return_stats else out
+            return out[0] if len(out) == 1 else out
+
+        if max_new_tokens == 0:
+            return result(torch.zeros((b, 0), dtype=torch.int64, device=dev), [0] * b)
+        greedy = top_k == 1 or temperature == 0
+        cache = KVCache(self, b, longest + max_new_tokens + k)
+        logits = self.prefill(idx, cache, lengths=lens)
+        pending = ops.sample_logits(logits, None if greedy else torch.rand(b, device=dev, generator=generator), temperature, top_k, top_p)
+        # the device's account: every row's tokens so far, the pending one last
+        start = torch.tensor(lens, dtype=torch.int64, device=dev).unsqueeze(1)
+        hist = torch.zeros((b, width), dtype=torch.int64, device=dev)
+        hist[:, :longest] = idx
+        hist.scatter_(1, start, pending.unsqueeze(1))
+        hlen = (start.squeeze(1) + 1).to(torch.int32)
+        # the host's account: where the rows stand in the cache (-1: parked) and how many tokens each has emitted
+        at = list(lens)
+        counts = [1] * b
+        first = pending.tolist() if eos_token is not None else None
+        done = [max_new_tokens == 1 or (first is not None and first[r] == eos_token) for r in range(b)]
+        newly = list(done)
+        col = torch.arange(k + 1, device=dev).view(1, -1)
+        while not all(done):
+            if any(newly):                                              # park what the last round finished: it stores and reads nothing
+                cache.park(torch.tensor(newly, device=dev))
+                at = [-1 if d else p for p, d in zip(at, done)]
+            us = None
+            if not greedy:
+                r = torch.rand(b * (k + 1), device=dev, generator=generator)
+                us = r[:b * k].view(b, k), r[b * k:]
+            x, n_accept, token, match_len = self.lookup_and_verify(pending, cache, hist, hlen, k, us, temperature, top_k, top_p, ngram)
+            a_dev = n_accept.long().unsqueeze(1)
+            emitted = torch.cat([x, token.unsqueeze(1)], dim=1).scatter(1, a_dev, token.unsqueeze(1))   # x_0 .. x_{a-1}, token, (stale)
+            hist.scatter_(1, hlen.long().unsqueeze(1) + col, emitted)   # behind the row's length: at most column width - 2
+            if eos_token is None:
+                eos_at = torch.full((b,), k + 1, device=dev)
+            else:
+                hit = (emitted == eos_token) & (col <= a_dev)
+                eos_at = torch.where(hit.any(dim=1), hit.to(torch.uint8).argmax(dim=1), torch.full((b,), k + 1, device=dev))
+            read = torch.stack([a_dev.squeeze(1), eos_at, match_len.long()], dim=1).tolist()   # the round's host synchronisation
+            stats["rounds"] += 1
+            back, now, newly, grow = [0] * b, [p + k + 1 if p >= 0 else -1 for p in at], [False] * b, [0] * b
+            for r in range(b):
+                if done[r]:
+                    continue
+                a, e, m = read[r]
+                n = min(a + 1, e + 1, max_new_tokens - counts[r])       # tokens of this round that count
+                stats["drafted"] += k
+                stats["accepted"] += a
+                stats["matched"] += m > 0
+                counts[r] += n
+                grow[r] = n
+                back[r] = k + 1 - n                                     # the pending token and the first n - 1 of this round's stay
+                newly[r] = done[r] = counts[r] >= max_new_tokens or e < n
+            cache.rewind_rows(back, now)
+            at = [p - n if p >= 0 else -1 for p, n in zip(now, back)]
+            hlen += torch.tensor(grow, dtype=torch.int32, device=dev)
+            pending = token
+        steps = max_new_tokens if lengths is None else max(counts)
+        fill = eos_token if lengths is None and eos_token is not None else pad
+        tokens = hist.gather(1, start + torch.arange(steps, device=dev).view(1, -1))    # row b's counts[b] tokens lie behind its prompt
+        tokens = torch.where(_live(torch.tensor(counts, device=dev), steps, dev), tokens, torch.full((), int(fill), dtype=torch.int64, device=dev))
+        return result(tokens, counts)
+
 
 def next_token_loss(logits, idx):
     """Mean cross entropy of position t's logits against token t + 1 over every row's first T - 1 positions — the loss of an

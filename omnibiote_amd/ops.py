@@ -567,6 +567,80 @@ def spec_verify(p, q, draft, u_accept=None, u_draw=None, temperature=1.0, top_k=
     return n_accept, token
 
 
+def _ngram(what, ngram):
+    """``ngram`` as (g_min, g_max), 1 <= g_min <= g_max <= 16, or a ValueError in ``what``'s name"""
+    ok = isinstance(ngram, (tuple, list)) and len(ngram) == 2 and all(isinstance(g, int) and not isinstance(g, bool) for g in ngram)
+    if not ok or not 1 <= ngram[0] <= ngram[1] <= L.LOOKUP_MAX_NGRAM:
+        raise ValueError(f"{what}: ngram must be (g_min, g_max) integers with 1 <= g_min <= g_max <= {L.LOOKUP_MAX_NGRAM}, got {ngram!r}")
+    return int(ngram[0]), int(ngram[1])
+
+
+def lookup_draft(hist, lens, k, ngram=(1, 4), vocab=65536):
+    """k drafted tokens per row from the row's own history, in one launch (obte_lookup_draft; the rule: include/omnibiote_hip_lookup.h,
+    restated in a plain loop by sampling.lookup_reference).  ``hist`` (B, W) int64, W <= 8192, rows at least W apart with stride 1
+    along a row; ``lens`` (B,) int32: row b's tokens are hist[b, :lens[b]].  The longest suffix of them of ``ngram`` = (g_min, g_max)
+    tokens that occurs earlier in the row — the most recent occurrence among equals — is followed by the draft, continued periodically
+    past the end of the history; without a match every drafted token repeats the last one.  Tokens outside [0, ``vocab``) match nothing;
+    a row with lens outside [1, W] gets zeros.  1 <= k <= 31.  Returns ``(draft (B, k) int64, match_len (B,) int32)``."""
+    _need(hist, "hist", torch.int64, contiguous=False); _need(lens, "lens", torch.int32)
+    if hist.dim() != 2 or hist.shape[0] < 1 or hist.shape[1] < 1:
+        raise ValueError(f"lookup_draft: hist must be (B, W) with B, W >= 1, got {tuple(hist.shape)}")
+    B, W = hist.shape
+    if W > L.LOOKUP_MAX_HISTORY:
+        raise ValueError(f"lookup_draft: a history of {W} tokens per row exceeds the {L.LOOKUP_MAX_HISTORY} the kernel takes")
+    if hist.stride(1) != 1 and W > 1:
+        raise ValueError("lookup_draft: hist must have stride 1 along a row")
+    if B > 1 and hist.stride(0) != W:
+        raise ValueError(f"lookup_draft: the rows of hist must lie their width {W} apart, got a stride of {hist.stride(0)}")
+    if lens.shape != (B,):
+        raise ValueError(f"lookup_draft: lens must be ({B},), got {tuple(lens.shape)}")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= L.SPEC_VERIFY_MAX_K:
+        raise ValueError(f"lookup_draft: k must lie in [1, {L.SPEC_VERIFY_MAX_K}], got {k!r}")
+    g_min, g_max = _ngram("lookup_draft", ngram)
+    if isinstance(vocab, bool) or not isinstance(vocab, int) or not 1 <= vocab <= 65536:
+        raise ValueError(f"lookup_draft: vocab must lie in [1, 65536], got {vocab!r}")
+    draft = torch.empty((B, k), dtype=torch.int64, device=hist.device)
+    match_len = torch.empty(B, dtype=torch.int32, device=hist.device)
+    L.check(L.lib().obte_lookup_draft(_ptr(hist), W, _ptr(lens), B, k, g_min, g_max, vocab, _ptr(draft), _ptr(match_len), _stream()), "obte_lookup_draft")
+    return draft, match_len
+
+
+def spec_verify_point(p, draft, u_accept=None, u_draw=None, temperature=1.0, top_k=None, top_p=None):
+    """``spec_verify`` for drafted tokens that come without a distribution (obte_spec_verify_point_bf16; the rule:
+    include/omnibiote_hip_lookup.h, in plain torch sampling.verify_point_reference): bit for bit ``spec_verify`` with the q that is 0 at
+    ``draft[b, j]`` and -inf everywhere else, which is never built — x_j stands while ``u_accept[b, j] < P_j(x_j)``, and behind a
+    rejection the token is drawn from P_a with x_a's weight removed.  ``p``, ``draft``, the uniforms and the returned ``(n_accept (B,) int32,
+    token (B,) int64)`` as in ``spec_verify``; without uniforms, with ``temperature == 0`` or ``top_k == 1`` the call is greedy."""
+    _need(p, "p", contiguous=False)
+    if p.dim() != 3 or p.shape[0] < 1 or p.shape[1] < 2 or p.shape[2] < 1:
+        raise ValueError(f"spec_verify_point: p must be (B, k + 1, V) with B, k, V >= 1, got {tuple(p.shape)}")
+    B, k, V = p.shape[0], p.shape[1] - 1, p.shape[2]
+    if p.stride(2) != 1 and V > 1:
+        raise RuntimeError("spec_verify_point: p must have stride 1 along the vocabulary")
+    ld_p = p.stride(1)
+    if B > 1 and p.stride(0) != (k + 1) * ld_p:
+        raise RuntimeError(f"spec_verify_point: the rows of p must be evenly spaced (stride(0) == {k + 1} * stride(1))")
+    _need(draft, "draft", torch.int64)
+    if draft.shape != (B, k):
+        raise ValueError(f"spec_verify_point: draft must be ({B}, {k}), got {tuple(draft.shape)}")
+    if (u_accept is None) != (u_draw is None):
+        raise ValueError("spec_verify_point: u_accept and u_draw come together (both None: greedy)")
+    if u_accept is not None:
+        _need(u_accept, "u_accept", torch.float32); _need(u_draw, "u_draw", torch.float32)
+        if u_accept.shape != (B, k) or u_draw.shape != (B,):
+            raise ValueError(f"spec_verify_point: u_accept must be ({B}, {k}) and u_draw ({B},), got {tuple(u_accept.shape)} and {tuple(u_draw.shape)}")
+    if top_k is not None and top_k < 1:
+        raise ValueError(f"spec_verify_point: top_k must be at least 1, got {top_k}")
+    n_accept = torch.empty(B, dtype=torch.int32, device=p.device)
+    token = torch.empty(B, dtype=torch.int64, device=p.device)
+    ws_bytes = max(int(L.lib().obte_spec_verify_point_ws_bytes(B, min(k, L.SPEC_VERIFY_MAX_K))), 8)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
+    L.check(L.lib().obte_spec_verify_point_bf16(_ptr(p), ld_p, _ptr(draft), B, k, V, _ptr(u_accept), _ptr(u_draw), float(temperature),
+                                                0 if top_k is None else min(int(top_k), 2 ** 31 - 1), 1.0 if top_p is None else float(top_p),
+                                                _ptr(n_accept), _ptr(token), _ptr(ws), ws_bytes, _stream()), "obte_spec_verify_point_bf16")
+    return n_accept, token
+
+
 def dropout(x, p, seed, site=L.SITE_USER, out=None):
     """out = dropout(x) with the library's counter-based mask: x is read as a matrix [numel / last dim, last dim] and
     element (row, col) decides (include/omnibiote_hip.h, dropout); x may alias out."""

@@ -175,6 +175,52 @@ def verify_reference(p, q, draft, u_accept=None, u_draw=None, temperature=1.0, t
     return tuple(t[0] for t in out) if one else out
 
 
+def verify_point_reference(p, draft, u_accept=None, u_draw=None, temperature=1.0, top_k=None, top_p=None):
+    """``verify_reference`` for a draft that is a token and not a distribution (obte_spec_verify_point_bf16,
+    include/omnibiote_hip_lookup.h): by definition ``verify_reference`` on the q whose row (b, j) is 0 at draft[b, j] and -inf everywhere
+    else — all -inf for a drafted token outside [0, V).  x_j stands while u_accept[j] < P_j(x_j); behind a rejection at a the token is
+    drawn from P_a with x_a's weight removed; behind k acceptances it is the draw on p[k].  ``p`` (B, k + 1, V) or (k + 1, V), ``draft``
+    (B, k) or (k,); returns what ``verify_reference`` returns."""
+    x = torch.as_tensor(draft, device=p.device).to(torch.int64)
+    v = p.shape[-1]
+    q = torch.full(tuple(x.shape) + (v,), float("-inf"), dtype=p.dtype, device=p.device)
+    inside = (x >= 0) & (x < v)
+    q.scatter_(-1, x.clamp(0, v - 1).unsqueeze(-1), torch.where(inside, 0.0, float("-inf")).to(p.dtype).unsqueeze(-1))
+    return verify_reference(p, q, x, u_accept, u_draw, temperature, top_k, top_p)
+
+
+def lookup_reference(hist, lens, k, g_min, g_max, V):
+    """The n-gram lookup draft in a plain loop (obte_lookup_draft, include/omnibiote_hip_lookup.h), written to be read: ``hist`` (B, W)
+    integers, ``lens`` (B,) integers.  Row b is active iff 1 <= n = lens[b] <= W.  A token outside [0, V) equals nothing, not even itself.
+    For a candidate end e in [1, n - 1], m(e) is the number of tokens before e — at most min(g_max, e) — that agree with the row's last
+    tokens, walking backwards; e* has the largest m(e), among equals the largest e.  m(e*) >= g_min: match_len = m(e*) and
+    draft[j] = hist[e* + (j mod (n - e*))], the history continued periodically past its end.  Otherwise match_len = 0 and every
+    draft[j] = hist[n - 1].  An inactive row gives zeros.  Returns (draft int64 (B, k), match_len int32 (B,)) on the CPU."""
+    rows = torch.as_tensor(hist).cpu().to(torch.int64).tolist()
+    ns = torch.as_tensor(lens).cpu().to(torch.int64).tolist()
+    draft, match = [], []
+    for h, n in zip(rows, ns):
+        if not 1 <= n <= len(h):
+            draft.append([0] * k)
+            match.append(0)
+            continue
+
+        def same(i, j):
+            return 0 <= h[i] < V and h[i] == h[j]
+
+        best_m, best_e = 0, n - 1
+        for e in range(1, n):
+            m = 0
+            while m < min(g_max, e) and same(e - 1 - m, n - 1 - m):
+                m += 1
+            if m >= max(best_m, g_min):                                                  # (e rises: an equal m later on is more recent)
+                best_m, best_e = m, e
+        d = n - best_e
+        draft.append([h[best_e + j % d] for j in range(k)])
+        match.append(best_m)
+    return torch.tensor(draft, dtype=torch.int64).view(len(rows), k), torch.tensor(match, dtype=torch.int32)
+
+
 def pack_token_mask(mask):
     """bool (..., V) -> uint8 (..., ceil(V / 8)): column i is bit i & 7 of byte i >> 3, the padding bits of the last byte clear (the
     ``allowed`` argument of include/omnibiote_hip_constrain.h).  Plain torch on any device."""
